@@ -18,6 +18,9 @@ with `--mode count` configs[4] (COUNT(*) + all-reduce).
 The table exists TWICE in HBM and consecutive steps alternate between the copies: a step's 300 MB would
 otherwise find part of itself in the 256 MiB Infinity Cache left by the step before, and the HBM roofline
 would be flattered.  Prints ONE JSON line on rank 0.
+
+`--dump-outputs DIR` also writes the answer of the last timed step as .npy files; the table is seeded, so two builds run
+with the same arguments can be compared answer for answer.
 """
 import argparse
 import ctypes as C
@@ -27,12 +30,6 @@ import os
 import pathlib
 import sys
 import time
-
-# The query stream keeps two queries in flight on two HIP streams; they only overlap if the runtime gives the two
-# streams different hardware queues.  ROCm's default pool is 4 queues shared by every stream of the process (torch's
-# included), assigned in an order the host cannot see; with 8 the two lanes never collide.  Has to be in the
-# environment before the HIP runtime starts (i.e. before torch is imported).
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 ROOT = pathlib.Path(__file__).resolve().parent
 PKG = ROOT / "parallel-query-processing-system_amd"
@@ -162,6 +159,43 @@ def numpy_checksum(ids):
     return s0, s1
 
 
+DUMP_MAX_IDS = 1 << 21         # --dump-outputs: at most 2 M IDs + their positions as float64 (32 MB)
+
+
+def ticket_answer(pq, ctx, ticket, count_only):
+    """(count, uint32 row IDs on the host or None) of an engine ticket; the ticket is released."""
+    import numpy as np
+    res = pq.DeviceResult()
+    try:
+        k = pq.lib().awaitQueryHIP(ticket, C.byref(res))
+        if k < 0:
+            raise pq.PqpsError("the last timed query failed")
+        if count_only:
+            return k, None
+        ids = np.empty(k, dtype=np.uint32)
+        if k:
+            ctx.download(ids.ctypes.data, res.ids_dev, 4 * k)
+        return k, ids
+    finally:
+        pq.lib().releaseQueryHIP(ticket)
+
+
+def dump_outputs(path, count, ids):
+    """count.npy, ids.npy (+ ids_pos.npy when the list is sampled): float64, exact for u32 row IDs.  A list longer than
+    DUMP_MAX_IDS is sampled at positions drawn from a fixed seed, so two runs of the same arguments sample alike."""
+    import numpy as np
+    path = pathlib.Path(path)
+    path.mkdir(parents=True, exist_ok=True)
+    np.save(path / "count.npy", np.array([count], dtype=np.float64))
+    if ids is None:
+        return
+    if len(ids) > DUMP_MAX_IDS:
+        pos = np.unique(np.random.default_rng(0x5EED).integers(0, len(ids), DUMP_MAX_IDS))
+        np.save(path / "ids_pos.npy", pos.astype(np.float64))
+        ids = ids[pos]
+    np.save(path / "ids.npy", ids.astype(np.float64))
+
+
 def gathered_checksum(parts):
     """Checksum of the concatenation of lists whose own (count, s0, s1) are `parts`, in order: entry i of a part lands at
     displacement + i, so its s1 grows by 2 * displacement * s0."""
@@ -208,6 +242,10 @@ def main():
     ap.add_argument("--engine-in-flight", type=int, default=3, help="tickets each thread keeps outstanding in the engine-level leg")
     ap.add_argument("--force-merge", action="store_true",
                     help="N=1 rehearsal: run the N>1 exchange (RCCL communicator of one rank: sizes, payload, merge) at both levels")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the answer of the last timed step of the level `value` comes from as DIR/*.npy (rank 0): "
+                         "count.npy, and for ID queries ids.npy (float64 row IDs; beyond %d IDs a seeded sample, its positions "
+                         "in ids_pos.npy)" % DUMP_MAX_IDS)
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -335,6 +373,8 @@ def main():
     torch.cuda.empty_cache()
 
     result_notes = []
+    last_answer = {}                                                # level -> (count, ids) of its last timed step (--dump-outputs)
+    dump = args.dump_outputs is not None and rank == 0
 
     # ==== engine level: the reference-facing API, a C loop issuing tickets =====================================================
     def engine_level():
@@ -410,9 +450,15 @@ def main():
             for r in range(max(1, args.reps)):
                 res = pq.BenchResult()
                 res.want_checksum = 0 if count_mode else 1
+                res.keep_last = 1 if dump and r == max(1, args.reps) - 1 else 0
                 rank_fence()
                 rc = B.hipEngineBench(arr, copies, wl.ptr, 1 if count_mode else 0, args.engine_threads, args.engine_in_flight,
                                       args.warmup if r == 0 else 2, args.steps, C.byref(res))
+                if res.last_ticket:
+                    try:
+                        last_answer["engine"] = ticket_answer(pq, ctx, res.last_ticket, count_mode)
+                    except pq.PqpsError as ex:                       # (reported at the end: the ranks go on in step)
+                        log(f"reading the last timed answer: {ex}")
                 rank_fence()
                 good = rc == 0 and res.mismatches == 0 and res.matches == total_matches and \
                     (count_mode or (res.have_checksum and (int(res.checksum[0]), int(res.checksum[1])) == (want_s0, want_s1)))
@@ -616,6 +662,24 @@ def main():
                     return False, "the query stream's list differs from the single scan's"
             return True, ""
 
+        def slot_answer(slot):
+            """(count, uint32 row IDs on the host or None) that ring slot `slot` holds: what a caller of this level receives."""
+            if count_mode:
+                if st["native"]:
+                    return st["xch"].count_result(slot)[0], None
+                torch.cuda.synchronize()
+                return int((st["count_all"][slot] if exchange else st["count_out"][2 * slot]).item()), None
+            if st["native"]:
+                merged = st["xch"].result(slot)[0]
+            elif exchange:
+                merged = st["mergers"][slot].result()
+            else:
+                m = st["mergers"][slot]
+                merged = np.empty(m.local_count(), dtype=np.uint32)
+                if len(merged):
+                    ctx.download(merged.ctypes.data, m.ids_ptr, 4 * len(merged), sptr)
+            return len(merged), merged
+
         # ---- warm-up, then verification BEFORE anything is timed (a wrong answer ends the run with rc != 0 on every rank)
         n_warm = max(args.warmup, RING if exchange else 1)
         ok, _, _ = phase(n_warm)
@@ -660,6 +724,8 @@ def main():
         good, why = verify_slot((args.steps - 1) % RING)
         if not agree(good):
             sys.exit("bench: the timed steps left a wrong answer: " + (why or "on another rank"))
+        if dump and eng is None:                                   # (this level is the one `value` comes from)
+            last_answer["shim"] = slot_answer((args.steps - 1) % RING)
         waited = 0.0
         in_stream_ms = None
         wire = eager = None
@@ -850,6 +916,11 @@ def main():
     if exchange:
         dist.barrier()
         dist.destroy_process_group()
+    if dump:
+        if level not in last_answer:
+            sys.exit(f"bench: --dump-outputs: the {level} level's last timed answer could not be read")
+        dump_outputs(args.dump_outputs, *last_answer[level])
+        log(f"--dump-outputs: the {level} level's last timed answer ({last_answer[level][0]:,} rows) in {args.dump_outputs}")
     sys.stdout.flush()
     os.dup2(real_stdout, 1)
     if rank == 0:

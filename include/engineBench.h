@@ -22,6 +22,9 @@ struct hipBenchResult {
                                        after the clock has stopped                                                          */
     int have_checksum;              /* OUT                                                                                  */
     unsigned long long checksum[2]; /* OUT: sum of the row numbers, sum of id[i] * (2 i + 1), mod 2^64                      */
+    int keep_last;                  /* IN: hand thread 0's last timed ticket back instead of releasing it                   */
+    struct hipQueryTicket *last_ticket; /* OUT (keep_last): that ticket, already awaited; the caller reads its answer
+                                       (awaitQueryHIP) and releases it.  NULL when the run failed                           */
 };
 
 /* `queries` queries per thread after `warmup` untimed ones, each thread keeping `in_flight` tickets outstanding

@@ -112,7 +112,8 @@ class BenchResult(C.Structure):
     """struct hipBenchResult (include/engineBench.h)."""
     _fields_ = [("seconds", C.c_double), ("queries", C.c_longlong), ("matches", C.c_longlong), ("mismatches", C.c_longlong),
                 ("issue_seconds", C.c_double), ("await_seconds", C.c_double),
-                ("want_checksum", C.c_int), ("have_checksum", C.c_int), ("checksum", C.c_ulonglong * 2)]
+                ("want_checksum", C.c_int), ("have_checksum", C.c_int), ("checksum", C.c_ulonglong * 2),
+                ("keep_last", C.c_int), ("last_ticket", C.c_void_p)]
 
 
 class EngineS(C.Structure):

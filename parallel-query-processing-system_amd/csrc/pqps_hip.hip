@@ -1014,12 +1014,6 @@ int run_filter(pqps_ctx *ctx, eval_fn k1, EvalArgs &a, uint64_t rows, int mode, 
 
 }  // namespace
 
-// Two queries in flight (pqps_qstream, pqps_exchange) need their two HIP streams on different hardware queues.
-// The runtime's pool is 4 queues for all streams of the process by default; ask for 8 unless the host has
-// chosen a number.  Only effective if this library is loaded before the HIP runtime initialises -- a host that
-// starts HIP first (torch) sets GPU_MAX_HW_QUEUES itself (bench.py does).
-__attribute__((constructor)) static void pqps_default_hw_queues() { setenv("GPU_MAX_HW_QUEUES", "8", 0); }
-
 extern "C" {
 
 const char *pqps_last_error(void) { return g_err; }

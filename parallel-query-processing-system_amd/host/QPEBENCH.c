@@ -85,7 +85,7 @@ int main(int argc, char *argv[]) {
         }
         hipEngineKernelTiming(engines[c], 1);
     }
-    struct hipBenchResult r;
+    struct hipBenchResult r = {0};
     /* a fresh process starts with the GPU's clocks down: a few hundred untimed queries (tens of milliseconds) first */
     const int rc = hipEngineBench(engines, copies, where, count_only, threads, in_flight, 400 / threads + 20, queries, &r);
     double scan_ms = 0.0, query_ms = 0.0;

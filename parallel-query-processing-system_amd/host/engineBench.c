@@ -19,7 +19,8 @@ struct bench_thread {
     struct engineS **engines;
     int n_engines;
     struct whereClauseS *where;
-    int count_only, in_flight, warmup, queries, id, checksum;
+    int count_only, in_flight, warmup, queries, id, checksum, keep_last;
+    struct hipQueryTicket *kept;         /* keep_last: the last timed ticket, not released */
     pthread_barrier_t *start, *timed;
     volatile int *abort_all;             /* a thread that cannot go on tells the others; everybody still reaches the barriers */
     double t_first, t_last, issue_s, await_s;
@@ -47,8 +48,9 @@ static void drain(struct bench_thread *b, struct hipQueryTicket **ring, const in
                 b->t_last = wall();
                 b->have_sums = hipQueryChecksumHIP(tk, b->sums) == 0;
             }
+            if (last_of_run && *held == 1 && b->keep_last) b->kept = tk;
         }
-        releaseQueryHIP(tk);
+        if (tk != b->kept) releaseQueryHIP(tk);
         *head = (*head + 1) % depth;
         (*held)--;
     }
@@ -99,7 +101,7 @@ static void *bench_main(void *arg) {
 int hipEngineBench(struct engineS **engines, int n_engines, struct whereClauseS *whereClause, int count_only,
                    int threads, int in_flight, int warmup, int queries, struct hipBenchResult *out) {
     if (!engines || n_engines < 1 || n_engines > 64 || !out || threads < 1 || threads > 64 || queries < 1 || warmup < 0) return -1;
-    const int want_checksum = out->want_checksum;
+    const int want_checksum = out->want_checksum, keep_last = out->keep_last;
     memset(out, 0, sizeof *out);
     /* Tickets keep their lane until they are released: `threads` threads with `in_flight` outstanding tickets spread over
      * n_engines engines hold up to threads * ceil(in_flight / n_engines) lanes of one engine.  More than it has would leave
@@ -125,6 +127,7 @@ int hipEngineBench(struct engineS **engines, int n_engines, struct whereClauseS 
     for (int i = 0; i < threads; i++) {
         bt[i] = (struct bench_thread){ .engines = engines, .n_engines = n_engines, .where = whereClause, .count_only = count_only,
                                        .in_flight = depth, .warmup = warmup, .queries = queries, .id = i, .checksum = want_checksum && i == 0,
+                                       .keep_last = keep_last && i == 0,
                                        .start = &start, .timed = &timed, .abort_all = &abort_all };
         if (i > 0 && pthread_create(&tid[i], NULL, bench_main, &bt[i]) != 0) { fprintf(stderr, "hipEngineBench: cannot start thread %d\n", i); exit(EXIT_FAILURE); }
     }
@@ -146,6 +149,11 @@ int hipEngineBench(struct engineS **engines, int n_engines, struct whereClauseS 
     out->have_checksum = bt[0].have_sums;
     out->checksum[0] = bt[0].sums[0];
     out->checksum[1] = bt[0].sums[1];
+    if (failed && bt[0].kept) {
+        releaseQueryHIP(bt[0].kept);
+        bt[0].kept = NULL;
+    }
+    out->last_ticket = bt[0].kept;
     pthread_barrier_destroy(&start);
     pthread_barrier_destroy(&timed);
     free(bt); free(tid);

@@ -13,9 +13,11 @@ Outputs (all data: inputs + what the reference answered):
   select_golden.json     SELECT cases: where-list as parsed by the reference,
                          result row numbers, sha256 of every projected cell
   parse_golden.json      SQL text -> reference token stream / ParsedSQL / where list
+  parse_wide_golden.json  the same for SQL past the parser's five conditions per level
   records_golden.json    CSV -> the 1040-byte records the reference loaded
   index_order_golden.json  leaf order of the reference's B+ trees
   print_golden.json      printTable() text for a few queries
+  reference_layout.txt   sizes / field offsets / enum values of the reference's headers
 Cases whose index candidates exceed num_records are never sent to the
 reference (it overflows its buffer, executeEngine-serial.c:342,447); they are
 recorded with "pinned": false and the oracle's answer.
@@ -34,6 +36,7 @@ sys.path.insert(0, str(HERE.parent))
 import qpelib as q  # noqa: E402
 
 REF_GEN = pathlib.Path("/root/reference/data-generation/generate_commands.py")
+REF_INCLUDE = pathlib.Path("/root/reference/include")
 HEADER = ("command_id,raw_command,base_command,shell_type,exit_code,timestamp,sudo_used,"
           "working_directory,user_id,user_name,host_name,risk_level")
 
@@ -152,6 +155,16 @@ PARSE_CASES = [
     "SELECT * FROM c WHERE a = @ 5",
     "SELECT * FROM c WHERE _x9 = 5 AND y_ = 'z'",
 ]
+# more than five conditions per level, ten select items, DELETE with a sub-chain: parse_wide_golden.json
+PARSE_CASES_WIDE = [
+    "SELECT * FROM c WHERE a=1 AND b=2 AND c=3 AND d=4 AND e=5 AND f=6",
+    "SELECT * FROM c WHERE a=1 OR b=2 OR c=3 OR d=4 OR e=5 OR f=6 OR g=7",
+    "SELECT * FROM c WHERE a=1 AND b=2 AND c=3 AND d=4 AND e=5",
+    "SELECT * FROM c WHERE (a=1 AND b=2 AND c=3 AND d=4 AND e=5 AND f=6) OR g=7",
+    "SELECT a,b,c,d,e,f,g,h,i,j FROM c WHERE x='1'",
+    "DELETE FROM c WHERE (a = 1 OR b = 2) AND c = 3",
+    "SELECT * FROM c WHERE a != 'x' AND b >= \"y z\" OR (c < 3 AND d <= 4)",
+]
 
 
 def make_edge_csv(path):
@@ -250,14 +263,8 @@ def main():
     edge = HERE / "edge_cases.csv"
     make_edge_csv(edge)
 
-    # ---- parse golden -------------------------------------------------
-    parse_out = []
-    all_sql = list(PARSE_CASES) + [compose(s, w) for _, s, w in SELECT_CASES]
-    for sql in all_sql:
-        toks = q.call_text(ref.refh_tokens, sql.encode("latin-1"))
-        parsed = q.call_text(ref.refh_parse, sql.encode("latin-1"))
-        parse_out.append({"sql": sql, "tokens": toks, "parse": parsed})
-    (HERE / "parse_golden.json").write_text(json.dumps(parse_out, indent=0))
+    n_parse = parse_goldens(ref)
+    layout_golden()
 
     # ---- records golden -----------------------------------------------
     rec_out = {}
@@ -337,7 +344,32 @@ def main():
 
     unpinned = [c["name"] + "/" + c["indexes"] for c in sel_out if not c["pinned"]]
     print(f"select cases: {len(sel_out)} ({len(unpinned)} not sent to the reference: {unpinned})")
-    print(f"parse cases: {len(parse_out)}")
+    print(f"parse cases: {n_parse}")
+
+
+def parse_goldens(ref):
+    """parse_golden.json, parse_wide_golden.json: SQL text -> the reference's token stream and parse."""
+    n = 0
+    for name, all_sql in (("parse_golden.json", list(PARSE_CASES) + [compose(s, w) for _, s, w in SELECT_CASES]),
+                          ("parse_wide_golden.json", PARSE_CASES_WIDE)):
+        parse_out = []
+        for sql in all_sql:
+            toks = q.call_text(ref.refh_tokens, sql.encode("latin-1"))
+            parsed = q.call_text(ref.refh_parse, sql.encode("latin-1"))
+            parse_out.append({"sql": sql, "tokens": toks, "parse": parsed})
+        (HERE / name).write_text(json.dumps(parse_out, indent=0))
+        n += len(parse_out)
+    return n
+
+
+def layout_golden():
+    """reference_layout.txt: tests/test_abi_layout.py's probe of sizes, field offsets and widths, enum values and macros,
+    compiled against the reference's own include/ (the numbers only; no header is copied)."""
+    sys.path.insert(0, str(HERE.parent))
+    import test_abi_layout
+    with tempfile.TemporaryDirectory() as td:
+        text = test_abi_layout._run_probe(pathlib.Path(td), "reference", [REF_INCLUDE])
+    (HERE / "reference_layout.txt").write_text(text)
 
 
 def random_where_cases(csv2k, n_cases, seed):
@@ -686,5 +718,9 @@ if __name__ == "__main__":
         boolprobe_goldens(HERE / "commands_2k.csv")
     elif "--random-only" in sys.argv:
         random_goldens(HERE / "commands_2k.csv")
+    elif "--parse-only" in sys.argv:
+        parse_goldens(q.load_ref())
+    elif "--layout-only" in sys.argv:
+        layout_golden()
     else:
         main()

@@ -1,12 +1,11 @@
 """The drop-in boundary without a GPU: struct layouts equal the reference's
-(sizes measured from /root/reference/include with gcc),
-and libpqps_hip.so exports every function include/*.h declares."""
+(sizes measured from the reference's include/ with gcc, SURVEY.md section 8b, and
+stored in tests/golden/reference_layout.txt), and libpqps_hip.so exports every
+function include/*.h declares."""
 import ctypes as C
 import pathlib
 import re
 import subprocess
-
-import pytest
 
 import qpelib as q
 
@@ -48,10 +47,6 @@ def test_struct_layouts_match_reference(tmp_path):
     assert pred_size == C.sizeof(q.pq.Predicate) and leaf_size == C.sizeof(q.pq.Leaf)
 
 
-REFERENCE_INCLUDE = pathlib.Path("/root/reference/include")
-# what only this repository has: the HIP engine's own headers (everything else of include/ restates a reference header)
-HIP_ONLY_HEADERS = ["executeEngine-hip.h", "buildEngine-hip.h", "hipPredicate.h", "pqps_hip.h"]
-
 SHARED_PROBE = r"""
 #include <stdio.h>
 #include <stddef.h>
@@ -92,31 +87,14 @@ def _run_probe(tmp_path, name, include_dirs):
     return subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
 
 
-@pytest.mark.skipif(not REFERENCE_INCLUDE.exists(), reason="the reference tree exists in the authoring container only")
 def test_struct_layouts_equal_the_reference_headers_themselves(tmp_path):
-    """The same probe compiled against /root/reference/include and against include/: every size, every field offset
-    and width of the contract structs, the enum values and the two macros the bridge uses."""
+    """The probe compiled against include/ prints what it printed compiled against the reference's own include/
+    (tests/golden/reference_layout.txt, make_golden.py --layout-only): every size, every field offset and width of the
+    contract structs, the enum values and the two macros the bridge uses."""
     ours = _run_probe(tmp_path, "ours", [q.ROOT / "include"])
-    theirs = _run_probe(tmp_path, "theirs", [REFERENCE_INCLUDE])
+    theirs = (q.GOLDEN / "reference_layout.txt").read_text()
     assert ours == theirs
     assert ours.splitlines()[0].split()[1:] == "1040 72 48 56 16 40 6336 260 336 24".split()
-
-
-@pytest.mark.skipif(not REFERENCE_INCLUDE.exists(), reason="the reference tree exists in the authoring container only")
-def test_engine_sources_compile_against_the_reference_headers(tmp_path):
-    """engine/hip/*.c drop into the reference's tree -- they compile against the REFERENCE's own
-    headers (executeEngine-serial.h, bplus.h, recordSchema.h, logType.h, sql.h ...) plus the four headers only this
-    repository has.  -Werror: a prototype that drifted from the reference's would be a conflicting declaration."""
-    hip_only = tmp_path / "hip_only"
-    hip_only.mkdir()
-    for h in HIP_ONLY_HEADERS:
-        (hip_only / h).write_text((q.ROOT / "include" / h).read_text())
-    sources = sorted((q.PKG / "engine" / "hip").glob("*.c"))
-    assert len(sources) >= 3
-    for src in sources:
-        p = subprocess.run(["gcc", "-std=c11", "-fsyntax-only", "-Wall", "-Werror", "-Wno-stringop-truncation", f"-I{REFERENCE_INCLUDE}", f"-I{hip_only}", str(src)],
-                           capture_output=True, text=True)
-        assert p.returncode == 0, (src.name, p.stderr[-2000:])
 
 
 def _declared_functions(header):
