@@ -97,6 +97,10 @@ struct hipTable {
     pqps_exchange *xch;
     int world, rank;
     uint64_t rows_total;
+    /* Bit plane of HIPCOL_SUDO_USED (width PQPS_WIDTH_BITS, capacity_rows / 8 bytes; data NULL without a byte column): what
+     * the scans read in place of the byte column.  Packed from the byte column wherever that is written (load, INSERT,
+     * DELETE) by the writer that wrote it; index builds, gathers, projection and compaction keep using the byte column. */
+    pqps_column sudo_bits;
 };
 
 #define HIP_MAX_SHARDS 16

@@ -63,7 +63,14 @@ extern "C" {
 
 /* One device-resident column.  `width` in {1,2,4,8} bytes per row; values are
  * compared as unsigned after the host has biased signed columns (see
- * pqps_leaf).  `data` must be 16-byte aligned. */
+ * pqps_leaf).  `data` must be 16-byte aligned.
+ *
+ * width == PQPS_WIDTH_BITS: a BIT PLANE of a boolean column -- row r is bit (r & 7) of byte r >> 3, LSB first, each
+ * row's value 0 or 1 (pqps_pack_bits makes one from a byte column).  `data` 16-byte aligned, readable up to the padded
+ * row count as for byte columns (n_rows rounded up to PQPS_STEP_ROWS rows = a multiple of 128 bytes).  Accepted by the
+ * scan entry points (pqps_filter_scan / _count / _flags, pqps_qstream_*, pqps_exchange_select / _count); every other
+ * entry point taking a pqps_column returns PQPS_EINVAL for one. */
+#define PQPS_WIDTH_BITS 0x81u
 typedef struct pqps_column {
     const void *data;
     uint32_t width;
@@ -154,6 +161,11 @@ int  pqps_copy_peer(pqps_ctx *dst_ctx, void *dst, pqps_ctx *src_ctx, const void 
  * Keeps the dictionary codes of a string column order-preserving when INSERT adds a value
  * at rank `threshold`. */
 int pqps_bump_codes(pqps_ctx *ctx, void *codes, uint32_t width, uint64_t n_rows, uint32_t threshold, void *stream);
+
+/* Bit plane of a byte column (a PQPS_WIDTH_BITS column): writes plane bytes [first_byte, plane_bytes), bit r = (bytes[r] != 0)
+ * for r < n_rows and 0 past it.  Reads bytes[r] for r < n_rows only.  `plane` 16-byte aligned.  Asynchronous on `stream`. */
+int pqps_pack_bits(pqps_ctx *ctx, const uint8_t *bytes, uint64_t n_rows, uint8_t *plane, uint64_t first_byte, uint64_t plane_bytes,
+                   void *stream);
 
 /* Scan mode.  Evaluates `pred` on rows [0, n_rows) of `cols` and writes the
  * matching row IDs (row + id_base, u32) in ASCENDING row order to out_ids and

@@ -31,6 +31,7 @@ TT_LEAVES = 6
 TILE_ROWS = 4096
 SLOT_HEADER_WORDS = 4
 ACCEPT, REJECT = 0xFE, 0xFF
+WIDTH_BITS = 0x81                  # pqps_column.width of a bit plane (PQPS_WIDTH_BITS)
 SYNTH_USERS = 2000
 
 COLUMNS = ["command_id", "raw_command", "base_command", "shell_type", "exit_code", "timestamp",
@@ -297,6 +298,7 @@ def lib():
     L.pqps_synth_generate_host.argtypes = [u64, u64, u64, vp, vp, C.POINTER(SynthCols)]
     L.pqps_synth_generate_host.restype = None
     L.pqps_bump_codes.argtypes = [vp, vp, u32, u64, u32, vp]
+    L.pqps_pack_bits.argtypes = [vp, vp, u64, vp, u64, u64, vp]
     L.pqps_compact_rows.argtypes = [vp, C.POINTER(Column), u32, u64, vp, C.POINTER(u64), vp]
     L.pqps_project_column.argtypes = [vp, C.POINTER(Column), vp, vp, u64, u32, vp, vp]
     L.pqps_gather_keys.argtypes = [vp, C.POINTER(Column), C.c_int, vp, vp, u64, u32, vp, vp]

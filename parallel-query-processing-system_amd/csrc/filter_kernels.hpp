@@ -50,6 +50,12 @@ constexpr int kGroupSteps = 64;             // steps per scan group (64 K rows)
 constexpr int kRplGeneric = 4;              // generic kernel: 4 consecutive rows per lane per chunk
 constexpr uint32_t kGatherParts = 16;       // gather (index mode): expander workgroups per group (each 64 / 16 = 4 steps, one per wave)
 constexpr int kSlotWords = 64;              // 16-bit entries of a step's slot in each of the two list areas of the sparse steps (128 bytes)
+// Bit-plane columns (PQPS_WIDTH_BITS: row r = bit r & 7 of byte r >> 3): EvalArgs::width_log2 code, and the width
+// parameter of the specialised kernels (the last, narrowest column of a shape).  wcost(): the byte column a plane stands
+// in for -- a shape with a plane keeps the register budget and steps per iteration of the byte shape it replaces.
+constexpr uint8_t kWidthLog2Bits = 7;
+constexpr int kBitPlane = -1;
+constexpr int wcost(int w) { return w == kBitPlane ? 1 : w; }
 
 enum Mode { MODE_IDS = 0, MODE_COUNT = 1, MODE_FLAGS = 2 };
 
@@ -270,21 +276,34 @@ __device__ __forceinline__ uint32_t leaf_mask(const T (&v)[R], T lo, T span) {
 
 struct LeafMasks { uint32_t m[PQPS_TT_LEAVES]; };
 
+__device__ __forceinline__ void set_leaf_mask(LeafMasks &lm, uint32_t k, uint32_t m) {
+    switch (k) {                                                // uniform: keeps lm in registers
+    case 0: lm.m[0] = m; break;
+    case 1: lm.m[1] = m; break;
+    case 2: lm.m[2] = m; break;
+    case 3: lm.m[3] = m; break;
+    case 4: lm.m[4] = m; break;
+    default: lm.m[5] = m; break;
+    }
+}
+
 template <typename T, int R>
 __device__ __forceinline__ void apply_leaves_masks(CArgs &a, uint32_t kb, uint32_t ke,
                                                    const T (&v)[R], LeafMasks &lm) {
     for (uint32_t k = kb; k < ke; k++) {                        // uniform; operands come in SGPRs
         uint32_t m = leaf_mask<T, R>(v, (T)a.lo[k], (T)a.span[k]);
         if ((a.negmask >> k) & 1u) m = ~m;
-        switch (k) {                                            // uniform: keeps lm in registers
-        case 0: lm.m[0] = m; break;
-        case 1: lm.m[1] = m; break;
-        case 2: lm.m[2] = m; break;
-        case 3: lm.m[3] = m; break;
-        case 4: lm.m[4] = m; break;
-        default: lm.m[5] = m; break;
-        }
+        set_leaf_mask(lm, k, m);
     }
+}
+
+// A leaf on a bit plane: the window test ((x - lo) <= span) of x in {0, 1} -- the test of a byte column of the same
+// values, in the same 32-bit arithmetic -- has two wave-uniform outcomes, so the raw hits of a lane's rows are its
+// plane bits, their complement, all or none: one or two VALU for 16 rows.
+__device__ __forceinline__ uint32_t bit_leaf_hits(uint32_t bits, uint64_t lo, uint64_t span) {
+    const uint32_t l = (uint32_t)lo, w = (uint32_t)span;
+    const bool h0 = (uint32_t)(0u - l) <= w, h1 = (uint32_t)(1u - l) <= w;
+    return (h1 ? bits : 0u) | (h0 ? ~bits : 0u);
 }
 
 // OR over the true rows of the truth table of AND over leaves (leaf or its complement).
@@ -437,6 +456,14 @@ template <bool NT> __device__ __forceinline__ uint32_t ld_x1(const void *p) {
     if constexpr (NT) return __builtin_nontemporal_load((const uint32_t *)p);
     else return *(const uint32_t *)p;
 }
+template <bool NT> __device__ __forceinline__ uint32_t ld_u8(const void *p) {
+    if constexpr (NT) return __builtin_nontemporal_load((const uint8_t *)p);
+    else return *(const uint8_t *)p;
+}
+template <bool NT> __device__ __forceinline__ uint32_t ld_u16(const void *p) {
+    if constexpr (NT) return __builtin_nontemporal_load((const uint16_t *)p);
+    else return *(const uint16_t *)p;
+}
 
 // Match bits of rows at or past n_rows never count.  Bit p of lane l <-> row step_row0 + (p / RPL) * 64 * RPL + l * RPL + p % RPL.
 // (The partial last step of a scan is evaluated like a full one -- column buffers are readable up to the next
@@ -497,6 +524,10 @@ __device__ __forceinline__ uint32_t eval_step_full(CArgs &a, uint64_t step_row0,
                     const uint2 q = ld_x2<NT>(base + r0 * 2);
                     v[4 * u] = q.x & 0xFFFFu; v[4 * u + 1] = q.x >> 16;
                     v[4 * u + 2] = q.y & 0xFFFFu; v[4 * u + 3] = q.y >> 16;
+                } else if (wl == kWidthLog2Bits) {                  // bit plane: the lane's 4 rows are a nibble (r0 is a multiple of 4)
+                    const uint32_t q = ld_u8<NT>(base + (r0 >> 3)) >> (uint32_t)(r0 & 4u);
+                    v[4 * u] = q & 1u; v[4 * u + 1] = (q >> 1) & 1u;
+                    v[4 * u + 2] = (q >> 2) & 1u; v[4 * u + 3] = (q >> 3) & 1u;
                 } else {
                     const uint32_t q = ld_x1<NT>(base + r0);
                     v[4 * u] = q & 0xFFu; v[4 * u + 1] = (q >> 8) & 0xFFu;
@@ -2000,13 +2031,39 @@ struct RawChunk {
     __device__ __forceinline__ uint64_t get64() const { return (uint64_t)d[2 * R] | ((uint64_t)d[2 * R + 1] << 32); }
 };
 
+// The RPL rows of a chunk on a bit plane: lane l's rows lane_row0 + u * 64 * RPL ... + RPL lie in byte l + 64u of the step's
+// 128 bytes (RPL 8), a u16 at 2l (RPL 16), a nibble of byte 32u + l / 2 (RPL 4) -- one coalesced sub-dword load per chunk.
+template <int RPL>
+struct RawChunk<kBitPlane, RPL> {
+    uint32_t d[1];                                              // bit R = row R of the chunk (RPL 4: bits above 3 belong to the other lane)
+    template <bool NT>
+    __device__ __forceinline__ void load_bits(const char *plane, uint64_t row0) {
+        if constexpr (RPL == 16) d[0] = ld_u16<NT>(plane + (row0 >> 3));
+        else if constexpr (RPL == 8) d[0] = ld_u8<NT>(plane + (row0 >> 3));
+        else d[0] = ld_u8<NT>(plane + (row0 >> 3)) >> (uint32_t)(row0 & 4u);
+    }
+    template <int R>
+    __device__ __forceinline__ uint32_t get32() const { return (d[0] >> R) & 1u; }
+};
+
 template <int W, int RPL, int U>
 struct RawCol {
     RawChunk<W, RPL> c[U];
     template <bool NT>
     __device__ __forceinline__ void load(const void *base, uint64_t lane_row0) {
 #pragma unroll
-        for (int u = 0; u < U; u++) c[u].template load<NT>((const char *)base + (lane_row0 + (uint64_t)u * 64 * RPL) * W);
+        for (int u = 0; u < U; u++) {
+            if constexpr (W == kBitPlane) c[u].template load_bits<NT>((const char *)base, lane_row0 + (uint64_t)u * 64 * RPL);
+            else c[u].template load<NT>((const char *)base + (lane_row0 + (uint64_t)u * 64 * RPL) * W);
+        }
+    }
+    // bit plane: the lane's 16 rows of the step as a 16-bit mask, bit r = row r as unpack32 numbers them
+    __device__ __forceinline__ uint32_t bits16() const {
+        static_assert(W == kBitPlane, "bit planes only");
+        uint32_t m = 0;
+#pragma unroll
+        for (int u = 0; u < U; u++) m |= (c[u].d[0] & ((1u << RPL) - 1u)) << (u * RPL);
+        return m;
     }
 };
 
@@ -2022,7 +2079,13 @@ __device__ __forceinline__ void unpack64(const RawCol<W, RPL, U> &raw, uint64_t 
 template <int W, int RPL, int U>
 __device__ __forceinline__ void eval_col_masks(CArgs &a, int slot, const RawCol<W, RPL, U> &raw, LeafMasks &lm) {
     const uint32_t kb = a.leaf_begin[slot], ke = a.leaf_begin[slot + 1];
-    if constexpr (W == 8) {
+    if constexpr (W == kBitPlane) {
+        const uint32_t bits = raw.bits16();
+        for (uint32_t k = kb; k < ke; k++) {                        // uniform
+            const uint32_t m = bit_leaf_hits(bits, a.lo[k], a.span[k]);
+            set_leaf_mask(lm, k, ((a.negmask >> k) & 1u) ? ~m : m);
+        }
+    } else if constexpr (W == 8) {
         uint64_t v[16];
         unpack64(raw, v, std::make_integer_sequence<int, 16>{});
         apply_leaves_masks<uint64_t, 16>(a, kb, ke, v, lm);
@@ -2106,6 +2169,19 @@ __device__ __forceinline__ void eval_col_valu(CArgs &a, int slot, const RawCol<W
     unpack32(raw, v, std::make_integer_sequence<int, 16>{});
     for (uint32_t k = kb; k < ke; k++)                              // uniform
         valu_leaf<uint32_t>(v, (uint32_t)a.lo[k], (uint32_t)a.span[k], ((a.chain_want >> k) & 1u) != 0, t);
+}
+
+// ... the leaves of a bit plane: the rows (bit r) where every leaf has the raw hit the chain wants
+template <int RPL, int U>
+__device__ __forceinline__ uint32_t chain_bits(CArgs &a, int slot, const RawCol<kBitPlane, RPL, U> &raw) {
+    const uint32_t kb = a.leaf_begin[slot], ke = a.leaf_begin[slot + 1];
+    const uint32_t bits = raw.bits16();
+    uint32_t keep = 0xFFFFu;
+    for (uint32_t k = kb; k < ke; k++) {                            // uniform
+        const uint32_t h = bit_leaf_hits(bits, a.lo[k], a.span[k]);
+        keep &= ((a.chain_want >> k) & 1u) ? h : ~h;
+    }
+    return keep;
 }
 
 constexpr int log2i(int x) { return x <= 1 ? 0 : 1 + log2i(x / 2); }
@@ -2193,11 +2269,13 @@ struct RawStep {
 #pragma unroll
             for (int r = 0; r < 16; r++) t[r] = 1u << r;
             eval_col_valu<W0, RPL, U>(a, 0, r0, t);
-            if constexpr (W1 != 0) eval_col_valu<W1, RPL, U>(a, 1, r1, t);
-            if constexpr (W2 != 0) eval_col_valu<W2, RPL, U>(a, 2, r2, t);
+            if constexpr (W1 != 0 && W1 != kBitPlane) eval_col_valu<W1, RPL, U>(a, 1, r1, t);
+            if constexpr (W2 != 0 && W2 != kBitPlane) eval_col_valu<W2, RPL, U>(a, 2, r2, t);
             uint32_t m = 0;
 #pragma unroll
             for (int r = 0; r < 16; r++) m |= t[r];
+            if constexpr (W1 == kBitPlane) m &= chain_bits<RPL, U>(a, 1, r1);     // (a plane is the last column)
+            if constexpr (W2 == kBitPlane) m &= chain_bits<RPL, U>(a, 2, r2);
             if (a.chain == 2) m ^= 0xFFFFu;                         // OR form: NOT of the AND
             if (MODE == MODE_IDS) {
                 // most steps of a sparse answer have no match: one compare + one scalar test instead of a wave reduction
@@ -2222,7 +2300,7 @@ struct RawStep {
     }
 };
 
-// W0 >= W1 >= W2 are the byte widths of the predicate columns (0 = slot unused).
+// W0 >= W1 >= W2 are the byte widths of the predicate columns (0 = slot unused; kBitPlane = a bit plane, the last column).
 // The kernel arguments the first loads depend on, fetched together at the very top: left to itself the
 // compiler fetches them where first used, three dependent scalar-load round trips (~0.6 us) before a
 // wave has a byte of the table in flight -- which a one-shot workgroup pays on every launch.
@@ -2234,7 +2312,7 @@ struct RawStep {
 
 // General tree of <= 6 leaves (row-mask path).
 template <int MODE, int W0, int W1, int W2, bool NT>
-__global__ __launch_bounds__(kBlock, MODE == MODE_IDS ? (W0 + W1 + W2 >= 12 ? 7 : 8) : 1) void eval_spec_kernel(const EvalArgs) {
+__global__ __launch_bounds__(kBlock, MODE == MODE_IDS ? (wcost(W0) + wcost(W1) + wcost(W2) >= 12 ? 7 : 8) : 1) void eval_spec_kernel(const EvalArgs) {
     CArgs &a = kernel_args();
     // consecutive rows per lane per chunk: the widest column is one dwordx4 per chunk
     // (an 8-byte column: two, so that RPL stays in {4, 8, 16})
@@ -2298,7 +2376,7 @@ __global__ __launch_bounds__(kBlock, MODE == MODE_IDS ? (W0 + W1 + W2 >= 12 ? 7 
 #ifndef PQPS_MULTI_BYTES
 #define PQPS_MULTI_BYTES 1
 #endif
-constexpr int chain_steps(int w0, int w1, int w2) { return w0 + w1 + w2 <= PQPS_MULTI_BYTES ? 2 : 1; }
+constexpr int chain_steps(int w0, int w1, int w2) { return wcost(w0) + wcost(w1) + wcost(w2) <= PQPS_MULTI_BYTES ? 2 : 1; }
 
 #ifndef PQPS_CHAIN_WGS
 #define PQPS_CHAIN_WGS 8

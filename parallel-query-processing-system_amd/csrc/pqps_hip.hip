@@ -403,6 +403,23 @@ __global__ void bump_codes_kernel(T *codes, uint64_t n, uint32_t threshold) {
     }
 }
 
+// ---- bit planes of boolean columns (PQPS_WIDTH_BITS) ----------------------------------------
+// One thread per plane byte: the 8 bytes of its rows in one load where all of them exist.
+__global__ void pack_bits_kernel(const uint8_t *bytes, uint64_t n_rows, uint8_t *plane, uint64_t first_byte, uint64_t plane_bytes) {
+    for (uint64_t b = first_byte + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; b < plane_bytes; b += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t r0 = b * 8;
+        uint32_t v = 0;
+        if (r0 + 8 <= n_rows) {
+            const uint64_t x = *(const uint64_t *)(bytes + r0);          // (16-byte aligned column, r0 a multiple of 8)
+#pragma unroll
+            for (int i = 0; i < 8; i++) v |= ((x >> (8 * i)) & 0xFFu) ? (1u << i) : 0u;
+        } else {
+            for (uint64_t i = 0; r0 + i < n_rows && i < 8; i++) v |= bytes[r0 + i] ? (1u << i) : 0u;
+        }
+        plane[b] = (uint8_t)v;
+    }
+}
+
 // Loads this library's code object (several MB, ~8 ms) when a context is created -- an engine does
 // that on a background thread beside its CSV parse -- instead of inside the first query.
 __global__ void warm_kernel() {}
@@ -621,7 +638,8 @@ int take_status_of(pqps_ctx *ctx, uint32_t lo, uint32_t hi, const char *who) {
     return fail(PQPS_EHIP, "an ID-output launch gave up waiting for its scan tiles (epoch %u): results of this %s are incomplete", st, who);
 }
 
-int check_pred(const pqps_column *cols, uint32_t n_cols, const pqps_predicate *pred) {
+// `bits_ok`: the call scans (bit-plane columns are read by the scan kernels); gathers take byte columns only
+int check_pred(const pqps_column *cols, uint32_t n_cols, const pqps_predicate *pred, bool bits_ok = true) {
     if (!pred) return fail(PQPS_EINVAL, "predicate is NULL");
     if (n_cols > PQPS_MAX_COLUMNS) return fail(PQPS_EINVAL, "too many columns: %u", n_cols);
     if (n_cols && !cols) return fail(PQPS_EINVAL, "column array is NULL");
@@ -629,7 +647,8 @@ int check_pred(const pqps_column *cols, uint32_t n_cols, const pqps_predicate *p
     if (pred->n_columns != n_cols) return fail(PQPS_EINVAL, "predicate uses %u columns, call passes %u", pred->n_columns, n_cols);
     for (uint32_t c = 0; c < n_cols; c++) {
         const uint32_t w = cols[c].width;
-        if (w != 1 && w != 2 && w != 4 && w != 8) return fail(PQPS_EINVAL, "column %u: width %u not in {1,2,4,8}", c, w);
+        if (w == PQPS_WIDTH_BITS && !bits_ok) return fail(PQPS_EINVAL, "column %u: a bit plane is read by scans only", c);
+        if (w != 1 && w != 2 && w != 4 && w != 8 && w != PQPS_WIDTH_BITS) return fail(PQPS_EINVAL, "column %u: width %u not in {1,2,4,8,bits}", c, w);
         if (!cols[c].data) return fail(PQPS_EINVAL, "column %u: NULL data", c);
         if (((uintptr_t)cols[c].data & 15u) != 0) return fail(PQPS_EINVAL, "column %u: data not 16-byte aligned", c);
     }
@@ -658,7 +677,8 @@ void fill_args(EvalArgs &a, const pqps_column *cols, uint32_t n_cols, const pqps
     a.truth = pred->truth;
     for (uint32_t c = 0; c < n_cols; c++) {
         a.col[c] = cols[c].data;
-        a.width_log2[c] = cols[c].width == 1 ? 0 : cols[c].width == 2 ? 1 : cols[c].width == 4 ? 2 : 3;
+        const uint32_t w = cols[c].width;
+        a.width_log2[c] = w == PQPS_WIDTH_BITS ? kWidthLog2Bits : w == 1 ? 0 : w == 2 ? 1 : w == 4 ? 2 : 3;
     }
     uint32_t k = 0;
     for (uint32_t c = 0; c <= n_cols; c++) {
@@ -694,15 +714,19 @@ void fill_args(EvalArgs &a, const pqps_column *cols, uint32_t n_cols, const pqps
 // ---- K1 dispatch: width-specialised instantiations ----------------------------------------
 typedef void (*eval_fn)(const EvalArgs);
 
-// every non-increasing (W0, W1, W2) from {8,4,2,1}, W = 0 marks an unused slot
+// every non-increasing (W0, W1, W2) from {8,4,2,1}, W = 0 marks an unused slot -- at most one 8-byte column (the schema has one,
+// command_id) -- and the same shapes with a bit plane (B) as their last column (the schema has one boolean, sudo_used).
+// A shape not listed (several planes, a plane before a byte column, a lone plane) takes the generic kernel.
 #ifdef PQPS_DEV_SHAPES   /* development builds: the bench shapes only (compiles in a fraction of the time) */
-#define PQPS_FOR_EACH_SHAPE(X) X(4,0,0) X(2,0,0) X(1,0,0) X(4,1,0) X(2,1,0) X(4,4,4)
+#define PQPS_FOR_EACH_SHAPE(X) X(4,0,0) X(2,0,0) X(1,0,0) X(4,1,0) X(2,1,0) X(4,4,4) X(4,B,0) X(2,B,0)
 #else
 #define PQPS_FOR_EACH_SHAPE(X) \
     X(8,0,0) X(4,0,0) X(2,0,0) X(1,0,0) \
-    X(8,8,0) X(8,4,0) X(8,2,0) X(8,1,0) X(4,4,0) X(4,2,0) X(4,1,0) X(2,2,0) X(2,1,0) X(1,1,0) \
-    X(8,8,8) X(8,8,4) X(8,8,2) X(8,8,1) X(8,4,4) X(8,4,2) X(8,4,1) X(8,2,2) X(8,2,1) X(8,1,1) \
-    X(4,4,4) X(4,4,2) X(4,4,1) X(4,2,2) X(4,2,1) X(4,1,1) X(2,2,2) X(2,2,1) X(2,1,1) X(1,1,1)
+    X(8,4,0) X(8,2,0) X(8,1,0) X(4,4,0) X(4,2,0) X(4,1,0) X(2,2,0) X(2,1,0) X(1,1,0) \
+    X(8,4,4) X(8,4,2) X(8,4,1) X(8,2,2) X(8,2,1) X(8,1,1) \
+    X(4,4,4) X(4,4,2) X(4,4,1) X(4,2,2) X(4,2,1) X(4,1,1) X(2,2,2) X(2,2,1) X(2,1,1) X(1,1,1) \
+    X(8,B,0) X(4,B,0) X(2,B,0) X(1,B,0) \
+    X(8,4,B) X(8,2,B) X(8,1,B) X(4,4,B) X(4,2,B) X(4,1,B) X(2,2,B) X(2,1,B) X(1,1,B)
 #endif
 
 // chain kernels exist with 1 step per iteration and (narrow shapes) with several, and in three evaluator variants:
@@ -710,13 +734,13 @@ typedef void (*eval_fn)(const EvalArgs);
 // on the vector unit (shapes of up to 8 bytes per row whose widest column has 4)
 constexpr uint64_t kInterleaveFromGroups = 8192;                    // from this many groups (537 M rows) on the expanders run among the scan tiles, see expand_lag()
 constexpr uint64_t kListAreaBelowGroups = 4096;                     // below this many groups (268 M rows) ID scans have a list area, and the S1 shape takes its vector-unit chain kernel
-constexpr bool valu_chain_shape(int a, int b, int c) { return a <= 4 && a + b + c <= 8; }
+constexpr bool valu_chain_shape(int a, int b, int c) { return a <= 4 && wcost(a) + wcost(b) + wcost(c) <= 8; }
 // ... and where it is the default.  A/B runs on one box (us per launch, ballots / vector unit): S1 = (2,1,0) as ID list at
 // 100 M rows 59.4 / 57.4, at 1 G rows 496 / 496, as COUNT(*) at 1 G rows 438 / 468; Q_B = (4,1,0) as ID list 103 / 113 (its
 // tile path spills at 64 VGPRs), at 1 G rows 901 / 959.  So: the u16 + u8 shape, ID output, below the size from which the
 // expanders run among the tiles.
-inline bool valu_chain_default(uint32_t w0, uint32_t w1, uint32_t w2, int mode, uint64_t n_rows) {
-    return mode == MODE_IDS && w0 == 2 && w1 == 1 && w2 == 0 && n_rows < kListAreaBelowGroups * (uint64_t)kGroupSteps * kStepRows;
+inline bool valu_chain_default(int w0, int w1, int w2, int mode, uint64_t n_rows) {
+    return mode == MODE_IDS && w0 == 2 && (w1 == 1 || w1 == kBitPlane) && w2 == 0 && n_rows < kListAreaBelowGroups * (uint64_t)kGroupSteps * kStepRows;
 }
 
 template <int MODE, int A, int B, int C, int S, bool NT>
@@ -730,14 +754,16 @@ eval_fn chain_variant(int ev) {
     return eval_chain_kernel<MODE, A, B, C, S, NT, 0>;
 }
 
+#define B kBitPlane
 template <int MODE, bool NT>
-eval_fn find_spec_nt(uint32_t w0, uint32_t w1, uint32_t w2, bool chain, bool multi_step, int vc) {
+eval_fn find_spec_nt(int w0, int w1, int w2, bool chain, bool multi_step, int vc) {
 #define X(A, B, C) if (w0 == A && w1 == B && w2 == C) return !chain ? eval_spec_kernel<MODE, A, B, C, NT> \
         : (multi_step ? chain_variant<MODE, A, B, C, chain_steps(A, B, C), NT>(vc) : chain_variant<MODE, A, B, C, 1, NT>(vc));
     PQPS_FOR_EACH_SHAPE(X)
 #undef X
     return nullptr;
 }
+#undef B
 
 // A scan is "streaming" once the columns it reads outgrow the Infinity Cache (256 MB on MI355X) by
 // a margin: it then uses `nt` loads and a one-shot grid; below that a repeated scan finds part of
@@ -749,14 +775,22 @@ bool is_streaming(uint64_t footprint) {
     return force ? atoi(force) != 0 : footprint > kStreamingFootprint;
 }
 
+// (the bytes the scan reads: a bit plane is an eighth of a byte per row)
 void set_streaming(EvalArgs &a, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows) {
-    uint64_t row_bytes = 0;
-    for (uint32_t c = 0; c < n_cols; c++) row_bytes += cols[c].width;
-    a.streaming = is_streaming(n_rows * row_bytes) ? 1u : 0u;
+    uint64_t row_eighths = 0;
+    for (uint32_t c = 0; c < n_cols; c++) row_eighths += cols[c].width == PQPS_WIDTH_BITS ? 1u : 8u * cols[c].width;
+    a.streaming = is_streaming(n_rows * row_eighths / 8) ? 1u : 0u;
+}
+
+// width of a column as the specialised kernels' template parameter
+int spec_width(uint32_t w) { return w == PQPS_WIDTH_BITS ? kBitPlane : (int)w; }
+const char *width_name(int w) {
+    static const char *const names[] = { "0", "1", "2", "?", "4", "?", "?", "?", "8" };
+    return w == kBitPlane ? "B" : (w >= 0 && w <= 8 ? names[w] : "?");
 }
 
 template <int MODE>
-eval_fn find_spec(uint32_t w0, uint32_t w1, uint32_t w2, bool chain, bool multi_step, bool nt, int vc) {
+eval_fn find_spec(int w0, int w1, int w2, bool chain, bool multi_step, bool nt, int vc) {
     return nt ? find_spec_nt<MODE, true>(w0, w1, w2, chain, multi_step, vc) : find_spec_nt<MODE, false>(w0, w1, w2, chain, multi_step, vc);
 }
 
@@ -765,7 +799,7 @@ template <int MODE>
 eval_fn pick_eval(const pqps_column *cols, uint32_t n_cols, const pqps_predicate *pred, EvalArgs &a, uint64_t n_rows) {
     set_streaming(a, cols, n_cols, n_rows);
     if (n_cols >= 1 && n_cols <= 3 && pred->n_leaves >= 1 && pred->n_leaves <= PQPS_TT_LEAVES) {
-        const uint32_t w0 = cols[0].width, w1 = n_cols > 1 ? cols[1].width : 0, w2 = n_cols > 2 ? cols[2].width : 0;
+        const int w0 = spec_width(cols[0].width), w1 = n_cols > 1 ? spec_width(cols[1].width) : 0, w2 = n_cols > 2 ? spec_width(cols[2].width) : 0;
         // several steps per iteration only where chain_steps() says so (a lone 1-byte column)
         static const char *force = tuning_env("PQPS_CHAIN_MULTI");
         const bool multi = force ? atoi(force) != 0 : true;
@@ -773,17 +807,17 @@ eval_fn pick_eval(const pqps_column *cols, uint32_t n_cols, const pqps_predicate
         // vector unit: see RawStep::one_leaf / valu_leaf
         static const char *valu_env = tuning_env("PQPS_VALU_CHAIN");                 // tuning runs: 0 / 1 = ballots / vector unit for every eligible chain
         const bool one = pred->n_leaves == 1 && n_cols == 1;
-        const bool valu = valu_chain_shape((int)w0, (int)w1, (int)w2) && (valu_env ? atoi(valu_env) != 0 : valu_chain_default(w0, w1, w2, MODE, n_rows));
+        const bool valu = valu_chain_shape(w0, w1, w2) && (valu_env ? atoi(valu_env) != 0 : valu_chain_default(w0, w1, w2, MODE, n_rows));
         const int vc = a.chain == 0 ? 0 : (one ? 1 : (valu ? 2 : 0));
         a.valu_chain = vc ? 1u : 0u;
         if (eval_fn f = find_spec<MODE>(w0, w1, w2, a.chain != 0, multi, a.streaming != 0, vc)) {   // nullptr unless widths are non-increasing
-            if (a.chain != 0 && multi) a.steps_per_iter = (uint32_t)chain_steps((int)w0, (int)w1, (int)w2);
+            if (a.chain != 0 && multi) a.steps_per_iter = (uint32_t)chain_steps(w0, w1, w2);
             const char *mode = MODE == MODE_IDS ? "MODE_IDS" : MODE == MODE_COUNT ? "MODE_COUNT" : "MODE_FLAGS";
             if (a.chain != 0)
-                snprintf(g_kernel, sizeof g_kernel, "eval_chain_kernel<%s, W0=%u, W1=%u, W2=%u, S=%u, NT=%s, EV=%d>", mode, w0, w1, w2,
+                snprintf(g_kernel, sizeof g_kernel, "eval_chain_kernel<%s, W0=%s, W1=%s, W2=%s, S=%u, NT=%s, EV=%d>", mode, width_name(w0), width_name(w1), width_name(w2),
                          a.steps_per_iter ? a.steps_per_iter : 1u, a.streaming ? "true" : "false", vc);
             else
-                snprintf(g_kernel, sizeof g_kernel, "eval_spec_kernel<%s, W0=%u, W1=%u, W2=%u, NT=%s>", mode, w0, w1, w2, a.streaming ? "true" : "false");
+                snprintf(g_kernel, sizeof g_kernel, "eval_spec_kernel<%s, W0=%s, W1=%s, W2=%s, NT=%s>", mode, width_name(w0), width_name(w1), width_name(w2), a.streaming ? "true" : "false");
             return f;
         }
     }
@@ -949,7 +983,7 @@ int run_filter(pqps_ctx *ctx, eval_fn k1, EvalArgs &a, uint64_t rows, int mode, 
         // ... not where the widest predicate column is one byte wide (as for the entries in the slots: a step is 1 KB of input there, and
         // an answer of a 1-byte predicate is rarely sparse; the second load of every look cost a lone u8 column 2.5 % at 1 G rows)
         bool narrow = a.n_cols > 0;
-        for (uint32_t c = 0; c < a.n_cols; c++) narrow = narrow && a.width_log2[c] == 0;
+        for (uint32_t c = 0; c < a.n_cols; c++) narrow = narrow && (a.width_log2[c] == 0 || a.width_log2[c] == kWidthLog2Bits);
         if (narrow && ctx->opt_tiny_max < 0 && env_tiny < 0) a.tiny_max = 0;
         a.list_max = m0 < kListIds ? m0 : kListIds;
         a.list_max_u8 = 0;                                           // (the kernels of 1-byte predicates carry neither form: step_form)
@@ -1322,7 +1356,7 @@ int gather_filter(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols,
                   uint32_t *out_ids, uint64_t out_capacity, uint64_t *out_count, void *stream, const void *key_col, const void *keys) {
     if (!ctx || !out_count || !cand || !range) return fail(PQPS_EINVAL, "ctx/cand/range/out_count is NULL");
     if (!out_ids && out_capacity) return fail(PQPS_EINVAL, "out_ids is NULL");
-    int rc = check_pred(cols, n_cols, pred);
+    int rc = check_pred(cols, n_cols, pred, false);
     if (rc) return rc;
     EvalArgs a;
     fill_args(a, cols, n_cols, pred);
@@ -1465,7 +1499,7 @@ int pqps_index_select(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, c
                       uint64_t *range, uint32_t *out_ids, uint64_t out_capacity, uint64_t *out_count, void *stream) {
     if (!ctx || !range || !index_column || !perm || !out_count || (!sorted_keys && n_rows)) return fail(PQPS_EINVAL, "NULL argument");
     if (!out_ids && out_capacity) return fail(PQPS_EINVAL, "out_ids is NULL");
-    int rc = check_pred(cols, n_cols, pred);
+    int rc = check_pred(cols, n_cols, pred, false);
     if (rc) return rc;
     hipStream_t s = pick_stream(ctx, stream);
     if (!probe_implies_predicate(cols, n_cols, index_column, key_kind, key_lo, key_hi, pred)) {
@@ -1550,6 +1584,19 @@ int pqps_bump_codes(pqps_ctx *ctx, void *codes, uint32_t width, uint64_t n_rows,
     else if (width == 2) hipLaunchKernelGGL((bump_codes_kernel<uint16_t>), dim3(blocks), dim3(256), 0, s, (uint16_t *)codes, n_rows, threshold);
     else if (width == 4) hipLaunchKernelGGL((bump_codes_kernel<uint32_t>), dim3(blocks), dim3(256), 0, s, (uint32_t *)codes, n_rows, threshold);
     else return fail(PQPS_EINVAL, "code width %u not in {1,2,4}", width);
+    HIP_TRY(hipGetLastError());
+    return PQPS_OK;
+}
+
+int pqps_pack_bits(pqps_ctx *ctx, const uint8_t *bytes, uint64_t n_rows, uint8_t *plane, uint64_t first_byte, uint64_t plane_bytes,
+                   void *stream) {
+    if (!ctx || !plane || (!bytes && n_rows)) return fail(PQPS_EINVAL, "NULL argument");
+    if ((((uintptr_t)bytes | (uintptr_t)plane) & 15u) != 0) return fail(PQPS_EINVAL, "byte column / plane not 16-byte aligned");
+    if (first_byte >= plane_bytes) return PQPS_OK;
+    hipStream_t s = pick_stream(ctx, stream);
+    const uint64_t want = (plane_bytes - first_byte + 255) / 256;
+    const uint32_t blocks = (uint32_t)(want < 8192 ? want : 8192);
+    hipLaunchKernelGGL(pack_bits_kernel, dim3(blocks), dim3(256), 0, s, bytes, n_rows, plane, first_byte, plane_bytes);
     HIP_TRY(hipGetLastError());
     return PQPS_OK;
 }

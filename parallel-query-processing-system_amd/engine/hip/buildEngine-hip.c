@@ -485,9 +485,28 @@ static void shard_alloc(struct hipTable *sh, pqps_ctx *ctx, const struct hipTabl
         if (pqps_memset(ctx, (char *)dev + count * width, 0, (sh->capacity_rows - count) * width, NULL) != PQPS_OK) hip_die("column clear");
         sh->col[c].data = dev;
     }
+    sh->sudo_bits.data = NULL;
+    sh->sudo_bits.width = PQPS_WIDTH_BITS;
+    if (sh->col[HIPCOL_SUDO_USED].width == 1) {
+        void *dev = NULL;
+        if (pqps_malloc(ctx, sh->capacity_rows / 8, &dev) != PQPS_OK) hip_die("bit plane allocation");
+        sh->sudo_bits.data = dev;
+    }
     lane_alloc(sh, &sh->own, false);
     if (pqps_ctx_reserve(ctx, sh->capacity_rows) != PQPS_OK) hip_die("filter scratch allocation");   /* not inside the first query */
 }
+
+/* The bit plane of the shard's sudo_used from its byte column: plane bytes [first_row / 8, end_byte), the bits past n_rows
+ * zero.  Synchronous: a query issued after the writer returns never sees a stale plane. */
+static void shard_pack_bits(struct hipTable *sh, uint64_t first_row, uint64_t end_byte) {
+    if (!sh->sudo_bits.data) return;
+    if (pqps_pack_bits(sh->ctx, (const uint8_t *)sh->col[HIPCOL_SUDO_USED].data, sh->n_rows, (uint8_t *)sh->sudo_bits.data, first_row / 8,
+                       end_byte, NULL) != PQPS_OK ||
+        pqps_ctx_sync(sh->ctx, NULL) != PQPS_OK)
+        hip_die("bit plane");
+}
+
+static void shard_pack_all_bits(struct hipTable *sh) { shard_pack_bits(sh, 0, sh->capacity_rows / 8); }
 
 /* Device side of one shard: rows [row0, row0 + count) of the staged columns. */
 static void shard_upload(struct hipTable *sh, pqps_ctx *ctx, const struct hipTable *widths, void *const *stage,
@@ -498,6 +517,7 @@ static void shard_upload(struct hipTable *sh, pqps_ctx *ctx, const struct hipTab
         if (count && width && pqps_upload(ctx, (void *)sh->col[c].data, (const char *)stage[c] + row0 * width, count * width, NULL) != PQPS_OK)
             hip_die("column upload");
     }
+    shard_pack_all_bits(sh);
 }
 
 /* The shard structs of a table over `n_shards` contexts (shard 0 = the table itself). */
@@ -718,6 +738,8 @@ static void shard_release(struct hipTable *sh, int n_indexes) {
         if (sh->col[c].data) pqps_free(sh->ctx, (void *)sh->col[c].data);
         sh->col[c].data = NULL;
     }
+    if (sh->sudo_bits.data) pqps_free(sh->ctx, (void *)sh->sudo_bits.data);
+    sh->sudo_bits.data = NULL;
     if (sh->index) {
         for (int i = 0; i < n_indexes; i++) {
             if (sh->index[i].perm_dev) pqps_free(sh->ctx, sh->index[i].perm_dev);
@@ -928,6 +950,7 @@ bool appendRowDeviceTableHIP(struct engineS *engine, const record *r) {
         if (w && pqps_upload(last->ctx, (char *)last->col[c].data + last->n_rows * w, &value, w, NULL) != PQPS_OK) hip_die("row upload");
     }
     last->n_rows += 1;
+    shard_pack_bits(last, last->n_rows - 1, (last->n_rows - 1) / 8 + 1);      /* the plane byte of the new row */
     for (int s = 0; s < n_shards; s++)                          /* shifted codes are keys of the other shards' indexes too */
         if (bumped || s == n_shards - 1) rebuild_indexes(engine, hipTableShard(t, s));
     return true;
@@ -950,6 +973,7 @@ void compactDeviceTableHIP(struct engineS *engine, uint8_t *const *delete_flags_
         sh->n_rows = kept;
         sh->row0 = total;
         total += kept;
+        if (changed) shard_pack_all_bits(sh);
         if (changed) rebuild_indexes(engine, sh);
     }
     if (total != (uint64_t)expected_rows) {
@@ -1069,6 +1093,7 @@ bool buildDeviceTableFromColumnsHIP(struct engineS *engine, unsigned long long n
             if (rc != PQPS_OK) hip_die("column copy");
         }
         if (pqps_ctx_sync(sh->ctx, NULL) != PQPS_OK) hip_die("column copy");
+        shard_pack_all_bits(sh);
     }
     free(ctxs);
     table_make_engine(t);
@@ -1166,6 +1191,7 @@ static bool synthetic_table(struct engineS *engine, unsigned long long num_rows,
         out.base_code = (uint8_t *)sh->col[HIPCOL_BASE_COMMAND].data;
         if (sh->n_rows && pqps_synth_generate(sh->ctx, seed, sh->row0, sh->n_rows, cdf_dev, shell_dev, &out, NULL) != PQPS_OK) hip_die("synthetic table generation");
         if (pqps_ctx_sync(sh->ctx, NULL) != PQPS_OK) hip_die("synthetic table generation");
+        shard_pack_all_bits(sh);
         pqps_free(sh->ctx, cdf_dev);
         pqps_free(sh->ctx, shell_dev);
     }

@@ -76,10 +76,17 @@ static void shard_pred_free(struct hipTable *sh, struct shard_pred *sp) {
     sp->n_flags = 0;
 }
 
-static void pass_columns(const struct hipTable *sh, const struct hipPass *pass, uint8_t *const *flags, pqps_column *cols) {
-    for (uint32_t i = 0; i < pass->pred.n_columns; i++) {
+/* `scan`: the columns go to a scan (pqps_filter_scan / _count / _flags, query stream, exchange), which reads sudo_used from
+ * its bit plane -- where the plane is the pass's last column (the width-specialised kernels' shapes: widths non-increasing,
+ * the plane last) or the pass takes the generic kernel anyway (more than 3 columns or more than 6 comparisons).  A lone
+ * bool column keeps its bytes: its scan time is all output, not input.  Index-mode gathers always get the byte column. */
+static void pass_columns(const struct hipTable *sh, const struct hipPass *pass, uint8_t *const *flags, bool scan, pqps_column *cols) {
+    const uint32_t n = pass->pred.n_columns;
+    const bool generic = n > 3 || pass->pred.n_leaves > PQPS_TT_LEAVES;
+    for (uint32_t i = 0; i < n; i++) {
         const int id = pass->column_ids[i];
         if (id >= PQPS_MAX_COLUMNS) { cols[i].data = flags[id - PQPS_MAX_COLUMNS]; cols[i].width = 1; }
+        else if (scan && id == HIPCOL_SUDO_USED && sh->sudo_bits.data && n > 1 && (i == n - 1 || generic)) cols[i] = sh->sudo_bits;
         else cols[i] = sh->col[id];
     }
 }
@@ -237,14 +244,14 @@ static int issue_calls(struct query *q, int s, pqps_ctx *ctx, void *stream) {
         for (int k = 0; k < sp->n_flags; k++) {
             pqps_column cols[PQPS_MAX_COLUMNS];
             TRY(pqps_malloc(sh->ctx, sh->capacity_rows, (void **)&sp->flags[k]), "flag allocation");
-            pass_columns(sh, &plan->pass[k], sp->flags, cols);
+            pass_columns(sh, &plan->pass[k], sp->flags, true, cols);
             TRY(pqps_filter_flags(ctx, cols, plan->pass[k].pred.n_columns, sh->n_rows, &plan->pass[k].pred,
                                   sp->flags[k], L->count_dev + 4, stream), "flag filter");
         }
     }
     sp->pred = &last->pred;
     sp->n_cols = last->pred.n_columns;
-    pass_columns(sh, last, sp->flags, sp->cols);
+    pass_columns(sh, last, sp->flags, q->count_only || q->n_probes == 0, sp->cols);
     if (q->count_only) {
         TRY(pqps_filter_count(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, L->count_dev, stream), "count filter");
     } else if (q->n_probes > 0) {
@@ -287,7 +294,7 @@ static int issue_on_shard(struct query *q, int s) {
         }
         sp->pred = &last->pred;
         sp->n_cols = last->pred.n_columns;
-        pass_columns(sh, last, NULL, sp->cols);
+        pass_columns(sh, last, NULL, true, sp->cols);
         if (q->count_only)
             TRY(pqps_exchange_count(q->t->xch, sp->cols, sp->n_cols, sh->n_rows, sp->pred, (uint32_t)q->lane, NULL), "count exchange");
         else
@@ -298,7 +305,7 @@ static int issue_on_shard(struct query *q, int s) {
     if (q->lane >= 0 && single) {
         sp->pred = &last->pred;
         sp->n_cols = last->pred.n_columns;
-        pass_columns(sh, last, NULL, sp->cols);
+        pass_columns(sh, last, NULL, true, sp->cols);
         if (q->count_only)
             TRY(pqps_qstream_count_slot(sh->qs, (uint32_t)q->lane, sp->cols, sp->n_cols, sh->n_rows, sp->pred, L->count_dev, NULL), "count filter");
         else
@@ -1452,14 +1459,14 @@ static int delete_flags(struct engineS *engine, struct hipTable *t, struct where
             for (int k = 0; k < sp->n_flags && rc == 0; k++) {
                 pqps_column cols[PQPS_MAX_COLUMNS];
                 if (pqps_malloc(sh->ctx, sh->capacity_rows, (void **)&sp->flags[k]) != PQPS_OK) { rc = engine_error("flag allocation"); break; }
-                pass_columns(sh, &head.pass[k], sp->flags, cols);
+                pass_columns(sh, &head.pass[k], sp->flags, true, cols);
                 if (pqps_filter_flags(sh->ctx, cols, head.pass[k].pred.n_columns, sh->n_rows, &head.pass[k].pred, sp->flags[k], sh->own.count_dev + 4, NULL) != PQPS_OK)
                     rc = engine_error("flag filter");
             }
         }
         sp->pred = &last->pred;
         sp->n_cols = last->pred.n_columns;
-        pass_columns(sh, last, sp->flags, sp->cols);
+        pass_columns(sh, last, sp->flags, true, sp->cols);
         if (rc == 0 && pqps_malloc(sh->ctx, sh->capacity_rows, (void **)&flags_dev[s]) != PQPS_OK) rc = engine_error("flag allocation");
         if (rc == 0 && pqps_filter_flags(sh->ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, flags_dev[s], sh->own.count_dev, NULL) != PQPS_OK)
             rc = engine_error("flag filter");
