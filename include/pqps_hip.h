@@ -78,9 +78,12 @@ typedef struct pqps_column {
 } pqps_column;
 
 /* One leaf comparison, normalised by the host to an unsigned window test
- *      hit = ((value - lo) <= span) XOR negate            (mod 2^w arithmetic)
- * which covers =, !=, <, <=, >, >= on u64 / i32 / bool / dictionary codes
- * (signed i32 windows work unchanged in two's complement). */
+ *      hit = ((value - lo) <= span) XOR negate
+ * in 32-bit arithmetic (value zero-extended, lo and span taken mod 2^32) for columns of width 1, 2 and 4 and for bit
+ * planes, and in 64-bit arithmetic for width 8 -- NOT in the column's own width: on a 1-byte column lo = 256 selects
+ * no value, where 8-bit arithmetic would read it as lo = 0.  The host compiler relies on this (a comparison past the
+ * last value of a full 256- or 65536-entry dictionary).  Covers =, !=, <, <=, >, >= on u64 / i32 / bool / dictionary
+ * codes (signed i32 windows work unchanged in two's complement). */
 typedef struct pqps_leaf {
     uint32_t column;          /* index into the pqps_column array of the call */
     uint32_t negate;          /* 0 or 1                                       */

@@ -1467,8 +1467,11 @@ int launch_probe(const void *sorted_keys, uint32_t width, int key_kind, uint64_t
 }
 
 // Is `pred` nothing but the probed comparison -- ONE leaf on the indexed column whose window is the probe's, accepted
-// when it holds?  Then every row the probe finds passes: key in [lo, hi] in the key's order <=> (key - lo) <= hi - lo in
-// w-bit arithmetic (two's complement for the signed keys), which is the leaf's own test.
+// when it holds?  Then every row the probe finds passes.  The probe looks for key in [key_lo, key_hi] in the key's order;
+// the leaf tests (key - lo) <= span in the arithmetic of pqps_leaf (32 bits for widths 1 / 2 / 4, 64 bits for width 8,
+// two's complement for the signed keys).  Both select the same keys when the key window lies within the key's width and
+// the leaf's lo / span, taken in that arithmetic, are exactly key_lo / key_hi - key_lo.  Compared in w bits instead, a
+// leaf `code >= 256` on a 1-byte column (no row) would pass for the probe of [0, 0].
 bool probe_implies_predicate(const pqps_column *cols, uint32_t n_cols, const pqps_column *index_column, int key_kind,
                              uint64_t key_lo, uint64_t key_hi, const pqps_predicate *pred) {
     static const bool enabled = [] { const char *e = getenv("PQPS_INDEX_COPY"); return !e || atoi(e) != 0; }();   // 0 (tests): always evaluate
@@ -1476,10 +1479,17 @@ bool probe_implies_predicate(const pqps_column *cols, uint32_t n_cols, const pqp
     const pqps_leaf &lf = pred->leaf[0];
     if (lf.column >= n_cols || cols[lf.column].data != index_column->data || cols[lf.column].width != index_column->width) return false;
     const uint32_t w = index_column->width;
-    const uint64_t mask = w >= 8 ? ~0ull : ((1ull << (8 * w)) - 1ull);
-    if (key_kind == 1) { if ((int32_t)(uint32_t)key_lo > (int32_t)(uint32_t)key_hi) return false; }
-    else if ((key_lo & mask) > (key_hi & mask)) return false;      // an empty window: left to the filter
-    if (((lf.lo ^ key_lo) & mask) != 0 || ((lf.span ^ (key_hi - key_lo)) & mask) != 0) return false;
+    if (w != 1 && w != 2 && w != 4 && w != 8) return false;
+    if (key_kind == 1 && w != 4) return false;
+    const uint64_t key_mask = w == 8 ? ~0ull : ((1ull << (8 * w)) - 1ull);      // the key's own width
+    const uint64_t leaf_mask = w == 8 ? ~0ull : 0xFFFFFFFFull;                   // the leaf test's arithmetic
+    // a window beyond the key width (the probe would truncate it) is left to the filter; signed keys may come sign-extended
+    auto in_width = [&](uint64_t k) { return (k & ~key_mask) == 0 || (key_kind == 1 && k == (uint64_t)(int64_t)(int32_t)(uint32_t)k); };
+    if (!in_width(key_lo) || !in_width(key_hi)) return false;
+    const uint64_t lo = key_lo & key_mask, hi = key_hi & key_mask;
+    if (key_kind == 1) { if ((int32_t)(uint32_t)lo > (int32_t)(uint32_t)hi) return false; }
+    else if (lo > hi) return false;                                              // an empty window: left to the filter
+    if ((lf.lo & leaf_mask) != lo || (lf.span & leaf_mask) != ((hi - lo) & leaf_mask)) return false;
     return ((pred->truth >> (1u ^ (lf.negate & 1u))) & 1ull) != 0;     // candidates: raw window hit = 1
 }
 

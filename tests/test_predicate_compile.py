@@ -187,3 +187,44 @@ def test_single_valued_dictionary_column_is_folded():
         assert pred.n_leaves == 0 and pred.truth == (1 if truth else 0), (op, lit)
         pred, ids = pq.compile_where(spec, [("raw_command", op, lit), "AND", ("risk_level", "=", "5")])
         assert (pred.n_leaves, len(ids)) == ((1, 1) if truth else (0, 0)), (op, lit)
+
+
+OPS = ["=", "!=", "<", "<=", ">", ">="]
+CMP = {"=": lambda a, b: a == b, "!=": lambda a, b: a != b, "<": lambda a, b: a < b, "<=": lambda a, b: a <= b,
+       ">": lambda a, b: a > b, ">=": lambda a, b: a >= b}
+
+
+def full_dictionary(count):
+    """`count` sorted NUL-free host names and the literals at the edges of the dictionary: before the first value, equal
+    to the first, between two values, equal to the last, after the last, the empty string and a proper prefix of the last."""
+    values = [b"host-%06d" % i for i in range(count)]
+    literals = [b"h", values[0], values[count // 2] + b"x", values[-1], b"zz", b"", values[-1][:-1]]
+    return values, literals
+
+
+def dict_width(count):
+    return 1 if count <= 256 else 2 if count <= 65536 else 4
+
+
+@pytest.mark.parametrize("count", [255, 256, 257, 65535, 65536, 65537])
+def test_full_dictionaries_compile_to_windows_that_hold_in_32_bits(count):
+    """A comparison past the last value of a dictionary of exactly 256 (65536) values compiles to lo = 256 (65536) on a
+    1-byte (2-byte) code column: a window that selects nothing in the 32-bit arithmetic of pqps_leaf and everything in the
+    column's own width.  Every code of the column, every operator, the edge literals; bytes comparison (strcmp order for
+    NUL-free values) is the reference."""
+    values, literals = full_dictionary(count)
+    w = dict_width(count)
+    spec = pq.SchemaSpec().set_dict("host_name", w, values).set_numeric("risk_level", 4)
+    codes = np.arange(count, dtype={1: np.uint8, 2: np.uint16, 4: np.uint32}[w])
+    risk = (np.arange(count) % 3).astype(np.int32)
+    for lit in literals:
+        for op in OPS:
+            want = np.array([CMP[op](v, lit) for v in values])
+            for chain, expect in (([("host_name", op, lit.decode())], want),
+                                  ([("host_name", op, lit.decode()), "AND", ("risk_level", "!=", "1")], want & (risk != 1)),
+                                  ([("risk_level", "=", "1"), "OR", ("host_name", op, lit.decode())], want | (risk == 1))):
+                (pred, ids), = pq.compile_plan(spec, chain)
+                cols = [{"host_name": codes, "risk_level": risk}[pq.COLUMNS[i]] for i in ids]
+                got = km.evaluate(pred, cols)
+                got = np.full(count, got) if isinstance(got, bool) else got
+                assert np.array_equal(got, expect), (count, op, lit, chain)

@@ -7,6 +7,8 @@ the oracle (and, for hand-built predicates, the numpy model of the kernel arithm
 
     python tests/variant_driver.py sizes  [n ...]     seeded synthetic tables, the suite's queries, vs the oracle
     python tests/variant_driver.py shapes [n]         every (W0, W1, W2) kernel shape, chain and tree form, vs numpy
+    python tests/variant_driver.py windows [n ...]    leaf windows at the edges of each column's range, every shape and
+                                                      entry point, vs a numpy restatement of the 32 / 64-bit window test
 """
 import ctypes as C
 import itertools
@@ -199,6 +201,229 @@ def sweep_wrap(ctx, n):
     print(f"wrap: 40 rounds of scan + gather + query stream ok at n={n}", flush=True)
 
 
+
+# ---- leaf windows at the edges of a column's range -------------------------------------------------------------------
+# pqps_leaf: hit = ((x - lo) <= span) ^ negate in 32-bit arithmetic for widths 1, 2, 4 and bit planes, in 64 bits for
+# width 8.  The catalogue holds the windows engine/hip/hipPredicate.c emits at the edges (window_dict with lb / ub at 0,
+# M - 1 and M for a dictionary of M = 2^(8w) values, window_i32 around INT_MIN / -1 / 0 / INT_MAX, which wrap,
+# window_unsigned near the top) and raw windows that mean something else in the column's own width.
+BIT = "B"                                                  # a bit-plane column in a shape
+PLANE_SHAPES = [(8, BIT), (4, BIT), (2, BIT), (1, BIT), (8, 4, BIT), (8, 2, BIT), (8, 1, BIT), (4, 4, BIT), (4, 2, BIT),
+                (4, 1, BIT), (2, 2, BIT), (2, 1, BIT), (1, 1, BIT)]
+GENERIC_SHAPES = [(BIT, 4), (4, 2, 1, BIT), (BIT,), (8, 4, 2, 1)]    # a plane first, four columns, a lone plane
+U64 = (1 << 64) - 1
+TOP32 = 0xFFFFFFFF
+I32_MIN, I32_MAX = -(1 << 31), (1 << 31) - 1
+
+
+def dict_windows(lb, ub):
+    """window_dict for a literal with lb values below it and ub = lb + (present): (lo, span, negate) per operator."""
+    out = [(ub, TOP32 - ub, 0), (lb, TOP32 - lb, 0)]                    # >, >=
+    if lb > 0:
+        out.append((0, lb - 1, 0))                                      # <
+    if ub > 0:
+        out.append((0, ub - 1, 0))                                      # <=
+    if ub > lb:
+        out += [(lb, 0, 0), (lb, 0, 1)]                                 # =, !=
+    return out
+
+
+def i32_windows(v):
+    uv, umin, umax = v & TOP32, 0x80000000, 0x7FFFFFFF
+    out = [(uv, 0, 0), (uv, 0, 1), (uv, (umax - uv) & TOP32, 0), (umin, (uv - umin) & TOP32, 0)]     # =, !=, >=, <=
+    if v != I32_MAX:
+        out.append(((uv + 1) & TOP32, (umax - (uv + 1)) & TOP32, 0))                                  # >
+    if v != I32_MIN:
+        out.append((umin, ((uv - 1) - umin) & TOP32, 0))                                              # <
+    return out
+
+
+def unsigned_windows(v, top):
+    out = [(v, 0, 0), (v, 0, 1), (0, min(v, top), 0)]                   # =, !=, <=
+    if v < top:
+        out.append((v + 1, top - (v + 1), 0))                           # >
+    if v > 0:
+        out.append((0, v - 1, 0))                                       # <
+    if v <= top:
+        out.append((v, top - v, 0))                                     # >=
+    return out
+
+
+def leaf_catalogue(w):
+    """(lo, span) pairs at the edges of a column of width w (a bit plane: w = BIT, values 0 / 1)."""
+    M = 2 if w == BIT else 1 << (8 * w)
+    top = 1 if w == BIT else M - 1
+    cat = set()
+    for lb in (0, M - 1, M):
+        for ub in {lb, lb + 1} if lb < M else {lb}:
+            cat.update(dict_windows(lb, ub))
+    if w == BIT:
+        cat.update(dict_windows(255, 256) + dict_windows(256, 256))    # a bool leaf with a 1-byte dictionary's lo
+    for v in (I32_MIN, -1, 0, I32_MAX):
+        cat.update(i32_windows(v))
+    for v in {0, 1, top - 1, top, U64 - 1, U64}:
+        cat.update(unsigned_windows(v, U64 if w == 8 else top))
+    for lo in (M, M + 1, TOP32):
+        for span in (M - 1, M, TOP32):
+            cat.add((lo, span, 0))
+    return sorted({(lo & U64, span & U64) for lo, span, _ in cat})
+
+
+def edge_column(rng, w, n):
+    """Random values of the column's whole range mixed with its edges (a bit plane: random 0 / 1)."""
+    if w == BIT:
+        return (rng.random(n) < 0.4).astype(np.uint8)
+    dt, M = DT[w], 1 << (8 * w)
+    a = rng.integers(0, np.iinfo(dt).max, n, dtype=dt, endpoint=True)
+    edges = [0, 1, 2, M - 2, M - 1]
+    if w == 4:
+        edges += [0x7FFFFFFE, 0x7FFFFFFF, 0x80000000, 0x80000001]
+    if w == 8:
+        edges += [(1 << 32) - 1, 1 << 32, (1 << 32) + 1, (1 << 63) - 1, 1 << 63, (1 << 63) + 1, U64]
+    pick = rng.random(n) < 0.5
+    a[pick] = np.array(edges, dtype=dt)[rng.integers(0, len(edges), int(pick.sum()))]
+    a[:len(edges)] = edges                                 # every edge at least once, and at the table's both ends
+    a[n - len(edges):] = edges
+    return a
+
+
+def window_hits(x, w, lo, span, negate):
+    """The reference: the window test restated in u32 (widths 1, 2, 4, planes) or u64 (width 8) arithmetic."""
+    if w == 8:
+        hit = (x.astype(np.uint64) - np.uint64(lo)) <= np.uint64(span)
+    else:
+        hit = (x.astype(np.int64) - (lo & TOP32)) % (1 << 32) <= (span & TOP32)
+    return hit != bool(negate)
+
+
+def reference(pred, arrays, widths):
+    hits = [window_hits(arrays[pred.leaf[k].column], widths[pred.leaf[k].column], pred.leaf[k].lo, pred.leaf[k].span,
+                        pred.leaf[k].negate) for k in range(pred.n_leaves)]
+    if pred.n_leaves <= pq.TT_LEAVES:
+        idx = sum(h.astype(np.int64) << k for k, h in enumerate(hits))
+        return ((np.uint64(pred.truth) >> idx.astype(np.uint64)) & np.uint64(1)) == 1
+    state = np.zeros(len(arrays[0]), dtype=np.int64)
+    for s in range(pred.n_leaves):                          # the jump program, step by step
+        state = np.where(state == s, np.where(hits[pred.order[s]], pred.on_true[s], pred.on_false[s]), state)
+    return state == pq.ACCEPT
+
+
+def edge_predicate(rng, widths, form):
+    cats = [leaf_catalogue(w) for w in widths]
+    per = {"one": [1], "wide": [8] + [1] * (len(widths) - 1)}.get(form, [2 if len(widths) <= 2 else 1] * len(widths))
+    if form == "one":
+        widths = widths[:1]
+    leaves = []
+    for c in range(len(widths)):
+        for _ in range(per[c]):
+            lo, span = cats[c][int(rng.integers(0, len(cats[c])))]
+            leaves.append((c, int(rng.integers(0, 2)), lo, span))
+    pred = pq.Predicate()
+    k = len(leaves)
+    pred.n_leaves, pred.n_columns = k, len(widths)
+    for i, (c, neg, lo, span) in enumerate(leaves):
+        pred.leaf[i].column, pred.leaf[i].negate, pred.leaf[i].lo, pred.leaf[i].span = c, neg, lo, span
+        pred.order[i] = i
+    if k > pq.TT_LEAVES:                                    # AND / OR mixed: each step goes on, or decides
+        for s in range(k):
+            last = s + 1 == k
+            pred.on_true[s] = pq.ACCEPT if last or rng.random() < 0.3 else s + 1
+            pred.on_false[s] = pq.REJECT if last or pred.on_true[s] != pq.ACCEPT or rng.random() < 0.5 else s + 1
+        return pred
+    for i in range(k):
+        pred.on_true[i], pred.on_false[i] = pq.ACCEPT, pq.REJECT
+    rows = 1 << k
+    if form in ("and", "one"):
+        pred.truth = 1 << (rows - 1)
+    elif form == "or":
+        pred.truth = ((1 << rows) - 1) & ~1
+    else:
+        pred.truth = int(rng.integers(1, 1 << min(rows, 62))) | (1 << (rows - 1))
+    return pred
+
+
+def sweep_windows(ctx, sizes):
+    """Every byte shape, every plane shape and the generic layouts; one leaf, AND, OR, a truth-table tree and a jump program
+    of more than six leaves; scan, COUNT(*), flags, the query stream and (byte columns) the gather filter over a permuted
+    candidate range -- each against the numpy restatement, which must agree with kernel_model.evaluate as well."""
+    L = pq.lib()
+    rng = np.random.default_rng(0xED6E)
+    qs = C.c_void_p()
+    pq.check(L.pqps_qstream_create(ctx.h, 2, C.byref(qs)), "qstream")
+    cases = 0
+    for n in sizes:
+        pad = (n + pq.TILE_ROWS - 1) // pq.TILE_ROWS * pq.TILE_ROWS
+        out = Out(ctx, n + 8)
+        flags, cand, rng_dev = ctx.malloc(pad + 64), ctx.malloc(4 * pad), ctx.malloc(64)
+        perm = rng.permutation(n).astype(np.uint32)
+        ctx.upload(cand, perm.ctypes.data, perm.nbytes)
+        r0, r1 = n // 7, n - n // 5
+        ctx.upload(rng_dev, np.array([r0, r1], dtype=np.uint64).ctypes.data, 16)
+        for shape in SHAPES + PLANE_SHAPES + GENERIC_SHAPES:
+            widths = list(w for w in shape if w)
+            arrays, ptrs = [], []
+            for w in widths:
+                a = edge_column(rng, w, n)
+                if w == BIT:
+                    a_dev = np.zeros(pad // 8, dtype=np.uint8)
+                    packed = np.packbits(a, bitorder="little")
+                    a_dev[:packed.size] = packed
+                else:
+                    a_dev = np.zeros(pad, dtype=a.dtype)
+                    a_dev[:n] = a
+                p = ctx.malloc(a_dev.nbytes)
+                ctx.upload(p, a_dev.ctypes.data, a_dev.nbytes)
+                arrays.append(a)
+                ptrs.append(p)
+            cols = pq.column_array([(p, pq.WIDTH_BITS if w == BIT else w) for p, w in zip(ptrs, widths)])
+            planes = BIT in widths
+            for form in ("one", "and", "or", "tree", "wide"):
+                pred = edge_predicate(rng, widths, form)
+                nc = pred.n_columns
+                mask = reference(pred, arrays, widths)
+                assert np.array_equal(mask, kernel_model.evaluate(pred, arrays[:nc])), (shape, form)
+                want = np.nonzero(mask)[0].astype(np.uint32)
+                what = f"n={n} shape={shape} form={form} leaves={[(l.column, l.negate, hex(l.lo), hex(l.span)) for l in pred.leaf[:pred.n_leaves]]}"
+                pq.check(L.pqps_filter_scan(ctx.h, cols, nc, n, 0, C.byref(pred), out.ids, out.cap, out.count, None), what)
+                k, got = out.result()
+                if k != len(want) or not np.array_equal(got, want):
+                    sys.exit(f"DIFF scan ids: {what}: {k} vs {len(want)} matches ({pq.lib().pqps_last_kernel().decode()})")
+                pq.check(L.pqps_filter_count(ctx.h, cols, nc, n, C.byref(pred), out.count, None), what)
+                k, _ = out.result()
+                if k != len(want):
+                    sys.exit(f"DIFF count: {what}: {k} vs {len(want)} ({pq.lib().pqps_last_kernel().decode()})")
+                pq.check(L.pqps_filter_flags(ctx.h, cols, nc, n, C.byref(pred), flags, out.count, None), what)
+                k, _ = out.result()
+                f = np.zeros(n, dtype=np.uint8)
+                ctx.download(f.ctypes.data, flags, n)
+                if k != len(want) or not np.array_equal(f != 0, mask):
+                    sys.exit(f"DIFF flags: {what}: {k} vs {len(want)} ({pq.lib().pqps_last_kernel().decode()})")
+                slot = cases % 2
+                pq.check(L.pqps_qstream_scan_slot(qs, slot, cols, nc, n, 0, C.byref(pred), out.ids, out.cap, out.count, None), what)
+                pq.check(L.pqps_qstream_wait(qs, slot), "qstream wait")
+                k, got = out.result()
+                if k != len(want) or not np.array_equal(got, want):
+                    sys.exit(f"DIFF qstream ids: {what}: {k} vs {len(want)} matches")
+                if not planes:                               # the gather filter takes byte columns only
+                    ctx.memset(out.count, 0, 8)
+                    pq.check(L.pqps_filter_gather(ctx.h, cols, nc, cand, rng_dev, n, 0, C.byref(pred), out.ids, out.cap,
+                                                  out.count, None), what)
+                    k, got = out.result()
+                    exp = perm[r0:r1][mask[perm[r0:r1]]]
+                    if k != len(exp) or not np.array_equal(got, exp):
+                        sys.exit(f"DIFF gather: {what}: {k} vs {len(exp)} matches")
+                cases += 1
+            for p in ptrs:
+                ctx.free(p)
+        for p in (flags, cand, rng_dev):
+            ctx.free(p)
+        out.free()
+        print(f"windows: n={n} ok", flush=True)
+    pq.check(L.pqps_qstream_sync(qs), "qstream sync")
+    pq.check(L.pqps_qstream_destroy(qs), "qstream destroy")
+    print(f"windows: {cases} predicates x every entry point ok", flush=True)
+
+
 def main():
     mode = sys.argv[1]
     ctx = pq.Context(0)
@@ -206,10 +431,12 @@ def main():
         sweep_sizes(ctx, [int(x) for x in sys.argv[2:]] or [1, 4097, 65_537, 300_001, (1 << 21) + 17])
     elif mode == "shapes":
         sweep_shapes(ctx, int(sys.argv[2]) if len(sys.argv) > 2 else 70_001)
+    elif mode == "windows":
+        sweep_windows(ctx, [int(x) for x in sys.argv[2:]] or [70_001, (1 << 21) + 17])
     elif mode == "wrap":
         sweep_wrap(ctx, int(sys.argv[2]) if len(sys.argv) > 2 else 300_001)
     else:
-        sys.exit("usage: variant_driver.py sizes|shapes ...")
+        sys.exit("usage: variant_driver.py sizes|shapes|windows|wrap ...")
     ctx.close()
     print("OK")
 
