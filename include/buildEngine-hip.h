@@ -101,6 +101,10 @@ struct hipTable {
      * the scans read in place of the byte column.  Packed from the byte column wherever that is written (load, INSERT,
      * DELETE) by the writer that wrote it; index builds, gathers, projection and compaction keep using the byte column. */
     pqps_column sudo_bits;
+    /* Value range of the i32 columns a grouped COUNT has grouped on (executeQueryGroupCountHIP), over every shard's rows;
+     * shard 0 only, computed on first use.  INSERT widens a known range; DELETE leaves it (then possibly wider than the data). */
+    int bounds_known[HIPCOL_COUNT];
+    int32_t bounds_lo[HIPCOL_COUNT], bounds_hi[HIPCOL_COUNT];
 };
 
 #define HIP_MAX_SHARDS 16

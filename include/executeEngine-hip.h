@@ -212,6 +212,36 @@ int hipEngineProbeBoolIndexes(struct engineS *engine, int enable);
  * `rows` (may be NULL, room for that many entries) receives the rows each shard holds. */
 int hipEngineShards(struct engineS *engine, unsigned long long *rows, int capacity);
 
+/* Grouped COUNT(*): how many matching rows carry each value of one column (no aggregates in the reference; the SQL layer
+ * stays the reference's, so this is reached through the C API and the Python package only).
+ * SEMANTICS: the counts are the rows executeQuerySelectIdsHIP(engine, whereClause) returns, grouped by the value of
+ * `groupColumn` -- in index mode too, rows that several probed conditions return more than once included; `total` equals
+ * that call's count.  A NULL WHERE groups the whole table; a WHERE that matches nothing gives numGroups = 0, success = true.
+ * Groups with at least one row only, in ascending key order: numeric order for i32 columns, false before true, the
+ * dictionary's strcmp order for string columns.  keys: the i32 value, 0 / 1, or the dictionary code at the time of the query;
+ * keyText: as get_attribute_string_value (serial:216-248) formats the value (%d, true / false, the string).
+ * REFUSED (success = false, the reason on stderr): command_id (u64 and unique: grouping on it is the SELECT itself), an
+ * unknown column, more than 65 536 groups in the column's range (e.g. timestamp on a 1 M-row CSV), an engine joined across
+ * ranks (hipEngineJoinRanksHIP).  A reader like COUNT: it takes a query lane, so the lane rules above apply (a thread that
+ * holds every lane is refused at once).  Execution: a single-pass scan-mode WHERE runs ONE fused filter-and-histogram launch
+ * per shard (pqps_filter_group); index probes and WHERE lists of several passes run the selection and then
+ * pqps_group_list over each shard's list; the shards' bins are summed on the host.  i32 columns: the value range is found
+ * on first use (pqps_column_bounds) and cached with the table. */
+struct hipGroupResult {
+    int column;                        /* HIPCOL_* of the group column                                   */
+    int kind;                          /* HIPKIND_I32 / _BOOL / _DICT                                    */
+    int numGroups;                     /* groups with at least one row, ascending key order              */
+    long long total;                   /* sum of counts                                                  */
+    long long *keys;                   /* i32 value, 0/1, or dictionary code at the time of the query    */
+    char **keyText;                    /* owned copies, formatted as get_attribute_string_value would    */
+    unsigned long long *counts;
+    double queryTime;
+    bool success;
+};
+struct hipGroupResult *executeQueryGroupCountHIP(struct engineS *engine, const char *groupColumn,
+                                                 struct whereClauseS *whereClause);
+void freeGroupResultHIP(struct hipGroupResult *result);
+
 /* COUNT(*) through the backend API (the reference parser cannot express it,
  * SURVEY.md fact 10): scan-mode count of matching rows, no ID list. */
 long long executeQueryCountHIP(struct engineS *engine, struct whereClauseS *whereClause);

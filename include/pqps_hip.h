@@ -424,6 +424,28 @@ void pqps_exchange_wire_bytes(pqps_exchange *x, uint64_t out[2], int reset);
 void pqps_exchange_eager(pqps_exchange *x, uint64_t out[3], int reset);
 int pqps_exchange_destroy(pqps_exchange *x);
 
+/* ---- grouped COUNT(*): how many matching rows carry each value of one column ----------------------------------------
+ * No counterpart in the reference (its engines have no aggregates).  The BIN of a row is (value - bin_base) in 32-bit
+ * arithmetic: the dictionary code of a string column (bin_base 0), the value minus the column's minimum for an i32 column,
+ * 0 / 1 for a boolean column.  bins[0 .. n_bins) are u32 device words; rows whose bin is >= n_bins are not counted.  All three
+ * calls are asynchronous on `stream`; n_bins above 65 536 (or 0) returns PQPS_EINVAL.
+ *
+ * pqps_filter_group: COUNT(*) of `pred` over rows [0, n_rows) of `cols`, grouped by `group_col` -- ONE scan that evaluates the
+ *   WHERE and builds the histogram (the group column is read only in steps of 1024 rows that hold a match).  `group_col`
+ *   1, 2 or 4 bytes wide or a bit plane (PQPS_WIDTH_BITS).  The bins are zeroed by the call.  The readable-padding rule of
+ *   pqps_filter_scan applies to the predicate columns AND to `group_col`.  D <= 16 bins: per-lane counters; D <= 16 384: a
+ *   histogram in LDS; up to 65 536: atomics straight into the bins (slow: a path for correctness at high cardinality).
+ *   The context's timing recorder (pqps_ctx_set_timing) records the launch like a COUNT's.
+ * pqps_group_list: the same bins over an ID list -- ids[0 .. min(*count_dev, capacity)), row = id - id_base < n_rows --
+ *   by gathering `group_col` (1, 2 or 4 bytes wide, no bit plane).  The bins are zeroed by the call.
+ * pqps_column_bounds: out_dev[0] = minimum, out_dev[1] = maximum of rows [0, n_rows) of a 4-byte column read as signed i32
+ *   (device memory, two words; INT32_MAX / INT32_MIN for no rows). */
+int pqps_filter_group(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                      const pqps_column *group_col, uint32_t bin_base, uint32_t n_bins, uint32_t *bins, void *stream);
+int pqps_group_list(pqps_ctx *ctx, const pqps_column *group_col, uint64_t n_rows, const uint32_t *ids, const uint64_t *count_dev,
+                    uint64_t capacity, uint32_t id_base, uint32_t bin_base, uint32_t n_bins, uint32_t *bins, void *stream);
+int pqps_column_bounds(pqps_ctx *ctx, const pqps_column *col, uint64_t n_rows, int32_t *out_dev, void *stream);
+
 /* Checksums of a device-resident ID list: out[0] = sum of ids[i], out[1] = sum of ids[i] * (2 i + 1), both mod 2^64 (the
  * second depends on the order).  Synchronous; what a bench or a test compares two lists with without downloading them. */
 int pqps_ids_checksum(pqps_ctx *ctx, const uint32_t *ids, uint64_t count, uint64_t out[2], void *stream);

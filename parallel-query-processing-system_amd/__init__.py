@@ -97,6 +97,13 @@ class ColumnarResult(C.Structure):
                 ("queryTime", C.c_double), ("success", C.c_bool)]
 
 
+class GroupResult(C.Structure):
+    """struct hipGroupResult (include/executeEngine-hip.h)."""
+    _fields_ = [("column", C.c_int), ("kind", C.c_int), ("numGroups", C.c_int), ("total", C.c_longlong),
+                ("keys", C.POINTER(C.c_longlong)), ("keyText", C.POINTER(C.c_char_p)),
+                ("counts", C.POINTER(C.c_ulonglong)), ("queryTime", C.c_double), ("success", C.c_bool)]
+
+
 class ColumnData(C.Structure):
     """struct hipColumnData (include/executeEngine-hip.h)."""
     _fields_ = [("values", C.c_void_p), ("width", C.c_uint), ("on_device", C.c_int),
@@ -396,6 +403,13 @@ def lib():
     L.hipEngineShards.argtypes = [E, C.POINTER(C.c_ulonglong), C.c_int]
     L.executeQueryCountHIP.restype = C.c_longlong
     L.executeQueryCountHIP.argtypes = [E, W]
+    L.executeQueryGroupCountHIP.restype = C.POINTER(GroupResult)
+    L.executeQueryGroupCountHIP.argtypes = [E, C.c_char_p, W]
+    L.freeGroupResultHIP.argtypes = [C.POINTER(GroupResult)]
+    L.freeGroupResultHIP.restype = None
+    L.pqps_filter_group.argtypes = [vp, C.POINTER(Column), u32, u64, C.POINTER(Predicate), C.POINTER(Column), u32, u32, vp, vp]
+    L.pqps_group_list.argtypes = [vp, C.POINTER(Column), u64, vp, vp, u64, u32, u32, u32, vp, vp]
+    L.pqps_column_bounds.argtypes = [vp, C.POINTER(Column), u64, vp, vp]
     CR = C.POINTER(ColumnarResult)
     L.executeQuerySelectColumnarHIP.restype = CR
     L.executeQuerySelectColumnarHIP.argtypes = [E, C.POINTER(C.c_char_p), C.c_int, W]
@@ -780,6 +794,21 @@ class HipEngine:
     def count(self, chain):
         wl = WhereList(chain)
         return lib().executeQueryCountHIP(self.e, wl.ptr)
+
+    def group_count(self, column, chain=None):
+        """executeQueryGroupCountHIP: [(key_text, count), ...] in key order for the rows select_ids(chain) returns,
+        grouped by `column`.  Raises PqpsError when the engine refuses (reason on stderr)."""
+        wl = WhereList(chain)
+        res = lib().executeQueryGroupCountHIP(self.e, column.encode(), wl.ptr)
+        if not res:
+            raise PqpsError(f"group_count({column!r}): no result")
+        try:
+            r = res.contents
+            if not r.success:
+                raise PqpsError(f"group_count({column!r}) refused or failed (reason on stderr)")
+            return [(r.keyText[g].decode("latin-1"), int(r.counts[g])) for g in range(r.numGroups)]
+        finally:
+            lib().freeGroupResultHIP(res)
 
     def select(self, columns, chain):
         wl = WhereList(chain)

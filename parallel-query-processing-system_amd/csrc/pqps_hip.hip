@@ -21,6 +21,7 @@
 
 #include "pqps_hip.h"
 #include "filter_kernels.hpp"
+#include "group_kernels.hpp"
 #include "radix_sort.hpp"
 
 namespace {
@@ -507,6 +508,8 @@ struct pqps_ctx {
     long opt_list16, opt_list16_min, opt_list16_min_u8, opt_list_max, opt_list_max_u8, opt_tiny_max, opt_expand_lag, opt_sum_lag, opt_tune;
     void *sort_tmp;
     size_t sort_tmp_bytes;
+    uint32_t *group_parts;      // grouped COUNT: partial rows of the fused scan's workgroups (grown on demand)
+    size_t group_parts_words;
     // optional per-launch timing (bench.py roofline)
     bool timing;
     int timed;                  // launches recorded since the last reset
@@ -1102,6 +1105,8 @@ int create_ctx(int device, bool lane, pqps_ctx **out) {
     ctx->opt_list16 = ctx->opt_list16_min = ctx->opt_list16_min_u8 = ctx->opt_list_max = ctx->opt_list_max_u8 = ctx->opt_tiny_max = ctx->opt_expand_lag = ctx->opt_sum_lag = ctx->opt_tune = -1;
     ctx->sort_tmp = nullptr;
     ctx->sort_tmp_bytes = 0;
+    ctx->group_parts = nullptr;
+    ctx->group_parts_words = 0;
     ctx->timing = false;
     ctx->timed = 0;
     ctx->ev_start = ctx->ev_eval = ctx->ev_stop = nullptr;
@@ -1161,6 +1166,7 @@ void pqps_ctx_destroy(pqps_ctx *ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     free_scratch(ctx);
     if (ctx->sort_tmp) (void)hipFree(ctx->sort_tmp);
+    if (ctx->group_parts) (void)hipFree(ctx->group_parts);
     if (ctx->ev_start) {
         for (int i = 0; i < kMaxTimedLaunches; i++) {
             (void)hipEventDestroy(ctx->ev_start[i]); (void)hipEventDestroy(ctx->ev_eval[i]); (void)hipEventDestroy(ctx->ev_stop[i]);
@@ -2801,6 +2807,116 @@ int pqps_ids_checksum(pqps_ctx *ctx, const uint32_t *ids, uint64_t count, uint64
     }
     HIP_TRY(hipMemcpyAsync(out, ctx->check_dev, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
+    return PQPS_OK;
+}
+
+// ---- grouped COUNT(*) (group_kernels.hpp) --------------------------------------------------------------------------
+int pqps_filter_group(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                      const pqps_column *group_col, uint32_t bin_base, uint32_t n_bins, uint32_t *bins, void *stream) {
+    if (!ctx || !group_col || !bins) return fail(PQPS_EINVAL, "ctx/group_col/bins is NULL");
+    if (n_bins == 0 || n_bins > kGroupMaxBins) return fail(PQPS_EINVAL, "%u bins: 1 .. %u", n_bins, kGroupMaxBins);
+    const uint32_t gw = group_col->width;
+    if (gw != 1 && gw != 2 && gw != 4 && gw != PQPS_WIDTH_BITS) return fail(PQPS_EINVAL, "group column: width %u not in {1,2,4,bits}", gw);
+    if (!group_col->data || ((uintptr_t)group_col->data & 15u) != 0) return fail(PQPS_EINVAL, "group column: NULL or not 16-byte aligned");
+    int rc = check_pred(cols, n_cols, pred);
+    if (rc) return rc;
+    hipStream_t s = pick_stream(ctx, stream);
+    GroupArgs g;
+    memset(&g, 0, sizeof g);
+    fill_args(g.e, cols, n_cols, pred);
+    g.e.n_rows = n_rows;
+    set_streaming(g.e, cols, n_cols, n_rows);
+    HIP_TRY(hipMemsetAsync(bins, 0, (size_t)n_bins * sizeof(uint32_t), s));
+    if (n_rows == 0) return PQPS_OK;
+    const int path = n_bins <= kGroupSmallBins ? GROUP_SMALL : n_bins <= kGroupLdsBins ? GROUP_LDS : GROUP_GLOBAL;
+    // persistent grid: up to 8 workgroups per CU (the LDS path: as many as its histogram lets into 160 KiB), never more
+    // than one step per wave
+    const uint64_t steps = (n_rows + kStepRows - 1) / kStepRows;
+    const uint64_t hist_bytes = path == GROUP_LDS ? (uint64_t)n_bins * sizeof(uint32_t) : 0;
+    uint64_t per_cu = path == GROUP_LDS ? (160ull << 10) / (hist_bytes + 1024) : 8;
+    if (per_cu > 8) per_cu = 8;
+    if (per_cu < 1) per_cu = 1;
+    const uint64_t want = (steps + kWaves - 1) / kWaves;
+    const uint64_t cap = (uint64_t)ctx->compute_units * per_cu;
+    const uint32_t grid = (uint32_t)(want < cap ? want : cap);
+    const uint32_t stride = (n_bins + 63u) & ~63u;
+    if (path != GROUP_GLOBAL) {
+        const size_t words = (size_t)grid * stride;
+        if (words > ctx->group_parts_words) {
+            if (ctx->group_parts) { HIP_TRY(hipStreamSynchronize(s)); (void)hipFree(ctx->group_parts); ctx->group_parts = nullptr; ctx->group_parts_words = 0; }
+            HIP_TRY(hipMalloc((void **)&ctx->group_parts, words * sizeof(uint32_t)));
+            ctx->group_parts_words = words;
+        }
+    }
+    g.gcol = group_col->data;
+    g.bins = bins;
+    g.parts = ctx->group_parts;
+    g.stride = stride;
+    g.gwidth_log2 = gw == PQPS_WIDTH_BITS ? kWidthLog2Bits : gw == 1 ? 0u : gw == 2 ? 1u : 2u;
+    g.bin_base = bin_base;
+    g.n_bins = n_bins;
+    typedef void (*group_fn)(const GroupArgs);
+    static const group_fn fns[3][2] = {
+        {group_scan_kernel<GROUP_SMALL, false>, group_scan_kernel<GROUP_SMALL, true>},
+        {group_scan_kernel<GROUP_LDS, false>, group_scan_kernel<GROUP_LDS, true>},
+        {group_scan_kernel<GROUP_GLOBAL, false>, group_scan_kernel<GROUP_GLOBAL, true>},
+    };
+    static const char *const names[3] = {"GROUP_SMALL", "GROUP_LDS", "GROUP_GLOBAL"};
+    snprintf(g_kernel, sizeof g_kernel, "group_scan_kernel<%s, NT=%s>", names[path], g.e.streaming ? "true" : "false");
+    const group_fn k = fns[path][g.e.streaming ? 1 : 0];
+    const bool timed = ctx->timing && ctx->timed < kMaxTimedLaunches;
+    if (timed) hipExtLaunchKernelGGL(k, dim3(grid), dim3(kBlock), (uint32_t)hist_bytes, s, ctx->ev_start[ctx->timed], ctx->ev_eval[ctx->timed], 0, g);
+    else hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), (uint32_t)hist_bytes, s, g);
+    HIP_TRY(hipGetLastError());
+    if (path != GROUP_GLOBAL) {
+        const dim3 sg(stride / 64u, (grid + kGroupSumParts - 1) / kGroupSumParts);
+        if (timed) hipExtLaunchKernelGGL(group_sum_kernel, sg, dim3(kBlock), 0, s, nullptr, ctx->ev_stop[ctx->timed], 0,
+                                         (const uint32_t *)ctx->group_parts, grid, stride, n_bins, bins);
+        else hipLaunchKernelGGL(group_sum_kernel, sg, dim3(kBlock), 0, s, (const uint32_t *)ctx->group_parts, grid, stride, n_bins, bins);
+        HIP_TRY(hipGetLastError());
+    }
+    if (timed) { ctx->stop_is_eval[ctx->timed] = path == GROUP_GLOBAL; ctx->timed++; }
+    return PQPS_OK;
+}
+
+int pqps_group_list(pqps_ctx *ctx, const pqps_column *group_col, uint64_t n_rows, const uint32_t *ids, const uint64_t *count_dev,
+                    uint64_t capacity, uint32_t id_base, uint32_t bin_base, uint32_t n_bins, uint32_t *bins, void *stream) {
+    if (!ctx || !group_col || !bins || !count_dev || (capacity && !ids)) return fail(PQPS_EINVAL, "NULL argument");
+    if (n_bins == 0 || n_bins > kGroupMaxBins) return fail(PQPS_EINVAL, "%u bins: 1 .. %u", n_bins, kGroupMaxBins);
+    const uint32_t gw = group_col->width;
+    if (gw != 1 && gw != 2 && gw != 4) return fail(PQPS_EINVAL, "group column: width %u not in {1,2,4}", gw);
+    if (!group_col->data) return fail(PQPS_EINVAL, "group column: NULL data");
+    hipStream_t s = pick_stream(ctx, stream);
+    HIP_TRY(hipMemsetAsync(bins, 0, (size_t)n_bins * sizeof(uint32_t), s));
+    if (capacity == 0 || n_rows == 0) return PQPS_OK;
+    uint64_t blocks = (capacity + kBlock - 1) / kBlock;
+    const uint64_t cap = (uint64_t)ctx->compute_units * 4;
+    if (blocks > cap) blocks = cap;
+    const uint32_t wl = gw == 1 ? 0u : gw == 2 ? 1u : 2u;
+    if (n_bins <= kGroupLdsBins)
+        hipLaunchKernelGGL(group_list_kernel<true>, dim3((uint32_t)blocks), dim3(kBlock), n_bins * (uint32_t)sizeof(uint32_t), s,
+                           group_col->data, wl, n_rows, ids, count_dev, capacity, id_base, bin_base, n_bins, bins);
+    else
+        hipLaunchKernelGGL(group_list_kernel<false>, dim3((uint32_t)blocks), dim3(kBlock), 0, s,
+                           group_col->data, wl, n_rows, ids, count_dev, capacity, id_base, bin_base, n_bins, bins);
+    HIP_TRY(hipGetLastError());
+    return PQPS_OK;
+}
+
+int pqps_column_bounds(pqps_ctx *ctx, const pqps_column *col, uint64_t n_rows, int32_t *out_dev, void *stream) {
+    if (!ctx || !col || !out_dev) return fail(PQPS_EINVAL, "NULL argument");
+    if (col->width != 4 || (n_rows && !col->data)) return fail(PQPS_EINVAL, "bounds: a 4-byte column");
+    hipStream_t s = pick_stream(ctx, stream);
+    HIP_TRY(hipMemsetAsync(out_dev, 0, 2 * sizeof(int32_t), s));
+    if (n_rows) {
+        uint64_t blocks = (n_rows + kBlock - 1) / kBlock;
+        const uint64_t cap = (uint64_t)ctx->compute_units * 8;
+        if (blocks > cap) blocks = cap;
+        hipLaunchKernelGGL(group_bounds_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, s, (const int32_t *)col->data, n_rows, (uint32_t *)out_dev);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(group_bounds_finish_kernel, dim3(1), dim3(1), 0, s, (uint32_t *)out_dev);
+    HIP_TRY(hipGetLastError());
     return PQPS_OK;
 }
 

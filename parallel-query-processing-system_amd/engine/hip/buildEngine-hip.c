@@ -924,7 +924,13 @@ bool appendRowDeviceTableHIP(struct engineS *engine, const record *r) {
         const char *p = (const char *)r + k_offset[c];
         switch (k_kind[c]) {
         case HIPKIND_U64: value = *(const uint64_t *)p; break;
-        case HIPKIND_I32: value = (uint32_t)*(const int *)p; break;
+        case HIPKIND_I32:
+            value = (uint32_t)*(const int *)p;
+            if (t->bounds_known[c]) {                           /* a cached group range covers the new row */
+                if (*(const int *)p < t->bounds_lo[c]) t->bounds_lo[c] = *(const int *)p;
+                if (*(const int *)p > t->bounds_hi[c]) t->bounds_hi[c] = *(const int *)p;
+            }
+            break;
         case HIPKIND_BOOL: value = *(const bool *)p ? 1 : 0; break;
         default: {
             struct hipDictionary *d = &t->dict[c];

@@ -195,6 +195,7 @@ struct query {
     const uint32_t *ids_dev;
     pqps_ctx *ids_ctx;                   /* a context of the device ids_dev lives on (downloads) */
     bool exchanged;                      /* issued through the ranks' exchange: the answer is the exchange slot's */
+    bool per_shard;                      /* several shards: leave each shard's list on its device (grouped COUNT) */
 };
 
 static struct hipLane *query_lane(const struct query *q, int s) {
@@ -484,7 +485,7 @@ static int query_await(struct query *q) {
         if (query_issue_all(q) != 0) return -1;
     }
     if (q->count_only) return 0;
-    if (q->n_shards == 1) {
+    if (q->n_shards == 1 || q->per_shard) {
         q->ids_dev = query_lane(q, 0)->ids_dev;
         q->ids_ctx = lane_copy_ctx(q, 0);
         return 0;
@@ -700,6 +701,213 @@ long long executeQueryCountHIP(struct engineS *engine, struct whereClauseS *wher
     const long long count = awaitQueryHIP(tk, NULL);
     releaseQueryHIP(tk);
     return count;
+}
+
+/* ---- grouped COUNT(*) (include/executeEngine-hip.h) --------------------------------------------------------------- */
+
+static const int k_group_kind[HIPCOL_COUNT] = {
+    HIPKIND_U64, HIPKIND_DICT, HIPKIND_DICT, HIPKIND_DICT, HIPKIND_I32, HIPKIND_DICT,
+    HIPKIND_BOOL, HIPKIND_DICT, HIPKIND_I32, HIPKIND_DICT, HIPKIND_DICT, HIPKIND_I32
+};
+#define HIP_GROUP_MAX_BINS 65536ull
+
+/* [lo, hi] of an i32 column over every shard, computed once (pqps_column_bounds on each shard) and cached with the table.
+ * Readers hold the table shared: two of them may come here at once. */
+static pthread_mutex_t g_bounds_lock = PTHREAD_MUTEX_INITIALIZER;
+
+static int column_bounds(struct query *q, int c, int32_t *lo, int32_t *hi) {
+    struct hipTable *t = q->t;
+    int rc = 0;
+    pthread_mutex_lock(&g_bounds_lock);
+    if (!t->bounds_known[c]) {
+        int32_t l = INT_MAX, h = INT_MIN;
+        for (int s = 0; s < q->n_shards && rc == 0; s++) {
+            struct hipTable *sh = hipTableShard(t, s);
+            if (sh->n_rows == 0) continue;
+            pqps_ctx *cs = lane_copy_ctx(q, s);
+            int32_t *out_dev = NULL, out[2];
+            if (pqps_malloc(sh->ctx, 2 * sizeof(int32_t), (void **)&out_dev) != PQPS_OK) { rc = engine_error("bounds buffer"); break; }
+            if (pqps_column_bounds(cs, &sh->col[c], sh->n_rows, out_dev, NULL) != PQPS_OK ||
+                pqps_download(cs, out, out_dev, sizeof out, NULL) != PQPS_OK)
+                rc = engine_error("column bounds");
+            pqps_free(sh->ctx, out_dev);
+            if (rc == 0) { if (out[0] < l) l = out[0]; if (out[1] > h) h = out[1]; }
+        }
+        if (rc == 0) { t->bounds_lo[c] = l; t->bounds_hi[c] = h; t->bounds_known[c] = 1; }
+    }
+    *lo = t->bounds_lo[c];
+    *hi = t->bounds_hi[c];
+    pthread_mutex_unlock(&g_bounds_lock);
+    return rc;
+}
+
+/* The bins of the query on every shard, summed into counts[0 .. n_bins) on the host.  `fused`: one pqps_filter_group launch
+ * per shard on the query's lane; otherwise the selection (query_issue_all + query_await, each shard's list left on its own
+ * device) and pqps_group_list over every list.  `gcol[s]`: shard s's group column. */
+static int group_bins(struct query *q, bool fused, const pqps_column *gcol, uint32_t bin_base, uint32_t n_bins, uint64_t *counts) {
+    uint32_t *bins_dev[HIP_MAX_SHARDS] = { NULL };
+    uint32_t *host = malloc((size_t)n_bins * sizeof *host);
+    int rc = host ? 0 : -1;
+    if (!host) fprintf(stderr, "HIP engine: out of memory\n");
+    for (int s = 0; s < q->n_shards && rc == 0; s++)
+        if (pqps_malloc(hipTableShard(q->t, s)->ctx, (size_t)n_bins * sizeof(uint32_t), (void **)&bins_dev[s]) != PQPS_OK) rc = engine_error("bins allocation");
+    if (rc == 0 && fused) {
+        const struct hipPass *last = &q->plan.pass[0];
+        hipTableLockIssue(q->t);
+        for (int s = 0; s < q->n_shards && rc == 0; s++) {
+            struct hipTable *sh = hipTableShard(q->t, s);
+            struct shard_pred *sp = &q->sp[s];
+            pqps_ctx *ctx = sh->ctx;
+            void *stream = NULL;
+            if (sh->n_rows == 0) continue;
+            if (q->lane >= 0 && pqps_qstream_lane(sh->qs, (uint32_t)q->lane, sh->n_rows, NULL, &ctx, &stream) != PQPS_OK) { rc = engine_error("query lane"); break; }
+            sp->pred = &last->pred;
+            sp->n_cols = last->pred.n_columns;
+            pass_columns(sh, last, NULL, true, sp->cols);
+            if (pqps_filter_group(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, &gcol[s], bin_base, n_bins, bins_dev[s], stream) != PQPS_OK)
+                rc = engine_error("group filter");
+            /* marked even after a failed call: the lane must not be handed on while a launch of this query runs */
+            if (q->lane >= 0 && pqps_qstream_mark(sh->qs, (uint32_t)q->lane) != PQPS_OK && rc == 0) rc = engine_error("query lane");
+        }
+        hipTableUnlockIssue(q->t);
+        for (int s = 0; s < q->n_shards; s++) if (wait_shard(q, s) != 0 && rc == 0) rc = -1;
+        for (int s = 0; s < q->n_shards && rc == 0; s++)
+            if (hipTableShard(q->t, s)->n_rows == 0) continue;
+            else if (pqps_download(lane_copy_ctx(q, s), host, bins_dev[s], (size_t)n_bins * sizeof *host, NULL) != PQPS_OK) rc = engine_error("bins download");
+            else for (uint32_t k = 0; k < n_bins; k++) counts[k] += host[k];
+    } else if (rc == 0) {
+        q->per_shard = true;
+        rc = query_issue_all(q);
+        if (rc == 0) rc = query_await(q);
+        for (int s = 0; s < q->n_shards && rc == 0; s++) {
+            struct hipTable *sh = hipTableShard(q->t, s);
+            struct hipLane *L = query_lane(q, s);
+            pqps_ctx *cs = lane_copy_ctx(q, s);
+            if (q->count[s] == 0) continue;
+            if (pqps_group_list(cs, &gcol[s], sh->n_rows, L->ids_dev, L->count_dev, q->count[s], (uint32_t)sh->row0, bin_base, n_bins, bins_dev[s], NULL) != PQPS_OK ||
+                pqps_download(cs, host, bins_dev[s], (size_t)n_bins * sizeof *host, NULL) != PQPS_OK)
+                rc = engine_error("group list");
+            else for (uint32_t k = 0; k < n_bins; k++) counts[k] += host[k];
+        }
+    }
+    for (int s = 0; s < q->n_shards; s++) if (bins_dev[s]) pqps_free(hipTableShard(q->t, s)->ctx, bins_dev[s]);
+    free(host);
+    return rc;
+}
+
+static int group_result_fill(struct hipGroupResult *res, const struct hipTable *t, const uint64_t *counts, uint32_t n_bins, int32_t lo) {
+    int n = 0;
+    for (uint32_t k = 0; k < n_bins; k++) n += counts[k] != 0;
+    res->keys = calloc((size_t)n + 1, sizeof *res->keys);
+    res->keyText = calloc((size_t)n + 1, sizeof *res->keyText);
+    res->counts = calloc((size_t)n + 1, sizeof *res->counts);
+    if (!res->keys || !res->keyText || !res->counts) { fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
+    int g = 0;
+    for (uint32_t k = 0; k < n_bins; k++) {
+        if (!counts[k]) continue;
+        char buf[32];
+        const char *text = buf;
+        if (res->kind == HIPKIND_I32) { res->keys[g] = (long long)lo + (long long)k; snprintf(buf, sizeof buf, "%d", (int)res->keys[g]); }
+        else if (res->kind == HIPKIND_BOOL) { res->keys[g] = k; text = k ? "true" : "false"; }
+        else { res->keys[g] = k; text = t->dict[res->column].values[k]; }
+        res->keyText[g] = strdup(text);
+        if (!res->keyText[g]) { fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
+        res->counts[g] = counts[k];
+        res->total += (long long)counts[k];
+        g++;
+    }
+    res->numGroups = n;
+    return 0;
+}
+
+struct hipGroupResult *executeQueryGroupCountHIP(struct engineS *engine, const char *groupColumn, struct whereClauseS *whereClause) {
+    const double t0 = now_seconds();
+    struct hipGroupResult *res = calloc(1, sizeof *res);
+    if (!res) { fprintf(stderr, "HIP engine: out of memory\n"); return NULL; }
+    res->column = -1;
+    res->kind = -1;
+    if (!engine || !engine->record_block || !groupColumn) { fprintf(stderr, "HIP engine: grouped COUNT without an engine or a column\n"); return res; }
+    const int c = hipColumnId(groupColumn);
+    if (c < 0) { fprintf(stderr, "HIP engine: grouped COUNT: unknown column '%s'\n", groupColumn); return res; }
+    if (c == HIPCOL_COMMAND_ID) { fprintf(stderr, "HIP engine: grouped COUNT: command_id is unique -- grouping on it is the SELECT\n"); return res; }
+    struct hipTable *t = engine->record_block;
+    if (t->xch) { fprintf(stderr, "HIP engine: grouped COUNT is not exchanged across ranks\n"); return res; }
+    res->column = c;
+    res->kind = k_group_kind[c];
+    hipTableLockShared(t);
+    const int lane = hipTableAcquireLane(t);
+    if (lane == HIP_LANE_REFUSED) { hipTableUnlockShared(t); return res; }  /* reason on stderr */
+    struct query q;
+    query_init(&q, engine, t, lane, false);
+    uint64_t *counts = NULL;
+    int rc = bind_where(t, whereClause, &q.plan);
+    q.have_plan = rc == 0;
+    if (rc == 0) {
+        q.n_probes = list_probes(engine, t, whereClause, &q.probes);
+        if (q.n_probes < 0) { q.n_probes = 0; rc = -1; }
+    }
+    /* bins: codes of a dictionary (none for a single-valued column: every row is bin 0), 0 / 1, or the i32 range */
+    uint32_t n_bins = 1, bin_base = 0;
+    int32_t lo = 0, hi = -1;
+    bool single = false, empty = false;
+    uint64_t rows = 0;
+    for (int s = 0; s < q.n_shards; s++) rows += hipTableShard(t, s)->n_rows;
+    if (rc == 0 && rows == 0) empty = true;                              /* an empty table: no groups */
+    else if (rc == 0) {
+        if (res->kind == HIPKIND_DICT) {
+            n_bins = t->dict[c].count > 0 ? (uint32_t)t->dict[c].count : 1u;
+            single = t->col[c].width == 0;
+        } else if (res->kind == HIPKIND_BOOL) {
+            n_bins = 2;
+        } else if ((rc = column_bounds(&q, c, &lo, &hi)) == 0) {
+            if (lo > hi) empty = true;                                   /* no rows at all */
+            else if ((uint64_t)((int64_t)hi - (int64_t)lo) + 1u > HIP_GROUP_MAX_BINS) {
+                fprintf(stderr, "HIP engine: grouped COUNT: %s spans %lld values, more than %llu groups\n", groupColumn,
+                        (long long)hi - (long long)lo + 1, HIP_GROUP_MAX_BINS);
+                rc = -1;
+            } else {
+                n_bins = (uint32_t)((int64_t)hi - (int64_t)lo + 1);
+                bin_base = (uint32_t)lo;
+            }
+        }
+    }
+    if (rc == 0 && !empty) {
+        counts = calloc(n_bins, sizeof *counts);
+        if (!counts) { fprintf(stderr, "HIP engine: out of memory\n"); rc = -1; }
+    }
+    if (rc == 0 && !empty) {
+        if (single) {
+            /* one value: the number of rows the selection returns (scan mode: the count, no list) */
+            q.count_only = q.n_probes == 0;
+            rc = query_issue_all(&q);
+            if (rc == 0) rc = query_await(&q);
+            if (rc == 0) counts[0] = q.total;
+        } else {
+            pqps_column gcol[HIP_MAX_SHARDS];
+            const bool fused = q.plan.n_passes == 1 && q.n_probes == 0;
+            for (int s = 0; s < q.n_shards; s++) {
+                const struct hipTable *sh = hipTableShard(t, s);
+                gcol[s] = fused && c == HIPCOL_SUDO_USED && sh->sudo_bits.data ? sh->sudo_bits : sh->col[c];
+            }
+            rc = group_bins(&q, fused, gcol, bin_base, n_bins, counts);
+        }
+    }
+    if (rc == 0 && group_result_fill(res, t, counts ? counts : (uint64_t[1]){ 0 }, empty ? 0u : n_bins, lo) == 0) res->success = true;
+    free(counts);
+    query_free(&q);
+    hipTableReleaseLane(t, lane);
+    hipTableUnlockShared(t);
+    res->queryTime = now_seconds() - t0;
+    return res;
+}
+
+void freeGroupResultHIP(struct hipGroupResult *res) {
+    if (!res) return;
+    for (int g = 0; g < res->numGroups && res->keyText; g++) free(res->keyText[g]);
+    free(res->keyText);
+    free(res->keys);
+    free(res->counts);
+    free(res);
 }
 
 /* ---- projection ------------------------------------------------------------------ */
