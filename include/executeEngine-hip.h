@@ -242,6 +242,40 @@ struct hipGroupResult *executeQueryGroupCountHIP(struct engineS *engine, const c
                                                  struct whereClauseS *whereClause);
 void freeGroupResultHIP(struct hipGroupResult *result);
 
+/* COUNT, SUM, MIN and MAX of one numeric column, overall or per group (no aggregates in the reference; reached through the
+ * C API and the Python package only, like the grouped COUNT above).
+ * ROWS: exactly the rows executeQuerySelectIdsHIP(engine, whereClause) returns -- in index mode too, so a row several probed
+ * conditions return more than once is counted and added that many times, as in executeQueryGroupCountHIP; `total` equals
+ * that call's count.
+ * NO GROUP BY (groupColumn == NULL): one group over all those rows -- numGroups is 1 if any row matches and 0 otherwise;
+ * keys and keyText are NULL, groupColumn and groupKind are -1.
+ * GROUP BY: the groups, keys, key text and key order of executeQueryGroupCountHIP for the same column and WHERE, and
+ * counts[g] equals its count.
+ * VALUES: exit_code, user_id, risk_level (HIPKIND_I32): sums exact in int64 (no overflow below 2^32 rows), min / max signed.
+ * command_id (HIPKIND_U64): the sum is modulo 2^64, min / max unsigned, all three returned as the u64 bits in the long long
+ * fields (valueKind says which).  There is no AVG on the device: AVG is sums[g] / counts[g].
+ * REFUSED (success = false, the reason on stderr): a dictionary or boolean value column, an unknown value or group column,
+ * and every group-column refusal of executeQueryGroupCountHIP (command_id, more than 65 536 groups, an engine joined across
+ * ranks -- with or without GROUP BY).  A reader like COUNT: shared lock and one query lane; the lane rules above apply.
+ * Execution: as executeQueryGroupCountHIP -- a single-pass scan-mode WHERE runs ONE fused filter-and-aggregate launch per
+ * shard (pqps_filter_aggregate), everything else the selection and then pqps_aggregate_list over each shard's list; shards
+ * are combined on the host.  An empty table, or a WHERE that matches nothing, gives numGroups = 0 with success = true. */
+struct hipAggregateResult {
+    int valueColumn, valueKind;        /* HIPCOL_*, HIPKIND_I32 / HIPKIND_U64                            */
+    int groupColumn, groupKind;        /* HIPCOL_*, HIPKIND_*; -1 / -1 without GROUP BY                  */
+    int numGroups;
+    long long total;                   /* sum of counts = executeQuerySelectIdsHIP's count               */
+    long long *keys;                   /* as hipGroupResult; NULL without GROUP BY                       */
+    char **keyText;                    /* as hipGroupResult; NULL without GROUP BY                       */
+    unsigned long long *counts;
+    long long *sums, *mins, *maxs;     /* u64 bits when valueKind == HIPKIND_U64                         */
+    double queryTime;
+    bool success;
+};
+struct hipAggregateResult *executeQueryAggregateHIP(struct engineS *engine, const char *valueColumn, const char *groupColumn,
+                                                    struct whereClauseS *whereClause);
+void freeAggregateResultHIP(struct hipAggregateResult *result);
+
 /* COUNT(*) through the backend API (the reference parser cannot express it,
  * SURVEY.md fact 10): scan-mode count of matching rows, no ID list. */
 long long executeQueryCountHIP(struct engineS *engine, struct whereClauseS *whereClause);

@@ -446,6 +446,31 @@ int pqps_group_list(pqps_ctx *ctx, const pqps_column *group_col, uint64_t n_rows
                     uint64_t capacity, uint32_t id_base, uint32_t bin_base, uint32_t n_bins, uint32_t *bins, void *stream);
 int pqps_column_bounds(pqps_ctx *ctx, const pqps_column *col, uint64_t n_rows, int32_t *out_dev, void *stream);
 
+/* ---- COUNT / SUM / MIN / MAX of a value column, overall or per group ------------------------------------------------
+ * No counterpart in the reference.  `value_col`: 4 bytes (read as signed i32) or 8 bytes (read as u64); a bit plane or a
+ * byte column is never a value.  OUTPUT per call (one shard): out[4 * n_bins] u64 device words, field-major --
+ *   out[0 * n_bins + b]  count of the matching rows of bin b
+ *   out[1 * n_bins + b]  sum of their values, sign-extended (i32) or as is (u64), mod 2^64
+ *   out[2 * n_bins + b]  minimum of their IMAGES, out[3 * n_bins + b] maximum: the image of an i32 value v is
+ *                        (uint64_t)(int64_t)v ^ 2^63, of a u64 value the value itself (unsigned order either way)
+ * A bin without rows reads count 0, sum 0, min image UINT64_MAX, max image 0.  The bins are those of pqps_filter_group
+ * ((value - bin_base) in 32-bit arithmetic, rows whose bin is >= n_bins are left out); `group_col` NULL means no GROUP BY:
+ * n_bins must be 1 and every matching row is bin 0.  The calls initialise `out` themselves and are asynchronous on `stream`.
+ *
+ * pqps_filter_aggregate: ONE scan of `pred` over rows [0, n_rows) of `cols` (the value column, and the group column, are
+ *   read only in steps of 1024 rows that hold a match).  `group_col` 1, 2 or 4 bytes wide or a bit plane.  The readable-
+ *   padding rule of pqps_filter_scan applies to the predicate columns, `value_col` and `group_col`.  No GROUP BY: per-lane
+ *   registers; D <= 2304 bins: a table in LDS; up to 65 536: atomics straight into `out` (slow: a correctness path).  The
+ *   context's timing recorder records the launch like a COUNT's.
+ * pqps_aggregate_list: the same over an ID list -- ids[0 .. min(*count_dev, capacity)), row = id - id_base < n_rows --
+ *   gathering `value_col` and `group_col` (1, 2 or 4 bytes wide, no bit plane) per listed row. */
+int pqps_filter_aggregate(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                          const pqps_column *value_col, const pqps_column *group_col, uint32_t bin_base, uint32_t n_bins,
+                          uint64_t *out, void *stream);
+int pqps_aggregate_list(pqps_ctx *ctx, const pqps_column *value_col, const pqps_column *group_col, uint64_t n_rows,
+                        const uint32_t *ids, const uint64_t *count_dev, uint64_t capacity, uint32_t id_base, uint32_t bin_base,
+                        uint32_t n_bins, uint64_t *out, void *stream);
+
 /* Checksums of a device-resident ID list: out[0] = sum of ids[i], out[1] = sum of ids[i] * (2 i + 1), both mod 2^64 (the
  * second depends on the order).  Synchronous; what a bench or a test compares two lists with without downloading them. */
 int pqps_ids_checksum(pqps_ctx *ctx, const uint32_t *ids, uint64_t count, uint64_t out[2], void *stream);

@@ -32,6 +32,7 @@ TILE_ROWS = 4096
 SLOT_HEADER_WORDS = 4
 ACCEPT, REJECT = 0xFE, 0xFF
 WIDTH_BITS = 0x81                  # pqps_column.width of a bit plane (PQPS_WIDTH_BITS)
+HIPKIND_U64, HIPKIND_I32, HIPKIND_BOOL, HIPKIND_DICT = 0, 1, 2, 3     # include/hipPredicate.h
 SYNTH_USERS = 2000
 
 COLUMNS = ["command_id", "raw_command", "base_command", "shell_type", "exit_code", "timestamp",
@@ -102,6 +103,15 @@ class GroupResult(C.Structure):
     _fields_ = [("column", C.c_int), ("kind", C.c_int), ("numGroups", C.c_int), ("total", C.c_longlong),
                 ("keys", C.POINTER(C.c_longlong)), ("keyText", C.POINTER(C.c_char_p)),
                 ("counts", C.POINTER(C.c_ulonglong)), ("queryTime", C.c_double), ("success", C.c_bool)]
+
+
+class AggregateResult(C.Structure):
+    """struct hipAggregateResult (include/executeEngine-hip.h)."""
+    _fields_ = [("valueColumn", C.c_int), ("valueKind", C.c_int), ("groupColumn", C.c_int), ("groupKind", C.c_int),
+                ("numGroups", C.c_int), ("total", C.c_longlong),
+                ("keys", C.POINTER(C.c_longlong)), ("keyText", C.POINTER(C.c_char_p)), ("counts", C.POINTER(C.c_ulonglong)),
+                ("sums", C.POINTER(C.c_longlong)), ("mins", C.POINTER(C.c_longlong)), ("maxs", C.POINTER(C.c_longlong)),
+                ("queryTime", C.c_double), ("success", C.c_bool)]
 
 
 class ColumnData(C.Structure):
@@ -410,6 +420,13 @@ def lib():
     L.pqps_filter_group.argtypes = [vp, C.POINTER(Column), u32, u64, C.POINTER(Predicate), C.POINTER(Column), u32, u32, vp, vp]
     L.pqps_group_list.argtypes = [vp, C.POINTER(Column), u64, vp, vp, u64, u32, u32, u32, vp, vp]
     L.pqps_column_bounds.argtypes = [vp, C.POINTER(Column), u64, vp, vp]
+    L.executeQueryAggregateHIP.restype = C.POINTER(AggregateResult)
+    L.executeQueryAggregateHIP.argtypes = [E, C.c_char_p, C.c_char_p, W]
+    L.freeAggregateResultHIP.argtypes = [C.POINTER(AggregateResult)]
+    L.freeAggregateResultHIP.restype = None
+    L.pqps_filter_aggregate.argtypes = [vp, C.POINTER(Column), u32, u64, C.POINTER(Predicate), C.POINTER(Column), C.POINTER(Column),
+                                        u32, u32, vp, vp]
+    L.pqps_aggregate_list.argtypes = [vp, C.POINTER(Column), C.POINTER(Column), u64, vp, vp, u64, u32, u32, u32, vp, vp]
     CR = C.POINTER(ColumnarResult)
     L.executeQuerySelectColumnarHIP.restype = CR
     L.executeQuerySelectColumnarHIP.argtypes = [E, C.POINTER(C.c_char_p), C.c_int, W]
@@ -809,6 +826,30 @@ class HipEngine:
             return [(r.keyText[g].decode("latin-1"), int(r.counts[g])) for g in range(r.numGroups)]
         finally:
             lib().freeGroupResultHIP(res)
+
+    def aggregate(self, value_column, group_column=None, chain=None):
+        """executeQueryAggregateHIP: [(key_text, count, sum, min, max), ...] of `value_column` over the rows select_ids(chain)
+        returns -- in the key order of group_count(group_column, chain), or one entry with key_text None without a group
+        column (none when no row matches).  Python ints; command_id's sum (mod 2^64), min and max are unsigned.  Raises
+        PqpsError when the engine refuses (reason on stderr)."""
+        wl = WhereList(chain)
+        res = lib().executeQueryAggregateHIP(self.e, value_column.encode(), group_column.encode() if group_column else None, wl.ptr)
+        what = f"aggregate({value_column!r}, {group_column!r})"
+        if not res:
+            raise PqpsError(f"{what}: no result")
+        try:
+            r = res.contents
+            if not r.success:
+                raise PqpsError(f"{what} refused or failed (reason on stderr)")
+            fix = (lambda x: x & 0xFFFFFFFFFFFFFFFF) if r.valueKind == HIPKIND_U64 else int
+            return [(r.keyText[g].decode("latin-1") if r.groupColumn >= 0 else None, int(r.counts[g]),
+                     fix(r.sums[g]), fix(r.mins[g]), fix(r.maxs[g])) for g in range(r.numGroups)]
+        finally:
+            lib().freeAggregateResultHIP(res)
+
+    def average(self, value_column, group_column=None, chain=None):
+        """AVG as sum / count of aggregate(): [(key_text, avg), ...] (the device computes no AVG)."""
+        return [(k, s / c) for k, c, s, _, _ in self.aggregate(value_column, group_column, chain)]
 
     def select(self, columns, chain):
         wl = WhereList(chain)

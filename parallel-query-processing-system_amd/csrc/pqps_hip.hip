@@ -22,6 +22,7 @@
 #include "pqps_hip.h"
 #include "filter_kernels.hpp"
 #include "group_kernels.hpp"
+#include "aggregate_kernels.hpp"
 #include "radix_sort.hpp"
 
 namespace {
@@ -508,7 +509,7 @@ struct pqps_ctx {
     long opt_list16, opt_list16_min, opt_list16_min_u8, opt_list_max, opt_list_max_u8, opt_tiny_max, opt_expand_lag, opt_sum_lag, opt_tune;
     void *sort_tmp;
     size_t sort_tmp_bytes;
-    uint32_t *group_parts;      // grouped COUNT: partial rows of the fused scan's workgroups (grown on demand)
+    uint32_t *group_parts;      // grouped COUNT / aggregates: partial rows of the fused scan's workgroups (grown on demand)
     size_t group_parts_words;
     // optional per-launch timing (bench.py roofline)
     bool timing;
@@ -2811,6 +2812,15 @@ int pqps_ids_checksum(pqps_ctx *ctx, const uint32_t *ids, uint64_t count, uint64
 }
 
 // ---- grouped COUNT(*) (group_kernels.hpp) --------------------------------------------------------------------------
+// ctx->group_parts holds at least `words` u32 words (the fused scans' partial rows)
+static int grow_group_parts(pqps_ctx *ctx, hipStream_t s, size_t words) {
+    if (words <= ctx->group_parts_words) return PQPS_OK;
+    if (ctx->group_parts) { HIP_TRY(hipStreamSynchronize(s)); (void)hipFree(ctx->group_parts); ctx->group_parts = nullptr; ctx->group_parts_words = 0; }
+    HIP_TRY(hipMalloc((void **)&ctx->group_parts, words * sizeof(uint32_t)));
+    ctx->group_parts_words = words;
+    return PQPS_OK;
+}
+
 int pqps_filter_group(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
                       const pqps_column *group_col, uint32_t bin_base, uint32_t n_bins, uint32_t *bins, void *stream) {
     if (!ctx || !group_col || !bins) return fail(PQPS_EINVAL, "ctx/group_col/bins is NULL");
@@ -2841,12 +2851,8 @@ int pqps_filter_group(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, u
     const uint32_t grid = (uint32_t)(want < cap ? want : cap);
     const uint32_t stride = (n_bins + 63u) & ~63u;
     if (path != GROUP_GLOBAL) {
-        const size_t words = (size_t)grid * stride;
-        if (words > ctx->group_parts_words) {
-            if (ctx->group_parts) { HIP_TRY(hipStreamSynchronize(s)); (void)hipFree(ctx->group_parts); ctx->group_parts = nullptr; ctx->group_parts_words = 0; }
-            HIP_TRY(hipMalloc((void **)&ctx->group_parts, words * sizeof(uint32_t)));
-            ctx->group_parts_words = words;
-        }
+        rc = grow_group_parts(ctx, s, (size_t)grid * stride);
+        if (rc) return rc;
     }
     g.gcol = group_col->data;
     g.bins = bins;
@@ -2916,6 +2922,124 @@ int pqps_column_bounds(pqps_ctx *ctx, const pqps_column *col, uint64_t n_rows, i
         HIP_TRY(hipGetLastError());
     }
     hipLaunchKernelGGL(group_bounds_finish_kernel, dim3(1), dim3(1), 0, s, (uint32_t *)out_dev);
+    HIP_TRY(hipGetLastError());
+    return PQPS_OK;
+}
+
+// ---- COUNT / SUM / MIN / MAX of a value column (aggregate_kernels.hpp) -----------------------------------------------
+static int check_aggregate_cols(const pqps_column *value_col, const pqps_column *group_col, uint32_t n_bins, bool plane_ok) {
+    if (!value_col) return fail(PQPS_EINVAL, "value column is NULL");
+    if (value_col->width != 4 && value_col->width != 8) return fail(PQPS_EINVAL, "value column: width %u not in {4,8}", value_col->width);
+    if (!value_col->data || ((uintptr_t)value_col->data & 15u) != 0) return fail(PQPS_EINVAL, "value column: NULL or not 16-byte aligned");
+    if (!group_col) return n_bins == 1 ? PQPS_OK : fail(PQPS_EINVAL, "no group column: 1 bin, not %u", n_bins);
+    if (n_bins == 0 || n_bins > kGroupMaxBins) return fail(PQPS_EINVAL, "%u bins: 1 .. %u", n_bins, kGroupMaxBins);
+    const uint32_t gw = group_col->width;
+    if (gw != 1 && gw != 2 && gw != 4 && !(plane_ok && gw == PQPS_WIDTH_BITS))
+        return fail(PQPS_EINVAL, "group column: width %u not in {1,2,4%s}", gw, plane_ok ? ",bits" : "");
+    if (!group_col->data || ((uintptr_t)group_col->data & 15u) != 0) return fail(PQPS_EINVAL, "group column: NULL or not 16-byte aligned");
+    return PQPS_OK;
+}
+
+// out[4][n_bins]: counts and sums 0, min images ~0, max images 0
+static int init_aggregate_out(uint64_t *out, uint32_t n_bins, hipStream_t s) {
+    HIP_TRY(hipMemsetAsync(out, 0, (size_t)kAggFields * n_bins * sizeof(uint64_t), s));
+    HIP_TRY(hipMemsetAsync(out + 2 * (size_t)n_bins, 0xFF, (size_t)n_bins * sizeof(uint64_t), s));
+    return PQPS_OK;
+}
+
+int pqps_filter_aggregate(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                          const pqps_column *value_col, const pqps_column *group_col, uint32_t bin_base, uint32_t n_bins,
+                          uint64_t *out, void *stream) {
+    if (!ctx || !out) return fail(PQPS_EINVAL, "ctx/out is NULL");
+    int rc = check_aggregate_cols(value_col, group_col, n_bins, true);
+    if (rc) return rc;
+    rc = check_pred(cols, n_cols, pred);
+    if (rc) return rc;
+    hipStream_t s = pick_stream(ctx, stream);
+    AggArgs g;
+    memset(&g, 0, sizeof g);
+    fill_args(g.e, cols, n_cols, pred);
+    g.e.n_rows = n_rows;
+    set_streaming(g.e, cols, n_cols, n_rows);
+    rc = init_aggregate_out(out, n_bins, s);
+    if (rc || n_rows == 0) return rc;
+    const int path = !group_col ? AGG_ONE : n_bins <= kAggLdsBins ? AGG_LDS : AGG_GLOBAL;
+    // persistent grid as pqps_filter_group's: up to 8 workgroups per CU (the LDS path: as many as its table lets into
+    // 160 KiB), never more than one step per wave
+    const uint64_t steps = (n_rows + kStepRows - 1) / kStepRows;
+    const uint64_t table_bytes = path == AGG_LDS ? (uint64_t)n_bins * (3 * sizeof(uint64_t) + sizeof(uint32_t)) : 0;
+    uint64_t per_cu = path == AGG_LDS ? (160ull << 10) / (table_bytes + 1024) : 8;
+    if (per_cu > 8) per_cu = 8;
+    if (per_cu < 1) per_cu = 1;
+    const uint64_t want = (steps + kWaves - 1) / kWaves;
+    const uint64_t cap = (uint64_t)ctx->compute_units * per_cu;
+    const uint32_t grid = (uint32_t)(want < cap ? want : cap);
+    if (path != AGG_GLOBAL) {
+        rc = grow_group_parts(ctx, s, (size_t)grid * kAggFields * n_bins * 2);
+        if (rc) return rc;
+    }
+    const uint32_t gw = group_col ? group_col->width : 1;
+    g.vcol = value_col->data;
+    g.gcol = group_col ? group_col->data : nullptr;
+    g.out = out;
+    g.parts = (uint64_t *)ctx->group_parts;
+    g.gwidth_log2 = gw == PQPS_WIDTH_BITS ? kWidthLog2Bits : gw == 1 ? 0u : gw == 2 ? 1u : 2u;
+    g.bin_base = bin_base;
+    g.n_bins = n_bins;
+    const bool u64 = value_col->width == 8;
+    typedef void (*agg_fn)(const AggArgs);
+    static const agg_fn fns[3][2][2] = {
+        {{agg_scan_kernel<AGG_ONE, false, false>, agg_scan_kernel<AGG_ONE, false, true>},
+         {agg_scan_kernel<AGG_ONE, true, false>, agg_scan_kernel<AGG_ONE, true, true>}},
+        {{agg_scan_kernel<AGG_LDS, false, false>, agg_scan_kernel<AGG_LDS, false, true>},
+         {agg_scan_kernel<AGG_LDS, true, false>, agg_scan_kernel<AGG_LDS, true, true>}},
+        {{agg_scan_kernel<AGG_GLOBAL, false, false>, agg_scan_kernel<AGG_GLOBAL, false, true>},
+         {agg_scan_kernel<AGG_GLOBAL, true, false>, agg_scan_kernel<AGG_GLOBAL, true, true>}},
+    };
+    static const char *const names[3] = {"AGG_ONE", "AGG_LDS", "AGG_GLOBAL"};
+    snprintf(g_kernel, sizeof g_kernel, "agg_scan_kernel<%s, %s, NT=%s>", names[path], u64 ? "u64" : "i32", g.e.streaming ? "true" : "false");
+    const agg_fn k = fns[path][u64 ? 1 : 0][g.e.streaming ? 1 : 0];
+    const bool timed = ctx->timing && ctx->timed < kMaxTimedLaunches;
+    if (timed) hipExtLaunchKernelGGL(k, dim3(grid), dim3(kBlock), (uint32_t)table_bytes, s, ctx->ev_start[ctx->timed], ctx->ev_eval[ctx->timed], 0, g);
+    else hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), (uint32_t)table_bytes, s, g);
+    HIP_TRY(hipGetLastError());
+    if (path != AGG_GLOBAL) {
+        const dim3 sg((n_bins + 63u) / 64u, (grid + kAggSumParts - 1) / kAggSumParts);
+        if (timed) hipExtLaunchKernelGGL(agg_sum_kernel, sg, dim3(kBlock), 0, s, nullptr, ctx->ev_stop[ctx->timed], 0,
+                                         (const uint64_t *)ctx->group_parts, grid, n_bins, out);
+        else hipLaunchKernelGGL(agg_sum_kernel, sg, dim3(kBlock), 0, s, (const uint64_t *)ctx->group_parts, grid, n_bins, out);
+        HIP_TRY(hipGetLastError());
+    }
+    if (timed) { ctx->stop_is_eval[ctx->timed] = path == AGG_GLOBAL; ctx->timed++; }
+    return PQPS_OK;
+}
+
+int pqps_aggregate_list(pqps_ctx *ctx, const pqps_column *value_col, const pqps_column *group_col, uint64_t n_rows,
+                        const uint32_t *ids, const uint64_t *count_dev, uint64_t capacity, uint32_t id_base, uint32_t bin_base,
+                        uint32_t n_bins, uint64_t *out, void *stream) {
+    if (!ctx || !out || !count_dev || (capacity && !ids)) return fail(PQPS_EINVAL, "NULL argument");
+    int rc = check_aggregate_cols(value_col, group_col, n_bins, false);
+    if (rc) return rc;
+    hipStream_t s = pick_stream(ctx, stream);
+    rc = init_aggregate_out(out, n_bins, s);
+    if (rc || capacity == 0 || n_rows == 0) return rc;
+    uint64_t blocks = (capacity + kBlock - 1) / kBlock;
+    const uint64_t cap = (uint64_t)ctx->compute_units * 4;
+    if (blocks > cap) blocks = cap;
+    const uint32_t gw = group_col ? group_col->width : 1;
+    const uint32_t wl = gw == 1 ? 0u : gw == 2 ? 1u : 2u;
+    const void *gdata = group_col ? group_col->data : nullptr;
+    const int path = !group_col ? AGG_ONE : n_bins <= kAggLdsBins ? AGG_LDS : AGG_GLOBAL;
+    const uint32_t lds = path == AGG_LDS ? n_bins * (uint32_t)(3 * sizeof(uint64_t) + sizeof(uint32_t)) : 0u;
+    typedef void (*list_fn)(const void *, const void *, uint32_t, uint64_t, const uint32_t *, const uint64_t *, uint64_t, uint32_t,
+                            uint32_t, uint32_t, uint64_t *);
+    static const list_fn fns[3][2] = {
+        {agg_list_kernel<AGG_ONE, false>, agg_list_kernel<AGG_ONE, true>},
+        {agg_list_kernel<AGG_LDS, false>, agg_list_kernel<AGG_LDS, true>},
+        {agg_list_kernel<AGG_GLOBAL, false>, agg_list_kernel<AGG_GLOBAL, true>},
+    };
+    hipLaunchKernelGGL(fns[path][value_col->width == 8 ? 1 : 0], dim3((uint32_t)blocks), dim3(kBlock), lds, s,
+                       value_col->data, gdata, wl, n_rows, ids, count_dev, capacity, id_base, bin_base, n_bins, out);
     HIP_TRY(hipGetLastError());
     return PQPS_OK;
 }

@@ -741,17 +741,100 @@ static int column_bounds(struct query *q, int c, int32_t *lo, int32_t *hi) {
     return rc;
 }
 
-/* The bins of the query on every shard, summed into counts[0 .. n_bins) on the host.  `fused`: one pqps_filter_group launch
- * per shard on the query's lane; otherwise the selection (query_issue_all + query_await, each shard's list left on its own
- * device) and pqps_group_list over every list.  `gcol[s]`: shard s's group column. */
-static int group_bins(struct query *q, bool fused, const pqps_column *gcol, uint32_t bin_base, uint32_t n_bins, uint64_t *counts) {
-    uint32_t *bins_dev[HIP_MAX_SHARDS] = { NULL };
-    uint32_t *host = malloc((size_t)n_bins * sizeof *host);
+/* How a grouped query bins its rows (shared by grouped COUNT and the aggregates). */
+struct group_plan {
+    int c;                               /* HIPCOL_* of the group column, -1 without GROUP BY                        */
+    int kind;                            /* k_group_kind[c], -1 without GROUP BY                                     */
+    uint32_t n_bins, bin_base;           /* 1 / 0 without GROUP BY                                                   */
+    int32_t lo;                          /* i32 group column: the key of bin 0                                       */
+    bool single;                         /* a single-valued dictionary column (no buffer): every row is bin 0        */
+    bool empty;                          /* no rows in the table: no groups, nothing to launch                      */
+    bool fused;                          /* single-pass scan-mode WHERE: one fused launch per shard                 */
+    pqps_column gcol[HIP_MAX_SHARDS];    /* shard s's group column (sudo_used: its bit plane on the fused path)      */
+};
+
+/* The HIPCOL_* of a group column, or -1 with the reason on stderr (`what`: the query's name in the message). */
+static int group_column_id(const char *what, const char *column) {
+    const int c = hipColumnId(column);
+    if (c < 0) { fprintf(stderr, "HIP engine: %s: unknown column '%s'\n", what, column); return -1; }
+    if (c == HIPCOL_COMMAND_ID) { fprintf(stderr, "HIP engine: %s: command_id is unique -- grouping on it is the SELECT\n", what); return -1; }
+    return c;
+}
+
+/* Binds the WHERE into q (plan and index probes) and decides the bins of group column c (-1: none): codes of a dictionary
+ * (none for a single-valued column: every row is bin 0), 0 / 1, or the i32 range.  `column`: its name, `what`: the query's,
+ * for the messages. */
+static int group_plan_init(struct engineS *engine, struct whereClauseS *whereClause, struct query *q, int c, const char *column,
+                           const char *what, struct group_plan *gp) {
+    struct hipTable *t = q->t;
+    memset(gp, 0, sizeof *gp);
+    gp->c = c;
+    gp->kind = c >= 0 ? k_group_kind[c] : -1;
+    gp->n_bins = 1;
+    int rc = bind_where(t, whereClause, &q->plan);
+    q->have_plan = rc == 0;
+    if (rc == 0) {
+        q->n_probes = list_probes(engine, t, whereClause, &q->probes);
+        if (q->n_probes < 0) { q->n_probes = 0; rc = -1; }
+    }
+    int32_t hi = -1;
+    uint64_t rows = 0;
+    for (int s = 0; s < q->n_shards; s++) rows += hipTableShard(t, s)->n_rows;
+    if (rc == 0 && rows == 0) gp->empty = true;                          /* an empty table: no groups */
+    else if (rc == 0 && c >= 0) {
+        if (gp->kind == HIPKIND_DICT) {
+            gp->n_bins = t->dict[c].count > 0 ? (uint32_t)t->dict[c].count : 1u;
+            gp->single = t->col[c].width == 0;
+        } else if (gp->kind == HIPKIND_BOOL) {
+            gp->n_bins = 2;
+        } else if ((rc = column_bounds(q, c, &gp->lo, &hi)) == 0) {
+            if (gp->lo > hi) gp->empty = true;                           /* no rows at all */
+            else if ((uint64_t)((int64_t)hi - (int64_t)gp->lo) + 1u > HIP_GROUP_MAX_BINS) {
+                fprintf(stderr, "HIP engine: %s: %s spans %lld values, more than %llu groups\n", what, column,
+                        (long long)hi - (long long)gp->lo + 1, HIP_GROUP_MAX_BINS);
+                rc = -1;
+            } else {
+                gp->n_bins = (uint32_t)((int64_t)hi - (int64_t)gp->lo + 1);
+                gp->bin_base = (uint32_t)gp->lo;
+            }
+        }
+    }
+    gp->fused = q->plan.n_passes == 1 && q->n_probes == 0;
+    for (int s = 0; s < q->n_shards && c >= 0; s++) {
+        const struct hipTable *sh = hipTableShard(t, s);
+        gp->gcol[s] = gp->fused && c == HIPCOL_SUDO_USED && sh->sudo_bits.data ? sh->sudo_bits : sh->col[c];
+    }
+    return rc;
+}
+
+/* One shard's result added into the host accumulators: COUNT (vc < 0) u32 bins into acc[0 .. n_bins); an aggregate the
+ * [4][n_bins] u64 fields of pqps_filter_aggregate into acc[4 * n_bins] (counts and sums added, min / max images taken). */
+static void group_combine(uint64_t *acc, const void *host, uint32_t n_bins, int vc) {
+    if (vc < 0) {
+        for (uint32_t k = 0; k < n_bins; k++) acc[k] += ((const uint32_t *)host)[k];
+        return;
+    }
+    const uint64_t *h = host;
+    for (uint32_t k = 0; k < 2 * n_bins; k++) acc[k] += h[k];
+    for (uint32_t k = 2 * n_bins; k < 3 * n_bins; k++) if (h[k] < acc[k]) acc[k] = h[k];
+    for (uint32_t k = 3 * n_bins; k < 4 * n_bins; k++) if (h[k] > acc[k]) acc[k] = h[k];
+}
+
+/* The bins of the query on every shard, combined on the host (group_combine).  vc < 0: grouped COUNT (pqps_filter_group /
+ * pqps_group_list); otherwise the aggregates of value column vc (pqps_filter_aggregate / pqps_aggregate_list; no group
+ * column without GROUP BY or for a single-valued one).  gp->fused: one launch per shard on the query's lane; otherwise the
+ * selection (query_issue_all + query_await, each shard's list left on its own device) and the list kernel over every list. */
+static int group_bins(struct query *q, const struct group_plan *gp, int vc, uint64_t *acc) {
+    const uint32_t n_bins = gp->n_bins, bin_base = gp->bin_base;
+    const size_t bytes = vc < 0 ? (size_t)n_bins * sizeof(uint32_t) : (size_t)n_bins * 4 * sizeof(uint64_t);
+    const bool grouped = gp->c >= 0 && !gp->single;
+    void *bins_dev[HIP_MAX_SHARDS] = { NULL };
+    void *host = malloc(bytes);
     int rc = host ? 0 : -1;
     if (!host) fprintf(stderr, "HIP engine: out of memory\n");
     for (int s = 0; s < q->n_shards && rc == 0; s++)
-        if (pqps_malloc(hipTableShard(q->t, s)->ctx, (size_t)n_bins * sizeof(uint32_t), (void **)&bins_dev[s]) != PQPS_OK) rc = engine_error("bins allocation");
-    if (rc == 0 && fused) {
+        if (pqps_malloc(hipTableShard(q->t, s)->ctx, bytes, &bins_dev[s]) != PQPS_OK) rc = engine_error("bins allocation");
+    if (rc == 0 && gp->fused) {
         const struct hipPass *last = &q->plan.pass[0];
         hipTableLockIssue(q->t);
         for (int s = 0; s < q->n_shards && rc == 0; s++) {
@@ -764,7 +847,9 @@ static int group_bins(struct query *q, bool fused, const pqps_column *gcol, uint
             sp->pred = &last->pred;
             sp->n_cols = last->pred.n_columns;
             pass_columns(sh, last, NULL, true, sp->cols);
-            if (pqps_filter_group(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, &gcol[s], bin_base, n_bins, bins_dev[s], stream) != PQPS_OK)
+            if (vc < 0 ? pqps_filter_group(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, &gp->gcol[s], bin_base, n_bins, bins_dev[s], stream) != PQPS_OK
+                       : pqps_filter_aggregate(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, &sh->col[vc], grouped ? &gp->gcol[s] : NULL,
+                                               bin_base, n_bins, bins_dev[s], stream) != PQPS_OK)
                 rc = engine_error("group filter");
             /* marked even after a failed call: the lane must not be handed on while a launch of this query runs */
             if (q->lane >= 0 && pqps_qstream_mark(sh->qs, (uint32_t)q->lane) != PQPS_OK && rc == 0) rc = engine_error("query lane");
@@ -773,8 +858,8 @@ static int group_bins(struct query *q, bool fused, const pqps_column *gcol, uint
         for (int s = 0; s < q->n_shards; s++) if (wait_shard(q, s) != 0 && rc == 0) rc = -1;
         for (int s = 0; s < q->n_shards && rc == 0; s++)
             if (hipTableShard(q->t, s)->n_rows == 0) continue;
-            else if (pqps_download(lane_copy_ctx(q, s), host, bins_dev[s], (size_t)n_bins * sizeof *host, NULL) != PQPS_OK) rc = engine_error("bins download");
-            else for (uint32_t k = 0; k < n_bins; k++) counts[k] += host[k];
+            else if (pqps_download(lane_copy_ctx(q, s), host, bins_dev[s], bytes, NULL) != PQPS_OK) rc = engine_error("bins download");
+            else group_combine(acc, host, n_bins, vc);
     } else if (rc == 0) {
         q->per_shard = true;
         rc = query_issue_all(q);
@@ -784,15 +869,25 @@ static int group_bins(struct query *q, bool fused, const pqps_column *gcol, uint
             struct hipLane *L = query_lane(q, s);
             pqps_ctx *cs = lane_copy_ctx(q, s);
             if (q->count[s] == 0) continue;
-            if (pqps_group_list(cs, &gcol[s], sh->n_rows, L->ids_dev, L->count_dev, q->count[s], (uint32_t)sh->row0, bin_base, n_bins, bins_dev[s], NULL) != PQPS_OK ||
-                pqps_download(cs, host, bins_dev[s], (size_t)n_bins * sizeof *host, NULL) != PQPS_OK)
+            if ((vc < 0 ? pqps_group_list(cs, &gp->gcol[s], sh->n_rows, L->ids_dev, L->count_dev, q->count[s], (uint32_t)sh->row0, bin_base, n_bins, bins_dev[s], NULL)
+                        : pqps_aggregate_list(cs, &sh->col[vc], grouped ? &gp->gcol[s] : NULL, sh->n_rows, L->ids_dev, L->count_dev, q->count[s],
+                                              (uint32_t)sh->row0, bin_base, n_bins, bins_dev[s], NULL)) != PQPS_OK ||
+                pqps_download(cs, host, bins_dev[s], bytes, NULL) != PQPS_OK)
                 rc = engine_error("group list");
-            else for (uint32_t k = 0; k < n_bins; k++) counts[k] += host[k];
+            else group_combine(acc, host, n_bins, vc);
         }
     }
     for (int s = 0; s < q->n_shards; s++) if (bins_dev[s]) pqps_free(hipTableShard(q->t, s)->ctx, bins_dev[s]);
     free(host);
     return rc;
+}
+
+/* The key and key text of bin k of group column c (kind `kind`); text points into buf or the dictionary. */
+static const char *group_key(const struct hipTable *t, int c, int kind, uint32_t k, int32_t lo, long long *key, char *buf, size_t len) {
+    if (kind == HIPKIND_I32) { *key = (long long)lo + (long long)k; snprintf(buf, len, "%d", (int)*key); return buf; }
+    *key = k;
+    if (kind == HIPKIND_BOOL) return k ? "true" : "false";
+    return t->dict[c].values[k];
 }
 
 static int group_result_fill(struct hipGroupResult *res, const struct hipTable *t, const uint64_t *counts, uint32_t n_bins, int32_t lo) {
@@ -806,11 +901,7 @@ static int group_result_fill(struct hipGroupResult *res, const struct hipTable *
     for (uint32_t k = 0; k < n_bins; k++) {
         if (!counts[k]) continue;
         char buf[32];
-        const char *text = buf;
-        if (res->kind == HIPKIND_I32) { res->keys[g] = (long long)lo + (long long)k; snprintf(buf, sizeof buf, "%d", (int)res->keys[g]); }
-        else if (res->kind == HIPKIND_BOOL) { res->keys[g] = k; text = k ? "true" : "false"; }
-        else { res->keys[g] = k; text = t->dict[res->column].values[k]; }
-        res->keyText[g] = strdup(text);
+        res->keyText[g] = strdup(group_key(t, res->column, res->kind, k, lo, &res->keys[g], buf, sizeof buf));
         if (!res->keyText[g]) { fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
         res->counts[g] = counts[k];
         res->total += (long long)counts[k];
@@ -827,9 +918,8 @@ struct hipGroupResult *executeQueryGroupCountHIP(struct engineS *engine, const c
     res->column = -1;
     res->kind = -1;
     if (!engine || !engine->record_block || !groupColumn) { fprintf(stderr, "HIP engine: grouped COUNT without an engine or a column\n"); return res; }
-    const int c = hipColumnId(groupColumn);
-    if (c < 0) { fprintf(stderr, "HIP engine: grouped COUNT: unknown column '%s'\n", groupColumn); return res; }
-    if (c == HIPCOL_COMMAND_ID) { fprintf(stderr, "HIP engine: grouped COUNT: command_id is unique -- grouping on it is the SELECT\n"); return res; }
+    const int c = group_column_id("grouped COUNT", groupColumn);
+    if (c < 0) return res;
     struct hipTable *t = engine->record_block;
     if (t->xch) { fprintf(stderr, "HIP engine: grouped COUNT is not exchanged across ranks\n"); return res; }
     res->column = c;
@@ -840,59 +930,24 @@ struct hipGroupResult *executeQueryGroupCountHIP(struct engineS *engine, const c
     struct query q;
     query_init(&q, engine, t, lane, false);
     uint64_t *counts = NULL;
-    int rc = bind_where(t, whereClause, &q.plan);
-    q.have_plan = rc == 0;
-    if (rc == 0) {
-        q.n_probes = list_probes(engine, t, whereClause, &q.probes);
-        if (q.n_probes < 0) { q.n_probes = 0; rc = -1; }
-    }
-    /* bins: codes of a dictionary (none for a single-valued column: every row is bin 0), 0 / 1, or the i32 range */
-    uint32_t n_bins = 1, bin_base = 0;
-    int32_t lo = 0, hi = -1;
-    bool single = false, empty = false;
-    uint64_t rows = 0;
-    for (int s = 0; s < q.n_shards; s++) rows += hipTableShard(t, s)->n_rows;
-    if (rc == 0 && rows == 0) empty = true;                              /* an empty table: no groups */
-    else if (rc == 0) {
-        if (res->kind == HIPKIND_DICT) {
-            n_bins = t->dict[c].count > 0 ? (uint32_t)t->dict[c].count : 1u;
-            single = t->col[c].width == 0;
-        } else if (res->kind == HIPKIND_BOOL) {
-            n_bins = 2;
-        } else if ((rc = column_bounds(&q, c, &lo, &hi)) == 0) {
-            if (lo > hi) empty = true;                                   /* no rows at all */
-            else if ((uint64_t)((int64_t)hi - (int64_t)lo) + 1u > HIP_GROUP_MAX_BINS) {
-                fprintf(stderr, "HIP engine: grouped COUNT: %s spans %lld values, more than %llu groups\n", groupColumn,
-                        (long long)hi - (long long)lo + 1, HIP_GROUP_MAX_BINS);
-                rc = -1;
-            } else {
-                n_bins = (uint32_t)((int64_t)hi - (int64_t)lo + 1);
-                bin_base = (uint32_t)lo;
-            }
-        }
-    }
-    if (rc == 0 && !empty) {
-        counts = calloc(n_bins, sizeof *counts);
+    struct group_plan gp;
+    int rc = group_plan_init(engine, whereClause, &q, c, groupColumn, "grouped COUNT", &gp);
+    if (rc == 0 && !gp.empty) {
+        counts = calloc(gp.n_bins, sizeof *counts);
         if (!counts) { fprintf(stderr, "HIP engine: out of memory\n"); rc = -1; }
     }
-    if (rc == 0 && !empty) {
-        if (single) {
+    if (rc == 0 && !gp.empty) {
+        if (gp.single) {
             /* one value: the number of rows the selection returns (scan mode: the count, no list) */
             q.count_only = q.n_probes == 0;
             rc = query_issue_all(&q);
             if (rc == 0) rc = query_await(&q);
             if (rc == 0) counts[0] = q.total;
         } else {
-            pqps_column gcol[HIP_MAX_SHARDS];
-            const bool fused = q.plan.n_passes == 1 && q.n_probes == 0;
-            for (int s = 0; s < q.n_shards; s++) {
-                const struct hipTable *sh = hipTableShard(t, s);
-                gcol[s] = fused && c == HIPCOL_SUDO_USED && sh->sudo_bits.data ? sh->sudo_bits : sh->col[c];
-            }
-            rc = group_bins(&q, fused, gcol, bin_base, n_bins, counts);
+            rc = group_bins(&q, &gp, -1, counts);
         }
     }
-    if (rc == 0 && group_result_fill(res, t, counts ? counts : (uint64_t[1]){ 0 }, empty ? 0u : n_bins, lo) == 0) res->success = true;
+    if (rc == 0 && group_result_fill(res, t, counts ? counts : (uint64_t[1]){ 0 }, gp.empty ? 0u : gp.n_bins, gp.lo) == 0) res->success = true;
     free(counts);
     query_free(&q);
     hipTableReleaseLane(t, lane);
@@ -907,6 +962,102 @@ void freeGroupResultHIP(struct hipGroupResult *res) {
     free(res->keyText);
     free(res->keys);
     free(res->counts);
+    free(res);
+}
+
+/* ---- COUNT / SUM / MIN / MAX of a value column (include/executeEngine-hip.h) ---------------------------------------- */
+
+/* acc[4][n_bins] (count, sum, min image, max image: pqps_filter_aggregate's layout) into the result, groups with rows only */
+static int aggregate_result_fill(struct hipAggregateResult *res, const struct hipTable *t, const uint64_t *acc, uint32_t n_bins, int32_t lo) {
+    int n = 0;
+    for (uint32_t k = 0; k < n_bins; k++) n += acc[k] != 0;
+    const bool grouped = res->groupColumn >= 0;
+    res->counts = calloc((size_t)n + 1, sizeof *res->counts);
+    res->sums = calloc((size_t)n + 1, sizeof *res->sums);
+    res->mins = calloc((size_t)n + 1, sizeof *res->mins);
+    res->maxs = calloc((size_t)n + 1, sizeof *res->maxs);
+    if (grouped) {
+        res->keys = calloc((size_t)n + 1, sizeof *res->keys);
+        res->keyText = calloc((size_t)n + 1, sizeof *res->keyText);
+    }
+    if (!res->counts || !res->sums || !res->mins || !res->maxs || (grouped && (!res->keys || !res->keyText))) {
+        fprintf(stderr, "HIP engine: out of memory\n");
+        return -1;
+    }
+    /* the image of an i32 value is (u64)(i64)v ^ 2^63, of a u64 value the value itself */
+    const uint64_t flip = res->valueKind == HIPKIND_I32 ? 0x8000000000000000ull : 0;
+    int g = 0;
+    for (uint32_t k = 0; k < n_bins; k++) {
+        if (!acc[k]) continue;
+        if (grouped) {
+            char buf[32];
+            res->keyText[g] = strdup(group_key(t, res->groupColumn, res->groupKind, k, lo, &res->keys[g], buf, sizeof buf));
+            if (!res->keyText[g]) { res->numGroups = g; fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
+        }
+        res->counts[g] = acc[k];
+        res->sums[g] = (long long)acc[n_bins + k];
+        res->mins[g] = (long long)(acc[2 * n_bins + k] ^ flip);
+        res->maxs[g] = (long long)(acc[3 * n_bins + k] ^ flip);
+        res->total += (long long)acc[k];
+        g++;
+    }
+    res->numGroups = n;
+    return 0;
+}
+
+struct hipAggregateResult *executeQueryAggregateHIP(struct engineS *engine, const char *valueColumn, const char *groupColumn,
+                                                    struct whereClauseS *whereClause) {
+    const double t0 = now_seconds();
+    struct hipAggregateResult *res = calloc(1, sizeof *res);
+    if (!res) { fprintf(stderr, "HIP engine: out of memory\n"); return NULL; }
+    res->valueColumn = res->valueKind = res->groupColumn = res->groupKind = -1;
+    if (!engine || !engine->record_block || !valueColumn) { fprintf(stderr, "HIP engine: aggregate without an engine or a value column\n"); return res; }
+    const int v = hipColumnId(valueColumn);
+    if (v < 0) { fprintf(stderr, "HIP engine: aggregate: unknown value column '%s'\n", valueColumn); return res; }
+    if (k_group_kind[v] != HIPKIND_I32 && k_group_kind[v] != HIPKIND_U64) {
+        fprintf(stderr, "HIP engine: aggregate: %s is a %s column, not a number\n", valueColumn, k_group_kind[v] == HIPKIND_BOOL ? "boolean" : "dictionary");
+        return res;
+    }
+    const int c = groupColumn ? group_column_id("aggregate", groupColumn) : -1;
+    if (groupColumn && c < 0) return res;
+    struct hipTable *t = engine->record_block;
+    if (t->xch) { fprintf(stderr, "HIP engine: aggregates are not exchanged across ranks\n"); return res; }
+    res->valueColumn = v;
+    res->valueKind = k_group_kind[v];
+    res->groupColumn = c;
+    res->groupKind = c >= 0 ? k_group_kind[c] : -1;
+    hipTableLockShared(t);
+    const int lane = hipTableAcquireLane(t);
+    if (lane == HIP_LANE_REFUSED) { hipTableUnlockShared(t); return res; }  /* reason on stderr */
+    struct query q;
+    query_init(&q, engine, t, lane, false);
+    uint64_t *acc = NULL;
+    struct group_plan gp;
+    int rc = group_plan_init(engine, whereClause, &q, c, groupColumn, "aggregate", &gp);
+    if (rc == 0 && !gp.empty) {
+        acc = calloc((size_t)4 * gp.n_bins, sizeof *acc);
+        if (!acc) { fprintf(stderr, "HIP engine: out of memory\n"); rc = -1; }
+        else for (uint32_t k = 0; k < gp.n_bins; k++) acc[2 * gp.n_bins + k] = UINT64_MAX;
+    }
+    if (rc == 0 && !gp.empty) rc = group_bins(&q, &gp, v, acc);
+    if (rc == 0 && aggregate_result_fill(res, t, acc ? acc : (uint64_t[4]){ 0 }, gp.empty ? 0u : gp.n_bins, gp.lo) == 0) res->success = true;
+    free(acc);
+    query_free(&q);
+    hipTableReleaseLane(t, lane);
+    hipTableUnlockShared(t);
+    res->queryTime = now_seconds() - t0;
+    return res;
+}
+
+void freeAggregateResultHIP(struct hipAggregateResult *res) {
+    if (!res) return;
+    for (int g = 0; g < res->numGroups && res->keyText; g++) free(res->keyText[g]);
+    free(res->keyText);
+    free(res->keys);
+    free(res->counts);
+    free(res->sums);
+    free(res->mins);
+    free(res->maxs);
     free(res);
 }
 
