@@ -276,6 +276,38 @@ struct hipAggregateResult *executeQueryAggregateHIP(struct engineS *engine, cons
                                                     struct whereClauseS *whereClause);
 void freeAggregateResultHIP(struct hipAggregateResult *result);
 
+/* ORDER BY one column [ASC | DESC] with LIMIT (the reference parses ORDER BY into ParsedSQL.order_by / order_desc and
+ * executes it nowhere; reached through the C API and the Python package only -- the SQL driver still ignores it, so its
+ * output stays that of QPESeq).
+ * ROWS: exactly the rows executeQuerySelectIdsHIP(engine, whereClause) returns -- in index mode too, so a row several
+ * probed conditions return appears that many times, as in executeQueryGroupCountHIP / executeQueryAggregateHIP; *matches
+ * equals that call's count.
+ * ORDER: by the key of `orderColumn`, ascending, or descending with `descending`; TIES BY ASCENDING ROW NUMBER in both
+ * directions (copies of a row in index mode are adjacent: they share key and row).  The order is total and the same for
+ * every shard layout and every path.  exit_code, user_id, risk_level: signed.  command_id: unsigned 64-bit.  sudo_used:
+ * false before true.  String columns: the dictionary's strcmp order (the order-preserving codes); a single-valued string
+ * column makes every key equal, so the answer is the first rows by row number.  Every one of the 12 columns can be an
+ * order column.
+ * LIMIT: limit > 0 gives the first min(limit, matches) rows of that order, limit <= 0 all of them (a full ORDER BY).
+ * REFUSED (-1 / success = false, the reason on stderr): an unknown order column, and an engine joined across ranks.
+ * A reader like COUNT: shared lock and one query lane, the lane rules above apply; the device scratch of a query is
+ * allocated for it and freed with it, so two lanes never share any.
+ * Execution: a single-pass scan-mode WHERE with 0 < limit <= 1024 (512 for command_id) runs ONE fused filter-and-top-K
+ * launch per shard (pqps_filter_topk) and small rounds that reduce its waves' partial rows; everything else runs the
+ * selection, then per shard the same top-K selection over its list (pqps_topk_list) or, for limit <= 0 or above those
+ * bounds, a stable radix sort of the list (pqps_sort_list).  Shards are merged on the host.  An empty table, or a WHERE
+ * that matches nothing, gives 0 rows with matches = 0 and success. */
+/* Row numbers of the first `limit` rows (all if limit <= 0) in that order; returns how many were written to *ids
+ * (malloc'd, caller frees), -1 on error or refusal.  *matches (may be NULL) = executeQuerySelectIdsHIP's count. */
+long long executeQueryOrderIdsHIP(struct engineS *engine, struct whereClauseS *whereClause, const char *orderColumn,
+                                  bool descending, long long limit, unsigned int **ids, long long *matches, double *queryTime);
+/* The same rows, projected: a hipColumnarResult whose numRecords rows are in that order (cells exactly as
+ * executeQuerySelectColumnarHIP makes them; hipColumnarHead / hipColumnarCellText work on it unchanged).  *matches (may
+ * be NULL) as above. */
+struct hipColumnarResult *executeQuerySelectOrderedHIP(struct engineS *engine, const char **selectItems, int numSelectItems,
+                                                       struct whereClauseS *whereClause, const char *orderColumn,
+                                                       bool descending, long long limit, long long *matches);
+
 /* COUNT(*) through the backend API (the reference parser cannot express it,
  * SURVEY.md fact 10): scan-mode count of matching rows, no ID list. */
 long long executeQueryCountHIP(struct engineS *engine, struct whereClauseS *whereClause);

@@ -471,6 +471,39 @@ int pqps_aggregate_list(pqps_ctx *ctx, const pqps_column *value_col, const pqps_
                         const uint32_t *ids, const uint64_t *count_dev, uint64_t capacity, uint32_t id_base, uint32_t bin_base,
                         uint32_t n_bins, uint64_t *out, void *stream);
 
+/* ---- ORDER BY column [DESC] LIMIT K ------------------------------------------------------------------------------
+ * No counterpart in the reference (it parses ORDER BY and executes none).  KEYS: every row is one composite key whose
+ * ascending unsigned order is the answer's order -- the column's order-preserving image ascending (descending with
+ * `descending`), ties by ascending table-wide row number (row_base / id_base + local row):
+ *   key_col 1, 2 or 4 bytes wide, or a bit plane: one u64 per key, (img ^ x) << 32 | row, img = v ^ 2^31 when key_signed
+ *     (i32), the value itself otherwise (dictionary codes, the bool byte or bit), x = 0xFFFFFFFF when descending, else 0
+ *   key_col 8 bytes wide (command_id, unsigned): two u64 per key, (v ^ x, row), x = ~0 when descending, else 0
+ *   key_col NULL: every value 0 (a single-valued column), the order is the row order.
+ * OUTPUT (pqps_filter_topk / pqps_topk_list): out[0 .. k) keys (k or 2 k u64 words), ascending; of M candidates only the
+ * first min(k, M) are real, the rest read all ones.  K = 1 .. PQPS_TOPK_MAX (PQPS_TOPK_MAX_WIDE for 8-byte keys).  Row
+ * numbers stay below 2^32 - 1.  `scratch`: device memory of at least pqps_topk_scratch_bytes(ctx, n, k, wide, fused)
+ * bytes (n = n_rows of the fused scan, the list length otherwise) that nothing else uses until the call's work is done --
+ * the engine allocates it per query, so no two queries ever share it.  Asynchronous on `stream`.
+ *
+ * pqps_filter_topk: ONE scan of `pred` over rows [0, n_rows) (the key column read only in steps of 1024 rows that hold a
+ *   match; the readable-padding rule of pqps_filter_scan applies to it), each wave keeping its K best in LDS, then a few
+ *   small rounds that reduce the waves' partial rows to K.  *count (device) = the matching rows.  Recorded by the
+ *   context's timing recorder like a COUNT (the scan's start to the last round's end).
+ * pqps_topk_list: the same selection over ids[0 .. n) (table-wide rows, local row = id - id_base), keys gathered per
+ *   entry -- an entry listed twice is a candidate twice.  key_col 1, 2, 4 or 8 bytes wide (no bit plane).
+ * pqps_sort_list: the whole list in that order: out_ids[0 .. n) the rows, out_keys[0 .. n) (may be NULL) their sort keys
+ *   as u64 (narrow: (img ^ x) zero-extended; wide: v ^ x).  Two stable radix sorts (rows, then keys).  Synchronous. */
+#define PQPS_TOPK_MAX 1024u
+#define PQPS_TOPK_MAX_WIDE 512u
+uint64_t pqps_topk_scratch_bytes(pqps_ctx *ctx, uint64_t n, uint32_t k, int wide, int fused);
+int pqps_filter_topk(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                     const pqps_column *key_col, int key_signed, int descending, uint32_t row_base, uint32_t k,
+                     void *scratch, uint64_t scratch_bytes, uint64_t *out, uint64_t *count, void *stream);
+int pqps_topk_list(pqps_ctx *ctx, const pqps_column *key_col, int key_signed, int descending, const uint32_t *ids, uint64_t n,
+                   uint32_t id_base, uint32_t k, void *scratch, uint64_t scratch_bytes, uint64_t *out, void *stream);
+int pqps_sort_list(pqps_ctx *ctx, const pqps_column *key_col, int key_signed, int descending, const uint32_t *ids, uint64_t n,
+                   uint32_t id_base, uint32_t *out_ids, uint64_t *out_keys, void *stream);
+
 /* Checksums of a device-resident ID list: out[0] = sum of ids[i], out[1] = sum of ids[i] * (2 i + 1), both mod 2^64 (the
  * second depends on the order).  Synchronous; what a bench or a test compares two lists with without downloading them. */
 int pqps_ids_checksum(pqps_ctx *ctx, const uint32_t *ids, uint64_t count, uint64_t out[2], void *stream);

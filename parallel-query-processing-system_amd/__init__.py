@@ -427,9 +427,21 @@ def lib():
     L.pqps_filter_aggregate.argtypes = [vp, C.POINTER(Column), u32, u64, C.POINTER(Predicate), C.POINTER(Column), C.POINTER(Column),
                                         u32, u32, vp, vp]
     L.pqps_aggregate_list.argtypes = [vp, C.POINTER(Column), C.POINTER(Column), u64, vp, vp, u64, u32, u32, u32, vp, vp]
+    L.executeQueryOrderIdsHIP.restype = C.c_longlong
+    L.executeQueryOrderIdsHIP.argtypes = [E, W, C.c_char_p, C.c_bool, C.c_longlong, C.POINTER(C.POINTER(C.c_uint)),
+                                          C.POINTER(C.c_longlong), C.POINTER(C.c_double)]
+    L.pqps_topk_scratch_bytes.restype = u64
+    L.pqps_topk_scratch_bytes.argtypes = [vp, u64, u32, C.c_int, C.c_int]
+    L.pqps_filter_topk.argtypes = [vp, C.POINTER(Column), u32, u64, C.POINTER(Predicate), C.POINTER(Column), C.c_int, C.c_int, u32, u32,
+                                   vp, u64, vp, vp, vp]
+    L.pqps_topk_list.argtypes = [vp, C.POINTER(Column), C.c_int, C.c_int, vp, u64, u32, u32, vp, u64, vp, vp]
+    L.pqps_sort_list.argtypes = [vp, C.POINTER(Column), C.c_int, C.c_int, vp, u64, u32, vp, vp, vp]
     CR = C.POINTER(ColumnarResult)
     L.executeQuerySelectColumnarHIP.restype = CR
     L.executeQuerySelectColumnarHIP.argtypes = [E, C.POINTER(C.c_char_p), C.c_int, W]
+    L.executeQuerySelectOrderedHIP.restype = CR
+    L.executeQuerySelectOrderedHIP.argtypes = [E, C.POINTER(C.c_char_p), C.c_int, W, C.c_char_p, C.c_bool, C.c_longlong,
+                                               C.POINTER(C.c_longlong)]
     L.freeColumnarResultHIP.argtypes = [CR]
     L.hipColumnarCellText.restype = vp
     L.hipColumnarCellText.argtypes = [CR, C.c_int, C.c_int]
@@ -851,6 +863,22 @@ class HipEngine:
         """AVG as sum / count of aggregate(): [(key_text, avg), ...] (the device computes no AVG)."""
         return [(k, s / c) for k, c, s, _, _ in self.aggregate(value_column, group_column, chain)]
 
+    def order_ids(self, order_column, chain=None, descending=False, limit=None):
+        """executeQueryOrderIdsHIP: (ids, matches) -- the row numbers of the first `limit` rows (all with limit None or <= 0)
+        of select_ids(chain) ordered by `order_column` (descending with `descending`), ties by ascending row number;
+        matches = len(select_ids(chain)).  Raises PqpsError when the engine refuses (reason on stderr)."""
+        wl = WhereList(chain)
+        ids = C.POINTER(C.c_uint)()
+        matches = C.c_longlong()
+        qt = C.c_double()
+        n = lib().executeQueryOrderIdsHIP(self.e, wl.ptr, order_column.encode(), bool(descending), int(limit or 0), C.byref(ids),
+                                          C.byref(matches), C.byref(qt))
+        if n < 0:
+            raise PqpsError(f"order_ids({order_column!r}) refused or failed (reason on stderr)")
+        out = list(ids[:n])
+        lib().free(ids)
+        return out, int(matches.value)
+
     def select(self, columns, chain):
         wl = WhereList(chain)
         items = (C.c_char_p * max(1, len(columns or [])))(*[c.encode() for c in (columns or [])])
@@ -866,11 +894,17 @@ class HipEngine:
     def select_columnar(self, columns, chain, text=True):
         """executeQuerySelectColumnarHIP: typed per-column arrays gathered on the device; with text=True
         also every cell as the string hipColumnarCellText makes of it."""
-        import numpy as np
         L = lib()
         wl = WhereList(chain)
         items = (C.c_char_p * max(1, len(columns or [])))(*[c.encode() for c in (columns or [])])
         res = L.executeQuerySelectColumnarHIP(self.e, items if columns else None, len(columns or []), wl.ptr)
+        return self._columnar_dict(res, text)
+
+    @staticmethod
+    def _columnar_dict(res, text):
+        """The dict of select_columnar / select_ordered for a hipColumnarResult (which it keeps as "handle")."""
+        import numpy as np
+        L = lib()
         r = res.contents
         n, m = r.numRecords, r.numColumns
         dtypes = {0: np.uint64, 1: np.int32, 2: np.uint8, 3: np.uint32}
@@ -893,6 +927,22 @@ class HipEngine:
                     L.free(p)
                 rows.append(row)
             out["rows"] = rows
+        return out
+
+    def select_ordered(self, columns, chain, order_column, descending=False, limit=None, text=True):
+        """executeQuerySelectOrderedHIP: the dict select_columnar returns, its rows those of order_ids(order_column, chain,
+        descending, limit) in that order, plus `matches`.  Raises PqpsError when the engine refuses (reason on stderr)."""
+        wl = WhereList(chain)
+        items = (C.c_char_p * max(1, len(columns or [])))(*[c.encode() for c in (columns or [])])
+        matches = C.c_longlong()
+        res = lib().executeQuerySelectOrderedHIP(self.e, items if columns else None, len(columns or []), wl.ptr,
+                                                 order_column.encode(), bool(descending), int(limit or 0), C.byref(matches))
+        if not res or not res.contents.success:
+            if res:
+                lib().freeColumnarResultHIP(res)
+            raise PqpsError(f"select_ordered({order_column!r}) refused or failed (reason on stderr)")
+        out = self._columnar_dict(res, text)
+        out["matches"] = int(matches.value)
         return out
 
     def free_columnar(self, out):

@@ -23,6 +23,7 @@
 #include "filter_kernels.hpp"
 #include "group_kernels.hpp"
 #include "aggregate_kernels.hpp"
+#include "topk_kernels.hpp"
 #include "radix_sort.hpp"
 
 namespace {
@@ -3041,6 +3042,217 @@ int pqps_aggregate_list(pqps_ctx *ctx, const pqps_column *value_col, const pqps_
     hipLaunchKernelGGL(fns[path][value_col->width == 8 ? 1 : 0], dim3((uint32_t)blocks), dim3(kBlock), lds, s,
                        value_col->data, gdata, wl, n_rows, ids, count_dev, capacity, id_base, bin_base, n_bins, out);
     HIP_TRY(hipGetLastError());
+    return PQPS_OK;
+}
+
+// ---- ORDER BY column [DESC] LIMIT K (topk_kernels.hpp) --------------------------------------------------------------
+static int check_topk_key(const pqps_column *key_col, bool plane_ok, bool *wide, uint32_t *wl) {
+    *wide = false;
+    *wl = 0;
+    if (!key_col) return PQPS_OK;                                // every key 0
+    const uint32_t w = key_col->width;
+    if (w != 1 && w != 2 && w != 4 && w != 8 && !(plane_ok && w == PQPS_WIDTH_BITS))
+        return fail(PQPS_EINVAL, "key column: width %u not in {1,2,4,8%s}", w, plane_ok ? ",bits" : "");
+    if (!key_col->data || ((uintptr_t)key_col->data & 15u) != 0) return fail(PQPS_EINVAL, "key column: NULL or not 16-byte aligned");
+    *wide = w == 8;
+    *wl = w == PQPS_WIDTH_BITS ? kWidthLog2Bits : w == 1 ? 0u : w == 2 ? 1u : w == 4 ? 2u : 3u;
+    return PQPS_OK;
+}
+
+static uint64_t topk_xor(bool wide, int key_signed, int descending) {
+    if (wide) return descending ? ~0ull : 0ull;
+    return (key_signed ? 0x80000000ull : 0ull) ^ (descending ? 0xFFFFFFFFull : 0ull);
+}
+
+// buffer slots per wave: a power of two >= 2 K and >= K + 64
+static uint32_t topk_cap(uint32_t k) {
+    uint32_t cap = kTopkMinCap;
+    while (cap < 2 * k) cap <<= 1;
+    return cap;
+}
+
+// the fused scan's grid: as pqps_filter_group's, up to 8 workgroups per CU as far as the buffers let into 160 KiB, never
+// more than one step per wave
+static uint32_t topk_grid(const pqps_ctx *ctx, uint64_t n_rows, uint32_t lds) {
+    const uint64_t steps = (n_rows + kStepRows - 1) / kStepRows;
+    uint64_t per_cu = (160ull << 10) / ((uint64_t)lds + 1024);
+    if (per_cu > 8) per_cu = 8;
+    if (per_cu < 1) per_cu = 1;
+    const uint64_t want = (steps + kWaves - 1) / kWaves;
+    const uint64_t cap = (uint64_t)ctx->compute_units * per_cu;
+    const uint64_t grid = want < cap ? want : cap;
+    return (uint32_t)(grid ? grid : 1);
+}
+
+// keys of the follow-up rounds' two ping-pong areas for a first input of n keys
+static uint64_t topk_round_keys(uint64_t n, uint32_t k) { return n / kTopkChunk + k; }
+
+uint64_t pqps_topk_scratch_bytes(pqps_ctx *ctx, uint64_t n, uint32_t k, int wide, int fused) {
+    if (!ctx || k == 0) return 0;
+    const uint64_t key_bytes = wide ? 16 : 8;
+    uint64_t first = n;
+    if (fused) first = (uint64_t)topk_grid(ctx, n, (uint32_t)(kWaves * topk_cap(k) * key_bytes)) * kWaves * k;
+    return (first * (fused ? 1 : 0) + 2 * topk_round_keys(first, k)) * key_bytes + 64;
+}
+
+// Rounds of topk_select_kernel over n keys at `in` until one wave is left, whose K best go to `out`; x / y: the ping-pong
+// areas (topk_round_keys each).  The last launch records `stop` when given.
+extern "C++" {
+template <bool WIDE>
+static int topk_rounds(pqps_ctx *ctx, hipStream_t s, const TKey<WIDE> *in, const uint32_t *ids, const void *kcol, uint32_t kwl,
+                       uint64_t kxor, uint32_t id_base, uint64_t n, uint32_t k, TKey<WIDE> *x, TKey<WIDE> *y, TKey<WIDE> *out,
+                       hipEvent_t stop) {
+    const uint32_t cap = topk_cap(k);
+    const uint32_t lds = (uint32_t)(kWaves * cap * sizeof(TKey<WIDE>));
+    const uint64_t max_waves = (uint64_t)ctx->compute_units * kWaves * 2;
+    bool gather = ids != nullptr;
+    for (;;) {
+        uint64_t chunk = kTopkChunk * k;
+        if ((n + chunk - 1) / chunk > max_waves) chunk = (n + max_waves - 1) / max_waves;
+        chunk = (chunk + 63) & ~63ull;
+        const uint64_t waves = n ? (n + chunk - 1) / chunk : 1;
+        TKey<WIDE> *dst = waves == 1 ? out : x;
+        const dim3 grid((uint32_t)((waves + kWaves - 1) / kWaves));
+        if (gather) {
+            hipLaunchKernelGGL((topk_select_kernel<WIDE, true>), grid, dim3(kBlock), lds, s, nullptr, ids, kcol, kwl, kxor, id_base,
+                               n, chunk, waves, k, cap, dst);
+        } else if (waves == 1 && stop) {
+            hipExtLaunchKernelGGL((topk_select_kernel<WIDE, false>), grid, dim3(kBlock), lds, s, nullptr, stop, 0, in, nullptr, kcol, kwl,
+                                  kxor, id_base, n, chunk, waves, k, cap, dst);
+        } else {
+            hipLaunchKernelGGL((topk_select_kernel<WIDE, false>), grid, dim3(kBlock), lds, s, in, nullptr, kcol, kwl, kxor, id_base,
+                               n, chunk, waves, k, cap, dst);
+        }
+        HIP_TRY(hipGetLastError());
+        if (waves == 1) return PQPS_OK;
+        gather = false;
+        in = x;
+        n = waves * k;
+        TKey<WIDE> *t = x; x = y; y = t;
+    }
+}
+}  // extern "C++"
+
+int pqps_filter_topk(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                     const pqps_column *key_col, int key_signed, int descending, uint32_t row_base, uint32_t k,
+                     void *scratch, uint64_t scratch_bytes, uint64_t *out, uint64_t *count, void *stream) {
+    if (!ctx || !out || !count || !scratch) return fail(PQPS_EINVAL, "NULL argument");
+    bool wide;
+    uint32_t wl;
+    int rc = check_topk_key(key_col, true, &wide, &wl);
+    if (rc) return rc;
+    if (k == 0 || k > (wide ? kTopkMaxWide : kTopkMax)) return fail(PQPS_EINVAL, "K = %u: 1 .. %u", k, wide ? kTopkMaxWide : kTopkMax);
+    if (scratch_bytes < pqps_topk_scratch_bytes(ctx, n_rows, k, wide, 1)) return fail(PQPS_EINVAL, "scratch too small");
+    if ((uint64_t)row_base + n_rows >= 0xFFFFFFFFull) return fail(PQPS_EINVAL, "row numbers must stay below 2^32 - 1");
+    rc = check_pred(cols, n_cols, pred);
+    if (rc) return rc;
+    hipStream_t s = pick_stream(ctx, stream);
+    HIP_TRY(hipMemsetAsync(count, 0, sizeof(uint64_t), s));
+    if (n_rows == 0) return PQPS_OK;
+    TopkArgs g;
+    memset(&g, 0, sizeof g);
+    fill_args(g.e, cols, n_cols, pred);
+    g.e.n_rows = n_rows;
+    set_streaming(g.e, cols, n_cols, n_rows);
+    const uint32_t cap = topk_cap(k);
+    const uint32_t key_bytes = wide ? 16u : 8u;
+    const uint32_t lds = kWaves * cap * key_bytes;
+    const uint32_t grid = topk_grid(ctx, n_rows, lds);
+    const uint64_t parts = (uint64_t)grid * kWaves * k;
+    const uint64_t round = topk_round_keys(parts, k);
+    char *base = (char *)scratch;
+    g.kcol = key_col ? key_col->data : nullptr;
+    g.parts = base;
+    g.count = (unsigned long long *)count;
+    g.kxor = topk_xor(wide, key_signed, descending);
+    g.kwidth_log2 = wl;
+    g.row_base = row_base;
+    g.k = k;
+    g.cap = cap;
+    typedef void (*topk_fn)(const TopkArgs);
+    static const topk_fn fns[2][2] = {{topk_scan_kernel<false, false>, topk_scan_kernel<false, true>},
+                                      {topk_scan_kernel<true, false>, topk_scan_kernel<true, true>}};
+    snprintf(g_kernel, sizeof g_kernel, "topk_scan_kernel<%s, NT=%s>", wide ? "wide" : "narrow", g.e.streaming ? "true" : "false");
+    const topk_fn kf = fns[wide ? 1 : 0][g.e.streaming ? 1 : 0];
+    const bool timed = ctx->timing && ctx->timed < kMaxTimedLaunches;
+    if (timed) hipExtLaunchKernelGGL(kf, dim3(grid), dim3(kBlock), lds, s, ctx->ev_start[ctx->timed], ctx->ev_eval[ctx->timed], 0, g);
+    else hipLaunchKernelGGL(kf, dim3(grid), dim3(kBlock), lds, s, g);
+    HIP_TRY(hipGetLastError());
+    hipEvent_t stop = timed ? ctx->ev_stop[ctx->timed] : nullptr;
+    char *xa = base + parts * key_bytes, *ya = xa + round * key_bytes;
+    if (wide) rc = topk_rounds<true>(ctx, s, (const TKey<true> *)base, nullptr, nullptr, 0, 0, 0, parts, k, (TKey<true> *)xa,
+                                     (TKey<true> *)ya, (TKey<true> *)out, stop);
+    else rc = topk_rounds<false>(ctx, s, (const TKey<false> *)base, nullptr, nullptr, 0, 0, 0, parts, k, (TKey<false> *)xa,
+                                 (TKey<false> *)ya, (TKey<false> *)out, stop);
+    if (timed) { ctx->stop_is_eval[ctx->timed] = false; ctx->timed++; }
+    return rc;
+}
+
+int pqps_topk_list(pqps_ctx *ctx, const pqps_column *key_col, int key_signed, int descending, const uint32_t *ids, uint64_t n,
+                   uint32_t id_base, uint32_t k, void *scratch, uint64_t scratch_bytes, uint64_t *out, void *stream) {
+    if (!ctx || !out || !scratch || (n && !ids)) return fail(PQPS_EINVAL, "NULL argument");
+    bool wide;
+    uint32_t wl;
+    int rc = check_topk_key(key_col, false, &wide, &wl);
+    if (rc) return rc;
+    if (k == 0 || k > (wide ? kTopkMaxWide : kTopkMax)) return fail(PQPS_EINVAL, "K = %u: 1 .. %u", k, wide ? kTopkMaxWide : kTopkMax);
+    if (scratch_bytes < pqps_topk_scratch_bytes(ctx, n, k, wide, 0)) return fail(PQPS_EINVAL, "scratch too small");
+    if (n == 0) return PQPS_OK;
+    hipStream_t s = pick_stream(ctx, stream);
+    const uint64_t key_bytes = wide ? 16 : 8;
+    char *xa = (char *)scratch, *ya = xa + topk_round_keys(n, k) * key_bytes;
+    const void *kcol = key_col ? key_col->data : nullptr;
+    const uint64_t kxor = topk_xor(wide, key_signed, descending);
+    if (wide) return topk_rounds<true>(ctx, s, nullptr, ids, kcol, wl, kxor, id_base, n, k, (TKey<true> *)xa, (TKey<true> *)ya,
+                                       (TKey<true> *)out, nullptr);
+    return topk_rounds<false>(ctx, s, nullptr, ids, kcol, wl, kxor, id_base, n, k, (TKey<false> *)xa, (TKey<false> *)ya,
+                              (TKey<false> *)out, nullptr);
+}
+
+int pqps_sort_list(pqps_ctx *ctx, const pqps_column *key_col, int key_signed, int descending, const uint32_t *ids, uint64_t n,
+                   uint32_t id_base, uint32_t *out_ids, uint64_t *out_keys, void *stream) {
+    if (!ctx || !out_ids || (n && !ids)) return fail(PQPS_EINVAL, "NULL argument");
+    bool wide;
+    uint32_t wl;
+    int rc = check_topk_key(key_col, false, &wide, &wl);
+    if (rc) return rc;
+    if (n == 0) return PQPS_OK;
+    hipStream_t s = pick_stream(ctx, stream);
+    // two stable passes, minor criterion first: the rows ascending, then the sort keys of the rows in that order
+    pqps_sort::Workspace w;
+    uint32_t *ra = nullptr, *rb = nullptr, *va = nullptr, *vb = nullptr;
+    uint64_t *ka = nullptr, *kb = nullptr;
+    hipError_t e = pqps_sort::workspace_alloc(w, n);
+    if (e == hipSuccess) e = hipMalloc((void **)&ra, n * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&rb, n * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&va, n * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&vb, n * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&ka, n * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&kb, n * 8);
+    if (e == hipSuccess) e = hipMemcpyAsync(ra, ids, n * 4, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(va, ids, n * 4, hipMemcpyDeviceToDevice, s);
+    bool in_a = true;
+    if (e == hipSuccess) e = pqps_sort::sort_pairs<uint32_t, false>(w, ra, va, rb, vb, n, 32, ctx->compute_units, s, &in_a);
+    if (e == hipSuccess) {
+        const uint32_t *rows = in_a ? va : vb;
+        uint32_t *rows_b = in_a ? vb : va;
+        uint64_t blocks = (n + kBlock - 1) / kBlock;
+        if (blocks > (uint64_t)ctx->compute_units * 8) blocks = (uint64_t)ctx->compute_units * 8;
+        const void *kcol = key_col ? key_col->data : nullptr;
+        const uint64_t kxor = topk_xor(wide, key_signed, descending);
+        if (wide) hipLaunchKernelGGL(topk_sort_keys_kernel<true>, dim3((uint32_t)blocks), dim3(kBlock), 0, s, rows, n, kcol, wl, kxor, id_base, ka);
+        else hipLaunchKernelGGL(topk_sort_keys_kernel<false>, dim3((uint32_t)blocks), dim3(kBlock), 0, s, rows, n, kcol, wl, kxor, id_base, ka);
+        e = hipGetLastError();
+        bool in_b = true;
+        if (e == hipSuccess) e = pqps_sort::sort_pairs<uint64_t, false>(w, ka, (uint32_t *)rows, kb, rows_b, n, wide ? 64 : 32,
+                                                                        ctx->compute_units, s, &in_b);
+        if (e == hipSuccess) e = hipMemcpyAsync(out_ids, in_b ? rows : rows_b, n * 4, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess && out_keys) e = hipMemcpyAsync(out_keys, in_b ? ka : kb, n * 8, hipMemcpyDeviceToDevice, s);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(ra); (void)hipFree(rb); (void)hipFree(va); (void)hipFree(vb); (void)hipFree(ka); (void)hipFree(kb);
+    pqps_sort::workspace_free(w);
+    if (e != hipSuccess) return fail(PQPS_EHIP, "ORDER BY sort: %s", hipGetErrorString(e));
     return PQPS_OK;
 }
 

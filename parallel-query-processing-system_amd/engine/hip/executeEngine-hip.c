@@ -1229,6 +1229,41 @@ static int project_column(struct query *q, int c, void *const *gathered, bool sc
     return 0;
 }
 
+/* The columns of a columnar result for the `count` rows in the query's lanes (q->count[s] rows of shard s; `scattered`,
+ * sub_pos and tmp as project_column's). */
+static int project_result(struct query *q, const char **selectItems, int numSelectItems, uint64_t count, bool scattered,
+                          unsigned int *const *sub_pos, char *tmp, struct hipColumnarResult *res) {
+    struct hipTable *t = q->t;
+    struct hipSchema schema;
+    hipSchemaOfTable(t, &schema);
+    void *gathered[HIP_MAX_SHARDS];
+    memset(gathered, 0, sizeof gathered);
+    int rc = 0;
+    for (int s = 0; s < q->n_shards && rc == 0; s++)
+        if (q->count[s] && pqps_malloc(hipTableShard(t, s)->ctx, q->count[s] * 8, &gathered[s]) != PQPS_OK) rc = engine_error("projection buffer");
+    for (int j = 0; j < numSelectItems && rc == 0; j++) {
+        res->columnNames[j] = strdup(selectItems[j]);
+        const int c = hipColumnId(selectItems[j]);
+        res->columnKinds[j] = c < 0 ? -1 : schema.col[c].kind;
+        if (c < 0 || count == 0) continue;
+        const uint32_t w = t->col[c].width;
+        if (w == 0) {                                                    /* a single-valued string column: every row carries code 0 */
+            res->values[j] = calloc(count, sizeof(uint32_t));
+            if (!res->values[j]) { fprintf(stderr, "HIP engine: out of memory for the result set\n"); rc = -1; break; }
+            rc = own_dictionary(res, j, &t->dict[c], 4, count);
+            continue;
+        }
+        char *raw = malloc(count * w);
+        if (!raw) { fprintf(stderr, "HIP engine: out of memory for the result set\n"); rc = -1; break; }
+        res->values[j] = raw;
+        rc = project_column(q, c, gathered, scattered, sub_pos, raw, tmp);
+        if (rc == 0 && schema.col[c].kind == HIPKIND_DICT)
+            rc = own_dictionary(res, j, &t->dict[c], w, count);
+    }
+    for (int s = 0; s < q->n_shards; s++) if (gathered[s]) pqps_free(hipTableShard(t, s)->ctx, gathered[s]);
+    return rc;
+}
+
 /* Caller holds the table shared. */
 static int select_columnar(struct engineS *engine, struct hipTable *t, const char **selectItems, int numSelectItems,
                            struct whereClauseS *whereClause, struct hipColumnarResult *res) {
@@ -1241,11 +1276,7 @@ static int select_columnar(struct engineS *engine, struct hipTable *t, const cha
     else for (int s = 0; s < q.n_shards; s++) (void)wait_shard(&q, s);
     const int n_shards = q.n_shards;
     const uint64_t count = rc == 0 ? q.total : 0;
-    struct hipSchema schema;
-    hipSchemaOfTable(t, &schema);
-    void *gathered[HIP_MAX_SHARDS];
     unsigned int *sub_pos[HIP_MAX_SHARDS];
-    memset(gathered, 0, sizeof gathered);
     memset(sub_pos, 0, sizeof sub_pos);
     char *tmp = NULL;
     const bool scattered = rc == 0 && n_shards > 1 && q.n_probes > 0 && count > 0;
@@ -1280,31 +1311,8 @@ static int select_columnar(struct engineS *engine, struct hipTable *t, const cha
         tmp = malloc((biggest ? biggest : 1) * 8);
         if (!tmp) rc = -1;
     }
-    for (int s = 0; s < n_shards && rc == 0; s++)
-        if (q.count[s] && pqps_malloc(hipTableShard(t, s)->ctx, q.count[s] * 8, &gathered[s]) != PQPS_OK) rc = engine_error("projection buffer");
-    for (int j = 0; j < numSelectItems && rc == 0; j++) {
-        res->columnNames[j] = strdup(selectItems[j]);
-        const int c = hipColumnId(selectItems[j]);
-        res->columnKinds[j] = c < 0 ? -1 : schema.col[c].kind;
-        if (c < 0 || count == 0) continue;
-        const uint32_t w = t->col[c].width;
-        if (w == 0) {                                                    /* a single-valued string column: every row carries code 0 */
-            res->values[j] = calloc(count, sizeof(uint32_t));
-            if (!res->values[j]) { fprintf(stderr, "HIP engine: out of memory for the result set\n"); rc = -1; break; }
-            rc = own_dictionary(res, j, &t->dict[c], 4, count);
-            continue;
-        }
-        char *raw = malloc(count * w);
-        if (!raw) { fprintf(stderr, "HIP engine: out of memory for the result set\n"); rc = -1; break; }
-        res->values[j] = raw;
-        rc = project_column(&q, c, gathered, scattered, sub_pos, raw, tmp);
-        if (rc == 0 && schema.col[c].kind == HIPKIND_DICT)
-            rc = own_dictionary(res, j, &t->dict[c], w, count);
-    }
-    for (int s = 0; s < n_shards; s++) {
-        if (gathered[s]) pqps_free(hipTableShard(t, s)->ctx, gathered[s]);
-        free(sub_pos[s]);
-    }
+    if (rc == 0) rc = project_result(&q, selectItems, numSelectItems, count, scattered, sub_pos, tmp, res);
+    for (int s = 0; s < n_shards; s++) free(sub_pos[s]);
     free(tmp);
     res->numRecords = (int)count;
     query_free(&q);
@@ -1335,6 +1343,322 @@ struct hipColumnarResult *executeQuerySelectColumnarHIP(struct engineS *engine, 
     res->success = rc == 0;
     if (rc != 0) res->numRecords = 0;
     TRACE("SELECT (columnar): %d rows x %d columns in %.3f ms\n", res->numRecords, res->numColumns, res->queryTime * 1e3);
+    return res;
+}
+
+/* ---- ORDER BY column [DESC] LIMIT K (include/executeEngine-hip.h) -------------------------------------------------- */
+
+/* One ordered row as the host merges the shards: narrow keys a = (img ^ x) << 32 | row, b = 0; command_id a = v ^ x,
+ * b = row (pqps_filter_topk's keys) -- ascending (a, b) is the answer's order. */
+struct order_key { uint64_t a, b; };
+
+static int order_key_cmp(const void *x, const void *y) {
+    const struct order_key *p = x, *r = y;
+    if (p->a != r->a) return p->a < r->a ? -1 : 1;
+    return p->b < r->b ? -1 : p->b > r->b;
+}
+
+static uint32_t order_key_row(const struct order_key *k, bool wide) { return (uint32_t)(wide ? k->b : k->a); }
+
+/* How the rows of an ORDER BY are found and ordered. */
+struct order_plan {
+    int c;                               /* HIPCOL_* of the order column                                          */
+    bool desc, wide, key_signed;         /* command_id: 128-bit keys; i32 columns: signed images                    */
+    uint32_t k;                          /* the top-K paths: K = limit; 0: the full sort                            */
+    bool fused;                          /* single-pass scan-mode WHERE and K > 0: one fused launch per shard       */
+    pqps_column kcol[HIP_MAX_SHARDS];    /* shard s's key column (sudo_used on the fused path: its bit plane)       */
+    bool no_key;                         /* a single-valued string column: every key 0                             */
+};
+
+/* Shard s's keys of the top-K paths (n of them, K words each, downloaded from `out` on `cs`) appended to keys[*n_keys]. */
+static int order_collect(pqps_ctx *cs, const uint64_t *out_dev, uint64_t n, bool wide, struct order_key *keys, uint64_t *n_keys) {
+    if (n == 0) return 0;
+    uint64_t *h = malloc((size_t)n * (wide ? 16 : 8));
+    if (!h) { fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
+    if (pqps_download(cs, h, out_dev, (size_t)n * (wide ? 16 : 8), NULL) != PQPS_OK) { free(h); return engine_error("ORDER BY download"); }
+    for (uint64_t i = 0; i < n; i++) keys[*n_keys + i] = wide ? (struct order_key){ h[2 * i], h[2 * i + 1] } : (struct order_key){ h[i], 0 };
+    *n_keys += n;
+    free(h);
+    return 0;
+}
+
+/* The top-K paths on every shard: each shard's K best (fused: pqps_filter_topk on the query's lane; otherwise the
+ * selection, left per shard, and pqps_topk_list over every list) into keys[0 .. *n_keys), *matches the selection's rows. */
+static int order_topk(struct query *q, const struct order_plan *op, struct order_key *keys, uint64_t *n_keys, uint64_t *matches) {
+    const uint32_t k = op->k;
+    const size_t out_bytes = ((size_t)k * (op->wide ? 16 : 8) + 15) & ~(size_t)15;
+    void *buf[HIP_MAX_SHARDS] = { NULL };
+    uint64_t got[HIP_MAX_SHARDS] = { 0 };
+    size_t scratch_bytes[HIP_MAX_SHARDS] = { 0 };
+    int rc = 0;
+    *n_keys = 0;
+    *matches = 0;
+    if (!op->fused) {
+        q->per_shard = true;
+        rc = query_issue_all(q);
+        if (rc == 0) rc = query_await(q);
+        if (rc == 0) *matches = q->total;
+    }
+    /* per shard one buffer: [16 B count][out: K keys][scratch] */
+    for (int s = 0; s < q->n_shards && rc == 0; s++) {
+        struct hipTable *sh = hipTableShard(q->t, s);
+        const uint64_t n = op->fused ? sh->n_rows : q->count[s];
+        if (n == 0) continue;
+        scratch_bytes[s] = pqps_topk_scratch_bytes(sh->ctx, n, k, op->wide, op->fused);
+        if (pqps_malloc(sh->ctx, 16 + out_bytes + scratch_bytes[s], &buf[s]) != PQPS_OK) rc = engine_error("ORDER BY scratch");
+    }
+    if (rc == 0 && op->fused) {
+        const struct hipPass *last = &q->plan.pass[0];
+        hipTableLockIssue(q->t);
+        for (int s = 0; s < q->n_shards && rc == 0; s++) {
+            struct hipTable *sh = hipTableShard(q->t, s);
+            struct shard_pred *sp = &q->sp[s];
+            pqps_ctx *ctx = sh->ctx;
+            void *stream = NULL;
+            if (sh->n_rows == 0) continue;
+            if (q->lane >= 0 && pqps_qstream_lane(sh->qs, (uint32_t)q->lane, sh->n_rows, NULL, &ctx, &stream) != PQPS_OK) { rc = engine_error("query lane"); break; }
+            sp->pred = &last->pred;
+            sp->n_cols = last->pred.n_columns;
+            pass_columns(sh, last, NULL, true, sp->cols);
+            char *b = buf[s];
+            if (pqps_filter_topk(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, op->no_key ? NULL : &op->kcol[s], op->key_signed, op->desc,
+                                 (uint32_t)sh->row0, k, b + 16 + out_bytes, scratch_bytes[s], (uint64_t *)(b + 16), (uint64_t *)b, stream) != PQPS_OK)
+                rc = engine_error("ORDER BY filter");
+            /* marked even after a failed call: the lane must not be handed on while a launch of this query runs */
+            if (q->lane >= 0 && pqps_qstream_mark(sh->qs, (uint32_t)q->lane) != PQPS_OK && rc == 0) rc = engine_error("query lane");
+        }
+        hipTableUnlockIssue(q->t);
+        for (int s = 0; s < q->n_shards; s++) if (wait_shard(q, s) != 0 && rc == 0) rc = -1;
+        for (int s = 0; s < q->n_shards && rc == 0; s++) {
+            if (!buf[s]) continue;
+            if (pqps_download(lane_copy_ctx(q, s), &got[s], buf[s], sizeof got[s], NULL) != PQPS_OK) rc = engine_error("ORDER BY count");
+            *matches += got[s];
+        }
+    } else if (rc == 0) {
+        for (int s = 0; s < q->n_shards && rc == 0; s++) {
+            struct hipTable *sh = hipTableShard(q->t, s);
+            if (!buf[s]) continue;
+            char *b = buf[s];
+            got[s] = q->count[s];
+            if (pqps_topk_list(lane_copy_ctx(q, s), op->no_key ? NULL : &op->kcol[s], op->key_signed, op->desc, query_lane(q, s)->ids_dev, q->count[s],
+                               (uint32_t)sh->row0, k, b + 16 + out_bytes, scratch_bytes[s], (uint64_t *)(b + 16), NULL) != PQPS_OK)
+                rc = engine_error("ORDER BY list");
+        }
+    }
+    for (int s = 0; s < q->n_shards && rc == 0; s++)
+        if (buf[s]) rc = order_collect(lane_copy_ctx(q, s), (const uint64_t *)((char *)buf[s] + 16), got[s] < k ? got[s] : k, op->wide, keys, n_keys);
+    for (int s = 0; s < q->n_shards; s++) if (buf[s]) pqps_free(hipTableShard(q->t, s)->ctx, buf[s]);
+    return rc;
+}
+
+/* The full sort: the selection, every shard's list sorted on its device (pqps_sort_list), the first `want` rows of each
+ * downloaded and the shards merged on the host by (key, row) -- one shard needs no keys. */
+static int order_sort(struct query *q, const struct order_plan *op, uint64_t want, uint32_t **rows, uint64_t *n_rows, uint64_t *matches) {
+    q->per_shard = true;
+    int rc = query_issue_all(q);
+    if (rc == 0) rc = query_await(q);
+    if (rc != 0) return rc;
+    *matches = q->total;
+    const int n_shards = q->n_shards;
+    const bool merge = n_shards > 1;
+    uint32_t *ids[HIP_MAX_SHARDS] = { NULL };
+    uint64_t *keys[HIP_MAX_SHARDS] = { NULL }, take[HIP_MAX_SHARDS] = { 0 }, total = 0;
+    for (int s = 0; s < n_shards && rc == 0; s++) {
+        struct hipTable *sh = hipTableShard(q->t, s);
+        const uint64_t n = q->count[s];
+        if (n == 0) continue;
+        pqps_ctx *cs = lane_copy_ctx(q, s);
+        take[s] = n < want ? n : want;
+        uint32_t *ids_dev = NULL;
+        uint64_t *keys_dev = NULL;
+        ids[s] = malloc((size_t)take[s] * sizeof **ids);
+        if (merge) keys[s] = malloc((size_t)take[s] * sizeof **keys);
+        if (!ids[s] || (merge && !keys[s])) { fprintf(stderr, "HIP engine: out of memory\n"); rc = -1; break; }
+        if (pqps_malloc(sh->ctx, n * sizeof(uint32_t), (void **)&ids_dev) != PQPS_OK ||
+            (merge && pqps_malloc(sh->ctx, n * sizeof(uint64_t), (void **)&keys_dev) != PQPS_OK)) rc = engine_error("ORDER BY buffers");
+        else if (pqps_sort_list(cs, op->no_key ? NULL : &op->kcol[s], op->key_signed, op->desc, query_lane(q, s)->ids_dev, n, (uint32_t)sh->row0,
+                                ids_dev, keys_dev, NULL) != PQPS_OK) rc = engine_error("ORDER BY sort");
+        else if (pqps_download(cs, ids[s], ids_dev, (size_t)take[s] * sizeof **ids, NULL) != PQPS_OK ||
+                 (merge && pqps_download(cs, keys[s], keys_dev, (size_t)take[s] * sizeof **keys, NULL) != PQPS_OK)) rc = engine_error("ORDER BY download");
+        if (ids_dev) pqps_free(sh->ctx, ids_dev);
+        if (keys_dev) pqps_free(sh->ctx, keys_dev);
+        total += take[s];
+    }
+    if (total > want) total = want;
+    uint32_t *out = NULL;
+    if (rc == 0 && !merge) { out = ids[0]; ids[0] = NULL; }
+    else if (rc == 0) {
+        out = malloc((size_t)(total ? total : 1) * sizeof *out);
+        if (!out) { fprintf(stderr, "HIP engine: out of memory\n"); rc = -1; }
+        uint64_t at[HIP_MAX_SHARDS] = { 0 };
+        for (uint64_t i = 0; i < total && rc == 0; i++) {              /* (a later shard holds later rows: the keys decide) */
+            int best = -1;
+            struct order_key bk = { 0, 0 };
+            for (int s = 0; s < n_shards; s++) {
+                if (at[s] >= take[s]) continue;
+                const struct order_key ks = { keys[s][at[s]], ids[s][at[s]] };
+                if (best < 0 || order_key_cmp(&ks, &bk) < 0) { best = s; bk = ks; }
+            }
+            out[i] = ids[best][at[best]++];
+        }
+    }
+    for (int s = 0; s < n_shards; s++) { free(ids[s]); free(keys[s]); }
+    if (rc == 0) { *rows = out; *n_rows = total; }
+    else free(out);
+    return rc;
+}
+
+/* The rows of the ORDER BY (caller holds the table shared and the query's lane): *rows (malloc'd) in order, *n_rows of
+ * them, *matches the selection's count. */
+static int order_rows(struct engineS *engine, struct whereClauseS *whereClause, struct query *q, struct order_plan *op, long long limit,
+                      uint32_t **rows, uint64_t *n_rows, uint64_t *matches) {
+    struct hipTable *t = q->t;
+    *rows = NULL;
+    *n_rows = 0;
+    *matches = 0;
+    int rc = bind_where(t, whereClause, &q->plan);
+    q->have_plan = rc == 0;
+    if (rc == 0) {
+        q->n_probes = list_probes(engine, t, whereClause, &q->probes);
+        if (q->n_probes < 0) { q->n_probes = 0; rc = -1; }
+    }
+    if (rc != 0) return rc;
+    uint64_t all = 0;
+    for (int s = 0; s < q->n_shards; s++) all += hipTableShard(t, s)->n_rows;
+    if (all == 0) { *rows = malloc(sizeof **rows); return *rows ? 0 : -1; }      /* an empty table: no rows */
+    const uint32_t kmax = op->wide ? PQPS_TOPK_MAX_WIDE : PQPS_TOPK_MAX;
+    op->k = limit > 0 && limit <= (long long)kmax ? (uint32_t)limit : 0;
+    op->fused = op->k > 0 && q->plan.n_passes == 1 && q->n_probes == 0;
+    op->no_key = t->col[op->c].width == 0;
+    for (int s = 0; s < q->n_shards; s++) {
+        const struct hipTable *sh = hipTableShard(t, s);
+        op->kcol[s] = op->fused && op->c == HIPCOL_SUDO_USED && sh->sudo_bits.data ? sh->sudo_bits : sh->col[op->c];
+    }
+    if (op->k == 0) return order_sort(q, op, limit > 0 ? (uint64_t)limit : UINT64_MAX, rows, n_rows, matches);
+    struct order_key *keys = malloc((size_t)q->n_shards * op->k * sizeof *keys);
+    uint64_t n_keys = 0;
+    if (!keys) { fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
+    rc = order_topk(q, op, keys, &n_keys, matches);
+    if (rc == 0) {
+        qsort(keys, (size_t)n_keys, sizeof *keys, order_key_cmp);
+        const uint64_t n = n_keys < op->k ? n_keys : op->k;
+        *rows = malloc((size_t)(n ? n : 1) * sizeof **rows);
+        if (!*rows) { fprintf(stderr, "HIP engine: out of memory\n"); rc = -1; }
+        else {
+            for (uint64_t i = 0; i < n; i++) (*rows)[i] = order_key_row(&keys[i], op->wide);
+            *n_rows = n;
+        }
+    }
+    free(keys);
+    return rc;
+}
+
+/* The order column's plan, or -1 with the reason on stderr. */
+static int order_plan_init(struct hipTable *t, const char *orderColumn, bool descending, struct order_plan *op) {
+    memset(op, 0, sizeof *op);
+    if (!orderColumn) { fprintf(stderr, "HIP engine: ORDER BY without a column\n"); return -1; }
+    op->c = hipColumnId(orderColumn);
+    if (op->c < 0) { fprintf(stderr, "HIP engine: ORDER BY: unknown column '%s'\n", orderColumn); return -1; }
+    if (t->xch) { fprintf(stderr, "HIP engine: ORDER BY is not exchanged across ranks\n"); return -1; }
+    op->desc = descending;
+    op->wide = op->c == HIPCOL_COMMAND_ID;
+    op->key_signed = k_group_kind[op->c] == HIPKIND_I32;
+    return 0;
+}
+
+long long executeQueryOrderIdsHIP(struct engineS *engine, struct whereClauseS *whereClause, const char *orderColumn,
+                                  bool descending, long long limit, unsigned int **ids, long long *matches, double *queryTime) {
+    const double t0 = now_seconds();
+    if (matches) *matches = 0;
+    if (!engine || !engine->record_block || !ids) { fprintf(stderr, "HIP engine: ORDER BY without an engine or a result\n"); return -1; }
+    *ids = NULL;
+    struct hipTable *t = engine->record_block;
+    struct order_plan op;
+    if (order_plan_init(t, orderColumn, descending, &op) != 0) return -1;
+    hipTableLockShared(t);
+    const int lane = hipTableAcquireLane(t);
+    if (lane == HIP_LANE_REFUSED) { hipTableUnlockShared(t); return -1; }    /* reason on stderr */
+    struct query q;
+    query_init(&q, engine, t, lane, false);
+    uint32_t *rows = NULL;
+    uint64_t n = 0, m = 0;
+    const int rc = order_rows(engine, whereClause, &q, &op, limit, &rows, &n, &m);
+    query_free(&q);
+    hipTableReleaseLane(t, lane);
+    hipTableUnlockShared(t);
+    if (queryTime) *queryTime = now_seconds() - t0;
+    if (rc != 0) { free(rows); return -1; }
+    *ids = rows;
+    if (matches) *matches = (long long)m;
+    return (long long)n;
+}
+
+struct hipColumnarResult *executeQuerySelectOrderedHIP(struct engineS *engine, const char **selectItems, int numSelectItems,
+                                                       struct whereClauseS *whereClause, const char *orderColumn,
+                                                       bool descending, long long limit, long long *matches) {
+    if (matches) *matches = 0;
+    struct hipColumnarResult *res = calloc(1, sizeof *res);
+    if (!res) { perror("Failed to allocate memory for result set"); exit(EXIT_FAILURE); }
+    if (!engine || !engine->record_block) return res;
+    struct hipTable *t = engine->record_block;
+    if (selectItems == NULL || numSelectItems == 0) { selectItems = (const char **)k_all_columns; numSelectItems = 12; }
+    res->numColumns = numSelectItems;
+    res->columnNames = calloc((size_t)numSelectItems, sizeof(char *));
+    res->columnKinds = calloc((size_t)numSelectItems, sizeof(int));
+    res->values = calloc((size_t)numSelectItems, sizeof(void *));
+    res->dictionaries = calloc((size_t)numSelectItems, sizeof(*res->dictionaries));
+    res->dictionarySizes = calloc((size_t)numSelectItems, sizeof(int));
+    if (!res->columnNames || !res->columnKinds || !res->values || !res->dictionaries || !res->dictionarySizes) { perror("Failed to allocate memory for result set"); exit(EXIT_FAILURE); }
+    const double t0 = now_seconds();
+    struct order_plan op;
+    if (order_plan_init(t, orderColumn, descending, &op) != 0) return res;
+    hipTableLockShared(t);
+    const int lane = hipTableAcquireLane(t);
+    if (lane == HIP_LANE_REFUSED) { hipTableUnlockShared(t); return res; }  /* reason on stderr */
+    struct query q;
+    query_init(&q, engine, t, lane, false);
+    uint32_t *rows = NULL;
+    uint64_t n = 0, m = 0;
+    int rc = order_rows(engine, whereClause, &q, &op, limit, &rows, &n, &m);
+    /* the ordered rows become every shard's list in its lane: shard s's k-th row goes to position sub_pos[s][k] */
+    const int n_shards = q.n_shards;
+    unsigned int *sub_pos[HIP_MAX_SHARDS] = { NULL };
+    uint32_t *sub_ids[HIP_MAX_SHARDS] = { NULL };
+    uint64_t biggest = 0;
+    for (int s = 0; s < n_shards && rc == 0; s++) {
+        sub_ids[s] = malloc((size_t)(n ? n : 1) * sizeof **sub_ids);
+        sub_pos[s] = malloc((size_t)(n ? n : 1) * sizeof **sub_pos);
+        if (!sub_ids[s] || !sub_pos[s]) { fprintf(stderr, "HIP engine: out of memory\n"); rc = -1; }
+        q.count[s] = 0;
+    }
+    for (uint64_t i = 0; i < n && rc == 0; i++) {
+        int s = n_shards - 1;
+        while (s > 0 && rows[i] < hipTableShard(t, s)->row0) s--;
+        sub_ids[s][q.count[s]] = rows[i];
+        sub_pos[s][q.count[s]++] = (unsigned int)i;
+    }
+    for (int s = 0; s < n_shards && rc == 0; s++) {
+        struct hipTable *sh = hipTableShard(t, s);
+        struct hipLane *L = query_lane(&q, s);
+        if (q.count[s] > biggest) biggest = q.count[s];
+        if (q.count[s] == 0) continue;
+        if (grow_lane_ids(sh, L, q.count[s]) != 0) rc = -1;
+        else if (pqps_upload(lane_copy_ctx(&q, s), L->ids_dev, sub_ids[s], q.count[s] * sizeof **sub_ids, NULL) != PQPS_OK ||
+                 pqps_upload(lane_copy_ctx(&q, s), L->count_dev, &q.count[s], sizeof(uint64_t), NULL) != PQPS_OK) rc = engine_error("ID upload");
+    }
+    char *tmp = rc == 0 && n_shards > 1 ? malloc((biggest ? biggest : 1) * 8) : NULL;
+    if (rc == 0 && n_shards > 1 && !tmp) rc = -1;
+    if (rc == 0) rc = project_result(&q, selectItems, numSelectItems, n, n_shards > 1, sub_pos, tmp, res);
+    for (int s = 0; s < n_shards; s++) { free(sub_ids[s]); free(sub_pos[s]); }
+    free(tmp);
+    free(rows);
+    query_free(&q);
+    hipTableReleaseLane(t, lane);
+    hipTableUnlockShared(t);
+    res->numRecords = rc == 0 ? (int)n : 0;
+    res->queryTime = now_seconds() - t0;
+    res->success = rc == 0;
+    if (rc == 0 && matches) *matches = (long long)m;
     return res;
 }
 
