@@ -276,6 +276,46 @@ struct hipAggregateResult *executeQueryAggregateHIP(struct engineS *engine, cons
                                                     struct whereClauseS *whereClause);
 void freeAggregateResultHIP(struct hipAggregateResult *result);
 
+/* COUNT(DISTINCT one column), overall or per group (no aggregates in the reference; reached through the C API and the
+ * Python package only, like the grouped COUNT above -- the SQL driver has no COUNT(DISTINCT ...), so its output stays that
+ * of QPESeq).
+ * ROWS: exactly the rows executeQuerySelectIdsHIP(engine, whereClause) returns.  In index mode a row several probed
+ * conditions return more than once is a duplicate: it changes no distinct count, but it counts in `total`, which equals
+ * that call's count.
+ * DISTINCT: the number of different values of `valueColumn` among those rows.  exit_code, user_id, risk_level compare by
+ * signed value, command_id as u64, sudo_used as a bool, string columns by string equality (code equality: a dictionary
+ * holds each string once); a single-valued string column (no device buffer) gives 1 for every group with rows, with no
+ * kernel.  Every one of the 12 columns may be the value column, the group column too (then every group gives 1).
+ * NO GROUP BY (groupColumn == NULL): numGroups is 1 if any row matches and 0 otherwise; keys and keyText are NULL,
+ * groupColumn and groupKind are -1, as in hipAggregateResult.
+ * GROUP BY: the groups, keys, key text and key order of executeQueryGroupCountHIP for the same column and WHERE; a group is
+ * listed iff it has a matching row, i.e. iff distinct[g] >= 1.
+ * REFUSED (success = false, the reason on stderr): an unknown value or group column, and every group-column refusal of
+ * executeQueryGroupCountHIP (command_id, more than 65 536 groups, an engine joined across ranks -- with or without GROUP
+ * BY).  Nothing is refused for the size of the value domain.  A reader like COUNT: shared lock and one query lane; the
+ * lane rules above apply.
+ * Execution: value bins are dictionary codes, 0 / 1, or value - min for an i32 column (the range cached with the table and
+ * widened by INSERT).  With G groups and W = ceil(bins / 32) words, a presence bitmap of G x W x 32 <= 2^30 bits per shard:
+ * a single-pass scan-mode WHERE runs ONE fused filter-and-bitmap launch per shard (pqps_filter_distinct), everything else
+ * the selection and then pqps_distinct_list over each shard's list; shards' bitmaps are OR-ed before the popcount.
+ * command_id, or a bitmap over the cap: the selection, a radix sort of the (group, value) keys of each shard's list
+ * (pqps_distinct_sort), several shards merged on the host with duplicates dropped -- shard counts are never added.  An empty
+ * table, or a WHERE that matches nothing, gives numGroups = 0 with success = true. */
+struct hipDistinctResult {
+    int valueColumn, valueKind;        /* HIPCOL_*, HIPKIND_*                                              */
+    int groupColumn, groupKind;        /* HIPCOL_*, HIPKIND_*; -1 / -1 without GROUP BY                    */
+    int numGroups;
+    long long total;                   /* executeQuerySelectIdsHIP's count                                  */
+    long long *keys;                   /* as hipGroupResult; NULL without GROUP BY                         */
+    char **keyText;                    /* as hipGroupResult; NULL without GROUP BY                         */
+    unsigned long long *distinct;      /* distinct values per group, >= 1                                  */
+    double queryTime;
+    bool success;
+};
+struct hipDistinctResult *executeQueryCountDistinctHIP(struct engineS *engine, const char *valueColumn, const char *groupColumn,
+                                                       struct whereClauseS *whereClause);
+void freeDistinctResultHIP(struct hipDistinctResult *result);
+
 /* ORDER BY one column [ASC | DESC] with LIMIT (the reference parses ORDER BY into ParsedSQL.order_by / order_desc and
  * executes it nowhere; reached through the C API and the Python package only -- the SQL driver still ignores it, so its
  * output stays that of QPESeq).

@@ -504,6 +504,42 @@ int pqps_topk_list(pqps_ctx *ctx, const pqps_column *key_col, int key_signed, in
 int pqps_sort_list(pqps_ctx *ctx, const pqps_column *key_col, int key_signed, int descending, const uint32_t *ids, uint64_t n,
                    uint32_t id_base, uint32_t *out_ids, uint64_t *out_keys, void *stream);
 
+/* ---- COUNT(DISTINCT value column), overall or per group ---------------------------------------------------------------
+ * No counterpart in the reference.  BINS: a value bin is (value - v_base) in 32-bit arithmetic (dictionary codes with
+ * v_base 0, an i32 value minus the column's minimum, the bool byte or bit), a group bin (value - g_base) likewise;
+ * `group_col` NULL means no GROUP BY (n_groups must be 1, every matching row is group 0).  Rows whose value bin is >=
+ * n_values or whose group bin is >= n_groups are left out.  BITMAP (device, u32 words): n_groups rows of
+ * W = ceil(n_values / 32) words, pqps_distinct_bitmap_words(n_values, n_groups) in all; bit v of row g set iff a matching
+ * row has group bin g and value bin v.  The bitmap forms take n_groups x W x 32 <= 2^30 bits (128 MiB) -- wider domains
+ * go through pqps_distinct_sort.  `distinct` (device, n_groups u64; may be NULL where noted): the popcount of every row.
+ * The calls initialise their outputs themselves.
+ *
+ * pqps_filter_distinct: ONE scan of `pred` over rows [0, n_rows) of `cols` (the value and group columns read only in steps
+ *   of 1024 rows that hold a match; 1, 2, 4 bytes wide or a bit plane; the readable-padding rule of pqps_filter_scan
+ *   applies to both).  n_groups x n_values <= 64: per-lane registers; a bitmap of up to 16 384 words: dynamic LDS; larger:
+ *   test-before-set atomics on `bitmap` (a correctness path).  *total (device) = the matching rows.  `distinct` non-NULL:
+ *   the popcount pass too.  Asynchronous on `stream`; the context's timing recorder records it like a COUNT's (the scan's
+ *   start to the last launch's end).
+ * pqps_distinct_list: the same bitmap over an ID list -- ids[0 .. min(*count_dev, capacity)), row = id - id_base < n_rows --
+ *   gathering both columns (1, 2 or 4 bytes wide, no bit plane) per listed row.  Asynchronous.
+ * pqps_distinct_count: distinct[g] = the popcount of row g of a bitmap (e.g. the OR of several shards').  Asynchronous.
+ * pqps_distinct_sort: the sort form for any domain, command_id (8 bytes, unsigned) included: the listed rows' (group,
+ *   value) keys sorted by the stable LSD radix sort, distinct[g] = the keys of group g that differ from their predecessor.
+ *   `out_keys` (may be NULL) receives the sorted keys -- narrow values: n u64 (group bin << 32 | value bin); 8-byte values:
+ *   n u64 values followed by n u32 group bins (group-major, values ascending within a group).  Its scratch is allocated and
+ *   freed by the call.  Synchronous. */
+uint64_t pqps_distinct_bitmap_words(uint32_t n_values, uint32_t n_groups);
+int pqps_filter_distinct(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                         const pqps_column *value_col, uint32_t v_base, uint32_t n_values, const pqps_column *group_col,
+                         uint32_t g_base, uint32_t n_groups, uint32_t *bitmap, uint64_t *total, uint64_t *distinct, void *stream);
+int pqps_distinct_list(pqps_ctx *ctx, const pqps_column *value_col, uint32_t v_base, uint32_t n_values, const pqps_column *group_col,
+                       uint32_t g_base, uint32_t n_groups, uint64_t n_rows, const uint32_t *ids, const uint64_t *count_dev,
+                       uint64_t capacity, uint32_t id_base, uint32_t *bitmap, uint64_t *distinct, void *stream);
+int pqps_distinct_count(pqps_ctx *ctx, const uint32_t *bitmap, uint32_t n_values, uint32_t n_groups, uint64_t *distinct, void *stream);
+int pqps_distinct_sort(pqps_ctx *ctx, const pqps_column *value_col, uint32_t v_base, const pqps_column *group_col, uint32_t g_base,
+                       uint32_t n_groups, const uint32_t *ids, uint64_t n, uint32_t id_base, uint64_t *distinct, uint64_t *out_keys,
+                       void *stream);
+
 /* Checksums of a device-resident ID list: out[0] = sum of ids[i], out[1] = sum of ids[i] * (2 i + 1), both mod 2^64 (the
  * second depends on the order).  Synchronous; what a bench or a test compares two lists with without downloading them. */
 int pqps_ids_checksum(pqps_ctx *ctx, const uint32_t *ids, uint64_t count, uint64_t out[2], void *stream);

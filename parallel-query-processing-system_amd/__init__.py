@@ -114,6 +114,14 @@ class AggregateResult(C.Structure):
                 ("queryTime", C.c_double), ("success", C.c_bool)]
 
 
+class DistinctResult(C.Structure):
+    """struct hipDistinctResult (include/executeEngine-hip.h)."""
+    _fields_ = [("valueColumn", C.c_int), ("valueKind", C.c_int), ("groupColumn", C.c_int), ("groupKind", C.c_int),
+                ("numGroups", C.c_int), ("total", C.c_longlong),
+                ("keys", C.POINTER(C.c_longlong)), ("keyText", C.POINTER(C.c_char_p)), ("distinct", C.POINTER(C.c_ulonglong)),
+                ("queryTime", C.c_double), ("success", C.c_bool)]
+
+
 class ColumnData(C.Structure):
     """struct hipColumnData (include/executeEngine-hip.h)."""
     _fields_ = [("values", C.c_void_p), ("width", C.c_uint), ("on_device", C.c_int),
@@ -427,6 +435,17 @@ def lib():
     L.pqps_filter_aggregate.argtypes = [vp, C.POINTER(Column), u32, u64, C.POINTER(Predicate), C.POINTER(Column), C.POINTER(Column),
                                         u32, u32, vp, vp]
     L.pqps_aggregate_list.argtypes = [vp, C.POINTER(Column), C.POINTER(Column), u64, vp, vp, u64, u32, u32, u32, vp, vp]
+    L.executeQueryCountDistinctHIP.restype = C.POINTER(DistinctResult)
+    L.executeQueryCountDistinctHIP.argtypes = [E, C.c_char_p, C.c_char_p, W]
+    L.freeDistinctResultHIP.argtypes = [C.POINTER(DistinctResult)]
+    L.freeDistinctResultHIP.restype = None
+    L.pqps_distinct_bitmap_words.restype = u64
+    L.pqps_distinct_bitmap_words.argtypes = [u32, u32]
+    L.pqps_filter_distinct.argtypes = [vp, C.POINTER(Column), u32, u64, C.POINTER(Predicate), C.POINTER(Column), u32, u32,
+                                       C.POINTER(Column), u32, u32, vp, vp, vp, vp]
+    L.pqps_distinct_list.argtypes = [vp, C.POINTER(Column), u32, u32, C.POINTER(Column), u32, u32, u64, vp, vp, u64, u32, vp, vp, vp]
+    L.pqps_distinct_count.argtypes = [vp, vp, u32, u32, vp, vp]
+    L.pqps_distinct_sort.argtypes = [vp, C.POINTER(Column), u32, C.POINTER(Column), u32, u32, vp, u64, u32, vp, vp, vp]
     L.executeQueryOrderIdsHIP.restype = C.c_longlong
     L.executeQueryOrderIdsHIP.argtypes = [E, W, C.c_char_p, C.c_bool, C.c_longlong, C.POINTER(C.POINTER(C.c_uint)),
                                           C.POINTER(C.c_longlong), C.POINTER(C.c_double)]
@@ -878,6 +897,30 @@ class HipEngine:
         out = list(ids[:n])
         lib().free(ids)
         return out, int(matches.value)
+
+    def count_distinct_total(self, value_column, group_column=None, chain=None):
+        """executeQueryCountDistinctHIP: ([(key_text, distinct), ...], total) -- the number of different values of
+        `value_column` over the rows select_ids(chain) returns, in the key order of group_count(group_column, chain), or one
+        entry with key_text None without a group column (none when no row matches); total = select_ids(chain)'s length.
+        Raises PqpsError when the engine refuses (reason on stderr)."""
+        wl = WhereList(chain)
+        res = lib().executeQueryCountDistinctHIP(self.e, value_column.encode(), group_column.encode() if group_column else None, wl.ptr)
+        what = f"count_distinct({value_column!r}, {group_column!r})"
+        if not res:
+            raise PqpsError(f"{what}: no result")
+        try:
+            r = res.contents
+            if not r.success:
+                raise PqpsError(f"{what} refused or failed (reason on stderr)")
+            return ([(r.keyText[g].decode("latin-1") if r.groupColumn >= 0 else None, int(r.distinct[g])) for g in range(r.numGroups)],
+                    int(r.total))
+        finally:
+            lib().freeDistinctResultHIP(res)
+
+    def count_distinct(self, value_column, group_column=None, chain=None):
+        """COUNT(DISTINCT value_column) [GROUP BY group_column]: [(key_text, distinct), ...] (count_distinct_total without
+        the total)."""
+        return self.count_distinct_total(value_column, group_column, chain)[0]
 
     def select(self, columns, chain):
         wl = WhereList(chain)

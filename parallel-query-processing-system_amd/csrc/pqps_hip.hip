@@ -24,6 +24,7 @@
 #include "group_kernels.hpp"
 #include "aggregate_kernels.hpp"
 #include "topk_kernels.hpp"
+#include "distinct_kernels.hpp"
 #include "radix_sort.hpp"
 
 namespace {
@@ -3253,6 +3254,253 @@ int pqps_sort_list(pqps_ctx *ctx, const pqps_column *key_col, int key_signed, in
     (void)hipFree(ra); (void)hipFree(rb); (void)hipFree(va); (void)hipFree(vb); (void)hipFree(ka); (void)hipFree(kb);
     pqps_sort::workspace_free(w);
     if (e != hipSuccess) return fail(PQPS_EHIP, "ORDER BY sort: %s", hipGetErrorString(e));
+    return PQPS_OK;
+}
+
+// ---- COUNT(DISTINCT value column) (distinct_kernels.hpp) -------------------------------------------------------------
+// width code of a value / group column of the bitmap forms (1, 2, 4 bytes; a bit plane where the loads take one)
+static int distinct_col(const char *what, const pqps_column *col, bool plane_ok, uint32_t *wl) {
+    const uint32_t w = col->width;
+    if (w != 1 && w != 2 && w != 4 && !(plane_ok && w == PQPS_WIDTH_BITS))
+        return fail(PQPS_EINVAL, "%s column: width %u not in {1,2,4%s}", what, w, plane_ok ? ",bits" : "");
+    if (!col->data || ((uintptr_t)col->data & 15u) != 0) return fail(PQPS_EINVAL, "%s column: NULL or not 16-byte aligned", what);
+    *wl = w == PQPS_WIDTH_BITS ? kWidthLog2Bits : w == 1 ? 0u : w == 2 ? 1u : 2u;
+    return PQPS_OK;
+}
+
+static int check_distinct_bins(const pqps_column *value_col, const pqps_column *group_col, uint32_t n_values, uint32_t n_groups,
+                               bool plane_ok, uint32_t *vwl, uint32_t *gwl) {
+    if (!value_col) return fail(PQPS_EINVAL, "value column is NULL");
+    int rc = distinct_col("value", value_col, plane_ok, vwl);
+    if (rc) return rc;
+    *gwl = 0;
+    if (!group_col && n_groups != 1) return fail(PQPS_EINVAL, "no group column: 1 group, not %u", n_groups);
+    if (group_col && (rc = distinct_col("group", group_col, plane_ok, gwl)) != 0) return rc;
+    if (n_values == 0 || n_groups == 0 || n_groups > kGroupMaxBins) return fail(PQPS_EINVAL, "%u values x %u groups", n_values, n_groups);
+    if (pqps_distinct_bitmap_words(n_values, n_groups) * 32 > kDistMaxBits)
+        return fail(PQPS_EINVAL, "%u values x %u groups: over the bitmap cap of 2^30 bits", n_values, n_groups);
+    return PQPS_OK;
+}
+
+static int distinct_path(uint32_t n_values, uint32_t n_groups) {
+    if ((uint64_t)n_values * n_groups <= kDistRegBits) return DIST_REG;
+    return pqps_distinct_bitmap_words(n_values, n_groups) <= kDistLdsWords ? DIST_LDS : DIST_GLOBAL;
+}
+
+static const char *const k_dist_names[3] = {"DIST_REG", "DIST_LDS", "DIST_GLOBAL"};
+
+uint64_t pqps_distinct_bitmap_words(uint32_t n_values, uint32_t n_groups) {
+    return (uint64_t)n_groups * (((uint64_t)n_values + 31) / 32);
+}
+
+// distinct[0 .. n_groups) = popcount of the bitmap's rows, on `s`; `stop` (may be NULL) recorded at the end
+static int distinct_count_launch(pqps_ctx *ctx, hipStream_t s, const uint32_t *bitmap, uint32_t n_values, uint32_t n_groups,
+                                 uint64_t *distinct, hipEvent_t stop) {
+    HIP_TRY(hipMemsetAsync(distinct, 0, (size_t)n_groups * sizeof(uint64_t), s));
+    const uint64_t nw = ((uint64_t)n_values + 31) / 32;
+    const uint64_t items = (uint64_t)n_groups * ((nw + 255) / 256);
+    uint64_t blocks = (items + kWaves - 1) / kWaves;
+    if (blocks > (uint64_t)ctx->compute_units * 8) blocks = (uint64_t)ctx->compute_units * 8;
+    if (stop) hipExtLaunchKernelGGL(dist_count_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, s, nullptr, stop, 0, bitmap, n_groups, nw,
+                                    (unsigned long long *)distinct);
+    else hipLaunchKernelGGL(dist_count_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, s, bitmap, n_groups, nw, (unsigned long long *)distinct);
+    HIP_TRY(hipGetLastError());
+    return PQPS_OK;
+}
+
+int pqps_filter_distinct(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                         const pqps_column *value_col, uint32_t v_base, uint32_t n_values, const pqps_column *group_col,
+                         uint32_t g_base, uint32_t n_groups, uint32_t *bitmap, uint64_t *total, uint64_t *distinct, void *stream) {
+    if (!ctx || !bitmap || !total) return fail(PQPS_EINVAL, "ctx/bitmap/total is NULL");
+    uint32_t vwl, gwl;
+    int rc = check_distinct_bins(value_col, group_col, n_values, n_groups, true, &vwl, &gwl);
+    if (rc) return rc;
+    rc = check_pred(cols, n_cols, pred);
+    if (rc) return rc;
+    hipStream_t s = pick_stream(ctx, stream);
+    const uint64_t bm_words = pqps_distinct_bitmap_words(n_values, n_groups);
+    HIP_TRY(hipMemsetAsync(bitmap, 0, bm_words * sizeof(uint32_t), s));
+    HIP_TRY(hipMemsetAsync(total, 0, sizeof(uint64_t), s));
+    if (n_rows == 0) return distinct ? distinct_count_launch(ctx, s, bitmap, n_values, n_groups, distinct, nullptr) : PQPS_OK;
+    DistArgs g;
+    memset(&g, 0, sizeof g);
+    fill_args(g.e, cols, n_cols, pred);
+    g.e.n_rows = n_rows;
+    set_streaming(g.e, cols, n_cols, n_rows);
+    const int path = distinct_path(n_values, n_groups);
+    const uint32_t row_words = path == DIST_GLOBAL ? 0u : (uint32_t)bm_words;
+    // persistent grid as pqps_filter_aggregate's: up to 8 workgroups per CU (the LDS form: as many as its bitmap lets into
+    // 160 KiB), never more than one step per wave
+    const uint64_t steps = (n_rows + kStepRows - 1) / kStepRows;
+    const uint32_t lds = path == DIST_LDS ? row_words * (uint32_t)sizeof(uint32_t) : 0u;
+    uint64_t per_cu = path == DIST_LDS ? (160ull << 10) / ((uint64_t)lds + 1024) : 8;
+    if (per_cu > 8) per_cu = 8;
+    if (per_cu < 1) per_cu = 1;
+    const uint64_t want = (steps + kWaves - 1) / kWaves;
+    const uint64_t cap = (uint64_t)ctx->compute_units * per_cu;
+    const uint32_t grid = (uint32_t)(want < cap ? want : cap);
+    // ctx->group_parts: [grid] u64 totals, then [grid][row_words] partial bitmaps
+    rc = grow_group_parts(ctx, s, (size_t)grid * 2 + (size_t)grid * row_words);
+    if (rc) return rc;
+    g.vcol = value_col->data;
+    g.gcol = group_col ? group_col->data : nullptr;
+    g.bitmap = bitmap;
+    g.totals = (uint64_t *)ctx->group_parts;
+    g.parts = ctx->group_parts + (size_t)grid * 2;
+    g.vwidth_log2 = vwl;
+    g.gwidth_log2 = gwl;
+    g.v_base = v_base;
+    g.g_base = g_base;
+    g.n_values = n_values;
+    g.n_groups = n_groups;
+    g.words = (n_values + 31) / 32;
+    typedef void (*dist_fn)(const DistArgs);
+    static const dist_fn fns[3][2][2] = {
+        {{dist_scan_kernel<DIST_REG, false, false>, dist_scan_kernel<DIST_REG, false, true>},
+         {dist_scan_kernel<DIST_REG, true, false>, dist_scan_kernel<DIST_REG, true, true>}},
+        {{dist_scan_kernel<DIST_LDS, false, false>, dist_scan_kernel<DIST_LDS, false, true>},
+         {dist_scan_kernel<DIST_LDS, true, false>, dist_scan_kernel<DIST_LDS, true, true>}},
+        {{dist_scan_kernel<DIST_GLOBAL, false, false>, dist_scan_kernel<DIST_GLOBAL, false, true>},
+         {dist_scan_kernel<DIST_GLOBAL, true, false>, dist_scan_kernel<DIST_GLOBAL, true, true>}},
+    };
+    snprintf(g_kernel, sizeof g_kernel, "dist_scan_kernel<%s, GROUPED=%s, NT=%s>", k_dist_names[path], group_col ? "true" : "false",
+             g.e.streaming ? "true" : "false");
+    const dist_fn k = fns[path][group_col ? 1 : 0][g.e.streaming ? 1 : 0];
+    const bool timed = ctx->timing && ctx->timed < kMaxTimedLaunches;
+    if (timed) hipExtLaunchKernelGGL(k, dim3(grid), dim3(kBlock), lds, s, ctx->ev_start[ctx->timed], ctx->ev_eval[ctx->timed], 0, g);
+    else hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), lds, s, g);
+    HIP_TRY(hipGetLastError());
+    // the partial bitmaps OR-ed and the totals summed (GLOBAL: the totals only)
+    const dim3 og(row_words ? (row_words + 63u) / 64u : 1u, (grid + kDistOrParts - 1) / kDistOrParts);
+    hipEvent_t stop = timed ? ctx->ev_stop[ctx->timed] : nullptr;
+    if (timed && !distinct) hipExtLaunchKernelGGL(dist_or_kernel, og, dim3(kBlock), 0, s, nullptr, stop, 0, (const uint32_t *)g.parts,
+                                                  (const uint64_t *)g.totals, grid, row_words, bitmap, (unsigned long long *)total);
+    else hipLaunchKernelGGL(dist_or_kernel, og, dim3(kBlock), 0, s, (const uint32_t *)g.parts, (const uint64_t *)g.totals, grid, row_words,
+                            bitmap, (unsigned long long *)total);
+    HIP_TRY(hipGetLastError());
+    if (distinct) rc = distinct_count_launch(ctx, s, bitmap, n_values, n_groups, distinct, stop);
+    if (timed) { ctx->stop_is_eval[ctx->timed] = false; ctx->timed++; }
+    return rc;
+}
+
+int pqps_distinct_list(pqps_ctx *ctx, const pqps_column *value_col, uint32_t v_base, uint32_t n_values, const pqps_column *group_col,
+                       uint32_t g_base, uint32_t n_groups, uint64_t n_rows, const uint32_t *ids, const uint64_t *count_dev,
+                       uint64_t capacity, uint32_t id_base, uint32_t *bitmap, uint64_t *distinct, void *stream) {
+    if (!ctx || !bitmap || !count_dev || (capacity && !ids)) return fail(PQPS_EINVAL, "NULL argument");
+    uint32_t vwl, gwl;
+    int rc = check_distinct_bins(value_col, group_col, n_values, n_groups, false, &vwl, &gwl);
+    if (rc) return rc;
+    hipStream_t s = pick_stream(ctx, stream);
+    const uint64_t bm_words = pqps_distinct_bitmap_words(n_values, n_groups);
+    HIP_TRY(hipMemsetAsync(bitmap, 0, bm_words * sizeof(uint32_t), s));
+    if (capacity && n_rows) {
+        uint64_t blocks = (capacity + kBlock - 1) / kBlock;
+        const uint64_t cap = (uint64_t)ctx->compute_units * 4;
+        if (blocks > cap) blocks = cap;
+        const int path = distinct_path(n_values, n_groups);
+        const uint32_t lds = path == DIST_LDS ? (uint32_t)bm_words * (uint32_t)sizeof(uint32_t) : 0u;
+        typedef void (*list_fn)(const void *, uint32_t, const void *, uint32_t, uint64_t, const uint32_t *, const uint64_t *, uint64_t,
+                                uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t *);
+        static const list_fn fns[3][2] = {
+            {dist_list_kernel<DIST_REG, false>, dist_list_kernel<DIST_REG, true>},
+            {dist_list_kernel<DIST_LDS, false>, dist_list_kernel<DIST_LDS, true>},
+            {dist_list_kernel<DIST_GLOBAL, false>, dist_list_kernel<DIST_GLOBAL, true>},
+        };
+        snprintf(g_kernel, sizeof g_kernel, "dist_list_kernel<%s, GROUPED=%s>", k_dist_names[path], group_col ? "true" : "false");
+        hipLaunchKernelGGL(fns[path][group_col ? 1 : 0], dim3((uint32_t)blocks), dim3(kBlock), lds, s, value_col->data, vwl,
+                           group_col ? group_col->data : nullptr, gwl, n_rows, ids, count_dev, capacity, id_base, v_base, n_values,
+                           g_base, n_groups, (n_values + 31u) / 32u, bitmap);
+        HIP_TRY(hipGetLastError());
+    }
+    return distinct ? distinct_count_launch(ctx, s, bitmap, n_values, n_groups, distinct, nullptr) : PQPS_OK;
+}
+
+int pqps_distinct_count(pqps_ctx *ctx, const uint32_t *bitmap, uint32_t n_values, uint32_t n_groups, uint64_t *distinct, void *stream) {
+    if (!ctx || !bitmap || !distinct) return fail(PQPS_EINVAL, "NULL argument");
+    if (n_values == 0 || n_groups == 0 || pqps_distinct_bitmap_words(n_values, n_groups) * 32 > kDistMaxBits)
+        return fail(PQPS_EINVAL, "%u values x %u groups", n_values, n_groups);
+    return distinct_count_launch(ctx, pick_stream(ctx, stream), bitmap, n_values, n_groups, distinct, nullptr);
+}
+
+int pqps_distinct_sort(pqps_ctx *ctx, const pqps_column *value_col, uint32_t v_base, const pqps_column *group_col, uint32_t g_base,
+                       uint32_t n_groups, const uint32_t *ids, uint64_t n, uint32_t id_base, uint64_t *distinct, uint64_t *out_keys,
+                       void *stream) {
+    if (!ctx || !value_col || !distinct || (n && !ids)) return fail(PQPS_EINVAL, "NULL argument");
+    if (n_groups == 0 || n_groups > kGroupMaxBins || (!group_col && n_groups != 1)) return fail(PQPS_EINVAL, "%u groups", n_groups);
+    const bool wide = value_col->width == 8;
+    uint32_t vwl = 3, gwl = 0;
+    int rc = wide ? (value_col->data && ((uintptr_t)value_col->data & 15u) == 0 ? PQPS_OK : fail(PQPS_EINVAL, "value column: NULL or not 16-byte aligned"))
+                  : distinct_col("value", value_col, false, &vwl);
+    if (rc == PQPS_OK && group_col) rc = distinct_col("group", group_col, false, &gwl);
+    if (rc) return rc;
+    hipStream_t s = pick_stream(ctx, stream);
+    HIP_TRY(hipMemsetAsync(distinct, 0, (size_t)n_groups * sizeof(uint64_t), s));
+    snprintf(g_kernel, sizeof g_kernel, "dist_unique_kernel<%s> (sort)", wide ? "wide" : "narrow");
+    if (n == 0) { HIP_TRY(hipStreamSynchronize(s)); return PQPS_OK; }
+    pqps_sort::Workspace w;
+    uint64_t *ka = nullptr, *kb = nullptr, *vf = nullptr;
+    uint32_t *ga = nullptr, *gb = nullptr, *pa = nullptr, *pb = nullptr;
+    hipError_t e = pqps_sort::workspace_alloc(w, n);
+    if (e == hipSuccess) e = hipMalloc((void **)&ka, n * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&kb, n * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&ga, n * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&gb, n * 4);
+    uint64_t blocks = (n + kBlock - 1) / kBlock;
+    if (blocks > (uint64_t)ctx->compute_units * 8) blocks = (uint64_t)ctx->compute_units * 8;
+    const dim3 grid((uint32_t)blocks);
+    const void *gdata = group_col ? group_col->data : nullptr;
+    const uint64_t *keys = nullptr;                              // the sorted keys the boundary kernel reads
+    const uint32_t *grps = nullptr;                              // (wide) their groups
+    if (e == hipSuccess && !wide) {
+        // one u64 per row, (group << 32 | value image): one sort by the whole key (the payload is not read)
+        hipLaunchKernelGGL(dist_keys_kernel<false>, grid, dim3(kBlock), 0, s, value_col->data, vwl, gdata, gwl, ids, n, id_base, v_base,
+                           g_base, n_groups, ka, (uint32_t *)nullptr);
+        e = hipGetLastError();
+        bool in_a = true;
+        if (e == hipSuccess) e = pqps_sort::sort_pairs<uint64_t, false>(w, ka, ga, kb, gb, n, 64, ctx->compute_units, s, &in_a);
+        keys = in_a ? ka : kb;
+    } else if (e == hipSuccess) {
+        // (value, group): by value, then stably by group -- the groups carry the positions of the value order
+        hipLaunchKernelGGL(dist_keys_kernel<true>, grid, dim3(kBlock), 0, s, value_col->data, vwl, gdata, gwl, ids, n, id_base, v_base,
+                           g_base, n_groups, ka, ga);
+        e = hipGetLastError();
+        bool in_a = true;
+        if (e == hipSuccess) e = pqps_sort::sort_pairs<uint64_t, false>(w, ka, ga, kb, gb, n, 64, ctx->compute_units, s, &in_a);
+        keys = in_a ? ka : kb;
+        grps = in_a ? ga : gb;
+        if (e == hipSuccess && n_groups > 1) {
+            uint32_t *g_in = in_a ? ga : gb, *g_out = in_a ? gb : ga;
+            if (e == hipSuccess) e = hipMalloc((void **)&pa, n * 4);
+            if (e == hipSuccess) e = hipMalloc((void **)&pb, n * 4);
+            if (e == hipSuccess) e = hipMalloc((void **)&vf, n * 8);
+            if (e == hipSuccess) { hipLaunchKernelGGL(dist_iota_kernel, grid, dim3(kBlock), 0, s, pa, n); e = hipGetLastError(); }
+            bool g_in_a = true;
+            if (e == hipSuccess) e = pqps_sort::sort_pairs<uint32_t, false>(w, g_in, pa, g_out, pb, n, 32, ctx->compute_units, s, &g_in_a);
+            if (e == hipSuccess) {
+                hipLaunchKernelGGL(dist_permute_kernel, grid, dim3(kBlock), 0, s, keys, g_in_a ? pa : pb, n, vf);
+                e = hipGetLastError();
+            }
+            keys = vf;
+            grps = g_in_a ? g_in : g_out;
+        }
+    }
+    if (e == hipSuccess) {
+        if (wide) hipLaunchKernelGGL(dist_unique_kernel<true>, grid, dim3(kBlock), 0, s, keys, grps, n, n_groups, (unsigned long long *)distinct);
+        else hipLaunchKernelGGL(dist_unique_kernel<false>, grid, dim3(kBlock), 0, s, keys, (const uint32_t *)nullptr, n, n_groups,
+                                (unsigned long long *)distinct);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && out_keys) {
+        e = hipMemcpyAsync(out_keys, keys, n * 8, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess && wide) e = hipMemcpyAsync(out_keys + n, grps, n * 4, hipMemcpyDeviceToDevice, s);   // then n u32 groups
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(ka); (void)hipFree(kb); (void)hipFree(ga); (void)hipFree(gb);
+    if (pa) (void)hipFree(pa);
+    if (pb) (void)hipFree(pb);
+    if (vf) (void)hipFree(vf);
+    pqps_sort::workspace_free(w);
+    if (e != hipSuccess) return fail(PQPS_EHIP, "COUNT(DISTINCT) sort: %s", hipGetErrorString(e));
     return PQPS_OK;
 }
 

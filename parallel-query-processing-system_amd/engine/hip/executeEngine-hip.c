@@ -1061,6 +1061,296 @@ void freeAggregateResultHIP(struct hipAggregateResult *res) {
     free(res);
 }
 
+/* ---- COUNT(DISTINCT value column) (include/executeEngine-hip.h) ---------------------------------------------------- */
+
+#define HIP_DISTINCT_MAX_BITS (1ull << 30)          /* the bitmap forms' cap per shard: 128 MiB */
+
+/* How COUNT(DISTINCT) reads its value column. */
+struct distinct_plan {
+    int v;                               /* HIPCOL_* of the value column                                             */
+    bool single;                         /* a single-valued dictionary column (no buffer): 1 per non-empty group    */
+    bool sort;                           /* command_id, or a bitmap above the cap: the sort form                    */
+    uint32_t v_base, n_values;           /* value bins: (value - v_base), n_values of them (the bitmap forms)        */
+    pqps_column vcol[HIP_MAX_SHARDS];    /* shard s's value column (sudo_used on the fused path: its bit plane)      */
+};
+
+/* The value side of the plan (gp already made by group_plan_init, not empty). */
+static int distinct_plan_init(struct query *q, const struct group_plan *gp, int v, struct distinct_plan *dp) {
+    struct hipTable *t = q->t;
+    memset(dp, 0, sizeof *dp);
+    dp->v = v;
+    dp->n_values = 1;
+    const int kind = k_group_kind[v];
+    uint64_t dv = 1;
+    if (kind == HIPKIND_U64) dp->sort = true;
+    else if (kind == HIPKIND_DICT) { dp->single = t->col[v].width == 0; dv = t->dict[v].count > 0 ? (uint64_t)t->dict[v].count : 1u; }
+    else if (kind == HIPKIND_BOOL) dv = 2;
+    else {
+        int32_t lo = 0, hi = -1;
+        const int rc = column_bounds(q, v, &lo, &hi);
+        if (rc != 0) return rc;
+        dv = lo > hi ? 1u : (uint64_t)((int64_t)hi - (int64_t)lo) + 1u;
+        dp->v_base = (uint32_t)lo;
+    }
+    /* (dv <= 2^32: an i32 range over the cap goes to the sort form, whose value image is 32 bits) */
+    if (!dp->sort && (uint64_t)gp->n_bins * ((dv + 31) / 32) * 32 > HIP_DISTINCT_MAX_BITS) dp->sort = true;
+    if (!dp->sort) dp->n_values = (uint32_t)dv;
+    for (int s = 0; s < q->n_shards; s++) {
+        const struct hipTable *sh = hipTableShard(t, s);
+        dp->vcol[s] = gp->fused && !dp->sort && v == HIPCOL_SUDO_USED && sh->sudo_bits.data ? sh->sudo_bits : sh->col[v];
+    }
+    return 0;
+}
+
+/* The rows of every group (counts[0 .. n_bins)), as executeQueryGroupCountHIP finds them. */
+static int group_counts(struct query *q, const struct group_plan *gp, uint64_t *counts) {
+    if (!gp->single && gp->c >= 0) return group_bins(q, gp, -1, counts);
+    /* one group: the number of rows the selection returns (scan mode: the count, no list) */
+    q->count_only = q->n_probes == 0;
+    int rc = query_issue_all(q);
+    if (rc == 0) rc = query_await(q);
+    if (rc == 0) counts[0] = q->total;
+    return rc;
+}
+
+/* The bitmap forms on every shard: one shard pops its bitmap on its device; several download theirs, OR them on the host
+ * and pop the union on the first shard's device -- shard counts are never added.  distinct[0 .. n_bins), *total the rows. */
+static int distinct_bitmap(struct query *q, const struct group_plan *gp, const struct distinct_plan *dp, uint64_t *distinct, uint64_t *total) {
+    const uint32_t G = gp->n_bins, D = dp->n_values;
+    const uint64_t words = pqps_distinct_bitmap_words(D, G);
+    const size_t head = 16 + (((size_t)G * 8 + 15) & ~(size_t)15);   /* [total][distinct][bitmap] */
+    const size_t bytes = head + words * 4;
+    const bool grouped = gp->c >= 0 && !gp->single;
+    const bool multi = q->n_shards > 1;
+    void *buf[HIP_MAX_SHARDS] = { NULL };
+    bool filled[HIP_MAX_SHARDS] = { false };
+    int rc = 0;
+    *total = 0;
+    for (int s = 0; s < q->n_shards && rc == 0; s++)
+        if (pqps_malloc(hipTableShard(q->t, s)->ctx, bytes, &buf[s]) != PQPS_OK) rc = engine_error("COUNT(DISTINCT) bitmap");
+#define DBUF_TOTAL(s) ((uint64_t *)buf[s])
+#define DBUF_DISTINCT(s) ((uint64_t *)((char *)buf[s] + 16))
+#define DBUF_BITMAP(s) ((uint32_t *)((char *)buf[s] + head))
+    if (rc == 0 && gp->fused) {
+        const struct hipPass *last = &q->plan.pass[0];
+        hipTableLockIssue(q->t);
+        for (int s = 0; s < q->n_shards && rc == 0; s++) {
+            struct hipTable *sh = hipTableShard(q->t, s);
+            struct shard_pred *sp = &q->sp[s];
+            pqps_ctx *ctx = sh->ctx;
+            void *stream = NULL;
+            if (sh->n_rows == 0) continue;
+            if (q->lane >= 0 && pqps_qstream_lane(sh->qs, (uint32_t)q->lane, sh->n_rows, NULL, &ctx, &stream) != PQPS_OK) { rc = engine_error("query lane"); break; }
+            sp->pred = &last->pred;
+            sp->n_cols = last->pred.n_columns;
+            pass_columns(sh, last, NULL, true, sp->cols);
+            if (pqps_filter_distinct(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, &dp->vcol[s], dp->v_base, D, grouped ? &gp->gcol[s] : NULL,
+                                     gp->bin_base, G, DBUF_BITMAP(s), DBUF_TOTAL(s), multi ? NULL : DBUF_DISTINCT(s), stream) != PQPS_OK)
+                rc = engine_error("COUNT(DISTINCT) filter");
+            else filled[s] = true;
+            /* marked even after a failed call: the lane must not be handed on while a launch of this query runs */
+            if (q->lane >= 0 && pqps_qstream_mark(sh->qs, (uint32_t)q->lane) != PQPS_OK && rc == 0) rc = engine_error("query lane");
+        }
+        hipTableUnlockIssue(q->t);
+        for (int s = 0; s < q->n_shards; s++) if (wait_shard(q, s) != 0 && rc == 0) rc = -1;
+        for (int s = 0; s < q->n_shards && rc == 0; s++) {
+            uint64_t n = 0;
+            if (!filled[s]) continue;
+            if (pqps_download(lane_copy_ctx(q, s), &n, DBUF_TOTAL(s), sizeof n, NULL) != PQPS_OK) rc = engine_error("COUNT(DISTINCT) total");
+            *total += n;
+        }
+    } else if (rc == 0) {
+        q->per_shard = true;
+        rc = query_issue_all(q);
+        if (rc == 0) rc = query_await(q);
+        if (rc == 0) *total = q->total;
+        for (int s = 0; s < q->n_shards && rc == 0; s++) {
+            const struct hipTable *sh = hipTableShard(q->t, s);
+            struct hipLane *L = query_lane(q, s);
+            if (q->count[s] == 0) continue;
+            if (pqps_distinct_list(lane_copy_ctx(q, s), &dp->vcol[s], dp->v_base, D, grouped ? &gp->gcol[s] : NULL, gp->bin_base, G, sh->n_rows,
+                                   L->ids_dev, L->count_dev, q->count[s], (uint32_t)sh->row0, DBUF_BITMAP(s), multi ? NULL : DBUF_DISTINCT(s), NULL) != PQPS_OK)
+                rc = engine_error("COUNT(DISTINCT) list");
+            else filled[s] = true;
+        }
+    }
+    if (rc == 0 && !multi) {
+        if (filled[0] && pqps_download(lane_copy_ctx(q, 0), distinct, DBUF_DISTINCT(0), (size_t)G * 8, NULL) != PQPS_OK) rc = engine_error("COUNT(DISTINCT) download");
+    } else if (rc == 0) {
+        uint32_t *merged = calloc(words, sizeof *merged), *part = malloc(words * sizeof *part);
+        if (!merged || !part) { fprintf(stderr, "HIP engine: out of memory\n"); rc = -1; }
+        bool any = false;
+        for (int s = 0; s < q->n_shards && rc == 0; s++) {
+            if (!filled[s]) continue;
+            if (pqps_download(lane_copy_ctx(q, s), part, DBUF_BITMAP(s), words * 4, NULL) != PQPS_OK) { rc = engine_error("COUNT(DISTINCT) download"); break; }
+            for (uint64_t i = 0; i < words; i++) merged[i] |= part[i];
+            any = true;
+        }
+        pqps_ctx *c0 = lane_copy_ctx(q, 0);
+        if (rc == 0 && any && (pqps_upload(c0, DBUF_BITMAP(0), merged, words * 4, NULL) != PQPS_OK ||
+                               pqps_distinct_count(c0, DBUF_BITMAP(0), D, G, DBUF_DISTINCT(0), NULL) != PQPS_OK ||
+                               pqps_download(c0, distinct, DBUF_DISTINCT(0), (size_t)G * 8, NULL) != PQPS_OK))
+            rc = engine_error("COUNT(DISTINCT) merge");
+        free(merged);
+        free(part);
+    }
+#undef DBUF_TOTAL
+#undef DBUF_DISTINCT
+#undef DBUF_BITMAP
+    for (int s = 0; s < q->n_shards; s++) if (buf[s]) pqps_free(hipTableShard(q->t, s)->ctx, buf[s]);
+    return rc;
+}
+
+/* One shard's sorted keys on the host, as (group bin, value) pairs in ascending order. */
+struct distinct_keys { const uint64_t *k; const uint32_t *g; uint64_t n, at; bool wide; };
+
+static void distinct_key_at(const struct distinct_keys *d, uint64_t i, uint64_t *g, uint64_t *v) {
+    if (d->wide) { *g = d->g[i]; *v = d->k[i]; }
+    else { *g = d->k[i] >> 32; *v = d->k[i] & 0xFFFFFFFFull; }
+}
+
+/* The sort form: the selection, every shard's list sorted on its device (pqps_distinct_sort).  One shard counts on its
+ * device; several download their sorted keys and are merged on the host with duplicates dropped. */
+static int distinct_sort(struct query *q, const struct group_plan *gp, const struct distinct_plan *dp, uint64_t *distinct, uint64_t *total) {
+    const uint32_t G = gp->n_bins;
+    const bool grouped = gp->c >= 0 && !gp->single;
+    const bool wide = dp->v == HIPCOL_COMMAND_ID;
+    const bool multi = q->n_shards > 1;
+    q->per_shard = true;
+    int rc = query_issue_all(q);
+    if (rc == 0) rc = query_await(q);
+    if (rc != 0) return rc;
+    *total = q->total;
+    struct distinct_keys keys[HIP_MAX_SHARDS];
+    void *host[HIP_MAX_SHARDS] = { NULL };
+    memset(keys, 0, sizeof keys);
+    for (int s = 0; s < q->n_shards && rc == 0; s++) {
+        struct hipTable *sh = hipTableShard(q->t, s);
+        const uint64_t n = q->count[s];
+        if (n == 0) continue;
+        pqps_ctx *cs = lane_copy_ctx(q, s);
+        const size_t key_bytes = (size_t)n * (wide ? 12 : 8);
+        void *dev = NULL;
+        if (pqps_malloc(sh->ctx, (size_t)G * 8 + (multi ? key_bytes : 0), &dev) != PQPS_OK) { rc = engine_error("COUNT(DISTINCT) buffers"); break; }
+        uint64_t *keys_dev = multi ? (uint64_t *)((char *)dev + (size_t)G * 8) : NULL;
+        if (pqps_distinct_sort(cs, &sh->col[dp->v], dp->v_base, grouped ? &sh->col[gp->c] : NULL, gp->bin_base, G, query_lane(q, s)->ids_dev, n,
+                               (uint32_t)sh->row0, dev, keys_dev, NULL) != PQPS_OK) rc = engine_error("COUNT(DISTINCT) sort");
+        else if (!multi) { if (pqps_download(cs, distinct, dev, (size_t)G * 8, NULL) != PQPS_OK) rc = engine_error("COUNT(DISTINCT) download"); }
+        else if (!(host[s] = malloc(key_bytes))) { fprintf(stderr, "HIP engine: out of memory\n"); rc = -1; }
+        else if (pqps_download(cs, host[s], keys_dev, key_bytes, NULL) != PQPS_OK) rc = engine_error("COUNT(DISTINCT) download");
+        else keys[s] = (struct distinct_keys){ host[s], wide ? (const uint32_t *)((uint64_t *)host[s] + n) : NULL, n, 0, wide };
+        pqps_free(sh->ctx, dev);
+    }
+    if (rc == 0 && multi) {                                              /* k-way merge by (group, value), each key once */
+        bool have_last = false;
+        uint64_t lg = 0, lv = 0;
+        for (;;) {
+            int best = -1;
+            uint64_t bg = 0, bv = 0;
+            for (int s = 0; s < q->n_shards; s++) {
+                if (keys[s].at >= keys[s].n) continue;
+                uint64_t g, v;
+                distinct_key_at(&keys[s], keys[s].at, &g, &v);
+                if (best < 0 || g < bg || (g == bg && v < bv)) { best = s; bg = g; bv = v; }
+            }
+            if (best < 0) break;
+            keys[best].at++;
+            if (have_last && bg == lg && bv == lv) continue;
+            have_last = true;
+            lg = bg;
+            lv = bv;
+            if (bg < G) distinct[bg]++;
+        }
+    }
+    for (int s = 0; s < q->n_shards; s++) free(host[s]);
+    return rc;
+}
+
+/* distinct[0 .. n_bins) into the result: the groups with rows, in bin order */
+static int distinct_result_fill(struct hipDistinctResult *res, const struct hipTable *t, const uint64_t *distinct, uint32_t n_bins, int32_t lo) {
+    int n = 0;
+    for (uint32_t k = 0; k < n_bins; k++) n += distinct[k] != 0;
+    const bool grouped = res->groupColumn >= 0;
+    res->distinct = calloc((size_t)n + 1, sizeof *res->distinct);
+    if (grouped) {
+        res->keys = calloc((size_t)n + 1, sizeof *res->keys);
+        res->keyText = calloc((size_t)n + 1, sizeof *res->keyText);
+    }
+    if (!res->distinct || (grouped && (!res->keys || !res->keyText))) { fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
+    int g = 0;
+    for (uint32_t k = 0; k < n_bins; k++) {
+        if (!distinct[k]) continue;
+        if (grouped) {
+            char buf[32];
+            res->keyText[g] = strdup(group_key(t, res->groupColumn, res->groupKind, k, lo, &res->keys[g], buf, sizeof buf));
+            if (!res->keyText[g]) { res->numGroups = g; fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
+        }
+        res->distinct[g++] = distinct[k];
+    }
+    res->numGroups = n;
+    return 0;
+}
+
+struct hipDistinctResult *executeQueryCountDistinctHIP(struct engineS *engine, const char *valueColumn, const char *groupColumn,
+                                                       struct whereClauseS *whereClause) {
+    const double t0 = now_seconds();
+    struct hipDistinctResult *res = calloc(1, sizeof *res);
+    if (!res) { fprintf(stderr, "HIP engine: out of memory\n"); return NULL; }
+    res->valueColumn = res->valueKind = res->groupColumn = res->groupKind = -1;
+    if (!engine || !engine->record_block || !valueColumn) { fprintf(stderr, "HIP engine: COUNT(DISTINCT) without an engine or a value column\n"); return res; }
+    const int v = hipColumnId(valueColumn);
+    if (v < 0) { fprintf(stderr, "HIP engine: COUNT(DISTINCT): unknown value column '%s'\n", valueColumn); return res; }
+    const int c = groupColumn ? group_column_id("COUNT(DISTINCT)", groupColumn) : -1;
+    if (groupColumn && c < 0) return res;
+    struct hipTable *t = engine->record_block;
+    if (t->xch) { fprintf(stderr, "HIP engine: COUNT(DISTINCT) is not exchanged across ranks\n"); return res; }
+    res->valueColumn = v;
+    res->valueKind = k_group_kind[v];
+    res->groupColumn = c;
+    res->groupKind = c >= 0 ? k_group_kind[c] : -1;
+    hipTableLockShared(t);
+    const int lane = hipTableAcquireLane(t);
+    if (lane == HIP_LANE_REFUSED) { hipTableUnlockShared(t); return res; }  /* reason on stderr */
+    struct query q;
+    query_init(&q, engine, t, lane, false);
+    uint64_t *distinct = NULL, total = 0;
+    struct group_plan gp;
+    struct distinct_plan dp;
+    int rc = group_plan_init(engine, whereClause, &q, c, groupColumn, "COUNT(DISTINCT)", &gp);
+    if (rc == 0 && !gp.empty) {
+        distinct = calloc(gp.n_bins, sizeof *distinct);
+        if (!distinct) { fprintf(stderr, "HIP engine: out of memory\n"); rc = -1; }
+    }
+    if (rc == 0 && !gp.empty) rc = distinct_plan_init(&q, &gp, v, &dp);
+    if (rc == 0 && !gp.empty) {
+        if (dp.single) {                                                 /* one value: 1 for every group with rows */
+            rc = group_counts(&q, &gp, distinct);
+            for (uint32_t k = 0; k < gp.n_bins && rc == 0; k++) { total += distinct[k]; distinct[k] = distinct[k] != 0; }
+        } else if (dp.sort) {
+            rc = distinct_sort(&q, &gp, &dp, distinct, &total);
+        } else {
+            rc = distinct_bitmap(&q, &gp, &dp, distinct, &total);
+        }
+    }
+    res->total = (long long)total;
+    if (rc == 0 && distinct_result_fill(res, t, distinct ? distinct : (uint64_t[1]){ 0 }, gp.empty ? 0u : gp.n_bins, gp.lo) == 0) res->success = true;
+    free(distinct);
+    query_free(&q);
+    hipTableReleaseLane(t, lane);
+    hipTableUnlockShared(t);
+    res->queryTime = now_seconds() - t0;
+    return res;
+}
+
+void freeDistinctResultHIP(struct hipDistinctResult *res) {
+    if (!res) return;
+    for (int g = 0; g < res->numGroups && res->keyText; g++) free(res->keyText[g]);
+    free(res->keyText);
+    free(res->keys);
+    free(res->distinct);
+    free(res);
+}
+
 /* ---- projection ------------------------------------------------------------------ */
 
 /* get_attribute_string_value, S:216-248, with the column resolved once per query
