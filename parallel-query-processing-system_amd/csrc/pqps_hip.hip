@@ -511,7 +511,7 @@ struct pqps_ctx {
     long opt_list16, opt_list16_min, opt_list16_min_u8, opt_list_max, opt_list_max_u8, opt_tiny_max, opt_expand_lag, opt_sum_lag, opt_tune;
     void *sort_tmp;
     size_t sort_tmp_bytes;
-    uint32_t *group_parts;      // grouped COUNT / aggregates: partial rows of the fused scan's workgroups (grown on demand)
+    uint32_t *group_parts;      // every fused scan (group / aggregate / distinct): its workgroups' partial results (grow_group_parts)
     size_t group_parts_words;
     // optional per-launch timing (bench.py roofline)
     bool timing;
@@ -853,6 +853,83 @@ uint32_t eval_grid(pqps_ctx *ctx, uint64_t steps, bool streaming, uint32_t steps
     }
     const uint64_t g = want < cap ? want : cap;
     return (uint32_t)(g ? g : 1);
+}
+
+// ---- host scaffolding of the fused filter-and-aggregate scans ------------------------------------------------------
+// Grouped COUNT(*), SUM / MIN / MAX, ORDER BY .. LIMIT and COUNT(DISTINCT) differ in their kernels; what is around the
+// kernels is here, once.
+
+// The persistent grid of a fused scan: up to 8 workgroups per CU, as many as `lds_bytes` of dynamic LDS each let into
+// 160 KiB, never more than one step per wave; at least 1.
+uint32_t fused_grid(const pqps_ctx *ctx, uint64_t n_rows, uint64_t lds_bytes) {
+    const uint64_t steps = (n_rows + kStepRows - 1) / kStepRows;
+    uint64_t per_cu = (160ull << 10) / (lds_bytes + 1024);
+    if (per_cu > 8) per_cu = 8;
+    if (per_cu < 1) per_cu = 1;
+    const uint64_t want = (steps + kWaves - 1) / kWaves;
+    const uint64_t cap = (uint64_t)ctx->compute_units * per_cu;
+    const uint64_t grid = want < cap ? want : cap;
+    return (uint32_t)(grid ? grid : 1);
+}
+
+// The grid of a kernel that strides over n items, one per thread: at most `per_cu` workgroups per CU.
+uint32_t list_grid(const pqps_ctx *ctx, uint64_t n, uint32_t per_cu) {
+    const uint64_t blocks = (n + kBlock - 1) / kBlock, cap = (uint64_t)ctx->compute_units * per_cu;
+    return (uint32_t)(blocks < cap ? blocks : cap);
+}
+
+// The predicate half of a fused scan's (zeroed) args: checked, filled in, with the row count and the load flavour.
+int fused_args(EvalArgs &e, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred) {
+    const int rc = check_pred(cols, n_cols, pred);
+    if (rc) return rc;
+    fill_args(e, cols, n_cols, pred);
+    e.n_rows = n_rows;
+    set_streaming(e, cols, n_cols, n_rows);
+    return PQPS_OK;
+}
+
+// *wl = the width code the kernels' loads take for the `what` ("group", "value", "key") column: 1, 2 or 4 bytes, 8 where
+// `wide_ok`, a bit plane where `plane_ok`.  Its data must be there, and 16-byte aligned where `aligned` (the fused scans'
+// vector loads; a kernel that gathers by row does not care).
+int column_width_code(const char *what, const pqps_column *col, bool plane_ok, bool wide_ok, bool aligned, uint32_t *wl) {
+    const uint32_t w = col->width;
+    if (w != 1 && w != 2 && w != 4 && !(wide_ok && w == 8) && !(plane_ok && w == PQPS_WIDTH_BITS))
+        return fail(PQPS_EINVAL, "%s column: width %u not in {1,2,4%s%s}", what, w, wide_ok ? ",8" : "", plane_ok ? ",bits" : "");
+    if (!col->data || (aligned && ((uintptr_t)col->data & 15u) != 0))
+        return fail(PQPS_EINVAL, "%s column: NULL%s", what, aligned ? " or not 16-byte aligned" : "");
+    *wl = w == PQPS_WIDTH_BITS ? kWidthLog2Bits : w == 1 ? 0u : w == 2 ? 1u : w == 4 ? 2u : 3u;
+    return PQPS_OK;
+}
+
+// One launch on `s` of 256-thread workgroups.  `stop` (may be NULL) rides on the kernel's own dispatch packet and is
+// ready when it has finished: see run_filter.
+template <typename K, typename... A>
+int launch_stop(K k, dim3 grid, uint32_t lds, hipStream_t s, hipEvent_t stop, A... args) {
+    if (stop) hipExtLaunchKernelGGL(k, grid, dim3(kBlock), lds, s, nullptr, stop, 0, args...);
+    else hipLaunchKernelGGL(k, grid, dim3(kBlock), lds, s, args...);
+    HIP_TRY(hipGetLastError());
+    return PQPS_OK;
+}
+
+// The scan kernel of a fused query.  Where the context records timings it takes the next record's start and eval
+// events, and *stop is the record's stop event for the LAST follow-up launch of the query (launch_stop); else *stop is
+// NULL.  fused_close() after the last launch, whatever that returned.
+template <typename Args>
+int fused_launch(pqps_ctx *ctx, void (*k)(const Args), uint32_t grid, uint32_t lds, hipStream_t s, const Args &g, hipEvent_t *stop) {
+    const bool timed = ctx->timing && ctx->timed < kMaxTimedLaunches;
+    *stop = timed ? ctx->ev_stop[ctx->timed] : nullptr;
+    if (timed) hipExtLaunchKernelGGL(k, dim3(grid), dim3(kBlock), lds, s, ctx->ev_start[ctx->timed], ctx->ev_eval[ctx->timed], 0, g);
+    else hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), lds, s, g);
+    HIP_TRY(hipGetLastError());
+    return PQPS_OK;
+}
+
+// Closes the timing record fused_launch() opened (`stop` as it left it).  `stop_is_eval`: no follow-up kernel took
+// `stop`, the scan's eval event is the end of the query.
+void fused_close(pqps_ctx *ctx, hipEvent_t stop, bool stop_is_eval) {
+    if (!stop) return;
+    ctx->stop_is_eval[ctx->timed] = stop_is_eval;
+    ctx->timed++;
 }
 
 // Placement in the grid.  The chip has ~8 workgroups per CU in flight, i.e. `base` groups, and a round of loads
@@ -2814,7 +2891,9 @@ int pqps_ids_checksum(pqps_ctx *ctx, const uint32_t *ids, uint64_t count, uint64
 }
 
 // ---- grouped COUNT(*) (group_kernels.hpp) --------------------------------------------------------------------------
-// ctx->group_parts holds at least `words` u32 words (the fused scans' partial rows)
+// ctx->group_parts holds at least `words` u32 words.  The name is grouped COUNT's; all four fused scans keep what their
+// workgroups hand to the follow-up kernel here (partial histograms, aggregate tables, bitmaps and totals), one query at a
+// time per context.
 static int grow_group_parts(pqps_ctx *ctx, hipStream_t s, size_t words) {
     if (words <= ctx->group_parts_words) return PQPS_OK;
     if (ctx->group_parts) { HIP_TRY(hipStreamSynchronize(s)); (void)hipFree(ctx->group_parts); ctx->group_parts = nullptr; ctx->group_parts_words = 0; }
@@ -2827,30 +2906,17 @@ int pqps_filter_group(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, u
                       const pqps_column *group_col, uint32_t bin_base, uint32_t n_bins, uint32_t *bins, void *stream) {
     if (!ctx || !group_col || !bins) return fail(PQPS_EINVAL, "ctx/group_col/bins is NULL");
     if (n_bins == 0 || n_bins > kGroupMaxBins) return fail(PQPS_EINVAL, "%u bins: 1 .. %u", n_bins, kGroupMaxBins);
-    const uint32_t gw = group_col->width;
-    if (gw != 1 && gw != 2 && gw != 4 && gw != PQPS_WIDTH_BITS) return fail(PQPS_EINVAL, "group column: width %u not in {1,2,4,bits}", gw);
-    if (!group_col->data || ((uintptr_t)group_col->data & 15u) != 0) return fail(PQPS_EINVAL, "group column: NULL or not 16-byte aligned");
-    int rc = check_pred(cols, n_cols, pred);
-    if (rc) return rc;
-    hipStream_t s = pick_stream(ctx, stream);
     GroupArgs g;
     memset(&g, 0, sizeof g);
-    fill_args(g.e, cols, n_cols, pred);
-    g.e.n_rows = n_rows;
-    set_streaming(g.e, cols, n_cols, n_rows);
+    int rc = column_width_code("group", group_col, true, false, true, &g.gwidth_log2);
+    if (rc == PQPS_OK) rc = fused_args(g.e, cols, n_cols, n_rows, pred);
+    if (rc) return rc;
+    hipStream_t s = pick_stream(ctx, stream);
     HIP_TRY(hipMemsetAsync(bins, 0, (size_t)n_bins * sizeof(uint32_t), s));
     if (n_rows == 0) return PQPS_OK;
     const int path = n_bins <= kGroupSmallBins ? GROUP_SMALL : n_bins <= kGroupLdsBins ? GROUP_LDS : GROUP_GLOBAL;
-    // persistent grid: up to 8 workgroups per CU (the LDS path: as many as its histogram lets into 160 KiB), never more
-    // than one step per wave
-    const uint64_t steps = (n_rows + kStepRows - 1) / kStepRows;
-    const uint64_t hist_bytes = path == GROUP_LDS ? (uint64_t)n_bins * sizeof(uint32_t) : 0;
-    uint64_t per_cu = path == GROUP_LDS ? (160ull << 10) / (hist_bytes + 1024) : 8;
-    if (per_cu > 8) per_cu = 8;
-    if (per_cu < 1) per_cu = 1;
-    const uint64_t want = (steps + kWaves - 1) / kWaves;
-    const uint64_t cap = (uint64_t)ctx->compute_units * per_cu;
-    const uint32_t grid = (uint32_t)(want < cap ? want : cap);
+    const uint32_t hist_bytes = path == GROUP_LDS ? n_bins * (uint32_t)sizeof(uint32_t) : 0u;
+    const uint32_t grid = fused_grid(ctx, n_rows, hist_bytes);
     const uint32_t stride = (n_bins + 63u) & ~63u;
     if (path != GROUP_GLOBAL) {
         rc = grow_group_parts(ctx, s, (size_t)grid * stride);
@@ -2860,7 +2926,6 @@ int pqps_filter_group(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, u
     g.bins = bins;
     g.parts = ctx->group_parts;
     g.stride = stride;
-    g.gwidth_log2 = gw == PQPS_WIDTH_BITS ? kWidthLog2Bits : gw == 1 ? 0u : gw == 2 ? 1u : 2u;
     g.bin_base = bin_base;
     g.n_bins = n_bins;
     typedef void (*group_fn)(const GroupArgs);
@@ -2871,19 +2936,15 @@ int pqps_filter_group(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, u
     };
     static const char *const names[3] = {"GROUP_SMALL", "GROUP_LDS", "GROUP_GLOBAL"};
     snprintf(g_kernel, sizeof g_kernel, "group_scan_kernel<%s, NT=%s>", names[path], g.e.streaming ? "true" : "false");
-    const group_fn k = fns[path][g.e.streaming ? 1 : 0];
-    const bool timed = ctx->timing && ctx->timed < kMaxTimedLaunches;
-    if (timed) hipExtLaunchKernelGGL(k, dim3(grid), dim3(kBlock), (uint32_t)hist_bytes, s, ctx->ev_start[ctx->timed], ctx->ev_eval[ctx->timed], 0, g);
-    else hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), (uint32_t)hist_bytes, s, g);
-    HIP_TRY(hipGetLastError());
+    hipEvent_t stop;
+    rc = fused_launch(ctx, fns[path][g.e.streaming ? 1 : 0], grid, hist_bytes, s, g, &stop);
+    if (rc) return rc;
     if (path != GROUP_GLOBAL) {
         const dim3 sg(stride / 64u, (grid + kGroupSumParts - 1) / kGroupSumParts);
-        if (timed) hipExtLaunchKernelGGL(group_sum_kernel, sg, dim3(kBlock), 0, s, nullptr, ctx->ev_stop[ctx->timed], 0,
-                                         (const uint32_t *)ctx->group_parts, grid, stride, n_bins, bins);
-        else hipLaunchKernelGGL(group_sum_kernel, sg, dim3(kBlock), 0, s, (const uint32_t *)ctx->group_parts, grid, stride, n_bins, bins);
-        HIP_TRY(hipGetLastError());
+        rc = launch_stop(group_sum_kernel, sg, 0, s, stop, (const uint32_t *)ctx->group_parts, grid, stride, n_bins, bins);
+        if (rc) return rc;
     }
-    if (timed) { ctx->stop_is_eval[ctx->timed] = path == GROUP_GLOBAL; ctx->timed++; }
+    fused_close(ctx, stop, path == GROUP_GLOBAL);
     return PQPS_OK;
 }
 
@@ -2891,21 +2952,18 @@ int pqps_group_list(pqps_ctx *ctx, const pqps_column *group_col, uint64_t n_rows
                     uint64_t capacity, uint32_t id_base, uint32_t bin_base, uint32_t n_bins, uint32_t *bins, void *stream) {
     if (!ctx || !group_col || !bins || !count_dev || (capacity && !ids)) return fail(PQPS_EINVAL, "NULL argument");
     if (n_bins == 0 || n_bins > kGroupMaxBins) return fail(PQPS_EINVAL, "%u bins: 1 .. %u", n_bins, kGroupMaxBins);
-    const uint32_t gw = group_col->width;
-    if (gw != 1 && gw != 2 && gw != 4) return fail(PQPS_EINVAL, "group column: width %u not in {1,2,4}", gw);
-    if (!group_col->data) return fail(PQPS_EINVAL, "group column: NULL data");
+    uint32_t wl;
+    const int rc = column_width_code("group", group_col, false, false, false, &wl);   // gathered by row: any alignment
+    if (rc) return rc;
     hipStream_t s = pick_stream(ctx, stream);
     HIP_TRY(hipMemsetAsync(bins, 0, (size_t)n_bins * sizeof(uint32_t), s));
     if (capacity == 0 || n_rows == 0) return PQPS_OK;
-    uint64_t blocks = (capacity + kBlock - 1) / kBlock;
-    const uint64_t cap = (uint64_t)ctx->compute_units * 4;
-    if (blocks > cap) blocks = cap;
-    const uint32_t wl = gw == 1 ? 0u : gw == 2 ? 1u : 2u;
+    const dim3 grid(list_grid(ctx, capacity, 4));
     if (n_bins <= kGroupLdsBins)
-        hipLaunchKernelGGL(group_list_kernel<true>, dim3((uint32_t)blocks), dim3(kBlock), n_bins * (uint32_t)sizeof(uint32_t), s,
+        hipLaunchKernelGGL(group_list_kernel<true>, grid, dim3(kBlock), n_bins * (uint32_t)sizeof(uint32_t), s,
                            group_col->data, wl, n_rows, ids, count_dev, capacity, id_base, bin_base, n_bins, bins);
     else
-        hipLaunchKernelGGL(group_list_kernel<false>, dim3((uint32_t)blocks), dim3(kBlock), 0, s,
+        hipLaunchKernelGGL(group_list_kernel<false>, grid, dim3(kBlock), 0, s,
                            group_col->data, wl, n_rows, ids, count_dev, capacity, id_base, bin_base, n_bins, bins);
     HIP_TRY(hipGetLastError());
     return PQPS_OK;
@@ -2917,10 +2975,7 @@ int pqps_column_bounds(pqps_ctx *ctx, const pqps_column *col, uint64_t n_rows, i
     hipStream_t s = pick_stream(ctx, stream);
     HIP_TRY(hipMemsetAsync(out_dev, 0, 2 * sizeof(int32_t), s));
     if (n_rows) {
-        uint64_t blocks = (n_rows + kBlock - 1) / kBlock;
-        const uint64_t cap = (uint64_t)ctx->compute_units * 8;
-        if (blocks > cap) blocks = cap;
-        hipLaunchKernelGGL(group_bounds_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, s, (const int32_t *)col->data, n_rows, (uint32_t *)out_dev);
+        hipLaunchKernelGGL(group_bounds_kernel, dim3(list_grid(ctx, n_rows, 8)), dim3(kBlock), 0, s, (const int32_t *)col->data, n_rows, (uint32_t *)out_dev);
         HIP_TRY(hipGetLastError());
     }
     hipLaunchKernelGGL(group_bounds_finish_kernel, dim3(1), dim3(1), 0, s, (uint32_t *)out_dev);
@@ -2929,17 +2984,15 @@ int pqps_column_bounds(pqps_ctx *ctx, const pqps_column *col, uint64_t n_rows, i
 }
 
 // ---- COUNT / SUM / MIN / MAX of a value column (aggregate_kernels.hpp) -----------------------------------------------
-static int check_aggregate_cols(const pqps_column *value_col, const pqps_column *group_col, uint32_t n_bins, bool plane_ok) {
+// *gwl = the group column's width code (0 without one)
+static int check_aggregate_cols(const pqps_column *value_col, const pqps_column *group_col, uint32_t n_bins, bool plane_ok, uint32_t *gwl) {
+    *gwl = 0;
     if (!value_col) return fail(PQPS_EINVAL, "value column is NULL");
     if (value_col->width != 4 && value_col->width != 8) return fail(PQPS_EINVAL, "value column: width %u not in {4,8}", value_col->width);
     if (!value_col->data || ((uintptr_t)value_col->data & 15u) != 0) return fail(PQPS_EINVAL, "value column: NULL or not 16-byte aligned");
     if (!group_col) return n_bins == 1 ? PQPS_OK : fail(PQPS_EINVAL, "no group column: 1 bin, not %u", n_bins);
     if (n_bins == 0 || n_bins > kGroupMaxBins) return fail(PQPS_EINVAL, "%u bins: 1 .. %u", n_bins, kGroupMaxBins);
-    const uint32_t gw = group_col->width;
-    if (gw != 1 && gw != 2 && gw != 4 && !(plane_ok && gw == PQPS_WIDTH_BITS))
-        return fail(PQPS_EINVAL, "group column: width %u not in {1,2,4%s}", gw, plane_ok ? ",bits" : "");
-    if (!group_col->data || ((uintptr_t)group_col->data & 15u) != 0) return fail(PQPS_EINVAL, "group column: NULL or not 16-byte aligned");
-    return PQPS_OK;
+    return column_width_code("group", group_col, plane_ok, false, true, gwl);
 }
 
 // out[4][n_bins]: counts and sums 0, min images ~0, max images 0
@@ -2953,39 +3006,25 @@ int pqps_filter_aggregate(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_col
                           const pqps_column *value_col, const pqps_column *group_col, uint32_t bin_base, uint32_t n_bins,
                           uint64_t *out, void *stream) {
     if (!ctx || !out) return fail(PQPS_EINVAL, "ctx/out is NULL");
-    int rc = check_aggregate_cols(value_col, group_col, n_bins, true);
-    if (rc) return rc;
-    rc = check_pred(cols, n_cols, pred);
-    if (rc) return rc;
-    hipStream_t s = pick_stream(ctx, stream);
     AggArgs g;
     memset(&g, 0, sizeof g);
-    fill_args(g.e, cols, n_cols, pred);
-    g.e.n_rows = n_rows;
-    set_streaming(g.e, cols, n_cols, n_rows);
+    int rc = check_aggregate_cols(value_col, group_col, n_bins, true, &g.gwidth_log2);
+    if (rc == PQPS_OK) rc = fused_args(g.e, cols, n_cols, n_rows, pred);
+    if (rc) return rc;
+    hipStream_t s = pick_stream(ctx, stream);
     rc = init_aggregate_out(out, n_bins, s);
     if (rc || n_rows == 0) return rc;
     const int path = !group_col ? AGG_ONE : n_bins <= kAggLdsBins ? AGG_LDS : AGG_GLOBAL;
-    // persistent grid as pqps_filter_group's: up to 8 workgroups per CU (the LDS path: as many as its table lets into
-    // 160 KiB), never more than one step per wave
-    const uint64_t steps = (n_rows + kStepRows - 1) / kStepRows;
-    const uint64_t table_bytes = path == AGG_LDS ? (uint64_t)n_bins * (3 * sizeof(uint64_t) + sizeof(uint32_t)) : 0;
-    uint64_t per_cu = path == AGG_LDS ? (160ull << 10) / (table_bytes + 1024) : 8;
-    if (per_cu > 8) per_cu = 8;
-    if (per_cu < 1) per_cu = 1;
-    const uint64_t want = (steps + kWaves - 1) / kWaves;
-    const uint64_t cap = (uint64_t)ctx->compute_units * per_cu;
-    const uint32_t grid = (uint32_t)(want < cap ? want : cap);
+    const uint32_t table_bytes = path == AGG_LDS ? n_bins * (uint32_t)(3 * sizeof(uint64_t) + sizeof(uint32_t)) : 0u;
+    const uint32_t grid = fused_grid(ctx, n_rows, table_bytes);
     if (path != AGG_GLOBAL) {
         rc = grow_group_parts(ctx, s, (size_t)grid * kAggFields * n_bins * 2);
         if (rc) return rc;
     }
-    const uint32_t gw = group_col ? group_col->width : 1;
     g.vcol = value_col->data;
     g.gcol = group_col ? group_col->data : nullptr;
     g.out = out;
     g.parts = (uint64_t *)ctx->group_parts;
-    g.gwidth_log2 = gw == PQPS_WIDTH_BITS ? kWidthLog2Bits : gw == 1 ? 0u : gw == 2 ? 1u : 2u;
     g.bin_base = bin_base;
     g.n_bins = n_bins;
     const bool u64 = value_col->width == 8;
@@ -3000,19 +3039,15 @@ int pqps_filter_aggregate(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_col
     };
     static const char *const names[3] = {"AGG_ONE", "AGG_LDS", "AGG_GLOBAL"};
     snprintf(g_kernel, sizeof g_kernel, "agg_scan_kernel<%s, %s, NT=%s>", names[path], u64 ? "u64" : "i32", g.e.streaming ? "true" : "false");
-    const agg_fn k = fns[path][u64 ? 1 : 0][g.e.streaming ? 1 : 0];
-    const bool timed = ctx->timing && ctx->timed < kMaxTimedLaunches;
-    if (timed) hipExtLaunchKernelGGL(k, dim3(grid), dim3(kBlock), (uint32_t)table_bytes, s, ctx->ev_start[ctx->timed], ctx->ev_eval[ctx->timed], 0, g);
-    else hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), (uint32_t)table_bytes, s, g);
-    HIP_TRY(hipGetLastError());
+    hipEvent_t stop;
+    rc = fused_launch(ctx, fns[path][u64 ? 1 : 0][g.e.streaming ? 1 : 0], grid, table_bytes, s, g, &stop);
+    if (rc) return rc;
     if (path != AGG_GLOBAL) {
         const dim3 sg((n_bins + 63u) / 64u, (grid + kAggSumParts - 1) / kAggSumParts);
-        if (timed) hipExtLaunchKernelGGL(agg_sum_kernel, sg, dim3(kBlock), 0, s, nullptr, ctx->ev_stop[ctx->timed], 0,
-                                         (const uint64_t *)ctx->group_parts, grid, n_bins, out);
-        else hipLaunchKernelGGL(agg_sum_kernel, sg, dim3(kBlock), 0, s, (const uint64_t *)ctx->group_parts, grid, n_bins, out);
-        HIP_TRY(hipGetLastError());
+        rc = launch_stop(agg_sum_kernel, sg, 0, s, stop, (const uint64_t *)ctx->group_parts, grid, n_bins, out);
+        if (rc) return rc;
     }
-    if (timed) { ctx->stop_is_eval[ctx->timed] = path == AGG_GLOBAL; ctx->timed++; }
+    fused_close(ctx, stop, path == AGG_GLOBAL);
     return PQPS_OK;
 }
 
@@ -3020,16 +3055,12 @@ int pqps_aggregate_list(pqps_ctx *ctx, const pqps_column *value_col, const pqps_
                         const uint32_t *ids, const uint64_t *count_dev, uint64_t capacity, uint32_t id_base, uint32_t bin_base,
                         uint32_t n_bins, uint64_t *out, void *stream) {
     if (!ctx || !out || !count_dev || (capacity && !ids)) return fail(PQPS_EINVAL, "NULL argument");
-    int rc = check_aggregate_cols(value_col, group_col, n_bins, false);
+    uint32_t wl;
+    int rc = check_aggregate_cols(value_col, group_col, n_bins, false, &wl);
     if (rc) return rc;
     hipStream_t s = pick_stream(ctx, stream);
     rc = init_aggregate_out(out, n_bins, s);
     if (rc || capacity == 0 || n_rows == 0) return rc;
-    uint64_t blocks = (capacity + kBlock - 1) / kBlock;
-    const uint64_t cap = (uint64_t)ctx->compute_units * 4;
-    if (blocks > cap) blocks = cap;
-    const uint32_t gw = group_col ? group_col->width : 1;
-    const uint32_t wl = gw == 1 ? 0u : gw == 2 ? 1u : 2u;
     const void *gdata = group_col ? group_col->data : nullptr;
     const int path = !group_col ? AGG_ONE : n_bins <= kAggLdsBins ? AGG_LDS : AGG_GLOBAL;
     const uint32_t lds = path == AGG_LDS ? n_bins * (uint32_t)(3 * sizeof(uint64_t) + sizeof(uint32_t)) : 0u;
@@ -3040,7 +3071,7 @@ int pqps_aggregate_list(pqps_ctx *ctx, const pqps_column *value_col, const pqps_
         {agg_list_kernel<AGG_LDS, false>, agg_list_kernel<AGG_LDS, true>},
         {agg_list_kernel<AGG_GLOBAL, false>, agg_list_kernel<AGG_GLOBAL, true>},
     };
-    hipLaunchKernelGGL(fns[path][value_col->width == 8 ? 1 : 0], dim3((uint32_t)blocks), dim3(kBlock), lds, s,
+    hipLaunchKernelGGL(fns[path][value_col->width == 8 ? 1 : 0], dim3(list_grid(ctx, capacity, 4)), dim3(kBlock), lds, s,
                        value_col->data, gdata, wl, n_rows, ids, count_dev, capacity, id_base, bin_base, n_bins, out);
     HIP_TRY(hipGetLastError());
     return PQPS_OK;
@@ -3051,13 +3082,8 @@ static int check_topk_key(const pqps_column *key_col, bool plane_ok, bool *wide,
     *wide = false;
     *wl = 0;
     if (!key_col) return PQPS_OK;                                // every key 0
-    const uint32_t w = key_col->width;
-    if (w != 1 && w != 2 && w != 4 && w != 8 && !(plane_ok && w == PQPS_WIDTH_BITS))
-        return fail(PQPS_EINVAL, "key column: width %u not in {1,2,4,8%s}", w, plane_ok ? ",bits" : "");
-    if (!key_col->data || ((uintptr_t)key_col->data & 15u) != 0) return fail(PQPS_EINVAL, "key column: NULL or not 16-byte aligned");
-    *wide = w == 8;
-    *wl = w == PQPS_WIDTH_BITS ? kWidthLog2Bits : w == 1 ? 0u : w == 2 ? 1u : w == 4 ? 2u : 3u;
-    return PQPS_OK;
+    *wide = key_col->width == 8;
+    return column_width_code("key", key_col, plane_ok, true, true, wl);
 }
 
 static uint64_t topk_xor(bool wide, int key_signed, int descending) {
@@ -3072,19 +3098,6 @@ static uint32_t topk_cap(uint32_t k) {
     return cap;
 }
 
-// the fused scan's grid: as pqps_filter_group's, up to 8 workgroups per CU as far as the buffers let into 160 KiB, never
-// more than one step per wave
-static uint32_t topk_grid(const pqps_ctx *ctx, uint64_t n_rows, uint32_t lds) {
-    const uint64_t steps = (n_rows + kStepRows - 1) / kStepRows;
-    uint64_t per_cu = (160ull << 10) / ((uint64_t)lds + 1024);
-    if (per_cu > 8) per_cu = 8;
-    if (per_cu < 1) per_cu = 1;
-    const uint64_t want = (steps + kWaves - 1) / kWaves;
-    const uint64_t cap = (uint64_t)ctx->compute_units * per_cu;
-    const uint64_t grid = want < cap ? want : cap;
-    return (uint32_t)(grid ? grid : 1);
-}
-
 // keys of the follow-up rounds' two ping-pong areas for a first input of n keys
 static uint64_t topk_round_keys(uint64_t n, uint32_t k) { return n / kTopkChunk + k; }
 
@@ -3092,7 +3105,7 @@ uint64_t pqps_topk_scratch_bytes(pqps_ctx *ctx, uint64_t n, uint32_t k, int wide
     if (!ctx || k == 0) return 0;
     const uint64_t key_bytes = wide ? 16 : 8;
     uint64_t first = n;
-    if (fused) first = (uint64_t)topk_grid(ctx, n, (uint32_t)(kWaves * topk_cap(k) * key_bytes)) * kWaves * k;
+    if (fused) first = (uint64_t)fused_grid(ctx, n, (uint32_t)(kWaves * topk_cap(k) * key_bytes)) * kWaves * k;
     return (first * (fused ? 1 : 0) + 2 * topk_round_keys(first, k)) * key_bytes + 64;
 }
 
@@ -3114,18 +3127,11 @@ static int topk_rounds(pqps_ctx *ctx, hipStream_t s, const TKey<WIDE> *in, const
         const uint64_t waves = n ? (n + chunk - 1) / chunk : 1;
         TKey<WIDE> *dst = waves == 1 ? out : x;
         const dim3 grid((uint32_t)((waves + kWaves - 1) / kWaves));
-        if (gather) {
-            hipLaunchKernelGGL((topk_select_kernel<WIDE, true>), grid, dim3(kBlock), lds, s, nullptr, ids, kcol, kwl, kxor, id_base,
-                               n, chunk, waves, k, cap, dst);
-        } else if (waves == 1 && stop) {
-            hipExtLaunchKernelGGL((topk_select_kernel<WIDE, false>), grid, dim3(kBlock), lds, s, nullptr, stop, 0, in, nullptr, kcol, kwl,
-                                  kxor, id_base, n, chunk, waves, k, cap, dst);
-        } else {
-            hipLaunchKernelGGL((topk_select_kernel<WIDE, false>), grid, dim3(kBlock), lds, s, in, nullptr, kcol, kwl, kxor, id_base,
-                               n, chunk, waves, k, cap, dst);
-        }
-        HIP_TRY(hipGetLastError());
-        if (waves == 1) return PQPS_OK;
+        const int rc = gather ? launch_stop(topk_select_kernel<WIDE, true>, grid, lds, s, nullptr, nullptr, ids, kcol, kwl, kxor, id_base,
+                                            n, chunk, waves, k, cap, dst)
+                              : launch_stop(topk_select_kernel<WIDE, false>, grid, lds, s, waves == 1 ? stop : nullptr, in, nullptr, kcol,
+                                            kwl, kxor, id_base, n, chunk, waves, k, cap, dst);
+        if (rc || waves == 1) return rc;
         gather = false;
         in = x;
         n = waves * k;
@@ -3145,20 +3151,17 @@ int pqps_filter_topk(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, ui
     if (k == 0 || k > (wide ? kTopkMaxWide : kTopkMax)) return fail(PQPS_EINVAL, "K = %u: 1 .. %u", k, wide ? kTopkMaxWide : kTopkMax);
     if (scratch_bytes < pqps_topk_scratch_bytes(ctx, n_rows, k, wide, 1)) return fail(PQPS_EINVAL, "scratch too small");
     if ((uint64_t)row_base + n_rows >= 0xFFFFFFFFull) return fail(PQPS_EINVAL, "row numbers must stay below 2^32 - 1");
-    rc = check_pred(cols, n_cols, pred);
+    TopkArgs g;
+    memset(&g, 0, sizeof g);
+    rc = fused_args(g.e, cols, n_cols, n_rows, pred);
     if (rc) return rc;
     hipStream_t s = pick_stream(ctx, stream);
     HIP_TRY(hipMemsetAsync(count, 0, sizeof(uint64_t), s));
     if (n_rows == 0) return PQPS_OK;
-    TopkArgs g;
-    memset(&g, 0, sizeof g);
-    fill_args(g.e, cols, n_cols, pred);
-    g.e.n_rows = n_rows;
-    set_streaming(g.e, cols, n_cols, n_rows);
     const uint32_t cap = topk_cap(k);
     const uint32_t key_bytes = wide ? 16u : 8u;
     const uint32_t lds = kWaves * cap * key_bytes;
-    const uint32_t grid = topk_grid(ctx, n_rows, lds);
+    const uint32_t grid = fused_grid(ctx, n_rows, lds);
     const uint64_t parts = (uint64_t)grid * kWaves * k;
     const uint64_t round = topk_round_keys(parts, k);
     char *base = (char *)scratch;
@@ -3174,18 +3177,15 @@ int pqps_filter_topk(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, ui
     static const topk_fn fns[2][2] = {{topk_scan_kernel<false, false>, topk_scan_kernel<false, true>},
                                       {topk_scan_kernel<true, false>, topk_scan_kernel<true, true>}};
     snprintf(g_kernel, sizeof g_kernel, "topk_scan_kernel<%s, NT=%s>", wide ? "wide" : "narrow", g.e.streaming ? "true" : "false");
-    const topk_fn kf = fns[wide ? 1 : 0][g.e.streaming ? 1 : 0];
-    const bool timed = ctx->timing && ctx->timed < kMaxTimedLaunches;
-    if (timed) hipExtLaunchKernelGGL(kf, dim3(grid), dim3(kBlock), lds, s, ctx->ev_start[ctx->timed], ctx->ev_eval[ctx->timed], 0, g);
-    else hipLaunchKernelGGL(kf, dim3(grid), dim3(kBlock), lds, s, g);
-    HIP_TRY(hipGetLastError());
-    hipEvent_t stop = timed ? ctx->ev_stop[ctx->timed] : nullptr;
+    hipEvent_t stop;
+    rc = fused_launch(ctx, fns[wide ? 1 : 0][g.e.streaming ? 1 : 0], grid, lds, s, g, &stop);
+    if (rc) return rc;
     char *xa = base + parts * key_bytes, *ya = xa + round * key_bytes;
     if (wide) rc = topk_rounds<true>(ctx, s, (const TKey<true> *)base, nullptr, nullptr, 0, 0, 0, parts, k, (TKey<true> *)xa,
                                      (TKey<true> *)ya, (TKey<true> *)out, stop);
     else rc = topk_rounds<false>(ctx, s, (const TKey<false> *)base, nullptr, nullptr, 0, 0, 0, parts, k, (TKey<false> *)xa,
                                  (TKey<false> *)ya, (TKey<false> *)out, stop);
-    if (timed) { ctx->stop_is_eval[ctx->timed] = false; ctx->timed++; }
+    fused_close(ctx, stop, false);
     return rc;
 }
 
@@ -3237,12 +3237,11 @@ int pqps_sort_list(pqps_ctx *ctx, const pqps_column *key_col, int key_signed, in
     if (e == hipSuccess) {
         const uint32_t *rows = in_a ? va : vb;
         uint32_t *rows_b = in_a ? vb : va;
-        uint64_t blocks = (n + kBlock - 1) / kBlock;
-        if (blocks > (uint64_t)ctx->compute_units * 8) blocks = (uint64_t)ctx->compute_units * 8;
+        const dim3 grid(list_grid(ctx, n, 8));
         const void *kcol = key_col ? key_col->data : nullptr;
         const uint64_t kxor = topk_xor(wide, key_signed, descending);
-        if (wide) hipLaunchKernelGGL(topk_sort_keys_kernel<true>, dim3((uint32_t)blocks), dim3(kBlock), 0, s, rows, n, kcol, wl, kxor, id_base, ka);
-        else hipLaunchKernelGGL(topk_sort_keys_kernel<false>, dim3((uint32_t)blocks), dim3(kBlock), 0, s, rows, n, kcol, wl, kxor, id_base, ka);
+        if (wide) hipLaunchKernelGGL(topk_sort_keys_kernel<true>, grid, dim3(kBlock), 0, s, rows, n, kcol, wl, kxor, id_base, ka);
+        else hipLaunchKernelGGL(topk_sort_keys_kernel<false>, grid, dim3(kBlock), 0, s, rows, n, kcol, wl, kxor, id_base, ka);
         e = hipGetLastError();
         bool in_b = true;
         if (e == hipSuccess) e = pqps_sort::sort_pairs<uint64_t, false>(w, ka, (uint32_t *)rows, kb, rows_b, n, wide ? 64 : 32,
@@ -3258,24 +3257,14 @@ int pqps_sort_list(pqps_ctx *ctx, const pqps_column *key_col, int key_signed, in
 }
 
 // ---- COUNT(DISTINCT value column) (distinct_kernels.hpp) -------------------------------------------------------------
-// width code of a value / group column of the bitmap forms (1, 2, 4 bytes; a bit plane where the loads take one)
-static int distinct_col(const char *what, const pqps_column *col, bool plane_ok, uint32_t *wl) {
-    const uint32_t w = col->width;
-    if (w != 1 && w != 2 && w != 4 && !(plane_ok && w == PQPS_WIDTH_BITS))
-        return fail(PQPS_EINVAL, "%s column: width %u not in {1,2,4%s}", what, w, plane_ok ? ",bits" : "");
-    if (!col->data || ((uintptr_t)col->data & 15u) != 0) return fail(PQPS_EINVAL, "%s column: NULL or not 16-byte aligned", what);
-    *wl = w == PQPS_WIDTH_BITS ? kWidthLog2Bits : w == 1 ? 0u : w == 2 ? 1u : 2u;
-    return PQPS_OK;
-}
-
 static int check_distinct_bins(const pqps_column *value_col, const pqps_column *group_col, uint32_t n_values, uint32_t n_groups,
                                bool plane_ok, uint32_t *vwl, uint32_t *gwl) {
     if (!value_col) return fail(PQPS_EINVAL, "value column is NULL");
-    int rc = distinct_col("value", value_col, plane_ok, vwl);
+    int rc = column_width_code("value", value_col, plane_ok, false, true, vwl);
     if (rc) return rc;
     *gwl = 0;
     if (!group_col && n_groups != 1) return fail(PQPS_EINVAL, "no group column: 1 group, not %u", n_groups);
-    if (group_col && (rc = distinct_col("group", group_col, plane_ok, gwl)) != 0) return rc;
+    if (group_col && (rc = column_width_code("group", group_col, plane_ok, false, true, gwl)) != 0) return rc;
     if (n_values == 0 || n_groups == 0 || n_groups > kGroupMaxBins) return fail(PQPS_EINVAL, "%u values x %u groups", n_values, n_groups);
     if (pqps_distinct_bitmap_words(n_values, n_groups) * 32 > kDistMaxBits)
         return fail(PQPS_EINVAL, "%u values x %u groups: over the bitmap cap of 2^30 bits", n_values, n_groups);
@@ -3298,47 +3287,28 @@ static int distinct_count_launch(pqps_ctx *ctx, hipStream_t s, const uint32_t *b
                                  uint64_t *distinct, hipEvent_t stop) {
     HIP_TRY(hipMemsetAsync(distinct, 0, (size_t)n_groups * sizeof(uint64_t), s));
     const uint64_t nw = ((uint64_t)n_values + 31) / 32;
-    const uint64_t items = (uint64_t)n_groups * ((nw + 255) / 256);
-    uint64_t blocks = (items + kWaves - 1) / kWaves;
-    if (blocks > (uint64_t)ctx->compute_units * 8) blocks = (uint64_t)ctx->compute_units * 8;
-    if (stop) hipExtLaunchKernelGGL(dist_count_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, s, nullptr, stop, 0, bitmap, n_groups, nw,
-                                    (unsigned long long *)distinct);
-    else hipLaunchKernelGGL(dist_count_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, s, bitmap, n_groups, nw, (unsigned long long *)distinct);
-    HIP_TRY(hipGetLastError());
-    return PQPS_OK;
+    const uint64_t items = (uint64_t)n_groups * ((nw + 255) / 256);               // a wave each
+    return launch_stop(dist_count_kernel, dim3(list_grid(ctx, items * 64, 8)), 0, s, stop, bitmap, n_groups, nw, (unsigned long long *)distinct);
 }
 
 int pqps_filter_distinct(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
                          const pqps_column *value_col, uint32_t v_base, uint32_t n_values, const pqps_column *group_col,
                          uint32_t g_base, uint32_t n_groups, uint32_t *bitmap, uint64_t *total, uint64_t *distinct, void *stream) {
     if (!ctx || !bitmap || !total) return fail(PQPS_EINVAL, "ctx/bitmap/total is NULL");
-    uint32_t vwl, gwl;
-    int rc = check_distinct_bins(value_col, group_col, n_values, n_groups, true, &vwl, &gwl);
-    if (rc) return rc;
-    rc = check_pred(cols, n_cols, pred);
+    DistArgs g;
+    memset(&g, 0, sizeof g);
+    int rc = check_distinct_bins(value_col, group_col, n_values, n_groups, true, &g.vwidth_log2, &g.gwidth_log2);
+    if (rc == PQPS_OK) rc = fused_args(g.e, cols, n_cols, n_rows, pred);
     if (rc) return rc;
     hipStream_t s = pick_stream(ctx, stream);
     const uint64_t bm_words = pqps_distinct_bitmap_words(n_values, n_groups);
     HIP_TRY(hipMemsetAsync(bitmap, 0, bm_words * sizeof(uint32_t), s));
     HIP_TRY(hipMemsetAsync(total, 0, sizeof(uint64_t), s));
     if (n_rows == 0) return distinct ? distinct_count_launch(ctx, s, bitmap, n_values, n_groups, distinct, nullptr) : PQPS_OK;
-    DistArgs g;
-    memset(&g, 0, sizeof g);
-    fill_args(g.e, cols, n_cols, pred);
-    g.e.n_rows = n_rows;
-    set_streaming(g.e, cols, n_cols, n_rows);
     const int path = distinct_path(n_values, n_groups);
     const uint32_t row_words = path == DIST_GLOBAL ? 0u : (uint32_t)bm_words;
-    // persistent grid as pqps_filter_aggregate's: up to 8 workgroups per CU (the LDS form: as many as its bitmap lets into
-    // 160 KiB), never more than one step per wave
-    const uint64_t steps = (n_rows + kStepRows - 1) / kStepRows;
     const uint32_t lds = path == DIST_LDS ? row_words * (uint32_t)sizeof(uint32_t) : 0u;
-    uint64_t per_cu = path == DIST_LDS ? (160ull << 10) / ((uint64_t)lds + 1024) : 8;
-    if (per_cu > 8) per_cu = 8;
-    if (per_cu < 1) per_cu = 1;
-    const uint64_t want = (steps + kWaves - 1) / kWaves;
-    const uint64_t cap = (uint64_t)ctx->compute_units * per_cu;
-    const uint32_t grid = (uint32_t)(want < cap ? want : cap);
+    const uint32_t grid = fused_grid(ctx, n_rows, lds);
     // ctx->group_parts: [grid] u64 totals, then [grid][row_words] partial bitmaps
     rc = grow_group_parts(ctx, s, (size_t)grid * 2 + (size_t)grid * row_words);
     if (rc) return rc;
@@ -3347,8 +3317,6 @@ int pqps_filter_distinct(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols
     g.bitmap = bitmap;
     g.totals = (uint64_t *)ctx->group_parts;
     g.parts = ctx->group_parts + (size_t)grid * 2;
-    g.vwidth_log2 = vwl;
-    g.gwidth_log2 = gwl;
     g.v_base = v_base;
     g.g_base = g_base;
     g.n_values = n_values;
@@ -3365,21 +3333,16 @@ int pqps_filter_distinct(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols
     };
     snprintf(g_kernel, sizeof g_kernel, "dist_scan_kernel<%s, GROUPED=%s, NT=%s>", k_dist_names[path], group_col ? "true" : "false",
              g.e.streaming ? "true" : "false");
-    const dist_fn k = fns[path][group_col ? 1 : 0][g.e.streaming ? 1 : 0];
-    const bool timed = ctx->timing && ctx->timed < kMaxTimedLaunches;
-    if (timed) hipExtLaunchKernelGGL(k, dim3(grid), dim3(kBlock), lds, s, ctx->ev_start[ctx->timed], ctx->ev_eval[ctx->timed], 0, g);
-    else hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), lds, s, g);
-    HIP_TRY(hipGetLastError());
-    // the partial bitmaps OR-ed and the totals summed (GLOBAL: the totals only)
+    hipEvent_t stop;
+    rc = fused_launch(ctx, fns[path][group_col ? 1 : 0][g.e.streaming ? 1 : 0], grid, lds, s, g, &stop);
+    if (rc) return rc;
+    // the partial bitmaps OR-ed and the totals summed (GLOBAL: the totals only); the last launch takes `stop`
     const dim3 og(row_words ? (row_words + 63u) / 64u : 1u, (grid + kDistOrParts - 1) / kDistOrParts);
-    hipEvent_t stop = timed ? ctx->ev_stop[ctx->timed] : nullptr;
-    if (timed && !distinct) hipExtLaunchKernelGGL(dist_or_kernel, og, dim3(kBlock), 0, s, nullptr, stop, 0, (const uint32_t *)g.parts,
-                                                  (const uint64_t *)g.totals, grid, row_words, bitmap, (unsigned long long *)total);
-    else hipLaunchKernelGGL(dist_or_kernel, og, dim3(kBlock), 0, s, (const uint32_t *)g.parts, (const uint64_t *)g.totals, grid, row_words,
-                            bitmap, (unsigned long long *)total);
-    HIP_TRY(hipGetLastError());
+    rc = launch_stop(dist_or_kernel, og, 0, s, distinct ? nullptr : stop, (const uint32_t *)g.parts, (const uint64_t *)g.totals, grid,
+                     row_words, bitmap, (unsigned long long *)total);
+    if (rc) return rc;
     if (distinct) rc = distinct_count_launch(ctx, s, bitmap, n_values, n_groups, distinct, stop);
-    if (timed) { ctx->stop_is_eval[ctx->timed] = false; ctx->timed++; }
+    fused_close(ctx, stop, false);
     return rc;
 }
 
@@ -3394,9 +3357,6 @@ int pqps_distinct_list(pqps_ctx *ctx, const pqps_column *value_col, uint32_t v_b
     const uint64_t bm_words = pqps_distinct_bitmap_words(n_values, n_groups);
     HIP_TRY(hipMemsetAsync(bitmap, 0, bm_words * sizeof(uint32_t), s));
     if (capacity && n_rows) {
-        uint64_t blocks = (capacity + kBlock - 1) / kBlock;
-        const uint64_t cap = (uint64_t)ctx->compute_units * 4;
-        if (blocks > cap) blocks = cap;
         const int path = distinct_path(n_values, n_groups);
         const uint32_t lds = path == DIST_LDS ? (uint32_t)bm_words * (uint32_t)sizeof(uint32_t) : 0u;
         typedef void (*list_fn)(const void *, uint32_t, const void *, uint32_t, uint64_t, const uint32_t *, const uint64_t *, uint64_t,
@@ -3407,7 +3367,7 @@ int pqps_distinct_list(pqps_ctx *ctx, const pqps_column *value_col, uint32_t v_b
             {dist_list_kernel<DIST_GLOBAL, false>, dist_list_kernel<DIST_GLOBAL, true>},
         };
         snprintf(g_kernel, sizeof g_kernel, "dist_list_kernel<%s, GROUPED=%s>", k_dist_names[path], group_col ? "true" : "false");
-        hipLaunchKernelGGL(fns[path][group_col ? 1 : 0], dim3((uint32_t)blocks), dim3(kBlock), lds, s, value_col->data, vwl,
+        hipLaunchKernelGGL(fns[path][group_col ? 1 : 0], dim3(list_grid(ctx, capacity, 4)), dim3(kBlock), lds, s, value_col->data, vwl,
                            group_col ? group_col->data : nullptr, gwl, n_rows, ids, count_dev, capacity, id_base, v_base, n_values,
                            g_base, n_groups, (n_values + 31u) / 32u, bitmap);
         HIP_TRY(hipGetLastError());
@@ -3428,10 +3388,9 @@ int pqps_distinct_sort(pqps_ctx *ctx, const pqps_column *value_col, uint32_t v_b
     if (!ctx || !value_col || !distinct || (n && !ids)) return fail(PQPS_EINVAL, "NULL argument");
     if (n_groups == 0 || n_groups > kGroupMaxBins || (!group_col && n_groups != 1)) return fail(PQPS_EINVAL, "%u groups", n_groups);
     const bool wide = value_col->width == 8;
-    uint32_t vwl = 3, gwl = 0;
-    int rc = wide ? (value_col->data && ((uintptr_t)value_col->data & 15u) == 0 ? PQPS_OK : fail(PQPS_EINVAL, "value column: NULL or not 16-byte aligned"))
-                  : distinct_col("value", value_col, false, &vwl);
-    if (rc == PQPS_OK && group_col) rc = distinct_col("group", group_col, false, &gwl);
+    uint32_t vwl, gwl = 0;
+    int rc = column_width_code("value", value_col, false, true, true, &vwl);
+    if (rc == PQPS_OK && group_col) rc = column_width_code("group", group_col, false, false, true, &gwl);
     if (rc) return rc;
     hipStream_t s = pick_stream(ctx, stream);
     HIP_TRY(hipMemsetAsync(distinct, 0, (size_t)n_groups * sizeof(uint64_t), s));
@@ -3445,9 +3404,7 @@ int pqps_distinct_sort(pqps_ctx *ctx, const pqps_column *value_col, uint32_t v_b
     if (e == hipSuccess) e = hipMalloc((void **)&kb, n * 8);
     if (e == hipSuccess) e = hipMalloc((void **)&ga, n * 4);
     if (e == hipSuccess) e = hipMalloc((void **)&gb, n * 4);
-    uint64_t blocks = (n + kBlock - 1) / kBlock;
-    if (blocks > (uint64_t)ctx->compute_units * 8) blocks = (uint64_t)ctx->compute_units * 8;
-    const dim3 grid((uint32_t)blocks);
+    const dim3 grid(list_grid(ctx, n, 8));
     const void *gdata = group_col ? group_col->data : nullptr;
     const uint64_t *keys = nullptr;                              // the sorted keys the boundary kernel reads
     const uint32_t *grps = nullptr;                              // (wide) their groups

@@ -703,6 +703,60 @@ long long executeQueryCountHIP(struct engineS *engine, struct whereClauseS *wher
     return count;
 }
 
+/* ---- what grouped COUNT, the aggregates, COUNT(DISTINCT) and ORDER BY share --------------------------------------- */
+
+/* The table locked shared, a lane taken and q ready for a query; false where the lane is refused (reason on stderr,
+ * nothing held).  query_close() gives all of it back. */
+static bool query_open(struct engineS *engine, struct query *q) {
+    struct hipTable *t = engine->record_block;
+    hipTableLockShared(t);
+    const int lane = hipTableAcquireLane(t);
+    if (lane == HIP_LANE_REFUSED) { hipTableUnlockShared(t); return false; }
+    query_init(q, engine, t, lane, false);
+    return true;
+}
+
+static void query_close(struct query *q) {
+    query_free(q);
+    hipTableReleaseLane(q->t, q->lane);
+    hipTableUnlockShared(q->t);
+}
+
+/* The selection, every shard's list left on its own device (q->count[s] rows in query_lane(q, s)); q->total of them. */
+static int query_lists(struct query *q) {
+    q->per_shard = true;
+    const int rc = query_issue_all(q);
+    return rc == 0 ? query_await(q) : rc;
+}
+
+/* A fused query (single-pass scan-mode WHERE): under the issue lock `call` makes the ONE shim call of every non-empty
+ * shard s, on (ctx, stream) of the query's lane with q->sp[s] holding the pass's predicate and columns, and returns 0 or
+ * the engine_error; then every shard is waited for, also after an error. */
+typedef int (*fused_call)(struct query *q, int s, pqps_ctx *ctx, void *stream, void *arg);
+
+static int fused_issue(struct query *q, fused_call call, void *arg) {
+    const struct hipPass *last = &q->plan.pass[0];
+    int rc = 0;
+    hipTableLockIssue(q->t);
+    for (int s = 0; s < q->n_shards && rc == 0; s++) {
+        struct hipTable *sh = hipTableShard(q->t, s);
+        struct shard_pred *sp = &q->sp[s];
+        pqps_ctx *ctx = sh->ctx;
+        void *stream = NULL;
+        if (sh->n_rows == 0) continue;
+        if (q->lane >= 0 && pqps_qstream_lane(sh->qs, (uint32_t)q->lane, sh->n_rows, NULL, &ctx, &stream) != PQPS_OK) { rc = engine_error("query lane"); break; }
+        sp->pred = &last->pred;
+        sp->n_cols = last->pred.n_columns;
+        pass_columns(sh, last, NULL, true, sp->cols);
+        rc = call(q, s, ctx, stream, arg);
+        /* marked even after a failed call: the lane must not be handed on while a launch of this query runs */
+        if (q->lane >= 0 && pqps_qstream_mark(sh->qs, (uint32_t)q->lane) != PQPS_OK && rc == 0) rc = engine_error("query lane");
+    }
+    hipTableUnlockIssue(q->t);
+    for (int s = 0; s < q->n_shards; s++) if (wait_shard(q, s) != 0 && rc == 0) rc = -1;
+    return rc;
+}
+
 /* ---- grouped COUNT(*) (include/executeEngine-hip.h) --------------------------------------------------------------- */
 
 static const int k_group_kind[HIPCOL_COUNT] = {
@@ -824,6 +878,20 @@ static void group_combine(uint64_t *acc, const void *host, uint32_t n_bins, int 
  * pqps_group_list); otherwise the aggregates of value column vc (pqps_filter_aggregate / pqps_aggregate_list; no group
  * column without GROUP BY or for a single-valued one).  gp->fused: one launch per shard on the query's lane; otherwise the
  * selection (query_issue_all + query_await, each shard's list left on its own device) and the list kernel over every list. */
+struct group_call { const struct group_plan *gp; int vc; void **bins_dev; };
+
+static int group_fused_call(struct query *q, int s, pqps_ctx *ctx, void *stream, void *arg) {
+    const struct group_call *a = arg;
+    const struct group_plan *gp = a->gp;
+    const struct hipTable *sh = hipTableShard(q->t, s);
+    const struct shard_pred *sp = &q->sp[s];
+    const bool grouped = gp->c >= 0 && !gp->single;
+    const int rc = a->vc < 0 ? pqps_filter_group(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, &gp->gcol[s], gp->bin_base, gp->n_bins, a->bins_dev[s], stream)
+                             : pqps_filter_aggregate(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, &sh->col[a->vc], grouped ? &gp->gcol[s] : NULL,
+                                                     gp->bin_base, gp->n_bins, a->bins_dev[s], stream);
+    return rc == PQPS_OK ? 0 : engine_error("group filter");
+}
+
 static int group_bins(struct query *q, const struct group_plan *gp, int vc, uint64_t *acc) {
     const uint32_t n_bins = gp->n_bins, bin_base = gp->bin_base;
     const size_t bytes = vc < 0 ? (size_t)n_bins * sizeof(uint32_t) : (size_t)n_bins * 4 * sizeof(uint64_t);
@@ -835,35 +903,13 @@ static int group_bins(struct query *q, const struct group_plan *gp, int vc, uint
     for (int s = 0; s < q->n_shards && rc == 0; s++)
         if (pqps_malloc(hipTableShard(q->t, s)->ctx, bytes, &bins_dev[s]) != PQPS_OK) rc = engine_error("bins allocation");
     if (rc == 0 && gp->fused) {
-        const struct hipPass *last = &q->plan.pass[0];
-        hipTableLockIssue(q->t);
-        for (int s = 0; s < q->n_shards && rc == 0; s++) {
-            struct hipTable *sh = hipTableShard(q->t, s);
-            struct shard_pred *sp = &q->sp[s];
-            pqps_ctx *ctx = sh->ctx;
-            void *stream = NULL;
-            if (sh->n_rows == 0) continue;
-            if (q->lane >= 0 && pqps_qstream_lane(sh->qs, (uint32_t)q->lane, sh->n_rows, NULL, &ctx, &stream) != PQPS_OK) { rc = engine_error("query lane"); break; }
-            sp->pred = &last->pred;
-            sp->n_cols = last->pred.n_columns;
-            pass_columns(sh, last, NULL, true, sp->cols);
-            if (vc < 0 ? pqps_filter_group(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, &gp->gcol[s], bin_base, n_bins, bins_dev[s], stream) != PQPS_OK
-                       : pqps_filter_aggregate(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, &sh->col[vc], grouped ? &gp->gcol[s] : NULL,
-                                               bin_base, n_bins, bins_dev[s], stream) != PQPS_OK)
-                rc = engine_error("group filter");
-            /* marked even after a failed call: the lane must not be handed on while a launch of this query runs */
-            if (q->lane >= 0 && pqps_qstream_mark(sh->qs, (uint32_t)q->lane) != PQPS_OK && rc == 0) rc = engine_error("query lane");
-        }
-        hipTableUnlockIssue(q->t);
-        for (int s = 0; s < q->n_shards; s++) if (wait_shard(q, s) != 0 && rc == 0) rc = -1;
+        rc = fused_issue(q, group_fused_call, &(struct group_call){ gp, vc, bins_dev });
         for (int s = 0; s < q->n_shards && rc == 0; s++)
             if (hipTableShard(q->t, s)->n_rows == 0) continue;
             else if (pqps_download(lane_copy_ctx(q, s), host, bins_dev[s], bytes, NULL) != PQPS_OK) rc = engine_error("bins download");
             else group_combine(acc, host, n_bins, vc);
     } else if (rc == 0) {
-        q->per_shard = true;
-        rc = query_issue_all(q);
-        if (rc == 0) rc = query_await(q);
+        rc = query_lists(q);
         for (int s = 0; s < q->n_shards && rc == 0; s++) {
             struct hipTable *sh = hipTableShard(q->t, s);
             struct hipLane *L = query_lane(q, s);
@@ -882,6 +928,17 @@ static int group_bins(struct query *q, const struct group_plan *gp, int vc, uint
     return rc;
 }
 
+/* The rows of every group (counts[0 .. n_bins)), as grouped COUNT finds them (COUNT(DISTINCT) of a single-valued column too). */
+static int group_counts(struct query *q, const struct group_plan *gp, uint64_t *counts) {
+    if (!gp->single && gp->c >= 0) return group_bins(q, gp, -1, counts);
+    /* one group: the number of rows the selection returns (scan mode: the count, no list) */
+    q->count_only = q->n_probes == 0;
+    int rc = query_issue_all(q);
+    if (rc == 0) rc = query_await(q);
+    if (rc == 0) counts[0] = q->total;
+    return rc;
+}
+
 /* The key and key text of bin k of group column c (kind `kind`); text points into buf or the dictionary. */
 static const char *group_key(const struct hipTable *t, int c, int kind, uint32_t k, int32_t lo, long long *key, char *buf, size_t len) {
     if (kind == HIPKIND_I32) { *key = (long long)lo + (long long)k; snprintf(buf, len, "%d", (int)*key); return buf; }
@@ -890,24 +947,44 @@ static const char *group_key(const struct hipTable *t, int c, int kind, uint32_t
     return t->dict[c].values[k];
 }
 
-static int group_result_fill(struct hipGroupResult *res, const struct hipTable *t, const uint64_t *counts, uint32_t n_bins, int32_t lo) {
+/* The groups of a result: the bins k of 0 .. n_bins with nonzero[k], in bin order.  *numGroups = how many; with a group
+ * column (column >= 0) *keys and *keyText get their keys and owned texts (one spare entry each).  -1 when out of memory:
+ * *numGroups then counts the texts made, so that free_group_keys() frees what there is. */
+static int group_keys_fill(const struct hipTable *t, int column, int kind, int32_t lo, const uint64_t *nonzero, uint32_t n_bins,
+                           long long **keys, char ***keyText, int *numGroups) {
     int n = 0;
-    for (uint32_t k = 0; k < n_bins; k++) n += counts[k] != 0;
-    res->keys = calloc((size_t)n + 1, sizeof *res->keys);
-    res->keyText = calloc((size_t)n + 1, sizeof *res->keyText);
-    res->counts = calloc((size_t)n + 1, sizeof *res->counts);
-    if (!res->keys || !res->keyText || !res->counts) { fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
+    for (uint32_t k = 0; k < n_bins; k++) n += nonzero[k] != 0;
+    *numGroups = column >= 0 ? 0 : n;
+    if (column < 0) return 0;
+    *keys = calloc((size_t)n + 1, sizeof **keys);
+    *keyText = calloc((size_t)n + 1, sizeof **keyText);
+    for (uint32_t k = 0; k < n_bins && *keys && *keyText; k++) {
+        if (!nonzero[k]) continue;
+        char buf[32];
+        if (!((*keyText)[*numGroups] = strdup(group_key(t, column, kind, k, lo, &(*keys)[*numGroups], buf, sizeof buf)))) break;
+        ++*numGroups;
+    }
+    if (*keys && *keyText && *numGroups == n) return 0;
+    fprintf(stderr, "HIP engine: out of memory\n");
+    return -1;
+}
+
+static void free_group_keys(long long *keys, char **keyText, int numGroups) {
+    for (int g = 0; g < numGroups && keyText; g++) free(keyText[g]);
+    free(keyText);
+    free(keys);
+}
+
+static int group_result_fill(struct hipGroupResult *res, const struct hipTable *t, const uint64_t *counts, uint32_t n_bins, int32_t lo) {
+    if (group_keys_fill(t, res->column, res->kind, lo, counts, n_bins, &res->keys, &res->keyText, &res->numGroups) != 0) return -1;
+    res->counts = calloc((size_t)res->numGroups + 1, sizeof *res->counts);
+    if (!res->counts) { fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
     int g = 0;
     for (uint32_t k = 0; k < n_bins; k++) {
         if (!counts[k]) continue;
-        char buf[32];
-        res->keyText[g] = strdup(group_key(t, res->column, res->kind, k, lo, &res->keys[g], buf, sizeof buf));
-        if (!res->keyText[g]) { fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
-        res->counts[g] = counts[k];
+        res->counts[g++] = counts[k];
         res->total += (long long)counts[k];
-        g++;
     }
-    res->numGroups = n;
     return 0;
 }
 
@@ -924,11 +1001,8 @@ struct hipGroupResult *executeQueryGroupCountHIP(struct engineS *engine, const c
     if (t->xch) { fprintf(stderr, "HIP engine: grouped COUNT is not exchanged across ranks\n"); return res; }
     res->column = c;
     res->kind = k_group_kind[c];
-    hipTableLockShared(t);
-    const int lane = hipTableAcquireLane(t);
-    if (lane == HIP_LANE_REFUSED) { hipTableUnlockShared(t); return res; }  /* reason on stderr */
     struct query q;
-    query_init(&q, engine, t, lane, false);
+    if (!query_open(engine, &q)) return res;                             /* reason on stderr */
     uint64_t *counts = NULL;
     struct group_plan gp;
     int rc = group_plan_init(engine, whereClause, &q, c, groupColumn, "grouped COUNT", &gp);
@@ -936,31 +1010,17 @@ struct hipGroupResult *executeQueryGroupCountHIP(struct engineS *engine, const c
         counts = calloc(gp.n_bins, sizeof *counts);
         if (!counts) { fprintf(stderr, "HIP engine: out of memory\n"); rc = -1; }
     }
-    if (rc == 0 && !gp.empty) {
-        if (gp.single) {
-            /* one value: the number of rows the selection returns (scan mode: the count, no list) */
-            q.count_only = q.n_probes == 0;
-            rc = query_issue_all(&q);
-            if (rc == 0) rc = query_await(&q);
-            if (rc == 0) counts[0] = q.total;
-        } else {
-            rc = group_bins(&q, &gp, -1, counts);
-        }
-    }
+    if (rc == 0 && !gp.empty) rc = group_counts(&q, &gp, counts);
     if (rc == 0 && group_result_fill(res, t, counts ? counts : (uint64_t[1]){ 0 }, gp.empty ? 0u : gp.n_bins, gp.lo) == 0) res->success = true;
     free(counts);
-    query_free(&q);
-    hipTableReleaseLane(t, lane);
-    hipTableUnlockShared(t);
+    query_close(&q);
     res->queryTime = now_seconds() - t0;
     return res;
 }
 
 void freeGroupResultHIP(struct hipGroupResult *res) {
     if (!res) return;
-    for (int g = 0; g < res->numGroups && res->keyText; g++) free(res->keyText[g]);
-    free(res->keyText);
-    free(res->keys);
+    free_group_keys(res->keys, res->keyText, res->numGroups);
     free(res->counts);
     free(res);
 }
@@ -969,31 +1029,18 @@ void freeGroupResultHIP(struct hipGroupResult *res) {
 
 /* acc[4][n_bins] (count, sum, min image, max image: pqps_filter_aggregate's layout) into the result, groups with rows only */
 static int aggregate_result_fill(struct hipAggregateResult *res, const struct hipTable *t, const uint64_t *acc, uint32_t n_bins, int32_t lo) {
-    int n = 0;
-    for (uint32_t k = 0; k < n_bins; k++) n += acc[k] != 0;
-    const bool grouped = res->groupColumn >= 0;
-    res->counts = calloc((size_t)n + 1, sizeof *res->counts);
-    res->sums = calloc((size_t)n + 1, sizeof *res->sums);
-    res->mins = calloc((size_t)n + 1, sizeof *res->mins);
-    res->maxs = calloc((size_t)n + 1, sizeof *res->maxs);
-    if (grouped) {
-        res->keys = calloc((size_t)n + 1, sizeof *res->keys);
-        res->keyText = calloc((size_t)n + 1, sizeof *res->keyText);
-    }
-    if (!res->counts || !res->sums || !res->mins || !res->maxs || (grouped && (!res->keys || !res->keyText))) {
-        fprintf(stderr, "HIP engine: out of memory\n");
-        return -1;
-    }
+    if (group_keys_fill(t, res->groupColumn, res->groupKind, lo, acc, n_bins, &res->keys, &res->keyText, &res->numGroups) != 0) return -1;
+    const size_t n = (size_t)res->numGroups;
+    res->counts = calloc(n + 1, sizeof *res->counts);
+    res->sums = calloc(n + 1, sizeof *res->sums);
+    res->mins = calloc(n + 1, sizeof *res->mins);
+    res->maxs = calloc(n + 1, sizeof *res->maxs);
+    if (!res->counts || !res->sums || !res->mins || !res->maxs) { fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
     /* the image of an i32 value is (u64)(i64)v ^ 2^63, of a u64 value the value itself */
     const uint64_t flip = res->valueKind == HIPKIND_I32 ? 0x8000000000000000ull : 0;
     int g = 0;
     for (uint32_t k = 0; k < n_bins; k++) {
         if (!acc[k]) continue;
-        if (grouped) {
-            char buf[32];
-            res->keyText[g] = strdup(group_key(t, res->groupColumn, res->groupKind, k, lo, &res->keys[g], buf, sizeof buf));
-            if (!res->keyText[g]) { res->numGroups = g; fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
-        }
         res->counts[g] = acc[k];
         res->sums[g] = (long long)acc[n_bins + k];
         res->mins[g] = (long long)(acc[2 * n_bins + k] ^ flip);
@@ -1001,7 +1048,6 @@ static int aggregate_result_fill(struct hipAggregateResult *res, const struct hi
         res->total += (long long)acc[k];
         g++;
     }
-    res->numGroups = n;
     return 0;
 }
 
@@ -1026,11 +1072,8 @@ struct hipAggregateResult *executeQueryAggregateHIP(struct engineS *engine, cons
     res->valueKind = k_group_kind[v];
     res->groupColumn = c;
     res->groupKind = c >= 0 ? k_group_kind[c] : -1;
-    hipTableLockShared(t);
-    const int lane = hipTableAcquireLane(t);
-    if (lane == HIP_LANE_REFUSED) { hipTableUnlockShared(t); return res; }  /* reason on stderr */
     struct query q;
-    query_init(&q, engine, t, lane, false);
+    if (!query_open(engine, &q)) return res;                             /* reason on stderr */
     uint64_t *acc = NULL;
     struct group_plan gp;
     int rc = group_plan_init(engine, whereClause, &q, c, groupColumn, "aggregate", &gp);
@@ -1042,18 +1085,14 @@ struct hipAggregateResult *executeQueryAggregateHIP(struct engineS *engine, cons
     if (rc == 0 && !gp.empty) rc = group_bins(&q, &gp, v, acc);
     if (rc == 0 && aggregate_result_fill(res, t, acc ? acc : (uint64_t[4]){ 0 }, gp.empty ? 0u : gp.n_bins, gp.lo) == 0) res->success = true;
     free(acc);
-    query_free(&q);
-    hipTableReleaseLane(t, lane);
-    hipTableUnlockShared(t);
+    query_close(&q);
     res->queryTime = now_seconds() - t0;
     return res;
 }
 
 void freeAggregateResultHIP(struct hipAggregateResult *res) {
     if (!res) return;
-    for (int g = 0; g < res->numGroups && res->keyText; g++) free(res->keyText[g]);
-    free(res->keyText);
-    free(res->keys);
+    free_group_keys(res->keys, res->keyText, res->numGroups);
     free(res->counts);
     free(res->sums);
     free(res->mins);
@@ -1102,15 +1141,27 @@ static int distinct_plan_init(struct query *q, const struct group_plan *gp, int 
     return 0;
 }
 
-/* The rows of every group (counts[0 .. n_bins)), as executeQueryGroupCountHIP finds them. */
-static int group_counts(struct query *q, const struct group_plan *gp, uint64_t *counts) {
-    if (!gp->single && gp->c >= 0) return group_bins(q, gp, -1, counts);
-    /* one group: the number of rows the selection returns (scan mode: the count, no list) */
-    q->count_only = q->n_probes == 0;
-    int rc = query_issue_all(q);
-    if (rc == 0) rc = query_await(q);
-    if (rc == 0) counts[0] = q->total;
-    return rc;
+struct distinct_call { const struct group_plan *gp; const struct distinct_plan *dp; void **buf; size_t head; bool *filled; };
+
+/* shard s's buffer buf[s] of the bitmap forms: [total][distinct][bitmap], the bitmap `head` bytes in */
+#define DBUF_TOTAL(s) ((uint64_t *)buf[s])
+#define DBUF_DISTINCT(s) ((uint64_t *)((char *)buf[s] + 16))
+#define DBUF_BITMAP(s) ((uint32_t *)((char *)buf[s] + head))
+
+static int distinct_fused_call(struct query *q, int s, pqps_ctx *ctx, void *stream, void *arg) {
+    const struct distinct_call *a = arg;
+    const struct group_plan *gp = a->gp;
+    const struct distinct_plan *dp = a->dp;
+    void **buf = a->buf;
+    const size_t head = a->head;
+    const struct shard_pred *sp = &q->sp[s];
+    const bool grouped = gp->c >= 0 && !gp->single;
+    if (pqps_filter_distinct(ctx, sp->cols, sp->n_cols, hipTableShard(q->t, s)->n_rows, sp->pred, &dp->vcol[s], dp->v_base, dp->n_values,
+                             grouped ? &gp->gcol[s] : NULL, gp->bin_base, gp->n_bins, DBUF_BITMAP(s), DBUF_TOTAL(s),
+                             q->n_shards > 1 ? NULL : DBUF_DISTINCT(s), stream) != PQPS_OK)
+        return engine_error("COUNT(DISTINCT) filter");
+    a->filled[s] = true;
+    return 0;
 }
 
 /* The bitmap forms on every shard: one shard pops its bitmap on its device; several download theirs, OR them on the host
@@ -1128,31 +1179,8 @@ static int distinct_bitmap(struct query *q, const struct group_plan *gp, const s
     *total = 0;
     for (int s = 0; s < q->n_shards && rc == 0; s++)
         if (pqps_malloc(hipTableShard(q->t, s)->ctx, bytes, &buf[s]) != PQPS_OK) rc = engine_error("COUNT(DISTINCT) bitmap");
-#define DBUF_TOTAL(s) ((uint64_t *)buf[s])
-#define DBUF_DISTINCT(s) ((uint64_t *)((char *)buf[s] + 16))
-#define DBUF_BITMAP(s) ((uint32_t *)((char *)buf[s] + head))
     if (rc == 0 && gp->fused) {
-        const struct hipPass *last = &q->plan.pass[0];
-        hipTableLockIssue(q->t);
-        for (int s = 0; s < q->n_shards && rc == 0; s++) {
-            struct hipTable *sh = hipTableShard(q->t, s);
-            struct shard_pred *sp = &q->sp[s];
-            pqps_ctx *ctx = sh->ctx;
-            void *stream = NULL;
-            if (sh->n_rows == 0) continue;
-            if (q->lane >= 0 && pqps_qstream_lane(sh->qs, (uint32_t)q->lane, sh->n_rows, NULL, &ctx, &stream) != PQPS_OK) { rc = engine_error("query lane"); break; }
-            sp->pred = &last->pred;
-            sp->n_cols = last->pred.n_columns;
-            pass_columns(sh, last, NULL, true, sp->cols);
-            if (pqps_filter_distinct(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, &dp->vcol[s], dp->v_base, D, grouped ? &gp->gcol[s] : NULL,
-                                     gp->bin_base, G, DBUF_BITMAP(s), DBUF_TOTAL(s), multi ? NULL : DBUF_DISTINCT(s), stream) != PQPS_OK)
-                rc = engine_error("COUNT(DISTINCT) filter");
-            else filled[s] = true;
-            /* marked even after a failed call: the lane must not be handed on while a launch of this query runs */
-            if (q->lane >= 0 && pqps_qstream_mark(sh->qs, (uint32_t)q->lane) != PQPS_OK && rc == 0) rc = engine_error("query lane");
-        }
-        hipTableUnlockIssue(q->t);
-        for (int s = 0; s < q->n_shards; s++) if (wait_shard(q, s) != 0 && rc == 0) rc = -1;
+        rc = fused_issue(q, distinct_fused_call, &(struct distinct_call){ gp, dp, buf, head, filled });
         for (int s = 0; s < q->n_shards && rc == 0; s++) {
             uint64_t n = 0;
             if (!filled[s]) continue;
@@ -1160,9 +1188,7 @@ static int distinct_bitmap(struct query *q, const struct group_plan *gp, const s
             *total += n;
         }
     } else if (rc == 0) {
-        q->per_shard = true;
-        rc = query_issue_all(q);
-        if (rc == 0) rc = query_await(q);
+        rc = query_lists(q);
         if (rc == 0) *total = q->total;
         for (int s = 0; s < q->n_shards && rc == 0; s++) {
             const struct hipTable *sh = hipTableShard(q->t, s);
@@ -1216,9 +1242,7 @@ static int distinct_sort(struct query *q, const struct group_plan *gp, const str
     const bool grouped = gp->c >= 0 && !gp->single;
     const bool wide = dp->v == HIPCOL_COMMAND_ID;
     const bool multi = q->n_shards > 1;
-    q->per_shard = true;
-    int rc = query_issue_all(q);
-    if (rc == 0) rc = query_await(q);
+    int rc = query_lists(q);
     if (rc != 0) return rc;
     *total = q->total;
     struct distinct_keys keys[HIP_MAX_SHARDS];
@@ -1268,26 +1292,11 @@ static int distinct_sort(struct query *q, const struct group_plan *gp, const str
 
 /* distinct[0 .. n_bins) into the result: the groups with rows, in bin order */
 static int distinct_result_fill(struct hipDistinctResult *res, const struct hipTable *t, const uint64_t *distinct, uint32_t n_bins, int32_t lo) {
-    int n = 0;
-    for (uint32_t k = 0; k < n_bins; k++) n += distinct[k] != 0;
-    const bool grouped = res->groupColumn >= 0;
-    res->distinct = calloc((size_t)n + 1, sizeof *res->distinct);
-    if (grouped) {
-        res->keys = calloc((size_t)n + 1, sizeof *res->keys);
-        res->keyText = calloc((size_t)n + 1, sizeof *res->keyText);
-    }
-    if (!res->distinct || (grouped && (!res->keys || !res->keyText))) { fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
+    if (group_keys_fill(t, res->groupColumn, res->groupKind, lo, distinct, n_bins, &res->keys, &res->keyText, &res->numGroups) != 0) return -1;
+    res->distinct = calloc((size_t)res->numGroups + 1, sizeof *res->distinct);
+    if (!res->distinct) { fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
     int g = 0;
-    for (uint32_t k = 0; k < n_bins; k++) {
-        if (!distinct[k]) continue;
-        if (grouped) {
-            char buf[32];
-            res->keyText[g] = strdup(group_key(t, res->groupColumn, res->groupKind, k, lo, &res->keys[g], buf, sizeof buf));
-            if (!res->keyText[g]) { res->numGroups = g; fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
-        }
-        res->distinct[g++] = distinct[k];
-    }
-    res->numGroups = n;
+    for (uint32_t k = 0; k < n_bins; k++) if (distinct[k]) res->distinct[g++] = distinct[k];
     return 0;
 }
 
@@ -1308,11 +1317,8 @@ struct hipDistinctResult *executeQueryCountDistinctHIP(struct engineS *engine, c
     res->valueKind = k_group_kind[v];
     res->groupColumn = c;
     res->groupKind = c >= 0 ? k_group_kind[c] : -1;
-    hipTableLockShared(t);
-    const int lane = hipTableAcquireLane(t);
-    if (lane == HIP_LANE_REFUSED) { hipTableUnlockShared(t); return res; }  /* reason on stderr */
     struct query q;
-    query_init(&q, engine, t, lane, false);
+    if (!query_open(engine, &q)) return res;                             /* reason on stderr */
     uint64_t *distinct = NULL, total = 0;
     struct group_plan gp;
     struct distinct_plan dp;
@@ -1335,18 +1341,14 @@ struct hipDistinctResult *executeQueryCountDistinctHIP(struct engineS *engine, c
     res->total = (long long)total;
     if (rc == 0 && distinct_result_fill(res, t, distinct ? distinct : (uint64_t[1]){ 0 }, gp.empty ? 0u : gp.n_bins, gp.lo) == 0) res->success = true;
     free(distinct);
-    query_free(&q);
-    hipTableReleaseLane(t, lane);
-    hipTableUnlockShared(t);
+    query_close(&q);
     res->queryTime = now_seconds() - t0;
     return res;
 }
 
 void freeDistinctResultHIP(struct hipDistinctResult *res) {
     if (!res) return;
-    for (int g = 0; g < res->numGroups && res->keyText; g++) free(res->keyText[g]);
-    free(res->keyText);
-    free(res->keys);
+    free_group_keys(res->keys, res->keyText, res->numGroups);
     free(res->distinct);
     free(res);
 }
@@ -1672,6 +1674,20 @@ static int order_collect(pqps_ctx *cs, const uint64_t *out_dev, uint64_t n, bool
     return 0;
 }
 
+struct topk_call { const struct order_plan *op; void **buf; const size_t *scratch_bytes; size_t out_bytes; };
+
+static int topk_fused_call(struct query *q, int s, pqps_ctx *ctx, void *stream, void *arg) {
+    const struct topk_call *a = arg;
+    const struct order_plan *op = a->op;
+    const struct hipTable *sh = hipTableShard(q->t, s);
+    const struct shard_pred *sp = &q->sp[s];
+    char *b = a->buf[s];
+    if (pqps_filter_topk(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, op->no_key ? NULL : &op->kcol[s], op->key_signed, op->desc,
+                         (uint32_t)sh->row0, op->k, b + 16 + a->out_bytes, a->scratch_bytes[s], (uint64_t *)(b + 16), (uint64_t *)b, stream) != PQPS_OK)
+        return engine_error("ORDER BY filter");
+    return 0;
+}
+
 /* The top-K paths on every shard: each shard's K best (fused: pqps_filter_topk on the query's lane; otherwise the
  * selection, left per shard, and pqps_topk_list over every list) into keys[0 .. *n_keys), *matches the selection's rows. */
 static int order_topk(struct query *q, const struct order_plan *op, struct order_key *keys, uint64_t *n_keys, uint64_t *matches) {
@@ -1684,9 +1700,7 @@ static int order_topk(struct query *q, const struct order_plan *op, struct order
     *n_keys = 0;
     *matches = 0;
     if (!op->fused) {
-        q->per_shard = true;
-        rc = query_issue_all(q);
-        if (rc == 0) rc = query_await(q);
+        rc = query_lists(q);
         if (rc == 0) *matches = q->total;
     }
     /* per shard one buffer: [16 B count][out: K keys][scratch] */
@@ -1698,27 +1712,7 @@ static int order_topk(struct query *q, const struct order_plan *op, struct order
         if (pqps_malloc(sh->ctx, 16 + out_bytes + scratch_bytes[s], &buf[s]) != PQPS_OK) rc = engine_error("ORDER BY scratch");
     }
     if (rc == 0 && op->fused) {
-        const struct hipPass *last = &q->plan.pass[0];
-        hipTableLockIssue(q->t);
-        for (int s = 0; s < q->n_shards && rc == 0; s++) {
-            struct hipTable *sh = hipTableShard(q->t, s);
-            struct shard_pred *sp = &q->sp[s];
-            pqps_ctx *ctx = sh->ctx;
-            void *stream = NULL;
-            if (sh->n_rows == 0) continue;
-            if (q->lane >= 0 && pqps_qstream_lane(sh->qs, (uint32_t)q->lane, sh->n_rows, NULL, &ctx, &stream) != PQPS_OK) { rc = engine_error("query lane"); break; }
-            sp->pred = &last->pred;
-            sp->n_cols = last->pred.n_columns;
-            pass_columns(sh, last, NULL, true, sp->cols);
-            char *b = buf[s];
-            if (pqps_filter_topk(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, op->no_key ? NULL : &op->kcol[s], op->key_signed, op->desc,
-                                 (uint32_t)sh->row0, k, b + 16 + out_bytes, scratch_bytes[s], (uint64_t *)(b + 16), (uint64_t *)b, stream) != PQPS_OK)
-                rc = engine_error("ORDER BY filter");
-            /* marked even after a failed call: the lane must not be handed on while a launch of this query runs */
-            if (q->lane >= 0 && pqps_qstream_mark(sh->qs, (uint32_t)q->lane) != PQPS_OK && rc == 0) rc = engine_error("query lane");
-        }
-        hipTableUnlockIssue(q->t);
-        for (int s = 0; s < q->n_shards; s++) if (wait_shard(q, s) != 0 && rc == 0) rc = -1;
+        rc = fused_issue(q, topk_fused_call, &(struct topk_call){ op, buf, scratch_bytes, out_bytes });
         for (int s = 0; s < q->n_shards && rc == 0; s++) {
             if (!buf[s]) continue;
             if (pqps_download(lane_copy_ctx(q, s), &got[s], buf[s], sizeof got[s], NULL) != PQPS_OK) rc = engine_error("ORDER BY count");
@@ -1744,9 +1738,7 @@ static int order_topk(struct query *q, const struct order_plan *op, struct order
 /* The full sort: the selection, every shard's list sorted on its device (pqps_sort_list), the first `want` rows of each
  * downloaded and the shards merged on the host by (key, row) -- one shard needs no keys. */
 static int order_sort(struct query *q, const struct order_plan *op, uint64_t want, uint32_t **rows, uint64_t *n_rows, uint64_t *matches) {
-    q->per_shard = true;
-    int rc = query_issue_all(q);
-    if (rc == 0) rc = query_await(q);
+    int rc = query_lists(q);
     if (rc != 0) return rc;
     *matches = q->total;
     const int n_shards = q->n_shards;
@@ -1865,17 +1857,12 @@ long long executeQueryOrderIdsHIP(struct engineS *engine, struct whereClauseS *w
     struct hipTable *t = engine->record_block;
     struct order_plan op;
     if (order_plan_init(t, orderColumn, descending, &op) != 0) return -1;
-    hipTableLockShared(t);
-    const int lane = hipTableAcquireLane(t);
-    if (lane == HIP_LANE_REFUSED) { hipTableUnlockShared(t); return -1; }    /* reason on stderr */
     struct query q;
-    query_init(&q, engine, t, lane, false);
+    if (!query_open(engine, &q)) return -1;                              /* reason on stderr */
     uint32_t *rows = NULL;
     uint64_t n = 0, m = 0;
     const int rc = order_rows(engine, whereClause, &q, &op, limit, &rows, &n, &m);
-    query_free(&q);
-    hipTableReleaseLane(t, lane);
-    hipTableUnlockShared(t);
+    query_close(&q);
     if (queryTime) *queryTime = now_seconds() - t0;
     if (rc != 0) { free(rows); return -1; }
     *ids = rows;
@@ -1902,11 +1889,8 @@ struct hipColumnarResult *executeQuerySelectOrderedHIP(struct engineS *engine, c
     const double t0 = now_seconds();
     struct order_plan op;
     if (order_plan_init(t, orderColumn, descending, &op) != 0) return res;
-    hipTableLockShared(t);
-    const int lane = hipTableAcquireLane(t);
-    if (lane == HIP_LANE_REFUSED) { hipTableUnlockShared(t); return res; }  /* reason on stderr */
     struct query q;
-    query_init(&q, engine, t, lane, false);
+    if (!query_open(engine, &q)) return res;                             /* reason on stderr */
     uint32_t *rows = NULL;
     uint64_t n = 0, m = 0;
     int rc = order_rows(engine, whereClause, &q, &op, limit, &rows, &n, &m);
@@ -1942,9 +1926,7 @@ struct hipColumnarResult *executeQuerySelectOrderedHIP(struct engineS *engine, c
     for (int s = 0; s < n_shards; s++) { free(sub_ids[s]); free(sub_pos[s]); }
     free(tmp);
     free(rows);
-    query_free(&q);
-    hipTableReleaseLane(t, lane);
-    hipTableUnlockShared(t);
+    query_close(&q);
     res->numRecords = rc == 0 ? (int)n : 0;
     res->queryTime = now_seconds() - t0;
     res->success = rc == 0;
