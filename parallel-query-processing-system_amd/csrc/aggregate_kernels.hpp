@@ -1,5 +1,5 @@
 // aggregate_kernels.hpp -- device code of COUNT / SUM / MIN / MAX of a value column, overall or per group (included once by
-// pqps_hip.hip, after group_kernels.hpp, whose bins and group-column loads it shares).
+// pqps_hip.hip, after fused_common.hpp).
 //
 // No counterpart in the reference (its engines have no aggregates).  One accumulator form for both value widths, four u64
 // words per bin:
@@ -10,9 +10,8 @@
 // so that every update is a native 64-bit add / unsigned min / unsigned max (ds_add_u64, ds_min_u64, ds_max_u64,
 // global_atomic_add_x2 / umin_x2 / umax_x2 -- no compare-and-swap loops).  The host undoes the image.
 //
-// Fused scan (pqps_filter_aggregate): the structure of group_scan_kernel -- eval_step_full on every step, rows_below on the
-// partial last one -- and, in a wave whose step holds a match, one round of value-column loads (and group-column loads) in
-// the predicate's per-lane pattern (RPL = 4: one ld_x4 per 256-row chunk for an i32 value, two for command_id).  Bin paths:
+// Fused scan (pqps_filter_aggregate): the shared scan loop (fused_common.hpp) with one round of value-column loads (one
+// ld_x4 per 256-row chunk for an i32 value, two for command_id) and group-column loads per step that holds a match.  Bin paths:
 //   ONE    no GROUP BY   per-lane registers, a wave reduction (shuffles, once per workgroup), the 4 waves through LDS
 //   LDS    D <= 2304     a table of 28 B per bin in dynamic LDS (u32 count, u64 sum / min / max), 64 KiB at most
 //   GLOBAL D <= 65536    four global 64-bit atomics per matching row straight into the output (a correctness path, like
@@ -32,7 +31,7 @@ constexpr uint32_t kAggFields = 4;                 // count, sum, min image, max
 constexpr uint32_t kAggSumParts = 64;              // partial rows one workgroup of agg_sum_kernel combines
 
 struct AggArgs {
-    EvalArgs e;                      // the WHERE, as the COUNT kernels take it -- first: eval_step_full reads it in place
+    EvalArgs e;                      // the WHERE, as the COUNT kernels take it -- first: the scan loop reads it in place
     const void *vcol;                // value column: i32 or u64
     const void *gcol;                // group column (bytes, u16, u32 or a bit plane); unused by AGG_ONE
     uint64_t *out;                   // GLOBAL: [4][n_bins] (initialised before the launch)
@@ -41,43 +40,11 @@ struct AggArgs {
     uint32_t bin_base;
     uint32_t n_bins;
 };
-typedef const __attribute__((address_space(4))) AggArgs ACArgs;
-__device__ __forceinline__ ACArgs &agg_args() { return *(ACArgs *)__builtin_amdgcn_kernarg_segment_ptr(); }
 
-// the value a sum adds and its order-preserving image
-template <bool U64> __device__ __forceinline__ uint64_t agg_widen(uint64_t raw) {
-    if constexpr (U64) return raw;
-    else return (uint64_t)(int64_t)(int32_t)(uint32_t)raw;
-}
+// the order-preserving image of the value a sum adds (widen_value)
 template <bool U64> __device__ __forceinline__ uint64_t agg_image(uint64_t wide) {
     if constexpr (U64) return wide;
     else return wide ^ 0x8000000000000000ull;
-}
-
-// The values of a lane's 16 rows of one full step, in eval_step_full's bit order.
-template <bool U64, bool NT>
-__device__ __forceinline__ void load_value_step(const char *base, uint64_t step_row0, uint32_t lane, uint64_t (&v)[16]) {
-    const uint64_t lane_row0 = step_row0 + lane * kRplGeneric;
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-        const uint64_t r0 = lane_row0 + (uint64_t)u * 256;
-        if constexpr (U64) {
-            const uint4 q0 = ld_x4<NT>(base + r0 * 8);
-            const uint4 q1 = ld_x4<NT>(base + r0 * 8 + 16);
-            v[4 * u] = (uint64_t)q0.x | ((uint64_t)q0.y << 32); v[4 * u + 1] = (uint64_t)q0.z | ((uint64_t)q0.w << 32);
-            v[4 * u + 2] = (uint64_t)q1.x | ((uint64_t)q1.y << 32); v[4 * u + 3] = (uint64_t)q1.z | ((uint64_t)q1.w << 32);
-        } else {
-            const uint4 q = ld_x4<NT>(base + r0 * 4);
-            v[4 * u] = agg_widen<false>(q.x); v[4 * u + 1] = agg_widen<false>(q.y);
-            v[4 * u + 2] = agg_widen<false>(q.z); v[4 * u + 3] = agg_widen<false>(q.w);
-        }
-    }
-}
-
-__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int off) {
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, off, 64);
-    const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), off, 64);
-    return (uint64_t)lo | ((uint64_t)hi << 32);
 }
 
 // (count, sum, min image, max image) of the 64 lanes, in every lane
@@ -137,30 +104,22 @@ __device__ __forceinline__ void agg_global_add(uint64_t *out, uint32_t nb, uint3
 
 template <int PATH, bool U64, bool NT>
 __global__ __launch_bounds__(kBlock, 1) void agg_scan_kernel(const AggArgs) {
-    ACArgs &g = agg_args();
+    const auto &g = kernarg<AggArgs>();
     CArgs &a = g.e;
     extern __shared__ uint64_t agg_lds[];                       // LDS path: the table
     const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const uint32_t nb = g.n_bins, base_bin = g.bin_base, wl = g.gwidth_log2;
     const char *vbase = (const char *)g.vcol;
     const char *gbase = (const char *)g.gcol;
-    const uint64_t wave = (uint64_t)blockIdx.x * kWaves + wv;
-    const uint64_t n_waves = (uint64_t)gridDim.x * kWaves;
-    const uint64_t n_rows = a.n_rows;
-    const uint64_t steps = (n_rows + kStepRows - 1) / kStepRows;
     AggLds t(agg_lds, nb);
     if constexpr (PATH == AGG_LDS) {
         t.clear(nb);
         __syncthreads();
     }
     uint64_t cnt = 0, sum = 0, mn = ~0ull, mx = 0;              // AGG_ONE
-    for (uint64_t step = wave; step < steps; step += n_waves) {
-        const uint64_t step_row0 = step * kStepRows;
-        uint32_t mbits = eval_step_full<NT>(a, step_row0, lane);
-        if (step_row0 + kStepRows > n_rows) mbits &= rows_below<kRplGeneric>(step_row0, n_rows, lane);   // the partial last step
-        if (__ballot(mbits != 0u) == 0) continue;               // uniform: no match, no value load
+    fused_scan_steps<NT>(a, lane, wv, [&](uint64_t step_row0, uint32_t mbits) {
         uint64_t v[16];
-        load_value_step<U64, NT>(vbase, step_row0, lane, v);
+        load_step_u64<U64, NT>(vbase, step_row0, lane, v);
         if constexpr (PATH == AGG_ONE) {
             cnt += __popc(mbits);
 #pragma unroll
@@ -173,7 +132,7 @@ __global__ __launch_bounds__(kBlock, 1) void agg_scan_kernel(const AggArgs) {
             }
         } else {
             uint32_t gv[16];
-            load_group_step<NT>(gbase, wl, step_row0, lane, gv);
+            load_step_u32<NT>(gbase, wl, step_row0, lane, gv);
 #pragma unroll
             for (int p = 0; p < 16; p++) {
                 const uint32_t b = gv[p] - base_bin;
@@ -183,7 +142,7 @@ __global__ __launch_bounds__(kBlock, 1) void agg_scan_kernel(const AggArgs) {
                 }
             }
         }
-    }
+    });
     if constexpr (PATH == AGG_ONE) {
         block_reduce_acc(cnt, sum, mn, mx);
         if (threadIdx.x == 0) {
@@ -232,6 +191,7 @@ __global__ __launch_bounds__(kBlock) void agg_sum_kernel(const uint64_t *__restr
 // The accumulators over an ID list: ids[0 .. min(*count, capacity)), row = id - id_base.  gcol == nullptr: no GROUP BY
 // (n_bins = 1), per-lane registers reduced per workgroup, one atomic per field and workgroup; LDS: a workgroup table
 // flushed with one atomic per field of a bin that has rows; otherwise four atomics per row.  out initialised before the launch.
+// The walk is for_each_listed_row's, written out here (why: DESIGN.md §7a).
 template <int PATH, bool U64>
 __global__ __launch_bounds__(kBlock) void agg_list_kernel(const void *vcol, const void *gcol, uint32_t gwlog2, uint64_t n_rows,
                                                           const uint32_t *__restrict__ ids, const uint64_t *count, uint64_t capacity,
@@ -248,15 +208,14 @@ __global__ __launch_bounds__(kBlock) void agg_list_kernel(const void *vcol, cons
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
         const uint64_t row = (uint64_t)(ids[i] - id_base);
         if (row >= n_rows) continue;                            // (never: a shard's list holds its own rows)
-        const uint64_t v = U64 ? ((const uint64_t *)vcol)[row] : agg_widen<false>((uint32_t)((const int32_t *)vcol)[row]);
+        const uint64_t v = U64 ? ((const uint64_t *)vcol)[row] : widen_value<false>((uint32_t)((const int32_t *)vcol)[row]);
         const uint64_t img = agg_image<U64>(v);
         if constexpr (PATH == AGG_ONE) {
             cnt++; sum += v;
             mn = img < mn ? img : mn;
             mx = img > mx ? img : mx;
         } else {
-            const uint32_t gv = gwlog2 == 0 ? ((const uint8_t *)gcol)[row] : gwlog2 == 1 ? ((const uint16_t *)gcol)[row] : ((const uint32_t *)gcol)[row];
-            const uint32_t b = gv - bin_base;
+            const uint32_t b = gather_narrow(gcol, gwlog2, row) - bin_base;
             if (b >= n_bins) continue;
             if constexpr (PATH == AGG_LDS) t.add(b, v, img);
             else agg_global_add(out, n_bins, b, 1, v, img, img);

@@ -1,5 +1,5 @@
 // distinct_kernels.hpp -- device code of COUNT(DISTINCT value column), overall or per group (included once by pqps_hip.hip,
-// after group_kernels.hpp, whose bins and column loads it shares).
+// after fused_common.hpp).
 //
 // No counterpart in the reference (its engines have no aggregates).  The accumulator is a PRESENCE BITMAP: G rows (group
 // bins, 1 without GROUP BY) of W = ceil(Dv / 32) u32 words, bit v of row g set iff some matching row has group bin g and
@@ -7,9 +7,8 @@
 // string column, the value minus the column's minimum for an i32 column, 0 / 1 for sudo_used.  Bits only ever go from 0
 // to 1, so every update is an OR, partial bitmaps merge by OR (shards too), and the answer is a popcount per row.
 //
-// Fused scan (pqps_filter_distinct): the loop of group_scan_kernel / agg_scan_kernel -- eval_step_full on every step,
-// rows_below on the partial last one -- and, in a wave whose step holds a match, one round of value-column loads (and
-// group-column loads) in the predicate's per-lane pattern (load_group_step: 1, 2, 4 bytes or a bit plane).  Bitmap forms:
+// Fused scan (pqps_filter_distinct): the shared scan loop (fused_common.hpp) with one round of value-column loads (and
+// group-column loads: 1, 2, 4 bytes or a bit plane each) per step that holds a match.  Bitmap forms:
 //   REG    G x Dv <= 64     one u64 mask per lane (bit g * Dv + v), OR-reduced over the wave on the DPP path and over the
 //                           workgroup through LDS; the workgroup stores its G x W words into a partial row
 //   LDS    G x W <= 16384   the bitmap in dynamic LDS (64 KiB at most: two workgroups per CU).  TEST BEFORE SET: a row
@@ -37,7 +36,7 @@ constexpr uint64_t kDistMaxBits = 1ull << 30;      // G x W x 32 of the bitmap f
 constexpr uint32_t kDistOrParts = 64;              // partial rows one workgroup of dist_or_kernel combines
 
 struct DistArgs {
-    EvalArgs e;                      // the WHERE, as the COUNT kernels take it -- first: eval_step_full reads it in place
+    EvalArgs e;                      // the WHERE, as the COUNT kernels take it -- first: the scan loop reads it in place
     const void *vcol;                // value column (bytes, u16, u32 or a bit plane)
     const void *gcol;                // group column (the same forms); unused without GROUP BY
     uint32_t *bitmap;                // GLOBAL: [G][W] (zeroed before the launch)
@@ -48,19 +47,6 @@ struct DistArgs {
     uint32_t n_values, n_groups;     // Dv, G
     uint32_t words;                  // W
 };
-typedef const __attribute__((address_space(4))) DistArgs DCArgs;
-__device__ __forceinline__ DCArgs &dist_args() { return *(DCArgs *)__builtin_amdgcn_kernarg_segment_ptr(); }
-
-// OR over the 64 lanes, returned in every lane (the DPP pattern of wave_sum_u32)
-__device__ __forceinline__ uint32_t wave_or_u32(uint32_t v) {
-    v |= dpp_or_zero<0xb1>(v);
-    v |= dpp_or_zero<0x4e>(v);
-    v |= dpp_or_zero<0x124>(v);
-    v |= dpp_or_zero<0x128>(v);
-    v |= dpp_or_zero<0x142, 0xa>(v);
-    v |= dpp_or_zero<0x143, 0xc>(v);
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
 
 // word (g, w) of the bitmap out of the register form's mask (bit g * Dv + v)
 __device__ __forceinline__ uint32_t dist_reg_word(uint64_t mask, uint32_t t, uint32_t nv, uint32_t nw) {
@@ -92,7 +78,7 @@ __device__ __forceinline__ void dist_block_reduce(uint64_t &mask, uint64_t &cnt)
 
 template <int PATH, bool GROUPED, bool NT>
 __global__ __launch_bounds__(kBlock, 1) void dist_scan_kernel(const DistArgs) {
-    DCArgs &g = dist_args();
+    const auto &g = kernarg<DistArgs>();
     CArgs &a = g.e;
     extern __shared__ uint32_t dist_lds[];                      // LDS form: the bitmap
     const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -100,25 +86,17 @@ __global__ __launch_bounds__(kBlock, 1) void dist_scan_kernel(const DistArgs) {
     const uint32_t vwl = g.vwidth_log2, gwl = g.gwidth_log2;
     const char *vbase = (const char *)g.vcol;
     const char *gbase = (const char *)g.gcol;
-    const uint64_t wave = (uint64_t)blockIdx.x * kWaves + wv;
-    const uint64_t n_waves = (uint64_t)gridDim.x * kWaves;
-    const uint64_t n_rows = a.n_rows;
-    const uint64_t steps = (n_rows + kStepRows - 1) / kStepRows;
     const uint32_t n_words = ng * nw;                           // <= kDistLdsWords on the LDS form
     if constexpr (PATH == DIST_LDS) {
         for (uint32_t i = threadIdx.x; i < n_words; i += kBlock) dist_lds[i] = 0;
         __syncthreads();
     }
     uint64_t mask = 0, cnt = 0;
-    for (uint64_t step = wave; step < steps; step += n_waves) {
-        const uint64_t step_row0 = step * kStepRows;
-        uint32_t mbits = eval_step_full<NT>(a, step_row0, lane);
-        if (step_row0 + kStepRows > n_rows) mbits &= rows_below<kRplGeneric>(step_row0, n_rows, lane);   // the partial last step
-        if (__ballot(mbits != 0u) == 0) continue;               // uniform: no match, no value load
+    fused_scan_steps<NT>(a, lane, wv, [&](uint64_t step_row0, uint32_t mbits) {
         cnt += __popc(mbits);
         uint32_t v[16], gv[16];
-        load_group_step<NT>(vbase, vwl, step_row0, lane, v);
-        if constexpr (GROUPED) load_group_step<NT>(gbase, gwl, step_row0, lane, gv);
+        load_step_u32<NT>(vbase, vwl, step_row0, lane, v);
+        if constexpr (GROUPED) load_step_u32<NT>(gbase, gwl, step_row0, lane, gv);
 #pragma unroll
         for (int p = 0; p < 16; p++) {
             const uint32_t vb = v[p] - vb0;
@@ -132,7 +110,7 @@ __global__ __launch_bounds__(kBlock, 1) void dist_scan_kernel(const DistArgs) {
                 else dist_test_set(g.bitmap, idx, 1u << (vb & 31u));
             }
         }
-    }
+    });
     dist_block_reduce(mask, cnt);                               // (REG: the mask; every form: the count)
     if (threadIdx.x == 0) g.totals[blockIdx.x] = cnt;
     if constexpr (PATH == DIST_REG) {
@@ -202,11 +180,6 @@ __global__ __launch_bounds__(kBlock) void dist_count_kernel(const uint32_t *__re
     }
 }
 
-// value of row `row` of a 1, 2 or 4 byte column
-__device__ __forceinline__ uint32_t dist_gather(const void *col, uint32_t wl, uint64_t row) {
-    return wl == 0 ? ((const uint8_t *)col)[row] : wl == 1 ? ((const uint16_t *)col)[row] : ((const uint32_t *)col)[row];
-}
-
 // The bitmap over an ID list: ids[0 .. min(*count, capacity)), row = id - id_base.  REG: per-lane masks reduced per
 // workgroup, one atomic OR per non-zero word; LDS: a workgroup bitmap, one atomic OR per non-zero word; GLOBAL: test before
 // set on the bitmap.  bitmap zeroed before the launch.
@@ -222,21 +195,17 @@ __global__ __launch_bounds__(kBlock) void dist_list_kernel(const void *vcol, uin
         __syncthreads();
     }
     uint64_t mask = 0, unused = 0;
-    uint64_t n = *count;
-    if (n > capacity) n = capacity;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t row = (uint64_t)(ids[i] - id_base);
-        if (row >= n_rows) continue;                            // (never: a shard's list holds its own rows)
-        const uint32_t vb = dist_gather(vcol, vwl, row) - v_base;
-        const uint32_t gb = GROUPED ? dist_gather(gcol, gwl, row) - g_base : 0u;
-        if (vb >= n_values || gb >= n_groups) continue;
+    for_each_listed_row(ids, count, capacity, id_base, n_rows, [&](uint64_t row) {
+        const uint32_t vb = gather_narrow(vcol, vwl, row) - v_base;
+        const uint32_t gb = GROUPED ? gather_narrow(gcol, gwl, row) - g_base : 0u;
+        if (vb >= n_values || gb >= n_groups) return;
         if constexpr (PATH == DIST_REG) mask |= 1ull << (gb * n_values + vb);
         else {
             const uint64_t idx = (uint64_t)gb * n_words_row + (vb >> 5);
             if constexpr (PATH == DIST_LDS) dist_test_set(dist_lds, idx, 1u << (vb & 31u));
             else dist_test_set(bitmap, idx, 1u << (vb & 31u));
         }
-    }
+    });
     if constexpr (PATH == DIST_REG) {
         dist_block_reduce(mask, unused);
         if (threadIdx.x < n_words) {
@@ -260,13 +229,13 @@ __global__ __launch_bounds__(kBlock) void dist_keys_kernel(const void *vcol, uin
                                                            uint64_t *key, uint32_t *grp) {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
         const uint64_t row = (uint64_t)(ids[i] - id_base);
-        uint32_t gb = gcol ? dist_gather(gcol, gwl, row) - g_base : 0u;
+        uint32_t gb = gcol ? gather_narrow(gcol, gwl, row) - g_base : 0u;
         if (gb > n_groups) gb = n_groups;
         if constexpr (WIDE) {
             key[i] = ((const uint64_t *)vcol)[row];
             grp[i] = gb;
         } else {
-            key[i] = (uint64_t)gb << 32 | (uint32_t)(dist_gather(vcol, vwl, row) - v_base);
+            key[i] = (uint64_t)gb << 32 | (uint32_t)(gather_narrow(vcol, vwl, row) - v_base);
         }
     }
 }

@@ -1,13 +1,11 @@
-// group_kernels.hpp -- device code of grouped COUNT(*) (included once by pqps_hip.hip, after filter_kernels.hpp).
+// group_kernels.hpp -- device code of grouped COUNT(*) (included once by pqps_hip.hip, after fused_common.hpp).
 //
 // No counterpart in the reference (its engines have no aggregates).  A histogram of the matching rows over the values of
 // one column: the bin of a row is (value - bin_base) in 32-bit arithmetic -- the dictionary code of a string column, the
 // value minus the column's minimum for an i32 column, 0 / 1 for sudo_used.
 //
-// Fused scan (pqps_filter_group): the grid-stride form of the COUNT kernels -- eval_step_full on every step, rows_below
-// masking on the partial last one -- and, in a wave whose step has a match (wave-uniform), ONE round of loads of the
-// group column in the predicate columns' per-lane pattern (RPL = 4: lane l owns rows l*4 .. l*4+3 of each 256-row chunk).
-// A sparse WHERE therefore reads almost nothing beyond its predicate bytes.  Three bin paths, picked on the host by D:
+// Fused scan (pqps_filter_group): the shared scan loop (fused_common.hpp) with ONE round of loads of the group column per
+// step that holds a match.  Three bin paths, picked on the host by D:
 //   SMALL  D <= 16      per-lane counters in VGPRs (8-bit fields of two u64 per step, unpacked into 16 u32 counters), wave
 //                       sums on the DPP path (wave_sum_u32), workgroup sum through LDS
 //   LDS    D <= 16384   a u32 histogram in dynamic LDS (ds_add_u32 per matching row); 64 KiB at most, so that two
@@ -21,8 +19,7 @@
 // (a few workgroups per CU), so the partials are grid x D words, not table-sized.
 //
 // List form (pqps_group_list): the same bins over an ID list (index probes, several passes, a shard's list): a gather of
-// the group column per listed row.  Bounds (pqps_column_bounds): min / max of an i32 column.  No kernel here waits on
-// another workgroup.
+// the group column per listed row.  Bounds (pqps_column_bounds): min / max of an i32 column.
 #pragma once
 
 namespace {
@@ -34,7 +31,7 @@ constexpr uint32_t kGroupMaxBins = 65536;
 constexpr uint32_t kGroupSumParts = 64;            // partial rows one workgroup of group_sum_kernel adds up
 
 struct GroupArgs {
-    EvalArgs e;                      // the WHERE, as the COUNT kernels take it -- first: eval_step_full reads it in place
+    EvalArgs e;                      // the WHERE, as the COUNT kernels take it -- first: the scan loop reads it in place
     const void *gcol;                // group column (bytes, u16, u32 or a bit plane)
     uint32_t *bins;                  // GLOBAL: D u32 bins (zeroed before the launch)
     uint32_t *parts;                 // SMALL / LDS: [gridDim.x][stride] partial counts
@@ -43,48 +40,15 @@ struct GroupArgs {
     uint32_t bin_base;
     uint32_t n_bins;
 };
-typedef const __attribute__((address_space(4))) GroupArgs GCArgs;
-__device__ __forceinline__ GCArgs &group_args() { return *(GCArgs *)__builtin_amdgcn_kernarg_segment_ptr(); }
-
-// The group values of a lane's 16 rows of one full step, bit p <-> row step_row0 + (p / 4) * 256 + lane * 4 + p % 4
-// (the layout of eval_step_full's match bits).
-template <bool NT>
-__device__ __forceinline__ void load_group_step(const char *base, uint32_t wl, uint64_t step_row0, uint32_t lane, uint32_t (&v)[16]) {
-    const uint64_t lane_row0 = step_row0 + lane * kRplGeneric;
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-        const uint64_t r0 = lane_row0 + (uint64_t)u * 256;
-        if (wl == 2) {
-            const uint4 q = ld_x4<NT>(base + r0 * 4);
-            v[4 * u] = q.x; v[4 * u + 1] = q.y; v[4 * u + 2] = q.z; v[4 * u + 3] = q.w;
-        } else if (wl == 1) {
-            const uint2 q = ld_x2<NT>(base + r0 * 2);
-            v[4 * u] = q.x & 0xFFFFu; v[4 * u + 1] = q.x >> 16;
-            v[4 * u + 2] = q.y & 0xFFFFu; v[4 * u + 3] = q.y >> 16;
-        } else if (wl == kWidthLog2Bits) {                      // bit plane: the lane's 4 rows are a nibble
-            const uint32_t q = ld_u8<NT>(base + (r0 >> 3)) >> (uint32_t)(r0 & 4u);
-            v[4 * u] = q & 1u; v[4 * u + 1] = (q >> 1) & 1u;
-            v[4 * u + 2] = (q >> 2) & 1u; v[4 * u + 3] = (q >> 3) & 1u;
-        } else {
-            const uint32_t q = ld_x1<NT>(base + r0);
-            v[4 * u] = q & 0xFFu; v[4 * u + 1] = (q >> 8) & 0xFFu;
-            v[4 * u + 2] = (q >> 16) & 0xFFu; v[4 * u + 3] = q >> 24;
-        }
-    }
-}
 
 template <int PATH, bool NT>
 __global__ __launch_bounds__(kBlock, 1) void group_scan_kernel(const GroupArgs) {
-    GCArgs &g = group_args();
+    const auto &g = kernarg<GroupArgs>();
     CArgs &a = g.e;
     extern __shared__ uint32_t hist[];                          // LDS path: n_bins words
     const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const uint32_t nb = g.n_bins, base_bin = g.bin_base, wl = g.gwidth_log2;
     const char *gbase = (const char *)g.gcol;
-    const uint64_t wave = (uint64_t)blockIdx.x * kWaves + wv;
-    const uint64_t n_waves = (uint64_t)gridDim.x * kWaves;
-    const uint64_t n_rows = a.n_rows;
-    const uint64_t steps = (n_rows + kStepRows - 1) / kStepRows;
     if constexpr (PATH == GROUP_LDS) {
         for (uint32_t i = threadIdx.x; i < nb; i += kBlock) hist[i] = 0;
         __syncthreads();
@@ -92,13 +56,9 @@ __global__ __launch_bounds__(kBlock, 1) void group_scan_kernel(const GroupArgs) 
     uint32_t cnt[kGroupSmallBins];
 #pragma unroll
     for (uint32_t k = 0; k < kGroupSmallBins; k++) cnt[k] = 0;
-    for (uint64_t step = wave; step < steps; step += n_waves) {
-        const uint64_t step_row0 = step * kStepRows;
-        uint32_t mbits = eval_step_full<NT>(a, step_row0, lane);
-        if (step_row0 + kStepRows > n_rows) mbits &= rows_below<kRplGeneric>(step_row0, n_rows, lane);   // the partial last step
-        if (__ballot(mbits != 0u) == 0) continue;               // uniform: no match, no group load
+    fused_scan_steps<NT>(a, lane, wv, [&](uint64_t step_row0, uint32_t mbits) {
         uint32_t v[16];
-        load_group_step<NT>(gbase, wl, step_row0, lane, v);
+        load_step_u32<NT>(gbase, wl, step_row0, lane, v);
         if constexpr (PATH == GROUP_SMALL) {
             uint64_t f0 = 0, f1 = 0;                            // 8-bit fields: bins 0 .. 7 and 8 .. 15 (at most 16 rows per lane)
 #pragma unroll
@@ -121,7 +81,7 @@ __global__ __launch_bounds__(kBlock, 1) void group_scan_kernel(const GroupArgs) 
                 }
             }
         }
-    }
+    });
     if constexpr (PATH == GROUP_SMALL) {
         __shared__ uint32_t s_small[kWaves][kGroupSmallBins];
 #pragma unroll
@@ -179,17 +139,12 @@ __global__ __launch_bounds__(kBlock) void group_list_kernel(const void *col, uin
         for (uint32_t i = threadIdx.x; i < n_bins; i += kBlock) hist[i] = 0;
         __syncthreads();
     }
-    uint64_t n = *count;
-    if (n > capacity) n = capacity;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t row = (uint64_t)(ids[i] - id_base);
-        if (row >= n_rows) continue;                            // (never: a shard's list holds its own rows)
-        const uint32_t v = wlog2 == 0 ? ((const uint8_t *)col)[row] : wlog2 == 1 ? ((const uint16_t *)col)[row] : ((const uint32_t *)col)[row];
-        const uint32_t b = v - bin_base;
-        if (b >= n_bins) continue;
+    for_each_listed_row(ids, count, capacity, id_base, n_rows, [&](uint64_t row) {
+        const uint32_t b = gather_narrow(col, wlog2, row) - bin_base;
+        if (b >= n_bins) return;
         if constexpr (LDS) atomicAdd(&hist[b], 1u);
         else atomicAdd(&bins[b], 1u);
-    }
+    });
     if constexpr (LDS) {
         __syncthreads();
         for (uint32_t i = threadIdx.x; i < n_bins; i += kBlock)

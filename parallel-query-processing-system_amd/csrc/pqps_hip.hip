@@ -21,6 +21,7 @@
 
 #include "pqps_hip.h"
 #include "filter_kernels.hpp"
+#include "fused_common.hpp"
 #include "group_kernels.hpp"
 #include "aggregate_kernels.hpp"
 #include "topk_kernels.hpp"

@@ -1,5 +1,4 @@
-// topk_kernels.hpp -- device code of ORDER BY column [DESC] LIMIT K (included once by pqps_hip.hip, after
-// aggregate_kernels.hpp, whose per-step value loads it shares with group_kernels.hpp's).
+// topk_kernels.hpp -- device code of ORDER BY column [DESC] LIMIT K (included once by pqps_hip.hip, after fused_common.hpp).
 //
 // No counterpart in the reference (it parses ORDER BY and executes none).  Every row is one COMPOSITE key whose ascending
 // order is the answer's order -- key ascending or descending, ties by ascending table-wide row number:
@@ -17,11 +16,10 @@
 // compare-exchanges whatever the order of the input -- also when every match beats tau (a key monotone in scan
 // direction, such as ORDER BY command_id DESC over the synthetic table).
 //
-// topk_scan_kernel (pqps_filter_topk): group_scan_kernel's persistent-grid loop -- eval_step_full, rows_below on the
-// partial last step -- and, in a wave whose step holds a match, the key loads; at the end every wave stores its sorted K
-// best as a partial row and every workgroup adds its match count with ONE atomic.  topk_select_kernel: one wave per
-// `chunk` consecutive keys of a partial-row array (the follow-up rounds: grid x 4 x K keys to K), or of an ID list whose
-// keys it gathers (pqps_topk_list); the host runs rounds until one wave is left.
+// topk_scan_kernel (pqps_filter_topk): the shared scan loop (fused_common.hpp) with the key loads per step that holds a
+// match, written out in this kernel (why: DESIGN.md §7a).  At the end every wave stores its sorted K best as a partial row and
+// every workgroup adds its match count with ONE atomic.  topk_select_kernel: one wave per `chunk` consecutive keys of a partial-row
+// array (the follow-up rounds: grid x 4 x K keys to K), or of an ID list whose keys it gathers (pqps_topk_list); rounds until one wave is left.
 #pragma once
 
 namespace {
@@ -112,7 +110,7 @@ template <bool WIDE> struct WaveTopK {
 };
 
 struct TopkArgs {
-    EvalArgs e;                      // the WHERE, as the COUNT kernels take it -- first: eval_step_full reads it in place
+    EvalArgs e;                      // the WHERE, as the COUNT kernels take it -- first: the scan loop reads it in place
     const void *kcol;                // key column (narrow: bytes, u16, u32 or a bit plane; wide: u64); nullptr: every key 0
     void *parts;                     // [gridDim.x * kWaves][k] keys, each wave's sorted K best
     unsigned long long *count;       // += the matching rows (one atomic per workgroup; zeroed before the launch)
@@ -121,12 +119,10 @@ struct TopkArgs {
     uint32_t row_base;               // table-wide row number of row 0
     uint32_t k, cap;
 };
-typedef const __attribute__((address_space(4))) TopkArgs CTArgs;
-__device__ __forceinline__ CTArgs &topk_args() { return *(CTArgs *)__builtin_amdgcn_kernarg_segment_ptr(); }
 
 template <bool WIDE, bool NT>
 __global__ __launch_bounds__(kBlock, 1) void topk_scan_kernel(const TopkArgs) {
-    CTArgs &g = topk_args();
+    const auto &g = kernarg<TopkArgs>();
     CArgs &a = g.e;
     extern __shared__ uint64_t topk_lds[];
     const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -140,18 +136,18 @@ __global__ __launch_bounds__(kBlock, 1) void topk_scan_kernel(const TopkArgs) {
     WaveTopK<WIDE> w;
     w.init((TKey<WIDE> *)topk_lds + (uint64_t)wv * g.cap, g.cap, g.k, lane);
     uint32_t cnt = 0;
-    for (uint64_t step = wave; step < steps; step += n_waves) {
+    for (uint64_t step = wave; step < steps; step += n_waves) {     // fused_scan_steps, written out
         const uint64_t step_row0 = step * kStepRows;
         uint32_t mbits = eval_step_full<NT>(a, step_row0, lane);
-        if (step_row0 + kStepRows > n_rows) mbits &= rows_below<kRplGeneric>(step_row0, n_rows, lane);   // the partial last step
-        if (__ballot(mbits != 0u) == 0) continue;               // uniform: no match, no key load
+        if (step_row0 + kStepRows > n_rows) mbits &= rows_below<kRplGeneric>(step_row0, n_rows, lane);
+        if (__ballot(mbits != 0u) == 0) continue;
         cnt += __popc(mbits);
         uint64_t v[16];
         if constexpr (WIDE) {
-            load_value_step<true, NT>(kbase, step_row0, lane, v);
+            load_step_u64<true, NT>(kbase, step_row0, lane, v);
         } else {
             uint32_t u[16];
-            if (kbase) load_group_step<NT>(kbase, wl, step_row0, lane, u);
+            if (kbase) load_step_u32<NT>(kbase, wl, step_row0, lane, u);
             else {
 #pragma unroll
                 for (int p = 0; p < 16; p++) u[p] = 0;
@@ -199,13 +195,7 @@ __global__ __launch_bounds__(kBlock) void topk_select_kernel(const TKey<WIDE> *_
         if (valid) {
             if constexpr (GATHER) {
                 const uint32_t row = ids[i];
-                const uint64_t r = (uint64_t)(row - id_base);
-                uint64_t raw = 0;
-                if (kcol) {
-                    if constexpr (WIDE) raw = ((const uint64_t *)kcol)[r];
-                    else raw = kwl == 0 ? ((const uint8_t *)kcol)[r] : kwl == 1 ? ((const uint16_t *)kcol)[r] : ((const uint32_t *)kcol)[r];
-                }
-                key = make_key<WIDE>(raw, kxor, row);
+                key = make_key<WIDE>(gather_key<WIDE>(kcol, kwl, (uint64_t)(row - id_base)), kxor, row);
             } else {
                 key = in[i];
             }
@@ -221,12 +211,7 @@ template <bool WIDE>
 __global__ __launch_bounds__(kBlock) void topk_sort_keys_kernel(const uint32_t *__restrict__ rows, uint64_t n, const void *kcol, uint32_t kwl,
                                                                 uint64_t kxor, uint32_t id_base, uint64_t *__restrict__ keys) {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t r = (uint64_t)(rows[i] - id_base);
-        uint64_t raw = 0;
-        if (kcol) {
-            if constexpr (WIDE) raw = ((const uint64_t *)kcol)[r];
-            else raw = kwl == 0 ? ((const uint8_t *)kcol)[r] : kwl == 1 ? ((const uint16_t *)kcol)[r] : ((const uint32_t *)kcol)[r];
-        }
+        const uint64_t raw = gather_key<WIDE>(kcol, kwl, (uint64_t)(rows[i] - id_base));
         keys[i] = WIDE ? raw ^ kxor : (uint64_t)(((uint32_t)raw) ^ (uint32_t)kxor);
     }
 }
