@@ -12,6 +12,7 @@
 #include <cstring>
 #include <new>
 #include <utility>
+#include <vector>
 #include <dlfcn.h>
 #include <time.h>
 
@@ -1008,9 +1009,8 @@ int run_filter(pqps_ctx *ctx, eval_fn k1, EvalArgs &a, uint64_t rows, int mode, 
         else hipLaunchKernelGGL(k1, dim3(grid), dim3(kBlock), 0, s, a);
         HIP_TRY(hipGetLastError());
         if (timed) done = ctx->ev_stop[ctx->timed];              // the end of the query = the end of the reduction
-        if (done) hipExtLaunchKernelGGL(reduce_totals_kernel, dim3(1), dim3(kBlock), 0, s, nullptr, done, 0, ctx->partials, out_count);
-        else hipLaunchKernelGGL(reduce_totals_kernel, dim3(1), dim3(kBlock), 0, s, ctx->partials, out_count);
-        HIP_TRY(hipGetLastError());
+        rc = launch_stop(reduce_totals_kernel, dim3(1), 0, s, done, ctx->partials, out_count);
+        if (rc) return rc;
         if (timed) { ctx->stop_is_eval[ctx->timed] = false; ctx->timed++; }
         if (done_io) *done_io = done;
         return PQPS_OK;
@@ -1127,6 +1127,37 @@ int run_filter(pqps_ctx *ctx, eval_fn k1, EvalArgs &a, uint64_t rows, int mode, 
         ctx->timed++;
     }
     if (done_io) *done_io = stop;
+    return PQPS_OK;
+}
+
+// The front end of a plain scan (ID output or COUNT), once for the filter calls, the query stream and the exchange:
+// what the caller checks is its own handle and where the result goes; the rest is here.  run() launches it.
+struct ScanRequest {
+    EvalArgs a;
+    eval_fn k1;
+    int mode;
+    uint64_t n_rows, out_cap;
+    uint32_t id_base;
+    uint32_t *out_ids;
+
+    int run(pqps_ctx *ctx, hipStream_t s, uint64_t *out_count, hipEvent_t *done_io = nullptr) {
+        return run_filter(ctx, k1, a, n_rows, mode, false, id_base, out_ids, out_cap, out_count, s, done_io);
+    }
+};
+
+// Checks in the order every entry point has had them: the ID buffer, the u32 range of the IDs (ID output only), the
+// predicate.  Then the kernel's args and the instantiation that evaluates them (COUNT: out_ids NULL, capacity 0).
+int scan_request(ScanRequest &r, int mode, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, uint32_t id_base,
+                 const pqps_predicate *pred, uint32_t *out_ids, uint64_t out_capacity) {
+    if (!out_ids && out_capacity) return fail(PQPS_EINVAL, "out_ids is NULL");
+    if (mode == MODE_IDS && (n_rows > 0xFFFFFFFFull || (uint64_t)id_base + n_rows > 0x100000000ull))
+        return fail(PQPS_EINVAL, "row IDs are u32: id_base + n_rows must be <= 2^32");
+    const int rc = check_pred(cols, n_cols, pred);
+    if (rc) return rc;
+    fill_args(r.a, cols, n_cols, pred);
+    r.a.n_rows = n_rows;
+    r.k1 = mode == MODE_IDS ? pick_eval<MODE_IDS>(cols, n_cols, pred, r.a, n_rows) : pick_eval<MODE_COUNT>(cols, n_cols, pred, r.a, n_rows);
+    r.mode = mode; r.n_rows = n_rows; r.id_base = id_base; r.out_ids = out_ids; r.out_cap = out_capacity;
     return PQPS_OK;
 }
 
@@ -1391,29 +1422,17 @@ int pqps_filter_scan(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols,
                      uint64_t n_rows, uint32_t id_base, const pqps_predicate *pred,
                      uint32_t *out_ids, uint64_t out_capacity, uint64_t *out_count, void *stream) {
     if (!ctx || !out_count) return fail(PQPS_EINVAL, "ctx/out_count is NULL");
-    if (!out_ids && out_capacity) return fail(PQPS_EINVAL, "out_ids is NULL");
-    if (n_rows > 0xFFFFFFFFull || (uint64_t)id_base + n_rows > 0x100000000ull)
-        return fail(PQPS_EINVAL, "row IDs are u32: id_base + n_rows must be <= 2^32");
-    int rc = check_pred(cols, n_cols, pred);
-    if (rc) return rc;
-    EvalArgs a;
-    fill_args(a, cols, n_cols, pred);
-    a.n_rows = n_rows;
-    return run_filter(ctx, pick_eval<MODE_IDS>(cols, n_cols, pred, a, n_rows), a, n_rows, MODE_IDS, false,
-                      id_base, out_ids, out_capacity, out_count, pick_stream(ctx, stream));
+    ScanRequest r;
+    const int rc = scan_request(r, MODE_IDS, cols, n_cols, n_rows, id_base, pred, out_ids, out_capacity);
+    return rc ? rc : r.run(ctx, pick_stream(ctx, stream), out_count);
 }
 
 int pqps_filter_count(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols,
                       uint64_t n_rows, const pqps_predicate *pred, uint64_t *out_count, void *stream) {
     if (!ctx || !out_count) return fail(PQPS_EINVAL, "ctx/out_count is NULL");
-    int rc = check_pred(cols, n_cols, pred);
-    if (rc) return rc;
-    hipStream_t s = pick_stream(ctx, stream);
-    EvalArgs a;
-    fill_args(a, cols, n_cols, pred);
-    a.n_rows = n_rows;
-    return run_filter(ctx, pick_eval<MODE_COUNT>(cols, n_cols, pred, a, n_rows), a, n_rows, MODE_COUNT, false,
-                      0, nullptr, 0, out_count, s);
+    ScanRequest r;
+    const int rc = scan_request(r, MODE_COUNT, cols, n_cols, n_rows, 0, pred, nullptr, 0);
+    return rc ? rc : r.run(ctx, pick_stream(ctx, stream), out_count);
 }
 
 int pqps_filter_flags(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols,
@@ -1869,6 +1888,8 @@ int pqps_merge_slots(pqps_ctx *ctx, const uint32_t *slots, uint32_t world, uint6
     return PQPS_OK;
 }
 
+}  // extern "C"
+
 // ---- multi-GPU SELECT: shard scan + all-gatherv of the matching row IDs over RCCL -----------------
 // The exchange step of engine/mpi/executeEngine-mpi.c:703-768 with its own shape kept: MPI_Allgather of the
 // per-rank sizes (:753), displacements = exclusive prefix (:758-762), MPI_Allgatherv of the payload (:765).
@@ -1879,8 +1900,6 @@ int pqps_merge_slots(pqps_ctx *ctx, const uint32_t *slots, uint32_t world, uint6
 // query k's exchange only after query k+1's scan has been enqueued (see pqps_exchange_select).
 // RCCL is resolved at run time from the library the caller names (the process's torch build ships one;
 // /opt/rocm/lib/librccl.so is the system one), so the single-GPU engine does not link against it.
-}  // extern "C"
-
 namespace {
 
 struct RcclApi {
@@ -1926,9 +1945,75 @@ enum : uint8_t { kSlotIdle = 0, kSlotSizesInFlight = 1, kSlotDone = 2, kSlotCoun
 constexpr uint32_t kExchangeLanes = 2;      // scans in flight, each whole on a stream of its own (as in pqps_qstream)
 constexpr int kRcclUint8 = 1;               // ncclUint8: the compact payload travels as bytes
 
-}  // namespace
+// ---- the scan lanes of a query stream / an exchange ---------------------------------------------------------------------
+// Contexts with a scratch and a high-priority HIP stream of their own (create_ctx), on which whole queries run side by
+// side, and the event that puts them behind what the caller's stream holds.  Which lane a query takes is its owner's rule.
+constexpr uint32_t kMaxScanLanes = 8;
 
-extern "C" {
+struct ScanLanes {
+    pqps_ctx *lane[kMaxScanLanes] = {};
+    uint32_t n = 0;
+    hipEvent_t joined = nullptr;     // what the caller's stream held when the queries began
+    bool ordered = false;            // the lanes already wait for the caller's stream
+
+    int create(int device, uint32_t count) {
+        HIP_TRY(hipEventCreateWithFlags(&joined, hipEventDisableTiming));
+        for (; n < count; n++)
+            if (create_ctx(device, true, &lane[n]) != PQPS_OK) return PQPS_EHIP;
+        return PQPS_OK;
+    }
+
+    void destroy() {                 // (of a half-built set too; the owner goes with it)
+        for (uint32_t i = 0; i < n; i++) { (void)hipStreamSynchronize(lane[i]->stream); pqps_ctx_destroy(lane[i]); }
+        if (joined) (void)hipEventDestroy(joined);
+    }
+
+    // what the caller's stream holds (the table, ...) comes first; `ordered` is cleared by the owner's sync
+    int join(hipStream_t caller) {
+        if (ordered) return PQPS_OK;
+        HIP_TRY(hipEventRecord(joined, caller));
+        for (uint32_t i = 0; i < n; i++) HIP_TRY(hipStreamWaitEvent(lane[i]->stream, joined, 0));
+        ordered = true;
+        return PQPS_OK;
+    }
+
+    // Where a query runs: whole on lane `i`, behind the caller's stream.  While the PARENT context records timings it
+    // runs on the parent's own scratch and the caller's stream instead, one query at a time, so that the recorded
+    // events mean what pqps_ctx_kernel_time documents.
+    int route(pqps_ctx *parent, bool timing, hipStream_t caller, uint32_t i, pqps_ctx **ctx, hipStream_t *s) {
+        if (timing) { *ctx = parent; *s = caller; return PQPS_OK; }
+        const int rc = join(caller);
+        if (rc) return rc;
+        *ctx = lane[i]; *s = lane[i]->stream;
+        return PQPS_OK;
+    }
+};
+
+// One ring slot of an exchange: its events, the buffers that grow with the queries, and where its share of the
+// exchange's pooled allocations lies.
+struct ExchangeSlot {
+    hipEvent_t scan_done, sizes_done, merge_done;    // the scan's own launch (either arm of ScanLanes::route) / the sizes on the host / the result in place
+    uint32_t *merged;                // the gathered list, grown to what a query needs
+    uint64_t merged_cap;
+    uint8_t *wire_out;               // this rank's payload in compact form (wire_pack_kernel), grown to the rows of a call
+    uint64_t wire_out_cap;
+    uint8_t *wire_in;                // the peers' compact payloads as received, grown to what a query needs
+    uint64_t wire_in_cap;
+    uint8_t state;
+    bool eager;                      // the slot's query gathered eager blocks
+    uint64_t issued;                 // call number that last used the slot
+    uint64_t totals_host[2];         // merged / reported IDs of a SELECT slot
+    // the slot's part of the pooled allocations
+    uint32_t *local;                 // [stride]   [u64 count][u64 reserved][IDs] of this rank
+    uint64_t *hdr_dev;               // [4]        this rank's words of the sizes all-gather: reported count, rows, id_base, format
+    uint64_t *sizes_dev;             // [world][4] gathered headers
+    uint64_t *sizes_host;            // [world][4] ... on the host (pinned)
+    uint64_t *sizes_host_dev;        //            ... as the device addresses it (the eager unpack kernel writes the headers there itself)
+    uint64_t *totals;                // [2]        device: COUNT(*) result
+    uint8_t *eager_out, *eager_in;   // [block] this rank's block, [world][block] the gathered ones (from connect on, where eager_ids != 0)
+};
+
+}  // namespace
 
 struct pqps_exchange {
     pqps_ctx *ctx;
@@ -1938,26 +2023,13 @@ struct pqps_exchange {
     uint64_t cap, stride;            // IDs this rank's slot holds; u32 words per slot (header + IDs)
     uint64_t *caps;                  // [world] every rank's `cap` (they may differ: shards differ by a row)
     hipStream_t stream;              // the exchange stream
-    uint32_t *local;                 // [ring][stride]   [u64 count][u64 reserved][IDs] of this rank
-    uint64_t *hdr_dev;               // [ring][4]        this rank's words of the sizes all-gather: reported count, rows, id_base, format
-    uint64_t *sizes_dev;             // [ring][world][4] gathered headers
-    uint64_t *sizes_host;            // [ring][world][4] ... on the host (pinned)
-    uint64_t *sizes_host_dev;        //                  ... as the device addresses it (the eager unpack kernel writes the headers there itself)
-    uint8_t **wire_out;              // [ring]           this rank's payload in compact form (wire_pack_kernel), grown to the rows of a call
-    uint64_t *wire_out_cap;
-    uint8_t **wire_in;               // [ring]           the peers' compact payloads as received, grown to what a query needs
-    uint64_t *wire_in_cap;
-    uint32_t **merged;               // [ring]           the gathered list, grown to what a query needs
-    uint64_t *merged_cap;
-    uint64_t *totals;                // [ring][2]        device: COUNT(*) result
-    uint64_t *totals_host;           // [ring][2]        merged / reported IDs of a SELECT slot
-    hipEvent_t *scan_done, *k1_done, *sizes_done, *merge_done;
-    hipEvent_t joined;               // what the caller's stream held when the queries began
+    std::vector<ExchangeSlot> slots; // [ring]
+    // pooled over the ring (ExchangeSlot points into them)
+    uint32_t *local;
+    uint64_t *hdr_dev, *sizes_dev, *sizes_host, *totals;
+    uint8_t *eager_out, *eager_in;
     hipEvent_t fence;                // pqps_exchange_sync: the end of a stream, awaited with a bound
-    bool ordered;                    // the lanes already wait for the caller's stream
-    pqps_ctx **child;                // [kExchangeLanes] scratch + HIP stream of the scans in flight (see pqps_qstream)
-    uint8_t *state;
-    uint64_t *issued;                // [ring] call number that last used the slot
+    ScanLanes lanes;                 // [kExchangeLanes] the scans in flight (see pqps_qstream)
     uint64_t calls;
     uint64_t wait_ns;                // host time spent waiting for a slot to come free
     uint64_t sizes_wait_ns;          // host time spent waiting for the sizes of a query
@@ -1965,122 +2037,12 @@ struct pqps_exchange {
     uint64_t wire_bytes_in, u32_bytes_in;    // payload this rank has received: as it travelled / as u32 IDs would have
     uint64_t eager_want, eager_ids;  // IDs a rank's block of the sizes all-gather has room for (PQPS_EXCHANGE_EAGER_IDS; 0: none), as agreed at connect
     uint64_t eager_block;            // bytes of such a block: header + eager_ids IDs
-    uint8_t *eager_out, *eager_in;   // [ring][block] this rank's block, [ring][world][block] the gathered ones
     uint64_t *caps_dev;              // [world] `caps` for the unpack kernel
     bool eager_next;                 // the next SELECT gathers eager blocks: the last answer whose sizes were read fitted (every rank sees the same)
-    bool *eager_slot;                // [ring] the slot's query did
     uint64_t eager_queries, select_queries;   // SELECTs finished in the sizes all-gather alone / SELECTs finished
     double timeout_s;                // bound of every host wait of the exchange (PQPS_EXCHANGE_TIMEOUT_S, default 30; 0: none)
     bool dead;                       // a wait ran out (or a rank could not receive): the communicator is aborted, every call fails
 };
-
-int pqps_exchange_unique_id(const char *rccl_library, pqps_rccl_id *id) {
-    if (!id) return fail(PQPS_EINVAL, "id is NULL");
-    RcclApi api{};
-    int rc = load_rccl(rccl_library, &api);
-    if (rc) return rc;
-    int nrc = api.GetUniqueId(id);
-    if (nrc) return fail(PQPS_EHIP, "ncclGetUniqueId: %s", api.GetErrorString(nrc));
-    return PQPS_OK;
-}
-
-int pqps_exchange_destroy(pqps_exchange *x) {
-    if (!x) return PQPS_OK;
-    (void)hipSetDevice(x->ctx->device);
-    // a dead exchange may still have a collective of the aborted communicator in its stream: no unbounded wait for it
-    if (x->stream && !x->dead) (void)hipStreamSynchronize(x->stream);
-    if (x->comm) { if (x->dead && x->rccl.CommAbort) (void)x->rccl.CommAbort(x->comm); else (void)x->rccl.CommDestroy(x->comm); x->comm = nullptr; }
-    if (x->stream && x->dead) (void)hipStreamSynchronize(x->stream);     // (the abort has ended what was stuck)
-    for (uint32_t i = 0; i < x->ring; i++) {
-        if (x->scan_done && x->scan_done[i]) (void)hipEventDestroy(x->scan_done[i]);
-        if (x->k1_done && x->k1_done[i]) (void)hipEventDestroy(x->k1_done[i]);
-        if (x->sizes_done && x->sizes_done[i]) (void)hipEventDestroy(x->sizes_done[i]);
-        if (x->merge_done && x->merge_done[i]) (void)hipEventDestroy(x->merge_done[i]);
-        if (x->merged && x->merged[i]) (void)hipFree(x->merged[i]);
-        if (x->wire_out && x->wire_out[i]) (void)hipFree(x->wire_out[i]);
-        if (x->wire_in && x->wire_in[i]) (void)hipFree(x->wire_in[i]);
-    }
-    for (uint32_t i = 0; i < kExchangeLanes; i++)
-        if (x->child && x->child[i]) { (void)hipStreamSynchronize(x->child[i]->stream); pqps_ctx_destroy(x->child[i]); }
-    if (x->joined) (void)hipEventDestroy(x->joined);
-    if (x->fence) (void)hipEventDestroy(x->fence);
-    delete[] x->scan_done; delete[] x->k1_done; delete[] x->sizes_done; delete[] x->merge_done; delete[] x->child;
-    delete[] x->state; delete[] x->issued; delete[] x->merged; delete[] x->merged_cap; delete[] x->totals_host; delete[] x->caps;
-    delete[] x->wire_out; delete[] x->wire_out_cap; delete[] x->wire_in; delete[] x->wire_in_cap;
-    if (x->local) (void)hipFree(x->local);
-    if (x->eager_out) (void)hipFree(x->eager_out);
-    if (x->eager_in) (void)hipFree(x->eager_in);
-    if (x->caps_dev) (void)hipFree(x->caps_dev);
-    delete[] x->eager_slot;
-    if (x->hdr_dev) (void)hipFree(x->hdr_dev);
-    if (x->sizes_dev) (void)hipFree(x->sizes_dev);
-    if (x->sizes_host) (void)hipHostFree(x->sizes_host);
-    if (x->totals) (void)hipFree(x->totals);
-    if (x->stream) (void)hipStreamDestroy(x->stream);
-    delete x;
-    return PQPS_OK;
-}
-
-int pqps_exchange_prepare(pqps_ctx *ctx, const char *rccl_library, uint32_t world, uint32_t rank,
-                          uint64_t slot_capacity, uint32_t ring, pqps_exchange **out) {
-    if (!ctx || !out) return fail(PQPS_EINVAL, "NULL argument");
-    if (world == 0 || world > 1024 || rank >= world) return fail(PQPS_EINVAL, "rank %u / world %u out of range", rank, world);
-    if (ring == 0 || ring > 64) return fail(PQPS_EINVAL, "ring %u out of range (1..64)", ring);
-    if (slot_capacity == 0 || slot_capacity > 0xFFFFFFFFull) return fail(PQPS_EINVAL, "slot capacity out of range");
-    pqps_exchange *x = new (std::nothrow) pqps_exchange();
-    if (!x) return fail(PQPS_ENOMEM, "out of host memory");
-    x->ctx = ctx; x->world = world; x->rank = rank; x->ring = ring;
-    x->cap = (slot_capacity + 1) & ~1ull;                      // keeps every slot 8-byte aligned
-    x->stride = x->cap + kSlotHeaderWords;
-    { const char *e = getenv("PQPS_EXCHANGE_COMPACT"); x->compact = !e || atoi(e) != 0; }
-    { const char *e = getenv("PQPS_EXCHANGE_TIMEOUT_S"); x->timeout_s = e ? atof(e) : 30.0; if (x->timeout_s < 0) x->timeout_s = 0; }
-    { const char *e = getenv("PQPS_EXCHANGE_EAGER_IDS"); x->eager_want = e ? strtoull(e, nullptr, 10) : kEagerIdsDefault; }
-    x->eager_slot = new bool[ring]();
-    int rc = load_rccl(rccl_library, &x->rccl);
-    if (rc) { pqps_exchange_destroy(x); return rc; }
-#define X_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { pqps_exchange_destroy(x); \
-        return fail(PQPS_EHIP, "%s: %s", #expr, hipGetErrorString(e_)); } } while (0)
-    X_TRY(hipSetDevice(ctx->device));
-    X_TRY(hipStreamCreateWithFlags(&x->stream, hipStreamNonBlocking));
-    X_TRY(hipMalloc((void **)&x->local, (size_t)ring * x->stride * 4));
-    X_TRY(hipMalloc((void **)&x->hdr_dev, (size_t)ring * kWireHeaderWords * sizeof(uint64_t)));
-    X_TRY(hipMalloc((void **)&x->sizes_dev, (size_t)ring * world * kWireHeaderWords * sizeof(uint64_t)));
-    X_TRY(hipHostMalloc((void **)&x->sizes_host, (size_t)ring * world * kWireHeaderWords * sizeof(uint64_t), hipHostMallocDefault));
-    X_TRY(hipMalloc((void **)&x->totals, (size_t)ring * 2 * sizeof(uint64_t)));
-    // (on the exchange's own stream and awaited below: a fill on the null stream is not ordered against this non-blocking stream,
-    //  and the first thing connect puts on it is this rank's capacity INTO `local` -- found by the process-loopback rehearsal,
-    //  where one rank of three announced a capacity of 0)
-    X_TRY(hipMemsetAsync(x->local, 0, (size_t)ring * x->stride * 4, x->stream));
-    X_TRY(hipMemsetAsync(x->hdr_dev, 0, (size_t)ring * kWireHeaderWords * sizeof(uint64_t), x->stream));
-    X_TRY(hipMemsetAsync(x->totals, 0, (size_t)ring * 2 * sizeof(uint64_t), x->stream));
-    X_TRY(hipStreamSynchronize(x->stream));
-    memset(x->sizes_host, 0, (size_t)ring * world * kWireHeaderWords * sizeof(uint64_t));
-    X_TRY(hipHostGetDevicePointer((void **)&x->sizes_host_dev, x->sizes_host, 0));
-    x->scan_done = new hipEvent_t[ring](); x->k1_done = new hipEvent_t[ring](); x->sizes_done = new hipEvent_t[ring]();
-    x->merge_done = new hipEvent_t[ring]();
-    x->child = new pqps_ctx *[kExchangeLanes](); x->state = new uint8_t[ring](); x->issued = new uint64_t[ring]();
-    X_TRY(hipEventCreateWithFlags(&x->joined, hipEventDisableTiming));
-    X_TRY(hipEventCreateWithFlags(&x->fence, hipEventDisableTiming));
-    for (uint32_t i = 0; i < kExchangeLanes; i++)
-        if (create_ctx(ctx->device, true, &x->child[i]) != PQPS_OK) { pqps_exchange_destroy(x); return PQPS_EHIP; }
-    x->merged = new uint32_t *[ring](); x->merged_cap = new uint64_t[ring](); x->totals_host = new uint64_t[2 * (size_t)ring]();
-    x->wire_out = new uint8_t *[ring](); x->wire_out_cap = new uint64_t[ring](); x->wire_in = new uint8_t *[ring](); x->wire_in_cap = new uint64_t[ring]();
-    x->caps = new uint64_t[world]();
-    for (uint32_t i = 0; i < ring; i++) {
-        X_TRY(hipEventCreateWithFlags(&x->scan_done[i], hipEventDisableTiming));
-        X_TRY(hipEventCreateWithFlags(&x->k1_done[i], hipEventDisableTiming));
-        X_TRY(hipEventCreateWithFlags(&x->sizes_done[i], hipEventDisableTiming));
-        X_TRY(hipEventCreateWithFlags(&x->merge_done[i], hipEventDisableTiming));
-        // a first allocation for the gathered list; a query that needs more grows it (never too small)
-        x->merged_cap[i] = x->cap < ((uint64_t)1 << 20) ? x->cap : ((uint64_t)1 << 20);
-        X_TRY(hipMalloc((void **)&x->merged[i], x->merged_cap[i] * 4));
-    }
-#undef X_TRY
-    *out = x;
-    return PQPS_OK;
-}
-
-}  // extern "C"
 
 namespace {
 
@@ -2130,13 +2092,13 @@ int wire_room(pqps_exchange *x, uint8_t **buf, uint64_t *cap, uint64_t bytes) {
 
 // Second half of a SELECT slot: the sizes are on the host, the payload moves.  Every rank comes through here
 // for the same slots in the same order (the order of its pqps_exchange_* calls).
-int exchange_payload(pqps_exchange *x, uint32_t slot) {
-    if (x->state[slot] != kSlotSizesInFlight) return PQPS_OK;
+int exchange_payload(pqps_exchange *x, ExchangeSlot &sl) {
+    if (sl.state != kSlotSizesInFlight) return PQPS_OK;
     const uint64_t t0 = now_ns();
-    int rc = exchange_wait(x, x->sizes_done[slot], "the sizes all-gather");
+    int rc = exchange_wait(x, sl.sizes_done, "the sizes all-gather");
     x->sizes_wait_ns += now_ns() - t0;
     if (rc) return rc;
-    const uint64_t *hdr = x->sizes_host + (uint64_t)slot * x->world * kWireHeaderWords;      // [rank][count, rows, id_base, format]
+    const uint64_t *hdr = sl.sizes_host;      // [rank][count, rows, id_base, format]
     auto held = [&](uint32_t r) { const uint64_t c = hdr[r * kWireHeaderWords]; return c < x->caps[r] ? c : x->caps[r]; };   // a rank whose own slot overflowed sends what it holds
     uint64_t total = 0, reported = 0, staged = 0;
     for (uint32_t r = 0; r < x->world; r++) {                   // mpi:758-762
@@ -2149,31 +2111,31 @@ int exchange_payload(pqps_exchange *x, uint32_t slot) {
         bool fits = true;
         for (uint32_t r = 0; r < x->world; r++) if (hdr[r * kWireHeaderWords] > x->eager_ids) fits = false;
         x->eager_next = fits;
-        if (fits && x->eager_slot[slot]) {                       // the gathered blocks held the whole answer, and it is in place (eager_unpack_kernel)
+        if (fits && sl.eager) {                       // the gathered blocks held the whole answer, and it is in place (eager_unpack_kernel)
             for (uint32_t r = 0; r < x->world; r++)
                 if (r != x->rank) { x->wire_bytes_in += held(r) * 4; x->u32_bytes_in += held(r) * 4; }
             x->eager_queries++;
-            x->totals_host[2 * slot] = total;
-            x->totals_host[2 * slot + 1] = reported;
-            x->state[slot] = kSlotDone;                          // (merge_done was recorded with the sizes: nothing of this query is left to enqueue)
+            sl.totals_host[0] = total;
+            sl.totals_host[1] = reported;
+            sl.state = kSlotDone;                          // (merge_done was recorded with the sizes: nothing of this query is left to enqueue)
             return PQPS_OK;
         }
     }
     int grow = PQPS_OK;
-    if (total > x->merged_cap[slot]) {
+    if (total > sl.merged_cap) {
         // the consumer of this slot's previous result is done with it (the slot was handed out again)
         rc = exchange_wait_stream(x, x->stream, "growing the gathered list");
         if (rc) return rc;
-        (void)hipFree(x->merged[slot]);
-        x->merged[slot] = nullptr;
-        x->merged_cap[slot] = 0;
+        (void)hipFree(sl.merged);
+        sl.merged = nullptr;
+        sl.merged_cap = 0;
         uint64_t want = total + total / 4 + 4096;
-        hipError_t e = hipMalloc((void **)&x->merged[slot], want * 4);
-        if (e != hipSuccess) { (void)hipGetLastError(); want = total; e = hipMalloc((void **)&x->merged[slot], want * 4); }   // exactly what the payload needs
-        if (e != hipSuccess) { x->merged[slot] = nullptr; (void)hipGetLastError(); grow = fail(PQPS_ENOMEM, "gathered ID list of %llu entries: %s", (unsigned long long)want, hipGetErrorString(e)); }
-        else x->merged_cap[slot] = want;
+        hipError_t e = hipMalloc((void **)&sl.merged, want * 4);
+        if (e != hipSuccess) { (void)hipGetLastError(); want = total; e = hipMalloc((void **)&sl.merged, want * 4); }   // exactly what the payload needs
+        if (e != hipSuccess) { sl.merged = nullptr; (void)hipGetLastError(); grow = fail(PQPS_ENOMEM, "gathered ID list of %llu entries: %s", (unsigned long long)want, hipGetErrorString(e)); }
+        else sl.merged_cap = want;
     }
-    if (grow == PQPS_OK && staged) grow = wire_room(x, &x->wire_in[slot], &x->wire_in_cap[slot], staged);
+    if (grow == PQPS_OK && staged) grow = wire_room(x, &sl.wire_in, &sl.wire_in_cap, staged);
     if (grow != PQPS_OK) {
         // This rank cannot receive.  Its peers are about to enter (or already sit in) the same send / recv group and
         // would wait for this rank's half of it forever: abort the communicator, which ends their calls with an
@@ -2182,11 +2144,11 @@ int exchange_payload(pqps_exchange *x, uint32_t slot) {
         snprintf(why, sizeof why, "%s", g_err);
         x->dead = true;
         if (x->world > 1 && x->rccl.CommAbort && x->comm) { (void)x->rccl.CommAbort(x->comm); x->comm = nullptr; }
-        x->state[slot] = kSlotIdle;
+        sl.state = kSlotIdle;
         return fail(PQPS_ENOMEM, "%s (communicator aborted)", why);
     }
-    const uint32_t *mine = x->local + (uint64_t)slot * x->stride + kSlotHeaderWords;
-    uint32_t *merged = x->merged[slot];
+    const uint32_t *mine = sl.local + kSlotHeaderWords;
+    uint32_t *merged = sl.merged;
     int nrc = 0;
     // this rank's own part first: a failure here must not leave an opened group behind
     uint64_t displ = 0;
@@ -2201,12 +2163,12 @@ int exchange_payload(pqps_exchange *x, uint32_t slot) {
     for (uint32_t r = 0; r < x->world && !nrc; r++) {           // mpi:765, as point-to-point pairs
         const uint64_t k = held(r);
         if (r != x->rank) {
-            if (own) nrc = own_compact ? x->rccl.Send(x->wire_out[slot], (size_t)own_wire, kRcclUint8, (int)r, x->comm, x->stream)
+            if (own) nrc = own_compact ? x->rccl.Send(sl.wire_out, (size_t)own_wire, kRcclUint8, (int)r, x->comm, x->stream)
                                        : x->rccl.Send(mine, (size_t)own, kRcclUint32, (int)r, x->comm, x->stream);
             if (!nrc && k) {
                 if (hdr[r * kWireHeaderWords + 3]) {
                     const uint64_t wb = wire_bytes(hdr[r * kWireHeaderWords + 1], k);
-                    nrc = x->rccl.Recv(x->wire_in[slot] + at, (size_t)wb, kRcclUint8, (int)r, x->comm, x->stream);
+                    nrc = x->rccl.Recv(sl.wire_in + at, (size_t)wb, kRcclUint8, (int)r, x->comm, x->stream);
                     at += (wb + 15) & ~15ull;
                     x->wire_bytes_in += wb;
                 } else {
@@ -2240,7 +2202,7 @@ int exchange_payload(pqps_exchange *x, uint32_t slot) {
         if (r != x->rank && k && hdr[r * kWireHeaderWords + 3]) {
             const uint64_t rows = hdr[r * kWireHeaderWords + 1], groups = wire_groups(rows);
             auto &d = many.p[many.n++];
-            d.wire = x->wire_in[slot] + at; d.rows = rows; d.out = merged + displ; d.id_base = (uint32_t)hdr[r * kWireHeaderWords + 2]; d.pad = 0;
+            d.wire = sl.wire_in + at; d.rows = rows; d.out = merged + displ; d.id_base = (uint32_t)hdr[r * kWireHeaderWords + 2]; d.pad = 0;
             if (groups > most_groups) most_groups = groups;
             at += (wire_bytes(rows, k) + 15) & ~15ull;
             if (many.n == kWireManyPeers) { const int frc = flush(); if (frc) return frc; }
@@ -2248,10 +2210,10 @@ int exchange_payload(pqps_exchange *x, uint32_t slot) {
         displ += k;
     }
     { const int frc = flush(); if (frc) return frc; }
-    x->totals_host[2 * slot] = total;
-    x->totals_host[2 * slot + 1] = reported;
-    HIP_TRY(hipEventRecord(x->merge_done[slot], x->stream));
-    x->state[slot] = kSlotDone;
+    sl.totals_host[0] = total;
+    sl.totals_host[1] = reported;
+    HIP_TRY(hipEventRecord(sl.merge_done, x->stream));
+    sl.state = kSlotDone;
     return PQPS_OK;
 }
 
@@ -2259,31 +2221,141 @@ int exchange_payload(pqps_exchange *x, uint32_t slot) {
 // oldest first.
 int exchange_finish_older(pqps_exchange *x, uint64_t before) {
     for (;;) {
-        int pick = -1;
-        for (uint32_t i = 0; i < x->ring; i++)
-            if (x->state[i] == kSlotSizesInFlight && x->issued[i] < before && (pick < 0 || x->issued[i] < x->issued[pick])) pick = (int)i;
-        if (pick < 0) return PQPS_OK;
-        int rc = exchange_payload(x, (uint32_t)pick);
+        ExchangeSlot *pick = nullptr;
+        for (ExchangeSlot &sl : x->slots)
+            if (sl.state == kSlotSizesInFlight && sl.issued < before && (!pick || sl.issued < pick->issued)) pick = &sl;
+        if (!pick) return PQPS_OK;
+        int rc = exchange_payload(x, *pick);
         if (rc) return rc;
     }
 }
 
 // The slot is free again once whatever last used it has finished (a host wait, normally long satisfied).
-int exchange_claim(pqps_exchange *x, uint32_t slot) {
-    if (x->state[slot] == kSlotSizesInFlight) { int rc = exchange_payload(x, slot); if (rc) return rc; }
-    if (x->state[slot] != kSlotIdle) {
+int exchange_claim(pqps_exchange *x, ExchangeSlot &sl) {
+    if (sl.state == kSlotSizesInFlight) { int rc = exchange_payload(x, sl); if (rc) return rc; }
+    if (sl.state != kSlotIdle) {
         const uint64_t t0 = now_ns();
-        const int rc = exchange_wait(x, x->merge_done[slot], "the payload of an earlier query");
+        const int rc = exchange_wait(x, sl.merge_done, "the payload of an earlier query");
         x->wait_ns += now_ns() - t0;
         if (rc) return rc;
     }
-    x->state[slot] = kSlotIdle;
+    sl.state = kSlotIdle;
+    return PQPS_OK;
+}
+
+// The slot's scan, whole on one of two lanes (a stream and a scratch of its own: the tail of one query's launch is
+// filled by the scan tiles of the next, see pqps_qstream), its count into the head of the slot's `local`; everything
+// after it on the exchange stream, behind the launch's own completion event.
+int exchange_scan(pqps_exchange *x, ExchangeSlot &sl, ScanRequest &r, void *scan_stream) {
+    pqps_ctx *c = nullptr; hipStream_t s = nullptr;
+    int rc = x->lanes.route(x->ctx, x->ctx->timing, pick_stream(x->ctx, scan_stream), (uint32_t)(x->calls % kExchangeLanes), &c, &s);
+    if (rc) return rc;
+    hipEvent_t ev = sl.scan_done;
+    rc = r.run(c, s, (uint64_t *)sl.local, &ev);
+    if (rc) return rc;
+    HIP_TRY(hipStreamWaitEvent(x->stream, ev, 0));
     return PQPS_OK;
 }
 
 }  // namespace
 
 extern "C" {
+
+int pqps_exchange_unique_id(const char *rccl_library, pqps_rccl_id *id) {
+    if (!id) return fail(PQPS_EINVAL, "id is NULL");
+    RcclApi api{};
+    int rc = load_rccl(rccl_library, &api);
+    if (rc) return rc;
+    int nrc = api.GetUniqueId(id);
+    if (nrc) return fail(PQPS_EHIP, "ncclGetUniqueId: %s", api.GetErrorString(nrc));
+    return PQPS_OK;
+}
+
+int pqps_exchange_destroy(pqps_exchange *x) {
+    if (!x) return PQPS_OK;
+    (void)hipSetDevice(x->ctx->device);
+    // a dead exchange may still have a collective of the aborted communicator in its stream: no unbounded wait for it
+    if (x->stream && !x->dead) (void)hipStreamSynchronize(x->stream);
+    if (x->comm) { if (x->dead && x->rccl.CommAbort) (void)x->rccl.CommAbort(x->comm); else (void)x->rccl.CommDestroy(x->comm); x->comm = nullptr; }
+    if (x->stream && x->dead) (void)hipStreamSynchronize(x->stream);     // (the abort has ended what was stuck)
+    for (ExchangeSlot &sl : x->slots) {                        // (a half-built exchange: what is not there yet is NULL)
+        if (sl.scan_done) (void)hipEventDestroy(sl.scan_done);
+        if (sl.sizes_done) (void)hipEventDestroy(sl.sizes_done);
+        if (sl.merge_done) (void)hipEventDestroy(sl.merge_done);
+        if (sl.merged) (void)hipFree(sl.merged);
+        if (sl.wire_out) (void)hipFree(sl.wire_out);
+        if (sl.wire_in) (void)hipFree(sl.wire_in);
+    }
+    x->lanes.destroy();
+    if (x->fence) (void)hipEventDestroy(x->fence);
+    void *pooled[] = {x->local, x->hdr_dev, x->sizes_dev, x->totals, x->eager_out, x->eager_in, x->caps_dev};
+    for (void *d : pooled) if (d) (void)hipFree(d);
+    if (x->sizes_host) (void)hipHostFree(x->sizes_host);
+    if (x->stream) (void)hipStreamDestroy(x->stream);
+    delete[] x->caps;
+    delete x;
+    return PQPS_OK;
+}
+
+int pqps_exchange_prepare(pqps_ctx *ctx, const char *rccl_library, uint32_t world, uint32_t rank,
+                          uint64_t slot_capacity, uint32_t ring, pqps_exchange **out) {
+    if (!ctx || !out) return fail(PQPS_EINVAL, "NULL argument");
+    if (world == 0 || world > 1024 || rank >= world) return fail(PQPS_EINVAL, "rank %u / world %u out of range", rank, world);
+    if (ring == 0 || ring > 64) return fail(PQPS_EINVAL, "ring %u out of range (1..64)", ring);
+    if (slot_capacity == 0 || slot_capacity > 0xFFFFFFFFull) return fail(PQPS_EINVAL, "slot capacity out of range");
+    pqps_exchange *x = new (std::nothrow) pqps_exchange();
+    if (!x) return fail(PQPS_ENOMEM, "out of host memory");
+    x->ctx = ctx; x->world = world; x->rank = rank; x->ring = ring;
+    x->cap = (slot_capacity + 1) & ~1ull;                      // keeps every slot 8-byte aligned
+    x->stride = x->cap + kSlotHeaderWords;
+    { const char *e = getenv("PQPS_EXCHANGE_COMPACT"); x->compact = !e || atoi(e) != 0; }
+    { const char *e = getenv("PQPS_EXCHANGE_TIMEOUT_S"); x->timeout_s = e ? atof(e) : 30.0; if (x->timeout_s < 0) x->timeout_s = 0; }
+    { const char *e = getenv("PQPS_EXCHANGE_EAGER_IDS"); x->eager_want = e ? strtoull(e, nullptr, 10) : kEagerIdsDefault; }
+    x->slots.resize(ring);
+    x->caps = new uint64_t[world]();
+    int rc = load_rccl(rccl_library, &x->rccl);
+    if (rc) { pqps_exchange_destroy(x); return rc; }
+#define X_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { pqps_exchange_destroy(x); \
+        return fail(PQPS_EHIP, "%s: %s", #expr, hipGetErrorString(e_)); } } while (0)
+    X_TRY(hipSetDevice(ctx->device));
+    X_TRY(hipStreamCreateWithFlags(&x->stream, hipStreamNonBlocking));
+    X_TRY(hipMalloc((void **)&x->local, (size_t)ring * x->stride * 4));
+    X_TRY(hipMalloc((void **)&x->hdr_dev, (size_t)ring * kWireHeaderWords * sizeof(uint64_t)));
+    X_TRY(hipMalloc((void **)&x->sizes_dev, (size_t)ring * world * kWireHeaderWords * sizeof(uint64_t)));
+    X_TRY(hipHostMalloc((void **)&x->sizes_host, (size_t)ring * world * kWireHeaderWords * sizeof(uint64_t), hipHostMallocDefault));
+    X_TRY(hipMalloc((void **)&x->totals, (size_t)ring * 2 * sizeof(uint64_t)));
+    // (on the exchange's own stream and awaited below: a fill on the null stream is not ordered against this non-blocking stream,
+    //  and the first thing connect puts on it is this rank's capacity INTO `local` -- found by the process-loopback rehearsal,
+    //  where one rank of three announced a capacity of 0)
+    X_TRY(hipMemsetAsync(x->local, 0, (size_t)ring * x->stride * 4, x->stream));
+    X_TRY(hipMemsetAsync(x->hdr_dev, 0, (size_t)ring * kWireHeaderWords * sizeof(uint64_t), x->stream));
+    X_TRY(hipMemsetAsync(x->totals, 0, (size_t)ring * 2 * sizeof(uint64_t), x->stream));
+    X_TRY(hipStreamSynchronize(x->stream));
+    memset(x->sizes_host, 0, (size_t)ring * world * kWireHeaderWords * sizeof(uint64_t));
+    uint64_t *sizes_host_dev = nullptr;
+    X_TRY(hipHostGetDevicePointer((void **)&sizes_host_dev, x->sizes_host, 0));
+    X_TRY(hipEventCreateWithFlags(&x->fence, hipEventDisableTiming));
+    rc = x->lanes.create(ctx->device, kExchangeLanes);
+    if (rc) { pqps_exchange_destroy(x); return rc; }
+    for (uint32_t i = 0; i < ring; i++) {
+        ExchangeSlot &sl = x->slots[i];
+        sl.local = x->local + (uint64_t)i * x->stride;
+        sl.hdr_dev = x->hdr_dev + (uint64_t)i * kWireHeaderWords;
+        sl.sizes_dev = x->sizes_dev + (uint64_t)i * world * kWireHeaderWords;
+        sl.sizes_host = x->sizes_host + (uint64_t)i * world * kWireHeaderWords;
+        sl.sizes_host_dev = sizes_host_dev + (uint64_t)i * world * kWireHeaderWords;
+        sl.totals = x->totals + 2 * (uint64_t)i;
+        X_TRY(hipEventCreateWithFlags(&sl.scan_done, hipEventDisableTiming));
+        X_TRY(hipEventCreateWithFlags(&sl.sizes_done, hipEventDisableTiming));
+        X_TRY(hipEventCreateWithFlags(&sl.merge_done, hipEventDisableTiming));
+        // a first allocation for the gathered list; a query that needs more grows it (never too small)
+        sl.merged_cap = x->cap < ((uint64_t)1 << 20) ? x->cap : ((uint64_t)1 << 20);
+        X_TRY(hipMalloc((void **)&sl.merged, sl.merged_cap * 4));
+    }
+#undef X_TRY
+    *out = x;
+    return PQPS_OK;
+}
 
 int pqps_exchange_connect(pqps_exchange *x, const pqps_rccl_id *id) {
     if (!x || !id) return fail(PQPS_EINVAL, "NULL argument");
@@ -2328,13 +2400,16 @@ int pqps_exchange_connect(pqps_exchange *x, const pqps_rccl_id *id) {
             HIP_TRY(hipMemsetAsync(x->eager_out, 0, (size_t)x->ring * x->eager_block, x->stream));
             rc = exchange_wait_stream(x, x->stream, "setting up the eager blocks");
             if (rc) return rc;
-            for (uint32_t i = 0; i < x->ring; i++) {              // the gathered list of a slot holds every rank's eager IDs without growing
-                if (x->merged_cap[i] >= x->world * x->eager_ids) continue;
-                (void)hipFree(x->merged[i]);
-                x->merged[i] = nullptr;
-                x->merged_cap[i] = 0;
-                HIP_TRY(hipMalloc((void **)&x->merged[i], (size_t)x->world * x->eager_ids * 4));
-                x->merged_cap[i] = x->world * x->eager_ids;
+            for (uint32_t i = 0; i < x->ring; i++) {
+                ExchangeSlot &sl = x->slots[i];
+                sl.eager_out = x->eager_out + (uint64_t)i * x->eager_block;
+                sl.eager_in = x->eager_in + (uint64_t)i * x->world * x->eager_block;
+                if (sl.merged_cap >= x->world * x->eager_ids) continue;     // the gathered list of a slot holds every rank's eager IDs without growing
+                (void)hipFree(sl.merged);
+                sl.merged = nullptr;
+                sl.merged_cap = 0;
+                HIP_TRY(hipMalloc((void **)&sl.merged, (size_t)x->world * x->eager_ids * 4));
+                sl.merged_cap = x->world * x->eager_ids;
             }
             x->eager_next = true;
         }
@@ -2360,11 +2435,11 @@ int pqps_exchange_select(pqps_exchange *x, const pqps_column *cols, uint32_t n_c
     X_ALIVE(x);
     if (!x->comm) return fail(PQPS_EINVAL, "exchange is not connected");
     if (slot >= x->ring) return fail(PQPS_EINVAL, "slot %u >= ring %u", slot, x->ring);
-    if (n_rows > 0xFFFFFFFFull || (uint64_t)id_base + n_rows > 0x100000000ull)
-        return fail(PQPS_EINVAL, "row IDs are u32: id_base + n_rows must be <= 2^32");
-    int rc = check_pred(cols, n_cols, pred);
+    ExchangeSlot &sl = x->slots[slot];
+    ScanRequest r;                                               // (the slot's own ID area: this rank's list behind its count)
+    int rc = scan_request(r, MODE_IDS, cols, n_cols, n_rows, id_base, pred, sl.local + kSlotHeaderWords, x->cap);
     if (rc) return rc;
-    rc = exchange_claim(x, slot);
+    rc = exchange_claim(x, sl);
     if (rc) return rc;
     // First the payload of the query `hold` + 1 calls back.  With hold = 2 (a ring of 5 or more) nothing here waits
     // for a scan that can still be running while the two lanes are busy: the sizes needed on the host belong to
@@ -2377,48 +2452,17 @@ int pqps_exchange_select(pqps_exchange *x, const pqps_column *cols, uint32_t n_c
     const uint64_t hold = x->ring >= 5 ? 2 : (x->ring == 4 ? 1 : 0);
     rc = exchange_finish_older(x, x->calls + 1 - hold);
     if (rc) return rc;
-    uint32_t *local = x->local + (uint64_t)slot * x->stride;
-    uint64_t *hdr_dev = x->hdr_dev + (uint64_t)slot * kWireHeaderWords;
-    uint64_t *sizes_dev = x->sizes_dev + (uint64_t)slot * x->world * kWireHeaderWords;
-    uint64_t *sizes_host = x->sizes_host + (uint64_t)slot * x->world * kWireHeaderWords;
     const bool compact = x->compact && x->world > 1;
     if (compact) {                                               // room for this call's payload in compact form
-        rc = wire_room(x, &x->wire_out[slot], &x->wire_out_cap[slot], wire_bytes(n_rows, x->cap < n_rows ? x->cap : n_rows));
+        rc = wire_room(x, &sl.wire_out, &sl.wire_out_cap, wire_bytes(n_rows, x->cap < n_rows ? x->cap : n_rows));
         if (rc) return rc;
     }
-    hipStream_t scan = pick_stream(x->ctx, scan_stream);
-    EvalArgs a;
-    fill_args(a, cols, n_cols, pred);
-    a.n_rows = n_rows;
-    // the scan whole on one of two lanes (a stream and a scratch of its own: the tail of one query's launch is
-    // filled by the scan tiles of the next, see pqps_qstream); everything after it on the exchange stream, behind
-    // the launch's own completion event.
-    // (While the context records timings, the scan runs on the caller's stream with the context's own
-    // scratch, so that the recorded events mean what pqps_ctx_kernel_time documents.)
-    const bool timed = x->ctx->timing;
-    if (timed) {
-        hipEvent_t ev = x->scan_done[slot];
-        rc = run_filter(x->ctx, pick_eval<MODE_IDS>(cols, n_cols, pred, a, n_rows), a, n_rows, MODE_IDS, false, id_base,
-                        local + kSlotHeaderWords, x->cap, (uint64_t *)local, scan, &ev);
-        if (rc) return rc;
-        HIP_TRY(hipStreamWaitEvent(x->stream, ev, 0));
-    } else {
-        if (!x->ordered) {                                       // what the caller's stream holds (the table, ...) comes first
-            HIP_TRY(hipEventRecord(x->joined, scan));
-            for (uint32_t i = 0; i < kExchangeLanes; i++) HIP_TRY(hipStreamWaitEvent(x->child[i]->stream, x->joined, 0));
-            x->ordered = true;
-        }
-        pqps_ctx *lane = x->child[x->calls % kExchangeLanes];
-        hipEvent_t ev = x->k1_done[slot];
-        rc = run_filter(lane, pick_eval<MODE_IDS>(cols, n_cols, pred, a, n_rows), a, n_rows, MODE_IDS, false, id_base,
-                        local + kSlotHeaderWords, x->cap, (uint64_t *)local, lane->stream, &ev);
-        if (rc) return rc;
-        HIP_TRY(hipStreamWaitEvent(x->stream, ev, 0));
-    }
+    rc = exchange_scan(x, sl, r, scan_stream);
+    if (rc) return rc;
     // sizes: mpi:753.  They are needed on the host (send / recv counts): a 32-byte-per-rank all-gather -- reported count,
     // the shard's rows and first row (what a receiver needs to rebuild IDs from the compact form), the form the sender
     // chose -- then a copy into pinned memory behind it.  The pack kernel writes this rank's words (and the compact payload).
-    x->eager_slot[slot] = false;
+    sl.eager = false;
     if (x->world > 1) {
         const uint64_t n_max = x->cap < n_rows ? x->cap : n_rows;
         const bool eager = x->eager_ids && x->eager_next;
@@ -2427,10 +2471,10 @@ int pqps_exchange_select(pqps_exchange *x, const pqps_column *cols, uint32_t n_c
         const uint64_t max_blocks = (uint64_t)x->ctx->compute_units * 8;
         if (blocks > max_blocks) blocks = max_blocks;
         if (blocks == 0) blocks = 1;
-        uint8_t *block_out = eager ? x->eager_out + (uint64_t)slot * x->eager_block : nullptr;
-        uint8_t *blocks_in = eager ? x->eager_in + (uint64_t)slot * x->world * x->eager_block : nullptr;
-        hipLaunchKernelGGL(wire_pack_kernel, dim3((uint32_t)blocks), dim3(256), 0, x->stream, local, x->cap, n_rows, id_base, compact ? 1 : 0,
-                           wire_min_ids(), eager ? (uint64_t *)block_out : hdr_dev, x->wire_out[slot], eager ? x->eager_ids : (uint64_t)0,
+        uint8_t *block_out = eager ? sl.eager_out : nullptr;
+        uint8_t *blocks_in = eager ? sl.eager_in : nullptr;
+        hipLaunchKernelGGL(wire_pack_kernel, dim3((uint32_t)blocks), dim3(256), 0, x->stream, sl.local, x->cap, n_rows, id_base, compact ? 1 : 0,
+                           wire_min_ids(), eager ? (uint64_t *)block_out : sl.hdr_dev, sl.wire_out, eager ? x->eager_ids : (uint64_t)0,
                            eager ? (uint32_t *)(block_out + kWireHeaderWords * sizeof(uint64_t)) : nullptr);
         HIP_TRY(hipGetLastError());
         int nrc;
@@ -2440,22 +2484,22 @@ int pqps_exchange_select(pqps_exchange *x, const pqps_column *cols, uint32_t n_c
             if (nrc) return fail(PQPS_EHIP, "ncclAllGather: %s", x->rccl.GetErrorString(nrc));
             // (the headers go straight into the pinned host words: no copy launch behind the kernel)
             hipLaunchKernelGGL(eager_unpack_kernel, dim3(4, x->world), dim3(256), 0, x->stream, blocks_in, x->world, x->eager_block, x->eager_ids,
-                               x->caps_dev, x->merged[slot], x->sizes_host_dev + (uint64_t)slot * x->world * kWireHeaderWords);
+                               x->caps_dev, sl.merged, sl.sizes_host_dev);
             HIP_TRY(hipGetLastError());
-            x->eager_slot[slot] = true;
+            sl.eager = true;
         } else {
-            nrc = x->rccl.AllGather(hdr_dev, sizes_dev, kWireHeaderWords, kRcclUint64, x->comm, x->stream);
+            nrc = x->rccl.AllGather(sl.hdr_dev, sl.sizes_dev, kWireHeaderWords, kRcclUint64, x->comm, x->stream);
             if (nrc) return fail(PQPS_EHIP, "ncclAllGather: %s", x->rccl.GetErrorString(nrc));
-            HIP_TRY(hipMemcpyAsync(sizes_host, sizes_dev, (size_t)x->world * kWireHeaderWords * sizeof(uint64_t), hipMemcpyDeviceToHost, x->stream));
+            HIP_TRY(hipMemcpyAsync(sl.sizes_host, sl.sizes_dev, (size_t)x->world * kWireHeaderWords * sizeof(uint64_t), hipMemcpyDeviceToHost, x->stream));
         }
     } else {
-        HIP_TRY(hipMemcpyAsync(sizes_host, local, sizeof(uint64_t), hipMemcpyDeviceToHost, x->stream));    // (words 1 - 3 stay 0: nobody to tell)
+        HIP_TRY(hipMemcpyAsync(sl.sizes_host, sl.local, sizeof(uint64_t), hipMemcpyDeviceToHost, x->stream));    // (words 1 - 3 stay 0: nobody to tell)
     }
-    HIP_TRY(hipEventRecord(x->sizes_done[slot], x->stream));
+    HIP_TRY(hipEventRecord(sl.sizes_done, x->stream));
     // (an eager query may be complete at this point of the stream; if it is not, its payload step records the event again)
-    if (x->eager_slot[slot]) HIP_TRY(hipEventRecord(x->merge_done[slot], x->stream));
-    x->state[slot] = kSlotSizesInFlight;
-    x->issued[slot] = ++x->calls;
+    if (sl.eager) HIP_TRY(hipEventRecord(sl.merge_done, x->stream));
+    sl.state = kSlotSizesInFlight;
+    sl.issued = ++x->calls;
     return PQPS_OK;
 }
 
@@ -2465,40 +2509,22 @@ int pqps_exchange_count(pqps_exchange *x, const pqps_column *cols, uint32_t n_co
     X_ALIVE(x);
     if (!x->comm) return fail(PQPS_EINVAL, "exchange is not connected");
     if (slot >= x->ring) return fail(PQPS_EINVAL, "slot %u >= ring %u", slot, x->ring);
-    int rc = check_pred(cols, n_cols, pred);
+    ExchangeSlot &sl = x->slots[slot];
+    ScanRequest r;
+    int rc = scan_request(r, MODE_COUNT, cols, n_cols, n_rows, 0, pred, nullptr, 0);
     if (rc) return rc;
-    rc = exchange_claim(x, slot);
+    rc = exchange_claim(x, sl);
     if (rc) return rc;
     rc = exchange_finish_older(x, x->calls + 1);                  // collectives stay in call order on every rank
     if (rc) return rc;
-    uint32_t *local = x->local + (uint64_t)slot * x->stride;
-    uint64_t *totals = x->totals + 2 * (uint64_t)slot;
-    hipStream_t scan = pick_stream(x->ctx, scan_stream);
-    EvalArgs a;
-    fill_args(a, cols, n_cols, pred);
-    a.n_rows = n_rows;
-    hipEvent_t ev = x->scan_done[slot];
-    if (x->ctx->timing) {
-        rc = run_filter(x->ctx, pick_eval<MODE_COUNT>(cols, n_cols, pred, a, n_rows), a, n_rows, MODE_COUNT, false, 0,
-                        nullptr, 0, (uint64_t *)local, scan, &ev);
-    } else {                                                     // on one of the two scan lanes, as in pqps_exchange_select
-        if (!x->ordered) {
-            HIP_TRY(hipEventRecord(x->joined, scan));
-            for (uint32_t i = 0; i < kExchangeLanes; i++) HIP_TRY(hipStreamWaitEvent(x->child[i]->stream, x->joined, 0));
-            x->ordered = true;
-        }
-        pqps_ctx *lane = x->child[x->calls % kExchangeLanes];
-        rc = run_filter(lane, pick_eval<MODE_COUNT>(cols, n_cols, pred, a, n_rows), a, n_rows, MODE_COUNT, false, 0,
-                        nullptr, 0, (uint64_t *)local, lane->stream, &ev);
-    }
+    rc = exchange_scan(x, sl, r, scan_stream);
     if (rc) return rc;
-    HIP_TRY(hipStreamWaitEvent(x->stream, ev, 0));
-    HIP_TRY(hipMemsetAsync(totals + 1, 0, sizeof(uint64_t), x->stream));
-    int nrc = x->rccl.AllReduce(local, totals, 1, kRcclUint64, kRcclSum, x->comm, x->stream);      // mpi:745
+    HIP_TRY(hipMemsetAsync(sl.totals + 1, 0, sizeof(uint64_t), x->stream));
+    int nrc = x->rccl.AllReduce(sl.local, sl.totals, 1, kRcclUint64, kRcclSum, x->comm, x->stream);      // mpi:745
     if (nrc) return fail(PQPS_EHIP, "ncclAllReduce: %s", x->rccl.GetErrorString(nrc));
-    HIP_TRY(hipEventRecord(x->merge_done[slot], x->stream));
-    x->state[slot] = kSlotCount;
-    x->issued[slot] = ++x->calls;
+    HIP_TRY(hipEventRecord(sl.merge_done, x->stream));
+    sl.state = kSlotCount;
+    sl.issued = ++x->calls;
     return PQPS_OK;
 }
 
@@ -2506,21 +2532,22 @@ int pqps_exchange_result(pqps_exchange *x, uint32_t slot, const uint32_t **merge
                          uint64_t totals[2]) {
     if (!x || !totals) return fail(PQPS_EINVAL, "NULL argument");
     X_ALIVE(x);
-    if (slot >= x->ring || x->state[slot] == kSlotIdle) return fail(PQPS_EINVAL, "slot %u holds no result", slot);
-    int rc = exchange_finish_older(x, x->issued[slot] + 1);       // up to and including this slot, in call order
+    if (slot >= x->ring || x->slots[slot].state == kSlotIdle) return fail(PQPS_EINVAL, "slot %u holds no result", slot);
+    ExchangeSlot &sl = x->slots[slot];
+    int rc = exchange_finish_older(x, sl.issued + 1);       // up to and including this slot, in call order
     if (rc) return rc;
-    rc = exchange_wait(x, x->merge_done[slot], "the payload");
+    rc = exchange_wait(x, sl.merge_done, "the payload");
     if (rc) return rc;
-    if (x->state[slot] == kSlotCount) {
-        HIP_TRY(hipMemcpy(totals, x->totals + 2 * (uint64_t)slot, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        if (local_count) HIP_TRY(hipMemcpy(local_count, x->local + (uint64_t)slot * x->stride, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (sl.state == kSlotCount) {
+        HIP_TRY(hipMemcpy(totals, sl.totals, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        if (local_count) HIP_TRY(hipMemcpy(local_count, sl.local, sizeof(uint64_t), hipMemcpyDeviceToHost));
         if (merged_dev) *merged_dev = nullptr;
         return PQPS_OK;
     }
-    totals[0] = x->totals_host[2 * slot];
-    totals[1] = x->totals_host[2 * slot + 1];
-    if (local_count) *local_count = x->sizes_host[((uint64_t)slot * x->world + x->rank) * kWireHeaderWords];
-    if (merged_dev) *merged_dev = x->merged[slot];
+    totals[0] = sl.totals_host[0];
+    totals[1] = sl.totals_host[1];
+    if (local_count) *local_count = sl.sizes_host[x->rank * kWireHeaderWords];
+    if (merged_dev) *merged_dev = sl.merged;
     if (totals[1] > totals[0])
         return fail(PQPS_EOVERFLOW, "exchange slot overflow: %llu IDs reported, capacity %llu per rank",
                     (unsigned long long)totals[1], (unsigned long long)x->cap);
@@ -2583,17 +2610,19 @@ int pqps_exchange_sync(pqps_exchange *x) {
     int rc = exchange_finish_older(x, x->calls + 1);
     if (rc) return rc;
     (void)hipSetDevice(x->ctx->device);
-    for (uint32_t i = 0; i < kExchangeLanes; i++) {
-        rc = exchange_wait_stream(x, x->child[i]->stream, "a scan lane");
+    for (uint32_t i = 0; i < x->lanes.n; i++) {
+        rc = exchange_wait_stream(x, x->lanes.lane[i]->stream, "a scan lane");
         if (rc) return rc;
-        const int st = take_status(x->child[i], "exchange");
+        const int st = take_status(x->lanes.lane[i], "exchange");
         if (st) return st;
     }
     rc = exchange_wait_stream(x, x->stream, "the exchange stream");
     if (rc) return rc;
-    x->ordered = false;                                          // the caller may have put new work on its stream meanwhile
+    x->lanes.ordered = false;                                    // the caller may have put new work on its stream meanwhile
     return PQPS_OK;
 }
+
+}  // extern "C"
 
 // ---- a stream of queries on one GPU: two queries in flight, each whole on a HIP stream of its own --------
 // A query's launch ends with a tail the chip is mostly idle in (the last scan tiles drain, the expanders behind
@@ -2610,54 +2639,17 @@ int pqps_exchange_sync(pqps_exchange *x) {
 // go to lane 0, i.e. back to back on one stream; the slots still let the host run ahead.
 struct pqps_qstream {
     pqps_ctx *ctx;
-    uint32_t depth, lanes;
+    uint32_t depth;
     uint64_t seq;
-    pqps_ctx **child;                // [lanes] scratch + HIP stream of the queries in flight
+    ScanLanes lanes;                 // scratch + HIP stream of the queries in flight
     hipEvent_t *done;                // [depth] the slots' own events
     hipEvent_t *ready;               // [depth] what to wait for: the slot's own event, or the timing recorder's stop event of its launch
     pqps_ctx **ran_on;               // [depth] lane (or the parent context) the slot's query ran on
     uint32_t *ep_lo, *ep_hi;         // [depth] epochs of the slot's ID launches on that context (0, 0: none): whose status words are the slot's
-    hipEvent_t joined;               // what the caller's stream held when the stream of queries began
     bool *used;
-    bool ordered;                    // the lanes already wait for the caller's stream
     uint64_t wait_ns;                // host time spent waiting for an output buffer to come free
     std::atomic<int> dense;          // the last answers held a quarter of the rows or more: ID queries on one lane (pqps_qstream_hint_answer)
 };
-
-int pqps_qstream_destroy(pqps_qstream *q) {
-    if (!q) return PQPS_OK;
-    for (uint32_t i = 0; i < q->lanes; i++)
-        if (q->child && q->child[i]) { (void)hipStreamSynchronize(q->child[i]->stream); pqps_ctx_destroy(q->child[i]); }
-    for (uint32_t i = 0; i < q->depth; i++)
-        if (q->done && q->done[i]) (void)hipEventDestroy(q->done[i]);
-    if (q->joined) (void)hipEventDestroy(q->joined);
-    delete[] q->done; delete[] q->ready; delete[] q->ran_on; delete[] q->child; delete[] q->used; delete[] q->ep_lo; delete[] q->ep_hi;
-    delete q;
-    return PQPS_OK;
-}
-
-int pqps_qstream_create(pqps_ctx *ctx, uint32_t depth, pqps_qstream **out) {
-    if (!ctx || !out) return fail(PQPS_EINVAL, "NULL argument");
-    if (depth < 1 || depth > 64) return fail(PQPS_EINVAL, "depth %u out of range (1..64)", depth);
-    pqps_qstream *q = new (std::nothrow) pqps_qstream();
-    if (!q) return fail(PQPS_ENOMEM, "out of host memory");
-    q->ctx = ctx; q->depth = depth;
-    static const int lanes_env = [] { const char *e = tuning_env("PQPS_QSTREAM_LANES"); return e ? atoi(e) : 0; }();
-    q->lanes = lanes_env >= 1 && lanes_env <= 8 ? (uint32_t)lanes_env : 2u;
-    if (q->lanes > depth) q->lanes = depth;
-    q->child = new pqps_ctx *[q->lanes](); q->done = new hipEvent_t[depth](); q->ready = new hipEvent_t[depth]();
-    q->ran_on = new pqps_ctx *[depth](); q->used = new bool[depth](); q->ep_lo = new uint32_t[depth](); q->ep_hi = new uint32_t[depth]();
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&q->joined, hipEventDisableTiming);
-    for (uint32_t i = 0; i < depth && e == hipSuccess; i++) e = hipEventCreateWithFlags(&q->done[i], hipEventDisableTiming);
-    for (uint32_t i = 0; i < q->lanes && e == hipSuccess; i++)
-        if (create_ctx(ctx->device, true, &q->child[i]) != PQPS_OK) { pqps_qstream_destroy(q); return PQPS_EHIP; }
-    if (e != hipSuccess) { pqps_qstream_destroy(q); return fail(PQPS_EHIP, "query stream: %s", hipGetErrorString(e)); }
-    *out = q;
-    return PQPS_OK;
-}
-
-}  // extern "C"
 
 namespace {
 
@@ -2667,51 +2659,28 @@ bool one_lane_table(uint64_t n_rows) {
     return n_rows >= from;
 }
 
-// The slot is the caller's again (a host wait for the query that last used it, normally long satisfied), the lanes
-// come after what the caller's stream holds, and the query gets its lane.
-int qstream_begin(pqps_qstream *q, uint32_t slot, uint64_t n_rows, hipStream_t caller, pqps_ctx **lane, bool ids = false) {
+// The slot is the caller's again (a host wait for the query that last used it, normally long satisfied), and the query
+// gets its context and stream: a lane behind what the caller's stream holds -- or, while `timed`, the parent context
+// on the caller's stream (ScanLanes::route), where queries run one at a time and nothing is waited for.
+int qstream_begin(pqps_qstream *q, uint32_t slot, uint64_t n_rows, hipStream_t caller, bool timed, pqps_ctx **c, hipStream_t *s, bool ids = false) {
     if (slot >= q->depth) return fail(PQPS_EINVAL, "slot %u >= depth %u", slot, q->depth);
-    if (q->used[slot]) { const uint64_t t0 = now_ns(); HIP_TRY(hipEventSynchronize(q->ready[slot])); q->wait_ns += now_ns() - t0; }
-    if (!q->ordered) {                                           // what the caller's stream holds (the table, ...) comes first
-        HIP_TRY(hipEventRecord(q->joined, caller));
-        for (uint32_t i = 0; i < q->lanes; i++) HIP_TRY(hipStreamWaitEvent(q->child[i]->stream, q->joined, 0));
-        q->ordered = true;
-    }
+    if (!timed && q->used[slot]) { const uint64_t t0 = now_ns(); HIP_TRY(hipEventSynchronize(q->ready[slot])); q->wait_ns += now_ns() - t0; }
     const bool one = one_lane_table(n_rows) || (ids && q->dense.load(std::memory_order_relaxed) != 0);
-    *lane = q->child[one ? 0u : (uint32_t)(q->seq % q->lanes)];
-    return PQPS_OK;
+    return q->lanes.route(q->ctx, timed, caller, one ? 0u : (uint32_t)(q->seq % q->lanes.n), c, s);
 }
 
 int qstream_issue(pqps_qstream *q, uint32_t slot, int mode, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, uint32_t id_base,
                   const pqps_predicate *pred, uint32_t *out_ids, uint64_t out_capacity, uint64_t *out_count, void *scan_stream) {
     if (!q || !out_count) return fail(PQPS_EINVAL, "qstream/out_count is NULL");
-    if (mode == MODE_IDS) {
-        if (!out_ids && out_capacity) return fail(PQPS_EINVAL, "out_ids is NULL");
-        if (n_rows > 0xFFFFFFFFull || (uint64_t)id_base + n_rows > 0x100000000ull)
-            return fail(PQPS_EINVAL, "row IDs are u32: id_base + n_rows must be <= 2^32");
-    }
-    int rc = check_pred(cols, n_cols, pred);
+    ScanRequest r;
+    int rc = scan_request(r, mode, cols, n_cols, n_rows, id_base, pred, out_ids, out_capacity);
     if (rc) return rc;
-    EvalArgs a;
-    fill_args(a, cols, n_cols, pred);
-    a.n_rows = n_rows;
-    hipStream_t caller = pick_stream(q->ctx, scan_stream);
-    const eval_fn k1 = mode == MODE_IDS ? pick_eval<MODE_IDS>(cols, n_cols, pred, a, n_rows) : pick_eval<MODE_COUNT>(cols, n_cols, pred, a, n_rows);
-    pqps_ctx *c = nullptr;
-    hipStream_t s = caller;
-    if (q->ctx->timing) {
-        // While the PARENT context records timings the query runs whole on the caller's stream with the context's
-        // own scratch, one at a time, so that the recorded events mean what pqps_ctx_kernel_time documents.
-        if (slot >= q->depth) return fail(PQPS_EINVAL, "slot %u >= depth %u", slot, q->depth);
-        c = q->ctx;
-    } else {
-        rc = qstream_begin(q, slot, n_rows, caller, &c, mode == MODE_IDS);
-        if (rc) return rc;
-        s = c->stream;
-    }
+    pqps_ctx *c = nullptr; hipStream_t s = nullptr;
+    rc = qstream_begin(q, slot, n_rows, pick_stream(q->ctx, scan_stream), q->ctx->timing, &c, &s, mode == MODE_IDS);
+    if (rc) return rc;
     hipEvent_t ev = q->done[slot];
     const uint32_t before = c->epoch;
-    rc = run_filter(c, k1, a, n_rows, mode, false, id_base, out_ids, out_capacity, out_count, s, &ev);
+    rc = r.run(c, s, out_count, &ev);
     if (rc) return rc;
     q->ready[slot] = ev;
     q->ran_on[slot] = c;
@@ -2725,6 +2694,36 @@ int qstream_issue(pqps_qstream *q, uint32_t slot, int mode, const pqps_column *c
 }  // namespace
 
 extern "C" {
+
+int pqps_qstream_destroy(pqps_qstream *q) {
+    if (!q) return PQPS_OK;
+    q->lanes.destroy();
+    for (uint32_t i = 0; i < q->depth; i++)
+        if (q->done && q->done[i]) (void)hipEventDestroy(q->done[i]);
+    delete[] q->done; delete[] q->ready; delete[] q->ran_on; delete[] q->used; delete[] q->ep_lo; delete[] q->ep_hi;
+    delete q;
+    return PQPS_OK;
+}
+
+int pqps_qstream_create(pqps_ctx *ctx, uint32_t depth, pqps_qstream **out) {
+    if (!ctx || !out) return fail(PQPS_EINVAL, "NULL argument");
+    if (depth < 1 || depth > 64) return fail(PQPS_EINVAL, "depth %u out of range (1..64)", depth);
+    pqps_qstream *q = new (std::nothrow) pqps_qstream();
+    if (!q) return fail(PQPS_ENOMEM, "out of host memory");
+    q->ctx = ctx; q->depth = depth;
+    static const int lanes_env = [] { const char *e = tuning_env("PQPS_QSTREAM_LANES"); return e ? atoi(e) : 0; }();
+    uint32_t lanes = lanes_env >= 1 && lanes_env <= (int)kMaxScanLanes ? (uint32_t)lanes_env : 2u;
+    if (lanes > depth) lanes = depth;
+    q->done = new hipEvent_t[depth](); q->ready = new hipEvent_t[depth]();
+    q->ran_on = new pqps_ctx *[depth](); q->used = new bool[depth](); q->ep_lo = new uint32_t[depth](); q->ep_hi = new uint32_t[depth]();
+    hipError_t e = hipSetDevice(ctx->device);
+    for (uint32_t i = 0; i < depth && e == hipSuccess; i++) e = hipEventCreateWithFlags(&q->done[i], hipEventDisableTiming);
+    if (e != hipSuccess) { pqps_qstream_destroy(q); return fail(PQPS_EHIP, "query stream: %s", hipGetErrorString(e)); }
+    const int rc = q->lanes.create(ctx->device, lanes);
+    if (rc) { pqps_qstream_destroy(q); return rc; }
+    *out = q;
+    return PQPS_OK;
+}
 
 int pqps_qstream_scan_slot(pqps_qstream *q, uint32_t slot, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, uint32_t id_base,
                            const pqps_predicate *pred, uint32_t *out_ids, uint64_t out_capacity, uint64_t *out_count, void *scan_stream) {
@@ -2755,15 +2754,15 @@ int pqps_qstream_count(pqps_qstream *q, const pqps_column *cols, uint32_t n_cols
 // caller gets the lane the slot's query runs on, issues its calls there, and marks the end.
 int pqps_qstream_lane(pqps_qstream *q, uint32_t slot, uint64_t n_rows, void *scan_stream, pqps_ctx **lane_ctx, void **lane_stream) {
     if (!q || !lane_ctx || !lane_stream) return fail(PQPS_EINVAL, "NULL argument");
-    pqps_ctx *c = nullptr;
-    int rc = qstream_begin(q, slot, n_rows, pick_stream(q->ctx, scan_stream), &c);
+    pqps_ctx *c = nullptr; hipStream_t s = nullptr;
+    int rc = qstream_begin(q, slot, n_rows, pick_stream(q->ctx, scan_stream), false, &c, &s);
     if (rc) return rc;
     q->ran_on[slot] = c;
     q->ep_lo[slot] = c->epoch;                                   // (pqps_qstream_mark turns this into the range of the calls in between)
     q->ep_hi[slot] = 0;
     q->seq++;
     *lane_ctx = c;
-    *lane_stream = (void *)c->stream;
+    *lane_stream = (void *)s;
     return PQPS_OK;
 }
 
@@ -2812,11 +2811,11 @@ int pqps_qstream_reserve(pqps_qstream *q, uint64_t n_rows) {
     if (!q) return fail(PQPS_EINVAL, "qstream is NULL");
     HIP_TRY(hipSetDevice(q->ctx->device));
     const uint64_t steps = (n_rows + kStepRows - 1) / kStepRows;
-    for (uint32_t i = 0; i < q->lanes; i++) {
-        const int rc = ensure_scratch(q->child[i], steps);
+    for (uint32_t i = 0; i < q->lanes.n; i++) {
+        const int rc = ensure_scratch(q->lanes.lane[i], steps);
         if (rc) return rc;
         if ((steps + kGroupSteps - 1) / kGroupSteps < kListAreaBelowGroups)
-            (void)ensure_lists(q->child[i], steps);              // (larger tables scan without lists; refused: bit masks, same results)
+            (void)ensure_lists(q->lanes.lane[i], steps);              // (larger tables scan without lists; refused: bit masks, same results)
     }
     return PQPS_OK;
 }
@@ -2831,12 +2830,12 @@ uint64_t pqps_qstream_wait_ns(pqps_qstream *q, int reset) {
 int pqps_qstream_sync(pqps_qstream *q) {
     if (!q) return fail(PQPS_EINVAL, "qstream is NULL");
     (void)hipSetDevice(q->ctx->device);
-    for (uint32_t i = 0; i < q->lanes; i++) {
-        HIP_TRY(hipStreamSynchronize(q->child[i]->stream));
-        const int st = take_status(q->child[i], "query stream");
+    for (uint32_t i = 0; i < q->lanes.n; i++) {
+        HIP_TRY(hipStreamSynchronize(q->lanes.lane[i]->stream));
+        const int st = take_status(q->lanes.lane[i], "query stream");
         if (st) return st;
     }
-    q->ordered = false;                                          // the caller may have put new work on its stream meanwhile
+    q->lanes.ordered = false;                                    // the caller may have put new work on its stream meanwhile
     return PQPS_OK;
 }
 
@@ -2844,16 +2843,16 @@ int pqps_qstream_sync(pqps_qstream *q) {
 // events ride on the dispatch packets, so recording does not change how the launches overlap.
 int pqps_qstream_set_timing(pqps_qstream *q, int enable) {
     if (!q) return fail(PQPS_EINVAL, "qstream is NULL");
-    for (uint32_t i = 0; i < q->lanes; i++) { const int rc = pqps_ctx_set_timing(q->child[i], enable); if (rc) return rc; }
+    for (uint32_t i = 0; i < q->lanes.n; i++) { const int rc = pqps_ctx_set_timing(q->lanes.lane[i], enable); if (rc) return rc; }
     return PQPS_OK;
 }
 
 int pqps_qstream_kernel_time(pqps_qstream *q, double *eval_ms, double *total_ms, int *launches) {
     if (!q || !eval_ms || !total_ms || !launches) return fail(PQPS_EINVAL, "NULL argument");
     *eval_ms = 0.0; *total_ms = 0.0; *launches = 0;
-    for (uint32_t i = 0; i < q->lanes; i++) {
+    for (uint32_t i = 0; i < q->lanes.n; i++) {
         double e = 0.0, t = 0.0; int k = 0;
-        const int rc = pqps_ctx_kernel_time(q->child[i], &e, &t, &k);
+        const int rc = pqps_ctx_kernel_time(q->lanes.lane[i], &e, &t, &k);
         if (rc) return rc;
         *eval_ms += e; *total_ms += t; *launches += k;
     }
