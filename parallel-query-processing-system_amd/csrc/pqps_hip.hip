@@ -2928,16 +2928,18 @@ int pqps_filter_group(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, u
     g.stride = stride;
     g.bin_base = bin_base;
     g.n_bins = n_bins;
-    typedef void (*group_fn)(const GroupArgs);
-    static const group_fn fns[3][2] = {
-        {group_scan_kernel<GROUP_SMALL, false>, group_scan_kernel<GROUP_SMALL, true>},
-        {group_scan_kernel<GROUP_LDS, false>, group_scan_kernel<GROUP_LDS, true>},
-        {group_scan_kernel<GROUP_GLOBAL, false>, group_scan_kernel<GROUP_GLOBAL, true>},
+    // the instance and its name side by side: pqps_last_kernel() reports the entry that is launched
+    static const struct { void (*fn)(const GroupArgs); const char *name; } fns[3][2] = {
+#define PQPS_GROUP_SCAN(P, NT) {group_scan_kernel<P, NT>, "group_scan_kernel<" #P ", NT=" #NT ">"}
+        {PQPS_GROUP_SCAN(GROUP_SMALL, false), PQPS_GROUP_SCAN(GROUP_SMALL, true)},
+        {PQPS_GROUP_SCAN(GROUP_LDS, false), PQPS_GROUP_SCAN(GROUP_LDS, true)},
+        {PQPS_GROUP_SCAN(GROUP_GLOBAL, false), PQPS_GROUP_SCAN(GROUP_GLOBAL, true)},
+#undef PQPS_GROUP_SCAN
     };
-    static const char *const names[3] = {"GROUP_SMALL", "GROUP_LDS", "GROUP_GLOBAL"};
-    snprintf(g_kernel, sizeof g_kernel, "group_scan_kernel<%s, NT=%s>", names[path], g.e.streaming ? "true" : "false");
+    const auto &scan = fns[path][g.e.streaming ? 1 : 0];
+    snprintf(g_kernel, sizeof g_kernel, "%s", scan.name);
     hipEvent_t stop;
-    rc = fused_launch(ctx, fns[path][g.e.streaming ? 1 : 0], grid, hist_bytes, s, g, &stop);
+    rc = fused_launch(ctx, scan.fn, grid, hist_bytes, s, g, &stop);
     if (rc) return rc;
     if (path != GROUP_GLOBAL) {
         const dim3 sg(stride / 64u, (grid + kGroupSumParts - 1) / kGroupSumParts);
@@ -3028,19 +3030,21 @@ int pqps_filter_aggregate(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_col
     g.bin_base = bin_base;
     g.n_bins = n_bins;
     const bool u64 = value_col->width == 8;
-    typedef void (*agg_fn)(const AggArgs);
-    static const agg_fn fns[3][2][2] = {
-        {{agg_scan_kernel<AGG_ONE, false, false>, agg_scan_kernel<AGG_ONE, false, true>},
-         {agg_scan_kernel<AGG_ONE, true, false>, agg_scan_kernel<AGG_ONE, true, true>}},
-        {{agg_scan_kernel<AGG_LDS, false, false>, agg_scan_kernel<AGG_LDS, false, true>},
-         {agg_scan_kernel<AGG_LDS, true, false>, agg_scan_kernel<AGG_LDS, true, true>}},
-        {{agg_scan_kernel<AGG_GLOBAL, false, false>, agg_scan_kernel<AGG_GLOBAL, false, true>},
-         {agg_scan_kernel<AGG_GLOBAL, true, false>, agg_scan_kernel<AGG_GLOBAL, true, true>}},
+    // the instance and its name side by side: pqps_last_kernel() reports the entry that is launched
+    static const struct { void (*fn)(const AggArgs); const char *name; } fns[3][2][2] = {
+#define PQPS_AGG_SCAN(P, U64, V, NT) {agg_scan_kernel<P, U64, NT>, "agg_scan_kernel<" #P ", " V ", NT=" #NT ">"}
+        {{PQPS_AGG_SCAN(AGG_ONE, false, "i32", false), PQPS_AGG_SCAN(AGG_ONE, false, "i32", true)},
+         {PQPS_AGG_SCAN(AGG_ONE, true, "u64", false), PQPS_AGG_SCAN(AGG_ONE, true, "u64", true)}},
+        {{PQPS_AGG_SCAN(AGG_LDS, false, "i32", false), PQPS_AGG_SCAN(AGG_LDS, false, "i32", true)},
+         {PQPS_AGG_SCAN(AGG_LDS, true, "u64", false), PQPS_AGG_SCAN(AGG_LDS, true, "u64", true)}},
+        {{PQPS_AGG_SCAN(AGG_GLOBAL, false, "i32", false), PQPS_AGG_SCAN(AGG_GLOBAL, false, "i32", true)},
+         {PQPS_AGG_SCAN(AGG_GLOBAL, true, "u64", false), PQPS_AGG_SCAN(AGG_GLOBAL, true, "u64", true)}},
+#undef PQPS_AGG_SCAN
     };
-    static const char *const names[3] = {"AGG_ONE", "AGG_LDS", "AGG_GLOBAL"};
-    snprintf(g_kernel, sizeof g_kernel, "agg_scan_kernel<%s, %s, NT=%s>", names[path], u64 ? "u64" : "i32", g.e.streaming ? "true" : "false");
+    const auto &scan = fns[path][u64 ? 1 : 0][g.e.streaming ? 1 : 0];
+    snprintf(g_kernel, sizeof g_kernel, "%s", scan.name);
     hipEvent_t stop;
-    rc = fused_launch(ctx, fns[path][u64 ? 1 : 0][g.e.streaming ? 1 : 0], grid, table_bytes, s, g, &stop);
+    rc = fused_launch(ctx, scan.fn, grid, table_bytes, s, g, &stop);
     if (rc) return rc;
     if (path != AGG_GLOBAL) {
         const dim3 sg((n_bins + 63u) / 64u, (grid + kAggSumParts - 1) / kAggSumParts);
@@ -3157,7 +3161,10 @@ int pqps_filter_topk(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, ui
     if (rc) return rc;
     hipStream_t s = pick_stream(ctx, stream);
     HIP_TRY(hipMemsetAsync(count, 0, sizeof(uint64_t), s));
-    if (n_rows == 0) return PQPS_OK;
+    if (n_rows == 0) {                                           // no candidate: every key of `out` reads all ones
+        HIP_TRY(hipMemsetAsync(out, 0xFF, (size_t)k * (wide ? 16 : 8), s));
+        return PQPS_OK;
+    }
     const uint32_t cap = topk_cap(k);
     const uint32_t key_bytes = wide ? 16u : 8u;
     const uint32_t lds = kWaves * cap * key_bytes;
@@ -3173,12 +3180,17 @@ int pqps_filter_topk(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, ui
     g.row_base = row_base;
     g.k = k;
     g.cap = cap;
-    typedef void (*topk_fn)(const TopkArgs);
-    static const topk_fn fns[2][2] = {{topk_scan_kernel<false, false>, topk_scan_kernel<false, true>},
-                                      {topk_scan_kernel<true, false>, topk_scan_kernel<true, true>}};
-    snprintf(g_kernel, sizeof g_kernel, "topk_scan_kernel<%s, NT=%s>", wide ? "wide" : "narrow", g.e.streaming ? "true" : "false");
+    // the instance and its name side by side: pqps_last_kernel() reports the entry that is launched
+    static const struct { void (*fn)(const TopkArgs); const char *name; } fns[2][2] = {
+#define PQPS_TOPK_SCAN(WIDE, W, NT) {topk_scan_kernel<WIDE, NT>, "topk_scan_kernel<" W ", NT=" #NT ">"}
+        {PQPS_TOPK_SCAN(false, "narrow", false), PQPS_TOPK_SCAN(false, "narrow", true)},
+        {PQPS_TOPK_SCAN(true, "wide", false), PQPS_TOPK_SCAN(true, "wide", true)},
+#undef PQPS_TOPK_SCAN
+    };
+    const auto &scan = fns[wide ? 1 : 0][g.e.streaming ? 1 : 0];
+    snprintf(g_kernel, sizeof g_kernel, "%s", scan.name);
     hipEvent_t stop;
-    rc = fused_launch(ctx, fns[wide ? 1 : 0][g.e.streaming ? 1 : 0], grid, lds, s, g, &stop);
+    rc = fused_launch(ctx, scan.fn, grid, lds, s, g, &stop);
     if (rc) return rc;
     char *xa = base + parts * key_bytes, *ya = xa + round * key_bytes;
     if (wide) rc = topk_rounds<true>(ctx, s, (const TKey<true> *)base, nullptr, nullptr, 0, 0, 0, parts, k, (TKey<true> *)xa,
@@ -3198,9 +3210,12 @@ int pqps_topk_list(pqps_ctx *ctx, const pqps_column *key_col, int key_signed, in
     if (rc) return rc;
     if (k == 0 || k > (wide ? kTopkMaxWide : kTopkMax)) return fail(PQPS_EINVAL, "K = %u: 1 .. %u", k, wide ? kTopkMaxWide : kTopkMax);
     if (scratch_bytes < pqps_topk_scratch_bytes(ctx, n, k, wide, 0)) return fail(PQPS_EINVAL, "scratch too small");
-    if (n == 0) return PQPS_OK;
     hipStream_t s = pick_stream(ctx, stream);
     const uint64_t key_bytes = wide ? 16 : 8;
+    if (n == 0) {                                                // no candidate: every key of `out` reads all ones
+        HIP_TRY(hipMemsetAsync(out, 0xFF, (size_t)k * key_bytes, s));
+        return PQPS_OK;
+    }
     char *xa = (char *)scratch, *ya = xa + topk_round_keys(n, k) * key_bytes;
     const void *kcol = key_col ? key_col->data : nullptr;
     const uint64_t kxor = topk_xor(wide, key_signed, descending);
@@ -3322,19 +3337,21 @@ int pqps_filter_distinct(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols
     g.n_values = n_values;
     g.n_groups = n_groups;
     g.words = (n_values + 31) / 32;
-    typedef void (*dist_fn)(const DistArgs);
-    static const dist_fn fns[3][2][2] = {
-        {{dist_scan_kernel<DIST_REG, false, false>, dist_scan_kernel<DIST_REG, false, true>},
-         {dist_scan_kernel<DIST_REG, true, false>, dist_scan_kernel<DIST_REG, true, true>}},
-        {{dist_scan_kernel<DIST_LDS, false, false>, dist_scan_kernel<DIST_LDS, false, true>},
-         {dist_scan_kernel<DIST_LDS, true, false>, dist_scan_kernel<DIST_LDS, true, true>}},
-        {{dist_scan_kernel<DIST_GLOBAL, false, false>, dist_scan_kernel<DIST_GLOBAL, false, true>},
-         {dist_scan_kernel<DIST_GLOBAL, true, false>, dist_scan_kernel<DIST_GLOBAL, true, true>}},
+    // the instance and its name side by side: pqps_last_kernel() reports the entry that is launched
+    static const struct { void (*fn)(const DistArgs); const char *name; } fns[3][2][2] = {
+#define PQPS_DIST_SCAN(P, G, NT) {dist_scan_kernel<P, G, NT>, "dist_scan_kernel<" #P ", GROUPED=" #G ", NT=" #NT ">"}
+        {{PQPS_DIST_SCAN(DIST_REG, false, false), PQPS_DIST_SCAN(DIST_REG, false, true)},
+         {PQPS_DIST_SCAN(DIST_REG, true, false), PQPS_DIST_SCAN(DIST_REG, true, true)}},
+        {{PQPS_DIST_SCAN(DIST_LDS, false, false), PQPS_DIST_SCAN(DIST_LDS, false, true)},
+         {PQPS_DIST_SCAN(DIST_LDS, true, false), PQPS_DIST_SCAN(DIST_LDS, true, true)}},
+        {{PQPS_DIST_SCAN(DIST_GLOBAL, false, false), PQPS_DIST_SCAN(DIST_GLOBAL, false, true)},
+         {PQPS_DIST_SCAN(DIST_GLOBAL, true, false), PQPS_DIST_SCAN(DIST_GLOBAL, true, true)}},
+#undef PQPS_DIST_SCAN
     };
-    snprintf(g_kernel, sizeof g_kernel, "dist_scan_kernel<%s, GROUPED=%s, NT=%s>", k_dist_names[path], group_col ? "true" : "false",
-             g.e.streaming ? "true" : "false");
+    const auto &scan = fns[path][group_col ? 1 : 0][g.e.streaming ? 1 : 0];
+    snprintf(g_kernel, sizeof g_kernel, "%s", scan.name);
     hipEvent_t stop;
-    rc = fused_launch(ctx, fns[path][group_col ? 1 : 0][g.e.streaming ? 1 : 0], grid, lds, s, g, &stop);
+    rc = fused_launch(ctx, scan.fn, grid, lds, s, g, &stop);
     if (rc) return rc;
     // the partial bitmaps OR-ed and the totals summed (GLOBAL: the totals only); the last launch takes `stop`
     const dim3 og(row_words ? (row_words + 63u) / 64u : 1u, (grid + kDistOrParts - 1) / kDistOrParts);
