@@ -316,6 +316,48 @@ struct hipDistinctResult *executeQueryCountDistinctHIP(struct engineS *engine, c
                                                        struct whereClauseS *whereClause);
 void freeDistinctResultHIP(struct hipDistinctResult *result);
 
+/* GROUP BY two columns: COUNT(*), or COUNT / SUM / MIN / MAX of one numeric column, per pair of values (no aggregates in the
+ * reference; reached through the C API and the Python package only, like the grouped COUNT above).
+ * ROWS: exactly the rows executeQuerySelectIdsHIP(engine, whereClause) returns -- in index mode too, so a row several probed
+ * conditions return more than once is counted and added that many times, as in executeQueryGroupCountHIP and
+ * executeQueryAggregateHIP; `total` equals that call's count.
+ * GROUPS: a group is a pair (value of A, value of B) that at least one of those rows carries.  Pairs come in ascending
+ * lexicographic order: A's key order first, then B's, each column in executeQueryGroupCountHIP's key order (numeric for
+ * i32, false before true, the dictionary's strcmp order); keys[j] and keyText[j] per column are exactly that call's.
+ * VALUES (valueColumn != NULL): as executeQueryAggregateHIP -- i32 sums exact in int64, command_id sums modulo 2^64 with
+ * unsigned min / max, returned as the u64 bits (valueKind says which).  Without a value column sums, mins and maxs are NULL.
+ * There is no AVG on the device.
+ * MARGINALS: for every WHERE, summing counts over B for a fixed A gives executeQueryGroupCountHIP(A)'s count; summing sums
+ * and taking the min of mins and the max of maxs over B gives executeQueryAggregateHIP(value, A).
+ * SPECIAL CASES: a NULL WHERE groups the whole table; no match, or an empty table, gives numGroups = 0 with success = true;
+ * A == B is allowed (only diagonal pairs occur); a single-valued dictionary column (no device buffer) as A or B contributes
+ * its one key to every pair -- the query then runs as the one-column form on the other column, and as one group from the
+ * selection when both are single-valued.
+ * REFUSED (success = false, the reason on stderr): an unknown group or value column, a dictionary or boolean value column,
+ * and for either group column alone everything executeQueryGroupCountHIP refuses (command_id, an i32 column spanning more
+ * than 65 536 values, an engine joined across ranks).  NOTHING is refused for the size of the product: two columns of
+ * 65 536 bins each are a legal query.  A reader like COUNT: shared lock and one query lane; the lane rules above apply.
+ * Execution: with D = bins of A x bins of B (a 64-bit product).  D <= 65 536: a single-pass scan-mode WHERE runs ONE fused
+ * launch per shard (pqps_filter_group_pair), everything else the selection and then pqps_group_pair_list over each shard's
+ * list; shards' bins are added on the host.  D > 65 536, on any WHERE: the selection, then per shard a radix sort of the
+ * listed rows' composite keys and a run reduction on the device (pqps_group_pair_sort); the download is one entry per pair
+ * that occurs, and shards' runs are merged by key on the host (counts and sums added, min / max taken). */
+struct hipGroupPairResult {
+    int groupColumn[2], groupKind[2];   /* HIPCOL_*, HIPKIND_I32 / _BOOL / _DICT                          */
+    int valueColumn, valueKind;         /* -1 / -1: no value column, COUNT(*) per pair only                */
+    int numGroups;                      /* pairs with at least one row                                     */
+    long long total;                    /* sum of counts = executeQuerySelectIdsHIP's count                */
+    long long *keys[2];                 /* per pair, as hipGroupResult.keys for that column                */
+    char **keyText[2];                  /* per pair, owned copies, as get_attribute_string_value formats   */
+    unsigned long long *counts;
+    long long *sums, *mins, *maxs;      /* NULL without a value column; u64 bits for command_id            */
+    double queryTime;
+    bool success;
+};
+struct hipGroupPairResult *executeQueryGroupPairHIP(struct engineS *engine, const char *groupColumnA, const char *groupColumnB,
+                                                    const char *valueColumn /* may be NULL */, struct whereClauseS *whereClause);
+void freeGroupPairResultHIP(struct hipGroupPairResult *result);
+
 /* ORDER BY one column [ASC | DESC] with LIMIT (the reference parses ORDER BY into ParsedSQL.order_by / order_desc and
  * executes it nowhere; reached through the C API and the Python package only -- the SQL driver still ignores it, so its
  * output stays that of QPESeq).

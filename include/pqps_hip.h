@@ -540,6 +540,40 @@ int pqps_distinct_sort(pqps_ctx *ctx, const pqps_column *value_col, uint32_t v_b
                        uint32_t n_groups, const uint32_t *ids, uint64_t n, uint32_t id_base, uint64_t *distinct, uint64_t *out_keys,
                        void *stream);
 
+/* ---- GROUP BY two columns: COUNT(*), or COUNT / SUM / MIN / MAX of a value column, per pair of values ---------------------
+ * No counterpart in the reference.  BINS: each group column has the bins of pqps_filter_group -- bin_a = (value of A - a_base),
+ * bin_b = (value of B - b_base) in 32-bit arithmetic, n_a and n_b of them (1 .. 65 536 each); a row whose bin_a >= n_a or
+ * bin_b >= n_b is left out.  The bin of a row is bin_a * n_b + bin_b, D = n_a x n_b bins in all -- a 64-bit product: the
+ * two dense calls take D = 1 .. 65 536 and return PQPS_EINVAL for anything else (n_a or n_b 0 included), the sort call
+ * takes any D.  `value_col` NULL: COUNT(*) only; otherwise 4 bytes (signed i32) or 8 bytes (u64), as pqps_filter_aggregate.
+ * DENSE OUTPUT (`out`, device): without a value column D u32 counts, as pqps_filter_group's bins; with one the [4][D] u64
+ * fields of pqps_filter_aggregate (counts, sums, min images, max images; a bin without rows reads 0, 0, UINT64_MAX, 0).  The
+ * calls initialise `out` themselves and are asynchronous on `stream`.
+ *
+ * pqps_filter_group_pair: ONE scan of `pred` over rows [0, n_rows) of `cols`; A, B and the value column are read only in
+ *   steps of 1024 rows that hold a match.  `a_col` / `b_col` 1, 2 or 4 bytes wide or a bit plane each; the readable-padding
+ *   rule of pqps_filter_scan applies to the predicate columns, A, B and `value_col`.  COUNT(*): a u32 histogram in LDS for
+ *   D <= 16 384, atomics straight into the bins above (slow: a correctness path).  With a value: the 28-byte-per-bin table
+ *   in LDS for D <= 2304, four global 64-bit atomics per matching row above.  The context's timing recorder records the
+ *   launch like a COUNT's.
+ * pqps_group_pair_list: the same bins over an ID list -- ids[0 .. min(*count_dev, capacity)), row = id - id_base; a row
+ *   >= n_rows is skipped -- gathering A, B (1, 2 or 4 bytes wide, no bit plane) and the value per listed row.
+ * pqps_group_pair_sort: the sparse form for any D, over ids[0 .. n) (n below 2^32 - 1): one u64 key per listed row,
+ *   bin_a << 32 | bin_b (rows outside the bins or the table are left out), sorted with the row numbers by the stable LSD
+ *   radix sort over the bytes in which the keys differ, then reduced run by run.  OUTPUT: *n_runs (host) = the pairs that
+ *   occur, *runs_dev = device memory the call allocates (NULL for no runs; the caller frees it with pqps_free), compact and
+ *   field-major, *n_runs u64 entries per field, ascending by key: keys, counts, and with a value column sums, min images,
+ *   max images.  Its scratch is allocated and freed by the call.  Synchronous. */
+int pqps_filter_group_pair(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                           const pqps_column *a_col, uint32_t a_base, uint32_t n_a, const pqps_column *b_col, uint32_t b_base,
+                           uint32_t n_b, const pqps_column *value_col, void *out, void *stream);
+int pqps_group_pair_list(pqps_ctx *ctx, const pqps_column *a_col, uint32_t a_base, uint32_t n_a, const pqps_column *b_col, uint32_t b_base,
+                         uint32_t n_b, const pqps_column *value_col, uint64_t n_rows, const uint32_t *ids, const uint64_t *count_dev,
+                         uint64_t capacity, uint32_t id_base, void *out, void *stream);
+int pqps_group_pair_sort(pqps_ctx *ctx, const pqps_column *a_col, uint32_t a_base, uint32_t n_a, const pqps_column *b_col, uint32_t b_base,
+                         uint32_t n_b, const pqps_column *value_col, uint64_t n_rows, const uint32_t *ids, uint64_t n, uint32_t id_base,
+                         uint64_t **runs_dev, uint64_t *n_runs, void *stream);
+
 /* Checksums of a device-resident ID list: out[0] = sum of ids[i], out[1] = sum of ids[i] * (2 i + 1), both mod 2^64 (the
  * second depends on the order).  Synchronous; what a bench or a test compares two lists with without downloading them. */
 int pqps_ids_checksum(pqps_ctx *ctx, const uint32_t *ids, uint64_t count, uint64_t out[2], void *stream);

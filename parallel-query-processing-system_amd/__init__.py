@@ -114,6 +114,15 @@ class AggregateResult(C.Structure):
                 ("queryTime", C.c_double), ("success", C.c_bool)]
 
 
+class GroupPairResult(C.Structure):
+    """struct hipGroupPairResult (include/executeEngine-hip.h)."""
+    _fields_ = [("groupColumn", C.c_int * 2), ("groupKind", C.c_int * 2), ("valueColumn", C.c_int), ("valueKind", C.c_int),
+                ("numGroups", C.c_int), ("total", C.c_longlong),
+                ("keys", C.POINTER(C.c_longlong) * 2), ("keyText", C.POINTER(C.c_char_p) * 2), ("counts", C.POINTER(C.c_ulonglong)),
+                ("sums", C.POINTER(C.c_longlong)), ("mins", C.POINTER(C.c_longlong)), ("maxs", C.POINTER(C.c_longlong)),
+                ("queryTime", C.c_double), ("success", C.c_bool)]
+
+
 class DistinctResult(C.Structure):
     """struct hipDistinctResult (include/executeEngine-hip.h)."""
     _fields_ = [("valueColumn", C.c_int), ("valueKind", C.c_int), ("groupColumn", C.c_int), ("groupKind", C.c_int),
@@ -435,6 +444,16 @@ def lib():
     L.pqps_filter_aggregate.argtypes = [vp, C.POINTER(Column), u32, u64, C.POINTER(Predicate), C.POINTER(Column), C.POINTER(Column),
                                         u32, u32, vp, vp]
     L.pqps_aggregate_list.argtypes = [vp, C.POINTER(Column), C.POINTER(Column), u64, vp, vp, u64, u32, u32, u32, vp, vp]
+    L.executeQueryGroupPairHIP.restype = C.POINTER(GroupPairResult)
+    L.executeQueryGroupPairHIP.argtypes = [E, C.c_char_p, C.c_char_p, C.c_char_p, W]
+    L.freeGroupPairResultHIP.argtypes = [C.POINTER(GroupPairResult)]
+    L.freeGroupPairResultHIP.restype = None
+    L.pqps_filter_group_pair.argtypes = [vp, C.POINTER(Column), u32, u64, C.POINTER(Predicate), C.POINTER(Column), u32, u32,
+                                         C.POINTER(Column), u32, u32, C.POINTER(Column), vp, vp]
+    L.pqps_group_pair_list.argtypes = [vp, C.POINTER(Column), u32, u32, C.POINTER(Column), u32, u32, C.POINTER(Column), u64, vp, vp,
+                                       u64, u32, vp, vp]
+    L.pqps_group_pair_sort.argtypes = [vp, C.POINTER(Column), u32, u32, C.POINTER(Column), u32, u32, C.POINTER(Column), u64, vp, u64,
+                                       u32, C.POINTER(vp), C.POINTER(u64), vp]
     L.executeQueryCountDistinctHIP.restype = C.POINTER(DistinctResult)
     L.executeQueryCountDistinctHIP.argtypes = [E, C.c_char_p, C.c_char_p, W]
     L.freeDistinctResultHIP.argtypes = [C.POINTER(DistinctResult)]
@@ -877,6 +896,40 @@ class HipEngine:
                      fix(r.sums[g]), fix(r.mins[g]), fix(r.maxs[g])) for g in range(r.numGroups)]
         finally:
             lib().freeAggregateResultHIP(res)
+
+    def group_pair_total(self, group_columns, value_column=None, chain=None):
+        """executeQueryGroupPairHIP: (pairs, total, seconds) -- `pairs` as group_pair() returns them, total =
+        select_ids(chain)'s length, seconds = the engine's own queryTime."""
+        a, b = group_columns
+        wl = WhereList(chain)
+        res = lib().executeQueryGroupPairHIP(self.e, a.encode(), b.encode(), value_column.encode() if value_column else None, wl.ptr)
+        what = f"group_pair(({a!r}, {b!r}), {value_column!r})"
+        if not res:
+            raise PqpsError(f"{what}: no result")
+        try:
+            r = res.contents
+            if not r.success:
+                raise PqpsError(f"{what} refused or failed (reason on stderr)")
+            n = r.numGroups
+            ta, tb = r.keyText[0][:n], r.keyText[1][:n]
+            texts = [(x.decode("latin-1"), y.decode("latin-1")) for x, y in zip(ta, tb)]
+            counts = r.counts[:n]
+            if r.valueColumn < 0:
+                pairs = list(zip(texts, counts))
+            else:
+                fix = (lambda x: x & 0xFFFFFFFFFFFFFFFF) if r.valueKind == HIPKIND_U64 else int
+                pairs = [(t, c, fix(s), fix(lo), fix(hi)) for t, c, s, lo, hi in zip(texts, counts, r.sums[:n], r.mins[:n], r.maxs[:n])]
+            return pairs, int(r.total), float(r.queryTime)
+        finally:
+            lib().freeGroupPairResultHIP(res)
+
+    def group_pair(self, group_columns, value_column=None, chain=None):
+        """GROUP BY two columns: over the rows select_ids(chain) returns, per pair of values of `group_columns` (two names)
+        that occurs, ((text_a, text_b), count) -- or ((text_a, text_b), count, sum, min, max) of `value_column` -- in
+        ascending order of A's key, then B's (each column in group_count's key order).  Python ints; command_id's sum (mod
+        2^64), min and max are unsigned, as aggregate() returns them.  Raises PqpsError when the engine refuses (reason on
+        stderr)."""
+        return self.group_pair_total(group_columns, value_column, chain)[0]
 
     def average(self, value_column, group_column=None, chain=None):
         """AVG as sum / count of aggregate(): [(key_text, avg), ...] (the device computes no AVG)."""

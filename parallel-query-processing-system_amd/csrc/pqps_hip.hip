@@ -27,6 +27,7 @@
 #include "aggregate_kernels.hpp"
 #include "topk_kernels.hpp"
 #include "distinct_kernels.hpp"
+#include "group_pair_kernels.hpp"
 #include "radix_sort.hpp"
 
 namespace {
@@ -3475,6 +3476,201 @@ int pqps_distinct_sort(pqps_ctx *ctx, const pqps_column *value_col, uint32_t v_b
     if (vf) (void)hipFree(vf);
     pqps_sort::workspace_free(w);
     if (e != hipSuccess) return fail(PQPS_EHIP, "COUNT(DISTINCT) sort: %s", hipGetErrorString(e));
+    return PQPS_OK;
+}
+
+// ---- GROUP BY two columns (group_pair_kernels.hpp) -------------------------------------------------------------------
+// D = n_a x n_b in 64 bits; the dense calls take 1 .. 65 536.  *awl / *bwl / *val: the width codes and the PairValue.
+static int check_pair_cols(const pqps_column *a_col, uint32_t n_a, const pqps_column *b_col, uint32_t n_b, const pqps_column *value_col,
+                           bool dense, bool plane_ok, bool aligned, uint32_t *awl, uint32_t *bwl, int *val) {
+    if (!a_col || !b_col) return fail(PQPS_EINVAL, "a group column is NULL");
+    const uint64_t D = (uint64_t)n_a * n_b;
+    if (D == 0 || n_a > kGroupMaxBins || n_b > kGroupMaxBins || (dense && D > kGroupMaxBins))
+        return fail(PQPS_EINVAL, "%u x %u bins: 1 .. %u each%s", n_a, n_b, kGroupMaxBins, dense ? " and in all" : "");
+    int rc = column_width_code("group", a_col, plane_ok, false, aligned, awl);
+    if (rc == PQPS_OK) rc = column_width_code("group", b_col, plane_ok, false, aligned, bwl);
+    if (rc) return rc;
+    *val = PAIR_COUNT;
+    if (value_col) {
+        if (value_col->width != 4 && value_col->width != 8) return fail(PQPS_EINVAL, "value column: width %u not in {4,8}", value_col->width);
+        if (!value_col->data || ((uintptr_t)value_col->data & 15u) != 0) return fail(PQPS_EINVAL, "value column: NULL or not 16-byte aligned");
+        *val = value_col->width == 8 ? PAIR_U64 : PAIR_I32;
+    }
+    return PQPS_OK;
+}
+
+// the dense calls' output: D u32 bins, or the [4][D] u64 fields of pqps_filter_aggregate
+static int init_pair_out(void *out, uint32_t D, int val, hipStream_t s) {
+    if (val != PAIR_COUNT) return init_aggregate_out((uint64_t *)out, D, s);
+    HIP_TRY(hipMemsetAsync(out, 0, (size_t)D * sizeof(uint32_t), s));
+    return PQPS_OK;
+}
+
+static uint32_t pair_lds_bytes(uint32_t D, int val, bool *lds) {
+    *lds = val == PAIR_COUNT ? D <= kGroupLdsBins : D <= kAggLdsBins;
+    if (!*lds) return 0u;
+    return val == PAIR_COUNT ? D * (uint32_t)sizeof(uint32_t) : D * (uint32_t)(3 * sizeof(uint64_t) + sizeof(uint32_t));
+}
+
+int pqps_filter_group_pair(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                           const pqps_column *a_col, uint32_t a_base, uint32_t n_a, const pqps_column *b_col, uint32_t b_base,
+                           uint32_t n_b, const pqps_column *value_col, void *out, void *stream) {
+    if (!ctx || !out) return fail(PQPS_EINVAL, "ctx/out is NULL");
+    PairArgs g;
+    memset(&g, 0, sizeof g);
+    int val;
+    int rc = check_pair_cols(a_col, n_a, b_col, n_b, value_col, true, true, true, &g.awidth_log2, &g.bwidth_log2, &val);
+    if (rc == PQPS_OK) rc = fused_args(g.e, cols, n_cols, n_rows, pred);
+    if (rc) return rc;
+    const uint32_t D = n_a * n_b;
+    hipStream_t s = pick_stream(ctx, stream);
+    rc = init_pair_out(out, D, val, s);
+    if (rc || n_rows == 0) return rc;
+    bool lds;
+    const uint32_t lds_bytes = pair_lds_bytes(D, val, &lds);
+    const uint32_t grid = fused_grid(ctx, n_rows, lds_bytes);
+    const uint32_t stride = (D + 63u) & ~63u;
+    if (lds) {
+        rc = grow_group_parts(ctx, s, val == PAIR_COUNT ? (size_t)grid * stride : (size_t)grid * kAggFields * D * 2);
+        if (rc) return rc;
+    }
+    g.acol = a_col->data;
+    g.bcol = b_col->data;
+    g.vcol = value_col ? value_col->data : nullptr;
+    g.bins = (uint32_t *)out;
+    g.out = (uint64_t *)out;
+    g.parts = ctx->group_parts;
+    g.stride = stride;
+    g.a_base = a_base;
+    g.b_base = b_base;
+    g.n_a = n_a;
+    g.n_b = n_b;
+    // the instance and its name side by side: pqps_last_kernel() reports the entry that is launched
+    static const struct { void (*fn)(const PairArgs); const char *name; } fns[2][3][2] = {
+#define PQPS_PAIR_SCAN(P, V, NT) {pair_scan_kernel<P, V, NT>, "pair_scan_kernel<" #P ", " #V ", NT=" #NT ">"}
+        {{PQPS_PAIR_SCAN(PAIR_LDS, PAIR_COUNT, false), PQPS_PAIR_SCAN(PAIR_LDS, PAIR_COUNT, true)},
+         {PQPS_PAIR_SCAN(PAIR_LDS, PAIR_I32, false), PQPS_PAIR_SCAN(PAIR_LDS, PAIR_I32, true)},
+         {PQPS_PAIR_SCAN(PAIR_LDS, PAIR_U64, false), PQPS_PAIR_SCAN(PAIR_LDS, PAIR_U64, true)}},
+        {{PQPS_PAIR_SCAN(PAIR_GLOBAL, PAIR_COUNT, false), PQPS_PAIR_SCAN(PAIR_GLOBAL, PAIR_COUNT, true)},
+         {PQPS_PAIR_SCAN(PAIR_GLOBAL, PAIR_I32, false), PQPS_PAIR_SCAN(PAIR_GLOBAL, PAIR_I32, true)},
+         {PQPS_PAIR_SCAN(PAIR_GLOBAL, PAIR_U64, false), PQPS_PAIR_SCAN(PAIR_GLOBAL, PAIR_U64, true)}},
+#undef PQPS_PAIR_SCAN
+    };
+    const auto &scan = fns[lds ? PAIR_LDS : PAIR_GLOBAL][val][g.e.streaming ? 1 : 0];
+    snprintf(g_kernel, sizeof g_kernel, "%s", scan.name);
+    hipEvent_t stop;
+    rc = fused_launch(ctx, scan.fn, grid, lds_bytes, s, g, &stop);
+    if (rc) return rc;
+    if (lds && val == PAIR_COUNT) {
+        const dim3 sg(stride / 64u, (grid + kGroupSumParts - 1) / kGroupSumParts);
+        rc = launch_stop(group_sum_kernel, sg, 0, s, stop, (const uint32_t *)ctx->group_parts, grid, stride, D, (uint32_t *)out);
+    } else if (lds) {
+        const dim3 sg((D + 63u) / 64u, (grid + kAggSumParts - 1) / kAggSumParts);
+        rc = launch_stop(agg_sum_kernel, sg, 0, s, stop, (const uint64_t *)ctx->group_parts, grid, D, (uint64_t *)out);
+    }
+    fused_close(ctx, stop, !lds);
+    return rc;
+}
+
+int pqps_group_pair_list(pqps_ctx *ctx, const pqps_column *a_col, uint32_t a_base, uint32_t n_a, const pqps_column *b_col, uint32_t b_base,
+                         uint32_t n_b, const pqps_column *value_col, uint64_t n_rows, const uint32_t *ids, const uint64_t *count_dev,
+                         uint64_t capacity, uint32_t id_base, void *out, void *stream) {
+    if (!ctx || !out || !count_dev || (capacity && !ids)) return fail(PQPS_EINVAL, "NULL argument");
+    uint32_t awl, bwl;
+    int val;
+    int rc = check_pair_cols(a_col, n_a, b_col, n_b, value_col, true, false, false, &awl, &bwl, &val);   // gathered by row: any alignment
+    if (rc) return rc;
+    const uint32_t D = n_a * n_b;
+    hipStream_t s = pick_stream(ctx, stream);
+    rc = init_pair_out(out, D, val, s);
+    if (rc || capacity == 0 || n_rows == 0) return rc;
+    bool lds;
+    const uint32_t lds_bytes = pair_lds_bytes(D, val, &lds);
+    typedef void (*list_fn)(const void *, uint32_t, const void *, uint32_t, const void *, uint64_t, const uint32_t *, const uint64_t *, uint64_t,
+                            uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, void *);
+    static const list_fn fns[2][3] = {
+        {pair_list_kernel<false, PAIR_COUNT>, pair_list_kernel<false, PAIR_I32>, pair_list_kernel<false, PAIR_U64>},
+        {pair_list_kernel<true, PAIR_COUNT>, pair_list_kernel<true, PAIR_I32>, pair_list_kernel<true, PAIR_U64>},
+    };
+    snprintf(g_kernel, sizeof g_kernel, "pair_list_kernel<LDS=%s, %s>", lds ? "true" : "false", val == PAIR_COUNT ? "PAIR_COUNT" : val == PAIR_I32 ? "PAIR_I32" : "PAIR_U64");
+    hipLaunchKernelGGL(fns[lds ? 1 : 0][val], dim3(list_grid(ctx, capacity, 4)), dim3(kBlock), lds_bytes, s, a_col->data, awl, b_col->data, bwl,
+                       value_col ? value_col->data : nullptr, n_rows, ids, count_dev, capacity, id_base, a_base, b_base, n_a, n_b, out);
+    HIP_TRY(hipGetLastError());
+    return PQPS_OK;
+}
+
+int pqps_group_pair_sort(pqps_ctx *ctx, const pqps_column *a_col, uint32_t a_base, uint32_t n_a, const pqps_column *b_col, uint32_t b_base,
+                         uint32_t n_b, const pqps_column *value_col, uint64_t n_rows, const uint32_t *ids, uint64_t n, uint32_t id_base,
+                         uint64_t **runs_dev, uint64_t *n_runs, void *stream) {
+    if (!ctx || !runs_dev || !n_runs || (n && !ids)) return fail(PQPS_EINVAL, "NULL argument");
+    *runs_dev = nullptr;
+    *n_runs = 0;
+    uint32_t awl, bwl;
+    int val;
+    int rc = check_pair_cols(a_col, n_a, b_col, n_b, value_col, false, false, false, &awl, &bwl, &val);
+    if (rc) return rc;
+    if (n >= 0xFFFFFFFFull) return fail(PQPS_EINVAL, "a list of %llu rows", (unsigned long long)n);
+    hipStream_t s = pick_stream(ctx, stream);
+    snprintf(g_kernel, sizeof g_kernel, "pair_runs_kernel<%s> (sort)", val == PAIR_COUNT ? "PAIR_COUNT" : val == PAIR_I32 ? "PAIR_I32" : "PAIR_U64");
+    if (n == 0 || n_rows == 0) { HIP_TRY(hipStreamSynchronize(s)); return PQPS_OK; }
+    const uint64_t tiles = (n + 63) / 64, m = tiles + 1;        // heads[tiles] receives the number of runs
+    const uint32_t scan_blocks = (uint32_t)((m + pqps_sort::kScanBlock - 1) / pqps_sort::kScanBlock);
+    const uint32_t fields = val == PAIR_COUNT ? 2u : 5u;        // keys, counts [, sums, min images, max images]
+    pqps_sort::Workspace w;
+    uint64_t *ka = nullptr, *kb = nullptr, *out = nullptr;
+    uint32_t *ra = nullptr, *rb = nullptr, *heads = nullptr, *sums = nullptr;
+    hipError_t e = pqps_sort::workspace_alloc(w, n);
+    if (e == hipSuccess) e = hipMalloc((void **)&ka, n * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&kb, n * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&ra, n * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&rb, n * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&heads, m * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&sums, (size_t)scan_blocks * 4);
+    const dim3 grid(list_grid(ctx, n, 8));
+    const uint64_t *keys = nullptr;
+    const uint32_t *rows = nullptr;
+    uint32_t runs = 0;
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(pair_keys_kernel, grid, dim3(kBlock), 0, s, a_col->data, awl, b_col->data, bwl, ids, n, id_base, n_rows, a_base, b_base,
+                           n_a, n_b, ka, ra);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+        bool in_a = true;
+        e = pqps_sort::sort_pairs<uint64_t, false>(w, ka, ra, kb, rb, n, 64, ctx->compute_units, s, &in_a);
+        keys = in_a ? ka : kb;
+        rows = in_a ? ra : rb;
+    }
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(pair_heads_kernel, dim3(list_grid(ctx, m * 64, 8)), dim3(kBlock), 0, s, keys, n, tiles, heads);
+        hipLaunchKernelGGL(pqps_sort::scan_sums_kernel, dim3(scan_blocks), dim3(pqps_sort::kThreads), 0, s, (const uint32_t *)heads, m, sums);
+        hipLaunchKernelGGL(pqps_sort::scan_top_kernel, dim3(1), dim3(pqps_sort::kThreads), 0, s, sums, scan_blocks);
+        hipLaunchKernelGGL(pqps_sort::scan_apply_kernel, dim3(scan_blocks), dim3(pqps_sort::kThreads), 0, s, heads, m, (const uint32_t *)sums);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(&runs, heads + tiles, sizeof runs, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+    }
+    if (e == hipSuccess && runs) {
+        e = hipMalloc((void **)&out, (size_t)fields * runs * 8);
+        if (e == hipSuccess) e = hipMemsetAsync(out, 0, (size_t)fields * runs * 8, s);
+        if (e == hipSuccess && val != PAIR_COUNT) e = hipMemsetAsync(out + 3 * (size_t)runs, 0xFF, (size_t)runs * 8, s);
+        if (e == hipSuccess) {
+            typedef void (*runs_fn)(const uint64_t *, const uint32_t *, uint64_t, uint64_t, const uint32_t *, const void *, uint64_t, uint64_t *);
+            static const runs_fn fns[3] = {pair_runs_kernel<PAIR_COUNT>, pair_runs_kernel<PAIR_I32>, pair_runs_kernel<PAIR_U64>};
+            hipLaunchKernelGGL(fns[val], dim3(list_grid(ctx, n, 4)), dim3(kBlock), 0, s, keys, rows, n, tiles, (const uint32_t *)heads,
+                               value_col ? value_col->data : nullptr, (uint64_t)runs, out);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+    }
+    (void)hipFree(ka); (void)hipFree(kb); (void)hipFree(ra); (void)hipFree(rb); (void)hipFree(heads); (void)hipFree(sums);
+    pqps_sort::workspace_free(w);
+    if (e != hipSuccess) {
+        if (out) (void)hipFree(out);
+        return fail(PQPS_EHIP, "GROUP BY pair sort: %s", hipGetErrorString(e));
+    }
+    *runs_dev = out;
+    *n_runs = runs;
     return PQPS_OK;
 }
 

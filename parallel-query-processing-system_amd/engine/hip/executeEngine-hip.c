@@ -815,27 +815,27 @@ static int group_column_id(const char *what, const char *column) {
     return c;
 }
 
-/* Binds the WHERE into q (plan and index probes) and decides the bins of group column c (-1: none): codes of a dictionary
- * (none for a single-valued column: every row is bin 0), 0 / 1, or the i32 range.  `column`: its name, `what`: the query's,
- * for the messages. */
-static int group_plan_init(struct engineS *engine, struct whereClauseS *whereClause, struct query *q, int c, const char *column,
-                           const char *what, struct group_plan *gp) {
-    struct hipTable *t = q->t;
-    memset(gp, 0, sizeof *gp);
-    gp->c = c;
-    gp->kind = c >= 0 ? k_group_kind[c] : -1;
-    gp->n_bins = 1;
-    int rc = bind_where(t, whereClause, &q->plan);
+/* Binds the WHERE into q: the plan and the index probes. */
+static int query_bind(struct engineS *engine, struct whereClauseS *whereClause, struct query *q) {
+    int rc = bind_where(q->t, whereClause, &q->plan);
     q->have_plan = rc == 0;
     if (rc == 0) {
-        q->n_probes = list_probes(engine, t, whereClause, &q->probes);
+        q->n_probes = list_probes(engine, q->t, whereClause, &q->probes);
         if (q->n_probes < 0) { q->n_probes = 0; rc = -1; }
     }
+    return rc;
+}
+
+/* The bins of group column c (-1: none) of a bound query: codes of a dictionary (none for a single-valued column: every row
+ * is bin 0), 0 / 1, or the i32 range.  `column`: its name, `what`: the query's, for the messages. */
+static int group_plan_bins(struct query *q, int c, const char *column, const char *what, struct group_plan *gp) {
+    struct hipTable *t = q->t;
+    int rc = 0;
     int32_t hi = -1;
     uint64_t rows = 0;
     for (int s = 0; s < q->n_shards; s++) rows += hipTableShard(t, s)->n_rows;
-    if (rc == 0 && rows == 0) gp->empty = true;                          /* an empty table: no groups */
-    else if (rc == 0 && c >= 0) {
+    if (rows == 0) gp->empty = true;                                     /* an empty table: no groups */
+    else if (c >= 0) {
         if (gp->kind == HIPKIND_DICT) {
             gp->n_bins = t->dict[c].count > 0 ? (uint32_t)t->dict[c].count : 1u;
             gp->single = t->col[c].width == 0;
@@ -853,12 +853,29 @@ static int group_plan_init(struct engineS *engine, struct whereClauseS *whereCla
             }
         }
     }
+    return rc;
+}
+
+/* The plan of group column c (-1: none) of a query whose WHERE is bound (`bound` == 0; otherwise only the fields that need
+ * no table are set, and `bound` is returned): its bins, whether the query is fused, and every shard's group column. */
+static int group_plan_column(struct query *q, int bound, int c, const char *column, const char *what, struct group_plan *gp) {
+    memset(gp, 0, sizeof *gp);
+    gp->c = c;
+    gp->kind = c >= 0 ? k_group_kind[c] : -1;
+    gp->n_bins = 1;
+    const int rc = bound == 0 ? group_plan_bins(q, c, column, what, gp) : bound;
     gp->fused = q->plan.n_passes == 1 && q->n_probes == 0;
     for (int s = 0; s < q->n_shards && c >= 0; s++) {
-        const struct hipTable *sh = hipTableShard(t, s);
+        const struct hipTable *sh = hipTableShard(q->t, s);
         gp->gcol[s] = gp->fused && c == HIPCOL_SUDO_USED && sh->sudo_bits.data ? sh->sudo_bits : sh->col[c];
     }
     return rc;
+}
+
+/* Binds the WHERE into q (query_bind) and decides the bins of group column c (group_plan_column). */
+static int group_plan_init(struct engineS *engine, struct whereClauseS *whereClause, struct query *q, int c, const char *column,
+                           const char *what, struct group_plan *gp) {
+    return group_plan_column(q, query_bind(engine, whereClause, q), c, column, what, gp);
 }
 
 /* One shard's result added into the host accumulators: COUNT (vc < 0) u32 bins into acc[0 .. n_bins); an aggregate the
@@ -1350,6 +1367,244 @@ void freeDistinctResultHIP(struct hipDistinctResult *res) {
     if (!res) return;
     free_group_keys(res->keys, res->keyText, res->numGroups);
     free(res->distinct);
+    free(res);
+}
+
+/* ---- GROUP BY two columns (include/executeEngine-hip.h) ------------------------------------------------------------- */
+
+/* The pairs of an answer, ascending by key = bin of A << 32 | bin of B: counts, and with a value column sums and the min /
+ * max images of pqps_filter_aggregate. */
+struct pair_rows { uint64_t n; uint64_t *key, *cnt, *sum, *mn, *mx; };
+
+static void pair_rows_free(struct pair_rows *pr) {
+    free(pr->key); free(pr->cnt); free(pr->sum); free(pr->mn); free(pr->mx);
+    memset(pr, 0, sizeof *pr);
+}
+
+static int pair_rows_alloc(struct pair_rows *pr, uint64_t n, bool valued) {
+    memset(pr, 0, sizeof *pr);
+    pr->key = calloc((size_t)n + 1, sizeof *pr->key);
+    pr->cnt = calloc((size_t)n + 1, sizeof *pr->cnt);
+    if (valued) {
+        pr->sum = calloc((size_t)n + 1, sizeof *pr->sum);
+        pr->mn = calloc((size_t)n + 1, sizeof *pr->mn);
+        pr->mx = calloc((size_t)n + 1, sizeof *pr->mx);
+    }
+    if (pr->key && pr->cnt && (!valued || (pr->sum && pr->mn && pr->mx))) return 0;
+    fprintf(stderr, "HIP engine: out of memory\n");
+    pair_rows_free(pr);
+    return -1;
+}
+
+/* Dense bins (acc: D counts, or the [4][D] fields of group_combine) into pairs: bin k is the pair (k / n_b, k % n_b). */
+static int pair_rows_from_bins(const uint64_t *acc, uint32_t D, uint32_t n_b, bool valued, struct pair_rows *pr) {
+    uint64_t n = 0;
+    for (uint32_t k = 0; k < D; k++) n += acc[k] != 0;
+    if (pair_rows_alloc(pr, n, valued) != 0) return -1;
+    for (uint32_t k = 0; k < D; k++) {
+        if (!acc[k]) continue;
+        const uint64_t g = pr->n++;
+        pr->key[g] = (uint64_t)(k / n_b) << 32 | (k % n_b);
+        pr->cnt[g] = acc[k];
+        if (valued) { pr->sum[g] = acc[D + k]; pr->mn[g] = acc[2 * (size_t)D + k]; pr->mx[g] = acc[3 * (size_t)D + k]; }
+    }
+    return 0;
+}
+
+struct pair_call { const struct group_plan *a, *b; int vc; void **out_dev; };
+
+static int pair_fused_call(struct query *q, int s, pqps_ctx *ctx, void *stream, void *arg) {
+    const struct pair_call *p = arg;
+    const struct hipTable *sh = hipTableShard(q->t, s);
+    const struct shard_pred *sp = &q->sp[s];
+    const int rc = pqps_filter_group_pair(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, &p->a->gcol[s], p->a->bin_base, p->a->n_bins,
+                                          &p->b->gcol[s], p->b->bin_base, p->b->n_bins, p->vc >= 0 ? &sh->col[p->vc] : NULL, p->out_dev[s], stream);
+    return rc == PQPS_OK ? 0 : engine_error("group pair filter");
+}
+
+/* The dense bins (D = n_a x n_b <= 65 536) of the query on every shard, combined on the host as group_bins does: one fused
+ * launch per shard (pqps_filter_group_pair), or the selection and pqps_group_pair_list over every shard's list. */
+static int pair_dense(struct query *q, const struct group_plan *a, const struct group_plan *b, int vc, uint64_t *acc) {
+    const uint32_t D = a->n_bins * b->n_bins;
+    const size_t bytes = vc < 0 ? (size_t)D * sizeof(uint32_t) : (size_t)D * 4 * sizeof(uint64_t);
+    void *out_dev[HIP_MAX_SHARDS] = { NULL };
+    void *host = malloc(bytes);
+    int rc = host ? 0 : -1;
+    if (!host) fprintf(stderr, "HIP engine: out of memory\n");
+    for (int s = 0; s < q->n_shards && rc == 0; s++)
+        if (pqps_malloc(hipTableShard(q->t, s)->ctx, bytes, &out_dev[s]) != PQPS_OK) rc = engine_error("bins allocation");
+    if (rc == 0 && a->fused) {
+        rc = fused_issue(q, pair_fused_call, &(struct pair_call){ a, b, vc, out_dev });
+        for (int s = 0; s < q->n_shards && rc == 0; s++)
+            if (hipTableShard(q->t, s)->n_rows == 0) continue;
+            else if (pqps_download(lane_copy_ctx(q, s), host, out_dev[s], bytes, NULL) != PQPS_OK) rc = engine_error("bins download");
+            else group_combine(acc, host, D, vc);
+    } else if (rc == 0) {
+        rc = query_lists(q);
+        for (int s = 0; s < q->n_shards && rc == 0; s++) {
+            struct hipTable *sh = hipTableShard(q->t, s);
+            struct hipLane *L = query_lane(q, s);
+            pqps_ctx *cs = lane_copy_ctx(q, s);
+            if (q->count[s] == 0) continue;
+            if (pqps_group_pair_list(cs, &sh->col[a->c], a->bin_base, a->n_bins, &sh->col[b->c], b->bin_base, b->n_bins,
+                                     vc >= 0 ? &sh->col[vc] : NULL, sh->n_rows, L->ids_dev, L->count_dev, q->count[s], (uint32_t)sh->row0,
+                                     out_dev[s], NULL) != PQPS_OK ||
+                pqps_download(cs, host, out_dev[s], bytes, NULL) != PQPS_OK)
+                rc = engine_error("group pair list");
+            else group_combine(acc, host, D, vc);
+        }
+    }
+    for (int s = 0; s < q->n_shards; s++) if (out_dev[s]) pqps_free(hipTableShard(q->t, s)->ctx, out_dev[s]);
+    free(host);
+    return rc;
+}
+
+/* The sparse form: the selection, every shard's list sorted and reduced to its runs on its device (pqps_group_pair_sort),
+ * the compact runs downloaded and merged by key on the host: counts and sums added, min / max images taken. */
+static int pair_sparse(struct query *q, const struct group_plan *a, const struct group_plan *b, int vc, struct pair_rows *pr) {
+    const bool valued = vc >= 0;
+    const size_t fields = valued ? 5 : 2;
+    uint64_t *host[HIP_MAX_SHARDS] = { NULL };
+    uint64_t runs[HIP_MAX_SHARDS] = { 0 }, at[HIP_MAX_SHARDS] = { 0 }, all = 0;
+    memset(pr, 0, sizeof *pr);
+    int rc = query_lists(q);
+    for (int s = 0; s < q->n_shards && rc == 0; s++) {
+        struct hipTable *sh = hipTableShard(q->t, s);
+        pqps_ctx *cs = lane_copy_ctx(q, s);
+        uint64_t *runs_dev = NULL;
+        if (q->count[s] == 0) continue;
+        if (pqps_group_pair_sort(cs, &sh->col[a->c], a->bin_base, a->n_bins, &sh->col[b->c], b->bin_base, b->n_bins, valued ? &sh->col[vc] : NULL,
+                                 sh->n_rows, query_lane(q, s)->ids_dev, q->count[s], (uint32_t)sh->row0, &runs_dev, &runs[s], NULL) != PQPS_OK)
+            rc = engine_error("group pair sort");
+        else if (runs[s] && !(host[s] = malloc(fields * (size_t)runs[s] * 8))) { fprintf(stderr, "HIP engine: out of memory\n"); rc = -1; }
+        else if (runs[s] && pqps_download(cs, host[s], runs_dev, fields * (size_t)runs[s] * 8, NULL) != PQPS_OK) rc = engine_error("group pair download");
+        if (runs_dev) pqps_free(sh->ctx, runs_dev);
+        all += runs[s];
+    }
+    if (rc == 0) rc = pair_rows_alloc(pr, all, valued);
+    while (rc == 0) {                                                    /* k-way merge by key */
+        int best = -1;
+        for (int s = 0; s < q->n_shards; s++)
+            if (at[s] < runs[s] && (best < 0 || host[s][at[s]] < host[best][at[best]])) best = s;
+        if (best < 0) break;
+        const uint64_t *h = host[best], r = runs[best], i = at[best]++;
+        uint64_t g = pr->n;
+        if (g && pr->key[g - 1] == h[i]) g--;                            /* the pair of another shard's run */
+        else { pr->n++; pr->key[g] = h[i]; if (valued) pr->mn[g] = UINT64_MAX; }
+        pr->cnt[g] += h[r + i];
+        if (valued) {
+            pr->sum[g] += h[2 * r + i];
+            if (h[3 * r + i] < pr->mn[g]) pr->mn[g] = h[3 * r + i];
+            if (h[4 * r + i] > pr->mx[g]) pr->mx[g] = h[4 * r + i];
+        }
+    }
+    for (int s = 0; s < q->n_shards; s++) free(host[s]);
+    return rc;
+}
+
+static int pair_result_fill(struct hipGroupPairResult *res, const struct hipTable *t, const struct group_plan *gp[2], const struct pair_rows *pr) {
+    const size_t n = (size_t)pr->n;
+    const bool valued = res->valueColumn >= 0;
+    for (int j = 0; j < 2; j++) {
+        res->keys[j] = calloc(n + 1, sizeof **res->keys);
+        res->keyText[j] = calloc(n + 1, sizeof **res->keyText);
+    }
+    res->counts = calloc(n + 1, sizeof *res->counts);
+    if (valued) {
+        res->sums = calloc(n + 1, sizeof *res->sums);
+        res->mins = calloc(n + 1, sizeof *res->mins);
+        res->maxs = calloc(n + 1, sizeof *res->maxs);
+    }
+    if (!res->keys[0] || !res->keys[1] || !res->keyText[0] || !res->keyText[1] || !res->counts ||
+        (valued && (!res->sums || !res->mins || !res->maxs))) { fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
+    const uint64_t flip = res->valueKind == HIPKIND_I32 ? 0x8000000000000000ull : 0;
+    for (size_t g = 0; g < n; g++) {
+        const uint32_t bin[2] = { (uint32_t)(pr->key[g] >> 32), (uint32_t)pr->key[g] };
+        res->numGroups = (int)g + 1;                                     /* (what freeGroupPairResultHIP frees) */
+        for (int j = 0; j < 2; j++) {
+            char buf[32];
+            res->keyText[j][g] = strdup(group_key(t, gp[j]->c, gp[j]->kind, bin[j], gp[j]->lo, &res->keys[j][g], buf, sizeof buf));
+            if (!res->keyText[j][g]) { fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
+        }
+        res->counts[g] = pr->cnt[g];
+        res->total += (long long)pr->cnt[g];
+        if (valued) {
+            res->sums[g] = (long long)pr->sum[g];
+            res->mins[g] = (long long)(pr->mn[g] ^ flip);
+            res->maxs[g] = (long long)(pr->mx[g] ^ flip);
+        }
+    }
+    return 0;
+}
+
+struct hipGroupPairResult *executeQueryGroupPairHIP(struct engineS *engine, const char *groupColumnA, const char *groupColumnB,
+                                                    const char *valueColumn, struct whereClauseS *whereClause) {
+    const double t0 = now_seconds();
+    struct hipGroupPairResult *res = calloc(1, sizeof *res);
+    if (!res) { fprintf(stderr, "HIP engine: out of memory\n"); return NULL; }
+    res->groupColumn[0] = res->groupColumn[1] = res->groupKind[0] = res->groupKind[1] = res->valueColumn = res->valueKind = -1;
+    if (!engine || !engine->record_block || !groupColumnA || !groupColumnB) { fprintf(stderr, "HIP engine: GROUP BY pair without an engine or two columns\n"); return res; }
+    const char *names[2] = { groupColumnA, groupColumnB };
+    int c[2], v = -1;
+    for (int j = 0; j < 2; j++) if ((c[j] = group_column_id("GROUP BY pair", names[j])) < 0) return res;
+    if (valueColumn) {
+        v = hipColumnId(valueColumn);
+        if (v < 0) { fprintf(stderr, "HIP engine: GROUP BY pair: unknown value column '%s'\n", valueColumn); return res; }
+        if (k_group_kind[v] != HIPKIND_I32 && k_group_kind[v] != HIPKIND_U64) {
+            fprintf(stderr, "HIP engine: GROUP BY pair: %s is a %s column, not a number\n", valueColumn, k_group_kind[v] == HIPKIND_BOOL ? "boolean" : "dictionary");
+            return res;
+        }
+    }
+    struct hipTable *t = engine->record_block;
+    if (t->xch) { fprintf(stderr, "HIP engine: GROUP BY pair is not exchanged across ranks\n"); return res; }
+    for (int j = 0; j < 2; j++) { res->groupColumn[j] = c[j]; res->groupKind[j] = k_group_kind[c[j]]; }
+    res->valueColumn = v;
+    res->valueKind = v >= 0 ? k_group_kind[v] : -1;
+    struct query q;
+    if (!query_open(engine, &q)) return res;                             /* reason on stderr */
+    struct group_plan gp[2], none;
+    struct pair_rows pr;
+    memset(&pr, 0, sizeof pr);
+    int rc = query_bind(engine, whereClause, &q);                        /* the WHERE is bound once */
+    for (int j = 0; j < 2; j++) {
+        const int r = group_plan_column(&q, rc, c[j], names[j], "GROUP BY pair", &gp[j]);
+        if (rc == 0) rc = r;
+    }
+    if (rc == 0 && !gp[0].empty && !gp[1].empty) {
+        /* a single-valued column contributes its one key to every pair: the query runs as the one-column form on the other
+         * column (as one group when both are single-valued), through the one-column code */
+        const struct group_plan *one = gp[0].single && gp[1].single ? NULL : gp[0].single ? &gp[1] : gp[1].single ? &gp[0] : NULL;
+        const bool reduced = gp[0].single || gp[1].single;
+        const uint64_t D = reduced ? (one ? one->n_bins : 1u) : (uint64_t)gp[0].n_bins * gp[1].n_bins;   /* 64 bits: 65 536 x 65 536 = 2^32 */
+        if (!reduced && D > HIP_GROUP_MAX_BINS) rc = pair_sparse(&q, &gp[0], &gp[1], v, &pr);
+        else {
+            uint64_t *acc = calloc((size_t)(v < 0 ? 1 : 4) * D, sizeof *acc);
+            if (!acc) { fprintf(stderr, "HIP engine: out of memory\n"); rc = -1; }
+            else if (v >= 0) for (uint64_t k = 0; k < D; k++) acc[2 * D + k] = UINT64_MAX;
+            if (rc == 0 && !reduced) rc = pair_dense(&q, &gp[0], &gp[1], v, acc);
+            else if (rc == 0) {
+                if (!one) { (void)group_plan_column(&q, 0, -1, NULL, "GROUP BY pair", &none); one = &none; }
+                rc = v < 0 ? group_counts(&q, one, acc) : group_bins(&q, one, v, acc);
+            }
+            /* bin k of a reduced query: (0, k) where A is the single-valued one, (k, 0) otherwise */
+            if (rc == 0) rc = pair_rows_from_bins(acc, (uint32_t)D, !reduced ? gp[1].n_bins : gp[0].single ? (uint32_t)D : 1u, v >= 0, &pr);
+            free(acc);
+        }
+    }
+    if (rc == 0 && pair_result_fill(res, t, (const struct group_plan *[2]){ &gp[0], &gp[1] }, &pr) == 0) res->success = true;
+    pair_rows_free(&pr);
+    query_close(&q);
+    res->queryTime = now_seconds() - t0;
+    return res;
+}
+
+void freeGroupPairResultHIP(struct hipGroupPairResult *res) {
+    if (!res) return;
+    for (int j = 0; j < 2; j++) free_group_keys(res->keys[j], res->keyText[j], res->numGroups);
+    free(res->counts);
+    free(res->sums);
+    free(res->mins);
+    free(res->maxs);
     free(res);
 }
 
