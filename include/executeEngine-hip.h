@@ -128,6 +128,24 @@ struct engineS *initializeEngineSyntheticHIP(unsigned long long num_rows, unsign
                                              int num_indexes, const char *indexed_attributes[], const int attribute_types[],
                                              const char *tableName);
 
+/* ---- set predicates in WHERE: LIKE and IN --------------------------------------------------------------------------
+ * Beyond the reference's six comparisons a `struct whereClauseS` node may carry one of four operators, written exactly
+ * so: "LIKE", "NOT LIKE", "IN", "NOT IN".  They are reached through this API only (the reference's tokenizer and
+ * connectEngine never produce them); any other unknown operator stays "never true".
+ *   LIKE / NOT LIKE   string columns.  `value` is the pattern: `%` any run of bytes (none included), `_` exactly one byte,
+ *                     `\%` `\_` `\\` literals, a backslash anywhere else itself; byte-wise, case-sensitive, the whole
+ *                     string has to match.  On a numeric or boolean column the WHERE is refused.
+ *   IN / NOT IN       any column.  `value` is `( item, item, ... )`: a single-quoted string ('' = a quote inside it) or a
+ *                     bare token trimmed of white space, each typed by the column exactly as the literal of `=` is.
+ *                     `()` is legal (IN: never true).  Duplicates and strings no row carries are harmless.  Refused: no
+ *                     parentheses, an unterminated quote, an empty item, more than 65 536 items.
+ * A refused WHERE fails like any WHERE that cannot be compiled (message on stderr, the query reports failure).  Set
+ * conditions are never index probes: in index mode they are part of the re-filter of the probed rows.  A set of up to four
+ * runs of values costs nothing extra (it is window comparisons of the one fused scan, and crosses ranks like any other);
+ * a more fragmented one is a pass of its own in front of the scan (include/hipPredicate.h), which every query form and
+ * DELETE take in their stride -- the aggregates by their selection-then-list route -- and which an engine joined across
+ * ranks refuses, as it refuses every WHERE of several passes. */
+
 /* ---- asynchronous queries: several in flight, results left on the device -----------------------------------------
  * The engine's table has LANES (default 4, PQPS_ENGINE_LANES): result buffers + a slot of the table's query stream
  * (pqps_qstream: two launches in flight on two HIP streams, one for tables of 537 M rows and more).  Every SELECT /

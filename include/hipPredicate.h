@@ -58,14 +58,44 @@ int hipCompileWhere(const struct hipSchema *schema, const struct whereClauseS *w
 struct hipPass {
     pqps_predicate pred;
     int column_ids[PQPS_MAX_COLUMNS];
+    /* a member pass (see below) instead of a filter pass: pred and column_ids are unused */
+    int member;                  /* 0: filter pass, 1: member pass                              */
+    int member_column;           /* HIPCOL_* id of the table column it reads                    */
+    int member_form;             /* PQPS_MEMBER_BITMAP / PQPS_MEMBER_LIST                       */
+    uint32_t member_base;        /* bitmap: bit i stands for the value member_base + i (mod 2^32) */
+    uint64_t member_bits;        /* bitmap: number of bits                                      */
+    uint32_t *member_bitmap;     /* (member_bits + 31) / 32 words, LSB first; malloc'd          */
+    uint64_t *member_list;       /* list: ascending, duplicate-free values; malloc'd            */
+    uint32_t member_count;       /* list: number of values                                      */
 };
 struct hipPlan {
     int n_passes;
     struct hipPass *pass;        /* malloc'd; hipPlanFree */
 };
+/* SET PREDICATES.  Four operators beyond the reference's six: "LIKE", "NOT LIKE" (string columns; `%` any run of bytes,
+ * `_` one byte, `\%` `\_` `\\` literals, byte-wise, the whole string) and "IN", "NOT IN" (any column; value = a
+ * parenthesised list of single-quoted strings or bare tokens, each typed by the column as the literal of `=` is).  The host
+ * decides them once per distinct value -- on the dictionary of a string column -- into sorted runs of codes / values:
+ *   no run, or the whole domain: a constant;
+ *   up to PQPS_MEMBER_MAX_RUNS runs (else: so many runs of the complement within the column's domain): that many window
+ *     leaves, an OR ladder (an AND ladder of negated windows for the NOT form / the complement) -- `a IN (x, y)` compiles
+ *     to the very predicate of `a = x OR a = y`;
+ *   anything more fragmented: a MEMBER PASS of the plan, numbered like the other passes and in front of them, which
+ *     pqps_member_flags evaluates into the flag column PQPS_MAX_COLUMNS + pass; the node itself is the leaf `flags = 1`
+ *     (negated for the NOT form).  Dictionary codes and bool: a bitmap over [first, last] selected code; an i32 column: a
+ *     bitmap over [min, max] of the list when that is at most PQPS_MEMBER_MAX_BITS values, else the sorted list of u32 bit
+ *     patterns; command_id: the sorted list.
+ * LIKE on a numeric or boolean column and a malformed IN list (no parentheses, an unterminated quote, an empty item, more
+ * than PQPS_MEMBER_MAX_ITEMS items) fail the compile.  hipCompileWhere fails for a WHERE that needs a member pass. */
+#define PQPS_MEMBER_MAX_RUNS  4
+#define PQPS_MEMBER_MAX_ITEMS 65536
+#define PQPS_MEMBER_MAX_BITS  (1ull << 27)
 int hipCompileWherePlan(const struct hipSchema *schema, const struct whereClauseS *where,
                         struct hipPlan *plan, char *err, size_t errlen);
 void hipPlanFree(struct hipPlan *plan);
+
+/* 1 for "LIKE", "NOT LIKE", "IN", "NOT IN" (exactly so written), else 0. */
+int hipIsSetOperator(const char *op);
 
 /* Column name -> HIPCOL_* id, -1 if unknown. */
 int hipColumnId(const char *name);

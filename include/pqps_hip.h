@@ -32,6 +32,7 @@
  *                       equal-size slots (index mode across processes).
  *   pqps_compact_rows   the survivor compaction of DELETE (executeEngine-serial.c:646-680).
  *   pqps_bump_codes     (no counterpart: keeps dictionary codes order-preserving on INSERT).
+ *   pqps_member_flags   (no counterpart: LIKE / IN as a set of dictionary codes or values).
  *
  * All functions return 0 on success or a negative PQPS_E* code; the text of
  * the last error of the calling thread is at pqps_last_error().
@@ -169,6 +170,26 @@ int pqps_bump_codes(pqps_ctx *ctx, void *codes, uint32_t width, uint64_t n_rows,
  * for r < n_rows and 0 past it.  Reads bytes[r] for r < n_rows only.  `plane` 16-byte aligned.  Asynchronous on `stream`. */
 int pqps_pack_bits(pqps_ctx *ctx, const uint8_t *bytes, uint64_t n_rows, uint8_t *plane, uint64_t first_byte, uint64_t plane_bytes,
                    void *stream);
+
+/* Set membership of one column, row by row (the member pass of a WHERE with LIKE / IN: include/hipPredicate.h).  `col` 1, 2,
+ * 4 or 8 bytes wide; a bit plane, or an 8-byte column with the bitmap form, is PQPS_EINVAL.
+ *   PQPS_MEMBER_BITMAP: idx = value - base in 32-bit arithmetic; the row is a member iff idx < n_bits and bit idx of
+ *     bitmap_dev (u32 words, LSB first; n_bits <= 2^32) is set.  A bitmap of up to PQPS_MEMBER_LDS_BITS bits is staged into
+ *     LDS by every workgroup, a larger one is read from global memory (it stays in L2).
+ *   PQPS_MEMBER_LIST: the row is a member iff its value, zero-extended to u64, is in list_dev[0 .. n_list), ascending and
+ *     duplicate-free (binary search).  An i32 column takes part as its u32 bit pattern.
+ * OUTPUT.  PQPS_MEMBER_BYTES: out[r] = 0 / 1 for r < n_rows, as pqps_filter_flags writes; PQPS_MEMBER_PLANE: a
+ * PQPS_WIDTH_BITS plane as pqps_pack_bits writes, bytes [0, n_rows rounded up to PQPS_STEP_ROWS, / 8), the bits of rows at
+ * and past n_rows 0.  `out` 16-byte aligned.  *out_count (device, may be NULL) = the member rows.  `col` is read up to n_rows
+ * rounded up to PQPS_STEP_ROWS, as a scan reads it.  n_rows == 0 launches nothing (count 0).  Asynchronous on `stream`. */
+#define PQPS_MEMBER_BITMAP 0
+#define PQPS_MEMBER_LIST   1
+#define PQPS_MEMBER_BYTES  0
+#define PQPS_MEMBER_PLANE  1
+#define PQPS_MEMBER_LDS_BITS (1u << 18)   /* 32 KiB of LDS per workgroup: five workgroups fit a CU's 160 KiB */
+int pqps_member_flags(pqps_ctx *ctx, const pqps_column *col, uint64_t n_rows, int form, uint32_t base, uint64_t n_bits,
+                      const uint32_t *bitmap_dev, const uint64_t *list_dev, uint32_t n_list, int out_form, void *out,
+                      uint64_t *out_count, void *stream);
 
 /* Scan mode.  Evaluates `pred` on rows [0, n_rows) of `cols` and writes the
  * matching row IDs (row + id_base, u32) in ASCENDING row order to out_ids and

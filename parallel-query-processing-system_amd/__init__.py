@@ -33,6 +33,10 @@ SLOT_HEADER_WORDS = 4
 ACCEPT, REJECT = 0xFE, 0xFF
 WIDTH_BITS = 0x81                  # pqps_column.width of a bit plane (PQPS_WIDTH_BITS)
 HIPKIND_U64, HIPKIND_I32, HIPKIND_BOOL, HIPKIND_DICT = 0, 1, 2, 3     # include/hipPredicate.h
+MEMBER_BITMAP, MEMBER_LIST = 0, 1  # pqps_member_flags: lookup form ...
+MEMBER_BYTES, MEMBER_PLANE = 0, 1  # ... and output form
+MEMBER_LDS_BITS = 1 << 18          # a bitmap of up to this many bits is staged into LDS
+MEMBER_MAX_RUNS, MEMBER_MAX_ITEMS = 4, 65536
 SYNTH_USERS = 2000
 
 COLUMNS = ["command_id", "raw_command", "base_command", "shell_type", "exit_code", "timestamp",
@@ -188,7 +192,10 @@ class Predicate(C.Structure):
 
 class Pass(C.Structure):
     """struct hipPass (include/hipPredicate.h)."""
-    _fields_ = [("pred", Predicate), ("column_ids", C.c_int * MAX_COLUMNS)]
+    _fields_ = [("pred", Predicate), ("column_ids", C.c_int * MAX_COLUMNS),
+                ("member", C.c_int), ("member_column", C.c_int), ("member_form", C.c_int), ("member_base", C.c_uint32),
+                ("member_bits", C.c_uint64), ("member_bitmap", C.POINTER(C.c_uint32)), ("member_list", C.POINTER(C.c_uint64)),
+                ("member_count", C.c_uint32)]
 
 
 class Plan(C.Structure):
@@ -214,6 +221,7 @@ class Schema(C.Structure):
 
 
 assert C.sizeof(Record) == 1040 and C.sizeof(WhereClause) == 56
+assert C.sizeof(Predicate) == 880 and C.sizeof(Pass) == 976          # struct hipPass: a smaller mirror would be overwritten
 assert C.sizeof(ResultSet) == 48 and C.sizeof(EngineS) == 72
 
 
@@ -258,6 +266,23 @@ class WhereList:
     @property
     def ptr(self):
         return C.byref(self.head) if self.head is not None else None
+
+
+def in_list(values) -> str:
+    """The value text of `IN` / `NOT IN` for `values` (str, bytes as latin-1, int or bool): every item single-quoted,
+    a quote inside it doubled -- ("a", "it's") -> "('a', 'it''s')"."""
+    def text(v):
+        if isinstance(v, bytes):
+            v = v.decode("latin-1")
+        elif isinstance(v, bool):
+            v = "true" if v else "false"
+        return "'" + str(v).replace("'", "''") + "'"
+    return "(" + ", ".join(text(v) for v in values) + ")"
+
+
+def like_escape(text: str) -> str:
+    """`text` as a LIKE pattern that matches itself: `%`, `_` and the backslash escaped."""
+    return text.replace("\\", "\\\\").replace("%", "\\%").replace("_", "\\_")
 
 
 # ---- library --------------------------------------------------------------------------
@@ -333,6 +358,8 @@ def lib():
     L.pqps_synth_generate_host.restype = None
     L.pqps_bump_codes.argtypes = [vp, vp, u32, u64, u32, vp]
     L.pqps_pack_bits.argtypes = [vp, vp, u64, vp, u64, u64, vp]
+    L.pqps_member_flags.argtypes = [vp, C.POINTER(Column), u64, C.c_int, u32, u64, vp, vp, u32, C.c_int, vp, vp, vp]
+    L.hipIsSetOperator.argtypes = [C.c_char_p]
     L.pqps_compact_rows.argtypes = [vp, C.POINTER(Column), u32, u64, vp, C.POINTER(u64), vp]
     L.pqps_project_column.argtypes = [vp, C.POINTER(Column), vp, vp, u64, u32, vp, vp]
     L.pqps_gather_keys.argtypes = [vp, C.POINTER(Column), C.c_int, vp, vp, u64, u32, vp, vp]
@@ -540,9 +567,11 @@ class SchemaSpec:
         return self
 
 
-def compile_plan(spec: SchemaSpec, chain):
-    """-> [(Predicate, [column id per slot]), ...]: the passes of hipCompileWherePlan.  A column id >= MAX_COLUMNS
-    names the flags of pass (id - MAX_COLUMNS); the last pass is the query's result."""
+def compile_plan_sets(spec: SchemaSpec, chain):
+    """-> [(Predicate, [column id per slot], member), ...]: the passes of hipCompileWherePlan.  A column id >= MAX_COLUMNS
+    names the flags of pass (id - MAX_COLUMNS); the last pass is the query's result.  `member` is None for a filter pass;
+    for a member pass (a LIKE / IN set, include/hipPredicate.h; its Predicate is empty) it is a dict: "column" (id), "form"
+    (MEMBER_BITMAP / MEMBER_LIST), "base", "n_bits", "words" (the bitmap's u32 words) and "values" (the sorted list)."""
     wl = WhereList(chain)
     plan = Plan()
     err = C.create_string_buffer(200)
@@ -551,11 +580,23 @@ def compile_plan(spec: SchemaSpec, chain):
         raise PqpsError("hipCompileWherePlan: " + err.value.decode())
     out = []
     for k in range(plan.n_passes):
+        p = plan.passes[k]
         pred = Predicate()
-        C.memmove(C.byref(pred), C.byref(plan.passes[k].pred), C.sizeof(Predicate))
-        out.append((pred, list(plan.passes[k].column_ids[:pred.n_columns])))
+        C.memmove(C.byref(pred), C.byref(p.pred), C.sizeof(Predicate))
+        member = None
+        if p.member:
+            bitmap = p.member_form == MEMBER_BITMAP
+            member = dict(column=p.member_column, form=p.member_form, base=p.member_base, n_bits=p.member_bits,
+                          words=list(p.member_bitmap[:(p.member_bits + 31) // 32]) if bitmap else [],
+                          values=[] if bitmap else list(p.member_list[:p.member_count]))
+        out.append((pred, list(p.column_ids[:pred.n_columns]), member))
     lib().hipPlanFree(C.byref(plan))
     return out
+
+
+def compile_plan(spec: SchemaSpec, chain):
+    """-> [(Predicate, [column id per slot]), ...]: compile_plan_sets without the member descriptions."""
+    return [(pred, ids) for pred, ids, _ in compile_plan_sets(spec, chain)]
 
 
 def compile_where(spec: SchemaSpec, chain):

@@ -23,6 +23,7 @@
 #include "pqps_hip.h"
 #include "filter_kernels.hpp"
 #include "fused_common.hpp"
+#include "member_kernels.hpp"
 #include "group_kernels.hpp"
 #include "aggregate_kernels.hpp"
 #include "topk_kernels.hpp"
@@ -1714,6 +1715,41 @@ int pqps_pack_bits(pqps_ctx *ctx, const uint8_t *bytes, uint64_t n_rows, uint8_t
     const uint64_t want = (plane_bytes - first_byte + 255) / 256;
     const uint32_t blocks = (uint32_t)(want < 8192 ? want : 8192);
     hipLaunchKernelGGL(pack_bits_kernel, dim3(blocks), dim3(256), 0, s, bytes, n_rows, plane, first_byte, plane_bytes);
+    HIP_TRY(hipGetLastError());
+    return PQPS_OK;
+}
+
+int pqps_member_flags(pqps_ctx *ctx, const pqps_column *col, uint64_t n_rows, int form, uint32_t base, uint64_t n_bits,
+                      const uint32_t *bitmap_dev, const uint64_t *list_dev, uint32_t n_list, int out_form, void *out,
+                      uint64_t *out_count, void *stream) {
+    if (!ctx || !col || !out || (!col->data && n_rows)) return fail(PQPS_EINVAL, "NULL argument");
+    const uint32_t w = col->width;
+    if (w != 1 && w != 2 && w != 4 && w != 8) return fail(PQPS_EINVAL, "member column width %u not in {1,2,4,8}", w);
+    if (form != PQPS_MEMBER_BITMAP && form != PQPS_MEMBER_LIST) return fail(PQPS_EINVAL, "member form %d", form);
+    if (out_form != PQPS_MEMBER_BYTES && out_form != PQPS_MEMBER_PLANE) return fail(PQPS_EINVAL, "member output form %d", out_form);
+    if (form == PQPS_MEMBER_BITMAP) {
+        if (w == 8) return fail(PQPS_EINVAL, "an 8-byte column takes the list form");
+        if (!bitmap_dev || n_bits == 0 || n_bits > (1ull << 32)) return fail(PQPS_EINVAL, "bitmap of %llu bits", (unsigned long long)n_bits);
+    } else if (!list_dev && n_list) return fail(PQPS_EINVAL, "NULL list");
+    if ((((uintptr_t)col->data | (uintptr_t)out) & 15u) != 0) return fail(PQPS_EINVAL, "column / output not 16-byte aligned");
+    hipStream_t s = pick_stream(ctx, stream);
+    if (out_count) HIP_TRY(hipMemsetAsync(out_count, 0, sizeof(uint64_t), s));
+    if (n_rows == 0) return PQPS_OK;
+    const bool plane = out_form == PQPS_MEMBER_PLANE;
+    MemberArgs a;
+    a.col = (const char *)col->data;
+    a.n_rows = n_rows;
+    a.octets = plane ? (n_rows + PQPS_STEP_ROWS - 1) / PQPS_STEP_ROWS * (PQPS_STEP_ROWS / 8) : (n_rows + 7) / 8;
+    a.base = base; a.n_bits = n_bits; a.bitmap = bitmap_dev; a.list = list_dev; a.n_list = n_list;
+    a.out = (uint8_t *)out;
+    a.count = (unsigned long long *)out_count;
+    const bool lds = form == PQPS_MEMBER_BITMAP && n_bits <= PQPS_MEMBER_LDS_BITS;
+    /* a persistent grid: every workgroup of the LDS form stages the bitmap once */
+    const uint64_t want = (a.octets + kMemberBlock - 1) / kMemberBlock, cap = (uint64_t)ctx->compute_units * (lds ? 4u : 8u);
+    const uint32_t blocks = (uint32_t)(want < cap ? want : cap);
+    if (form == PQPS_MEMBER_LIST) member_launch_width<MEMBER_LIST>(w, plane, blocks, s, a);
+    else if (lds) member_launch_width<MEMBER_LDS>(w, plane, blocks, s, a);
+    else member_launch_width<MEMBER_GLOBAL>(w, plane, blocks, s, a);
     HIP_TRY(hipGetLastError());
     return PQPS_OK;
 }

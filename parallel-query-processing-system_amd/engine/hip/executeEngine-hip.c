@@ -66,29 +66,105 @@ struct shard_pred {
     pqps_column cols[PQPS_MAX_COLUMNS];
     uint32_t n_cols;
     uint8_t **flags;                 /* n_passes - 1 device buffers (NULL for a single pass) */
+    void **member;                   /* ... and the bitmap or list of each member pass among them, on the device */
+    bool *plane;                     /* ... flags[k] is a bit plane (a member pass all of whose readers are scans) */
     int n_flags;
 };
 
 static void shard_pred_free(struct hipTable *sh, struct shard_pred *sp) {
-    for (int k = 0; k < sp->n_flags; k++) if (sp->flags[k]) pqps_free(sh->ctx, sp->flags[k]);
+    for (int k = 0; k < sp->n_flags; k++) {
+        if (sp->flags[k]) pqps_free(sh->ctx, sp->flags[k]);
+        if (sp->member[k]) pqps_free(sh->ctx, sp->member[k]);
+    }
     free(sp->flags);
+    free(sp->member);
+    free(sp->plane);
     sp->flags = NULL;
+    sp->member = NULL;
+    sp->plane = NULL;
     sp->n_flags = 0;
 }
 
-/* `scan`: the columns go to a scan (pqps_filter_scan / _count / _flags, query stream, exchange), which reads sudo_used from
- * its bit plane -- where the plane is the pass's last column (the width-specialised kernels' shapes: widths non-increasing,
- * the plane last) or the pass takes the generic kernel anyway (more than 3 columns or more than 6 comparisons).  A lone
- * bool column keeps its bytes: its scan time is all output, not input.  Index-mode gathers always get the byte column. */
-static void pass_columns(const struct hipTable *sh, const struct hipPass *pass, uint8_t *const *flags, bool scan, pqps_column *cols) {
+/* Where a scan reads a 0 / 1 column from a bit plane: the plane is the pass's last column (the width-specialised kernels'
+ * shapes: widths non-increasing, the plane last) or the pass takes the generic kernel anyway (more than 3 columns or more
+ * than 6 comparisons).  A lone bool column keeps its bytes: its scan time is all output, not input. */
+static bool plane_slot(const struct hipPass *pass, uint32_t i) {
     const uint32_t n = pass->pred.n_columns;
     const bool generic = n > 3 || pass->pred.n_leaves > PQPS_TT_LEAVES;
+    return n > 1 && (i == n - 1 || generic);
+}
+
+/* `scan`: the columns go to a scan (pqps_filter_scan / _count / _flags, query stream, exchange), which reads sudo_used from
+ * its bit plane where plane_slot allows.  Index-mode gathers always get the byte column.  `sp`: the shard's flag buffers
+ * (NULL for a plan of one pass); the flags of a member pass are a plane where head_pass wrote one. */
+static void pass_columns(const struct hipTable *sh, const struct hipPass *pass, const struct shard_pred *sp, bool scan, pqps_column *cols) {
+    const uint32_t n = pass->pred.n_columns;
     for (uint32_t i = 0; i < n; i++) {
         const int id = pass->column_ids[i];
-        if (id >= PQPS_MAX_COLUMNS) { cols[i].data = flags[id - PQPS_MAX_COLUMNS]; cols[i].width = 1; }
-        else if (scan && id == HIPCOL_SUDO_USED && sh->sudo_bits.data && n > 1 && (i == n - 1 || generic)) cols[i] = sh->sudo_bits;
+        if (id >= PQPS_MAX_COLUMNS) {
+            cols[i].data = sp->flags[id - PQPS_MAX_COLUMNS];
+            cols[i].width = sp->plane[id - PQPS_MAX_COLUMNS] ? PQPS_WIDTH_BITS : 1;
+            cols[i].reserved = 0;
+        }
+        else if (scan && id == HIPCOL_SUDO_USED && sh->sudo_bits.data && plane_slot(pass, i)) cols[i] = sh->sudo_bits;
         else cols[i] = sh->col[id];
     }
+}
+
+/* A member pass writes a plane when every reader of its flag column is a scan that takes a plane in that slot
+ * (`scan_last`: the plan's last pass is a scan, not index-mode gathers). */
+static bool member_writes_plane(const struct hipPlan *plan, int k, bool scan_last) {
+    bool read = false;
+    for (int j = k + 1; j < plan->n_passes; j++) {
+        const struct hipPass *p = &plan->pass[j];
+        for (uint32_t i = 0; !p->member && i < p->pred.n_columns; i++) {
+            if (p->column_ids[i] != PQPS_MAX_COLUMNS + k) continue;
+            if (!(j < plan->n_passes - 1 || scan_last) || !plane_slot(p, i)) return false;
+            read = true;
+        }
+    }
+    return read;
+}
+
+/* The passes in front of the last on one shard, on (ctx, stream): each leaves one flag per row -- a filter pass through
+ * pqps_filter_flags, a member pass (a LIKE / IN set as a bitmap or list, uploaded here, owned by `sp`) through
+ * pqps_member_flags.  `count_dev`: a device word for the counts nobody reads. */
+static int head_passes(const struct hipPlan *plan, struct hipTable *sh, struct shard_pred *sp, pqps_ctx *ctx, void *stream,
+                       uint64_t *count_dev, bool scan_last) {
+    if (plan->n_passes < 2) return 0;
+    const size_t n = (size_t)plan->n_passes - 1;
+    sp->flags = calloc(n, sizeof *sp->flags);
+    sp->member = calloc(n, sizeof *sp->member);
+    sp->plane = calloc(n, sizeof *sp->plane);
+    if (!sp->flags || !sp->member || !sp->plane) {
+        free(sp->flags); free(sp->member); free(sp->plane);
+        sp->flags = NULL; sp->member = NULL; sp->plane = NULL;
+        fprintf(stderr, "HIP engine: out of memory\n");
+        return -1;
+    }
+    sp->n_flags = (int)n;
+    for (int k = 0; k < sp->n_flags; k++) {
+        const struct hipPass *pass = &plan->pass[k];
+        TRY(pqps_malloc(sh->ctx, sh->capacity_rows, (void **)&sp->flags[k]), "flag allocation");
+        if (!pass->member) {
+            pqps_column cols[PQPS_MAX_COLUMNS];
+            pass_columns(sh, pass, sp, true, cols);
+            TRY(pqps_filter_flags(ctx, cols, pass->pred.n_columns, sh->n_rows, &pass->pred, sp->flags[k], count_dev, stream), "flag filter");
+            continue;
+        }
+        const bool bitmap = pass->member_form == PQPS_MEMBER_BITMAP;
+        const void *host = bitmap ? (const void *)pass->member_bitmap : (const void *)pass->member_list;
+        const size_t bytes = bitmap ? (size_t)((pass->member_bits + 31) / 32) * sizeof(uint32_t) : (size_t)pass->member_count * sizeof(uint64_t);
+        if (bytes) {
+            TRY(pqps_malloc(sh->ctx, bytes, &sp->member[k]), "member set allocation");
+            TRY(pqps_upload(ctx, sp->member[k], host, bytes, stream), "member set upload");
+        }
+        sp->plane[k] = member_writes_plane(plan, k, scan_last);
+        TRY(pqps_member_flags(ctx, &sh->col[pass->member_column], sh->n_rows, pass->member_form, pass->member_base, pass->member_bits,
+                              bitmap ? sp->member[k] : NULL, bitmap ? NULL : sp->member[k], pass->member_count,
+                              sp->plane[k] ? PQPS_MEMBER_PLANE : PQPS_MEMBER_BYTES, sp->flags[k], count_dev, stream), "member flags");
+    }
+    return 0;
 }
 
 /* Inclusive key window of an indexed top-level condition, S:377-424.
@@ -140,6 +216,7 @@ static int list_probes(struct engineS *engine, const struct hipTable *t, struct 
     struct probe *pr = NULL;
     for (struct whereClauseS *wc = where; wc; wc = wc->next) {
         if (wc->attribute == NULL) continue;                           /* nested node, S:361-364 */
+        if (hipIsSetOperator(wc->operator)) continue;                  /* LIKE / IN: never a probe, part of the re-filter */
         for (int i = 0; i < engine->num_indexes; i++) {
             if (strcmp(wc->attribute, engine->indexed_attributes[i]) != 0) continue;
             const struct hipIndex *ix = &t->index[i];
@@ -237,22 +314,12 @@ static int issue_calls(struct query *q, int s, pqps_ctx *ctx, void *stream) {
     struct shard_pred *sp = &q->sp[s];
     const struct hipPlan *plan = &q->plan;
     const struct hipPass *last = &plan->pass[plan->n_passes - 1];
-    /* the passes before the last: one byte of flags per row each */
-    if (plan->n_passes > 1) {
-        sp->flags = calloc((size_t)plan->n_passes - 1, sizeof *sp->flags);
-        if (!sp->flags) { fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
-        sp->n_flags = plan->n_passes - 1;
-        for (int k = 0; k < sp->n_flags; k++) {
-            pqps_column cols[PQPS_MAX_COLUMNS];
-            TRY(pqps_malloc(sh->ctx, sh->capacity_rows, (void **)&sp->flags[k]), "flag allocation");
-            pass_columns(sh, &plan->pass[k], sp->flags, true, cols);
-            TRY(pqps_filter_flags(ctx, cols, plan->pass[k].pred.n_columns, sh->n_rows, &plan->pass[k].pred,
-                                  sp->flags[k], L->count_dev + 4, stream), "flag filter");
-        }
-    }
+    /* the passes before the last: one flag per row each */
+    const bool scan_last = q->count_only || q->n_probes == 0;
+    if (head_passes(plan, sh, sp, ctx, stream, L->count_dev + 4, scan_last) != 0) return -1;
     sp->pred = &last->pred;
     sp->n_cols = last->pred.n_columns;
-    pass_columns(sh, last, sp->flags, q->count_only || q->n_probes == 0, sp->cols);
+    pass_columns(sh, last, sp, scan_last, sp->cols);
     if (q->count_only) {
         TRY(pqps_filter_count(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, L->count_dev, stream), "count filter");
     } else if (q->n_probes > 0) {
@@ -2662,21 +2729,11 @@ static int delete_flags(struct engineS *engine, struct hipTable *t, struct where
         struct shard_pred *sp = &q.sp[s];
         memset(sp, 0, sizeof *sp);
         const struct hipPass *last = &head.pass[head.n_passes - 1];
-        if (head.n_passes > 1) {
-            sp->flags = calloc((size_t)head.n_passes - 1, sizeof *sp->flags);
-            if (!sp->flags) { rc = -1; break; }
-            sp->n_flags = head.n_passes - 1;
-            for (int k = 0; k < sp->n_flags && rc == 0; k++) {
-                pqps_column cols[PQPS_MAX_COLUMNS];
-                if (pqps_malloc(sh->ctx, sh->capacity_rows, (void **)&sp->flags[k]) != PQPS_OK) { rc = engine_error("flag allocation"); break; }
-                pass_columns(sh, &head.pass[k], sp->flags, true, cols);
-                if (pqps_filter_flags(sh->ctx, cols, head.pass[k].pred.n_columns, sh->n_rows, &head.pass[k].pred, sp->flags[k], sh->own.count_dev + 4, NULL) != PQPS_OK)
-                    rc = engine_error("flag filter");
-            }
-        }
+        rc = head_passes(&head, sh, sp, sh->ctx, NULL, sh->own.count_dev + 4, true);
+        if (rc != 0) break;
         sp->pred = &last->pred;
         sp->n_cols = last->pred.n_columns;
-        pass_columns(sh, last, sp->flags, true, sp->cols);
+        pass_columns(sh, last, sp, true, sp->cols);
         if (rc == 0 && pqps_malloc(sh->ctx, sh->capacity_rows, (void **)&flags_dev[s]) != PQPS_OK) rc = engine_error("flag allocation");
         if (rc == 0 && pqps_filter_flags(sh->ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, flags_dev[s], sh->own.count_dev, NULL) != PQPS_OK)
             rc = engine_error("flag filter");

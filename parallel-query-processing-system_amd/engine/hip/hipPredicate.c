@@ -122,13 +122,360 @@ static const struct hipColumnInfo *col_info(const struct hipSchema *schema, int 
 #define FLAG_MARK 0x7F1A6
 static _Thread_local int flag_passes;
 
+struct set_node;
+static const struct set_node *find_set(const struct whereClauseS *c);
+static int set_node_column(const struct set_node *sn);
+static int set_node_leaves(const struct set_node *sn);
+
+/* The column a leaf node reads: a table column, or the flags of an earlier pass -- for a flag leaf of the planner, and for
+ * a set node that became a member pass. */
 static int node_column(const struct whereClauseS *c) {
     if (c->attribute && c->attribute[0] == FLAG_ATTRIBUTE) {
         const int pass = atoi(c->attribute + 1);
         return c->value_type == FLAG_MARK && pass >= 0 && pass < flag_passes ? PQPS_MAX_COLUMNS + pass : -1;
     }
+    const struct set_node *sn = find_set(c);
+    if (sn) return set_node_column(sn);
     return hipColumnId(c->attribute);
 }
+
+/* comparisons a leaf node compiles to: a set node of several runs is that many window leaves */
+static int node_leaves(const struct whereClauseS *c) {
+    const struct set_node *sn = find_set(c);
+    return sn ? set_node_leaves(sn) : 1;
+}
+
+
+/* ---- set predicates: LIKE / NOT LIKE / IN / NOT IN (no counterpart in the reference) -------------------------------
+ * A set node is decided on the host, once per distinct value of its column, BEFORE leaves are counted and passes are
+ * planned: resolve_sets leaves one entry per node in a side table, the sorted runs of codes / values the node selects.
+ * A set of few runs becomes that many ordinary window leaves, anything more fragmented a member pass of the plan whose
+ * flags the node reads as the leaf `flags = 1` (include/hipPredicate.h). */
+enum { SET_LIKE = 0, SET_NOT_LIKE = 1, SET_IN = 2, SET_NOT_IN = 3 };
+static int set_op_code(const char *op) {
+    if (!op) return -1;
+    if (strcmp(op, "LIKE") == 0) return SET_LIKE;
+    if (strcmp(op, "NOT LIKE") == 0) return SET_NOT_LIKE;
+    if (strcmp(op, "IN") == 0) return SET_IN;
+    if (strcmp(op, "NOT IN") == 0) return SET_NOT_IN;
+    return -1;
+}
+
+int hipIsSetOperator(const char *op) { return set_op_code(op) >= 0; }
+
+enum { SM_FALSE = 0, SM_TRUE = 1, SM_WINDOWS = 2, SM_MEMBER = 3, SM_ABSENT = 4 };
+struct set_node {
+    const char *attribute, *operator, *value;   /* the node's identity: what a copy of the node keeps (fit_chain copies) */
+    int col, mode;
+    int negate;                                  /* windows: every leaf negated (an AND ladder); member: the flag leaf negated */
+    int n_runs;
+    uint64_t lo[PQPS_MEMBER_MAX_RUNS], span[PQPS_MEMBER_MAX_RUNS];
+    int pass;                                    /* SM_MEMBER: the pass that leaves the flags, -1 until it is emitted */
+    int form;
+    uint32_t base;
+    uint64_t n_bits;
+    uint32_t *bitmap;
+    uint64_t *list;
+    uint32_t n_list;
+};
+struct set_table { struct set_node *node; int n, cap; };
+static _Thread_local const struct set_table *sets;   /* the table of the compile running on this thread */
+
+static const struct set_node *find_set(const struct whereClauseS *c) {
+    if (!sets || c->sub) return NULL;
+    for (int i = 0; i < sets->n; i++) {
+        const struct set_node *sn = &sets->node[i];
+        if (sn->attribute == c->attribute && sn->operator == c->operator && sn->value == c->value) return sn;
+    }
+    return NULL;
+}
+
+static void set_table_free(struct set_table *T) {
+    for (int i = 0; i < T->n; i++) { free(T->node[i].bitmap); free(T->node[i].list); }
+    free(T->node);
+    memset(T, 0, sizeof *T);
+}
+
+static int set_fail(char *err, size_t errlen, const char *attribute, const char *what) {
+    if (err) snprintf(err, errlen, "%s: %s", attribute, what);
+    return -1;
+}
+
+static int is_blank(char c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r'; }
+
+/* `( item, item, ... )` -> malloc'd strings.  An item is a single-quoted string ('' is a quote inside it) or a bare
+ * token with the white space around it trimmed. */
+static int parse_in_list(const char *attribute, const char *value, char ***items_out, int *n_out, char *err, size_t errlen) {
+    *items_out = NULL; *n_out = 0;
+    const char *q = value, *e = value + strlen(value);
+    while (q < e && is_blank(*q)) q++;
+    while (e > q && is_blank(e[-1])) e--;
+    if (e - q < 2 || *q != '(' || e[-1] != ')') return set_fail(err, errlen, attribute, "IN needs a parenthesised list");
+    q++; e--;
+    char **items = NULL;
+    int n = 0, cap = 0, rc = 0;
+    char *buf = malloc((size_t)(e - q) + 1);
+    if (!buf) return set_fail(err, errlen, attribute, "out of memory");
+    while (q < e && is_blank(*q)) q++;
+    while (q < e) {                                                    /* (an interior of blanks only: the empty list) */
+        size_t len = 0;
+        while (q < e && is_blank(*q)) q++;
+        if (q < e && *q == '\'') {
+            q++;
+            for (;;) {
+                if (q >= e) { rc = set_fail(err, errlen, attribute, "unterminated quote in IN list"); break; }
+                if (*q == '\'') { if (q + 1 < e && q[1] == '\'') { buf[len++] = '\''; q += 2; continue; } q++; break; }
+                buf[len++] = *q++;
+            }
+            if (rc) break;
+            while (q < e && is_blank(*q)) q++;
+            if (q < e && *q != ',') { rc = set_fail(err, errlen, attribute, "malformed IN list"); break; }
+        } else {
+            const char *start = q;
+            while (q < e && *q != ',') q++;
+            const char *stop = q;
+            while (stop > start && is_blank(stop[-1])) stop--;
+            if (stop == start) { rc = set_fail(err, errlen, attribute, "empty item in IN list"); break; }
+            len = (size_t)(stop - start);
+            memcpy(buf, start, len);
+        }
+        if (n == PQPS_MEMBER_MAX_ITEMS) { rc = set_fail(err, errlen, attribute, "IN list has more than 65536 items"); break; }
+        if (n == cap) {
+            cap = cap ? 2 * cap : 16;
+            char **grown = realloc(items, (size_t)cap * sizeof *grown);
+            if (!grown) { rc = set_fail(err, errlen, attribute, "out of memory"); break; }
+            items = grown;
+        }
+        items[n] = malloc(len + 1);
+        if (!items[n]) { rc = set_fail(err, errlen, attribute, "out of memory"); break; }
+        memcpy(items[n], buf, len);
+        items[n++][len] = '\0';
+        if (q == e) break;
+        q++;                                                          /* the comma: another item has to follow */
+        if (q == e) { rc = set_fail(err, errlen, attribute, "empty item in IN list"); break; }
+    }
+    free(buf);
+    if (rc) { for (int i = 0; i < n; i++) free(items[i]); free(items); return rc; }
+    *items_out = items; *n_out = n;
+    return 0;
+}
+
+/* LIKE pattern as tokens: kind 0 = the literal byte lit[i], 1 = `_`, 2 = `%`.  `\%`, `\_` and `\\` are literals; a
+ * backslash in front of anything else, or at the end, is itself a literal backslash. */
+static int like_tokens(const char *pat, uint8_t *kind, unsigned char *lit) {
+    int m = 0;
+    for (const unsigned char *p = (const unsigned char *)pat; *p; p++) {
+        if (*p == '\\' && (p[1] == '%' || p[1] == '_' || p[1] == '\\')) { kind[m] = 0; lit[m++] = *++p; }
+        else if (*p == '%') { kind[m] = 2; lit[m++] = 0; }
+        else if (*p == '_') { kind[m] = 1; lit[m++] = 0; }
+        else { kind[m] = 0; lit[m++] = *p; }
+    }
+    return m;
+}
+
+/* whole-string match, byte-wise; `%` backtracks to the latest one only (enough for this grammar) */
+static int like_match(const unsigned char *s, const uint8_t *kind, const unsigned char *lit, int m) {
+    int i = 0, star = -1;
+    const unsigned char *resume = NULL;
+    while (*s) {
+        if (i < m && (kind[i] == 1 || (kind[i] == 0 && lit[i] == *s))) { i++; s++; }
+        else if (i < m && kind[i] == 2) { star = i++; resume = s; }
+        else if (star >= 0) { i = star + 1; s = ++resume; }
+        else return 0;
+    }
+    while (i < m && kind[i] == 2) i++;
+    return i == m;
+}
+
+struct runs { uint64_t *lo, *hi; size_t n, cap; };               /* ascending, disjoint, not adjacent; inclusive ends */
+static int runs_add(struct runs *r, uint64_t v) {                 /* values arrive ascending (duplicates allowed) */
+    if (r->n && (r->hi[r->n - 1] == v || r->hi[r->n - 1] + 1 == v)) { r->hi[r->n - 1] = v; return 0; }
+    if (r->n == r->cap) {
+        const size_t cap = r->cap ? 2 * r->cap : 16;
+        uint64_t *lo = realloc(r->lo, cap * sizeof *lo);
+        if (lo) r->lo = lo;
+        uint64_t *hi = realloc(r->hi, cap * sizeof *hi);
+        if (hi) r->hi = hi;
+        if (!lo || !hi) return -1;
+        r->cap = cap;
+    }
+    r->lo[r->n] = v; r->hi[r->n++] = v;
+    return 0;
+}
+
+static int cmp_u64(const void *a, const void *b) {
+    const uint64_t x = *(const uint64_t *)a, y = *(const uint64_t *)b;
+    return x < y ? -1 : x > y;
+}
+
+/* rank of the first dictionary entry whose first `len` bytes are >= (upper == 0) or > (upper != 0) `prefix` */
+static int prefix_bound(const struct hipColumnInfo *ci, const unsigned char *prefix, size_t len, int upper) {
+    int l = 0, r = ci->dict_count;
+    while (l < r) {
+        const int m = l + (r - l) / 2;
+        const int c = strncmp(ci->dict[m], (const char *)prefix, len);
+        if (upper ? c <= 0 : c < 0) l = m + 1; else r = m;
+    }
+    return l;
+}
+
+/* Marks the codes a LIKE pattern selects.  The literal bytes in front of the first wildcard give a code window (the codes
+ * are order-preserving: the strings with that prefix are neighbours); only its strings are matched, and none at all when
+ * nothing but `%` follows the literal. */
+static int like_marks(const struct hipColumnInfo *ci, const char *pattern, uint8_t *mark) {
+    const size_t plen = strlen(pattern);
+    uint8_t *kind = malloc(plen + 1);
+    unsigned char *lit = malloc(plen + 1);
+    if (!kind || !lit) { free(kind); free(lit); return -1; }
+    const int m = like_tokens(pattern, kind, lit);
+    int prefix = 0, rest_any = 1;
+    while (prefix < m && kind[prefix] == 0) prefix++;
+    for (int i = prefix; i < m; i++) if (kind[i] != 2) rest_any = 0;
+    const int first = prefix_bound(ci, lit, (size_t)prefix, 0), end = prefix_bound(ci, lit, (size_t)prefix, 1);
+    for (int c = first; c < end; c++) {
+        if (prefix == m) mark[c] = strlen(ci->dict[c]) == (size_t)m;      /* no wildcard: the string itself */
+        else mark[c] = rest_any ? 1 : (uint8_t)like_match((const unsigned char *)ci->dict[c], kind, lit, m);
+    }
+    free(kind); free(lit);
+    return 0;
+}
+
+/* From the runs of the set S (keys in [0, dmax], an order-preserving image of the column's values; `unbias` turns a key
+ * back into the pattern the kernels compare) to the node's form.  The set's own runs are taken when they are at most
+ * PQPS_MEMBER_MAX_RUNS -- `a IN (x, y)` is then exactly `a = x OR a = y` -- else those of its complement in the domain. */
+static int set_from_runs(struct set_node *sn, const struct runs *S, uint64_t dmax, uint64_t unbias, int not_form, int kind) {
+    if (S->n == 0) { sn->mode = not_form ? SM_TRUE : SM_FALSE; return 0; }
+    if (S->n == 1 && S->lo[0] == 0 && S->hi[0] == dmax) { sn->mode = not_form ? SM_FALSE : SM_TRUE; return 0; }
+    const uint64_t mask = kind == HIPKIND_U64 ? UINT64_MAX : 0xFFFFFFFFull;
+    const int head = S->lo[0] != 0, tail = S->hi[S->n - 1] != dmax;
+    const size_t n_gaps = S->n - 1 + (size_t)head + (size_t)tail;
+    if (S->n <= PQPS_MEMBER_MAX_RUNS) {
+        sn->mode = SM_WINDOWS; sn->negate = not_form; sn->n_runs = (int)S->n;
+        for (size_t i = 0; i < S->n; i++) { sn->lo[i] = (S->lo[i] ^ unbias) & mask; sn->span[i] = S->hi[i] - S->lo[i]; }
+        return 0;
+    }
+    if (n_gaps <= PQPS_MEMBER_MAX_RUNS) {
+        sn->mode = SM_WINDOWS; sn->negate = !not_form; sn->n_runs = 0;
+        for (size_t i = 0; i <= S->n; i++) {
+            if ((i == 0 && !head) || (i == S->n && !tail)) continue;
+            const uint64_t lo = i == 0 ? 0 : S->hi[i - 1] + 1, hi = i == S->n ? dmax : S->lo[i] - 1;
+            sn->lo[sn->n_runs] = (lo ^ unbias) & mask; sn->span[sn->n_runs++] = hi - lo;
+        }
+        return 0;
+    }
+    sn->mode = SM_MEMBER; sn->negate = not_form; sn->pass = -1;
+    const uint64_t extent = S->hi[S->n - 1] - S->lo[0];                /* keys the bitmap would span, minus one */
+    if (kind != HIPKIND_U64 && extent < PQPS_MEMBER_MAX_BITS) {
+        sn->form = PQPS_MEMBER_BITMAP;
+        sn->base = (uint32_t)(S->lo[0] ^ unbias);
+        sn->n_bits = extent + 1;
+        sn->bitmap = calloc((size_t)((sn->n_bits + 31) / 32), sizeof *sn->bitmap);
+        if (!sn->bitmap) return -1;
+        for (size_t i = 0; i < S->n; i++)
+            for (uint64_t k = S->lo[i] - S->lo[0]; k <= S->hi[i] - S->lo[0]; k++) sn->bitmap[k >> 5] |= 1u << (k & 31);
+        return 0;
+    }
+    sn->form = PQPS_MEMBER_LIST;                                        /* (numeric columns only: at most PQPS_MEMBER_MAX_ITEMS values) */
+    size_t total = 0;
+    for (size_t i = 0; i < S->n; i++) total += (size_t)(S->hi[i] - S->lo[i]) + 1;
+    sn->list = malloc(total * sizeof *sn->list);
+    if (!sn->list) return -1;
+    sn->n_list = 0;
+    for (size_t i = 0; i < S->n; i++)
+        for (uint64_t k = S->lo[i]; ; k++) { sn->list[sn->n_list++] = (k ^ unbias) & mask; if (k == S->hi[i]) break; }
+    qsort(sn->list, sn->n_list, sizeof *sn->list, cmp_u64);             /* an i32 column: by its u32 bit pattern, as the kernel searches */
+    return 0;
+}
+
+static int resolve_one(const struct hipSchema *schema, const struct whereClauseS *c, int op, int col, struct set_node *sn,
+                       char *err, size_t errlen) {
+    const struct hipColumnInfo *ci = &schema->col[col];
+    const int not_form = op == SET_NOT_LIKE || op == SET_NOT_IN;
+    const int is_like = op == SET_LIKE || op == SET_NOT_LIKE;
+    /* typed by the column, as the literal of `=` is (make_leaf) */
+    const int kind = col == 0 ? HIPKIND_U64 : (col == 4 || col == 8 || col == 11) ? HIPKIND_I32 : col == 6 ? HIPKIND_BOOL : HIPKIND_DICT;
+    if (is_like && kind != HIPKIND_DICT) return set_fail(err, errlen, c->attribute, "LIKE needs a string column");
+    char **items = NULL;
+    int n_items = 0;
+    if (!is_like && parse_in_list(c->attribute, c->value, &items, &n_items, err, errlen) != 0) return -1;
+    struct runs S;
+    memset(&S, 0, sizeof S);
+    int rc = 0;
+    uint64_t dmax = 0, unbias = 0;
+    if (kind == HIPKIND_DICT) {
+        if (!(ci->present && ci->kind == HIPKIND_DICT)) sn->mode = SM_ABSENT;      /* reported as absent if it can be reached */
+        else {
+            uint8_t *mark = calloc((size_t)ci->dict_count + 1, 1);
+            if (!mark) rc = -1;
+            else if (is_like) rc = like_marks(ci, c->value, mark);
+            else for (int i = 0; i < n_items; i++) {
+                int l = 0, r = ci->dict_count;
+                while (l < r) { const int m = l + (r - l) / 2; if (strcmp(ci->dict[m], items[i]) < 0) l = m + 1; else r = m; }
+                if (l < ci->dict_count && strcmp(ci->dict[l], items[i]) == 0) mark[l] = 1;
+            }
+            for (int k = 0; rc == 0 && k < ci->dict_count; k++) if (mark[k]) rc = runs_add(&S, (uint64_t)k);
+            free(mark);
+            dmax = ci->dict_count > 0 ? (uint64_t)ci->dict_count - 1 : 0;
+        }
+    } else {
+        uint64_t *v = malloc(((size_t)n_items + 1) * sizeof *v);
+        if (!v) rc = -1;
+        else {
+            for (int i = 0; i < n_items; i++) {
+                if (kind == HIPKIND_U64) v[i] = strtoull(items[i], NULL, 10);
+                else if (kind == HIPKIND_I32) v[i] = (uint64_t)((uint32_t)atoi(items[i]) ^ 0x80000000u);
+                else v[i] = (strcasecmp(items[i], "true") == 0 || strcmp(items[i], "1") == 0);
+            }
+            qsort(v, (size_t)n_items, sizeof *v, cmp_u64);
+            for (int i = 0; rc == 0 && i < n_items; i++) rc = runs_add(&S, v[i]);
+            free(v);
+        }
+        dmax = kind == HIPKIND_U64 ? UINT64_MAX : kind == HIPKIND_I32 ? 0xFFFFFFFFull : 1;
+        unbias = kind == HIPKIND_I32 ? 0x80000000ull : 0;
+    }
+    if (rc == 0 && sn->mode != SM_ABSENT) rc = set_from_runs(sn, &S, dmax, unbias, not_form, kind);
+    if (rc == 0 && sn->mode == SM_MEMBER && !ci->present) {               /* no column for a pass to read */
+        free(sn->bitmap); free(sn->list);
+        sn->bitmap = NULL; sn->list = NULL;
+        sn->mode = SM_ABSENT;
+    }
+    for (int i = 0; i < n_items; i++) free(items[i]);
+    free(items); free(S.lo); free(S.hi);
+    if (rc != 0 && err && errlen && !err[0]) snprintf(err, errlen, "out of memory");
+    return rc;
+}
+
+/* One table entry per set node of the tree.  Fails (message in err) where the node cannot be compiled at all. */
+static int resolve_sets(const struct hipSchema *schema, const struct whereClauseS *wc, struct set_table *T, char *err, size_t errlen) {
+    for (; wc; wc = wc->next) {
+        if (wc->sub) { if (resolve_sets(schema, wc->sub, T, err, errlen) != 0) return -1; continue; }
+        const int op = set_op_code(wc->operator);
+        const int col = wc->attribute ? hipColumnId(wc->attribute) : -1;
+        if (op < 0 || col < 0 || wc->value == NULL) continue;             /* never true, like any unknown attribute */
+        int known = 0;
+        for (int i = 0; i < T->n; i++)
+            if (T->node[i].attribute == wc->attribute && T->node[i].operator == wc->operator && T->node[i].value == wc->value) known = 1;
+        if (known) continue;
+        if (T->n == T->cap) {
+            const int cap = T->cap ? 2 * T->cap : 8;
+            struct set_node *grown = realloc(T->node, (size_t)cap * sizeof *grown);
+            if (!grown) { if (err) snprintf(err, errlen, "out of memory"); return -1; }
+            T->node = grown; T->cap = cap;
+        }
+        struct set_node *sn = &T->node[T->n];
+        memset(sn, 0, sizeof *sn);
+        sn->attribute = wc->attribute; sn->operator = wc->operator; sn->value = wc->value;
+        sn->col = col; sn->pass = -1;
+        T->n++;                                                            /* (set_table_free releases what a failed node holds) */
+        if (resolve_one(schema, wc, op, col, sn, err, errlen) != 0) return -1;
+    }
+    return 0;
+}
+
+static int set_node_column(const struct set_node *sn) {
+    return sn->mode == SM_MEMBER ? (sn->pass >= 0 ? PQPS_MAX_COLUMNS + sn->pass : -1) : sn->col;
+}
+static int set_node_leaves(const struct set_node *sn) { return sn->mode == SM_WINDOWS ? sn->n_runs : 1; }
 
 struct builder {
     const struct hipSchema *schema;
@@ -141,7 +488,7 @@ struct builder {
 
 static int count_leaves(const struct whereClauseS *wc) {
     int n = 0;
-    for (; wc; wc = wc->next) n += wc->sub ? count_leaves(wc->sub) : 1;
+    for (; wc; wc = wc->next) n += wc->sub ? count_leaves(wc->sub) : node_leaves(wc);
     return n;
 }
 
@@ -150,6 +497,18 @@ static void make_leaf(struct builder *b, struct step *s, const struct whereClaus
     s->kind = ST_FALSE;
     s->col = -1;
     const int col = node_column(c);
+    const struct set_node *sn = find_set(c);
+    if (sn) {                                                    /* a set node that is one step: decided, or the flags of its member pass */
+        if (sn->mode == SM_FALSE || col < 0) return;
+        if (sn->mode == SM_TRUE) { s->kind = ST_TRUE; return; }
+        s->kind = ST_LEAF; s->col = col; s->lo = 1; s->span = 0; s->neg = sn->negate;
+        if (sn->mode == SM_ABSENT) {
+            s->lo = 0; s->neg = 0;
+            b->failed = 1;
+            if (b->err) snprintf(b->err, b->errlen, "column '%s' is not materialised on the device", c->attribute);
+        }
+        return;
+    }
     const int op = op_code(c->operator);
     if (col < 0 || op < 0 || c->value == NULL) return;          /* S:212, S:279: never true */
     const struct hipColumnInfo *ci = col_info(b->schema, col);
@@ -187,15 +546,29 @@ static void make_leaf(struct builder *b, struct step *s, const struct whereClaus
  *   last          -> true: T,    false: F                                               */
 static void emit_chain(struct builder *b, const struct whereClauseS *wc, int start, int T, int F) {
     for (; wc; wc = wc->next) {
-        const int size = wc->sub ? count_leaves(wc->sub) : 1;
+        const int size = wc->sub ? count_leaves(wc->sub) : node_leaves(wc);
         const int next_start = start + size;
         int t = T, f = F;
         if (wc->next) {
             if (wc->logical_op && strcmp(wc->logical_op, "OR") == 0) f = next_start;
             else t = next_start;
         }
+        const struct set_node *sn = wc->sub ? NULL : find_set(wc);
         if (wc->sub) {
             emit_chain(b, wc->sub, start, t, f);
+        } else if (sn && sn->mode == SM_WINDOWS) {
+            /* the runs as window leaves at the node's own targets: an OR ladder, or an AND ladder of negated windows */
+            for (int i = 0; i < size; i++) {
+                struct step *s = &b->st[start + i];
+                const int more = i + 1 < size ? start + i + 1 : (sn->negate ? t : f);
+                s->kind = ST_LEAF; s->col = sn->col; s->lo = sn->lo[i]; s->span = sn->span[i]; s->neg = sn->negate;
+                s->t = sn->negate ? more : t;
+                s->f = sn->negate ? f : more;
+            }
+            if (!b->schema->col[sn->col].present) {
+                b->failed = 1;
+                if (b->err) snprintf(b->err, b->errlen, "column '%s' is not materialised on the device", wc->attribute);
+            }
         } else {
             struct step *s = &b->st[start];
             if (wc->attribute == NULL) { s->kind = ST_FALSE; s->col = -1; }   /* reference would crash; never true */
@@ -209,9 +582,9 @@ static void emit_chain(struct builder *b, const struct whereClauseS *wc, int sta
 
 static int cmp_int(const void *a, const void *b) { return *(const int *)a - *(const int *)b; }
 
-int hipCompileWhere(const struct hipSchema *schema, const struct whereClauseS *where,
-                    pqps_predicate *pred, int column_ids[PQPS_MAX_COLUMNS],
-                    char *err, size_t errlen) {
+static int compile_pass(const struct hipSchema *schema, const struct whereClauseS *where,
+                        pqps_predicate *pred, int column_ids[PQPS_MAX_COLUMNS],
+                        char *err, size_t errlen) {
     memset(pred, 0, sizeof *pred);
     if (err && errlen) err[0] = '\0';
     for (int i = 0; i < PQPS_MAX_COLUMNS; i++) column_ids[i] = -1;
@@ -332,6 +705,29 @@ int hipCompileWhere(const struct hipSchema *schema, const struct whereClauseS *w
     return 0;
 }
 
+int hipCompileWhere(const struct hipSchema *schema, const struct whereClauseS *where,
+                    pqps_predicate *pred, int column_ids[PQPS_MAX_COLUMNS],
+                    char *err, size_t errlen) {
+    struct set_table T;
+    memset(&T, 0, sizeof T);
+    memset(pred, 0, sizeof *pred);
+    if (err && errlen) err[0] = '\0';
+    for (int i = 0; i < PQPS_MAX_COLUMNS; i++) column_ids[i] = -1;
+    int rc = resolve_sets(schema, where, &T, err, errlen);
+    for (int i = 0; rc == 0 && i < T.n; i++)
+        if (T.node[i].mode == SM_MEMBER) {
+            if (err) snprintf(err, errlen, "%s: the set needs a member pass (hipCompileWherePlan)", T.node[i].attribute);
+            rc = -1;
+        }
+    if (rc == 0) {
+        sets = &T;
+        rc = compile_pass(schema, where, pred, column_ids, err, errlen);
+        sets = NULL;
+    }
+    set_table_free(&T);
+    return rc;
+}
+
 /* ---- multi-pass plans ----------------------------------------------------------------------------- */
 
 struct planner {
@@ -364,7 +760,7 @@ static void chain_columns(const struct whereClauseS *wc, uint32_t *table_mask, i
     }
 }
 
-static int element_leaves(const struct whereClauseS *e) { return e->sub ? count_leaves(e->sub) : 1; }
+static int element_leaves(const struct whereClauseS *e) { return e->sub ? count_leaves(e->sub) : node_leaves(e); }
 
 /* does [first, last] (elements of one array) fit one pass? */
 static int span_fits(const struct whereClauseS *first, const struct whereClauseS *last) {
@@ -382,17 +778,42 @@ static int span_fits(const struct whereClauseS *first, const struct whereClauseS
 }
 
 /* Compiles `chain` as the next pass; returns its number, -1 on failure. */
-static int emit_pass(struct planner *P, const struct whereClauseS *chain) {
+static struct hipPass *next_pass(struct planner *P) {
     struct hipPlan *plan = P->plan;
     if (plan->n_passes == P->capacity) {
         const int cap = P->capacity ? 2 * P->capacity : 4;
         struct hipPass *grown = realloc(plan->pass, (size_t)cap * sizeof *grown);
-        if (!grown) { if (P->err) snprintf(P->err, P->errlen, "out of memory"); return -1; }
+        if (!grown) { if (P->err) snprintf(P->err, P->errlen, "out of memory"); return NULL; }
         plan->pass = grown; P->capacity = cap;
     }
     struct hipPass *pass = &plan->pass[plan->n_passes];
+    memset(pass, 0, sizeof *pass);
+    return pass;
+}
+
+/* The member pass of a set node: takes the node's bitmap or list; the node reads its flags from now on. */
+static int emit_member(struct planner *P, struct set_node *sn) {
+    struct hipPass *pass = next_pass(P);
+    if (!pass) return -1;
+    for (int i = 0; i < PQPS_MAX_COLUMNS; i++) pass->column_ids[i] = -1;
+    pass->member = 1;
+    pass->member_column = sn->col;
+    pass->member_form = sn->form;
+    pass->member_base = sn->base;
+    pass->member_bits = sn->n_bits;
+    pass->member_bitmap = sn->bitmap; sn->bitmap = NULL;
+    pass->member_list = sn->list; sn->list = NULL;
+    pass->member_count = sn->n_list;
+    sn->pass = P->plan->n_passes;
+    return P->plan->n_passes++;
+}
+
+static int emit_pass(struct planner *P, const struct whereClauseS *chain) {
+    struct hipPlan *plan = P->plan;
+    struct hipPass *pass = next_pass(P);
+    if (!pass) return -1;
     flag_passes = plan->n_passes;                                  /* this pass may read the flags of the passes before it */
-    if (hipCompileWhere(P->schema, chain, &pass->pred, pass->column_ids, P->err, P->errlen) != 0) return -1;
+    if (compile_pass(P->schema, chain, &pass->pred, pass->column_ids, P->err, P->errlen) != 0) return -1;
     flag_passes = plan->n_passes + 1;                              /* the planner may now name this pass's flags */
     return plan->n_passes++;
 }
@@ -455,14 +876,28 @@ int hipCompileWherePlan(const struct hipSchema *schema, const struct whereClause
     struct planner P;
     memset(&P, 0, sizeof P);
     P.schema = schema; P.plan = plan; P.err = err; P.errlen = errlen;
-    /* one pass whenever the clause allows it (constant leaves are folded away first) */
-    flag_passes = 0;
-    if (count_leaves(where) <= MAX_RAW_STEPS && emit_pass(&P, where) == 0) return 0;
     if (err && errlen) err[0] = '\0';
-    plan->n_passes = 0;
-    struct whereClauseS *fitted = fit_chain(&P, where);
-    const int last = fitted ? emit_pass(&P, fitted) : -1;
+    /* set nodes first: what each selects, and a member pass for every set too fragmented for window leaves */
+    struct set_table T;
+    memset(&T, 0, sizeof T);
+    int last = resolve_sets(schema, where, &T, err, errlen);
+    sets = &T;
     flag_passes = 0;
+    for (int i = 0; last == 0 && i < T.n; i++)
+        if (T.node[i].mode == SM_MEMBER && emit_member(&P, &T.node[i]) < 0) last = -1;
+    const int n_member = plan->n_passes;
+    if (last == 0) {
+        /* one further pass whenever the clause allows it (constant leaves are folded away first) */
+        if (count_leaves(where) > MAX_RAW_STEPS || (last = emit_pass(&P, where)) < 0) {
+            if (err && errlen) err[0] = '\0';
+            plan->n_passes = n_member;
+            struct whereClauseS *fitted = fit_chain(&P, where);
+            last = fitted ? emit_pass(&P, fitted) : -1;
+        }
+    }
+    flag_passes = 0;
+    sets = NULL;
+    set_table_free(&T);
     for (int i = 0; i < P.n_arena; i++) free(P.arena[i]);
     free(P.arena);
     if (last < 0) { hipPlanFree(plan); return -1; }
@@ -471,6 +906,7 @@ int hipCompileWherePlan(const struct hipSchema *schema, const struct whereClause
 
 void hipPlanFree(struct hipPlan *plan) {
     if (!plan) return;
+    for (int k = 0; k < plan->n_passes; k++) { free(plan->pass[k].member_bitmap); free(plan->pass[k].member_list); }
     free(plan->pass);
     plan->pass = NULL;
     plan->n_passes = 0;
