@@ -159,6 +159,22 @@ bool appendRowDeviceTableHIP(struct engineS *engine, const record *r);
 /* DELETE: `delete_flags_dev[s]` (1 = row goes, from pqps_filter_flags on shard s) compacts that shard's
  * device columns in place; `expected_rows` = survivors counted on the host over all shards (cross-check). */
 void compactDeviceTableHIP(struct engineS *engine, uint8_t *const *delete_flags_dev, size_t expected_rows);
+/* UPDATE (executeQueryUpdateHIP), device side, in the order the engine calls them under the exclusive lock; `a` = the n
+ * assignments hipCompileAssignments made against the table's schema.
+ *   updateNeedsRebuildHIP       true when an assignment cannot be made in place: a string new to a dictionary that is full
+ *                               for its code width, or another value for a single-valued column without a buffer.
+ *   updateInsertStringsHIP      every string that is new goes into its dictionary at its rank, the codes at and above it are
+ *                               bumped on every shard (pqps_bump_codes, as INSERT); bit c of the result: column c was bumped.
+ *   updateTargetsHIP            the shard's targets of pqps_filter_assign / pqps_assign_flags (a single-valued column assigned
+ *                               its own value has none); returns their number.
+ *   finishUpdateDeviceTableHIP  matched[s] = rows shard s changed: repacks the sudo_used plane, widens the cached bounds of
+ *                               an i32 target, rebuilds the indexes on assigned columns (shards with a match) and on bumped
+ *                               columns (every shard). */
+struct hipAssignment;
+bool updateNeedsRebuildHIP(struct engineS *engine, const struct hipAssignment *a, int n);
+uint32_t updateInsertStringsHIP(struct engineS *engine, const struct hipAssignment *a, int n);
+int updateTargetsHIP(const struct hipTable *sh, const struct hipAssignment *a, int n, pqps_assign_target *targets);
+void finishUpdateDeviceTableHIP(struct engineS *engine, const struct hipAssignment *a, int n, const uint64_t *matched, uint32_t bumped);
 void destroyDeviceTableHIP(struct engineS *engine);
 
 /* Engines over device-resident columns (no host rows): see initializeEngineColumnsHIP / initializeEngineSyntheticHIP

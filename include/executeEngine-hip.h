@@ -146,6 +146,37 @@ struct engineS *initializeEngineSyntheticHIP(unsigned long long num_rows, unsign
  * DELETE take in their stride -- the aggregates by their selection-then-list route -- and which an engine joined across
  * ranks refuses, as it refuses every WHERE of several passes. */
 
+/* ---- UPDATE table SET column = value [, ...] [WHERE ...] ---------------------------------------------------------------
+ * No counterpart in the reference (its parser answers UPDATE with CMD_UNKNOWN); reached through this API only.
+ * `setColumns[i] = setValues[i]` for i < numSet (1 .. 12, no column twice); each value text is typed by its column exactly
+ * as the literal of `=` is typed in a WHERE (strtoull for command_id, atoi for the i32 columns, "true" in any case or "1"
+ * for sudo_used and anything else false, the string itself for a string column).  Returns the number of rows the WHERE
+ * selects -- a row that already carries the new value counts -- or -1 on refusal or error (reason on stderr).
+ *   ROWS        the rows for which the WHERE is true, each once: scan semantics, also on an engine with indexes, as DELETE
+ *               has.  NULL: every row.  LIKE / IN work as in any WHERE.
+ *   OLD VALUES  the WHERE reads the values from before the update, also of columns that are assigned.
+ *   STABILITY   row numbers, row order and every other column stay as they are.
+ *   WRITER      UPDATE runs alone like INSERT / DELETE: it waits until every ticket is released and is refused (-1) when
+ *               called from a thread that holds one.
+ *   REFUSED     (-1, table unchanged) what hipCompileAssignments refuses (include/hipPredicate.h: unknown column, a column
+ *               twice, numSet outside 1 .. 12, an empty or over-long string, command_id 0); a WHERE that cannot be compiled;
+ *               an engine joined across ranks; and, on an engine without host rows, an assignment that only a rebuild of the
+ *               table could make: a string new to a dictionary that is full for its code width (256 / 65 536 values), or
+ *               another value for a single-valued string column that has no device buffer (assigning that column its own
+ *               value is legal and changes nothing).  The engine decides this before it changes anything.
+ * A string that is new to its column's dictionary is inserted at its rank first and the codes at and above it are bumped on
+ * every shard (as INSERT does); when the WHERE then fails to compile or selects no row the dictionary keeps a value no
+ * row carries -- harmless, as after DELETE.
+ * Engines without host rows: a WHERE that is one scan pass is ONE fused launch per shard (pqps_filter_assign: the WHERE
+ * and the stores); any other WHERE leaves byte flags as for DELETE and pqps_assign_flags stores by them.  Engines with host
+ * rows and a CSV always take the flags: the flags come to the host, the matching host rows are changed and the CSV is
+ * rewritten as after DELETE (not at all when no row matches); the device stores by the same flags, or the table is
+ * rebuilt from the host rows where the assignment needs it.  Afterwards the sudo_used bit plane, the cached i32 bounds and
+ * the indexes on assigned or bumped columns are brought up to date. */
+long long executeQueryUpdateHIP(struct engineS *engine, const char *tableName,
+                                const char *const *setColumns, const char *const *setValues, int numSet,
+                                struct whereClauseS *whereClause, double *queryTime /* may be NULL */);
+
 /* ---- asynchronous queries: several in flight, results left on the device -----------------------------------------
  * The engine's table has LANES (default 4, PQPS_ENGINE_LANES): result buffers + a slot of the table's query stream
  * (pqps_qstream: two launches in flight on two HIP streams, one for tables of 537 M rows and more).  Every SELECT /
@@ -170,7 +201,7 @@ struct hipDeviceResult {
  *   - a thread may hold at most hipEngineLanes(engine) unreleased tickets of one engine; asking for one more returns NULL at
  *     once (reason on stderr).  Tickets held by SEVERAL threads can still add up to all lanes: a further request then waits
  *     for a release, at most PQPS_LANE_WAIT_MS (default 10 000), and returns NULL after that;
- *   - INSERT / DELETE / addAttributeIndexHIP / hipEngineProbeBoolIndexes / hipEngineKernelTiming wait until every ticket is
+ *   - INSERT / DELETE / UPDATE / addAttributeIndexHIP / hipEngineProbeBoolIndexes / hipEngineKernelTiming wait until every ticket is
  *     released; called from a thread that holds a ticket itself they are refused (false / success = false / -1).  While such
  *     a call waits, threads that hold no ticket wait behind it with new queries; a thread that holds one may take more. */
 int hipEngineLanes(struct engineS *engine);

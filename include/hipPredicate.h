@@ -97,6 +97,25 @@ void hipPlanFree(struct hipPlan *plan);
 /* 1 for "LIKE", "NOT LIKE", "IN", "NOT IN" (exactly so written), else 0. */
 int hipIsSetOperator(const char *op);
 
+/* THE SET LIST OF AN UPDATE.  One assignment `column = value`, its value text typed by the column exactly as the literal of
+ * `=` is typed in a WHERE (checkCondition, serial:251-289): strtoull for command_id, atoi for the three i32 columns, "true"
+ * (any case) or "1" for sudo_used and anything else false, the string itself for a string column. */
+struct hipAssignment {
+    int column;                  /* HIPCOL_* id                                                                   */
+    int kind;                    /* HIPKIND_*                                                                     */
+    uint64_t value;              /* U64: the value; I32: its u32 bit pattern; BOOL: 0 / 1; DICT: `rank`           */
+    int present;                 /* DICT: 1 when the string is in the dictionary (numeric columns: 1)             */
+    uint32_t rank;               /* DICT: number of dictionary values below the string -- its code when present,
+                                    the rank it is inserted at otherwise                                         */
+    const char *text;            /* DICT: the caller's string (not copied); NULL otherwise                        */
+};
+/* Compiles n assignments into out[0 .. n); pure host code.  Returns 0, or -1 with the reason on stderr and `out` untouched
+ * for: an unknown column or one the schema does not hold, the same column twice, n < 1 or n > PQPS_MAX_COLUMNS, a NULL
+ * value, an empty string for a string column, a string that does not fit its field of `record` with its NUL
+ * (include/logType.h), command_id 0 (the last two are INSERT's own rules, serial:544-551). */
+int hipCompileAssignments(const struct hipSchema *schema, const char *const *columns, const char *const *values, int n,
+                          struct hipAssignment *out);
+
 /* Column name -> HIPCOL_* id, -1 if unknown. */
 int hipColumnId(const char *name);
 

@@ -33,6 +33,7 @@
  *   pqps_compact_rows   the survivor compaction of DELETE (executeEngine-serial.c:646-680).
  *   pqps_bump_codes     (no counterpart: keeps dictionary codes order-preserving on INSERT).
  *   pqps_member_flags   (no counterpart: LIKE / IN as a set of dictionary codes or values).
+ *   pqps_filter_assign  (no counterpart: UPDATE SET ... WHERE, constants written in place).
  *
  * All functions return 0 on success or a negative PQPS_E* code; the text of
  * the last error of the calling thread is at pqps_last_error().
@@ -594,6 +595,27 @@ int pqps_group_pair_list(pqps_ctx *ctx, const pqps_column *a_col, uint32_t a_bas
 int pqps_group_pair_sort(pqps_ctx *ctx, const pqps_column *a_col, uint32_t a_base, uint32_t n_a, const pqps_column *b_col, uint32_t b_base,
                          uint32_t n_b, const pqps_column *value_col, uint64_t n_rows, const uint32_t *ids, uint64_t n, uint32_t id_base,
                          uint64_t **runs_dev, uint64_t *n_runs, void *stream);
+
+/* ---- UPDATE SET ... WHERE: constants assigned in place to the rows a WHERE selects -----------------------------------------
+ * No counterpart in the reference (its parser knows no UPDATE).  A TARGET is a column and the value every selected row of it
+ * receives: `data` 16-byte aligned and WRITABLE up to n_rows rounded up to PQPS_STEP_ROWS rows, `width` 1, 2, 4 or 8 bytes
+ * (never a bit plane: a boolean column is assigned in its byte column and the plane repacked with pqps_pack_bits), `value`
+ * the new value's low `width` bytes.  1 .. PQPS_MAX_COLUMNS targets per call, no column twice.  Rows that are not selected,
+ * and every row at or past n_rows (the padding included), keep their bits.  Row r is read and written by one lane only, and
+ * the WHERE of a row is evaluated before the row is written: a target may be one of the predicate's columns, the WHERE
+ * sees its old values.  Asynchronous on `stream`; n_rows == 0 launches nothing.
+ *
+ * pqps_filter_assign: ONE scan of `pred` over rows [0, n_rows) of `cols` (as pqps_filter_count takes them, bit planes
+ *   included) that stores into the targets as it goes; a 1024-row step without a match stores nothing and loads nothing
+ *   beyond the predicate's columns.  *matched_dev (device, may be NULL) = the rows selected.  The context's timing recorder
+ *   records the launch like a COUNT's.
+ * pqps_assign_flags: the same stores for the rows r < n_rows with flags[r] != 0 -- the byte flags pqps_filter_flags or
+ *   pqps_member_flags (PQPS_MEMBER_BYTES) wrote.  `flags` 16-byte aligned, read for r < n_rows only. */
+typedef struct { void *data; uint32_t width; uint64_t value; } pqps_assign_target;
+int pqps_filter_assign(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                       const pqps_assign_target *targets, uint32_t n_targets, uint64_t *matched_dev, void *stream);
+int pqps_assign_flags(pqps_ctx *ctx, const uint8_t *flags, uint64_t n_rows, const pqps_assign_target *targets, uint32_t n_targets,
+                      void *stream);
 
 /* Checksums of a device-resident ID list: out[0] = sum of ids[i], out[1] = sum of ids[i] * (2 i + 1), both mod 2^64 (the
  * second depends on the order).  Synchronous; what a bench or a test compares two lists with without downloading them. */

@@ -202,6 +202,11 @@ class Plan(C.Structure):
     _fields_ = [("n_passes", C.c_int), ("passes", C.POINTER(Pass))]
 
 
+class AssignTarget(C.Structure):
+    """pqps_assign_target (include/pqps_hip.h)."""
+    _fields_ = [("data", C.c_void_p), ("width", C.c_uint32), ("value", C.c_uint64)]
+
+
 class SynthCols(C.Structure):
     _fields_ = [
         ("command_id", C.c_void_p), ("exit_code", C.c_void_p), ("user_id", C.c_void_p),
@@ -218,6 +223,12 @@ class ColumnInfo(C.Structure):
 
 class Schema(C.Structure):
     _fields_ = [("col", ColumnInfo * MAX_COLUMNS)]
+
+
+class Assignment(C.Structure):
+    """struct hipAssignment (include/hipPredicate.h)."""
+    _fields_ = [("column", C.c_int), ("kind", C.c_int), ("value", C.c_uint64), ("present", C.c_int), ("rank", C.c_uint32),
+                ("text", C.c_char_p)]
 
 
 assert C.sizeof(Record) == 1040 and C.sizeof(WhereClause) == 56
@@ -360,6 +371,9 @@ def lib():
     L.pqps_pack_bits.argtypes = [vp, vp, u64, vp, u64, u64, vp]
     L.pqps_member_flags.argtypes = [vp, C.POINTER(Column), u64, C.c_int, u32, u64, vp, vp, u32, C.c_int, vp, vp, vp]
     L.hipIsSetOperator.argtypes = [C.c_char_p]
+    L.pqps_filter_assign.argtypes = [vp, C.POINTER(Column), u32, u64, C.POINTER(Predicate), C.POINTER(AssignTarget), u32, vp, vp]
+    L.pqps_assign_flags.argtypes = [vp, vp, u64, C.POINTER(AssignTarget), u32, vp]
+    L.hipCompileAssignments.argtypes = [C.POINTER(Schema), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_int, C.POINTER(Assignment)]
     L.pqps_compact_rows.argtypes = [vp, C.POINTER(Column), u32, u64, vp, C.POINTER(u64), vp]
     L.pqps_project_column.argtypes = [vp, C.POINTER(Column), vp, vp, u64, u32, vp, vp]
     L.pqps_gather_keys.argtypes = [vp, C.POINTER(Column), C.c_int, vp, vp, u64, u32, vp, vp]
@@ -515,6 +529,8 @@ def lib():
     L.freeResultSetHead.argtypes = [C.POINTER(ResultSet), C.c_int]
     L.executeQueryDeleteHIP.restype = C.POINTER(ResultSet)
     L.executeQueryDeleteHIP.argtypes = [E, C.c_char_p, W]
+    L.executeQueryUpdateHIP.restype = C.c_longlong
+    L.executeQueryUpdateHIP.argtypes = [E, C.c_char_p, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_int, W, C.POINTER(C.c_double)]
     L.executeQueryInsertHIP.restype = C.c_bool
     L.executeQueryInsertHIP.argtypes = [E, C.c_char_p, C.POINTER(Record)]
     L.addAttributeIndexHIP.restype = C.c_bool
@@ -609,6 +625,57 @@ def compile_where(spec: SchemaSpec, chain):
     if rc != 0:
         raise PqpsError("hipCompileWhere: " + err.value.decode())
     return pred, list(ids[:pred.n_columns])
+
+
+def assignment_texts(assignments):
+    """{column: str | bytes | int | bool} -> (ctypes array of column names, of value texts, n): the SET list as
+    executeQueryUpdateHIP / hipCompileAssignments take it (bytes as they are, a bool as "true" / "false")."""
+    def text(v):
+        if isinstance(v, bytes):
+            return v
+        if isinstance(v, bool):
+            return b"true" if v else b"false"
+        return str(v).encode("latin-1")
+    n = len(assignments)
+    names = (C.c_char_p * max(1, n))(*[k.encode() for k in assignments])
+    values = (C.c_char_p * max(1, n))(*[text(v) for v in assignments.values()])
+    return names, values, n
+
+
+def compile_assignments(spec: SchemaSpec, assignments):
+    """hipCompileAssignments: [(column id, kind, value, present, rank), ...] for {column: value text} -- value = the typed
+    value (an i32 as a Python int with its sign, a string column's rank), present / rank as struct hipAssignment has them.
+    Raises PqpsError when the SET list is refused (reason on stderr)."""
+    names, values, n = assignment_texts(assignments)
+    out = (Assignment * MAX_COLUMNS)()
+    if lib().hipCompileAssignments(C.byref(spec.schema), names, values, n, out) != 0:
+        raise PqpsError("hipCompileAssignments refused the SET list (reason on stderr)")
+    res = []
+    for a in out[:n]:
+        v = int(a.value)
+        if a.kind == HIPKIND_I32 and v >= 1 << 31:
+            v -= 1 << 32
+        res.append((a.column, a.kind, v, bool(a.present), int(a.rank)))
+    return res
+
+
+def assign_targets(triples):
+    """[(device_ptr, width, value), ...] -> ctypes array of pqps_assign_target."""
+    arr = (AssignTarget * max(1, len(triples)))()
+    for i, (p, w, v) in enumerate(triples):
+        arr[i].data, arr[i].width, arr[i].value = p, w, v & 0xFFFFFFFFFFFFFFFF
+    return arr
+
+
+def filter_assign(ctx, cols, n_cols, n_rows, pred, triples, matched_dev, stream=None):
+    """pqps_filter_assign: the fused filter-and-assign launch; `triples` as assign_targets takes them."""
+    check(lib().pqps_filter_assign(ctx.h, cols, n_cols, n_rows, C.byref(pred), assign_targets(triples), len(triples), matched_dev, stream),
+          "pqps_filter_assign")
+
+
+def assign_flags(ctx, flags_dev, n_rows, triples, stream=None):
+    """pqps_assign_flags: the same stores by byte flags."""
+    check(lib().pqps_assign_flags(ctx.h, flags_dev, n_rows, assign_targets(triples), len(triples), stream), "pqps_assign_flags")
 
 
 # ---- device objects ----------------------------------------------------------------------------
@@ -1015,6 +1082,17 @@ class HipEngine:
         """COUNT(DISTINCT value_column) [GROUP BY group_column]: [(key_text, distinct), ...] (count_distinct_total without
         the total)."""
         return self.count_distinct_total(value_column, group_column, chain)[0]
+
+    def update(self, assignments, chain=None):
+        """executeQueryUpdateHIP: UPDATE SET column = value, ... WHERE chain (None: every row); `assignments` is
+        {column: str | bytes | int | bool}.  -> the number of rows the WHERE selects.  Raises PqpsError when the engine
+        refuses (reason on stderr); the table is unchanged then."""
+        wl = WhereList(chain)
+        names, values, n = assignment_texts(assignments)
+        k = lib().executeQueryUpdateHIP(self.e, b"commands", names, values, n, wl.ptr, None)
+        if k < 0:
+            raise PqpsError(f"update({sorted(assignments)!r}) refused or failed (reason on stderr)")
+        return int(k)
 
     def select(self, columns, chain):
         wl = WhereList(chain)

@@ -29,6 +29,7 @@
 #include "topk_kernels.hpp"
 #include "distinct_kernels.hpp"
 #include "group_pair_kernels.hpp"
+#include "assign_kernels.hpp"
 #include "radix_sort.hpp"
 
 namespace {
@@ -3707,6 +3708,62 @@ int pqps_group_pair_sort(pqps_ctx *ctx, const pqps_column *a_col, uint32_t a_bas
     }
     *runs_dev = out;
     *n_runs = runs;
+    return PQPS_OK;
+}
+
+// ---- UPDATE SET ... WHERE (assign_kernels.hpp) -----------------------------------------------------------------------
+static int fill_assign_targets(const pqps_assign_target *targets, uint32_t n_targets, AssignTarget *out) {
+    if (!targets || n_targets == 0 || n_targets > PQPS_MAX_COLUMNS) return fail(PQPS_EINVAL, "%u assign targets: 1 .. %d", n_targets, PQPS_MAX_COLUMNS);
+    for (uint32_t t = 0; t < n_targets; t++) {
+        const uint32_t w = targets[t].width;
+        if (w != 1 && w != 2 && w != 4 && w != 8) return fail(PQPS_EINVAL, "assign target %u: width %u not in {1,2,4,8}", t, w);
+        if (!targets[t].data || ((uintptr_t)targets[t].data & 15u) != 0) return fail(PQPS_EINVAL, "assign target %u: NULL or not 16-byte aligned", t);
+        for (uint32_t k = 0; k < t; k++)
+            if (targets[k].data == targets[t].data) return fail(PQPS_EINVAL, "assign targets %u and %u are the same column", k, t);
+        out[t].data = (char *)targets[t].data;
+        out[t].width_log2 = w == 1 ? 0u : w == 2 ? 1u : w == 4 ? 2u : 3u;
+        out[t].value = w == 8 ? targets[t].value : targets[t].value & ((1ull << (8 * w)) - 1);
+        out[t].reserved = 0;
+    }
+    return PQPS_OK;
+}
+
+int pqps_filter_assign(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                       const pqps_assign_target *targets, uint32_t n_targets, uint64_t *matched_dev, void *stream) {
+    if (!ctx) return fail(PQPS_EINVAL, "ctx is NULL");
+    AssignArgs g;
+    memset(&g, 0, sizeof g);
+    int rc = fill_assign_targets(targets, n_targets, g.tgt);
+    if (rc == PQPS_OK) rc = fused_args(g.e, cols, n_cols, n_rows, pred);
+    if (rc) return rc;
+    hipStream_t s = pick_stream(ctx, stream);
+    if (matched_dev) HIP_TRY(hipMemsetAsync(matched_dev, 0, sizeof(uint64_t), s));
+    if (n_rows == 0) return PQPS_OK;
+    g.n_targets = n_targets;
+    g.matched = (unsigned long long *)matched_dev;
+    const bool nt = g.e.streaming != 0;
+    snprintf(g_kernel, sizeof g_kernel, "assign_scan_kernel<NT=%s>", nt ? "true" : "false");
+    hipEvent_t stop;
+    rc = fused_launch(ctx, nt ? assign_scan_kernel<true> : assign_scan_kernel<false>, fused_grid(ctx, n_rows, 0), 0, s, g, &stop);
+    if (rc) return rc;
+    fused_close(ctx, stop, true);
+    return PQPS_OK;
+}
+
+int pqps_assign_flags(pqps_ctx *ctx, const uint8_t *flags, uint64_t n_rows, const pqps_assign_target *targets, uint32_t n_targets,
+                      void *stream) {
+    if (!ctx || (!flags && n_rows)) return fail(PQPS_EINVAL, "ctx/flags is NULL");
+    if (((uintptr_t)flags & 15u) != 0) return fail(PQPS_EINVAL, "flags not 16-byte aligned");
+    AssignFlagsArgs g;
+    memset(&g, 0, sizeof g);
+    const int rc = fill_assign_targets(targets, n_targets, g.tgt);
+    if (rc) return rc;
+    if (n_rows == 0) return PQPS_OK;
+    g.flags = flags;
+    g.n_rows = n_rows;
+    g.n_targets = n_targets;
+    hipLaunchKernelGGL(assign_flags_kernel, dim3(fused_grid(ctx, n_rows, 0)), dim3(kBlock), 0, pick_stream(ctx, stream), g);
+    HIP_TRY(hipGetLastError());
     return PQPS_OK;
 }
 

@@ -879,15 +879,18 @@ void rebuildDeviceTableHIP(struct engineS *engine) {
     }
 }
 
-/* Rebuilds every device index of one shard (a device radix sort each; cheap next to a table rebuild). */
+/* Rebuilds one device index of one shard (a device radix sort; cheap next to a table rebuild) ... */
+static void rebuild_index(struct engineS *engine, struct hipTable *t, int i) {
+    if (t->index[i].perm_dev) pqps_free(t->ctx, t->index[i].perm_dev);
+    if (t->index[i].keys_dev) pqps_free(t->ctx, t->index[i].keys_dev);
+    t->index[i].perm_dev = NULL;
+    t->index[i].keys_dev = NULL;
+    build_index(engine, t, i);
+}
+
+/* ... and every one of them. */
 static void rebuild_indexes(struct engineS *engine, struct hipTable *t) {
-    for (int i = 0; i < engine->num_indexes; i++) {
-        if (t->index[i].perm_dev) pqps_free(t->ctx, t->index[i].perm_dev);
-        if (t->index[i].keys_dev) pqps_free(t->ctx, t->index[i].keys_dev);
-        t->index[i].perm_dev = NULL;
-        t->index[i].keys_dev = NULL;
-        build_index(engine, t, i);
-    }
+    for (int i = 0; i < engine->num_indexes; i++) rebuild_index(engine, t, i);
 }
 
 /* INSERT: appends the last host row (engine->all_records[n-1]) to the device columns of the last shard
@@ -960,6 +963,78 @@ bool appendRowDeviceTableHIP(struct engineS *engine, const record *r) {
     for (int s = 0; s < n_shards; s++)                          /* shifted codes are keys of the other shards' indexes too */
         if (bumped || s == n_shards - 1) rebuild_indexes(engine, hipTableShard(t, s));
     return true;
+}
+
+/* UPDATE: see include/buildEngine-hip.h. */
+static uint64_t code_limit(uint32_t width) { return width == 0 ? 1 : width == 1 ? 256 : width == 2 ? 65536 : 0xFFFFFFFFull; }
+
+bool updateNeedsRebuildHIP(struct engineS *engine, const struct hipAssignment *a, int n) {
+    const struct hipTable *t = engine->record_block;
+    for (int i = 0; i < n; i++) {
+        if (a[i].kind != HIPKIND_DICT || a[i].present) continue;
+        if ((uint64_t)t->dict[a[i].column].count + 1 > code_limit(t->col[a[i].column].width)) return true;
+    }
+    return false;
+}
+
+uint32_t updateInsertStringsHIP(struct engineS *engine, const struct hipAssignment *a, int n) {
+    struct hipTable *t = engine->record_block;
+    uint32_t bumped = 0;
+    for (int i = 0; i < n; i++) {
+        if (a[i].kind != HIPKIND_DICT || a[i].present) continue;
+        const int c = a[i].column;
+        struct hipDictionary *d = &t->dict[c];
+        const size_t pos = a[i].rank;
+        const char **grown = realloc(d->values, ((size_t)d->count + 1) * sizeof *grown);
+        char *copy = strdup(a[i].text);
+        if (!grown || !copy) { perror("Failed to grow dictionary"); exit(EXIT_FAILURE); }
+        d->values = grown;
+        memmove(&d->values[pos + 1], &d->values[pos], ((size_t)d->count - pos) * sizeof *grown);
+        d->values[pos] = copy;
+        d->count++;
+        for (int s = 0; s < hipTableShards(t); s++) {
+            struct hipTable *sh = hipTableShard(t, s);
+            if (pqps_bump_codes(sh->ctx, (void *)sh->col[c].data, sh->col[c].width, sh->n_rows, (uint32_t)pos, NULL) != PQPS_OK)
+                hip_die("dictionary code shift");
+        }
+        bumped |= 1u << c;
+    }
+    return bumped;
+}
+
+int updateTargetsHIP(const struct hipTable *sh, const struct hipAssignment *a, int n, pqps_assign_target *targets) {
+    int k = 0;
+    for (int i = 0; i < n; i++) {
+        const pqps_column *col = &sh->col[a[i].column];
+        if (!col->data) continue;                               /* a single-valued column keeps its one value */
+        targets[k++] = (pqps_assign_target){ (void *)col->data, col->width, a[i].value };
+    }
+    return k;
+}
+
+void finishUpdateDeviceTableHIP(struct engineS *engine, const struct hipAssignment *a, int n, const uint64_t *matched, uint32_t bumped) {
+    struct hipTable *t = engine->record_block;
+    uint32_t assigned = 0;
+    uint64_t total = 0;
+    for (int s = 0; s < hipTableShards(t); s++) total += matched[s];
+    for (int i = 0; i < n; i++) {
+        const int c = a[i].column;
+        assigned |= 1u << c;
+        if (a[i].kind == HIPKIND_I32 && total && t->bounds_known[c]) {     /* a cached group range covers the new value */
+            const int32_t v = (int32_t)(uint32_t)a[i].value;
+            if (v < t->bounds_lo[c]) t->bounds_lo[c] = v;
+            if (v > t->bounds_hi[c]) t->bounds_hi[c] = v;
+        }
+    }
+    for (int s = 0; s < hipTableShards(t); s++) {
+        struct hipTable *sh = hipTableShard(t, s);
+        if (matched[s] && (assigned & (1u << HIPCOL_SUDO_USED))) shard_pack_all_bits(sh);
+        for (int i = 0; i < engine->num_indexes; i++) {
+            const int c = sh->index[i].column >= 0 ? sh->index[i].column : hipColumnId(engine->indexed_attributes[i]);
+            if (c < 0 || !sh->col[c].data) continue;
+            if ((bumped & (1u << c)) || (matched[s] && (assigned & (1u << c)))) rebuild_index(engine, sh, i);
+        }
+    }
 }
 
 /* DELETE: drops the flagged rows from the device columns of every shard in place and re-sorts the

@@ -2712,21 +2712,18 @@ bool executeQueryInsertHIP(struct engineS *engine, const char *tableName, const 
 
 /* executeQueryDeleteSerial, S:627-715: the per-row decision is the GPU flag
  * kernel (the flag-array shape of engine/omp/executeEngine-omp.c:708-732). */
-/* Flags of the rows that go, per shard on the device; `flags` (may be NULL: an engine without host rows) receives them
- * for the whole table, *deleted their number. */
-static int delete_flags(struct engineS *engine, struct hipTable *t, struct whereClauseS *whereClause, size_t n, uint8_t **flags_dev, uint8_t *flags,
-                        uint64_t *deleted) {
-    struct query q;
-    query_init(&q, engine, t, -1, true);                            /* the writer is alone: the table's own context and buffers */
+/* Flags of the rows the bound WHERE of a writer's query selects (DELETE: the rows that go, UPDATE: the rows that change), per
+ * shard on the device; `flags` (may be NULL: an engine without host rows) receives them for the whole table, *deleted their
+ * number, per_shard[s] (may be NULL) each shard's. */
+static int row_flags(struct query *q, size_t n, uint8_t **flags_dev, uint8_t *flags, uint64_t *deleted, uint64_t *per_shard) {
+    struct hipTable *t = q->t;
     *deleted = 0;
-    if (bind_where(t, whereClause, &q.plan) != 0) return -1;
-    q.have_plan = true;
     int rc = 0;
-    for (int s = 0; s < q.n_shards && rc == 0; s++) {
+    for (int s = 0; s < q->n_shards && rc == 0; s++) {
         struct hipTable *sh = hipTableShard(t, s);
         /* the passes in front of the last as for any query, the last pass as flags instead of a count */
-        struct hipPlan head = q.plan;
-        struct shard_pred *sp = &q.sp[s];
+        struct hipPlan head = q->plan;
+        struct shard_pred *sp = &q->sp[s];
         memset(sp, 0, sizeof *sp);
         const struct hipPass *last = &head.pass[head.n_passes - 1];
         rc = head_passes(&head, sh, sp, sh->ctx, NULL, sh->own.count_dev + 4, true);
@@ -2738,15 +2735,27 @@ static int delete_flags(struct engineS *engine, struct hipTable *t, struct where
         if (rc == 0 && pqps_filter_flags(sh->ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, flags_dev[s], sh->own.count_dev, NULL) != PQPS_OK)
             rc = engine_error("flag filter");
     }
-    for (int s = 0; s < q.n_shards; s++) {
+    for (int s = 0; s < q->n_shards; s++) {
         struct hipTable *sh = hipTableShard(t, s);
         uint64_t k = 0;
         if (rc == 0 && pqps_ctx_sync(sh->ctx, NULL) != PQPS_OK) rc = engine_error("filter execution");
         if (rc == 0 && pqps_download(sh->ctx, &k, sh->own.count_dev, sizeof k, NULL) != PQPS_OK) rc = engine_error("count download");
         *deleted += k;
+        if (per_shard) per_shard[s] = k;
         if (rc == 0 && sh->row0 + sh->n_rows > n) { fprintf(stderr, "HIP engine: device shards hold more rows than the engine\n"); rc = -1; }
         if (rc == 0 && flags && sh->n_rows && pqps_download(sh->ctx, flags + sh->row0, flags_dev[s], sh->n_rows, NULL) != PQPS_OK) rc = engine_error("flag download");
     }
+    return rc;
+}
+
+static int delete_flags(struct engineS *engine, struct hipTable *t, struct whereClauseS *whereClause, size_t n, uint8_t **flags_dev, uint8_t *flags,
+                        uint64_t *deleted) {
+    struct query q;
+    query_init(&q, engine, t, -1, true);                            /* the writer is alone: the table's own context and buffers */
+    *deleted = 0;
+    if (bind_where(t, whereClause, &q.plan) != 0) return -1;
+    q.have_plan = true;
+    const int rc = row_flags(&q, n, flags_dev, flags, deleted, NULL);
     query_free(&q);
     return rc;
 }
@@ -2812,4 +2821,163 @@ struct resultSetS *executeQueryDeleteHIP(struct engineS *engine, const char *tab
     rs->queryTime = now_seconds() - t0;
     rs->success = true;
     return rs;
+}
+
+/* ---- UPDATE SET ... WHERE (include/executeEngine-hip.h) -------------------------------------------------------------- */
+
+static void assign_host_row(record *r, const struct hipAssignment *a, int n) {
+    for (int i = 0; i < n; i++) {
+        switch (a[i].column) {
+        case HIPCOL_COMMAND_ID: r->command_id = a[i].value; break;
+        case HIPCOL_EXIT_CODE: r->exit_code = (int)(uint32_t)a[i].value; break;
+        case HIPCOL_USER_ID: r->user_id = (int)(uint32_t)a[i].value; break;
+        case HIPCOL_RISK_LEVEL: r->risk_level = (int)(uint32_t)a[i].value; break;
+        case HIPCOL_SUDO_USED: r->sudo_used = a[i].value != 0; break;
+        case HIPCOL_RAW_COMMAND: strncpy(r->raw_command, a[i].text, sizeof r->raw_command); break;
+        case HIPCOL_BASE_COMMAND: strncpy(r->base_command, a[i].text, sizeof r->base_command); break;
+        case HIPCOL_SHELL_TYPE: strncpy(r->shell_type, a[i].text, sizeof r->shell_type); break;
+        case HIPCOL_TIMESTAMP: strncpy(r->timestamp, a[i].text, sizeof r->timestamp); break;
+        case HIPCOL_WORKING_DIRECTORY: strncpy(r->working_directory, a[i].text, sizeof r->working_directory); break;
+        case HIPCOL_USER_NAME: strncpy(r->user_name, a[i].text, sizeof r->user_name); break;
+        case HIPCOL_HOST_NAME: strncpy(r->host_name, a[i].text, sizeof r->host_name); break;
+        default: break;
+        }
+    }
+}
+
+/* The fused route: the WHERE of one scan pass and the stores, ONE launch per shard on the table's own context. */
+static int update_fused(struct query *q, const struct hipAssignment *a, int n, uint64_t *matched) {
+    const struct hipPass *pass = &q->plan.pass[0];
+    int rc = 0;
+    for (int s = 0; s < q->n_shards && rc == 0; s++) {
+        struct hipTable *sh = hipTableShard(q->t, s);
+        pqps_column cols[PQPS_MAX_COLUMNS];
+        pqps_assign_target targets[PQPS_MAX_COLUMNS];
+        pass_columns(sh, pass, NULL, true, cols);
+        const int k = updateTargetsHIP(sh, a, n, targets);
+        if (k == 0) {                                               /* nothing to store: the rows are counted all the same */
+            if (pqps_filter_count(sh->ctx, cols, pass->pred.n_columns, sh->n_rows, &pass->pred, sh->own.count_dev, NULL) != PQPS_OK)
+                rc = engine_error("count filter");
+        } else if (pqps_filter_assign(sh->ctx, cols, pass->pred.n_columns, sh->n_rows, &pass->pred, targets, (uint32_t)k, sh->own.count_dev,
+                                      NULL) != PQPS_OK)
+            rc = engine_error("filter and assign");
+    }
+    /* every shard that was launched on is waited for, whatever another one returned */
+    for (int s = 0; s < q->n_shards; s++) {
+        struct hipTable *sh = hipTableShard(q->t, s);
+        if (pqps_ctx_sync(sh->ctx, NULL) != PQPS_OK && rc == 0) rc = engine_error("filter and assign");
+        if (rc == 0 && pqps_download(sh->ctx, &matched[s], sh->own.count_dev, sizeof matched[s], NULL) != PQPS_OK) rc = engine_error("count download");
+    }
+    return rc;
+}
+
+/* The stores of the flags route, by the flags row_flags() left on every shard. */
+static int update_by_flags(struct hipTable *t, const struct hipAssignment *a, int n, uint8_t *const *flags_dev, const uint64_t *matched) {
+    int rc = 0;
+    for (int s = 0; s < hipTableShards(t) && rc == 0; s++) {
+        struct hipTable *sh = hipTableShard(t, s);
+        pqps_assign_target targets[PQPS_MAX_COLUMNS];
+        const int k = updateTargetsHIP(sh, a, n, targets);
+        if (k && matched[s] && pqps_assign_flags(sh->ctx, flags_dev[s], sh->n_rows, targets, (uint32_t)k, NULL) != PQPS_OK)
+            rc = engine_error("assign by flags");
+    }
+    for (int s = 0; s < hipTableShards(t); s++)
+        if (pqps_ctx_sync(hipTableShard(t, s)->ctx, NULL) != PQPS_OK && rc == 0) rc = engine_error("assign by flags");
+    return rc;
+}
+
+static long long update_locked(struct engineS *engine, struct hipTable *t, const char *const *setColumns, const char *const *setValues, int numSet,
+                               struct whereClauseS *whereClause) {
+    const double t0 = now_seconds();
+    if (t->xch) {
+        fprintf(stderr, "HIP engine: UPDATE is refused on an engine joined across ranks\n");
+        return -1;
+    }
+    /* 1. the SET list, and whether it can be made in place */
+    struct hipSchema schema;
+    struct hipAssignment a[PQPS_MAX_COLUMNS];
+    hipSchemaOfTable(t, &schema);
+    if (hipCompileAssignments(&schema, setColumns, setValues, numSet, a) != 0) return -1;
+    const bool rebuild = updateNeedsRebuildHIP(engine, a, numSet);
+    if (rebuild && t->device_only) {
+        fprintf(stderr, "HIP engine: UPDATE needs a table rebuild (a dictionary outgrowing its code width, or a second value for a column "
+                        "without a device buffer), which an engine without host rows cannot do\n");
+        return -1;
+    }
+    const size_t n = (size_t)engine->num_records;
+    const int n_shards = hipTableShards(t);
+    /* 2. new strings into their dictionaries, before the WHERE is bound: its constants are codes */
+    const uint32_t bumped = rebuild ? 0u : updateInsertStringsHIP(engine, a, numSet);
+    const double t1 = now_seconds();
+
+    /* 3. the rows */
+    uint64_t matched[HIP_MAX_SHARDS];
+    uint8_t *flags_dev[HIP_MAX_SHARDS];
+    memset(matched, 0, sizeof matched);
+    memset(flags_dev, 0, sizeof flags_dev);
+    uint64_t total = 0;
+    uint8_t *flags = NULL;
+    bool fused = false;
+    struct query q;
+    query_init(&q, engine, t, -1, true);                            /* the writer is alone: the table's own context and buffers */
+    int rc = bind_where(t, whereClause, &q.plan);
+    if (rc == 0) {
+        q.have_plan = true;
+        fused = t->device_only && q.plan.n_passes == 1;
+        if (fused) {
+            rc = update_fused(&q, a, numSet, matched);
+            for (int s = 0; s < n_shards; s++) total += matched[s];
+        } else {
+            if (!t->device_only) {
+                flags = malloc(n ? n : 1);
+                if (!flags) { fprintf(stderr, "HIP engine: out of memory for %zu update flags\n", n); rc = -1; }
+            }
+            if (rc == 0) rc = row_flags(&q, n, flags_dev, flags, &total, matched);
+        }
+        TRACE("UPDATE: %s route, %llu of %zu rows\n", fused ? "fused" : "flags", (unsigned long long)total, n);
+    }
+    query_free(&q);
+    const double t2 = now_seconds();
+    if (rc != 0) memset(matched, 0, sizeof matched);               /* (nothing was stored: the flags route stores below) */
+
+    /* host rows and the CSV, as after a DELETE */
+    double t3 = t2;
+    if (rc == 0 && !t->device_only && total) {
+        for (size_t i = 0; i < n; i++)
+            if (flags[i]) assign_host_row(&t->row_block[i], a, numSet);
+        FILE *f = fopen(engine->datafile, "w");                    /* no header written, S:683-701 */
+        if (f) {
+            write_csv_table(f, t->row_block, n);
+            fclose(f);
+        }
+        t3 = now_seconds();
+    }
+    free(flags);
+
+    /* the stores of the flags route, or the rebuild from the updated host rows.  A device step that fails after the host rows
+     * and the CSV have changed is fatal, as in INSERT / DELETE. */
+    if (rc == 0 && !fused && total && !rebuild && update_by_flags(t, a, numSet, flags_dev, matched) != 0) {
+        if (!t->device_only) exit(EXIT_FAILURE);
+        rc = -1;
+    }
+    for (int s = 0; s < n_shards; s++) if (flags_dev[s]) pqps_free(hipTableShard(t, s)->ctx, flags_dev[s]);
+    /* 4. plane, bounds, indexes (bumped codes are keys of indexes whatever became of the WHERE) */
+    if (rebuild) { if (rc == 0 && total) rebuildDeviceTableHIP(engine); }
+    else finishUpdateDeviceTableHIP(engine, a, numSet, matched, bumped);
+    TRACE("UPDATE: SET list + dictionaries %.3f ms, rows %.3f ms, host rows + CSV %.3f ms, device stores + plane + indexes %.3f ms\n",
+          (t1 - t0) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3, (now_seconds() - t3) * 1e3);
+    return rc == 0 ? (long long)total : -1;
+}
+
+long long executeQueryUpdateHIP(struct engineS *engine, const char *tableName, const char *const *setColumns, const char *const *setValues,
+                                int numSet, struct whereClauseS *whereClause, double *queryTime) {
+    (void)tableName;
+    if (!engine || !engine->record_block) return -1;
+    const double t0 = now_seconds();
+    struct hipTable *t = engine->record_block;
+    if (hipTableLockExclusive(t) != 0) return -1;
+    const long long k = update_locked(engine, t, setColumns, setValues, numSet, whereClause);
+    hipTableUnlockExclusive(t);
+    if (queryTime) *queryTime = now_seconds() - t0;
+    return k;
 }

@@ -7,6 +7,7 @@
  */
 #define _POSIX_C_SOURCE 200809L
 #include "hipPredicate.h"
+#include "logType.h"
 
 #include <limits.h>
 #include <stdio.h>
@@ -910,4 +911,63 @@ void hipPlanFree(struct hipPlan *plan) {
     free(plan->pass);
     plan->pass = NULL;
     plan->n_passes = 0;
+}
+
+/* ---- the SET list of an UPDATE ------------------------------------------------------------------------------------ */
+
+/* bytes of the `record` field of a string column (with its NUL), 0 for the others */
+static size_t field_bytes(int col) {
+    static const size_t k_bytes[PQPS_MAX_COLUMNS] = {
+        0, sizeof(((record *)0)->raw_command), sizeof(((record *)0)->base_command), sizeof(((record *)0)->shell_type), 0,
+        sizeof(((record *)0)->timestamp), 0, sizeof(((record *)0)->working_directory), 0, sizeof(((record *)0)->user_name),
+        sizeof(((record *)0)->host_name), 0
+    };
+    return k_bytes[col];
+}
+
+static int assign_fail(const char *column, const char *what) {
+    fprintf(stderr, "HIP engine: UPDATE SET %s: %s\n", column ? column : "(null)", what);
+    return -1;
+}
+
+int hipCompileAssignments(const struct hipSchema *schema, const char *const *columns, const char *const *values, int n,
+                          struct hipAssignment *out) {
+    struct hipAssignment a[PQPS_MAX_COLUMNS];
+    if (!schema || !columns || !values || !out) return assign_fail(NULL, "NULL argument");
+    if (n < 1 || n > PQPS_MAX_COLUMNS) return assign_fail(NULL, "1 to 12 assignments");
+    for (int i = 0; i < n; i++) {
+        const int col = hipColumnId(columns[i]);
+        if (col < 0) return assign_fail(columns[i], "unknown column");
+        if (!values[i]) return assign_fail(columns[i], "no value");
+        for (int k = 0; k < i; k++)
+            if (a[k].column == col) return assign_fail(columns[i], "assigned twice");
+        const struct hipColumnInfo *ci = &schema->col[col];
+        if (!ci->present) return assign_fail(columns[i], "the column is not materialised on the device");
+        a[i] = (struct hipAssignment){ col, ci->kind, 0, 1, 0, NULL };
+        switch (ci->kind) {
+        case HIPKIND_U64:
+            a[i].value = strtoull(values[i], NULL, 10);
+            if (a[i].value == 0) return assign_fail(columns[i], "command_id 0 is no row's id");
+            break;
+        case HIPKIND_I32:
+            a[i].value = (uint64_t)(uint32_t)atoi(values[i]);
+            break;
+        case HIPKIND_BOOL:
+            a[i].value = (strcasecmp(values[i], "true") == 0 || strcmp(values[i], "1") == 0) ? 1u : 0u;
+            break;
+        default: {
+            if (!values[i][0]) return assign_fail(columns[i], "an empty string");
+            if (strlen(values[i]) + 1 > field_bytes(col)) return assign_fail(columns[i], "the string does not fit the record's field");
+            int l = 0, r = ci->dict_count;
+            while (l < r) { const int m = l + (r - l) / 2; if (strcmp(ci->dict[m], values[i]) < 0) l = m + 1; else r = m; }
+            a[i].rank = (uint32_t)l;
+            a[i].value = (uint64_t)l;
+            a[i].present = l < ci->dict_count && strcmp(ci->dict[l], values[i]) == 0;
+            a[i].text = values[i];
+            break;
+        }
+        }
+    }
+    memcpy(out, a, (size_t)n * sizeof *a);
+    return 0;
 }
