@@ -19,6 +19,13 @@ The table exists TWICE in HBM and consecutive steps alternate between the copies
 otherwise find part of itself in the 256 MiB Infinity Cache left by the step before, and the HBM roofline
 would be flattered.  Prints ONE JSON line on rank 0.
 
+A plain run does what the headline figure needs and no more: set-up, one calibration scan (its count and checksum are what
+every timed answer is verified against), the warm-up, the timed regions, the result line.  `--full` adds everything else the
+benchmark measures: the shim-level leg beside an engine-level `value`, the one-launch-at-a-time leg that feeds `roofline.frac`,
+the other query shapes / index probes / projection / 1 G-row legs (`extra`; `--no-extras` leaves them out) and the CPU
+baselines with the end-to-end CSV runs (`cpu_baseline`; `--no-cpu-baseline` leaves them out).  `value`, `ms_per_step` and the
+dumped arrays are the same with and without it.
+
 `--dump-outputs DIR` also writes the answer of the last timed step as .npy files; the table is seeded, so two builds run
 with the same arguments can be compared answer for answer.
 """
@@ -222,8 +229,12 @@ def main():
     ap.add_argument("--copies", type=int, default=2, help="table copies the steps alternate between (1: the same buffers every step)")
     ap.add_argument("--query", default="S1", choices=sorted(QUERIES))
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=0x5EED)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary queries / index / projection / 1 B-row legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what `value` does not need: the shim-level leg beside an engine-level `value`, the one-launch-at-a-time "
+                         "leg of `roofline.frac`, the `extra` legs and the CPU baselines (off by default: a plain run sets up, warms up, "
+                         "times the steps and prints the result line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines and the end-to-end CSV runs")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary queries / index / projection / 1 B-row legs")
     ap.add_argument("--backend", default="nccl")
     ap.add_argument("--exchange", default="rccl", choices=["rccl", "torch"],
                     help="N>1 exchange step: 'rccl' = the product calls RCCL itself (engine API / shim); "
@@ -338,19 +349,26 @@ def main():
         keep.append(t)
         return t.data_ptr()
 
-    extras = [] if (args.no_extras or world > 1) else [k for k in QUERIES if k != args.query]
+    extras = [] if (not args.full or args.no_extras or world > 1) else [k for k in QUERIES if k != args.query]
     needed = {leaf[0] for k in [args.query] + extras for leaf in _leaves(QUERIES[k][0])} & set(pq.COLUMNS)
-    t0 = time.perf_counter()
     tables = []
-    for c in range(copies):
-        cols_c = set(needed)
-        if extras and c == 0:
-            cols_c |= {"command_id", "user_id", "risk_level"}      # index-mode leg (configs[2]), first copy only
-        tables.append(pq.SyntheticTable(ctx, count, seed=args.seed, row0=start, columns=sorted(cols_c), alloc=alloc, stream=sptr))
-    torch.cuda.synchronize()
-    log(f"{dev_name}, {cus} CUs: generated {count:,} rows x {sorted(needed)} x {copies} copies in {time.perf_counter() - t0:.2f} s")
+    bound = []                                                      # (pred, cols, n_cols, bytes per row) per copy
 
-    bound = [t.bind(chain) for t in tables]                         # (pred, cols, n_cols, bytes per row) per copy
+    def need_tables(n_copies):
+        """The first `n_copies` copies exist: one for the calibration scan, all of them once the shim level runs."""
+        if len(tables) >= n_copies:
+            return
+        t0 = time.perf_counter()
+        while len(tables) < n_copies:
+            cols_c = set(needed)
+            if extras and not tables:
+                cols_c |= {"command_id", "user_id", "risk_level"}      # index-mode leg (configs[2]), first copy only
+            tables.append(pq.SyntheticTable(ctx, count, seed=args.seed, row0=start, columns=sorted(cols_c), alloc=alloc, stream=sptr))
+            bound.append(tables[-1].bind(chain))
+        torch.cuda.synchronize()
+        log(f"{dev_name}, {cus} CUs: {count:,} rows x {sorted(needed)} generated, {len(tables)} of {copies} copies, in {time.perf_counter() - t0:.2f} s")
+
+    need_tables(1)
     bytes_per_row = bound[0][3]
     widths = sorted({tables[0].width[leaf[0]] for leaf in _leaves(chain)}, reverse=True)
     L = pq.lib()
@@ -507,6 +525,7 @@ def main():
     # ==== shim level: include/pqps_hip.h driven from Python (round 2's headline path; the fallback of the engine level) =========
     def shim_level():
         """-> dict.  Every rank calls this."""
+        need_tables(copies)
         slot_cap = (count + 4096) // 4096 * 4096 if (exchange and not count_mode) else \
             ((int(max_matches * 1.25) + 4096) // 4096 * 4096 if not count_mode else 4096)
         native = exchange and args.exchange == "rccl" and (args.backend == "nccl" or args.rccl_library is not None)
@@ -750,18 +769,22 @@ def main():
         log(f"shim level: {med / args.steps * 1e6:.1f} us/step (median of {len(regions)} regions: {min(regions) / args.steps * 1e6:.1f} .. "
             f"{max(regions) / args.steps * 1e6:.1f}); host: {(enq_s - waited) / n_steps_all * 1e6:.1f} us/step in runtime calls + "
             f"{waited / n_steps_all * 1e6:.1f} us/step waiting for a free ring slot")
-        # ---- the same steps once more with HIP events on the dispatch of every scan kernel (ID output: the ONE launch of
-        # the query -- scan tiles + expanders; COUNT(*): the scan, the 1-workgroup reduction after it in `pipeline`):
+        # ---- --full: the same steps once more with HIP events on the dispatch of every scan kernel (ID output: the ONE launch
+        # of the query -- scan tiles + expanders; COUNT(*): the scan, the 1-workgroup reduction after it in `pipeline`):
         # its average duration feeds `roofline`.  Kept out of the timed regions because in timing mode a query
         # runs whole on one stream (no overlap with its neighbours), which is not how `value` is produced.
-        ctx.set_timing(True)
-        ok, _, _ = phase(args.steps)
-        kern_ms, pipe_ms, launches = ctx.kernel_time()
-        ctx.set_timing(False)
-        if not ok:
-            sys.exit("bench: the per-launch timing steps failed")
+        kern_ms = pipe_ms = None
+        launches = 0
+        if args.full:
+            ctx.set_timing(True)
+            ok, _, _ = phase(args.steps)
+            kern_ms, pipe_ms, launches = ctx.kernel_time()
+            ctx.set_timing(False)
+            if not ok:
+                sys.exit("bench: the per-launch timing steps failed")
         out = {"value": n_global * args.steps / med, "ms_per_step": med / args.steps * 1e3, "regions_s": regions,
-               "avg_kernel_ms": kern_ms / max(launches, 1), "avg_pipeline_ms": pipe_ms / max(launches, 1), "launches_timed": launches,
+               "avg_kernel_ms": kern_ms / max(launches, 1) if args.full else None,
+               "avg_pipeline_ms": pipe_ms / max(launches, 1) if args.full else None, "launches_timed": launches,
                "in_stream_kernel_ms": in_stream_ms, "native": st["native"], "pipelined": qs is not None or st["native"],
                "wire_bytes_in_per_step": wire[0] / n_steps_all if wire else None, "u32_bytes_in_per_step": wire[1] / n_steps_all if wire else None,
                "one_collective_queries": eager[0] if eager else None, "exchanged_queries": eager[1] if eager else None,
@@ -797,9 +820,9 @@ def main():
         if eng is None:
             result_notes.append("engine level failed (" + str(err) + "); value is the shim-level figure")
     torch.cuda.empty_cache()
-    # the shim level runs at N = 1 always (its one-launch-at-a-time leg feeds `roofline`), at N > 1 when the engine level is not the headline
+    # the shim level runs when the engine level is not the headline, and with --full at N = 1 beside it (its one-launch-at-a-time leg feeds `roofline`)
     shim = None
-    if world == 1 or eng is None:
+    if eng is None or (args.full and world == 1):
         shim = shim_level()
     level = "engine" if eng is not None else "shim"
 
@@ -846,7 +869,7 @@ def main():
                    "query": sql, "mode": args.mode, "rows_per_gpu": count if strong else args.rows, "rows_total": n_global,
                    "matches_total": total_matches, "selectivity": total_matches / max(n_global, 1),
                    "bytes_per_row": bytes_per_row, "table_copies_alternated": copies,
-                   "level": level,
+                   "level": level, "full": args.full,
                    # both levels as flat keys (the driver's record keeps one level of this object)
                    "engine_ms_per_query": eng["ms_per_query"] if eng else None,
                    "engine_value": eng["value"] if eng else None,
@@ -867,7 +890,8 @@ def main():
                      "kernel": (kernel_chosen if not count_mode else kernel_chosen.replace("MODE_IDS", "MODE_COUNT"))
                                + (" -- the ONE launch of an ID query: scan tiles (the only readers of the table) + expander workgroups"
                                   if not count_mode else " -- the scan; the one-workgroup reduction of the totals follows it"),
-                     "frac_is": "ONE launch at a time at the shim level (HIP events on the dispatch), re-run after the timed regions; job_frac is the timed regions' figure",
+                     "frac_is": ("ONE launch at a time at the shim level (HIP events on the dispatch), re-run after the timed regions" if args.full else
+                                 "not measured: the one-launch-at-a-time leg runs with --full") + "; job_frac is the timed regions' figure",
                      "avg_kernel_ms": avg_kernel_ms, "avg_pipeline_ms": shim["avg_pipeline_ms"] if shim else None,
                      # the same launches as they ran IN the timed region (several in flight): longer each, shorter per query
                      "in_stream_kernel_ms": eng["in_stream_kernel_ms"] if eng else (shim["in_stream_kernel_ms"] if shim else None),
@@ -886,7 +910,7 @@ def main():
         result["shim_level"] = shim
 
     # side measurements must never cost the headline line
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         try:
             result["extra"] = extras_leg(pq, L, ctx, tables, count, start, sptr, torch, device, extras, log, alloc, args.seed)
             ns = result["extra"].get("north_star_1b", {})
@@ -902,7 +926,7 @@ def main():
         except Exception as e:                                   # noqa: BLE001
             log(f"extras leg failed: {e!r}")
             result["extra"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             result["cpu_baseline"] = cpu_baseline(pq, chain, sql, args.seed, log)
         except Exception as e:                                   # noqa: BLE001

@@ -11,6 +11,6 @@ vals=()
 while [ $# -gt 0 ] && [ "$1" != "--" ]; do vals+=("$1"); shift; done
 [ "$1" == "--" ] && shift
 for v in "${vals[@]}"; do
-  env "$var=$v" python bench.py --no-cpu-baseline --no-extras "$@" 2>/dev/null |
+  env "$var=$v" python bench.py --full --no-cpu-baseline --no-extras "$@" 2>/dev/null |
     python -c "import json,sys; d=json.load(sys.stdin); r=d['roofline']; print('$var=$v', 'K1 us', round(r['avg_kernel_ms']*1e3,1), 'frac', round(r['frac'],3), 'us/query', round(d['ms_per_step']*1e3,1))"
 done

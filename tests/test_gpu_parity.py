@@ -432,7 +432,8 @@ def test_compact_rows_equals_numpy_boolean_indexing(ctx):
 def test_bench_exchange_path_runs_on_one_gpu():
     """bench.py --force-merge: the N > 1 code path (torch.distributed bootstrap over RCCL, shim-driven
     all-gather + merge on the exchange stream, ring of slots) with a world of 1, in its own process
-    with bench.py's load order.  stdout must be exactly one JSON line."""
+    with bench.py's load order.  `--full`: the shim-level leg also runs beside an engine-level `value`.  stdout must be exactly
+    one JSON line."""
     import json
     import subprocess
     import sys
@@ -440,7 +441,7 @@ def test_bench_exchange_path_runs_on_one_gpu():
     # Python (pqps_exchange_*), torch.distributed (merge.IdMerger)
     for level, mode, who in (("engine", "rccl", "engine API"), ("shim", "rccl", "shim-driven"), ("engine", "torch", "torch.distributed")):
         p = subprocess.run([sys.executable, str(q.ROOT / "bench.py"), "--rows", "3000000", "--steps", "9", "--warmup", "2", "--reps", "3",
-                            "--no-extras", "--no-cpu-baseline", "--force-merge", "--exchange", mode, "--level", level],
+                            "--full", "--no-extras", "--no-cpu-baseline", "--force-merge", "--exchange", mode, "--level", level],
                            capture_output=True, text=True, timeout=600,
                            env=dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29533"))
         assert p.returncode == 0, p.stderr[-3000:]
@@ -452,6 +453,27 @@ def test_bench_exchange_path_runs_on_one_gpu():
         assert d["config"]["level"] == ("engine" if (level, mode) == ("engine", "rccl") else "shim")
         assert d["roofline"]["value_spread_reps"] == 3 and d["roofline"]["value_spread_min"] <= d["value"] <= d["roofline"]["value_spread_max"]
         assert d["config"]["shim_ms_per_step"] is not None and "NOTE" not in d["config"]["parallelism"]
+
+
+def test_bench_plain_run_measures_the_headline_only(tmp_path):
+    """bench.py without --full: the engine-level `value`, its answer verified and dumped, and none of the side legs -- no
+    shim-level leg beside it, no one-launch-at-a-time roofline leg, no `extra`, no `cpu_baseline`.  One JSON line."""
+    import subprocess
+    import sys
+    p = subprocess.run([sys.executable, str(q.ROOT / "bench.py"), "--gpus", "1", "--rows", "3000000", "--steps", "9", "--warmup", "2",
+                        "--reps", "3", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, p.stdout[:2000]
+    d = json.loads(lines[0])
+    assert d["config"]["full"] is False and d["config"]["level"] == "engine" and "NOTE" not in d["config"]["parallelism"]
+    assert d["value"] > 0 and d["unit"] == "rows/s" and d["higher_is_better"] is True and d["dtype"] == "u16/u8"
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 - 3000000) < 1e-3 * 3000000            # rows per step / seconds per step
+    assert d["config"]["engine_ms_per_query"] == d["ms_per_step"] and d["config"]["shim_ms_per_step"] is None
+    assert d["roofline"]["frac"] is None and d["roofline"]["job_frac"] > 0
+    assert not {"extra", "cpu_baseline", "shim_level"} & set(d)
+    assert "cpu " not in p.stderr and "shim level" not in p.stderr                        # the legs did not run at all
+    assert np.load(tmp_path / "count.npy")[0] == d["config"]["matches_total"] == len(np.load(tmp_path / "ids.npy")) > 0
 
 
 @pytest.mark.parametrize("ranks,extra", [(2, []), (3, ["--query", "Q_A"]), (2, ["--mode", "count"])])
@@ -470,7 +492,7 @@ def test_bench_with_several_ranks_sharing_the_gpu(ranks, extra):
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={ranks}",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), str(q.ROOT / "bench.py"),
                         "--gpus", str(ranks), "--backend", "gloo", "--rows", "2000003", "--steps", "12", "--warmup", "3",
-                        "--no-extras", "--no-cpu-baseline", *extra],
+                        "--full", "--no-extras", "--no-cpu-baseline", *extra],
                        capture_output=True, text=True, timeout=900, cwd=str(q.ROOT))
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
     lines = [ln for ln in p.stdout.splitlines() if ln.strip().startswith("{")]
@@ -501,7 +523,7 @@ def test_bench_engine_level_with_several_ranks_through_the_process_loopback(rank
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={ranks}",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), str(q.ROOT / "bench.py"),
                         "--gpus", str(ranks), "--backend", "gloo", "--exchange", "rccl", "--rccl-library", str(lib),
-                        "--rows", "2000003", "--steps", "12", "--warmup", "3", "--reps", "2", "--no-extras", "--no-cpu-baseline", *extra],
+                        "--rows", "2000003", "--steps", "12", "--warmup", "3", "--reps", "2", "--full", "--no-extras", "--no-cpu-baseline", *extra],
                        capture_output=True, text=True, timeout=900, cwd=str(q.ROOT), env=dict(os.environ, LOOPBACK_MP_OUTBOX_MB="64"))
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-4000:])
     lines = [ln for ln in p.stdout.splitlines() if ln.strip().startswith("{")]
