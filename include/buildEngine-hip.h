@@ -175,6 +175,29 @@ bool updateNeedsRebuildHIP(struct engineS *engine, const struct hipAssignment *a
 uint32_t updateInsertStringsHIP(struct engineS *engine, const struct hipAssignment *a, int n);
 int updateTargetsHIP(const struct hipTable *sh, const struct hipAssignment *a, int n, pqps_assign_target *targets);
 void finishUpdateDeviceTableHIP(struct engineS *engine, const struct hipAssignment *a, int n, const uint64_t *matched, uint32_t bumped);
+/* Batch INSERT (executeQueryInsertColumnsHIP / executeQueryInsertRowsHIP), device side, under the exclusive lock, in two steps
+ * so that everything that can be refused is decided before a row, a file or a dictionary changes:
+ *   prepareAppendColumnsHIP  checks the batch (shapes, widths, the dictionary merges of hipMergeDictionaries, INT_MAX rows), stages
+ *                            it on the last shard's device -- host arrays uploaded, device arrays copied -- and translates its
+ *                            codes into staging buffers of the column's final width (pqps_remap_codes with lut_new, whose count
+ *                            of out-of-range codes is the code check); command_id != 0 and sudo_used <= 1 are checked on the
+ *                            host.  NULL = refused (reason on stderr), nothing changed.  The caller's dictionaries must stay
+ *                            valid until the commit.
+ *   prepareAppendRowsHIP     the same from records: the batch's dictionaries and codes built on the host first.
+ *   commitAppendHIP          grows the last shard when its head-room is used up (shard_alloc's capacity for the new count);
+ *                            per string column whose merge is no identity or whose union needs wider codes ONE
+ *                            pqps_remap_codes with lut_old per shard (in place, or into a buffer of the next width that fits;
+ *                            a single-valued column gets its buffer); copies the staged columns behind the last row; packs
+ *                            the plane from the first new row; widens cached bounds; installs the unions as dictionaries;
+ *                            rebuilds the last shard's indexes and, on the other shards, those whose codes changed;
+ *                            advances engine->num_records; frees the batch.  A device failure here is fatal, as in INSERT.
+ *   discardAppendHIP         frees a prepared batch that is not committed. */
+struct hipAppend;
+struct hipColumnData;
+struct hipAppend *prepareAppendColumnsHIP(struct engineS *engine, unsigned long long num_rows, const struct hipColumnData *columns);
+struct hipAppend *prepareAppendRowsHIP(struct engineS *engine, const record *rows, unsigned long long num_rows);
+void commitAppendHIP(struct engineS *engine, struct hipAppend *batch);
+void discardAppendHIP(struct engineS *engine, struct hipAppend *batch);
 void destroyDeviceTableHIP(struct engineS *engine);
 
 /* Engines over device-resident columns (no host rows): see initializeEngineColumnsHIP / initializeEngineSyntheticHIP

@@ -146,6 +146,36 @@ struct engineS *initializeEngineSyntheticHIP(unsigned long long num_rows, unsign
  * DELETE take in their stride -- the aggregates by their selection-then-list route -- and which an engine joined across
  * ranks refuses, as it refuses every WHERE of several passes. */
 
+/* ---- batch INSERT: any number of rows appended in one call ----------------------------------------------------------------
+ * executeQueryInsertHIP takes one `record` per call and pays, per call, twelve small uploads, a rebuild of the last shard's
+ * indexes and -- for every string new to its dictionary -- a pass over that column on every shard (pqps_bump_codes) and a
+ * rebuild of every shard's indexes; on an engine without host rows it gives up when the head-room is used up or a dictionary
+ * outgrows its code width.  These two calls append a whole batch: ONE dictionary merge per string column on the host
+ * (hipMergeDictionaries), at most ONE remap pass per string column and shard on the device (pqps_remap_codes) whatever the
+ * number of new strings, ONE rebuild of the indexes; a column whose union outgrows its codes is widened 1 -> 2 -> 4 bytes, a
+ * single-valued column that receives a second string gets its buffer, and the last shard grows when its head-room is used up.
+ * executeQueryInsertHIP itself is unchanged.
+ * RESULT.  The engine answers every query form exactly as a fresh engine built from the old rows followed by the batch's rows
+ * in order: dictionaries are the sorted unions (a batch string no row carries still enters: harmless, as after DELETE), old
+ * rows keep their numbers, the new ones are n .. n + num_rows - 1 on the last shard (no re-balancing, as INSERT).
+ * Both return the rows appended, or -1 (reason on stderr) with NOTHING changed; num_rows == 0 returns 0.  Writers like INSERT,
+ * DELETE and UPDATE: the exclusive lock, refused from a thread that holds a ticket and on an engine joined across ranks.
+ *   executeQueryInsertColumnsHIP  the input of initializeEngineColumnsHIP: the batch's own ascending dictionaries, codes of 1, 2
+ *       or 4 bytes whatever the table's width, `values` NULL with a one-string dictionary for a single-valued column,
+ *       `on_device` honoured.  For engines WITHOUT host rows; an engine over a CSV refuses it (it has rows and a file to keep
+ *       in step).
+ *   executeQueryInsertRowsHIP     records; the batch's dictionaries and codes are built from them, then the same device route.  On
+ *       an engine with host rows the row store grows once, the batch goes to the CSV in one fopen("a") (the bytes B single
+ *       INSERTs leave) and the rows are copied, all after the batch has been accepted.
+ * REFUSED before anything changes: a dictionary list that is not strictly ascending, an empty or over-long string (the merge's
+ * refusals); a width outside 8 / 4 / 1 for the numeric columns or 1 / 2 / 4 for codes; values NULL with a dictionary of more
+ * than one string; command_id 0 or sudo_used > 1 in any batch row; a batch code >= its dictionary_count; more than INT_MAX
+ * rows in all.  `queryTime` may be NULL. */
+long long executeQueryInsertColumnsHIP(struct engineS *engine, const char *tableName, unsigned long long num_rows,
+                                       const struct hipColumnData columns[12], double *queryTime);
+long long executeQueryInsertRowsHIP(struct engineS *engine, const char *tableName, const record *rows, unsigned long long num_rows,
+                                    double *queryTime);
+
 /* ---- UPDATE table SET column = value [, ...] [WHERE ...] ---------------------------------------------------------------
  * No counterpart in the reference (its parser answers UPDATE with CMD_UNKNOWN); reached through this API only.
  * `setColumns[i] = setValues[i]` for i < numSet (1 .. 12, no column twice); each value text is typed by its column exactly

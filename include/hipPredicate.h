@@ -116,6 +116,21 @@ struct hipAssignment {
 int hipCompileAssignments(const struct hipSchema *schema, const char *const *columns, const char *const *values, int n,
                           struct hipAssignment *out);
 
+/* THE DICTIONARY MERGE OF A BATCH INSERT.  Two ascending, duplicate-free string lists -- a column's dictionary and the
+ * dictionary of a batch of rows -- into their sorted union in strcmp order; pure host code.
+ *   merged[0 .. *merged_count)   the union; the pointers are the inputs' own (nothing is copied), room for old_count +
+ *                                new_count of them
+ *   lut_old[old_count], lut_new[new_count]   the position of every input string in the union: what pqps_remap_codes sends the
+ *                                table's and the batch's codes through
+ *   *identity                    1 when lut_old[i] == i for every i -- every new string sorts behind every old one, or nothing
+ *                                is new: the table's codes stay as they are
+ * `column` (HIPCOL_* id of a string column) names the field of `record` the strings have to fit.  Returns 0, or -1 with the
+ * reason on stderr and every output untouched for: a NULL pointer (a list may be NULL when its count is 0), a negative
+ * count, a column that is no string column, a list that is not strictly ascending, an empty string (INSERT's rule,
+ * serial:544-551), a string that does not fit its field with its NUL (the limit hipCompileAssignments enforces). */
+int hipMergeDictionaries(const char *const *old_values, int old_count, const char *const *new_values, int new_count, int column,
+                         const char **merged, int *merged_count, uint32_t *lut_old, uint32_t *lut_new, int *identity);
+
 /* Column name -> HIPCOL_* id, -1 if unknown. */
 int hipColumnId(const char *name);
 

@@ -34,6 +34,7 @@
  *   pqps_bump_codes     (no counterpart: keeps dictionary codes order-preserving on INSERT).
  *   pqps_member_flags   (no counterpart: LIKE / IN as a set of dictionary codes or values).
  *   pqps_filter_assign  (no counterpart: UPDATE SET ... WHERE, constants written in place).
+ *   pqps_remap_codes    (no counterpart: batch INSERT, every code of a column to its place in a merged dictionary).
  *
  * All functions return 0 on success or a negative PQPS_E* code; the text of
  * the last error of the calling thread is at pqps_last_error().
@@ -616,6 +617,31 @@ int pqps_filter_assign(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, 
                        const pqps_assign_target *targets, uint32_t n_targets, uint64_t *matched_dev, void *stream);
 int pqps_assign_flags(pqps_ctx *ctx, const uint8_t *flags, uint64_t n_rows, const pqps_assign_target *targets, uint32_t n_targets,
                       void *stream);
+
+/* ---- batch INSERT: dictionary codes through a lookup table ----------------------------------------------------------------
+ * No counterpart in the reference.  dst[i] = lut[src[i]] for i < n: what is left for the device when a batch of rows merges
+ * its dictionary into a column's -- ONE pass per column and shard whatever the number of new strings (pqps_bump_codes is one
+ * pass per string).  `src_width`, `dst_width` 1, 2 or 4 bytes, dst_width >= src_width: the same call widens a column whose
+ * dictionary has outgrown its codes.  dst == src is legal exactly when the widths are equal (a lane reads and writes only
+ * its own elements); otherwise the two ranges must not overlap.  `src` is read for i < n only.  No byte of `dst` at or past
+ * n * dst_width changes; the dword the end cuts through is read and written back, so `dst` is readable and writable up to
+ * n * dst_width rounded up to 4 bytes.  A code >= lut_count never indexes the table: it is stored as 0 and counted into
+ * *bad_dev (device, may be NULL; zeroed by the call; one 64-bit atomic add per workgroup).  `lut_dev`: lut_count u32 words.
+ * FORMS, chosen by the caller (pqps_remap_form: the form the engine takes for a table of lut_count entries):
+ *   PQPS_REMAP_LDS     every workgroup stages the table into LDS once; lut_count <= PQPS_REMAP_LDS_CODES (16 KiB: the 8
+ *                      workgroups per CU of the persistent grid fit a CU's 160 KiB -- with fewer the pass waits on its
+ *                      loads)
+ *   PQPS_REMAP_GLOBAL  lookups go to memory: a full 2-byte dictionary's table is 256 KiB and lives in L2
+ * PQPS_EINVAL, nothing launched: a NULL pointer; `src` or `dst` not 16-byte aligned; a width pair outside the six; dst == src
+ * with different widths or a partial overlap; an unknown form, or the LDS form with a larger table; lut_count 0, or a
+ * lut_count whose largest position (lut_count - 1) does not fit dst_width.  n == 0 launches nothing.  Asynchronous on
+ * `stream`.  Traffic: src_width + dst_width bytes per row. */
+#define PQPS_REMAP_LDS    0
+#define PQPS_REMAP_GLOBAL 1
+#define PQPS_REMAP_LDS_CODES 4096u
+int pqps_remap_codes(pqps_ctx *ctx, const void *src, uint32_t src_width, void *dst, uint32_t dst_width, uint64_t n,
+                     const uint32_t *lut_dev, uint32_t lut_count, int form, uint64_t *bad_dev, void *stream);
+int pqps_remap_form(uint32_t lut_count);
 
 /* Checksums of a device-resident ID list: out[0] = sum of ids[i], out[1] = sum of ids[i] * (2 i + 1), both mod 2^64 (the
  * second depends on the order).  Synchronous; what a bench or a test compares two lists with without downloading them. */

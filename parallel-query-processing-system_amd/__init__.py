@@ -35,6 +35,8 @@ WIDTH_BITS = 0x81                  # pqps_column.width of a bit plane (PQPS_WIDT
 HIPKIND_U64, HIPKIND_I32, HIPKIND_BOOL, HIPKIND_DICT = 0, 1, 2, 3     # include/hipPredicate.h
 MEMBER_BITMAP, MEMBER_LIST = 0, 1  # pqps_member_flags: lookup form ...
 MEMBER_BYTES, MEMBER_PLANE = 0, 1  # ... and output form
+REMAP_LDS, REMAP_GLOBAL = 0, 1     # pqps_remap_codes: where the lookups go
+REMAP_LDS_CODES = 4096             # a table of up to this many codes is staged into LDS
 MEMBER_LDS_BITS = 1 << 18          # a bitmap of up to this many bits is staged into LDS
 MEMBER_MAX_RUNS, MEMBER_MAX_ITEMS = 4, 65536
 SYNTH_USERS = 2000
@@ -531,6 +533,14 @@ def lib():
     L.executeQueryDeleteHIP.argtypes = [E, C.c_char_p, W]
     L.executeQueryUpdateHIP.restype = C.c_longlong
     L.executeQueryUpdateHIP.argtypes = [E, C.c_char_p, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_int, W, C.POINTER(C.c_double)]
+    L.executeQueryInsertColumnsHIP.restype = C.c_longlong
+    L.executeQueryInsertColumnsHIP.argtypes = [E, C.c_char_p, C.c_ulonglong, C.POINTER(ColumnData), C.POINTER(C.c_double)]
+    L.executeQueryInsertRowsHIP.restype = C.c_longlong
+    L.executeQueryInsertRowsHIP.argtypes = [E, C.c_char_p, C.POINTER(Record), C.c_ulonglong, C.POINTER(C.c_double)]
+    L.hipMergeDictionaries.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.POINTER(C.c_char_p),
+                                       C.POINTER(C.c_int), C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_int)]
+    L.pqps_remap_codes.argtypes = [vp, vp, u32, vp, u32, u64, vp, u32, C.c_int, vp, vp]
+    L.pqps_remap_form.argtypes = [u32]
     L.executeQueryInsertHIP.restype = C.c_bool
     L.executeQueryInsertHIP.argtypes = [E, C.c_char_p, C.POINTER(Record)]
     L.addAttributeIndexHIP.restype = C.c_bool
@@ -676,6 +686,28 @@ def filter_assign(ctx, cols, n_cols, n_rows, pred, triples, matched_dev, stream=
 def assign_flags(ctx, flags_dev, n_rows, triples, stream=None):
     """pqps_assign_flags: the same stores by byte flags."""
     check(lib().pqps_assign_flags(ctx.h, flags_dev, n_rows, assign_targets(triples), len(triples), stream), "pqps_assign_flags")
+
+
+def remap_codes(ctx, src_dev, src_width, dst_dev, dst_width, n, lut_dev, lut_count, form=None, bad_dev=None, stream=None):
+    """pqps_remap_codes: dst[i] = lut[src[i]] for i < n; `form` None = the one pqps_remap_form picks for lut_count."""
+    if form is None:
+        form = lib().pqps_remap_form(lut_count)
+    check(lib().pqps_remap_codes(ctx.h, src_dev, src_width, dst_dev, dst_width, n, lut_dev, lut_count, form, bad_dev, stream),
+          "pqps_remap_codes")
+
+
+def merge_dictionaries(old, new, column="user_name"):
+    """hipMergeDictionaries: two ascending lists of bytes -> (merged, lut_old, lut_new, identity); `column` names the field of
+    `record` the strings have to fit.  Raises PqpsError when the merge is refused (reason on stderr)."""
+    a = (C.c_char_p * max(1, len(old)))(*old)
+    b = (C.c_char_p * max(1, len(new)))(*new)
+    merged = (C.c_char_p * max(1, len(old) + len(new)))()
+    count, identity = C.c_int(), C.c_int()
+    lut_old = (C.c_uint32 * max(1, len(old)))()
+    lut_new = (C.c_uint32 * max(1, len(new)))()
+    if lib().hipMergeDictionaries(a, len(old), b, len(new), COL[column], merged, C.byref(count), lut_old, lut_new, C.byref(identity)) != 0:
+        raise PqpsError("hipMergeDictionaries refused the lists (reason on stderr)")
+    return list(merged[:count.value]), list(lut_old[:len(old)]), list(lut_new[:len(new)]), bool(identity.value)
 
 
 # ---- device objects ----------------------------------------------------------------------------
@@ -900,12 +932,11 @@ class HipEngine:
             raise PqpsError("hipQueryChecksumHIP failed")
         return int(out[0]), int(out[1])
 
-    @classmethod
-    def from_columns(cls, n_rows, columns, indexes=()):
-        """initializeEngineColumnsHIP.  columns: {name: numpy array} for numeric columns,
-        {name: (codes array or None, [bytes, ...] dictionary)} for string columns (all 12 of them)."""
+    @staticmethod
+    def _column_data(columns):
+        """{name: numpy array} for numeric columns, {name: (codes array or None, [bytes, ...] dictionary)} for string columns
+        -> (ctypes array of the 12 struct hipColumnData, what has to stay alive while it is used)."""
         import numpy as np
-        self = cls.__new__(cls)
         arr = (ColumnData * MAX_COLUMNS)()
         keep = []
         for i, name in enumerate(COLUMNS):
@@ -923,12 +954,40 @@ class HipEngine:
                 a = np.ascontiguousarray(v)
                 keep.append(a)
                 arr[i].values, arr[i].width = a.ctypes.data, a.dtype.itemsize
+        return arr, keep
+
+    @classmethod
+    def from_columns(cls, n_rows, columns, indexes=()):
+        """initializeEngineColumnsHIP.  columns: {name: numpy array} for numeric columns,
+        {name: (codes array or None, [bytes, ...] dictionary)} for string columns (all 12 of them)."""
+        self = cls.__new__(cls)
+        arr, keep = cls._column_data(columns)
         names, types = cls._index_args(indexes)
         self.e = lib().initializeEngineColumnsHIP(n_rows, arr, len(indexes), names, types, b"commands")
         if not self.e:
             raise PqpsError("initializeEngineColumnsHIP failed")
         self.n = self.e.contents.num_records
         return self
+
+    def insert_columns(self, n_rows, columns):
+        """executeQueryInsertColumnsHIP: appends n_rows rows given as the `columns` dict of from_columns (the batch's own
+        dictionaries and codes); -> rows appended.  Raises PqpsError when the batch is refused (nothing changed)."""
+        arr, keep = self._column_data(columns)
+        k = lib().executeQueryInsertColumnsHIP(self.e, b"commands", n_rows, arr, None)
+        self.n = self.e.contents.num_records
+        if k < 0:
+            raise PqpsError("executeQueryInsertColumnsHIP refused the batch (reason on stderr)")
+        return int(k)
+
+    def insert_rows(self, records):
+        """executeQueryInsertRowsHIP: appends a list of Record (or a ctypes array of them); -> rows appended.  Raises
+        PqpsError when the batch is refused (nothing changed)."""
+        rows = records if isinstance(records, C.Array) else (Record * max(1, len(records)))(*records)
+        k = lib().executeQueryInsertRowsHIP(self.e, b"commands", rows, len(records), None)
+        self.n = self.e.contents.num_records
+        if k < 0:
+            raise PqpsError("executeQueryInsertRowsHIP refused the batch (reason on stderr)")
+        return int(k)
 
     def select_async(self, chain, count_only=False):
         """-> ticket (opaque).  The WHERE list only has to live until this call returns."""

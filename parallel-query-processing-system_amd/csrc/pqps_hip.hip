@@ -30,6 +30,7 @@
 #include "distinct_kernels.hpp"
 #include "group_pair_kernels.hpp"
 #include "assign_kernels.hpp"
+#include "remap_kernels.hpp"
 #include "radix_sort.hpp"
 
 namespace {
@@ -3763,6 +3764,43 @@ int pqps_assign_flags(pqps_ctx *ctx, const uint8_t *flags, uint64_t n_rows, cons
     g.n_rows = n_rows;
     g.n_targets = n_targets;
     hipLaunchKernelGGL(assign_flags_kernel, dim3(fused_grid(ctx, n_rows, 0)), dim3(kBlock), 0, pick_stream(ctx, stream), g);
+    HIP_TRY(hipGetLastError());
+    return PQPS_OK;
+}
+
+// ---- batch INSERT: dictionary codes through a lookup table (remap_kernels.hpp) ----------------------------------------
+int pqps_remap_form(uint32_t lut_count) { return lut_count <= PQPS_REMAP_LDS_CODES ? PQPS_REMAP_LDS : PQPS_REMAP_GLOBAL; }
+
+int pqps_remap_codes(pqps_ctx *ctx, const void *src, uint32_t src_width, void *dst, uint32_t dst_width, uint64_t n,
+                     const uint32_t *lut_dev, uint32_t lut_count, int form, uint64_t *bad_dev, void *stream) {
+    if (!ctx || !src || !dst || !lut_dev) return fail(PQPS_EINVAL, "NULL argument");
+    if ((((uintptr_t)src | (uintptr_t)dst) & 15u) != 0) return fail(PQPS_EINVAL, "source / destination not 16-byte aligned");
+    const bool sw_ok = src_width == 1 || src_width == 2 || src_width == 4, dw_ok = dst_width == 1 || dst_width == 2 || dst_width == 4;
+    if (!sw_ok || !dw_ok || dst_width < src_width) return fail(PQPS_EINVAL, "code widths %u -> %u: 1, 2 or 4 bytes, never narrower", src_width, dst_width);
+    if (n > (~0ull >> 3)) return fail(PQPS_EINVAL, "%llu codes", (unsigned long long)n);
+    if (dst == src) {
+        if (src_width != dst_width) return fail(PQPS_EINVAL, "in place only with equal widths");
+    } else {
+        const uintptr_t s0 = (uintptr_t)src, s1 = s0 + n * src_width, d0 = (uintptr_t)dst, d1 = d0 + n * dst_width;
+        if (s0 < d1 && d0 < s1) return fail(PQPS_EINVAL, "source and destination overlap");
+    }
+    if (form != PQPS_REMAP_LDS && form != PQPS_REMAP_GLOBAL) return fail(PQPS_EINVAL, "remap form %d", form);
+    if (lut_count == 0) return fail(PQPS_EINVAL, "an empty table");
+    if (form == PQPS_REMAP_LDS && lut_count > PQPS_REMAP_LDS_CODES) return fail(PQPS_EINVAL, "a table of %u codes does not fit the LDS form", lut_count);
+    if (dst_width < 4 && (uint64_t)lut_count > (1ull << (8 * dst_width)))
+        return fail(PQPS_EINVAL, "a table of %u codes holds values that do not fit %u bytes", lut_count, dst_width);
+    hipStream_t s = pick_stream(ctx, stream);
+    if (bad_dev) HIP_TRY(hipMemsetAsync(bad_dev, 0, sizeof(uint64_t), s));
+    if (n == 0) return PQPS_OK;
+    RemapArgs a;
+    a.src = (const char *)src; a.dst = (char *)dst; a.n = n; a.lut = lut_dev; a.lut_count = lut_count;
+    a.bad = (unsigned long long *)bad_dev;
+    const bool lds = form == PQPS_REMAP_LDS;
+    /* a persistent grid of 8 workgroups per CU -- 8 waves per SIMD, one 16-byte load in flight per lane: what the streaming side
+     * needs; every workgroup of the LDS form stages the table once (PQPS_REMAP_LDS_CODES keeps 8 of them within a CU's LDS) */
+    const uint64_t chunks = (n + 16 / src_width - 1) / (16 / src_width);
+    const uint64_t want = (chunks + kRemapBlock - 1) / kRemapBlock, cap = (uint64_t)ctx->compute_units * 8u;
+    remap_launch_widths(src_width, dst_width, lds, (uint32_t)(want < cap ? want : cap), s, a);
     HIP_TRY(hipGetLastError());
     return PQPS_OK;
 }

@@ -17,6 +17,7 @@
 #include "hipPredicate.h"
 
 #include <errno.h>
+#include <limits.h>
 #include <malloc.h>
 #include <pthread.h>
 #include <stdio.h>
@@ -1280,4 +1281,350 @@ static bool synthetic_table(struct engineS *engine, unsigned long long num_rows,
     table_make_engine_lanes(t, min_lanes);
     engine->record_block = t;
     return true;
+}
+
+/* ---- batch INSERT: see include/buildEngine-hip.h ---------------------------------------------------------------------- */
+
+struct hipAppend {
+    uint64_t rows;
+    uint32_t width[HIPCOL_COUNT];             /* the column's width on the device after the append (0: still no buffer)  */
+    void *stage[HIPCOL_COUNT];                /* last shard's device: the batch's column at that width, codes translated */
+    const char **merged[HIPCOL_COUNT];        /* string columns: the union (pointers into the old and the batch's lists) */
+    int merged_count[HIPCOL_COUNT], identity[HIPCOL_COUNT];
+    uint32_t *lut_old[HIPCOL_COUNT];
+    int have_bounds[HIPCOL_COUNT];
+    int32_t lo[HIPCOL_COUNT], hi[HIPCOL_COUNT];
+    /* the rows form: the batch's own dictionaries and code arrays live here until the commit */
+    struct hipDictionary batch_dict[HIPCOL_COUNT];
+    void *batch_values[HIPCOL_COUNT];
+};
+
+static uint32_t width_for_count(uint64_t count) { return count <= 256 ? 1u : count <= 65536 ? 2u : 4u; }
+
+static struct hipTable *last_shard(struct hipTable *t) { return hipTableShard(t, hipTableShards(t) - 1); }
+
+void discardAppendHIP(struct engineS *engine, struct hipAppend *b) {
+    if (!b) return;
+    struct hipTable *last = last_shard(engine->record_block);
+    for (int c = 0; c < HIPCOL_COUNT; c++) {
+        if (b->stage[c]) pqps_free(last->ctx, b->stage[c]);
+        free(b->merged[c]);
+        free(b->lut_old[c]);
+        dictionary_free(&b->batch_dict[c]);
+        free(b->batch_values[c]);
+    }
+    free(b);
+}
+
+static struct hipAppend *append_refuse(struct engineS *engine, struct hipAppend *b, const char *what, int column) {
+    if (column >= 0) fprintf(stderr, "HIP engine: batch INSERT refused: column %d: %s\n", column, what);
+    else fprintf(stderr, "HIP engine: batch INSERT refused: %s\n", what);
+    discardAppendHIP(engine, b);
+    return NULL;
+}
+
+/* the batch's `bytes` of one column, host or device memory of the engine's first device, to `dst` on `ctx`'s device */
+static int append_copy_in(pqps_ctx *ctx, pqps_ctx *ctx0, void *dst, const void *src, int on_device, size_t bytes) {
+    if (!on_device) return pqps_upload(ctx, dst, src, bytes, NULL);
+    const int rc = pqps_copy_peer(ctx, dst, ctx0, src, bytes, NULL);
+    return rc != PQPS_OK ? rc : pqps_ctx_sync(ctx, NULL);
+}
+
+/* codes of `bw` bytes as codes of the narrower `fw`; NULL when one of them is >= count (or out of memory) */
+static void *narrow_codes(const void *src, uint32_t bw, uint32_t fw, uint64_t n, uint64_t count) {
+    void *out = malloc((n ? n : 1) * fw);
+    for (uint64_t i = 0; out && i < n; i++) {
+        const uint32_t v = bw == 4 ? ((const uint32_t *)src)[i] : ((const uint16_t *)src)[i];
+        if ((uint64_t)v >= count) { free(out); return NULL; }
+        if (fw == 1) ((uint8_t *)out)[i] = (uint8_t)v; else ((uint16_t *)out)[i] = (uint16_t)v;
+    }
+    return out;
+}
+
+struct hipAppend *prepareAppendColumnsHIP(struct engineS *engine, unsigned long long num_rows, const struct hipColumnData *columns) {
+    struct hipTable *t = engine->record_block;
+    struct hipTable *last = last_shard(t);
+    pqps_ctx *ctx = last->ctx, *ctx0 = t->ctx;
+    const uint64_t B = num_rows;
+    if (!columns || B == 0) return append_refuse(engine, NULL, "no rows", -1);
+    if ((uint64_t)engine->num_records + B > (uint64_t)INT_MAX) return append_refuse(engine, NULL, "more than INT_MAX rows in all", -1);
+    if ((uint64_t)engine->num_records != last->row0 + last->n_rows) return append_refuse(engine, NULL, "the last shard does not end the table", -1);
+    for (int c = 0; c < HIPCOL_COUNT; c++) {
+        const struct hipColumnData *cd = &columns[c];
+        if (k_kind[c] != HIPKIND_DICT) {
+            if (cd->width != k_numeric_width[c] || !cd->values) return append_refuse(engine, NULL, "a numeric column of 8 / 4 / 1 bytes per row is expected", c);
+        } else {
+            if (cd->dictionary_count < 1 || !cd->dictionary) return append_refuse(engine, NULL, "a dictionary of at least one string is expected", c);
+            if (!cd->values && cd->dictionary_count != 1) return append_refuse(engine, NULL, "no codes, and a dictionary of more than one string", c);
+            if (cd->values && cd->width != 1 && cd->width != 2 && cd->width != 4) return append_refuse(engine, NULL, "codes of 1, 2 or 4 bytes are expected", c);
+        }
+    }
+    struct hipAppend *b = calloc(1, sizeof *b);
+    if (!b) return append_refuse(engine, NULL, "out of memory", -1);
+    b->rows = B;
+    uint32_t *lut_new[HIPCOL_COUNT] = { NULL };
+    void *raw_dev[HIPCOL_COUNT] = { NULL }, *lut_dev[HIPCOL_COUNT] = { NULL }, *narrowed = NULL, *fetched = NULL;
+    uint64_t *words_dev = NULL;
+    uint8_t *sudo_host = NULL;
+    uint64_t *id_host = NULL;
+    const char *why = NULL;
+    int why_col = -1;
+#define REFUSE(c, text) do { why = (text); why_col = (c); goto out; } while (0)
+    /* 1. the merges: host only */
+    for (int c = 0; c < HIPCOL_COUNT; c++) {
+        if (k_kind[c] != HIPKIND_DICT) { b->width[c] = k_numeric_width[c]; continue; }
+        const struct hipDictionary *d = &t->dict[c];
+        const int nn = columns[c].dictionary_count;
+        b->merged[c] = malloc(((size_t)d->count + (size_t)nn) * sizeof *b->merged[c]);
+        b->lut_old[c] = malloc(((size_t)d->count + 1) * sizeof(uint32_t));
+        lut_new[c] = malloc((size_t)nn * sizeof(uint32_t));
+        if (!b->merged[c] || !b->lut_old[c] || !lut_new[c]) REFUSE(c, "out of memory");
+        if (hipMergeDictionaries(d->values, d->count, columns[c].dictionary, nn, c, b->merged[c], &b->merged_count[c], b->lut_old[c],
+                                 lut_new[c], &b->identity[c]) != 0)
+            REFUSE(c, "the dictionaries cannot be merged");
+        const uint32_t tw = t->col[c].width, need = width_for_count((uint64_t)b->merged_count[c]);
+        b->width[c] = tw == 0 ? (b->merged_count[c] > 1 ? need : 0u) : (need > tw ? need : tw);
+    }
+    /* 2. the batch onto the last shard's device, codes translated to the union's at the final width */
+    if (pqps_malloc(ctx, 64 * sizeof(uint64_t), (void **)&words_dev) != PQPS_OK || pqps_memset(ctx, words_dev, 0, 64 * sizeof(uint64_t), NULL) != PQPS_OK)
+        REFUSE(-1, "device allocation");
+    for (int c = 0; c < HIPCOL_COUNT; c++) {
+        const struct hipColumnData *cd = &columns[c];
+        const uint32_t fw = b->width[c];
+        if (!fw) continue;
+        if (pqps_malloc(ctx, (B * fw + 15) / 16 * 16 + 64, &b->stage[c]) != PQPS_OK) REFUSE(c, "device allocation");
+        if (k_kind[c] != HIPKIND_DICT) {
+            if (append_copy_in(ctx, ctx0, b->stage[c], cd->values, cd->on_device, B * fw) != PQPS_OK) REFUSE(c, "column copy");
+            if (k_kind[c] == HIPKIND_I32 && t->bounds_known[c]) {
+                const pqps_column col = { b->stage[c], 4, 0 };
+                int32_t lohi[2];
+                if (pqps_column_bounds(ctx, &col, B, (int32_t *)(words_dev + 16 + c), NULL) != PQPS_OK ||
+                    pqps_download(ctx, lohi, words_dev + 16 + c, sizeof lohi, NULL) != PQPS_OK)
+                    REFUSE(c, "value range");
+                b->have_bounds[c] = 1; b->lo[c] = lohi[0]; b->hi[c] = lohi[1];
+            }
+            continue;
+        }
+        const void *values = cd->values;
+        uint32_t bw = cd->width;
+        int on_device = cd->on_device;
+        if (!values) {                                             /* a single-valued batch column: its one code, B times */
+            narrowed = malloc(B * fw);
+            if (!narrowed) REFUSE(c, "out of memory");
+            const uint32_t code = lut_new[c][0];
+            for (uint64_t i = 0; i < B; i++) {
+                if (fw == 1) ((uint8_t *)narrowed)[i] = (uint8_t)code;
+                else if (fw == 2) ((uint16_t *)narrowed)[i] = (uint16_t)code;
+                else ((uint32_t *)narrowed)[i] = code;
+            }
+            const int rc = pqps_upload(ctx, b->stage[c], narrowed, B * fw, NULL);
+            free(narrowed); narrowed = NULL;
+            if (rc != PQPS_OK) REFUSE(c, "column copy");
+            continue;
+        }
+        if (bw > fw) {                                             /* wider codes than the column's: narrowed on the host, checked there */
+            if (on_device) {
+                fetched = malloc(B * bw);
+                if (!fetched || pqps_download(ctx0, fetched, values, B * bw, NULL) != PQPS_OK) REFUSE(c, "column download");
+                values = fetched;
+            }
+            narrowed = narrow_codes(values, bw, fw, B, (uint64_t)cd->dictionary_count);
+            free(fetched); fetched = NULL;
+            if (!narrowed) REFUSE(c, "a code at or past the batch's dictionary count");
+            values = narrowed; bw = fw; on_device = 0;
+        }
+        int rc = pqps_malloc(ctx, (B * bw + 15) / 16 * 16 + 64, &raw_dev[c]);
+        if (rc == PQPS_OK) rc = append_copy_in(ctx, ctx0, raw_dev[c], values, on_device, B * bw);
+        free(narrowed); narrowed = NULL;
+        if (rc == PQPS_OK) rc = pqps_malloc(ctx, (size_t)cd->dictionary_count * sizeof(uint32_t), &lut_dev[c]);
+        if (rc == PQPS_OK) rc = pqps_upload(ctx, lut_dev[c], lut_new[c], (size_t)cd->dictionary_count * sizeof(uint32_t), NULL);
+        if (rc == PQPS_OK) rc = pqps_remap_codes(ctx, raw_dev[c], bw, b->stage[c], fw, B, lut_dev[c], (uint32_t)cd->dictionary_count,
+                                                 pqps_remap_form((uint32_t)cd->dictionary_count), words_dev + c, NULL);
+        if (rc != PQPS_OK) { fprintf(stderr, "HIP engine: %s\n", pqps_last_error()); REFUSE(c, "code translation"); }
+    }
+    /* 3. what the device found, and INSERT's rules for command_id and sudo_used on the host */
+    {
+        uint64_t bad[HIPCOL_COUNT];
+        if (pqps_ctx_sync(ctx, NULL) != PQPS_OK || pqps_download(ctx, bad, words_dev, sizeof bad, NULL) != PQPS_OK) REFUSE(-1, "code translation");
+        for (int c = 0; c < HIPCOL_COUNT; c++) if (bad[c]) REFUSE(c, "a code at or past the batch's dictionary count");
+        const uint64_t *ids = columns[HIPCOL_COMMAND_ID].values;
+        const uint8_t *sudo = columns[HIPCOL_SUDO_USED].values;
+        if (columns[HIPCOL_COMMAND_ID].on_device) {
+            id_host = malloc(B * sizeof *id_host);
+            if (!id_host || pqps_download(ctx, id_host, b->stage[HIPCOL_COMMAND_ID], B * sizeof *id_host, NULL) != PQPS_OK) REFUSE(HIPCOL_COMMAND_ID, "column download");
+            ids = id_host;
+        }
+        if (columns[HIPCOL_SUDO_USED].on_device) {
+            sudo_host = malloc(B);
+            if (!sudo_host || pqps_download(ctx, sudo_host, b->stage[HIPCOL_SUDO_USED], B, NULL) != PQPS_OK) REFUSE(HIPCOL_SUDO_USED, "column download");
+            sudo = sudo_host;
+        }
+        for (uint64_t i = 0; i < B; i++) {
+            if (ids[i] == 0) REFUSE(HIPCOL_COMMAND_ID, "command_id 0 is no row's id");
+            if (sudo[i] > 1) REFUSE(HIPCOL_SUDO_USED, "sudo_used is 0 or 1");
+        }
+    }
+out:
+#undef REFUSE
+    free(narrowed); free(fetched); free(id_host); free(sudo_host);
+    for (int c = 0; c < HIPCOL_COUNT; c++) {
+        free(lut_new[c]);
+        if (raw_dev[c]) pqps_free(ctx, raw_dev[c]);
+        if (lut_dev[c]) pqps_free(ctx, lut_dev[c]);
+    }
+    if (words_dev) pqps_free(ctx, words_dev);
+    if (why) return append_refuse(engine, b, why, why_col);
+    return b;
+}
+
+/* The rows form: the batch's dictionaries and codes from the records (as a load builds a table's), then the columns route. */
+struct hipAppend *prepareAppendRowsHIP(struct engineS *engine, const record *rows, unsigned long long num_rows) {
+    const size_t B = (size_t)num_rows;
+    if (!rows || B == 0) return append_refuse(engine, NULL, "no rows", -1);
+    struct hipColumnData cd[HIPCOL_COUNT];
+    struct hipDictionary dict[HIPCOL_COUNT];
+    void *values[HIPCOL_COUNT] = { NULL };
+    memset(cd, 0, sizeof cd);
+    memset(dict, 0, sizeof dict);
+    const record **ptr = malloc(B * sizeof *ptr);
+    bool ok = ptr != NULL;
+    for (size_t i = 0; ok && i < B; i++) ptr[i] = &rows[i];
+    for (int c = 0; ok && c < HIPCOL_COUNT; c++) {
+        const size_t w = k_kind[c] == HIPKIND_DICT ? 4 : k_numeric_width[c];
+        values[c] = malloc(B * w);
+        if (!values[c]) { ok = false; break; }
+        for (size_t i = 0; k_kind[c] != HIPKIND_DICT && i < B; i++) {
+            const char *p = (const char *)&rows[i] + k_offset[c];
+            if (k_kind[c] == HIPKIND_U64) ((uint64_t *)values[c])[i] = *(const uint64_t *)p;
+            else if (k_kind[c] == HIPKIND_I32) ((int32_t *)values[c])[i] = *(const int *)p;
+            else ((uint8_t *)values[c])[i] = *(const bool *)p ? 1 : 0;
+        }
+        if (k_kind[c] == HIPKIND_DICT && build_dictionary((record *const *)ptr, B, k_offset[c], &dict[c], values[c]) != 0) ok = false;
+        cd[c].values = values[c];
+        cd[c].width = (unsigned int)w;
+        cd[c].dictionary = dict[c].values;
+        cd[c].dictionary_count = dict[c].count;
+    }
+    free(ptr);
+    struct hipAppend *b = ok ? prepareAppendColumnsHIP(engine, num_rows, cd) : append_refuse(engine, NULL, "out of memory", -1);
+    for (int c = 0; c < HIPCOL_COUNT; c++) {
+        if (b) { b->batch_dict[c] = dict[c]; b->batch_values[c] = values[c]; }     /* the union points into these strings */
+        else { dictionary_free(&dict[c]); free(values[c]); }
+    }
+    return b;
+}
+
+/* One column buffer of `sh` at `width` bytes per row for the shard's capacity; the rows past `keep_rows` zero. */
+static void *column_buffer(struct hipTable *sh, uint32_t width, uint64_t keep_rows) {
+    void *dev = NULL;
+    if (pqps_malloc(sh->ctx, sh->capacity_rows * width, &dev) != PQPS_OK) hip_die("column allocation");
+    if (pqps_memset(sh->ctx, (char *)dev + keep_rows * width, 0, (sh->capacity_rows - keep_rows) * width, NULL) != PQPS_OK) hip_die("column clear");
+    return dev;
+}
+
+/* The last shard with room for `count` rows: every column and the plane moved to buffers of shard_alloc's capacity for that
+ * count, the lanes' ID buffers and the scan scratch brought along. */
+static void shard_grow(struct hipTable *sh, uint64_t count) {
+    sh->capacity_rows = (count + count / 16 + PQPS_TILE_ROWS) / PQPS_TILE_ROWS * PQPS_TILE_ROWS;
+    for (int c = 0; c < HIPCOL_COUNT; c++) {
+        const uint32_t w = sh->col[c].width;
+        if (!sh->col[c].data) continue;
+        void *dev = column_buffer(sh, w, sh->n_rows);
+        if (pqps_copy_peer(sh->ctx, dev, sh->ctx, sh->col[c].data, sh->n_rows * w, NULL) != PQPS_OK || pqps_ctx_sync(sh->ctx, NULL) != PQPS_OK)
+            hip_die("column copy");
+        pqps_free(sh->ctx, (void *)sh->col[c].data);
+        sh->col[c].data = dev;
+    }
+    if (sh->sudo_bits.data) {                                      /* repacked whole by the caller */
+        pqps_free(sh->ctx, (void *)sh->sudo_bits.data);
+        sh->sudo_bits.data = NULL;
+        if (pqps_malloc(sh->ctx, sh->capacity_rows / 8, (void **)&sh->sudo_bits.data) != PQPS_OK) hip_die("bit plane allocation");
+    }
+    struct hipLane *lanes[HIP_MAX_LANES + 1];
+    int n = 0;
+    lanes[n++] = &sh->own;
+    for (int k = 0; k < sh->n_lanes; k++) lanes[n++] = &sh->lane[k];
+    for (int k = 0; k < n; k++) {
+        if (lanes[k]->ids_dev) pqps_free(sh->ctx, lanes[k]->ids_dev);
+        lanes[k]->ids_dev = NULL;
+        lanes[k]->capacity_ids = sh->capacity_rows;
+        if (pqps_malloc(sh->ctx, lanes[k]->capacity_ids * sizeof(uint32_t), (void **)&lanes[k]->ids_dev) != PQPS_OK) hip_die("result allocation");
+    }
+    if (pqps_ctx_reserve(sh->ctx, sh->capacity_rows) != PQPS_OK) hip_die("filter scratch allocation");
+    if (sh->qs && pqps_qstream_reserve(sh->qs, sh->capacity_rows) != PQPS_OK) hip_die("query stream scratch");
+}
+
+void commitAppendHIP(struct engineS *engine, struct hipAppend *b) {
+    struct hipTable *t = engine->record_block;
+    const int n_shards = hipTableShards(t);
+    struct hipTable *last = hipTableShard(t, n_shards - 1);
+    const uint64_t B = b->rows, first_new = last->n_rows;
+    bool grown = false;
+    uint32_t changed = 0;                                          /* bit c: the codes of column c changed on every shard */
+    /* 1. head-room */
+    if (last->n_rows + B > last->capacity_rows) { shard_grow(last, last->n_rows + B); grown = true; }
+    /* 2. the old rows' codes to their places in the unions: at most one pass per string column and shard */
+    for (int c = 0; c < HIPCOL_COUNT; c++) {
+        if (k_kind[c] != HIPKIND_DICT) continue;
+        const uint32_t tw = t->col[c].width, fw = b->width[c];
+        if (b->identity[c] && fw == tw) continue;
+        changed |= 1u << c;
+        const uint32_t n_lut = tw == 0 ? 1u : (uint32_t)t->dict[c].count;
+        for (int s = 0; s < n_shards; s++) {
+            struct hipTable *sh = hipTableShard(t, s);
+            void *lut_dev = NULL;
+            if (pqps_malloc(sh->ctx, (size_t)(n_lut ? n_lut : 1) * sizeof(uint32_t), &lut_dev) != PQPS_OK) hip_die("code table allocation");
+            if (n_lut && pqps_upload(sh->ctx, lut_dev, b->lut_old[c], (size_t)n_lut * sizeof(uint32_t), NULL) != PQPS_OK) hip_die("code table upload");
+            void *old = (void *)sh->col[c].data, *dst = old;
+            const void *src = old;
+            if (tw == 0) {                                         /* a single-valued column gets its buffer: zeroes, then the old string's new code */
+                dst = column_buffer(sh, fw, 0);
+                src = dst;
+            } else if (fw != tw) {
+                dst = column_buffer(sh, fw, sh->n_rows);
+            }
+            if (n_lut && sh->n_rows &&
+                pqps_remap_codes(sh->ctx, src, tw == 0 ? fw : tw, dst, fw, sh->n_rows, lut_dev, n_lut, pqps_remap_form(n_lut), NULL, NULL) != PQPS_OK)
+                hip_die("dictionary code remap");
+            if (pqps_ctx_sync(sh->ctx, NULL) != PQPS_OK) hip_die("dictionary code remap");
+            pqps_free(sh->ctx, lut_dev);
+            if (dst != old && old) pqps_free(sh->ctx, old);
+            sh->col[c].data = dst;
+            sh->col[c].width = fw;
+        }
+    }
+    /* 3. the new rows behind the last one */
+    for (int c = 0; c < HIPCOL_COUNT; c++) {
+        const uint32_t w = last->col[c].width;
+        if (!w) continue;
+        if (pqps_copy_peer(last->ctx, (char *)last->col[c].data + first_new * w, last->ctx, b->stage[c], B * w, NULL) != PQPS_OK) hip_die("row copy");
+        if (b->have_bounds[c] && t->bounds_known[c]) {             /* a cached group range covers the new rows */
+            if (b->lo[c] < t->bounds_lo[c]) t->bounds_lo[c] = b->lo[c];
+            if (b->hi[c] > t->bounds_hi[c]) t->bounds_hi[c] = b->hi[c];
+        }
+    }
+    if (pqps_ctx_sync(last->ctx, NULL) != PQPS_OK) hip_die("row copy");
+    last->n_rows += B;
+    if (grown) shard_pack_all_bits(last);
+    else shard_pack_bits(last, first_new, (last->n_rows - 1) / 8 + 1);
+    /* 4. the unions become the dictionaries */
+    for (int c = 0; c < HIPCOL_COUNT; c++) {
+        if (k_kind[c] != HIPKIND_DICT || b->merged_count[c] == t->dict[c].count) continue;
+        struct hipDictionary d;
+        memset(&d, 0, sizeof d);
+        if (dictionary_from_strings(&d, b->merged[c], b->merged_count[c]) != 0) { perror("Failed to grow dictionary"); exit(EXIT_FAILURE); }
+        dictionary_free(&t->dict[c]);
+        t->dict[c] = d;
+    }
+    /* 5. the indexes, once: all of the last shard's, elsewhere those whose keys changed */
+    for (int s = 0; s < n_shards; s++) {
+        struct hipTable *sh = hipTableShard(t, s);
+        for (int i = 0; i < engine->num_indexes; i++) {
+            const int c = sh->index[i].column >= 0 ? sh->index[i].column : hipColumnId(engine->indexed_attributes[i]);
+            if (c < 0 || !sh->col[c].data) continue;
+            if (sh == last || (changed & (1u << c))) rebuild_index(engine, sh, i);
+        }
+    }
+    engine->num_records += (int)B;
+    discardAppendHIP(engine, b);
 }

@@ -2981,3 +2981,93 @@ long long executeQueryUpdateHIP(struct engineS *engine, const char *tableName, c
     if (queryTime) *queryTime = now_seconds() - t0;
     return k;
 }
+
+
+/* ---- batch INSERT: any number of rows in one call (include/executeEngine-hip.h) --------------------------------------- */
+
+/* the writer's gate of both forms: -1 with the lock NOT held */
+static int insert_batch_enter(struct engineS *engine, struct hipTable **t_out) {
+    if (!engine || !engine->record_block) return -1;
+    struct hipTable *t = engine->record_block;
+    if (hipTableLockExclusive(t) != 0) return -1;
+    if (t->xch) {
+        fprintf(stderr, "HIP engine: batch INSERT is refused on an engine joined across ranks\n");
+        hipTableUnlockExclusive(t);
+        return -1;
+    }
+    *t_out = t;
+    return 0;
+}
+
+long long executeQueryInsertColumnsHIP(struct engineS *engine, const char *tableName, unsigned long long num_rows,
+                                       const struct hipColumnData columns[12], double *queryTime) {
+    (void)tableName;
+    const double t0 = now_seconds();
+    struct hipTable *t = NULL;
+    if (insert_batch_enter(engine, &t) != 0) return -1;
+    long long k = -1;
+    if (!t->device_only) {
+        fprintf(stderr, "HIP engine: batch INSERT of columns is for engines without host rows; this one keeps rows and a CSV in step: use the rows form\n");
+    } else if (num_rows == 0) {
+        k = 0;
+    } else {
+        struct hipAppend *b = prepareAppendColumnsHIP(engine, num_rows, columns);
+        const double t1 = now_seconds();
+        if (b) {
+            commitAppendHIP(engine, b);
+            k = (long long)num_rows;
+            TRACE("INSERT of %llu rows: merge + staging %.3f ms, remap + append + indexes %.3f ms\n", num_rows, (t1 - t0) * 1e3, (now_seconds() - t1) * 1e3);
+        }
+    }
+    hipTableUnlockExclusive(t);
+    if (queryTime) *queryTime = now_seconds() - t0;
+    return k;
+}
+
+long long executeQueryInsertRowsHIP(struct engineS *engine, const char *tableName, const record *rows, unsigned long long num_rows,
+                                    double *queryTime) {
+    (void)tableName;
+    const double t0 = now_seconds();
+    struct hipTable *t = NULL;
+    if (insert_batch_enter(engine, &t) != 0) return -1;
+    long long k = -1;
+    struct hipAppend *b = NULL;
+    if (num_rows == 0) k = 0;
+    else if (!rows) fprintf(stderr, "HIP engine: batch INSERT: no rows\n");
+    else b = prepareAppendRowsHIP(engine, rows, num_rows);
+    if (b && !t->device_only) {
+        /* the host rows and the CSV, as B single INSERTs leave them: room first, then the file, then the rows */
+        const size_t n = (size_t)engine->num_records, total = n + (size_t)num_rows;
+        bool ok = true;
+        if (total > t->row_capacity) {
+            const size_t cap = total + total / 8 + 64;
+            record *block = realloc(t->row_block, cap * sizeof *block);
+            if (block) {
+                if (block != t->row_block) for (size_t i = 0; i < n; i++) engine->all_records[i] = &block[i];
+                t->row_block = block;
+            }
+            record **ptrs = block ? realloc(engine->all_records, cap * sizeof *ptrs) : NULL;
+            if (ptrs) engine->all_records = ptrs;
+            ok = block && ptrs;
+            if (ok) t->row_capacity = cap;
+        }
+        FILE *f = ok ? fopen(engine->datafile, "a") : NULL;
+        if (!f) {
+            fprintf(stderr, "HIP engine: batch INSERT: no room for the host rows, or the CSV cannot be appended to\n");
+            discardAppendHIP(engine, b);
+            b = NULL;
+        } else {
+            write_csv_table(f, rows, (size_t)num_rows);
+            fclose(f);
+            memcpy(&t->row_block[n], rows, (size_t)num_rows * sizeof *rows);
+            for (size_t i = n; i < total; i++) engine->all_records[i] = &t->row_block[i];
+        }
+    }
+    if (b) {
+        commitAppendHIP(engine, b);
+        k = (long long)num_rows;
+    }
+    hipTableUnlockExclusive(t);
+    if (queryTime) *queryTime = now_seconds() - t0;
+    return k;
+}

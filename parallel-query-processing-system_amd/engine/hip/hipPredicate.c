@@ -971,3 +971,51 @@ int hipCompileAssignments(const struct hipSchema *schema, const char *const *col
     memcpy(out, a, (size_t)n * sizeof *a);
     return 0;
 }
+
+/* ---- the dictionary merge of a batch INSERT ----------------------------------------------------------------------- */
+
+static int merge_fail(int column, const char *what) {
+    fprintf(stderr, "HIP engine: dictionary merge, column %d: %s\n", column, what);
+    return -1;
+}
+
+/* 0 when the list is strictly ascending, free of empty strings and of strings longer than the field */
+static int merge_check(const char *const *values, int count, size_t room, int column, const char *which) {
+    for (int i = 0; i < count; i++) {
+        if (!values[i]) return merge_fail(column, "a NULL string");
+        if (!values[i][0]) return merge_fail(column, "an empty string");
+        if (strlen(values[i]) + 1 > room) return merge_fail(column, "a string does not fit the record's field");
+        if (i > 0 && strcmp(values[i - 1], values[i]) >= 0) return merge_fail(column, which);
+    }
+    return 0;
+}
+
+int hipMergeDictionaries(const char *const *old_values, int old_count, const char *const *new_values, int new_count, int column,
+                         const char **merged, int *merged_count, uint32_t *lut_old, uint32_t *lut_new, int *identity) {
+    if (!merged || !merged_count || !lut_old || !lut_new || !identity || (!old_values && old_count > 0) || (!new_values && new_count > 0))
+        return merge_fail(column, "NULL argument");
+    if (old_count < 0 || new_count < 0) return merge_fail(column, "a negative count");
+    if (column < 0 || column >= PQPS_MAX_COLUMNS || field_bytes(column) == 0) return merge_fail(column, "not a string column");
+    const size_t room = field_bytes(column);
+    if (merge_check(old_values, old_count, room, column, "the old list is not strictly ascending") != 0 ||
+        merge_check(new_values, new_count, room, column, "the new list is not strictly ascending") != 0)
+        return -1;
+    /* nothing is refused from here on: the outputs may be written */
+    int i = 0, k = 0, m = 0, same = 1;
+    while (i < old_count || k < new_count) {
+        const int c = i >= old_count ? 1 : k >= new_count ? -1 : strcmp(old_values[i], new_values[k]);
+        if (c <= 0) {
+            merged[m] = old_values[i];
+            if (m != i) same = 0;
+            lut_old[i++] = (uint32_t)m;
+            if (c == 0) lut_new[k++] = (uint32_t)m;
+        } else {
+            merged[m] = new_values[k];
+            lut_new[k++] = (uint32_t)m;
+        }
+        m++;
+    }
+    *merged_count = m;
+    *identity = same;
+    return 0;
+}
