@@ -355,6 +355,55 @@ struct hipAggregateResult *executeQueryAggregateHIP(struct engineS *engine, cons
                                                     struct whereClauseS *whereClause);
 void freeAggregateResultHIP(struct hipAggregateResult *result);
 
+/* GROUP BY buckets: COUNT(*), or COUNT / SUM / MIN / MAX of one numeric column, per PREFIX of a string column or per RANGE
+ * of an i32 column -- "how many per hour / per day" of the ISO-8601 `timestamp` (prefix 13 is an hour, 10 a day, 7 a month),
+ * user_id in ranges of 100 (no aggregates in the reference; reached through the C API and the Python package only, like the
+ * grouped COUNT above).
+ * BUCKETS: HIPBUCKET_PREFIX, bucketArg = k >= 1, a string column: the bucket of a row is the first min(k, strlen) bytes of
+ * its string; keys[g] is the lowest dictionary code of the bucket at the time of the query, keyText[g] the truncated string.
+ * HIPBUCKET_WIDTH, bucketArg = w >= 1, an i32 column: the bucket is floor(value / w), floor towards minus infinity;
+ * keys[g] is its lower bound floor(value / w) * w (it may lie below INT_MIN), keyText[g] is %lld of it.
+ * ROWS: exactly the rows executeQuerySelectIdsHIP(engine, whereClause) returns -- in index mode too, so a row several probed
+ * conditions return more than once counts that many times; `total` equals that call's count.  Only buckets with at least one
+ * row are listed, in ascending key order (strcmp order of the prefixes, numeric order of the lower bounds).
+ * VALUES (valueColumn != NULL): as executeQueryAggregateHIP -- i32 sums exact in int64, command_id sums modulo 2^64 with
+ * unsigned min / max, returned as the u64 bits (valueKind says which).  Without a value column sums, mins and maxs are NULL.
+ * MARGINALS: for every WHERE, adding executeQueryGroupCountHIP's counts over the values of a bucket gives that bucket's
+ * count; a prefix longer than every string (and a width of 1) gives exactly executeQueryGroupCountHIP's groups.
+ * SPECIAL CASES: a NULL WHERE groups the whole table; no match, or an empty table, gives numGroups = 0 with success = true;
+ * a single-valued dictionary column (no device buffer) gives one bucket from the selection, with no bucket kernel -- with a
+ * value column the ungrouped aggregate.
+ * REFUSED (success = false, the reason on stderr): everything hipBucketBounds refuses (k < 1 or w < 1, PREFIX on a numeric
+ * or boolean column, WIDTH on a string or boolean column, command_id, an unknown column, more than 65 536 buckets), an
+ * unknown value column, a dictionary or boolean value column, an engine joined across ranks.  NOT refused: a dictionary of
+ * any size (timestamp on a 1 M-row CSV) or an i32 column spanning more than 65 536 values, while the BUCKETS are at most
+ * 65 536.  A reader like COUNT: shared lock and one query lane; the lane rules above apply.
+ * Execution: the bounds (the ascending run starts of the buckets in bin space, hipBucketBounds) are built once per query on
+ * the host and uploaded once per shard into scratch of the query's own, freed with it.  A single-pass scan-mode WHERE runs
+ * ONE fused launch per shard (pqps_filter_group_buckets / pqps_filter_aggregate_buckets); index probes, WHEREs of several
+ * passes and fragmented LIKE / IN sets run the selection and then pqps_group_buckets_list / pqps_aggregate_buckets_list over
+ * each shard's list; shards' buckets are added or merged on the host.  The i32 range is the table's cached one (it may be
+ * wider than the data after a DELETE: empty buckets are never listed). */
+enum { HIPBUCKET_PREFIX = 1, HIPBUCKET_WIDTH = 2 };
+struct hipBucketResult {
+    int groupColumn, groupKind;        /* HIPCOL_*, HIPKIND_DICT / HIPKIND_I32                           */
+    int bucketMode;                    /* HIPBUCKET_*                                                    */
+    long long bucketArg;               /* k or w                                                         */
+    int valueColumn, valueKind;        /* -1 / -1: no value column, COUNT(*) per bucket only             */
+    int numGroups;                     /* buckets with at least one row, ascending key order             */
+    long long total;                   /* sum of counts = executeQuerySelectIdsHIP's count               */
+    long long *keys;                   /* lowest code of the prefix's run / lower bound of the range     */
+    char **keyText;                    /* owned: the truncated string / %lld of the lower bound          */
+    unsigned long long *counts;
+    long long *sums, *mins, *maxs;     /* NULL without a value column; u64 bits for command_id           */
+    double queryTime;
+    bool success;
+};
+struct hipBucketResult *executeQueryGroupBucketsHIP(struct engineS *engine, const char *groupColumn, int bucketMode,
+                                                    long long bucketArg, const char *valueColumn /* may be NULL */,
+                                                    struct whereClauseS *whereClause);
+void freeBucketResultHIP(struct hipBucketResult *result);
+
 /* COUNT(DISTINCT one column), overall or per group (no aggregates in the reference; reached through the C API and the
  * Python package only, like the grouped COUNT above -- the SQL driver has no COUNT(DISTINCT ...), so its output stays that
  * of QPESeq).

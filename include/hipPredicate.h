@@ -19,6 +19,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "executeEngine-serial.h"
+#include "executeEngine-hip.h"
 #include "pqps_hip.h"
 
 #ifdef __cplusplus
@@ -130,6 +131,27 @@ int hipCompileAssignments(const struct hipSchema *schema, const char *const *col
  * serial:544-551), a string that does not fit its field with its NUL (the limit hipCompileAssignments enforces). */
 int hipMergeDictionaries(const char *const *old_values, int old_count, const char *const *new_values, int new_count, int column,
                          const char **merged, int *merged_count, uint32_t *lut_old, uint32_t *lut_new, int *identity);
+
+/* THE BUCKETS OF GROUP BY PREFIX(k) / WIDTH(w).  Dictionary codes are ranks in strcmp order and truncation to k bytes is
+ * monotone under strcmp, so the strings of one prefix are one run of codes; the values of one width bucket are one run of
+ * value - lo.  Both are therefore a short ascending list of run starts in bin space (code, or value - lo); pure host code.
+ *   PREFIX (arg = k >= 1, a string column: dict[0 .. dict_count) ascending; lo / hi unused)
+ *       bucket of a string = its first min(k, strlen) bytes; a bucket starts at every entry whose truncation differs from
+ *       its predecessor's; key = the lowest code of the run (the key text is dict[key] cut to k bytes)
+ *   WIDTH  (arg = w >= 1, an i32 column whose values lie in [lo, hi]; dict unused)
+ *       bucket = floor(value / w) towards minus infinity; key = its lower bound floor(value / w) * w, which may lie below
+ *       INT_MIN (the key text is %lld of it); run start j = max(lower bound j, lo) - lo; floor(hi / w) - floor(lo / w) + 1
+ *       buckets
+ *   (*bounds)[0 .. *n_buckets]   the run starts and, last, the sentinel: [0] == 0, strictly ascending, [*n_buckets] == the
+ *                                domain (dict_count, or hi - lo + 1) -- what pqps_filter_group_buckets takes
+ *   (*keys)[0 .. *n_buckets)     the key of every bucket
+ * Both are malloc'd; the caller frees them.  Returns 0, or -1 with the reason on stderr and every output untouched for: a
+ * NULL output, an unknown column, command_id, arg < 1, PREFIX on a numeric or boolean column, WIDTH on a string or boolean
+ * column, an empty dictionary or range, a range of 2^32 values (no u32 holds its sentinel), more than HIPBUCKET_MAX
+ * buckets. */
+#define HIPBUCKET_MAX 65536u     /* mode: HIPBUCKET_PREFIX / HIPBUCKET_WIDTH of executeEngine-hip.h */
+int hipBucketBounds(const char *column, const char *const *dict, int dict_count, int lo, int hi, int mode, long long arg,
+                    uint32_t **bounds, long long **keys, uint32_t *n_buckets);
 
 /* Column name -> HIPCOL_* id, -1 if unknown. */
 int hipColumnId(const char *name);

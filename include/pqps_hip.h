@@ -494,6 +494,39 @@ int pqps_aggregate_list(pqps_ctx *ctx, const pqps_column *value_col, const pqps_
                         const uint32_t *ids, const uint64_t *count_dev, uint64_t capacity, uint32_t id_base, uint32_t bin_base,
                         uint32_t n_bins, uint64_t *out, void *stream);
 
+/* ---- GROUP BY buckets: COUNT(*) and COUNT / SUM / MIN / MAX per run of bins -------------------------------------------
+ * No counterpart in the reference.  A BUCKET is a contiguous run of the bins of pqps_filter_group ((value - bin_base) in
+ * 32-bit arithmetic): the codes of the strings that share a prefix, the values of one range of an i32 column.  `bounds_dev`
+ * holds n_buckets + 1 u32 device words, the ascending run starts in bin space: bounds[0] == 0, strictly ascending,
+ * bounds[n_buckets] == `domain` (hipBucketBounds makes them).  The bucket of a row with bin b is
+ *     (number of entries of bounds[0 .. n_buckets] that are <= b) - 1,
+ * and a row whose bucket is >= n_buckets is left out: exactly the rows with b >= domain.  Whatever `bounds_dev` holds,
+ * nothing outside the output is written.  The four calls are asynchronous on `stream`, initialise their output themselves
+ * and return PQPS_EINVAL for n_buckets 0 or above 65 536, a NULL `bounds_dev`, and `domain` 0 or below n_buckets.
+ *
+ * pqps_filter_group_buckets: pqps_filter_group per bucket -- ONE scan; `group_col` 1, 2 or 4 bytes wide (no bit plane), read
+ *   only in steps that hold a match; bins[0 .. n_buckets) u32 device words.  The readable-padding rule of pqps_filter_scan
+ *   applies to the predicate columns and `group_col`.  The bounds sit in LDS while they fit beside the bins (a workgroup
+ *   takes at most 64 KiB); n_buckets <= 16: per-lane counters; <= 8191: a histogram in LDS; up to 65 536: atomics straight
+ *   into the bins (a correctness path), with the bounds in LDS up to 16 383 buckets and read from global memory above.
+ * pqps_group_buckets_list: the same over an ID list, as pqps_group_list.
+ * pqps_filter_aggregate_buckets: pqps_filter_aggregate per bucket; `value_col` 4 bytes (signed i32) or 8 bytes (u64);
+ *   out[4 * n_buckets] u64 device words in that call's field-major layout, images and empty-bin values (0, 0, UINT64_MAX,
+ *   0).  n_buckets <= 2047: a table in LDS beside the bounds; above: atomics straight into `out`, bounds as above.
+ * pqps_aggregate_buckets_list: the same over an ID list, as pqps_aggregate_list. */
+int pqps_filter_group_buckets(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                              const pqps_column *group_col, uint32_t bin_base, const uint32_t *bounds_dev, uint32_t n_buckets,
+                              uint32_t domain, uint32_t *bins, void *stream);
+int pqps_group_buckets_list(pqps_ctx *ctx, const pqps_column *group_col, uint64_t n_rows, const uint32_t *ids, const uint64_t *count_dev,
+                            uint64_t capacity, uint32_t id_base, uint32_t bin_base, const uint32_t *bounds_dev, uint32_t n_buckets,
+                            uint32_t domain, uint32_t *bins, void *stream);
+int pqps_filter_aggregate_buckets(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                                  const pqps_column *value_col, const pqps_column *group_col, uint32_t bin_base,
+                                  const uint32_t *bounds_dev, uint32_t n_buckets, uint32_t domain, uint64_t *out, void *stream);
+int pqps_aggregate_buckets_list(pqps_ctx *ctx, const pqps_column *value_col, const pqps_column *group_col, uint64_t n_rows,
+                                const uint32_t *ids, const uint64_t *count_dev, uint64_t capacity, uint32_t id_base, uint32_t bin_base,
+                                const uint32_t *bounds_dev, uint32_t n_buckets, uint32_t domain, uint64_t *out, void *stream);
+
 /* ---- ORDER BY column [DESC] LIMIT K ------------------------------------------------------------------------------
  * No counterpart in the reference (it parses ORDER BY and executes none).  KEYS: every row is one composite key whose
  * ascending unsigned order is the answer's order -- the column's order-preserving image ascending (descending with

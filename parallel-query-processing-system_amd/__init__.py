@@ -120,6 +120,15 @@ class AggregateResult(C.Structure):
                 ("queryTime", C.c_double), ("success", C.c_bool)]
 
 
+class BucketResult(C.Structure):
+    """struct hipBucketResult (include/executeEngine-hip.h)."""
+    _fields_ = [("groupColumn", C.c_int), ("groupKind", C.c_int), ("bucketMode", C.c_int), ("bucketArg", C.c_longlong),
+                ("valueColumn", C.c_int), ("valueKind", C.c_int), ("numGroups", C.c_int), ("total", C.c_longlong),
+                ("keys", C.POINTER(C.c_longlong)), ("keyText", C.POINTER(C.c_char_p)), ("counts", C.POINTER(C.c_ulonglong)),
+                ("sums", C.POINTER(C.c_longlong)), ("mins", C.POINTER(C.c_longlong)), ("maxs", C.POINTER(C.c_longlong)),
+                ("queryTime", C.c_double), ("success", C.c_bool)]
+
+
 class GroupPairResult(C.Structure):
     """struct hipGroupPairResult (include/executeEngine-hip.h)."""
     _fields_ = [("groupColumn", C.c_int * 2), ("groupKind", C.c_int * 2), ("valueColumn", C.c_int), ("valueKind", C.c_int),
@@ -487,6 +496,17 @@ def lib():
     L.pqps_filter_aggregate.argtypes = [vp, C.POINTER(Column), u32, u64, C.POINTER(Predicate), C.POINTER(Column), C.POINTER(Column),
                                         u32, u32, vp, vp]
     L.pqps_aggregate_list.argtypes = [vp, C.POINTER(Column), C.POINTER(Column), u64, vp, vp, u64, u32, u32, u32, vp, vp]
+    L.executeQueryGroupBucketsHIP.restype = C.POINTER(BucketResult)
+    L.executeQueryGroupBucketsHIP.argtypes = [E, C.c_char_p, C.c_int, C.c_longlong, C.c_char_p, W]
+    L.freeBucketResultHIP.argtypes = [C.POINTER(BucketResult)]
+    L.freeBucketResultHIP.restype = None
+    L.pqps_filter_group_buckets.argtypes = [vp, C.POINTER(Column), u32, u64, C.POINTER(Predicate), C.POINTER(Column), u32, vp, u32, u32, vp, vp]
+    L.pqps_group_buckets_list.argtypes = [vp, C.POINTER(Column), u64, vp, vp, u64, u32, u32, vp, u32, u32, vp, vp]
+    L.pqps_filter_aggregate_buckets.argtypes = [vp, C.POINTER(Column), u32, u64, C.POINTER(Predicate), C.POINTER(Column), C.POINTER(Column),
+                                                u32, vp, u32, u32, vp, vp]
+    L.pqps_aggregate_buckets_list.argtypes = [vp, C.POINTER(Column), C.POINTER(Column), u64, vp, vp, u64, u32, u32, vp, u32, u32, vp, vp]
+    L.hipBucketBounds.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong,
+                                  C.POINTER(C.POINTER(u32)), C.POINTER(C.POINTER(C.c_longlong)), C.POINTER(u32)]
     L.executeQueryGroupPairHIP.restype = C.POINTER(GroupPairResult)
     L.executeQueryGroupPairHIP.argtypes = [E, C.c_char_p, C.c_char_p, C.c_char_p, W]
     L.freeGroupPairResultHIP.argtypes = [C.POINTER(GroupPairResult)]
@@ -708,6 +728,27 @@ def merge_dictionaries(old, new, column="user_name"):
     if lib().hipMergeDictionaries(a, len(old), b, len(new), COL[column], merged, C.byref(count), lut_old, lut_new, C.byref(identity)) != 0:
         raise PqpsError("hipMergeDictionaries refused the lists (reason on stderr)")
     return list(merged[:count.value]), list(lut_old[:len(old)]), list(lut_new[:len(new)]), bool(identity.value)
+
+
+BUCKET_PREFIX, BUCKET_WIDTH = 1, 2                          # HIPBUCKET_* (include/executeEngine-hip.h)
+
+
+def bucket_bounds(column, mode, arg, dictionary=None, lo=0, hi=0):
+    """hipBucketBounds: (bounds, keys) of the buckets of `column` -- `dictionary` an ascending list of bytes (BUCKET_PREFIX,
+    arg = prefix length) or [lo, hi] the i32 range (BUCKET_WIDTH, arg = width).  bounds: the n + 1 ascending run starts in
+    bin space, the last one the domain; keys: the n keys.  Raises PqpsError when it is refused (reason on stderr)."""
+    values = list(dictionary) if dictionary is not None else []
+    d = (C.c_char_p * max(1, len(values)))(*values)
+    bounds, keys, n = C.POINTER(C.c_uint32)(), C.POINTER(C.c_longlong)(), C.c_uint32()
+    name = column.encode() if isinstance(column, str) else column
+    if lib().hipBucketBounds(name, d if dictionary is not None else None, len(values), lo, hi, mode, arg,
+                             C.byref(bounds), C.byref(keys), C.byref(n)) != 0:
+        raise PqpsError("hipBucketBounds refused the buckets (reason on stderr)")
+    try:
+        return list(bounds[:n.value + 1]), list(keys[:n.value])
+    finally:
+        lib().free(C.cast(bounds, C.c_void_p))
+        lib().free(C.cast(keys, C.c_void_p))
 
 
 # ---- device objects ----------------------------------------------------------------------------
@@ -1063,6 +1104,32 @@ class HipEngine:
                      fix(r.sums[g]), fix(r.mins[g]), fix(r.maxs[g])) for g in range(r.numGroups)]
         finally:
             lib().freeAggregateResultHIP(res)
+
+    def group_buckets(self, column, prefix=None, width=None, value_column=None, chain=None):
+        """executeQueryGroupBucketsHIP: the rows select_ids(chain) returns, grouped by the first `prefix` bytes of a string
+        column or by floor(value / `width`) of an i32 column (exactly one of the two is given) -- [(key_text, count), ...]
+        in key order, or [(key_text, count, sum, min, max), ...] with a `value_column` (Python ints; command_id's unsigned).
+        key_text is the truncated string, or the range's lower bound.  Raises PqpsError when the engine refuses (reason on
+        stderr)."""
+        if (prefix is None) == (width is None):
+            raise ValueError("group_buckets: exactly one of prefix / width")
+        mode, arg = (BUCKET_PREFIX, prefix) if width is None else (BUCKET_WIDTH, width)
+        wl = WhereList(chain)
+        res = lib().executeQueryGroupBucketsHIP(self.e, column.encode(), mode, arg, value_column.encode() if value_column else None, wl.ptr)
+        what = f"group_buckets({column!r}, prefix={prefix!r}, width={width!r}, {value_column!r})"
+        if not res:
+            raise PqpsError(f"{what}: no result")
+        try:
+            r = res.contents
+            if not r.success:
+                raise PqpsError(f"{what} refused or failed (reason on stderr)")
+            texts = [r.keyText[g].decode("latin-1") for g in range(r.numGroups)]
+            if r.valueColumn < 0:
+                return [(texts[g], int(r.counts[g])) for g in range(r.numGroups)]
+            fix = (lambda x: x & 0xFFFFFFFFFFFFFFFF) if r.valueKind == HIPKIND_U64 else int
+            return [(texts[g], int(r.counts[g]), fix(r.sums[g]), fix(r.mins[g]), fix(r.maxs[g])) for g in range(r.numGroups)]
+        finally:
+            lib().freeBucketResultHIP(res)
 
     def group_pair_total(self, group_columns, value_column=None, chain=None):
         """executeQueryGroupPairHIP: (pairs, total, seconds) -- `pairs` as group_pair() returns them, total =

@@ -23,6 +23,7 @@
 #include "pqps_hip.h"
 #include "filter_kernels.hpp"
 #include "fused_common.hpp"
+#include "bucket_kernels.hpp"
 #include "member_kernels.hpp"
 #include "group_kernels.hpp"
 #include "aggregate_kernels.hpp"
@@ -3118,6 +3119,186 @@ int pqps_aggregate_list(pqps_ctx *ctx, const pqps_column *value_col, const pqps_
                        value_col->data, gdata, wl, n_rows, ids, count_dev, capacity, id_base, bin_base, n_bins, out);
     HIP_TRY(hipGetLastError());
     return PQPS_OK;
+}
+
+// ---- GROUP BY buckets (bucket_kernels.hpp) ---------------------------------------------------------------------------
+// The bins path and where the bounds live, by the number of buckets (the limits: bucket_kernels.hpp).  `small_ok`: the
+// per-lane counters of the COUNT scan.  *lds = the dynamic LDS of a workgroup.
+static int bucket_path(uint32_t nb, bool valued, bool small_ok, bool *blds, uint32_t *lds) {
+    const uint32_t bounds_bytes = (nb + 1u) * (uint32_t)sizeof(uint32_t);
+    const uint32_t lds_max = valued ? kBucketAggLds : kBucketCountLds;
+    const int path = !valued && small_ok && nb <= kBucketSmall ? BUCKET_SMALL : nb <= lds_max ? BUCKET_LDS : BUCKET_GLOBAL;
+    *blds = nb <= kBucketBoundsLds;
+    *lds = (*blds ? bounds_bytes : 0u) + (path == BUCKET_LDS ? nb * (valued ? kBucketAggBinBytes : (uint32_t)sizeof(uint32_t)) : 0u);
+    return path;
+}
+
+static int check_buckets(const uint32_t *bounds_dev, uint32_t n_buckets, uint32_t domain) {
+    if (n_buckets == 0 || n_buckets > kBucketMax) return fail(PQPS_EINVAL, "%u buckets: 1 .. %u", n_buckets, kBucketMax);
+    if (!bounds_dev) return fail(PQPS_EINVAL, "bounds is NULL");
+    if (domain == 0 || domain < n_buckets) return fail(PQPS_EINVAL, "domain %u: at least one bin per bucket (%u)", domain, n_buckets);
+    return PQPS_OK;
+}
+
+static uint32_t bucket_top(uint32_t n_buckets) {
+    uint32_t top = 1;
+    while (top * 2u <= n_buckets + 1u) top *= 2u;
+    return top;
+}
+
+// the output of the four calls: n_buckets u32 bins, or the [4][n_buckets] u64 fields of pqps_filter_aggregate
+static int init_bucket_out(void *out, uint32_t n_buckets, bool valued, hipStream_t s) {
+    if (valued) return init_aggregate_out((uint64_t *)out, n_buckets, s);
+    HIP_TRY(hipMemsetAsync(out, 0, (size_t)n_buckets * sizeof(uint32_t), s));
+    return PQPS_OK;
+}
+
+// value_col == NULL: COUNT(*) per bucket
+static int filter_buckets(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                          const pqps_column *value_col, const pqps_column *group_col, uint32_t bin_base, const uint32_t *bounds_dev,
+                          uint32_t n_buckets, uint32_t domain, void *out, void *stream) {
+    if (!ctx || !group_col || !out) return fail(PQPS_EINVAL, "ctx/group_col/out is NULL");
+    const bool valued = value_col != nullptr;
+    BucketArgs g;
+    memset(&g, 0, sizeof g);
+    int rc = check_buckets(bounds_dev, n_buckets, domain);
+    if (rc == PQPS_OK) rc = valued ? check_aggregate_cols(value_col, group_col, n_buckets, false, &g.gwidth_log2)
+                                   : column_width_code("group", group_col, false, false, true, &g.gwidth_log2);
+    if (rc == PQPS_OK) rc = fused_args(g.e, cols, n_cols, n_rows, pred);
+    if (rc) return rc;
+    hipStream_t s = pick_stream(ctx, stream);
+    rc = init_bucket_out(out, n_buckets, valued, s);
+    if (rc || n_rows == 0) return rc;
+    bool blds;
+    uint32_t lds;
+    const int path = bucket_path(n_buckets, valued, true, &blds, &lds);
+    const uint32_t grid = fused_grid(ctx, n_rows, lds);
+    const uint32_t stride = (n_buckets + 63u) & ~63u;
+    if (path != BUCKET_GLOBAL) {
+        rc = grow_group_parts(ctx, s, valued ? (size_t)grid * kAggFields * n_buckets * 2 : (size_t)grid * stride);
+        if (rc) return rc;
+    }
+    g.gcol = group_col->data;
+    g.vcol = valued ? value_col->data : nullptr;
+    g.bounds = bounds_dev;
+    g.out = out;
+    g.parts = ctx->group_parts;
+    g.stride = stride;
+    g.bin_base = bin_base;
+    g.n_buckets = n_buckets;
+    g.top = bucket_top(n_buckets);
+    const int nt = g.e.streaming ? 1 : 0;
+    // the instances and their names side by side: pqps_last_kernel() reports the entry that is launched.  Index: SMALL, LDS,
+    // GLOBAL with the bounds in LDS, GLOBAL with the bounds in global memory (the aggregates have no SMALL).
+    typedef struct { void (*fn)(const BucketArgs); const char *name; } entry;
+    static const entry count_fns[4][2] = {
+#define PQPS_BUCKET_SCAN(P, B, NT) {bucket_scan_kernel<P, B, NT>, "bucket_scan_kernel<" #P ", BLDS=" #B ", NT=" #NT ">"}
+        {PQPS_BUCKET_SCAN(BUCKET_SMALL, true, false), PQPS_BUCKET_SCAN(BUCKET_SMALL, true, true)},
+        {PQPS_BUCKET_SCAN(BUCKET_LDS, true, false), PQPS_BUCKET_SCAN(BUCKET_LDS, true, true)},
+        {PQPS_BUCKET_SCAN(BUCKET_GLOBAL, true, false), PQPS_BUCKET_SCAN(BUCKET_GLOBAL, true, true)},
+        {PQPS_BUCKET_SCAN(BUCKET_GLOBAL, false, false), PQPS_BUCKET_SCAN(BUCKET_GLOBAL, false, true)},
+#undef PQPS_BUCKET_SCAN
+    };
+    static const entry agg_fns[4][2][2] = {
+#define PQPS_BUCKET_AGG(P, B, U64, V, NT) {bucket_agg_scan_kernel<P, B, U64, NT>, "bucket_agg_scan_kernel<" #P ", BLDS=" #B ", " V ", NT=" #NT ">"}
+#define PQPS_BUCKET_AGG4(P, B) {{PQPS_BUCKET_AGG(P, B, false, "i32", false), PQPS_BUCKET_AGG(P, B, false, "i32", true)}, \
+                                {PQPS_BUCKET_AGG(P, B, true, "u64", false), PQPS_BUCKET_AGG(P, B, true, "u64", true)}}
+        {{{nullptr, ""}, {nullptr, ""}}, {{nullptr, ""}, {nullptr, ""}}},
+        PQPS_BUCKET_AGG4(BUCKET_LDS, true),
+        PQPS_BUCKET_AGG4(BUCKET_GLOBAL, true),
+        PQPS_BUCKET_AGG4(BUCKET_GLOBAL, false),
+#undef PQPS_BUCKET_AGG4
+#undef PQPS_BUCKET_AGG
+    };
+    const int row = path == BUCKET_GLOBAL && !blds ? 3 : path;
+    const entry &scan = valued ? agg_fns[row][value_col->width == 8 ? 1 : 0][nt] : count_fns[row][nt];
+    snprintf(g_kernel, sizeof g_kernel, "%s", scan.name);
+    hipEvent_t stop;
+    rc = fused_launch(ctx, scan.fn, grid, lds, s, g, &stop);
+    if (rc) return rc;
+    if (path != BUCKET_GLOBAL) {
+        if (valued) {
+            const dim3 sg((n_buckets + 63u) / 64u, (grid + kAggSumParts - 1) / kAggSumParts);
+            rc = launch_stop(agg_sum_kernel, sg, 0, s, stop, (const uint64_t *)ctx->group_parts, grid, n_buckets, (uint64_t *)out);
+        } else {
+            const dim3 sg(stride / 64u, (grid + kGroupSumParts - 1) / kGroupSumParts);
+            rc = launch_stop(group_sum_kernel, sg, 0, s, stop, (const uint32_t *)ctx->group_parts, grid, stride, n_buckets, (uint32_t *)out);
+        }
+        if (rc) return rc;
+    }
+    fused_close(ctx, stop, path == BUCKET_GLOBAL);
+    return PQPS_OK;
+}
+
+static int list_buckets(pqps_ctx *ctx, const pqps_column *value_col, const pqps_column *group_col, uint64_t n_rows, const uint32_t *ids,
+                        const uint64_t *count_dev, uint64_t capacity, uint32_t id_base, uint32_t bin_base, const uint32_t *bounds_dev,
+                        uint32_t n_buckets, uint32_t domain, void *out, void *stream) {
+    if (!ctx || !group_col || !out || !count_dev || (capacity && !ids)) return fail(PQPS_EINVAL, "NULL argument");
+    const bool valued = value_col != nullptr;
+    BucketListArgs g;
+    memset(&g, 0, sizeof g);
+    int rc = check_buckets(bounds_dev, n_buckets, domain);
+    if (rc == PQPS_OK) rc = valued ? check_aggregate_cols(value_col, group_col, n_buckets, false, &g.gwidth_log2)
+                                   : column_width_code("group", group_col, false, false, false, &g.gwidth_log2);   // gathered by row
+    if (rc) return rc;
+    hipStream_t s = pick_stream(ctx, stream);
+    rc = init_bucket_out(out, n_buckets, valued, s);
+    if (rc || capacity == 0 || n_rows == 0) return rc;
+    bool blds;
+    uint32_t lds;
+    const int path = bucket_path(n_buckets, valued, false, &blds, &lds);
+    g.gcol = group_col->data;
+    g.vcol = valued ? value_col->data : nullptr;
+    g.bounds = bounds_dev;
+    g.ids = ids;
+    g.count = count_dev;
+    g.out = out;
+    g.n_rows = n_rows;
+    g.capacity = capacity;
+    g.id_base = id_base;
+    g.bin_base = bin_base;
+    g.n_buckets = n_buckets;
+    g.top = bucket_top(n_buckets);
+    typedef void (*list_fn)(const BucketListArgs);
+    // LDS, GLOBAL with the bounds in LDS, GLOBAL with the bounds in global memory
+    static const list_fn count_fns[3] = {bucket_list_kernel<BUCKET_LDS, true>, bucket_list_kernel<BUCKET_GLOBAL, true>,
+                                         bucket_list_kernel<BUCKET_GLOBAL, false>};
+    static const list_fn agg_fns[3][2] = {
+        {bucket_agg_list_kernel<BUCKET_LDS, true, false>, bucket_agg_list_kernel<BUCKET_LDS, true, true>},
+        {bucket_agg_list_kernel<BUCKET_GLOBAL, true, false>, bucket_agg_list_kernel<BUCKET_GLOBAL, true, true>},
+        {bucket_agg_list_kernel<BUCKET_GLOBAL, false, false>, bucket_agg_list_kernel<BUCKET_GLOBAL, false, true>},
+    };
+    const int row = path == BUCKET_LDS ? 0 : blds ? 1 : 2;
+    hipLaunchKernelGGL(valued ? agg_fns[row][value_col->width == 8 ? 1 : 0] : count_fns[row], dim3(list_grid(ctx, capacity, 4)), dim3(kBlock),
+                       lds, s, g);
+    HIP_TRY(hipGetLastError());
+    return PQPS_OK;
+}
+
+int pqps_filter_group_buckets(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                              const pqps_column *group_col, uint32_t bin_base, const uint32_t *bounds_dev, uint32_t n_buckets,
+                              uint32_t domain, uint32_t *bins, void *stream) {
+    return filter_buckets(ctx, cols, n_cols, n_rows, pred, nullptr, group_col, bin_base, bounds_dev, n_buckets, domain, bins, stream);
+}
+
+int pqps_group_buckets_list(pqps_ctx *ctx, const pqps_column *group_col, uint64_t n_rows, const uint32_t *ids, const uint64_t *count_dev,
+                            uint64_t capacity, uint32_t id_base, uint32_t bin_base, const uint32_t *bounds_dev, uint32_t n_buckets,
+                            uint32_t domain, uint32_t *bins, void *stream) {
+    return list_buckets(ctx, nullptr, group_col, n_rows, ids, count_dev, capacity, id_base, bin_base, bounds_dev, n_buckets, domain, bins, stream);
+}
+
+int pqps_filter_aggregate_buckets(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                                  const pqps_column *value_col, const pqps_column *group_col, uint32_t bin_base,
+                                  const uint32_t *bounds_dev, uint32_t n_buckets, uint32_t domain, uint64_t *out, void *stream) {
+    if (!value_col) return fail(PQPS_EINVAL, "value column is NULL");
+    return filter_buckets(ctx, cols, n_cols, n_rows, pred, value_col, group_col, bin_base, bounds_dev, n_buckets, domain, out, stream);
+}
+
+int pqps_aggregate_buckets_list(pqps_ctx *ctx, const pqps_column *value_col, const pqps_column *group_col, uint64_t n_rows,
+                                const uint32_t *ids, const uint64_t *count_dev, uint64_t capacity, uint32_t id_base, uint32_t bin_base,
+                                const uint32_t *bounds_dev, uint32_t n_buckets, uint32_t domain, uint64_t *out, void *stream) {
+    if (!value_col) return fail(PQPS_EINVAL, "value column is NULL");
+    return list_buckets(ctx, value_col, group_col, n_rows, ids, count_dev, capacity, id_base, bin_base, bounds_dev, n_buckets, domain, out, stream);
 }
 
 // ---- ORDER BY column [DESC] LIMIT K (topk_kernels.hpp) --------------------------------------------------------------

@@ -1184,6 +1184,221 @@ void freeAggregateResultHIP(struct hipAggregateResult *res) {
     free(res);
 }
 
+/* ---- GROUP BY buckets (include/executeEngine-hip.h) ---------------------------------------------------------------- */
+
+/* How a bucketed query bins its rows: gp as the grouped queries use it (column, kind, fused, every shard's group column;
+ * n_bins = the buckets), and the run starts of the buckets in bin space with their keys (hipBucketBounds; malloc'd). */
+struct bucket_plan {
+    struct group_plan gp;
+    int mode;
+    long long arg;
+    uint32_t *bounds;                    /* n_bins + 1 run starts, the last one the domain */
+    long long *keys;                     /* n_bins */
+};
+
+/* Binds the WHERE into q and decides the buckets of column c (valid for the mode: the caller has checked). */
+static int bucket_plan_init(struct engineS *engine, struct whereClauseS *whereClause, struct query *q, int c, const char *column,
+                            int mode, long long arg, struct bucket_plan *bp) {
+    struct hipTable *t = q->t;
+    struct group_plan *gp = &bp->gp;
+    memset(bp, 0, sizeof *bp);
+    bp->mode = mode;
+    bp->arg = arg;
+    gp->c = c;
+    gp->kind = k_group_kind[c];
+    gp->n_bins = 1;
+    int rc = query_bind(engine, whereClause, q);
+    gp->fused = q->plan.n_passes == 1 && q->n_probes == 0;
+    for (int s = 0; s < q->n_shards; s++) gp->gcol[s] = hipTableShard(t, s)->col[c];
+    if (rc != 0) return rc;
+    uint64_t rows = 0;
+    int32_t hi = -1;
+    for (int s = 0; s < q->n_shards; s++) rows += hipTableShard(t, s)->n_rows;
+    if (rows == 0 || (gp->kind == HIPKIND_DICT && t->dict[c].count < 1)) { gp->empty = true; return 0; }
+    if (gp->kind == HIPKIND_DICT) gp->single = t->col[c].width == 0;
+    else if ((rc = column_bounds(q, c, &gp->lo, &hi)) != 0) return rc;
+    else if (gp->lo > hi) { gp->empty = true; return 0; }
+    else gp->bin_base = (uint32_t)gp->lo;
+    return hipBucketBounds(column, gp->kind == HIPKIND_DICT ? (const char *const *)t->dict[c].values : NULL,
+                           gp->kind == HIPKIND_DICT ? (int)t->dict[c].count : 0, gp->lo, hi, mode, arg, &bp->bounds, &bp->keys, &gp->n_bins);
+}
+
+static void bucket_plan_free(struct bucket_plan *bp) {
+    free(bp->bounds);
+    free(bp->keys);
+}
+
+struct bucket_call { const struct bucket_plan *bp; int vc; void **buf; size_t head; };
+
+static int bucket_fused_call(struct query *q, int s, pqps_ctx *ctx, void *stream, void *arg) {
+    const struct bucket_call *a = arg;
+    const struct group_plan *gp = &a->bp->gp;
+    const struct hipTable *sh = hipTableShard(q->t, s);
+    const struct shard_pred *sp = &q->sp[s];
+    const uint32_t *bounds_dev = a->buf[s];
+    void *out = (char *)a->buf[s] + a->head;
+    const uint32_t domain = a->bp->bounds[gp->n_bins];
+    const int rc = a->vc < 0 ? pqps_filter_group_buckets(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, &gp->gcol[s], gp->bin_base, bounds_dev,
+                                                         gp->n_bins, domain, out, stream)
+                             : pqps_filter_aggregate_buckets(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, &sh->col[a->vc], &gp->gcol[s],
+                                                             gp->bin_base, bounds_dev, gp->n_bins, domain, out, stream);
+    return rc == PQPS_OK ? 0 : engine_error("bucket filter");
+}
+
+/* The buckets of the query on every shard, combined on the host (group_combine): vc < 0 the counts, otherwise the aggregates
+ * of value column vc.  Per shard one buffer of the query's own, [bounds][bins], the bounds uploaded once before anything is
+ * issued.  gp.fused: one launch per shard on the query's lane; otherwise the selection and the list call over every list. */
+static int bucket_bins(struct query *q, const struct bucket_plan *bp, int vc, uint64_t *acc) {
+    const struct group_plan *gp = &bp->gp;
+    const uint32_t n_bins = gp->n_bins, domain = bp->bounds[n_bins];
+    const size_t head = (((size_t)n_bins + 1) * sizeof(uint32_t) + 15) & ~(size_t)15;
+    const size_t bytes = vc < 0 ? (size_t)n_bins * sizeof(uint32_t) : (size_t)n_bins * 4 * sizeof(uint64_t);
+    void *buf[HIP_MAX_SHARDS] = { NULL };
+    void *host = malloc(bytes);
+    int rc = host ? 0 : -1;
+    if (!host) fprintf(stderr, "HIP engine: out of memory\n");
+    for (int s = 0; s < q->n_shards && rc == 0; s++) {
+        struct hipTable *sh = hipTableShard(q->t, s);
+        if (sh->n_rows == 0) continue;
+        if (pqps_malloc(sh->ctx, head + bytes, &buf[s]) != PQPS_OK) rc = engine_error("bucket scratch");
+        else if (pqps_upload(lane_copy_ctx(q, s), buf[s], bp->bounds, ((size_t)n_bins + 1) * sizeof(uint32_t), NULL) != PQPS_OK)
+            rc = engine_error("bucket bounds upload");
+    }
+    if (rc == 0 && gp->fused) {
+        rc = fused_issue(q, bucket_fused_call, &(struct bucket_call){ bp, vc, buf, head });
+        for (int s = 0; s < q->n_shards && rc == 0; s++)
+            if (!buf[s]) continue;
+            else if (pqps_download(lane_copy_ctx(q, s), host, (char *)buf[s] + head, bytes, NULL) != PQPS_OK) rc = engine_error("buckets download");
+            else group_combine(acc, host, n_bins, vc);
+    } else if (rc == 0) {
+        rc = query_lists(q);
+        for (int s = 0; s < q->n_shards && rc == 0; s++) {
+            struct hipTable *sh = hipTableShard(q->t, s);
+            struct hipLane *L = query_lane(q, s);
+            pqps_ctx *cs = lane_copy_ctx(q, s);
+            void *out = buf[s] ? (char *)buf[s] + head : NULL;
+            if (q->count[s] == 0 || !buf[s]) continue;
+            if ((vc < 0 ? pqps_group_buckets_list(cs, &gp->gcol[s], sh->n_rows, L->ids_dev, L->count_dev, q->count[s], (uint32_t)sh->row0, gp->bin_base,
+                                                  buf[s], n_bins, domain, out, NULL)
+                        : pqps_aggregate_buckets_list(cs, &sh->col[vc], &gp->gcol[s], sh->n_rows, L->ids_dev, L->count_dev, q->count[s],
+                                                      (uint32_t)sh->row0, gp->bin_base, buf[s], n_bins, domain, out, NULL)) != PQPS_OK ||
+                pqps_download(cs, host, out, bytes, NULL) != PQPS_OK)
+                rc = engine_error("bucket list");
+            else group_combine(acc, host, n_bins, vc);
+        }
+    }
+    for (int s = 0; s < q->n_shards; s++) if (buf[s]) pqps_free(hipTableShard(q->t, s)->ctx, buf[s]);
+    free(host);
+    return rc;
+}
+
+/* acc (counts, or the [4][n_bins] fields) into the result: buckets with rows only, with their keys and key texts */
+static int bucket_result_fill(struct hipBucketResult *res, const struct hipTable *t, const struct bucket_plan *bp, const uint64_t *acc, uint32_t n_bins) {
+    const bool valued = res->valueColumn >= 0;
+    size_t n = 0;
+    for (uint32_t k = 0; k < n_bins; k++) n += acc[k] != 0;
+    res->keys = calloc(n + 1, sizeof *res->keys);
+    res->keyText = calloc(n + 1, sizeof *res->keyText);
+    res->counts = calloc(n + 1, sizeof *res->counts);
+    if (valued) {
+        res->sums = calloc(n + 1, sizeof *res->sums);
+        res->mins = calloc(n + 1, sizeof *res->mins);
+        res->maxs = calloc(n + 1, sizeof *res->maxs);
+    }
+    if (!res->keys || !res->keyText || !res->counts || (valued && (!res->sums || !res->mins || !res->maxs))) {
+        fprintf(stderr, "HIP engine: out of memory\n");
+        return -1;
+    }
+    /* the image of an i32 value is (u64)(i64)v ^ 2^63, of a u64 value the value itself */
+    const uint64_t flip = res->valueKind == HIPKIND_I32 ? 0x8000000000000000ull : 0;
+    for (uint32_t k = 0; k < n_bins; k++) {
+        if (!acc[k]) continue;
+        const int g = res->numGroups;
+        char buf[32];
+        res->keys[g] = bp->keys[k];
+        if (bp->mode == HIPBUCKET_WIDTH) {
+            snprintf(buf, sizeof buf, "%lld", bp->keys[k]);
+            res->keyText[g] = strdup(buf);
+        } else {
+            const char *text = t->dict[res->groupColumn].values[bp->keys[k]];
+            const size_t len = strlen(text);
+            res->keyText[g] = strndup(text, (unsigned long long)bp->arg < len ? (size_t)bp->arg : len);
+        }
+        if (!res->keyText[g]) { fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
+        res->counts[g] = acc[k];
+        if (valued) {
+            res->sums[g] = (long long)acc[n_bins + k];
+            res->mins[g] = (long long)(acc[2 * n_bins + k] ^ flip);
+            res->maxs[g] = (long long)(acc[3 * n_bins + k] ^ flip);
+        }
+        res->total += (long long)acc[k];
+        res->numGroups++;
+    }
+    return 0;
+}
+
+struct hipBucketResult *executeQueryGroupBucketsHIP(struct engineS *engine, const char *groupColumn, int bucketMode, long long bucketArg,
+                                                    const char *valueColumn, struct whereClauseS *whereClause) {
+    const double t0 = now_seconds();
+    struct hipBucketResult *res = calloc(1, sizeof *res);
+    if (!res) { fprintf(stderr, "HIP engine: out of memory\n"); return NULL; }
+    res->groupColumn = res->groupKind = res->valueColumn = res->valueKind = -1;
+    res->bucketMode = bucketMode;
+    res->bucketArg = bucketArg;
+    if (!engine || !engine->record_block || !groupColumn) { fprintf(stderr, "HIP engine: GROUP BY buckets without an engine or a column\n"); return res; }
+    /* column, mode and argument are checked by hipBucketBounds itself, on a one-value column: nothing of the table is needed */
+    {
+        static const char *const one[1] = { "" };
+        uint32_t *b = NULL, n = 0;
+        long long *k = NULL;
+        if (hipBucketBounds(groupColumn, one, 1, 0, 0, bucketMode, bucketArg, &b, &k, &n) != 0) return res;
+        free(b);
+        free(k);
+    }
+    const int c = hipColumnId(groupColumn);
+    const int v = valueColumn ? hipColumnId(valueColumn) : -1;
+    if (valueColumn && v < 0) { fprintf(stderr, "HIP engine: GROUP BY buckets: unknown value column '%s'\n", valueColumn); return res; }
+    if (v >= 0 && k_group_kind[v] != HIPKIND_I32 && k_group_kind[v] != HIPKIND_U64) {
+        fprintf(stderr, "HIP engine: GROUP BY buckets: %s is a %s column, not a number\n", valueColumn, k_group_kind[v] == HIPKIND_BOOL ? "boolean" : "dictionary");
+        return res;
+    }
+    struct hipTable *t = engine->record_block;
+    if (t->xch) { fprintf(stderr, "HIP engine: GROUP BY buckets is not exchanged across ranks\n"); return res; }
+    res->groupColumn = c;
+    res->groupKind = k_group_kind[c];
+    res->valueColumn = v;
+    res->valueKind = v >= 0 ? k_group_kind[v] : -1;
+    struct query q;
+    if (!query_open(engine, &q)) return res;                             /* reason on stderr */
+    uint64_t *acc = NULL;
+    struct bucket_plan bp;
+    int rc = bucket_plan_init(engine, whereClause, &q, c, groupColumn, bucketMode, bucketArg, &bp);
+    const uint32_t n_bins = rc == 0 && !bp.gp.empty ? bp.gp.n_bins : 0u;
+    if (n_bins) {
+        acc = calloc((size_t)(v >= 0 ? 4 : 1) * n_bins, sizeof *acc);
+        if (!acc) { fprintf(stderr, "HIP engine: out of memory\n"); rc = -1; }
+        else if (v >= 0) for (uint32_t k = 0; k < n_bins; k++) acc[2 * n_bins + k] = UINT64_MAX;
+    }
+    /* a single-valued column has no device buffer: one bucket from the selection (group_counts), or the ungrouped aggregate */
+    if (rc == 0 && n_bins) rc = !bp.gp.single ? bucket_bins(&q, &bp, v, acc) : v < 0 ? group_counts(&q, &bp.gp, acc) : group_bins(&q, &bp.gp, v, acc);
+    if (rc == 0 && bucket_result_fill(res, t, &bp, acc ? acc : (uint64_t[4]){ 0 }, n_bins) == 0) res->success = true;
+    free(acc);
+    bucket_plan_free(&bp);
+    query_close(&q);
+    res->queryTime = now_seconds() - t0;
+    return res;
+}
+
+void freeBucketResultHIP(struct hipBucketResult *res) {
+    if (!res) return;
+    free_group_keys(res->keys, res->keyText, res->numGroups);
+    free(res->counts);
+    free(res->sums);
+    free(res->mins);
+    free(res->maxs);
+    free(res);
+}
+
 /* ---- COUNT(DISTINCT value column) (include/executeEngine-hip.h) ---------------------------------------------------- */
 
 #define HIP_DISTINCT_MAX_BITS (1ull << 30)          /* the bitmap forms' cap per shard: 128 MiB */

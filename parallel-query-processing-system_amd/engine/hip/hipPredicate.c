@@ -1019,3 +1019,80 @@ int hipMergeDictionaries(const char *const *old_values, int old_count, const cha
     *identity = same;
     return 0;
 }
+
+/* ---- the buckets of GROUP BY PREFIX(k) / WIDTH(w) ------------------------------------------------------------------ */
+
+static const int k_bucket_kind[PQPS_MAX_COLUMNS] = {
+    HIPKIND_U64, HIPKIND_DICT, HIPKIND_DICT, HIPKIND_DICT, HIPKIND_I32, HIPKIND_DICT,
+    HIPKIND_BOOL, HIPKIND_DICT, HIPKIND_I32, HIPKIND_DICT, HIPKIND_DICT, HIPKIND_I32
+};
+
+static int bucket_fail(const char *column, const char *what) {
+    fprintf(stderr, "HIP engine: buckets of %s: %s\n", column ? column : "(null)", what);
+    return -1;
+}
+
+/* floor(v / w) for w >= 1 */
+static long long floor_div(long long v, long long w) {
+    return v / w - (v % w < 0);
+}
+
+/* 1 when a and b differ within their first k bytes (either may end sooner) */
+static int prefix_differs(const char *a, const char *b, long long k) {
+    for (long long i = 0; i < k; i++) {
+        if (a[i] != b[i]) return 1;
+        if (!a[i]) return 0;
+    }
+    return 0;
+}
+
+int hipBucketBounds(const char *column, const char *const *dict, int dict_count, int lo, int hi, int mode, long long arg,
+                    uint32_t **bounds, long long **keys, uint32_t *n_buckets) {
+    if (!bounds || !keys || !n_buckets) return bucket_fail(column, "NULL argument");
+    const int c = hipColumnId(column);
+    if (c < 0) return bucket_fail(column, "unknown column");
+    if (c == 0) return bucket_fail(column, "command_id is unique -- it has no buckets");
+    if (mode != HIPBUCKET_PREFIX && mode != HIPBUCKET_WIDTH) return bucket_fail(column, "the mode is neither PREFIX nor WIDTH");
+    const int kind = k_bucket_kind[c];
+    if (arg < 1) return bucket_fail(column, mode == HIPBUCKET_PREFIX ? "a prefix of less than 1 byte" : "a width of less than 1");
+    if (mode == HIPBUCKET_PREFIX && kind != HIPKIND_DICT) return bucket_fail(column, "PREFIX needs a string column");
+    if (mode == HIPBUCKET_WIDTH && kind != HIPKIND_I32) return bucket_fail(column, "WIDTH needs an i32 column");
+    uint64_t n = 0, domain;
+    if (mode == HIPBUCKET_PREFIX) {
+        if (!dict || dict_count < 1) return bucket_fail(column, "an empty dictionary");
+        domain = (uint64_t)dict_count;
+        for (int i = 0; i < dict_count; i++) {
+            if (!dict[i]) return bucket_fail(column, "a NULL string");
+            n += i == 0 || prefix_differs(dict[i - 1], dict[i], arg);
+        }
+    } else {
+        if (lo > hi) return bucket_fail(column, "an empty range");
+        domain = (uint64_t)((long long)hi - (long long)lo) + 1u;
+        if (domain > UINT32_MAX) return bucket_fail(column, "the range spans 2^32 values: no u32 holds the sentinel");
+        n = (uint64_t)(floor_div(hi, arg) - floor_div(lo, arg)) + 1u;
+    }
+    if (n > HIPBUCKET_MAX) {
+        fprintf(stderr, "HIP engine: buckets of %s: %llu buckets, more than %u\n", column, (unsigned long long)n, HIPBUCKET_MAX);
+        return -1;
+    }
+    uint32_t *b = malloc((size_t)(n + 1) * sizeof *b);
+    long long *k = malloc((size_t)n * sizeof *k);
+    if (!b || !k) { free(b); free(k); return bucket_fail(column, "out of memory"); }
+    if (mode == HIPBUCKET_PREFIX) {
+        uint64_t j = 0;
+        for (int i = 0; i < dict_count; i++)
+            if (i == 0 || prefix_differs(dict[i - 1], dict[i], arg)) { b[j] = (uint32_t)i; k[j++] = i; }
+    } else {
+        const long long q0 = floor_div(lo, arg);
+        for (uint64_t j = 0; j < n; j++) {
+            const long long lower = (q0 + (long long)j) * arg;
+            k[j] = lower;
+            b[j] = (uint32_t)((lower > lo ? lower : (long long)lo) - (long long)lo);
+        }
+    }
+    b[n] = (uint32_t)domain;
+    *bounds = b;
+    *keys = k;
+    *n_buckets = (uint32_t)n;
+    return 0;
+}
