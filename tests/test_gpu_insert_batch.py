@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import qpelib as q
+from column_model import apply, coded, concat, copy_model, rows_of, without     # the model operations: shared with the writer sequences
 
 pq = q.pq
 pytestmark = pytest.mark.gpu
@@ -50,23 +51,8 @@ def base_model():
     return m
 
 
-def copy_model(m):
-    return {k: (v.copy() if isinstance(v, np.ndarray) else (None if v[0] is None else v[0].copy(), list(v[1]))) for k, v in m.items()}
-
-
-def rows_of(m):
-    return len(m["command_id"])
-
-
 def engine_of(m, indexes=INDEXES):
     return pq.HipEngine.from_columns(rows_of(m), m, indexes)
-
-
-def coded(texts, dtype=np.uint8, extra=()):
-    """Per-row strings -> (codes, dictionary): the batch's own ascending dictionary (`extra`: strings in it that no row carries)."""
-    values = sorted(set(texts) | set(extra))
-    rank = {v: i for i, v in enumerate(values)}
-    return np.array([rank[v] for v in texts], dtype=dtype), values
 
 
 def make_batch(B, seed, **over):
@@ -89,60 +75,6 @@ def make_batch(B, seed, **over):
     }
     b.update(over)
     return b
-
-
-def code_dtype(count):
-    return np.uint8 if count <= 256 else np.uint16 if count <= 65536 else np.uint32
-
-
-def concat(m, b):
-    """The model of the old rows followed by the batch's: dictionaries the sorted unions, codes their positions in them."""
-    out = {}
-    for name, v in m.items():
-        if isinstance(v, np.ndarray):
-            out[name] = np.concatenate([v, np.asarray(b[name]).astype(v.dtype)])
-            continue
-        (oc, ov), (nc, nv) = v, b[name]
-        merged = sorted(set(ov) | set(nv))
-        if len(merged) == 1:
-            out[name] = (None, merged)
-            continue
-        pos = {s: i for i, s in enumerate(merged)}
-        lut_old, lut_new = np.array([pos[s] for s in ov]), np.array([pos[s] for s in nv])
-        old = lut_old[oc] if oc is not None else np.full(rows_of(m), lut_old[0])
-        new = lut_new[nc] if nc is not None else np.full(rows_of(b), lut_new[0])
-        out[name] = (np.concatenate([old, new]).astype(code_dtype(len(merged))), merged)
-    return out
-
-
-def typed(column, value):
-    if column == "sudo_used":
-        return 1 if str(value).lower() == "true" or str(value) == "1" else 0
-    return int(value)
-
-
-def apply(m, assignments, mask):
-    """The model after UPDATE SET assignments for the rows of `mask`."""
-    out = copy_model(m)
-    for column, value in assignments.items():
-        if pq.COLUMN_KIND[pq.COL[column]] != pq.KIND_DICT:
-            out[column][mask] = typed(column, value)
-            continue
-        codes, values = out[column]
-        text = value if isinstance(value, bytes) else value.encode()
-        if text not in values:
-            rank = sum(v < text for v in values)
-            values.insert(rank, text)
-            if codes is not None:
-                codes[codes >= rank] += 1
-        if codes is not None:
-            codes[mask] = values.index(text)
-    return out
-
-
-def without(m, mask):
-    """The model after DELETE of the rows of `mask` (the dictionaries stay)."""
-    return {k: (v[~mask] if isinstance(v, np.ndarray) else (None if v[0] is None else v[0][~mask], list(v[1]))) for k, v in m.items()}
 
 
 def column_text(m, column):

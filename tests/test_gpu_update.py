@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import qpelib as q
+from column_model import apply                                  # the model operation: shared with the writer sequences
 
 pq = q.pq
 pytestmark = pytest.mark.gpu
@@ -46,37 +47,8 @@ def base_model():
     return m
 
 
-def copy_model(m):
-    return {k: (v.copy() if isinstance(v, np.ndarray) else (None if v[0] is None else v[0].copy(), list(v[1]))) for k, v in m.items()}
-
-
 def engine_of(m):
     return pq.HipEngine.from_columns(N, m, INDEXES)
-
-
-def typed(column, value):
-    if column == "sudo_used":
-        return 1 if str(value).lower() == "true" or str(value) == "1" else 0
-    return int(value)
-
-
-def apply(m, assignments, mask):
-    """The model after UPDATE SET assignments for the rows of `mask`."""
-    out = copy_model(m)
-    for column, value in assignments.items():
-        if pq.COLUMN_KIND[pq.COL[column]] != pq.KIND_DICT:
-            out[column][mask] = typed(column, value)
-            continue
-        codes, values = out[column]
-        text = value if isinstance(value, bytes) else value.encode()
-        if text not in values:
-            rank = sum(v < text for v in values)
-            values.insert(rank, text)
-            if codes is not None:
-                codes[codes >= rank] += 1
-        if codes is not None:
-            codes[mask] = values.index(text)
-    return out
 
 
 def column_text(m, column):
