@@ -582,8 +582,9 @@ int pqps_sort_list(pqps_ctx *ctx, const pqps_column *key_col, int key_signed, in
  * pqps_distinct_sort: the sort form for any domain, command_id (8 bytes, unsigned) included: the listed rows' (group,
  *   value) keys sorted by the stable LSD radix sort, distinct[g] = the keys of group g that differ from their predecessor.
  *   `out_keys` (may be NULL) receives the sorted keys -- narrow values: n u64 (group bin << 32 | value bin); 8-byte values:
- *   n u64 values followed by n u32 group bins (group-major, values ascending within a group).  Its scratch is allocated and
- *   freed by the call.  Synchronous. */
+ *   n u64 values followed by n u32 group bins (group-major, values ascending within a group).  A listed row whose group bin
+ *   is >= n_groups is not counted; in `out_keys` it carries a group bin >= n_groups and sorts behind the rows of every group.
+ *   Its scratch is allocated and freed by the call.  Synchronous. */
 uint64_t pqps_distinct_bitmap_words(uint32_t n_values, uint32_t n_groups);
 int pqps_filter_distinct(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
                          const pqps_column *value_col, uint32_t v_base, uint32_t n_values, const pqps_column *group_col,

@@ -3654,7 +3654,9 @@ int pqps_distinct_sort(pqps_ctx *ctx, const pqps_column *value_col, uint32_t v_b
         if (e == hipSuccess) e = pqps_sort::sort_pairs<uint64_t, false>(w, ka, ga, kb, gb, n, 64, ctx->compute_units, s, &in_a);
         keys = in_a ? ka : kb;
     } else if (e == hipSuccess) {
-        // (value, group): by value, then stably by group -- the groups carry the positions of the value order
+        // (value, group): by value, then stably by group -- the groups carry the positions of the value order.  The group pass
+        // runs whenever there is a group column, for one group too: a row outside the bins carries group n_groups and has to
+        // leave the run of group 0, or dist_unique_kernel meets a value listed (in, out, in) twice
         hipLaunchKernelGGL(dist_keys_kernel<true>, grid, dim3(kBlock), 0, s, value_col->data, vwl, gdata, gwl, ids, n, id_base, v_base,
                            g_base, n_groups, ka, ga);
         e = hipGetLastError();
@@ -3662,7 +3664,7 @@ int pqps_distinct_sort(pqps_ctx *ctx, const pqps_column *value_col, uint32_t v_b
         if (e == hipSuccess) e = pqps_sort::sort_pairs<uint64_t, false>(w, ka, ga, kb, gb, n, 64, ctx->compute_units, s, &in_a);
         keys = in_a ? ka : kb;
         grps = in_a ? ga : gb;
-        if (e == hipSuccess && n_groups > 1) {
+        if (e == hipSuccess && group_col) {
             uint32_t *g_in = in_a ? ga : gb, *g_out = in_a ? gb : ga;
             if (e == hipSuccess) e = hipMalloc((void **)&pa, n * 4);
             if (e == hipSuccess) e = hipMalloc((void **)&pb, n * 4);

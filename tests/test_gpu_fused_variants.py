@@ -9,6 +9,9 @@ reads PQPS_NT_LOADS once (tests/fused_driver.py does the work; see its docstring
     K on the steps of the top-K buffer, top-K without input, list forms with capacity < count and bases at the top of u32
   * rows in the readable padding that WOULD match and change the answer: the trim of the partial last step
   * after every fused call pqps_last_kernel() names the path the case expects and this process's load flavour
+
+Not here, because they read no once-per-process switch: the sort forms pqps_sort_list and pqps_distinct_sort, pqps_distinct_count
+and pqps_column_bounds are called at the shim by tests/test_gpu_sort_shim.py (pqps_group_pair_sort by test_gpu_group_pair_shim.py).
 """
 import os
 import re
