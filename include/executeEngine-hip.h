@@ -518,6 +518,58 @@ struct hipColumnarResult *executeQuerySelectOrderedHIP(struct engineS *engine, c
                                                        struct whereClauseS *whereClause, const char *orderColumn,
                                                        bool descending, long long limit, long long *matches);
 
+/* The first row of every group: per value of `groupColumn`, the matching row that comes first in the order of `orderColumn`
+ * -- "the latest command of every user", "the first sudo on every host" (SQL: DISTINCT ON, ROW_NUMBER() OVER (PARTITION BY
+ * g ORDER BY k) = 1, argMin / argMax; no counterpart in the reference, reached through the C API and the Python package only
+ * -- the SQL driver has no GROUP BY, so its output stays that of QPESeq).
+ * ROWS: exactly the rows executeQuerySelectIdsHIP(engine, whereClause) returns.  In index mode a row several probed
+ * conditions return more than once changes nothing except `total`, which equals that call's count.
+ * GROUPS: the groups, keys, key text and key order of executeQueryGroupCountHIP for the same column and WHERE; a group is
+ * listed iff it has a matching row.  groupColumn == NULL: one group over all those rows -- numGroups is 1 if any row matches
+ * and 0 otherwise, keys and keyText are NULL, groupColumn and groupKind are -1, as in hipAggregateResult.
+ * ORDER: exactly executeQueryOrderIdsHIP's -- exit_code, user_id, risk_level signed, command_id unsigned 64-bit, false before
+ * true, string columns in the dictionary's strcmp order (the codes); ascending, or descending with `descending`; TIES GO TO
+ * THE LOWEST ROW NUMBER IN BOTH DIRECTIONS.  Every one of the 12 columns can be the order column; a single-valued string
+ * column (no device buffer) makes every key equal, so the answer is the lowest matching row of each group.  Group column ==
+ * order column is legal.
+ * CONSEQUENCE: for every WHERE, rows[g] equals the first row of executeQueryOrderIdsHIP(whereClause AND groupColumn =
+ * keyText[g], orderColumn, descending, limit 1); with groupColumn == NULL it equals that call's for whereClause itself.
+ * REFUSED (success = false, the reason on stderr): an unknown group or order column, and every group-column refusal of
+ * executeQueryGroupCountHIP (command_id as the group column, more than 65 536 groups, an engine joined across ranks -- with
+ * or without GROUP BY).  NOTHING is refused for the size of the order column's domain: timestamp with 4-byte codes on a
+ * 1 M-row CSV is a legal order column.  A reader like COUNT: shared lock and one query lane, the lane rules above apply; the
+ * device buffers of a query are allocated for it and freed with it.
+ * Execution: as executeQueryAggregateHIP -- a single-pass scan-mode WHERE runs ONE fused launch per shard
+ * (pqps_filter_group_first: one 64-bit atomic min per matching row; two launches, i.e. two scans of the WHERE, for
+ * command_id, whose keys need 96 bits), everything else the selection and then pqps_group_first_list over each shard's list.
+ * Shards are merged on the host by the minimum word per bin (rows are table-wide; command_id compares (key, row)).  A
+ * single-valued group column gives one group from the ungrouped form.  An empty table, or a WHERE that matches nothing,
+ * gives numGroups = 0 with success = true. */
+struct hipGroupFirstResult {
+    int groupColumn, groupKind;        /* HIPCOL_*, HIPKIND_*; -1 / -1 without GROUP BY                    */
+    int orderColumn, orderKind;        /* HIPCOL_*, HIPKIND_*                                              */
+    bool descending;
+    int numGroups;
+    long long total;                   /* executeQuerySelectIdsHIP's count                                  */
+    long long *keys;                   /* as hipGroupResult; NULL without GROUP BY                         */
+    char **keyText;                    /* as hipGroupResult; NULL without GROUP BY                         */
+    unsigned int *rows;                /* table-wide row number of each group's first row                  */
+    long long *orderKeys;              /* that row's order key: i32 value, 0 / 1, dictionary code at the time of the query,
+                                          the u64 bits for command_id                                      */
+    char **orderText;                  /* owned: as get_attribute_string_value formats the order column's cell */
+    double queryTime;
+    bool success;
+};
+struct hipGroupFirstResult *executeQueryGroupFirstHIP(struct engineS *engine, const char *groupColumn /* may be NULL */,
+                                                      const char *orderColumn, bool descending, struct whereClauseS *whereClause);
+void freeGroupFirstResultHIP(struct hipGroupFirstResult *result);
+/* The same rows, projected: a hipColumnarResult whose numRecords = numGroups rows are those first rows in group key order
+ * (cells exactly as executeQuerySelectColumnarHIP makes them; the device gather executeQuerySelectOrderedHIP uses).
+ * *matches (may be NULL) = executeQuerySelectIdsHIP's count. */
+struct hipColumnarResult *executeQuerySelectGroupFirstHIP(struct engineS *engine, const char **selectItems, int numSelectItems,
+                                                          struct whereClauseS *whereClause, const char *groupColumn /* may be NULL */,
+                                                          const char *orderColumn, bool descending, long long *matches);
+
 /* COUNT(*) through the backend API (the reference parser cannot express it,
  * SURVEY.md fact 10): scan-mode count of matching rows, no ID list. */
 long long executeQueryCountHIP(struct engineS *engine, struct whereClauseS *whereClause);

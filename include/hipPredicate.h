@@ -153,6 +153,13 @@ int hipMergeDictionaries(const char *const *old_values, int old_count, const cha
 int hipBucketBounds(const char *column, const char *const *dict, int dict_count, int lo, int hi, int mode, long long arg,
                     uint32_t **bounds, long long **keys, uint32_t *n_buckets);
 
+/* THE WORD OF "THE FIRST ROW OF EVERY GROUP".  pqps_filter_group_first / pqps_group_first_list leave one u64 per bin for a
+ * narrow order column: (img ^ x) << 32 | row, img = v ^ 2^31 for an i32 column and the dictionary code or the bool otherwise,
+ * x = 0xFFFFFFFF when descending and 0 otherwise; all ones = no row.  Pure host code.  Returns 0 for the empty word (*key and
+ * *row untouched), -1 for a kind that has no such word (HIPKIND_U64: command_id takes the two-pass form), otherwise 1 with
+ * *key = the i32 value, 0 / 1, or the dictionary code, and *row = the table-wide row number (either may be NULL). */
+int hipFirstKeyDecode(int kind, int descending, unsigned long long word, long long *key, unsigned int *row);
+
 /* Column name -> HIPCOL_* id, -1 if unknown. */
 int hipColumnId(const char *name);
 

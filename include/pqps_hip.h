@@ -560,6 +560,43 @@ int pqps_topk_list(pqps_ctx *ctx, const pqps_column *key_col, int key_signed, in
 int pqps_sort_list(pqps_ctx *ctx, const pqps_column *key_col, int key_signed, int descending, const uint32_t *ids, uint64_t n,
                    uint32_t id_base, uint32_t *out_ids, uint64_t *out_keys, void *stream);
 
+/* ---- the first row of every group: per bin, the matching row that comes first in the order of a key column -------------
+ * No counterpart in the reference (SQL: DISTINCT ON, ROW_NUMBER() OVER (PARTITION BY g ORDER BY k) = 1, argMin / argMax).
+ * BINS: those of pqps_filter_group ((value - bin_base) in 32-bit arithmetic; rows whose bin is >= n_bins are left out);
+ * `group_col` NULL means no GROUP BY: n_bins must be 1 and every matching row is bin 0.  n_bins 1 .. 65 536.
+ * ORDER: that of the top-K family above -- the key column's image ascending (descending with `descending`), ties by
+ * ascending table-wide row number (row_base / id_base + local row) in BOTH directions.  Row numbers stay below 2^32 - 1.
+ * WORDS: out[0 .. n_bins) u64 device words, one per bin; all ones = the bin has no row.
+ *   key_col 1, 2 or 4 bytes wide, or a bit plane: out[b] = the MINIMUM over the bin's rows of the top-K key
+ *     (img ^ x) << 32 | row, img = v ^ 2^31 when key_signed (i32), the value itself otherwise, x = 0xFFFFFFFF when
+ *     descending, else 0 (hipFirstKeyDecode of hipPredicate.h undoes it); `best` is not used and may be NULL
+ *   key_col NULL: every value 0 (a single-valued column): out[b] = the lowest matching row of the bin
+ *   key_col 8 bytes wide (command_id, unsigned): 96 bits do not fit one atomic, so the call runs TWO passes over the rows
+ *     (two scans of the WHERE): best[b] = the minimum of v ^ x (x = ~0 when descending, else 0), then out[b] = the lowest
+ *     row among the bin's rows whose v ^ x equals best[b].  `best` (n_bins u64 device words) is required; best[b] means
+ *     something only where out[b] is not all ones.
+ * The calls initialise `out`, `best` and `*count` themselves and are asynchronous on `stream`.  No scratch argument: the
+ * partial rows of the fused scan live in the context's fused-scan scratch, which the call grows as pqps_filter_aggregate
+ * does (one fused query at a time per context, as for its siblings).
+ *
+ * pqps_filter_group_first: ONE scan of `pred` over rows [0, n_rows) of `cols` (two for an 8-byte key); the key column and the
+ *   group column are read only in steps of 1024 rows that hold a match, and every matching row costs ONE 64-bit unsigned
+ *   atomic min.  `group_col` 1, 2 or 4 bytes wide or a bit plane.  The readable-padding rule of pqps_filter_scan applies to
+ *   the predicate columns, `key_col` and `group_col`.  No GROUP BY: per-lane minima; D <= 8192 bins: a table of 8 B per bin
+ *   in LDS; up to 65 536: atomics straight into `out` (slow: a correctness path).  *count (device) = the matching rows,
+ *   those of bins >= n_bins included.  The context's timing recorder records the launch like a COUNT's (an 8-byte key: two
+ *   records).
+ * pqps_group_first_list: the same words over an ID list -- ids[0 .. min(*count_dev, capacity)), row = id - id_base <
+ *   n_rows -- gathering `key_col` (1, 2, 4 or 8 bytes wide, no bit plane) and `group_col` (1, 2 or 4 bytes wide, no bit
+ *   plane) per listed row; an id listed twice changes nothing.  capacity or n_rows 0: `out` all ones, nothing launched. */
+int pqps_filter_group_first(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                            const pqps_column *key_col, int key_signed, int descending, uint32_t row_base,
+                            const pqps_column *group_col, uint32_t bin_base, uint32_t n_bins, uint64_t *out, uint64_t *best,
+                            uint64_t *count, void *stream);
+int pqps_group_first_list(pqps_ctx *ctx, const pqps_column *key_col, int key_signed, int descending, const pqps_column *group_col,
+                          uint32_t bin_base, uint32_t n_bins, uint64_t n_rows, const uint32_t *ids, const uint64_t *count_dev,
+                          uint64_t capacity, uint32_t id_base, uint64_t *out, uint64_t *best, void *stream);
+
 /* ---- COUNT(DISTINCT value column), overall or per group ---------------------------------------------------------------
  * No counterpart in the reference.  BINS: a value bin is (value - v_base) in 32-bit arithmetic (dictionary codes with
  * v_base 0, an i32 value minus the column's minimum, the bool byte or bit), a group bin (value - g_base) likewise;

@@ -146,6 +146,15 @@ class DistinctResult(C.Structure):
                 ("queryTime", C.c_double), ("success", C.c_bool)]
 
 
+class GroupFirstResult(C.Structure):
+    """struct hipGroupFirstResult (include/executeEngine-hip.h)."""
+    _fields_ = [("groupColumn", C.c_int), ("groupKind", C.c_int), ("orderColumn", C.c_int), ("orderKind", C.c_int),
+                ("descending", C.c_bool), ("numGroups", C.c_int), ("total", C.c_longlong),
+                ("keys", C.POINTER(C.c_longlong)), ("keyText", C.POINTER(C.c_char_p)), ("rows", C.POINTER(C.c_uint)),
+                ("orderKeys", C.POINTER(C.c_longlong)), ("orderText", C.POINTER(C.c_char_p)),
+                ("queryTime", C.c_double), ("success", C.c_bool)]
+
+
 class ColumnData(C.Structure):
     """struct hipColumnData (include/executeEngine-hip.h)."""
     _fields_ = [("values", C.c_void_p), ("width", C.c_uint), ("on_device", C.c_int),
@@ -537,12 +546,24 @@ def lib():
                                    vp, u64, vp, vp, vp]
     L.pqps_topk_list.argtypes = [vp, C.POINTER(Column), C.c_int, C.c_int, vp, u64, u32, u32, vp, u64, vp, vp]
     L.pqps_sort_list.argtypes = [vp, C.POINTER(Column), C.c_int, C.c_int, vp, u64, u32, vp, vp, vp]
+    L.pqps_filter_group_first.argtypes = [vp, C.POINTER(Column), u32, u64, C.POINTER(Predicate), C.POINTER(Column), C.c_int, C.c_int, u32,
+                                          C.POINTER(Column), u32, u32, vp, vp, vp, vp]
+    L.pqps_group_first_list.argtypes = [vp, C.POINTER(Column), C.c_int, C.c_int, C.POINTER(Column), u32, u32, u64, vp, vp, u64, u32,
+                                        vp, vp, vp]
+    L.hipFirstKeyDecode.argtypes = [C.c_int, C.c_int, C.c_ulonglong, C.POINTER(C.c_longlong), C.POINTER(C.c_uint)]
+    L.executeQueryGroupFirstHIP.restype = C.POINTER(GroupFirstResult)
+    L.executeQueryGroupFirstHIP.argtypes = [E, C.c_char_p, C.c_char_p, C.c_bool, W]
+    L.freeGroupFirstResultHIP.argtypes = [C.POINTER(GroupFirstResult)]
+    L.freeGroupFirstResultHIP.restype = None
     CR = C.POINTER(ColumnarResult)
     L.executeQuerySelectColumnarHIP.restype = CR
     L.executeQuerySelectColumnarHIP.argtypes = [E, C.POINTER(C.c_char_p), C.c_int, W]
     L.executeQuerySelectOrderedHIP.restype = CR
     L.executeQuerySelectOrderedHIP.argtypes = [E, C.POINTER(C.c_char_p), C.c_int, W, C.c_char_p, C.c_bool, C.c_longlong,
                                                C.POINTER(C.c_longlong)]
+    L.executeQuerySelectGroupFirstHIP.restype = CR
+    L.executeQuerySelectGroupFirstHIP.argtypes = [E, C.POINTER(C.c_char_p), C.c_int, W, C.c_char_p, C.c_char_p, C.c_bool,
+                                                  C.POINTER(C.c_longlong)]
     L.freeColumnarResultHIP.argtypes = [CR]
     L.hipColumnarCellText.restype = vp
     L.hipColumnarCellText.argtypes = [CR, C.c_int, C.c_int]
@@ -706,6 +727,33 @@ def filter_assign(ctx, cols, n_cols, n_rows, pred, triples, matched_dev, stream=
 def assign_flags(ctx, flags_dev, n_rows, triples, stream=None):
     """pqps_assign_flags: the same stores by byte flags."""
     check(lib().pqps_assign_flags(ctx.h, flags_dev, n_rows, assign_targets(triples), len(triples), stream), "pqps_assign_flags")
+
+
+def filter_group_first(ctx, cols, n_cols, n_rows, pred, key_col, key_signed, descending, row_base, group_col, bin_base, n_bins,
+                       out_dev, best_dev, count_dev, stream=None):
+    """pqps_filter_group_first: the fused filter-and-first-row launch; `pred` a Predicate (or its byref), `key_col` /
+    `group_col` a Column or None."""
+    ref = lambda c: C.byref(c) if c is not None else None
+    check(lib().pqps_filter_group_first(ctx.h, cols, n_cols, n_rows, C.byref(pred) if isinstance(pred, Predicate) else pred,
+                                        ref(key_col), int(key_signed), int(descending), row_base, ref(group_col), bin_base, n_bins,
+                                        out_dev, best_dev, count_dev, stream), "pqps_filter_group_first")
+
+
+def group_first_list(ctx, key_col, key_signed, descending, group_col, bin_base, n_bins, n_rows, ids_dev, count_dev, capacity, id_base,
+                     out_dev, best_dev, stream=None):
+    """pqps_group_first_list: the same words over an ID list."""
+    ref = lambda c: C.byref(c) if c is not None else None
+    check(lib().pqps_group_first_list(ctx.h, ref(key_col), int(key_signed), int(descending), ref(group_col), bin_base, n_bins, n_rows,
+                                      ids_dev, count_dev, capacity, id_base, out_dev, best_dev, stream), "pqps_group_first_list")
+
+
+def first_key_decode(kind, descending, word):
+    """hipFirstKeyDecode: None for the empty word, else (key, row); ValueError for a kind without such a word."""
+    key, row = C.c_longlong(), C.c_uint()
+    rc = lib().hipFirstKeyDecode(kind, int(descending), word, C.byref(key), C.byref(row))
+    if rc < 0:
+        raise ValueError(f"hipFirstKeyDecode: kind {kind} has no one-word key")
+    return (int(key.value), int(row.value)) if rc else None
 
 
 def remap_codes(ctx, src_dev, src_width, dst_dev, dst_width, n, lut_dev, lut_count, form=None, bad_dev=None, stream=None):
@@ -1282,6 +1330,54 @@ class HipEngine:
             if res:
                 lib().freeColumnarResultHIP(res)
             raise PqpsError(f"select_ordered({order_column!r}) refused or failed (reason on stderr)")
+        out = self._columnar_dict(res, text)
+        out["matches"] = int(matches.value)
+        return out
+
+    def group_first(self, group_column, order_column, chain=None, descending=False):
+        """executeQueryGroupFirstHIP: (groups, total) -- per group of `group_column` (None: one group) among the rows
+        select_ids(chain) returns, (key_text_or_None, row, order_text) of the row that comes first in order_ids' order of
+        `order_column` (ties to the lowest row number in both directions), in group_count's key order; total =
+        len(select_ids(chain)).  Raises PqpsError when the engine refuses (reason on stderr)."""
+        return self.group_first_result(group_column, order_column, chain, descending)[:2]
+
+    def group_first_result(self, group_column, order_column, chain=None, descending=False):
+        """group_first plus the raw fields: (groups, total, dict(keys, order_keys, seconds, ...))."""
+        wl = WhereList(chain)
+        res = lib().executeQueryGroupFirstHIP(self.e, group_column.encode() if group_column else None, order_column.encode(),
+                                              bool(descending), wl.ptr)
+        what = f"group_first({group_column!r}, {order_column!r})"
+        if not res:
+            raise PqpsError(f"{what}: no result")
+        try:
+            r = res.contents
+            if not r.success:
+                raise PqpsError(f"{what} refused or failed (reason on stderr)")
+            n = r.numGroups
+            grouped = r.groupColumn >= 0
+            groups = [(r.keyText[g].decode("latin-1") if grouped else None, int(r.rows[g]), r.orderText[g].decode("latin-1"))
+                      for g in range(n)]
+            fix = (lambda x: x & 0xFFFFFFFFFFFFFFFF) if r.orderKind == HIPKIND_U64 else int
+            raw = dict(keys=[int(r.keys[g]) for g in range(n)] if grouped else None, order_keys=[fix(r.orderKeys[g]) for g in range(n)],
+                       group_column=r.groupColumn, group_kind=r.groupKind, order_column=r.orderColumn, order_kind=r.orderKind,
+                       descending=bool(r.descending), seconds=float(r.queryTime))
+            return groups, int(r.total), raw
+        finally:
+            lib().freeGroupFirstResultHIP(res)
+
+    def select_group_first(self, columns, chain, group_column, order_column, descending=False, text=True):
+        """executeQuerySelectGroupFirstHIP: the dict select_columnar returns, its rows those of group_first(group_column,
+        order_column, chain, descending) in that order, plus `matches`.  Raises PqpsError when the engine refuses."""
+        wl = WhereList(chain)
+        items = (C.c_char_p * max(1, len(columns or [])))(*[c.encode() for c in (columns or [])])
+        matches = C.c_longlong()
+        res = lib().executeQuerySelectGroupFirstHIP(self.e, items if columns else None, len(columns or []), wl.ptr,
+                                                    group_column.encode() if group_column else None, order_column.encode(),
+                                                    bool(descending), C.byref(matches))
+        if not res or not res.contents.success:
+            if res:
+                lib().freeColumnarResultHIP(res)
+            raise PqpsError(f"select_group_first({group_column!r}, {order_column!r}) refused or failed (reason on stderr)")
         out = self._columnar_dict(res, text)
         out["matches"] = int(matches.value)
         return out

@@ -1,5 +1,5 @@
-// fused_common.hpp -- device scaffolding shared by the four fused filter-and-aggregate families: group_, agg_, topk_ and
-// dist_kernels.hpp (included once by pqps_hip.hip, after filter_kernels.hpp and before those four).
+// fused_common.hpp -- device scaffolding shared by the fused filter-and-aggregate families: group_, agg_, topk_, first_ and
+// dist_kernels.hpp (included once by pqps_hip.hip, after filter_kernels.hpp and before them).
 //
 // A fused scan is the grid-stride form of the COUNT kernels (fused_scan_steps): a wave takes the 1024-row steps wave,
 // wave + n_waves, ... of a persistent grid, evaluates the WHERE of each (eval_step_full; match bit p of lane l <-> row
@@ -7,7 +7,7 @@
 // (wave-uniform) reaches the kernel's body, which loads its own columns in the predicate columns' per-lane pattern
 // (load_step_u32 / load_step_u64: RPL = 4, lane l owns rows l*4 .. l*4+3 of each 256-row chunk), so a sparse WHERE reads
 // almost nothing beyond its predicate bytes.  The list forms walk an ID list instead (for_each_listed_row) and gather their
-// columns per listed row (gather_narrow / gather_key).  No kernel of the four families waits on another workgroup.
+// columns per listed row (gather_narrow / gather_key).  No kernel of these families waits on another workgroup.
 #pragma once
 
 namespace {

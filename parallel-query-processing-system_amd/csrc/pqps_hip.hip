@@ -28,6 +28,7 @@
 #include "group_kernels.hpp"
 #include "aggregate_kernels.hpp"
 #include "topk_kernels.hpp"
+#include "first_kernels.hpp"
 #include "distinct_kernels.hpp"
 #include "group_pair_kernels.hpp"
 #include "assign_kernels.hpp"
@@ -3488,6 +3489,127 @@ int pqps_sort_list(pqps_ctx *ctx, const pqps_column *key_col, int key_signed, in
     (void)hipFree(ra); (void)hipFree(rb); (void)hipFree(va); (void)hipFree(vb); (void)hipFree(ka); (void)hipFree(kb);
     pqps_sort::workspace_free(w);
     if (e != hipSuccess) return fail(PQPS_EHIP, "ORDER BY sort: %s", hipGetErrorString(e));
+    return PQPS_OK;
+}
+
+// ---- the first row of every group (first_kernels.hpp) ----------------------------------------------------------------
+// The key column as the top-K family checks it, the group column and the bins as the aggregates check theirs; an 8-byte key
+// needs `best`.
+static int check_first_cols(const pqps_column *key_col, const pqps_column *group_col, uint32_t n_bins, const uint64_t *best,
+                            bool plane_ok, bool *wide, uint32_t *kwl, uint32_t *gwl) {
+    *gwl = 0;
+    int rc = check_topk_key(key_col, plane_ok, wide, kwl);
+    if (rc) return rc;
+    if (*wide && !best) return fail(PQPS_EINVAL, "an 8-byte key column needs `best`");
+    if (!group_col) return n_bins == 1 ? PQPS_OK : fail(PQPS_EINVAL, "no group column: 1 bin, not %u", n_bins);
+    if (n_bins == 0 || n_bins > kGroupMaxBins) return fail(PQPS_EINVAL, "%u bins: 1 .. %u", n_bins, kGroupMaxBins);
+    return column_width_code("group", group_col, plane_ok, false, plane_ok, gwl);
+}
+
+// out[n_bins] (and best[n_bins] of an 8-byte key): all ones
+static int init_first_out(uint64_t *out, uint64_t *best, bool wide, uint32_t n_bins, hipStream_t s) {
+    HIP_TRY(hipMemsetAsync(out, 0xFF, (size_t)n_bins * sizeof(uint64_t), s));
+    if (wide) HIP_TRY(hipMemsetAsync(best, 0xFF, (size_t)n_bins * sizeof(uint64_t), s));
+    return PQPS_OK;
+}
+
+static int first_path(const pqps_column *group_col, uint32_t n_bins) {
+    return !group_col ? FIRST_ONE : n_bins <= kFirstLdsBins ? FIRST_LDS : FIRST_GLOBAL;
+}
+
+int pqps_filter_group_first(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                            const pqps_column *key_col, int key_signed, int descending, uint32_t row_base,
+                            const pqps_column *group_col, uint32_t bin_base, uint32_t n_bins, uint64_t *out, uint64_t *best,
+                            uint64_t *count, void *stream) {
+    if (!ctx || !out || !count) return fail(PQPS_EINVAL, "ctx/out/count is NULL");
+    FirstArgs g;
+    memset(&g, 0, sizeof g);
+    bool wide;
+    int rc = check_first_cols(key_col, group_col, n_bins, best, true, &wide, &g.kwidth_log2, &g.gwidth_log2);
+    if (rc) return rc;
+    if ((uint64_t)row_base + n_rows >= 0xFFFFFFFFull) return fail(PQPS_EINVAL, "row numbers must stay below 2^32 - 1");
+    rc = fused_args(g.e, cols, n_cols, n_rows, pred);
+    if (rc) return rc;
+    hipStream_t s = pick_stream(ctx, stream);
+    HIP_TRY(hipMemsetAsync(count, 0, sizeof(uint64_t), s));
+    rc = init_first_out(out, best, wide, n_bins, s);
+    if (rc || n_rows == 0) return rc;
+    const int path = first_path(group_col, n_bins);
+    const uint32_t table_bytes = path == FIRST_LDS ? n_bins * (uint32_t)sizeof(uint64_t) : 0u;
+    const uint32_t grid = fused_grid(ctx, n_rows, table_bytes);
+    if (path != FIRST_GLOBAL) {
+        rc = grow_group_parts(ctx, s, (size_t)grid * n_bins * 2);
+        if (rc) return rc;
+    }
+    g.kcol = key_col ? key_col->data : nullptr;
+    g.gcol = group_col ? group_col->data : nullptr;
+    g.parts = (uint64_t *)ctx->group_parts;
+    g.kxor = topk_xor(wide, key_signed, descending);
+    g.bin_base = bin_base;
+    g.n_bins = n_bins;
+    g.row_base = row_base;
+    // the instance and its name side by side: pqps_last_kernel() reports the entry that is launched
+    static const struct { void (*fn)(const FirstArgs); const char *name; } fns[3][3][2] = {
+#define PQPS_FIRST_SCAN(P, M, NT) {first_scan_kernel<P, M, NT>, "first_scan_kernel<" #P ", " #M ", NT=" #NT ">"}
+#define PQPS_FIRST_SCANS(P) {{PQPS_FIRST_SCAN(P, FIRST_NARROW, false), PQPS_FIRST_SCAN(P, FIRST_NARROW, true)},   \
+                             {PQPS_FIRST_SCAN(P, FIRST_WIDE_A, false), PQPS_FIRST_SCAN(P, FIRST_WIDE_A, true)},   \
+                             {PQPS_FIRST_SCAN(P, FIRST_WIDE_B, false), PQPS_FIRST_SCAN(P, FIRST_WIDE_B, true)}}
+        PQPS_FIRST_SCANS(FIRST_ONE), PQPS_FIRST_SCANS(FIRST_LDS), PQPS_FIRST_SCANS(FIRST_GLOBAL),
+#undef PQPS_FIRST_SCANS
+#undef PQPS_FIRST_SCAN
+    };
+    // narrow keys: one pass into `out`; an 8-byte key: pass A into `best`, then pass B into `out`
+    for (int mode = wide ? FIRST_WIDE_A : FIRST_NARROW; mode <= (wide ? FIRST_WIDE_B : FIRST_NARROW); mode++) {
+        uint64_t *target = mode == FIRST_WIDE_A ? best : out;
+        g.out = target;
+        g.best = mode == FIRST_WIDE_B ? best : nullptr;
+        g.count = mode == FIRST_WIDE_B ? nullptr : (unsigned long long *)count;
+        const auto &scan = fns[path][mode][g.e.streaming ? 1 : 0];
+        snprintf(g_kernel, sizeof g_kernel, "%s", scan.name);
+        hipEvent_t stop;
+        rc = fused_launch(ctx, scan.fn, grid, table_bytes, s, g, &stop);
+        if (rc) return rc;
+        if (path != FIRST_GLOBAL) {
+            const dim3 sg((n_bins + 63u) / 64u, (grid + kFirstMinParts - 1) / kFirstMinParts);
+            rc = launch_stop(first_min_kernel, sg, 0, s, stop, (const uint64_t *)ctx->group_parts, grid, n_bins, target);
+        }
+        fused_close(ctx, stop, path == FIRST_GLOBAL);
+        if (rc) return rc;
+    }
+    return PQPS_OK;
+}
+
+int pqps_group_first_list(pqps_ctx *ctx, const pqps_column *key_col, int key_signed, int descending, const pqps_column *group_col,
+                          uint32_t bin_base, uint32_t n_bins, uint64_t n_rows, const uint32_t *ids, const uint64_t *count_dev,
+                          uint64_t capacity, uint32_t id_base, uint64_t *out, uint64_t *best, void *stream) {
+    if (!ctx || !out || !count_dev || (capacity && !ids)) return fail(PQPS_EINVAL, "NULL argument");
+    bool wide;
+    uint32_t kwl, gwl;
+    int rc = check_first_cols(key_col, group_col, n_bins, best, false, &wide, &kwl, &gwl);
+    if (rc) return rc;
+    if ((uint64_t)id_base + n_rows >= 0xFFFFFFFFull) return fail(PQPS_EINVAL, "row numbers must stay below 2^32 - 1");
+    hipStream_t s = pick_stream(ctx, stream);
+    rc = init_first_out(out, best, wide, n_bins, s);
+    if (rc || capacity == 0 || n_rows == 0) return rc;
+    const void *kdata = key_col ? key_col->data : nullptr;
+    const void *gdata = group_col ? group_col->data : nullptr;
+    const uint64_t kxor = topk_xor(wide, key_signed, descending);
+    const int path = first_path(group_col, n_bins);
+    const uint32_t lds = path == FIRST_LDS ? n_bins * (uint32_t)sizeof(uint64_t) : 0u;
+    typedef void (*list_fn)(const void *, uint32_t, uint64_t, const void *, uint32_t, uint64_t, const uint32_t *, const uint64_t *,
+                            uint64_t, uint32_t, uint32_t, uint32_t, const uint64_t *, uint64_t *);
+    static const list_fn fns[3][3] = {
+        {first_list_kernel<FIRST_ONE, FIRST_NARROW>, first_list_kernel<FIRST_ONE, FIRST_WIDE_A>, first_list_kernel<FIRST_ONE, FIRST_WIDE_B>},
+        {first_list_kernel<FIRST_LDS, FIRST_NARROW>, first_list_kernel<FIRST_LDS, FIRST_WIDE_A>, first_list_kernel<FIRST_LDS, FIRST_WIDE_B>},
+        {first_list_kernel<FIRST_GLOBAL, FIRST_NARROW>, first_list_kernel<FIRST_GLOBAL, FIRST_WIDE_A>, first_list_kernel<FIRST_GLOBAL, FIRST_WIDE_B>},
+    };
+    const dim3 grid(list_grid(ctx, capacity, path == FIRST_LDS ? 2 : 4));
+    for (int mode = wide ? FIRST_WIDE_A : FIRST_NARROW; mode <= (wide ? FIRST_WIDE_B : FIRST_NARROW); mode++) {
+        hipLaunchKernelGGL(fns[path][mode], grid, dim3(kBlock), lds, s, kdata, kwl, kxor, gdata, gwl, n_rows, ids, count_dev, capacity,
+                           id_base, bin_base, n_bins, (const uint64_t *)(mode == FIRST_WIDE_B ? best : nullptr),
+                           mode == FIRST_WIDE_A ? best : out);
+        HIP_TRY(hipGetLastError());
+    }
     return PQPS_OK;
 }
 

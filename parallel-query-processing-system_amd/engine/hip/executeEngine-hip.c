@@ -2407,6 +2407,46 @@ long long executeQueryOrderIdsHIP(struct engineS *engine, struct whereClauseS *w
     return (long long)n;
 }
 
+/* rows[0 .. n) (table-wide, in the result's order) projected into res (caller holds the table shared and the query's lane):
+ * they become every shard's list in its lane, and the device gather of the columnar SELECT runs over those. */
+static int project_listed_rows(struct query *q, const uint32_t *rows, uint64_t n, const char **selectItems, int numSelectItems,
+                               struct hipColumnarResult *res) {
+    struct hipTable *t = q->t;
+    int rc = 0;
+    /* shard s's k-th row goes to position sub_pos[s][k] of the result */
+    const int n_shards = q->n_shards;
+    unsigned int *sub_pos[HIP_MAX_SHARDS] = { NULL };
+    uint32_t *sub_ids[HIP_MAX_SHARDS] = { NULL };
+    uint64_t biggest = 0;
+    for (int s = 0; s < n_shards && rc == 0; s++) {
+        sub_ids[s] = malloc((size_t)(n ? n : 1) * sizeof **sub_ids);
+        sub_pos[s] = malloc((size_t)(n ? n : 1) * sizeof **sub_pos);
+        if (!sub_ids[s] || !sub_pos[s]) { fprintf(stderr, "HIP engine: out of memory\n"); rc = -1; }
+        q->count[s] = 0;
+    }
+    for (uint64_t i = 0; i < n && rc == 0; i++) {
+        int s = n_shards - 1;
+        while (s > 0 && rows[i] < hipTableShard(t, s)->row0) s--;
+        sub_ids[s][q->count[s]] = rows[i];
+        sub_pos[s][q->count[s]++] = (unsigned int)i;
+    }
+    for (int s = 0; s < n_shards && rc == 0; s++) {
+        struct hipTable *sh = hipTableShard(t, s);
+        struct hipLane *L = query_lane(q, s);
+        if (q->count[s] > biggest) biggest = q->count[s];
+        if (q->count[s] == 0) continue;
+        if (grow_lane_ids(sh, L, q->count[s]) != 0) rc = -1;
+        else if (pqps_upload(lane_copy_ctx(q, s), L->ids_dev, sub_ids[s], q->count[s] * sizeof **sub_ids, NULL) != PQPS_OK ||
+                 pqps_upload(lane_copy_ctx(q, s), L->count_dev, &q->count[s], sizeof(uint64_t), NULL) != PQPS_OK) rc = engine_error("ID upload");
+    }
+    char *tmp = rc == 0 && n_shards > 1 ? malloc((biggest ? biggest : 1) * 8) : NULL;
+    if (rc == 0 && n_shards > 1 && !tmp) rc = -1;
+    if (rc == 0) rc = project_result(q, selectItems, numSelectItems, n, n_shards > 1, sub_pos, tmp, res);
+    for (int s = 0; s < n_shards; s++) { free(sub_ids[s]); free(sub_pos[s]); }
+    free(tmp);
+    return rc;
+}
+
 struct hipColumnarResult *executeQuerySelectOrderedHIP(struct engineS *engine, const char **selectItems, int numSelectItems,
                                                        struct whereClauseS *whereClause, const char *orderColumn,
                                                        bool descending, long long limit, long long *matches) {
@@ -2431,43 +2471,240 @@ struct hipColumnarResult *executeQuerySelectOrderedHIP(struct engineS *engine, c
     uint32_t *rows = NULL;
     uint64_t n = 0, m = 0;
     int rc = order_rows(engine, whereClause, &q, &op, limit, &rows, &n, &m);
-    /* the ordered rows become every shard's list in its lane: shard s's k-th row goes to position sub_pos[s][k] */
-    const int n_shards = q.n_shards;
-    unsigned int *sub_pos[HIP_MAX_SHARDS] = { NULL };
-    uint32_t *sub_ids[HIP_MAX_SHARDS] = { NULL };
-    uint64_t biggest = 0;
-    for (int s = 0; s < n_shards && rc == 0; s++) {
-        sub_ids[s] = malloc((size_t)(n ? n : 1) * sizeof **sub_ids);
-        sub_pos[s] = malloc((size_t)(n ? n : 1) * sizeof **sub_pos);
-        if (!sub_ids[s] || !sub_pos[s]) { fprintf(stderr, "HIP engine: out of memory\n"); rc = -1; }
-        q.count[s] = 0;
-    }
-    for (uint64_t i = 0; i < n && rc == 0; i++) {
-        int s = n_shards - 1;
-        while (s > 0 && rows[i] < hipTableShard(t, s)->row0) s--;
-        sub_ids[s][q.count[s]] = rows[i];
-        sub_pos[s][q.count[s]++] = (unsigned int)i;
-    }
-    for (int s = 0; s < n_shards && rc == 0; s++) {
-        struct hipTable *sh = hipTableShard(t, s);
-        struct hipLane *L = query_lane(&q, s);
-        if (q.count[s] > biggest) biggest = q.count[s];
-        if (q.count[s] == 0) continue;
-        if (grow_lane_ids(sh, L, q.count[s]) != 0) rc = -1;
-        else if (pqps_upload(lane_copy_ctx(&q, s), L->ids_dev, sub_ids[s], q.count[s] * sizeof **sub_ids, NULL) != PQPS_OK ||
-                 pqps_upload(lane_copy_ctx(&q, s), L->count_dev, &q.count[s], sizeof(uint64_t), NULL) != PQPS_OK) rc = engine_error("ID upload");
-    }
-    char *tmp = rc == 0 && n_shards > 1 ? malloc((biggest ? biggest : 1) * 8) : NULL;
-    if (rc == 0 && n_shards > 1 && !tmp) rc = -1;
-    if (rc == 0) rc = project_result(&q, selectItems, numSelectItems, n, n_shards > 1, sub_pos, tmp, res);
-    for (int s = 0; s < n_shards; s++) { free(sub_ids[s]); free(sub_pos[s]); }
-    free(tmp);
+    if (rc == 0) rc = project_listed_rows(&q, rows, n, selectItems, numSelectItems, res);
     free(rows);
     query_close(&q);
     res->numRecords = rc == 0 ? (int)n : 0;
     res->queryTime = now_seconds() - t0;
     res->success = rc == 0;
     if (rc == 0 && matches) *matches = (long long)m;
+    return res;
+}
+
+/* ---- the first row of every group (include/executeEngine-hip.h) ---------------------------------------------------- */
+
+/* One shard's device buffer: [16 B: the matching rows][out: n_bins words][best: n_bins words, command_id only]. */
+struct first_call { const struct group_plan *gp; const struct order_plan *op; uint64_t **buf; };
+
+static int first_fused_call(struct query *q, int s, pqps_ctx *ctx, void *stream, void *arg) {
+    const struct first_call *a = arg;
+    const struct group_plan *gp = a->gp;
+    const struct order_plan *op = a->op;
+    const struct hipTable *sh = hipTableShard(q->t, s);
+    const struct shard_pred *sp = &q->sp[s];
+    const bool grouped = gp->c >= 0 && !gp->single;
+    uint64_t *b = a->buf[s];
+    if (pqps_filter_group_first(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, op->no_key ? NULL : &op->kcol[s], op->key_signed, op->desc,
+                                (uint32_t)sh->row0, grouped ? &gp->gcol[s] : NULL, gp->bin_base, gp->n_bins, b + 2,
+                                op->wide ? b + 2 + gp->n_bins : NULL, b, stream) != PQPS_OK)
+        return engine_error("first-row filter");
+    return 0;
+}
+
+/* One shard's words h (out[n_bins], then best[n_bins] for command_id) merged into the host's: rows are table-wide, so the
+ * minimum word per bin is the answer; command_id compares (best, row). */
+static void first_combine(uint64_t *out, uint64_t *best, const uint64_t *h, uint32_t n_bins, bool wide) {
+    for (uint32_t k = 0; k < n_bins; k++) {
+        if (h[k] == UINT64_MAX) continue;
+        if (!wide) { if (h[k] < out[k]) out[k] = h[k]; continue; }
+        const uint64_t hb = h[n_bins + k];
+        if (out[k] == UINT64_MAX || hb < best[k] || (hb == best[k] && h[k] < out[k])) { out[k] = h[k]; best[k] = hb; }
+    }
+}
+
+/* The words of the query on every shard, merged on the host (first_combine) into out[n_bins] (and best[n_bins] for
+ * command_id), all ones on entry; *matches = the selection's rows.  gp->fused: pqps_filter_group_first on the query's lane;
+ * otherwise the selection, each shard's list left on its own device, and pqps_group_first_list over every list. */
+static int first_bins(struct query *q, const struct group_plan *gp, const struct order_plan *op, uint64_t *out, uint64_t *best,
+                      uint64_t *matches) {
+    const uint32_t n_bins = gp->n_bins;
+    const size_t bytes = 16 + (size_t)n_bins * (op->wide ? 2 : 1) * sizeof(uint64_t);
+    const bool grouped = gp->c >= 0 && !gp->single;
+    uint64_t *buf[HIP_MAX_SHARDS] = { NULL };
+    uint64_t *host = malloc(bytes);
+    int rc = host ? 0 : -1;
+    *matches = 0;
+    if (!host) fprintf(stderr, "HIP engine: out of memory\n");
+    for (int s = 0; s < q->n_shards && rc == 0; s++)
+        if (pqps_malloc(hipTableShard(q->t, s)->ctx, bytes, (void **)&buf[s]) != PQPS_OK) rc = engine_error("first-row buffers");
+    if (rc == 0 && gp->fused) {
+        rc = fused_issue(q, first_fused_call, &(struct first_call){ gp, op, buf });
+        for (int s = 0; s < q->n_shards && rc == 0; s++) {
+            if (hipTableShard(q->t, s)->n_rows == 0) continue;
+            if (pqps_download(lane_copy_ctx(q, s), host, buf[s], bytes, NULL) != PQPS_OK) { rc = engine_error("first-row download"); break; }
+            *matches += host[0];
+            first_combine(out, best, host + 2, n_bins, op->wide);
+        }
+    } else if (rc == 0) {
+        rc = query_lists(q);
+        if (rc == 0) *matches = q->total;
+        for (int s = 0; s < q->n_shards && rc == 0; s++) {
+            struct hipTable *sh = hipTableShard(q->t, s);
+            struct hipLane *L = query_lane(q, s);
+            pqps_ctx *cs = lane_copy_ctx(q, s);
+            if (q->count[s] == 0) continue;
+            if (pqps_group_first_list(cs, op->no_key ? NULL : &op->kcol[s], op->key_signed, op->desc, grouped ? &gp->gcol[s] : NULL,
+                                      gp->bin_base, n_bins, sh->n_rows, L->ids_dev, L->count_dev, q->count[s], (uint32_t)sh->row0,
+                                      buf[s] + 2, op->wide ? buf[s] + 2 + n_bins : NULL, NULL) != PQPS_OK ||
+                pqps_download(cs, host, buf[s], bytes, NULL) != PQPS_OK)
+                rc = engine_error("first-row list");
+            else first_combine(out, best, host + 2, n_bins, op->wide);
+        }
+    }
+    for (int s = 0; s < q->n_shards; s++) if (buf[s]) pqps_free(hipTableShard(q->t, s)->ctx, buf[s]);
+    free(host);
+    return rc;
+}
+
+/* Checks the two columns and the engine; fills the result's column fields and the order plan.  -1: refused, reason on stderr. */
+static int group_first_begin(struct engineS *engine, const char *groupColumn, const char *orderColumn, bool descending,
+                             struct hipGroupFirstResult *res, struct order_plan *op) {
+    res->groupColumn = res->groupKind = res->orderColumn = res->orderKind = -1;
+    res->descending = descending;
+    if (!engine || !engine->record_block || !orderColumn) { fprintf(stderr, "HIP engine: first row per group without an engine or an order column\n"); return -1; }
+    memset(op, 0, sizeof *op);
+    op->c = hipColumnId(orderColumn);
+    if (op->c < 0) { fprintf(stderr, "HIP engine: first row per group: unknown order column '%s'\n", orderColumn); return -1; }
+    const int c = groupColumn ? group_column_id("first row per group", groupColumn) : -1;
+    if (groupColumn && c < 0) return -1;
+    if (((struct hipTable *)engine->record_block)->xch) { fprintf(stderr, "HIP engine: first row per group is not exchanged across ranks\n"); return -1; }
+    op->desc = descending;
+    op->wide = op->c == HIPCOL_COMMAND_ID;
+    op->key_signed = k_group_kind[op->c] == HIPKIND_I32;
+    res->groupColumn = c;
+    res->groupKind = c >= 0 ? k_group_kind[c] : -1;
+    res->orderColumn = op->c;
+    res->orderKind = k_group_kind[op->c];
+    return 0;
+}
+
+/* out[n_bins] (best[n_bins] for command_id) into the result: groups with a row only, in bin order. */
+static int group_first_fill(struct hipGroupFirstResult *res, const struct hipTable *t, const uint64_t *out, const uint64_t *best,
+                            uint32_t n_bins, int32_t lo) {
+    uint64_t *present = calloc((size_t)n_bins + 1, sizeof *present);
+    if (!present) { fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
+    for (uint32_t k = 0; k < n_bins; k++) present[k] = out[k] != UINT64_MAX;
+    const int rc = group_keys_fill(t, res->groupColumn, res->groupKind, lo, present, n_bins, &res->keys, &res->keyText, &res->numGroups);
+    free(present);
+    if (rc != 0) return -1;
+    const size_t n = (size_t)res->numGroups;
+    res->rows = calloc(n + 1, sizeof *res->rows);
+    res->orderKeys = calloc(n + 1, sizeof *res->orderKeys);
+    res->orderText = calloc(n + 1, sizeof *res->orderText);
+    if (!res->rows || !res->orderKeys || !res->orderText) { fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
+    const int oc = res->orderColumn, kind = res->orderKind;
+    size_t g = 0;
+    for (uint32_t k = 0; k < n_bins; k++) {
+        if (out[k] == UINT64_MAX) continue;
+        char buf[32];
+        const char *text = buf;
+        if (kind == HIPKIND_U64) {
+            res->rows[g] = (unsigned int)out[k];
+            res->orderKeys[g] = (long long)(best[k] ^ (res->descending ? UINT64_MAX : 0));
+            snprintf(buf, sizeof buf, "%llu", (unsigned long long)res->orderKeys[g]);
+        } else {
+            hipFirstKeyDecode(kind, res->descending, out[k], &res->orderKeys[g], &res->rows[g]);
+            if (kind == HIPKIND_I32) snprintf(buf, sizeof buf, "%d", (int)res->orderKeys[g]);
+            else if (kind == HIPKIND_BOOL) text = res->orderKeys[g] ? "true" : "false";
+            else if (res->orderKeys[g] < (long long)t->dict[oc].count) text = t->dict[oc].values[res->orderKeys[g]];
+            else { fprintf(stderr, "HIP engine: first row per group: code %lld outside the dictionary\n", res->orderKeys[g]); return -1; }
+        }
+        if (!(res->orderText[g] = strdup(text))) { fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
+        g++;
+    }
+    return 0;
+}
+
+/* The query itself (caller holds the table shared and the query's lane, group_first_begin has passed). */
+static int group_first_run(struct engineS *engine, struct query *q, const char *groupColumn, struct order_plan *op,
+                           struct whereClauseS *whereClause, struct hipGroupFirstResult *res) {
+    struct hipTable *t = q->t;
+    struct group_plan gp;
+    uint64_t *out = NULL, *best = NULL, matches = 0;
+    int rc = group_plan_init(engine, whereClause, q, res->groupColumn, groupColumn, "first row per group", &gp);
+    if (rc == 0 && !gp.empty) {
+        out = malloc((size_t)gp.n_bins * sizeof *out);
+        best = op->wide ? malloc((size_t)gp.n_bins * sizeof *best) : NULL;
+        if (!out || (op->wide && !best)) { fprintf(stderr, "HIP engine: out of memory\n"); rc = -1; }
+        else {
+            memset(out, 0xFF, (size_t)gp.n_bins * sizeof *out);
+            if (best) memset(best, 0xFF, (size_t)gp.n_bins * sizeof *best);
+        }
+        op->fused = gp.fused;
+        op->no_key = t->col[op->c].width == 0;
+        for (int s = 0; s < q->n_shards; s++) {
+            const struct hipTable *sh = hipTableShard(t, s);
+            op->kcol[s] = gp.fused && op->c == HIPCOL_SUDO_USED && sh->sudo_bits.data ? sh->sudo_bits : sh->col[op->c];
+        }
+    }
+    if (rc == 0 && !gp.empty) rc = first_bins(q, &gp, op, out, best, &matches);
+    if (rc == 0) rc = group_first_fill(res, t, out, best, gp.empty ? 0u : gp.n_bins, gp.lo);
+    if (rc == 0) res->total = (long long)matches;
+    free(out);
+    free(best);
+    return rc;
+}
+
+static void group_first_clear(struct hipGroupFirstResult *res) {
+    free_group_keys(res->keys, res->keyText, res->numGroups);
+    for (int g = 0; g < res->numGroups && res->orderText; g++) free(res->orderText[g]);
+    free(res->orderText);
+    free(res->orderKeys);
+    free(res->rows);
+}
+
+struct hipGroupFirstResult *executeQueryGroupFirstHIP(struct engineS *engine, const char *groupColumn, const char *orderColumn,
+                                                      bool descending, struct whereClauseS *whereClause) {
+    const double t0 = now_seconds();
+    struct hipGroupFirstResult *res = calloc(1, sizeof *res);
+    if (!res) { fprintf(stderr, "HIP engine: out of memory\n"); return NULL; }
+    struct order_plan op;
+    if (group_first_begin(engine, groupColumn, orderColumn, descending, res, &op) != 0) return res;
+    struct query q;
+    if (!query_open(engine, &q)) return res;                             /* reason on stderr */
+    if (group_first_run(engine, &q, groupColumn, &op, whereClause, res) == 0) res->success = true;
+    query_close(&q);
+    res->queryTime = now_seconds() - t0;
+    return res;
+}
+
+void freeGroupFirstResultHIP(struct hipGroupFirstResult *res) {
+    if (!res) return;
+    group_first_clear(res);
+    free(res);
+}
+
+struct hipColumnarResult *executeQuerySelectGroupFirstHIP(struct engineS *engine, const char **selectItems, int numSelectItems,
+                                                          struct whereClauseS *whereClause, const char *groupColumn,
+                                                          const char *orderColumn, bool descending, long long *matches) {
+    if (matches) *matches = 0;
+    struct hipColumnarResult *res = calloc(1, sizeof *res);
+    if (!res) { perror("Failed to allocate memory for result set"); exit(EXIT_FAILURE); }
+    if (!engine || !engine->record_block) return res;
+    if (selectItems == NULL || numSelectItems == 0) { selectItems = (const char **)k_all_columns; numSelectItems = 12; }
+    res->numColumns = numSelectItems;
+    res->columnNames = calloc((size_t)numSelectItems, sizeof(char *));
+    res->columnKinds = calloc((size_t)numSelectItems, sizeof(int));
+    res->values = calloc((size_t)numSelectItems, sizeof(void *));
+    res->dictionaries = calloc((size_t)numSelectItems, sizeof(*res->dictionaries));
+    res->dictionarySizes = calloc((size_t)numSelectItems, sizeof(int));
+    if (!res->columnNames || !res->columnKinds || !res->values || !res->dictionaries || !res->dictionarySizes) { perror("Failed to allocate memory for result set"); exit(EXIT_FAILURE); }
+    const double t0 = now_seconds();
+    struct hipGroupFirstResult gf;
+    struct order_plan op;
+    memset(&gf, 0, sizeof gf);
+    if (group_first_begin(engine, groupColumn, orderColumn, descending, &gf, &op) != 0) return res;
+    struct query q;
+    if (!query_open(engine, &q)) return res;                             /* reason on stderr */
+    int rc = group_first_run(engine, &q, groupColumn, &op, whereClause, &gf);
+    const uint64_t n = rc == 0 ? (uint64_t)gf.numGroups : 0;
+    if (rc == 0) rc = project_listed_rows(&q, gf.rows, n, selectItems, numSelectItems, res);
+    query_close(&q);
+    res->numRecords = rc == 0 ? (int)n : 0;
+    res->queryTime = now_seconds() - t0;
+    res->success = rc == 0;
+    if (rc == 0 && matches) *matches = gf.total;
+    group_first_clear(&gf);
     return res;
 }
 

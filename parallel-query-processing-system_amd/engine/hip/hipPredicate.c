@@ -1096,3 +1096,15 @@ int hipBucketBounds(const char *column, const char *const *dict, int dict_count,
     *n_buckets = (uint32_t)n;
     return 0;
 }
+
+/* ---- the word of pqps_filter_group_first, undone --------------------------------------------------------------------- */
+
+int hipFirstKeyDecode(int kind, int descending, unsigned long long word, long long *key, unsigned int *row) {
+    if (kind != HIPKIND_I32 && kind != HIPKIND_BOOL && kind != HIPKIND_DICT) return -1;
+    if (word == ~0ull) return 0;
+    uint32_t img = (uint32_t)(word >> 32);
+    if (descending) img = ~img;
+    if (key) *key = kind == HIPKIND_I32 ? (long long)(int32_t)(img ^ 0x80000000u) : (long long)img;
+    if (row) *row = (unsigned int)(word & 0xFFFFFFFFull);
+    return 1;
+}
