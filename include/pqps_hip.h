@@ -219,7 +219,10 @@ int pqps_filter_flags(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols,
  * numbers, `range` = 2 device u64 as written by pqps_index_probe); rows that
  * satisfy `pred` are APPENDED, candidate order preserved, at
  * out_ids[*out_count ...], and *out_count (device u64) is advanced -- several
- * probes concatenate without a host round trip (executeEngine-serial.c:444-448). */
+ * probes concatenate without a host round trip (executeEngine-serial.c:444-448).
+ * Only out_ids[0 .. out_capacity) is ever written: an ID whose place is at or past out_capacity is dropped, and
+ * *out_count still advances by every row that passed (a count above out_capacity says the list was cut), also
+ * when it was at or above out_capacity before the call.  IDs are row + id_base in 32-bit arithmetic. */
 int pqps_filter_gather(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols,
                        const uint32_t *cand, const uint64_t *range, uint64_t max_candidates,
                        uint32_t id_base, const pqps_predicate *pred,
@@ -228,13 +231,16 @@ int pqps_filter_gather(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols,
 
 /* Builds perm[0..n) = row numbers sorted by (key ascending, row DESCENDING)
  * and sorted_keys[0..n) (same width as the column).  key_kind: 0 = unsigned,
- * 1 = signed i32. */
+ * 1 = signed i32.  Nothing behind perm[n - 1] / sorted_keys[n - 1] is written; n_rows == 0
+ * returns PQPS_OK and writes nothing.  Synchronises the stream. */
 int pqps_index_build(pqps_ctx *ctx, const pqps_column *col, uint64_t n_rows, int key_kind,
                      uint32_t *perm, void *sorted_keys, void *stream);
 
 /* range[0] = first position with key >= key_lo, range[1] = first position with
  * key > key_hi (inclusive window, findRange semantics); keys as raw 64-bit
- * patterns, compared signed when key_kind == 1. */
+ * patterns, compared signed when key_kind == 1.  The key is the low `width` bytes of
+ * its pattern (an i32 key may come zero- or sign-extended).  range[1] is never below
+ * range[0]: key_lo > key_hi gives the empty range at range[0].  n_rows == 0 gives (0, 0). */
 int pqps_index_probe(pqps_ctx *ctx, const void *sorted_keys, uint32_t width, int key_kind,
                      uint64_t n_rows, uint64_t key_lo, uint64_t key_hi,
                      uint64_t *range, void *stream);
@@ -244,7 +250,8 @@ int pqps_index_probe(pqps_ctx *ctx, const void *sorted_keys, uint32_t width, int
  * `index_column` = the column the index (perm / sorted_keys) was built on.  When `pred` is nothing but the probed
  * comparison itself -- ONE leaf on the indexed column whose window is [key_lo, key_hi], accepted when it holds (the
  * reference's `risk_level > 3` with an index on risk_level) -- every row found passes, and the rows are copied in
- * index order instead of evaluated (PQPS_INDEX_COPY=0, tests: always evaluate; same result). */
+ * index order instead of evaluated (PQPS_INDEX_COPY=0, tests: always evaluate; same result) -- cut at out_capacity
+ * and counted exactly as pqps_filter_gather does. */
 int pqps_index_select(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, const pqps_column *index_column,
                       const uint32_t *perm, const void *sorted_keys, int key_kind, uint64_t n_rows,
                       uint64_t key_lo, uint64_t key_hi, uint32_t id_base, const pqps_predicate *pred,
@@ -273,7 +280,16 @@ int pqps_project_column(pqps_ctx *ctx, const pqps_column *col, const uint32_t *i
  * (`world` x (slot_stride - PQPS_SLOT_HEADER_WORDS) u64) and writes the merged order.  One probed
  * condition per call; a query with several probed conditions (whose results the serial engine
  * concatenates, duplicates included) merges each condition's segment with its own call.
- * Synchronises the stream (the sort needs the total on the host). */
+ * Synchronises the stream (the sort needs the total on the host).
+ *   pqps_gather_keys: keys_out[i] for i < min(*count_dev, capacity), row = ids[i] - id_base in 32-bit arithmetic; nothing
+ *     behind that is written.  pqps_project_column stops at the same place.
+ *   pqps_merge_index_slots: the slots are those of pqps_merge_slots (a slot that reports more than slot_stride -
+ *     PQPS_SLOT_HEADER_WORDS IDs holds that many).  Rank r's keys begin at key_slots[r * (slot_stride -
+ *     PQPS_SLOT_HEADER_WORDS)] -- the key slots are that far apart, NOT slot_stride -- key i going with ID i of the slot.
+ *     The call sorts the union, so the IDs of a slot may come in any order (the engine delivers leaf order).  `totals`
+ *     must not be NULL (PQPS_EINVAL): totals[0] = IDs held by the slots, totals[1] = the sum of the reported counts.
+ *     totals[0] > merged_capacity: PQPS_EOVERFLOW, both totals written, `merged` untouched.  Otherwise merged[0 .. totals[0])
+ *     is written and nothing behind it. */
 int pqps_gather_keys(pqps_ctx *ctx, const pqps_column *col, int key_kind, const uint32_t *ids, const uint64_t *count_dev,
                      uint64_t capacity, uint32_t id_base, uint64_t *keys_out, void *stream);
 int pqps_merge_index_slots(pqps_ctx *ctx, const uint32_t *slots, const uint64_t *key_slots, uint32_t world,
@@ -287,7 +303,11 @@ int pqps_merge_index_slots(pqps_ctx *ctx, const uint32_t *slots, const uint64_t 
  * MPI_Allgatherv of the data, engine/mpi/executeEngine-mpi.c:753-765, become a single
  * collective).  Writes the rank-order concatenation of the ID lists to `merged` and, if
  * `totals` != NULL, totals[0] = IDs merged, totals[1] = sum of the reported counts (larger
- * => a slot overflowed).  Everything stays on the device. */
+ * => a slot overflowed).  A slot that reports more than slot_stride - PQPS_SLOT_HEADER_WORDS IDs
+ * holds that many; what a slot holds behind its count is never read into `merged`.
+ * merged_capacity below totals[0]: the call still returns PQPS_OK, `merged` holds the first
+ * merged_capacity IDs of the concatenation, nothing behind them is written, and totals[0] says
+ * what there was (the caller compares).  Everything stays on the device. */
 #define PQPS_SLOT_HEADER_WORDS 4
 int pqps_merge_slots(pqps_ctx *ctx, const uint32_t *slots, uint32_t world, uint64_t slot_stride,
                      uint32_t *merged, uint64_t merged_capacity, uint64_t *totals, void *stream);
