@@ -518,6 +518,23 @@ struct hipColumnarResult *executeQuerySelectOrderedHIP(struct engineS *engine, c
                                                        struct whereClauseS *whereClause, const char *orderColumn,
                                                        bool descending, long long limit, long long *matches);
 
+/* ORDER BY k1 [DESC], ... , kN [DESC] LIMIT: 1 <= numKeys <= HIP_ORDER_MAX_KEYS (hipPredicate.h).  The rows and *matches are
+ * those of the one-column calls; the order is lexicographic by the keys, each in its column's order above and reversed by its
+ * own `descending`; rows equal in ALL keys come in ascending row number, whatever the directions.  A column named a second
+ * time and a single-valued string column carry no information and are ignored: with one key left the query IS the
+ * one-column query, with none the answer is the row order.  Otherwise the keys are packed into one number per row
+ * (hipOrderKeyPlan: ceil(log2 domain) bits per key from the dictionary counts and the table-wide i32 bounds) and the three
+ * paths above run on it: up to 32 bits as the narrow key (limit <= 1024 for the top-K paths), up to 64 as the wide key
+ * (limit <= 512); more than 64 bits, or command_id among several keys, takes one stable radix sort per key
+ * (pqps_sort_list_chain) whatever the limit.  Refused (-1 / success = false, reason on stderr): numKeys outside 1 .. 4, a NULL
+ * or unknown column, an engine joined across ranks. */
+struct hipOrderKey { const char *column; bool descending; };
+long long executeQueryOrderIdsByHIP(struct engineS *engine, struct whereClauseS *whereClause, const struct hipOrderKey *keys,
+                                    int numKeys, long long limit, unsigned int **ids, long long *matches, double *queryTime);
+struct hipColumnarResult *executeQuerySelectOrderedByHIP(struct engineS *engine, const char **selectItems, int numSelectItems,
+                                                         struct whereClauseS *whereClause, const struct hipOrderKey *keys, int numKeys,
+                                                         long long limit, long long *matches);
+
 /* The first row of every group: per value of `groupColumn`, the matching row that comes first in the order of `orderColumn`
  * -- "the latest command of every user", "the first sudo on every host" (SQL: DISTINCT ON, ROW_NUMBER() OVER (PARTITION BY
  * g ORDER BY k) = 1, argMin / argMax; no counterpart in the reference, reached through the C API and the Python package only

@@ -160,6 +160,41 @@ int hipBucketBounds(const char *column, const char *const *dict, int dict_count,
  * *key = the i32 value, 0 / 1, or the dictionary code, and *row = the table-wide row number (either may be NULL). */
 int hipFirstKeyDecode(int kind, int descending, unsigned long long word, long long *key, unsigned int *row);
 
+/* THE PACKED KEY OF ORDER BY k1 [DESC], ... , kN [DESC].  Turns a key list into the fields of one unsigned number whose
+ * ascending order is the lexicographic order of the keys, each in its own direction; pure host code.
+ *   INPUT   columns[0 .. n_keys) / descending[0 .. n_keys): the key list, 1 <= n_keys <= HIP_ORDER_MAX_KEYS;
+ *           dict_counts[c], lo[c], hi[c] (c = HIPCOL_* id, PQPS_MAX_COLUMNS entries each): the dictionary count of every
+ *           string column and the table-wide [lo, hi] of every i32 column (lo > hi: no rows); other entries are not read.
+ *   KEY LIST  a column named a second time is ignored at its later positions; a string column of at most one value is
+ *           ignored; what remains are the fields, field 0 the most significant.
+ *   FIELD   domain D = the dictionary count, 2 for sudo_used, hi - lo + 1 for an i32 column (2^64 for command_id);
+ *           bits = ceil(log2 D) (0 for D <= 1, 32 for an i32 column over more than 2^31 values, 64 for command_id);
+ *           base = lo as u32 for an i32 column, else 0; shift = the bits of all later fields (0 in the CHAIN form);
+ *           a row's field = min(value - base, 2^bits - 1) ^ (descending ? 2^bits - 1 : 0), value - base in 32-bit arithmetic
+ *   FORM    HIPORDER_ROWS    no field remains: the answer is the row order
+ *           HIPORDER_ONE     one field remains: the one-column ORDER BY of field[0]
+ *           HIPORDER_PACK32  T = total_bits <= 32: one u64 per row, packed << 32 | row
+ *           HIPORDER_PACK64  32 < T <= 64: the pair (packed, row)
+ *           HIPORDER_CHAIN   T > 64, or command_id among two or more fields: no packed key, one stable sort per field
+ * Returns 0, or -1 with the reason on stderr and *plan untouched for: a NULL argument, n_keys outside
+ * 1 .. HIP_ORDER_MAX_KEYS, a NULL or unknown column. */
+#define HIP_ORDER_MAX_KEYS 4
+enum { HIPORDER_ROWS = 0, HIPORDER_ONE = 1, HIPORDER_PACK32 = 2, HIPORDER_PACK64 = 3, HIPORDER_CHAIN = 4 };
+struct hipOrderField {
+    int column;                  /* HIPCOL_* id                                                                   */
+    int kind;                    /* HIPKIND_*                                                                     */
+    int descending;
+    uint32_t base, bits, shift;
+};
+struct hipOrderKeyPlan {
+    int form;                    /* HIPORDER_*                                                                    */
+    int n_fields;
+    uint32_t total_bits;         /* T                                                                             */
+    struct hipOrderField field[HIP_ORDER_MAX_KEYS];
+};
+int hipOrderKeyPlan(const char *const *columns, const int *descending, int n_keys, const int *dict_counts,
+                    const int *lo, const int *hi, struct hipOrderKeyPlan *plan);
+
 /* Column name -> HIPCOL_* id, -1 if unknown. */
 int hipColumnId(const char *name);
 

@@ -580,6 +580,43 @@ int pqps_topk_list(pqps_ctx *ctx, const pqps_column *key_col, int key_signed, in
 int pqps_sort_list(pqps_ctx *ctx, const pqps_column *key_col, int key_signed, int descending, const uint32_t *ids, uint64_t n,
                    uint32_t id_base, uint32_t *out_ids, uint64_t *out_keys, void *stream);
 
+/* ---- ORDER BY k1 [DESC], ... , kN [DESC] LIMIT K: several columns packed into one key ------------------------------
+ * Field j (j = 0 the most significant) of a row whose column holds v:
+ *     bin = v - base (32-bit arithmetic)     field = min(bin, 2^bits - 1) ^ (descending ? 2^bits - 1 : 0)
+ *     packed = OR of field_j << shift_j
+ * The caller chooses base and bits so that every bin fits (base = the column's lowest value as u32 for an i32 column, else
+ * 0; bits = ceil(log2(domain))) and the shifts so that the fields do not overlap and earlier fields lie higher; a value
+ * outside its domain is clamped into its own field.  T = the highest bit any field reaches (max of shift + bits):
+ *     T <= 32   narrow keys, one u64: packed << 32 | row          K = 1 .. PQPS_TOPK_MAX
+ *     T <= 64   wide keys, two u64: (packed, row)                 K = 1 .. PQPS_TOPK_MAX_WIDE
+ * exactly the key forms, outputs and scratch rule (pqps_topk_scratch_bytes, wide = T > 32) of the one-column calls above;
+ * ties in every field go to the ascending row number.  Field columns are 1, 2 or 4 bytes wide; pqps_filter_topk_multi also
+ * takes bit planes.  PQPS_EINVAL: n_fields outside 1 .. PQPS_ORDER_MAX_FIELDS, a field of more than 32 bits, a field that
+ * ends past bit 64 (so T > 64), overlapping fields, K over the form's bound, a bit plane in a list call.
+ * pqps_filter_topk_multi: as pqps_filter_topk, every field's column read in the steps that hold a match.
+ * pqps_topk_list_multi:   the selection of pqps_topk_list, but SYNCHRONOUS: the keys of the list are packed into a temporary
+ *   of n keys that the call allocates, waits for and frees (one hipMalloc, one stream synchronize, one hipFree per call).
+ * pqps_sort_list_multi:   as pqps_sort_list; out_keys (may be NULL) = the packed word of every row as u64.
+ * pqps_sort_list_chain:   the order of 1 .. PQPS_ORDER_MAX_FIELDS whole one-column keys (as pqps_sort_list takes them: 1, 2, 4
+ *   or 8 bytes wide), for key lists that fit no packed key: one stable radix sort by row, then one per key from the last
+ *   to the first.  out_keys (may be NULL): n_keys arrays of n u64, array j = key j's image (pqps_sort_list's) of every
+ *   row of out_ids -- ascending (image 0, ..., image N-1, row) is the answer's order.  Synchronous. */
+#define PQPS_ORDER_MAX_FIELDS 4u
+typedef struct pqps_order_field {
+    pqps_column col;
+    uint32_t base, bits, shift;
+    int descending;
+} pqps_order_field;
+int pqps_filter_topk_multi(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                           const pqps_order_field *fields, uint32_t n_fields, uint32_t row_base, uint32_t k,
+                           void *scratch, uint64_t scratch_bytes, uint64_t *out, uint64_t *count, void *stream);
+int pqps_topk_list_multi(pqps_ctx *ctx, const pqps_order_field *fields, uint32_t n_fields, const uint32_t *ids, uint64_t n,
+                         uint32_t id_base, uint32_t k, void *scratch, uint64_t scratch_bytes, uint64_t *out, void *stream);
+int pqps_sort_list_multi(pqps_ctx *ctx, const pqps_order_field *fields, uint32_t n_fields, const uint32_t *ids, uint64_t n,
+                         uint32_t id_base, uint32_t *out_ids, uint64_t *out_keys, void *stream);
+int pqps_sort_list_chain(pqps_ctx *ctx, const pqps_column *key_cols, const int *key_signed, const int *descending, uint32_t n_keys,
+                         const uint32_t *ids, uint64_t n, uint32_t id_base, uint32_t *out_ids, uint64_t *out_keys, void *stream);
+
 /* ---- the first row of every group: per bin, the matching row that comes first in the order of a key column -------------
  * No counterpart in the reference (SQL: DISTINCT ON, ROW_NUMBER() OVER (PARTITION BY g ORDER BY k) = 1, argMin / argMax).
  * BINS: those of pqps_filter_group ((value - bin_base) in 32-bit arithmetic; rows whose bin is >= n_bins are left out);

@@ -256,6 +256,27 @@ assert C.sizeof(Predicate) == 880 and C.sizeof(Pass) == 976          # struct hi
 assert C.sizeof(ResultSet) == 48 and C.sizeof(EngineS) == 72
 
 
+class OrderField(C.Structure):                               # pqps_order_field
+    _fields_ = [("col", Column), ("base", C.c_uint32), ("bits", C.c_uint32), ("shift", C.c_uint32), ("descending", C.c_int)]
+
+
+class OrderKey(C.Structure):                                 # struct hipOrderKey
+    _fields_ = [("column", C.c_char_p), ("descending", C.c_bool)]
+
+
+class OrderPlanField(C.Structure):                           # struct hipOrderField
+    _fields_ = [("column", C.c_int), ("kind", C.c_int), ("descending", C.c_int),
+                ("base", C.c_uint32), ("bits", C.c_uint32), ("shift", C.c_uint32)]
+
+
+ORDER_MAX_KEYS = 4                                           # HIP_ORDER_MAX_KEYS
+ORDER_ROWS, ORDER_ONE, ORDER_PACK32, ORDER_PACK64, ORDER_CHAIN = range(5)   # HIPORDER_*
+
+
+class OrderKeyPlan(C.Structure):                             # struct hipOrderKeyPlan
+    _fields_ = [("form", C.c_int), ("n_fields", C.c_int), ("total_bits", C.c_uint32), ("field", OrderPlanField * ORDER_MAX_KEYS)]
+
+
 class PqpsError(RuntimeError):
     pass
 
@@ -546,6 +567,16 @@ def lib():
                                    vp, u64, vp, vp, vp]
     L.pqps_topk_list.argtypes = [vp, C.POINTER(Column), C.c_int, C.c_int, vp, u64, u32, u32, vp, u64, vp, vp]
     L.pqps_sort_list.argtypes = [vp, C.POINTER(Column), C.c_int, C.c_int, vp, u64, u32, vp, vp, vp]
+    L.pqps_filter_topk_multi.argtypes = [vp, C.POINTER(Column), u32, u64, C.POINTER(Predicate), C.POINTER(OrderField), u32, u32, u32,
+                                         vp, u64, vp, vp, vp]
+    L.pqps_topk_list_multi.argtypes = [vp, C.POINTER(OrderField), u32, vp, u64, u32, u32, vp, u64, vp, vp]
+    L.pqps_sort_list_multi.argtypes = [vp, C.POINTER(OrderField), u32, vp, u64, u32, vp, vp, vp]
+    L.pqps_sort_list_chain.argtypes = [vp, C.POINTER(Column), C.POINTER(C.c_int), C.POINTER(C.c_int), u32, vp, u64, u32, vp, vp, vp]
+    L.hipOrderKeyPlan.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                  C.POINTER(C.c_int), C.POINTER(OrderKeyPlan)]
+    L.executeQueryOrderIdsByHIP.restype = C.c_longlong
+    L.executeQueryOrderIdsByHIP.argtypes = [E, W, C.POINTER(OrderKey), C.c_int, C.c_longlong, C.POINTER(C.POINTER(C.c_uint)),
+                                            C.POINTER(C.c_longlong), C.POINTER(C.c_double)]
     L.pqps_filter_group_first.argtypes = [vp, C.POINTER(Column), u32, u64, C.POINTER(Predicate), C.POINTER(Column), C.c_int, C.c_int, u32,
                                           C.POINTER(Column), u32, u32, vp, vp, vp, vp]
     L.pqps_group_first_list.argtypes = [vp, C.POINTER(Column), C.c_int, C.c_int, C.POINTER(Column), u32, u32, u64, vp, vp, u64, u32,
@@ -564,6 +595,9 @@ def lib():
     L.executeQuerySelectGroupFirstHIP.restype = CR
     L.executeQuerySelectGroupFirstHIP.argtypes = [E, C.POINTER(C.c_char_p), C.c_int, W, C.c_char_p, C.c_char_p, C.c_bool,
                                                   C.POINTER(C.c_longlong)]
+    L.executeQuerySelectOrderedByHIP.restype = CR
+    L.executeQuerySelectOrderedByHIP.argtypes = [E, C.POINTER(C.c_char_p), C.c_int, W, C.POINTER(OrderKey), C.c_int, C.c_longlong,
+                                                 C.POINTER(C.c_longlong)]
     L.freeColumnarResultHIP.argtypes = [CR]
     L.hipColumnarCellText.restype = vp
     L.hipColumnarCellText.argtypes = [CR, C.c_int, C.c_int]
@@ -776,6 +810,71 @@ def merge_dictionaries(old, new, column="user_name"):
     if lib().hipMergeDictionaries(a, len(old), b, len(new), COL[column], merged, C.byref(count), lut_old, lut_new, C.byref(identity)) != 0:
         raise PqpsError("hipMergeDictionaries refused the lists (reason on stderr)")
     return list(merged[:count.value]), list(lut_old[:len(old)]), list(lut_new[:len(new)]), bool(identity.value)
+
+
+def order_keys(keys):
+    """A key list -- column names or (column, descending) pairs -- as (hipOrderKey array, count)."""
+    pairs = [(k, False) if isinstance(k, (str, bytes)) else (k[0], bool(k[1])) for k in keys]
+    arr = (OrderKey * max(1, len(pairs)))()
+    for i, (name, desc) in enumerate(pairs):
+        arr[i].column = name.encode() if isinstance(name, str) else name
+        arr[i].descending = desc
+    return arr, len(pairs)
+
+
+def order_key_plan(keys, dict_counts=None, bounds=None):
+    """hipOrderKeyPlan: `keys` as order_keys takes them, dict_counts {column: count}, bounds {column: (lo, hi)} ->
+    dict(form, total_bits, fields=[dict(column, kind, descending, base, bits, shift), ...]).  Raises PqpsError when the key
+    list is refused (reason on stderr)."""
+    pairs = [(k, False) if isinstance(k, (str, bytes)) else (k[0], bool(k[1])) for k in keys]
+    names = (C.c_char_p * max(1, len(pairs)))(*[n.encode() if isinstance(n, str) else n for n, _ in pairs])
+    desc = (C.c_int * max(1, len(pairs)))(*[int(d) for _, d in pairs])
+    counts, lo, hi = (C.c_int * 12)(), (C.c_int * 12)(), (C.c_int * 12)()
+    for name, count in (dict_counts or {}).items():
+        counts[COL[name]] = count
+    for name, (l, h) in (bounds or {}).items():
+        lo[COL[name]], hi[COL[name]] = l, h
+    plan = OrderKeyPlan()
+    if lib().hipOrderKeyPlan(names, desc, len(pairs), counts, lo, hi, C.byref(plan)) != 0:
+        raise PqpsError("hipOrderKeyPlan refused the key list (reason on stderr)")
+    fields = [dict(column=f.column, kind=f.kind, descending=bool(f.descending), base=f.base, bits=f.bits, shift=f.shift)
+              for f in plan.field[:plan.n_fields]]
+    return dict(form=plan.form, total_bits=plan.total_bits, fields=fields)
+
+
+def order_fields(fields):
+    """[(Column, base, bits, shift, descending), ...] as a pqps_order_field array."""
+    arr = (OrderField * max(1, len(fields)))()
+    for i, (col, base, bits, shift, desc) in enumerate(fields):
+        arr[i].col, arr[i].base, arr[i].bits, arr[i].shift, arr[i].descending = col, base, bits, shift, int(desc)
+    return arr
+
+
+def filter_topk_multi(ctx, cols, n_cols, n_rows, pred, fields, row_base, k, scratch_dev, scratch_bytes, out_dev, count_dev, stream=None):
+    """pqps_filter_topk_multi; `fields` as order_fields takes them.  -> the status (PQPS_OK = 0)."""
+    return lib().pqps_filter_topk_multi(ctx.h, cols, n_cols, n_rows, C.byref(pred) if isinstance(pred, Predicate) else pred, order_fields(fields), len(fields), row_base, k,
+                                        scratch_dev, scratch_bytes, out_dev, count_dev, stream)
+
+
+def topk_list_multi(ctx, fields, ids_dev, n, id_base, k, scratch_dev, scratch_bytes, out_dev, stream=None):
+    """pqps_topk_list_multi -> the status."""
+    return lib().pqps_topk_list_multi(ctx.h, order_fields(fields), len(fields), ids_dev, n, id_base, k, scratch_dev, scratch_bytes,
+                                      out_dev, stream)
+
+
+def sort_list_multi(ctx, fields, ids_dev, n, id_base, out_ids_dev, out_keys_dev=None, stream=None):
+    """pqps_sort_list_multi -> the status."""
+    return lib().pqps_sort_list_multi(ctx.h, order_fields(fields), len(fields), ids_dev, n, id_base, out_ids_dev, out_keys_dev, stream)
+
+
+def sort_list_chain(ctx, keys, ids_dev, n, id_base, out_ids_dev, out_keys_dev=None, stream=None):
+    """pqps_sort_list_chain; keys: [(Column, key_signed, descending), ...] -> the status."""
+    cols = (Column * max(1, len(keys)))()
+    for i, (col, _, _) in enumerate(keys):
+        cols[i].data, cols[i].width = col.data, col.width
+    signed = (C.c_int * max(1, len(keys)))(*[int(sg) for _, sg, _ in keys])
+    desc = (C.c_int * max(1, len(keys)))(*[int(d) for _, _, d in keys])
+    return lib().pqps_sort_list_chain(ctx.h, cols, signed, desc, len(keys), ids_dev, n, id_base, out_ids_dev, out_keys_dev, stream)
 
 
 BUCKET_PREFIX, BUCKET_WIDTH = 1, 2                          # HIPBUCKET_* (include/executeEngine-hip.h)
@@ -1233,6 +1332,23 @@ class HipEngine:
         lib().free(ids)
         return out, int(matches.value)
 
+    def order_ids_by(self, keys, chain=None, limit=None):
+        """executeQueryOrderIdsByHIP: (ids, matches) as order_ids, ordered by up to four keys -- column names or (column,
+        descending) pairs, the first the most significant; rows equal in all keys come in ascending row number.  Raises
+        PqpsError when the engine refuses (reason on stderr)."""
+        wl = WhereList(chain)
+        arr, n_keys = order_keys(keys)
+        ids = C.POINTER(C.c_uint)()
+        matches = C.c_longlong()
+        qt = C.c_double()
+        n = lib().executeQueryOrderIdsByHIP(self.e, wl.ptr, arr, n_keys, int(limit or 0), C.byref(ids), C.byref(matches), C.byref(qt))
+        if n < 0:
+            raise PqpsError(f"order_ids_by({list(keys)!r}) refused or failed (reason on stderr)")
+        out = list(ids[:n])
+        lib().free(ids)
+        self.last_query_time = qt.value
+        return out, int(matches.value)
+
     def count_distinct_total(self, value_column, group_column=None, chain=None):
         """executeQueryCountDistinctHIP: ([(key_text, distinct), ...], total) -- the number of different values of
         `value_column` over the rows select_ids(chain) returns, in the key order of group_count(group_column, chain), or one
@@ -1330,6 +1446,23 @@ class HipEngine:
             if res:
                 lib().freeColumnarResultHIP(res)
             raise PqpsError(f"select_ordered({order_column!r}) refused or failed (reason on stderr)")
+        out = self._columnar_dict(res, text)
+        out["matches"] = int(matches.value)
+        return out
+
+    def select_ordered_by(self, columns, chain, keys, limit=None, text=True):
+        """executeQuerySelectOrderedByHIP: the dict select_columnar returns, its rows those of order_ids_by(keys, chain,
+        limit) in that order, plus `matches`.  Raises PqpsError when the engine refuses (reason on stderr)."""
+        wl = WhereList(chain)
+        items = (C.c_char_p * max(1, len(columns or [])))(*[c.encode() for c in (columns or [])])
+        arr, n_keys = order_keys(keys)
+        matches = C.c_longlong()
+        res = lib().executeQuerySelectOrderedByHIP(self.e, items if columns else None, len(columns or []), wl.ptr, arr, n_keys,
+                                                   int(limit or 0), C.byref(matches))
+        if not res or not res.contents.success:
+            if res:
+                lib().freeColumnarResultHIP(res)
+            raise PqpsError(f"select_ordered_by({list(keys)!r}) refused or failed (reason on stderr)")
         out = self._columnar_dict(res, text)
         out["matches"] = int(matches.value)
         return out

@@ -28,6 +28,7 @@
 #include "group_kernels.hpp"
 #include "aggregate_kernels.hpp"
 #include "topk_kernels.hpp"
+#include "order_multi_kernels.hpp"
 #include "first_kernels.hpp"
 #include "distinct_kernels.hpp"
 #include "group_pair_kernels.hpp"
@@ -3446,6 +3447,55 @@ int pqps_topk_list(pqps_ctx *ctx, const pqps_column *key_col, int key_signed, in
                               (TKey<false> *)out, nullptr);
 }
 
+// The buffers of a list sort and its first stable pass.  After list_sort_open `rows` holds ids[0 .. n) ascending; every
+// list_sort_by_key sorts the pairs (ka[i], rows[i]) stably by key and leaves them in `ka` / `rows` again.
+struct ListSort {
+    pqps_sort::Workspace w;
+    uint32_t *ra = nullptr, *rb = nullptr, *rows = nullptr, *spare = nullptr;
+    uint64_t *ka = nullptr, *kb = nullptr;
+};
+
+static hipError_t list_sort_open(pqps_ctx *ctx, ListSort &b, const uint32_t *ids, uint64_t n, hipStream_t s) {
+    hipError_t e = pqps_sort::workspace_alloc(b.w, n);
+    if (e == hipSuccess) e = hipMalloc((void **)&b.ra, n * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&b.rb, n * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&b.rows, n * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&b.spare, n * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&b.ka, n * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&b.kb, n * 8);
+    if (e == hipSuccess) e = hipMemcpyAsync(b.ra, ids, n * 4, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(b.rows, ids, n * 4, hipMemcpyDeviceToDevice, s);
+    bool in_a = true;
+    if (e == hipSuccess) e = pqps_sort::sort_pairs<uint32_t, false>(b.w, b.ra, b.rows, b.rb, b.spare, n, 32, ctx->compute_units, s, &in_a);
+    if (!in_a) std::swap(b.rows, b.spare);
+    return e;
+}
+
+static hipError_t list_sort_by_key(pqps_ctx *ctx, ListSort &b, uint64_t n, uint32_t bits, hipStream_t s) {
+    hipError_t e = hipGetLastError();                            // the launch that wrote ka
+    bool in_a = true;
+    if (e == hipSuccess) e = pqps_sort::sort_pairs<uint64_t, false>(b.w, b.ka, b.rows, b.kb, b.spare, n, bits, ctx->compute_units, s, &in_a);
+    if (!in_a) { std::swap(b.rows, b.spare); std::swap(b.ka, b.kb); }
+    return e;
+}
+
+// Waits for the sort's work, frees its buffers; `e` is the sort's status so far.
+static int list_sort_close(ListSort &b, hipError_t e, hipStream_t s, const char *what) {
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(b.ra); (void)hipFree(b.rb); (void)hipFree(b.rows); (void)hipFree(b.spare); (void)hipFree(b.ka); (void)hipFree(b.kb);
+    pqps_sort::workspace_free(b.w);
+    if (e != hipSuccess) return fail(PQPS_EHIP, "%s: %s", what, hipGetErrorString(e));
+    return PQPS_OK;
+}
+
+// the sort image of key column `kcol` for every row of rows[0 .. n), into `keys`
+static void launch_sort_keys(pqps_ctx *ctx, hipStream_t s, bool wide, const uint32_t *rows, uint64_t n, const void *kcol, uint32_t wl,
+                             uint64_t kxor, uint32_t id_base, uint64_t *keys) {
+    const dim3 grid(list_grid(ctx, n, 8));
+    if (wide) hipLaunchKernelGGL(topk_sort_keys_kernel<true>, grid, dim3(kBlock), 0, s, rows, n, kcol, wl, kxor, id_base, keys);
+    else hipLaunchKernelGGL(topk_sort_keys_kernel<false>, grid, dim3(kBlock), 0, s, rows, n, kcol, wl, kxor, id_base, keys);
+}
+
 int pqps_sort_list(pqps_ctx *ctx, const pqps_column *key_col, int key_signed, int descending, const uint32_t *ids, uint64_t n,
                    uint32_t id_base, uint32_t *out_ids, uint64_t *out_keys, void *stream) {
     if (!ctx || !out_ids || (n && !ids)) return fail(PQPS_EINVAL, "NULL argument");
@@ -3456,40 +3506,208 @@ int pqps_sort_list(pqps_ctx *ctx, const pqps_column *key_col, int key_signed, in
     if (n == 0) return PQPS_OK;
     hipStream_t s = pick_stream(ctx, stream);
     // two stable passes, minor criterion first: the rows ascending, then the sort keys of the rows in that order
-    pqps_sort::Workspace w;
-    uint32_t *ra = nullptr, *rb = nullptr, *va = nullptr, *vb = nullptr;
-    uint64_t *ka = nullptr, *kb = nullptr;
-    hipError_t e = pqps_sort::workspace_alloc(w, n);
-    if (e == hipSuccess) e = hipMalloc((void **)&ra, n * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&rb, n * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&va, n * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&vb, n * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&ka, n * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&kb, n * 8);
-    if (e == hipSuccess) e = hipMemcpyAsync(ra, ids, n * 4, hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(va, ids, n * 4, hipMemcpyDeviceToDevice, s);
-    bool in_a = true;
-    if (e == hipSuccess) e = pqps_sort::sort_pairs<uint32_t, false>(w, ra, va, rb, vb, n, 32, ctx->compute_units, s, &in_a);
+    ListSort b;
+    hipError_t e = list_sort_open(ctx, b, ids, n, s);
     if (e == hipSuccess) {
-        const uint32_t *rows = in_a ? va : vb;
-        uint32_t *rows_b = in_a ? vb : va;
-        const dim3 grid(list_grid(ctx, n, 8));
-        const void *kcol = key_col ? key_col->data : nullptr;
-        const uint64_t kxor = topk_xor(wide, key_signed, descending);
-        if (wide) hipLaunchKernelGGL(topk_sort_keys_kernel<true>, grid, dim3(kBlock), 0, s, rows, n, kcol, wl, kxor, id_base, ka);
-        else hipLaunchKernelGGL(topk_sort_keys_kernel<false>, grid, dim3(kBlock), 0, s, rows, n, kcol, wl, kxor, id_base, ka);
-        e = hipGetLastError();
-        bool in_b = true;
-        if (e == hipSuccess) e = pqps_sort::sort_pairs<uint64_t, false>(w, ka, (uint32_t *)rows, kb, rows_b, n, wide ? 64 : 32,
-                                                                        ctx->compute_units, s, &in_b);
-        if (e == hipSuccess) e = hipMemcpyAsync(out_ids, in_b ? rows : rows_b, n * 4, hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess && out_keys) e = hipMemcpyAsync(out_keys, in_b ? ka : kb, n * 8, hipMemcpyDeviceToDevice, s);
+        launch_sort_keys(ctx, s, wide, b.rows, n, key_col ? key_col->data : nullptr, wl, topk_xor(wide, key_signed, descending), id_base, b.ka);
+        e = list_sort_by_key(ctx, b, n, wide ? 64 : 32, s);
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(ra); (void)hipFree(rb); (void)hipFree(va); (void)hipFree(vb); (void)hipFree(ka); (void)hipFree(kb);
-    pqps_sort::workspace_free(w);
-    if (e != hipSuccess) return fail(PQPS_EHIP, "ORDER BY sort: %s", hipGetErrorString(e));
+    if (e == hipSuccess) e = hipMemcpyAsync(out_ids, b.rows, n * 4, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess && out_keys) e = hipMemcpyAsync(out_keys, b.ka, n * 8, hipMemcpyDeviceToDevice, s);
+    return list_sort_close(b, e, s, "ORDER BY sort");
+}
+
+// ---- ORDER BY several columns: packed keys (order_multi_kernels.hpp) -----------------------------------------------------
+// The caller's fields, checked, as the kernels take them: f[0 .. *nf) (fields of 0 bits carry nothing and are left out; if
+// none is left, one field of mask 0 stands for "every key 0"), *wide = the packed word needs more than 32 bits.
+static int pack_fields(const pqps_order_field *fields, uint32_t n_fields, bool plane_ok, OrderField *f, uint32_t *nf, bool *wide) {
+    if (!fields) return fail(PQPS_EINVAL, "NULL argument");
+    if (n_fields < 1 || n_fields > PQPS_ORDER_MAX_FIELDS) return fail(PQPS_EINVAL, "%u order fields: 1 .. %u", n_fields, PQPS_ORDER_MAX_FIELDS);
+    uint64_t used = 0;
+    uint32_t top = 0;
+    *nf = 0;
+    for (uint32_t j = 0; j < n_fields; j++) {
+        const pqps_order_field &in = fields[j];
+        uint32_t wl;
+        const int rc = column_width_code("order field", &in.col, plane_ok, false, plane_ok, &wl);   // the lists gather by row: any alignment
+        if (rc) return rc;
+        if (in.bits > 32) return fail(PQPS_EINVAL, "order field %u: %u bits, more than 32", j, in.bits);
+        if (in.bits == 0) continue;
+        // (fields that do not overlap and end at or below bit 64 hold at most 64 bits between them)
+        if (in.shift > 64 || in.shift + in.bits > 64) return fail(PQPS_EINVAL, "order field %u: bits %u .. %u, past 64", j, in.shift, in.shift + in.bits);
+        const uint64_t m = ((1ull << in.bits) - 1) << in.shift;
+        if (used & m) return fail(PQPS_EINVAL, "order field %u overlaps another", j);
+        used |= m;
+        if (in.shift + in.bits > top) top = in.shift + in.bits;
+        OrderField &o = f[(*nf)++];
+        o.col = in.col.data;
+        o.wl = wl;
+        o.base = in.base;
+        o.mask = in.bits == 32 ? 0xFFFFFFFFu : (1u << in.bits) - 1u;
+        o.shift = in.shift;
+        o.flip = in.descending ? o.mask : 0u;
+    }
+    if (*nf == 0) {
+        uint32_t wl;
+        (void)column_width_code("order field", &fields[0].col, plane_ok, false, plane_ok, &wl);
+        f[0] = OrderField{fields[0].col.data, wl, 0u, 0u, 0u, 0u};
+        *nf = 1;
+    }
+    *wide = top > 32;
     return PQPS_OK;
+}
+
+static int check_pack_k(uint32_t k, bool wide) {
+    if (k == 0 || k > (wide ? kTopkMaxWide : kTopkMax)) return fail(PQPS_EINVAL, "K = %u: 1 .. %u", k, wide ? kTopkMaxWide : kTopkMax);
+    return PQPS_OK;
+}
+
+int pqps_filter_topk_multi(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                           const pqps_order_field *fields, uint32_t n_fields, uint32_t row_base, uint32_t k,
+                           void *scratch, uint64_t scratch_bytes, uint64_t *out, uint64_t *count, void *stream) {
+    if (!ctx || !out || !count || !scratch) return fail(PQPS_EINVAL, "NULL argument");
+    PackArgs g;
+    memset(&g, 0, sizeof g);
+    bool wide;
+    uint32_t nf;
+    int rc = pack_fields(fields, n_fields, true, g.f, &nf, &wide);
+    if (rc == PQPS_OK) rc = check_pack_k(k, wide);
+    if (rc) return rc;
+    if (scratch_bytes < pqps_topk_scratch_bytes(ctx, n_rows, k, wide, 1)) return fail(PQPS_EINVAL, "scratch too small");
+    if ((uint64_t)row_base + n_rows >= 0xFFFFFFFFull) return fail(PQPS_EINVAL, "row numbers must stay below 2^32 - 1");
+    rc = fused_args(g.e, cols, n_cols, n_rows, pred);
+    if (rc) return rc;
+    hipStream_t s = pick_stream(ctx, stream);
+    HIP_TRY(hipMemsetAsync(count, 0, sizeof(uint64_t), s));
+    if (n_rows == 0) {                                           // no candidate: every key of `out` reads all ones
+        HIP_TRY(hipMemsetAsync(out, 0xFF, (size_t)k * (wide ? 16 : 8), s));
+        return PQPS_OK;
+    }
+    const uint32_t cap = topk_cap(k);
+    const uint32_t key_bytes = wide ? 16u : 8u;
+    const uint32_t lds = kWaves * cap * key_bytes;
+    const uint32_t grid = fused_grid(ctx, n_rows, lds);
+    const uint64_t parts = (uint64_t)grid * kWaves * k;
+    const uint64_t round = topk_round_keys(parts, k);
+    char *base = (char *)scratch;
+    g.parts = base;
+    g.count = (unsigned long long *)count;
+    g.row_base = row_base;
+    g.k = k;
+    g.cap = cap;
+    // the instance and its name side by side: pqps_last_kernel() reports the entry that is launched
+    static const struct { void (*fn)(const PackArgs); const char *name; } fns[2][kOrderMaxFields][2] = {
+#define PQPS_PACK_SCAN(WIDE, W, NF, NT) {topk_pack_scan_kernel<WIDE, NF, NT>, "topk_pack_scan_kernel<" W ", NF=" #NF ", NT=" #NT ">"}
+#define PQPS_PACK_SCAN_NF(WIDE, W, NF) {PQPS_PACK_SCAN(WIDE, W, NF, false), PQPS_PACK_SCAN(WIDE, W, NF, true)}
+        {PQPS_PACK_SCAN_NF(false, "pack32", 1), PQPS_PACK_SCAN_NF(false, "pack32", 2), PQPS_PACK_SCAN_NF(false, "pack32", 3), PQPS_PACK_SCAN_NF(false, "pack32", 4)},
+        {PQPS_PACK_SCAN_NF(true, "pack64", 1), PQPS_PACK_SCAN_NF(true, "pack64", 2), PQPS_PACK_SCAN_NF(true, "pack64", 3), PQPS_PACK_SCAN_NF(true, "pack64", 4)},
+#undef PQPS_PACK_SCAN_NF
+#undef PQPS_PACK_SCAN
+    };
+    const auto &scan = fns[wide ? 1 : 0][nf - 1][g.e.streaming ? 1 : 0];
+    snprintf(g_kernel, sizeof g_kernel, "%s", scan.name);
+    hipEvent_t stop;
+    rc = fused_launch(ctx, scan.fn, grid, lds, s, g, &stop);
+    if (rc) return rc;
+    char *xa = base + parts * key_bytes, *ya = xa + round * key_bytes;
+    if (wide) rc = topk_rounds<true>(ctx, s, (const TKey<true> *)base, nullptr, nullptr, 0, 0, 0, parts, k, (TKey<true> *)xa,
+                                     (TKey<true> *)ya, (TKey<true> *)out, stop);
+    else rc = topk_rounds<false>(ctx, s, (const TKey<false> *)base, nullptr, nullptr, 0, 0, 0, parts, k, (TKey<false> *)xa,
+                                 (TKey<false> *)ya, (TKey<false> *)out, stop);
+    fused_close(ctx, stop, false);
+    return rc;
+}
+
+int pqps_topk_list_multi(pqps_ctx *ctx, const pqps_order_field *fields, uint32_t n_fields, const uint32_t *ids, uint64_t n,
+                         uint32_t id_base, uint32_t k, void *scratch, uint64_t scratch_bytes, uint64_t *out, void *stream) {
+    if (!ctx || !out || !scratch || (n && !ids)) return fail(PQPS_EINVAL, "NULL argument");
+    PackListArgs g;
+    memset(&g, 0, sizeof g);
+    bool wide;
+    int rc = pack_fields(fields, n_fields, false, g.f, &g.n_fields, &wide);
+    if (rc == PQPS_OK) rc = check_pack_k(k, wide);
+    if (rc) return rc;
+    if (scratch_bytes < pqps_topk_scratch_bytes(ctx, n, k, wide, 0)) return fail(PQPS_EINVAL, "scratch too small");
+    g.id_base = id_base;
+    hipStream_t s = pick_stream(ctx, stream);
+    const uint64_t key_bytes = wide ? 16 : 8;
+    if (n == 0) {                                                // no candidate: every key of `out` reads all ones
+        HIP_TRY(hipMemsetAsync(out, 0xFF, (size_t)k * key_bytes, s));
+        return PQPS_OK;
+    }
+    void *keys = nullptr;                                        // the list's n keys: the rounds read keys, not columns
+    HIP_TRY(hipMalloc(&keys, n * key_bytes));
+    char *xa = (char *)scratch, *ya = xa + topk_round_keys(n, k) * key_bytes;
+    const dim3 grid(list_grid(ctx, n, 8));
+    hipError_t launched = hipSuccess;
+    if (wide) {
+        hipLaunchKernelGGL(order_pack_keys_kernel<true>, grid, dim3(kBlock), 0, s, ids, n, g, (TKey<true> *)keys, (uint64_t *)nullptr);
+        launched = hipGetLastError();
+        if (launched == hipSuccess) rc = topk_rounds<true>(ctx, s, (const TKey<true> *)keys, nullptr, nullptr, 0, 0, 0, n, k, (TKey<true> *)xa, (TKey<true> *)ya,
+                               (TKey<true> *)out, nullptr);
+    } else {
+        hipLaunchKernelGGL(order_pack_keys_kernel<false>, grid, dim3(kBlock), 0, s, ids, n, g, (TKey<false> *)keys, (uint64_t *)nullptr);
+        launched = hipGetLastError();
+        if (launched == hipSuccess) rc = topk_rounds<false>(ctx, s, (const TKey<false> *)keys, nullptr, nullptr, 0, 0, 0, n, k, (TKey<false> *)xa, (TKey<false> *)ya,
+                                (TKey<false> *)out, nullptr);
+    }
+    hipError_t e = hipStreamSynchronize(s);                      // the temporary is read until the first round is done
+    (void)hipFree(keys);
+    if (launched != hipSuccess) e = launched;
+    if (rc == PQPS_OK && e != hipSuccess) return fail(PQPS_EHIP, "ORDER BY list: %s", hipGetErrorString(e));
+    return rc;
+}
+
+int pqps_sort_list_multi(pqps_ctx *ctx, const pqps_order_field *fields, uint32_t n_fields, const uint32_t *ids, uint64_t n,
+                         uint32_t id_base, uint32_t *out_ids, uint64_t *out_keys, void *stream) {
+    if (!ctx || !out_ids || (n && !ids)) return fail(PQPS_EINVAL, "NULL argument");
+    PackListArgs g;
+    memset(&g, 0, sizeof g);
+    bool wide;
+    int rc = pack_fields(fields, n_fields, false, g.f, &g.n_fields, &wide);
+    if (rc) return rc;
+    if (n == 0) return PQPS_OK;
+    g.id_base = id_base;
+    hipStream_t s = pick_stream(ctx, stream);
+    ListSort b;
+    hipError_t e = list_sort_open(ctx, b, ids, n, s);
+    if (e == hipSuccess) {
+        const dim3 grid(list_grid(ctx, n, 8));
+        if (wide) hipLaunchKernelGGL(order_pack_keys_kernel<true>, grid, dim3(kBlock), 0, s, b.rows, n, g, (TKey<true> *)nullptr, b.ka);
+        else hipLaunchKernelGGL(order_pack_keys_kernel<false>, grid, dim3(kBlock), 0, s, b.rows, n, g, (TKey<false> *)nullptr, b.ka);
+        e = list_sort_by_key(ctx, b, n, wide ? 64 : 32, s);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out_ids, b.rows, n * 4, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess && out_keys) e = hipMemcpyAsync(out_keys, b.ka, n * 8, hipMemcpyDeviceToDevice, s);
+    return list_sort_close(b, e, s, "ORDER BY sort");
+}
+
+int pqps_sort_list_chain(pqps_ctx *ctx, const pqps_column *key_cols, const int *key_signed, const int *descending, uint32_t n_keys,
+                         const uint32_t *ids, uint64_t n, uint32_t id_base, uint32_t *out_ids, uint64_t *out_keys, void *stream) {
+    if (!ctx || !out_ids || !key_cols || !key_signed || !descending || (n && !ids)) return fail(PQPS_EINVAL, "NULL argument");
+    if (n_keys < 1 || n_keys > PQPS_ORDER_MAX_FIELDS) return fail(PQPS_EINVAL, "%u order keys: 1 .. %u", n_keys, PQPS_ORDER_MAX_FIELDS);
+    bool wide[PQPS_ORDER_MAX_FIELDS];
+    uint32_t wl[PQPS_ORDER_MAX_FIELDS];
+    for (uint32_t j = 0; j < n_keys; j++) {
+        const int rc = check_topk_key(&key_cols[j], false, &wide[j], &wl[j]);
+        if (rc) return rc;
+    }
+    if (n == 0) return PQPS_OK;
+    hipStream_t s = pick_stream(ctx, stream);
+    ListSort b;
+    hipError_t e = list_sort_open(ctx, b, ids, n, s);
+    // stable passes, minor criterion first: the last key, ..., the first key, each over the rows in the order so far
+    for (uint32_t j = n_keys; j-- > 0 && e == hipSuccess;) {
+        launch_sort_keys(ctx, s, wide[j], b.rows, n, key_cols[j].data, wl[j], topk_xor(wide[j], key_signed[j], descending[j]), id_base, b.ka);
+        e = list_sort_by_key(ctx, b, n, wide[j] ? 64 : 32, s);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out_ids, b.rows, n * 4, hipMemcpyDeviceToDevice, s);
+    for (uint32_t j = 0; j < n_keys && out_keys && e == hipSuccess; j++) {          // the images of the rows in their final order
+        launch_sort_keys(ctx, s, wide[j], b.rows, n, key_cols[j].data, wl[j], topk_xor(wide[j], key_signed[j], descending[j]), id_base,
+                         out_keys + (uint64_t)j * n);
+        e = hipGetLastError();
+    }
+    return list_sort_close(b, e, s, "ORDER BY chain sort");
 }
 
 // ---- the first row of every group (first_kernels.hpp) ----------------------------------------------------------------

@@ -2197,7 +2197,17 @@ struct order_plan {
     bool fused;                          /* single-pass scan-mode WHERE and K > 0: one fused launch per shard       */
     pqps_column kcol[HIP_MAX_SHARDS];    /* shard s's key column (sudo_used on the fused path: its bit plane)       */
     bool no_key;                         /* a single-valued string column: every key 0                             */
+    /* ORDER BY several columns (order_plan_keys): the one-column fields above describe field[0] where one key remains */
+    bool rows_only;                      /* no key remains: every key 0, the answer is the row order               */
+    bool multi;                          /* kp.form is PACK32, PACK64 or CHAIN                                      */
+    struct hipOrderKeyPlan kp;           /* one plan for all shards: bounds and dictionaries are table-wide          */
+    pqps_order_field fld[HIP_MAX_SHARDS][HIP_ORDER_MAX_KEYS];   /* PACK32 / PACK64: shard s's fields                */
+    pqps_column ccol[HIP_MAX_SHARDS][HIP_ORDER_MAX_KEYS];       /* CHAIN: shard s's key columns ...                 */
+    int csigned[HIP_ORDER_MAX_KEYS], cdesc[HIP_ORDER_MAX_KEYS]; /* ... and their images' rules                      */
 };
+
+static bool order_is_chain(const struct order_plan *op) { return op->multi && op->kp.form == HIPORDER_CHAIN; }
+static bool order_is_packed(const struct order_plan *op) { return op->multi && op->kp.form != HIPORDER_CHAIN; }
 
 /* Shard s's keys of the top-K paths (n of them, K words each, downloaded from `out` on `cs`) appended to keys[*n_keys]. */
 static int order_collect(pqps_ctx *cs, const uint64_t *out_dev, uint64_t n, bool wide, struct order_key *keys, uint64_t *n_keys) {
@@ -2219,9 +2229,12 @@ static int topk_fused_call(struct query *q, int s, pqps_ctx *ctx, void *stream, 
     const struct hipTable *sh = hipTableShard(q->t, s);
     const struct shard_pred *sp = &q->sp[s];
     char *b = a->buf[s];
-    if (pqps_filter_topk(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, op->no_key ? NULL : &op->kcol[s], op->key_signed, op->desc,
-                         (uint32_t)sh->row0, op->k, b + 16 + a->out_bytes, a->scratch_bytes[s], (uint64_t *)(b + 16), (uint64_t *)b, stream) != PQPS_OK)
-        return engine_error("ORDER BY filter");
+    const int rc = order_is_packed(op)
+        ? pqps_filter_topk_multi(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, op->fld[s], (uint32_t)op->kp.n_fields, (uint32_t)sh->row0,
+                                 op->k, b + 16 + a->out_bytes, a->scratch_bytes[s], (uint64_t *)(b + 16), (uint64_t *)b, stream)
+        : pqps_filter_topk(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, op->no_key ? NULL : &op->kcol[s], op->key_signed, op->desc,
+                           (uint32_t)sh->row0, op->k, b + 16 + a->out_bytes, a->scratch_bytes[s], (uint64_t *)(b + 16), (uint64_t *)b, stream);
+    if (rc != PQPS_OK) return engine_error("ORDER BY filter");
     return 0;
 }
 
@@ -2261,9 +2274,12 @@ static int order_topk(struct query *q, const struct order_plan *op, struct order
             if (!buf[s]) continue;
             char *b = buf[s];
             got[s] = q->count[s];
-            if (pqps_topk_list(lane_copy_ctx(q, s), op->no_key ? NULL : &op->kcol[s], op->key_signed, op->desc, query_lane(q, s)->ids_dev, q->count[s],
-                               (uint32_t)sh->row0, k, b + 16 + out_bytes, scratch_bytes[s], (uint64_t *)(b + 16), NULL) != PQPS_OK)
-                rc = engine_error("ORDER BY list");
+            const int lrc = order_is_packed(op)
+                ? pqps_topk_list_multi(lane_copy_ctx(q, s), op->fld[s], (uint32_t)op->kp.n_fields, query_lane(q, s)->ids_dev, q->count[s],
+                                       (uint32_t)sh->row0, k, b + 16 + out_bytes, scratch_bytes[s], (uint64_t *)(b + 16), NULL)
+                : pqps_topk_list(lane_copy_ctx(q, s), op->no_key ? NULL : &op->kcol[s], op->key_signed, op->desc, query_lane(q, s)->ids_dev, q->count[s],
+                                 (uint32_t)sh->row0, k, b + 16 + out_bytes, scratch_bytes[s], (uint64_t *)(b + 16), NULL);
+            if (lrc != PQPS_OK) rc = engine_error("ORDER BY list");
         }
     }
     for (int s = 0; s < q->n_shards && rc == 0; s++)
@@ -2272,14 +2288,26 @@ static int order_topk(struct query *q, const struct order_plan *op, struct order
     return rc;
 }
 
-/* The full sort: the selection, every shard's list sorted on its device (pqps_sort_list), the first `want` rows of each
- * downloaded and the shards merged on the host by (key, row) -- one shard needs no keys. */
+/* Row i of shard x against row j of shard y in the CHAIN form: the per-key images (nk arrays of take rows each), then the row. */
+static int order_chain_cmp(const uint64_t *kx, uint64_t tx, uint64_t i, uint32_t rx, const uint64_t *ky, uint64_t ty, uint64_t j, uint32_t ry, int nk) {
+    for (int f = 0; f < nk; f++) {
+        const uint64_t a = kx[(uint64_t)f * tx + i], b = ky[(uint64_t)f * ty + j];
+        if (a != b) return a < b ? -1 : 1;
+    }
+    return rx < ry ? -1 : rx > ry;
+}
+
+/* The full sort: the selection, every shard's list sorted on its device (pqps_sort_list; several keys: pqps_sort_list_multi
+ * by the packed key, or pqps_sort_list_chain key by key), the first `want` rows of each downloaded and the shards merged on
+ * the host by (key, row), the CHAIN form by (key 0, ..., key N-1, row) -- one shard needs no keys. */
 static int order_sort(struct query *q, const struct order_plan *op, uint64_t want, uint32_t **rows, uint64_t *n_rows, uint64_t *matches) {
     int rc = query_lists(q);
     if (rc != 0) return rc;
     *matches = q->total;
     const int n_shards = q->n_shards;
     const bool merge = n_shards > 1;
+    const bool chain = order_is_chain(op);
+    const int nk = chain ? op->kp.n_fields : 1;                          /* key arrays per shard */
     uint32_t *ids[HIP_MAX_SHARDS] = { NULL };
     uint64_t *keys[HIP_MAX_SHARDS] = { NULL }, take[HIP_MAX_SHARDS] = { 0 }, total = 0;
     for (int s = 0; s < n_shards && rc == 0; s++) {
@@ -2291,14 +2319,20 @@ static int order_sort(struct query *q, const struct order_plan *op, uint64_t wan
         uint32_t *ids_dev = NULL;
         uint64_t *keys_dev = NULL;
         ids[s] = malloc((size_t)take[s] * sizeof **ids);
-        if (merge) keys[s] = malloc((size_t)take[s] * sizeof **keys);
+        if (merge) keys[s] = malloc((size_t)take[s] * (size_t)nk * sizeof **keys);
         if (!ids[s] || (merge && !keys[s])) { fprintf(stderr, "HIP engine: out of memory\n"); rc = -1; break; }
         if (pqps_malloc(sh->ctx, n * sizeof(uint32_t), (void **)&ids_dev) != PQPS_OK ||
-            (merge && pqps_malloc(sh->ctx, n * sizeof(uint64_t), (void **)&keys_dev) != PQPS_OK)) rc = engine_error("ORDER BY buffers");
-        else if (pqps_sort_list(cs, op->no_key ? NULL : &op->kcol[s], op->key_signed, op->desc, query_lane(q, s)->ids_dev, n, (uint32_t)sh->row0,
-                                ids_dev, keys_dev, NULL) != PQPS_OK) rc = engine_error("ORDER BY sort");
-        else if (pqps_download(cs, ids[s], ids_dev, (size_t)take[s] * sizeof **ids, NULL) != PQPS_OK ||
-                 (merge && pqps_download(cs, keys[s], keys_dev, (size_t)take[s] * sizeof **keys, NULL) != PQPS_OK)) rc = engine_error("ORDER BY download");
+            (merge && pqps_malloc(sh->ctx, n * (size_t)nk * sizeof(uint64_t), (void **)&keys_dev) != PQPS_OK)) rc = engine_error("ORDER BY buffers");
+        else if ((chain ? pqps_sort_list_chain(cs, op->ccol[s], op->csigned, op->cdesc, (uint32_t)nk, query_lane(q, s)->ids_dev, n, (uint32_t)sh->row0,
+                                               ids_dev, keys_dev, NULL)
+                  : op->multi ? pqps_sort_list_multi(cs, op->fld[s], (uint32_t)op->kp.n_fields, query_lane(q, s)->ids_dev, n, (uint32_t)sh->row0,
+                                                     ids_dev, keys_dev, NULL)
+                  : pqps_sort_list(cs, op->no_key ? NULL : &op->kcol[s], op->key_signed, op->desc, query_lane(q, s)->ids_dev, n, (uint32_t)sh->row0,
+                                   ids_dev, keys_dev, NULL)) != PQPS_OK) rc = engine_error("ORDER BY sort");
+        else if (pqps_download(cs, ids[s], ids_dev, (size_t)take[s] * sizeof **ids, NULL) != PQPS_OK) rc = engine_error("ORDER BY download");
+        for (int f = 0; f < nk && merge && rc == 0; f++)                 /* the first take[s] of every key array of n */
+            if (pqps_download(cs, keys[s] + (size_t)f * take[s], keys_dev + (size_t)f * n, (size_t)take[s] * sizeof **keys, NULL) != PQPS_OK)
+                rc = engine_error("ORDER BY download");
         if (ids_dev) pqps_free(sh->ctx, ids_dev);
         if (keys_dev) pqps_free(sh->ctx, keys_dev);
         total += take[s];
@@ -2315,6 +2349,10 @@ static int order_sort(struct query *q, const struct order_plan *op, uint64_t wan
             struct order_key bk = { 0, 0 };
             for (int s = 0; s < n_shards; s++) {
                 if (at[s] >= take[s]) continue;
+                if (chain) {
+                    if (best < 0 || order_chain_cmp(keys[s], take[s], at[s], ids[s][at[s]], keys[best], take[best], at[best], ids[best][at[best]], nk) < 0) best = s;
+                    continue;
+                }
                 const struct order_key ks = { keys[s][at[s]], ids[s][at[s]] };
                 if (best < 0 || order_key_cmp(&ks, &bk) < 0) { best = s; bk = ks; }
             }
@@ -2345,13 +2383,19 @@ static int order_rows(struct engineS *engine, struct whereClauseS *whereClause, 
     uint64_t all = 0;
     for (int s = 0; s < q->n_shards; s++) all += hipTableShard(t, s)->n_rows;
     if (all == 0) { *rows = malloc(sizeof **rows); return *rows ? 0 : -1; }      /* an empty table: no rows */
-    const uint32_t kmax = op->wide ? PQPS_TOPK_MAX_WIDE : PQPS_TOPK_MAX;
+    const uint32_t kmax = order_is_chain(op) ? 0 : op->wide ? PQPS_TOPK_MAX_WIDE : PQPS_TOPK_MAX;   /* CHAIN: the sort only */
     op->k = limit > 0 && limit <= (long long)kmax ? (uint32_t)limit : 0;
     op->fused = op->k > 0 && q->plan.n_passes == 1 && q->n_probes == 0;
-    op->no_key = t->col[op->c].width == 0;
+    op->no_key = op->rows_only || t->col[op->c].width == 0;
     for (int s = 0; s < q->n_shards; s++) {
         const struct hipTable *sh = hipTableShard(t, s);
         op->kcol[s] = op->fused && op->c == HIPCOL_SUDO_USED && sh->sudo_bits.data ? sh->sudo_bits : sh->col[op->c];
+        for (int j = 0; j < op->kp.n_fields && op->multi; j++) {
+            const struct hipOrderField *f = &op->kp.field[j];
+            op->ccol[s][j] = sh->col[f->column];
+            op->fld[s][j] = (pqps_order_field){ op->fused && f->column == HIPCOL_SUDO_USED && sh->sudo_bits.data ? sh->sudo_bits : sh->col[f->column],
+                                                f->base, f->bits, f->shift, f->descending };
+        }
     }
     if (op->k == 0) return order_sort(q, op, limit > 0 ? (uint64_t)limit : UINT64_MAX, rows, n_rows, matches);
     struct order_key *keys = malloc((size_t)q->n_shards * op->k * sizeof *keys);
@@ -2385,26 +2429,91 @@ static int order_plan_init(struct hipTable *t, const char *orderColumn, bool des
     return 0;
 }
 
-long long executeQueryOrderIdsHIP(struct engineS *engine, struct whereClauseS *whereClause, const char *orderColumn,
-                                  bool descending, long long limit, unsigned int **ids, long long *matches, double *queryTime) {
+/* The plan of a key list (the query is open: the i32 bounds are the table's cached ones), or -1 with the reason on stderr.
+ * One remaining key is the one-column plan; none is the row order. */
+static int order_plan_keys(struct query *q, const struct hipOrderKey *keys, int numKeys, struct order_plan *op) {
+    struct hipTable *t = q->t;
+    memset(op, 0, sizeof *op);
+    if (!keys) { fprintf(stderr, "HIP engine: ORDER BY without keys\n"); return -1; }
+    if (numKeys < 1 || numKeys > HIP_ORDER_MAX_KEYS) { fprintf(stderr, "HIP engine: ORDER BY: %d keys, not 1 .. %d\n", numKeys, HIP_ORDER_MAX_KEYS); return -1; }
+    if (t->xch) { fprintf(stderr, "HIP engine: ORDER BY is not exchanged across ranks\n"); return -1; }
+    const char *names[HIP_ORDER_MAX_KEYS];
+    int desc[HIP_ORDER_MAX_KEYS], counts[HIPCOL_COUNT] = { 0 }, lo[HIPCOL_COUNT] = { 0 }, hi[HIPCOL_COUNT] = { 0 };
+    for (int i = 0; i < numKeys; i++) {
+        names[i] = keys[i].column;
+        desc[i] = keys[i].descending;
+        const int c = names[i] ? hipColumnId(names[i]) : -1;
+        if (c < 0) continue;                                             /* hipOrderKeyPlan refuses it */
+        if (k_group_kind[c] == HIPKIND_DICT) counts[c] = t->col[c].width == 0 ? (t->dict[c].count > 0) : (int)t->dict[c].count;
+    }
+    /* which keys remain does not depend on the i32 bounds: they are asked for (a min / max pass on first use) only where
+     * several keys remain, so a key list that comes down to one column costs what the one-column query costs */
+    if (hipOrderKeyPlan(names, desc, numKeys, counts, lo, hi, &op->kp) != 0) return -1;
+    if (op->kp.form >= HIPORDER_PACK32) {
+        for (int j = 0; j < op->kp.n_fields; j++) {
+            const int c = op->kp.field[j].column;
+            int32_t l, h;
+            if (k_group_kind[c] != HIPKIND_I32) continue;
+            if (column_bounds(q, c, &l, &h) != 0) return -1;
+            lo[c] = l;
+            hi[c] = h;
+        }
+        if (hipOrderKeyPlan(names, desc, numKeys, counts, lo, hi, &op->kp) != 0) return -1;
+    }
+    op->rows_only = op->kp.form == HIPORDER_ROWS;
+    op->multi = op->kp.form >= HIPORDER_PACK32;
+    if (op->multi) {
+        op->wide = op->kp.form == HIPORDER_PACK64;
+        for (int j = 0; j < op->kp.n_fields; j++) {
+            op->csigned[j] = op->kp.field[j].kind == HIPKIND_I32;
+            op->cdesc[j] = op->kp.field[j].descending;
+        }
+    } else {
+        op->c = op->rows_only ? HIPCOL_COMMAND_ID : op->kp.field[0].column;  /* (no key: the column is not read) */
+        op->desc = !op->rows_only && op->kp.field[0].descending;
+        op->wide = !op->rows_only && op->c == HIPCOL_COMMAND_ID;
+        op->key_signed = k_group_kind[op->c] == HIPKIND_I32;
+    }
+    return 0;
+}
+
+/* What an ORDER BY entry point orders by: a key list, or (keys == NULL) one column. */
+struct order_request { const struct hipOrderKey *keys; int numKeys; const char *column; bool descending; };
+
+static int order_request_plan(struct query *q, const struct order_request *r, struct order_plan *op) {
+    return r->keys || r->numKeys ? order_plan_keys(q, r->keys, r->numKeys, op) : order_plan_init(q->t, r->column, r->descending, op);
+}
+
+static long long order_ids_run(struct engineS *engine, struct whereClauseS *whereClause, const struct order_request *r, long long limit,
+                               unsigned int **ids, long long *matches, double *queryTime) {
     const double t0 = now_seconds();
     if (matches) *matches = 0;
     if (!engine || !engine->record_block || !ids) { fprintf(stderr, "HIP engine: ORDER BY without an engine or a result\n"); return -1; }
     *ids = NULL;
-    struct hipTable *t = engine->record_block;
-    struct order_plan op;
-    if (order_plan_init(t, orderColumn, descending, &op) != 0) return -1;
     struct query q;
     if (!query_open(engine, &q)) return -1;                              /* reason on stderr */
+    struct order_plan op;
     uint32_t *rows = NULL;
     uint64_t n = 0, m = 0;
-    const int rc = order_rows(engine, whereClause, &q, &op, limit, &rows, &n, &m);
+    int rc = order_request_plan(&q, r, &op);
+    if (rc == 0) rc = order_rows(engine, whereClause, &q, &op, limit, &rows, &n, &m);
     query_close(&q);
     if (queryTime) *queryTime = now_seconds() - t0;
     if (rc != 0) { free(rows); return -1; }
     *ids = rows;
     if (matches) *matches = (long long)m;
     return (long long)n;
+}
+
+long long executeQueryOrderIdsByHIP(struct engineS *engine, struct whereClauseS *whereClause, const struct hipOrderKey *keys,
+                                    int numKeys, long long limit, unsigned int **ids, long long *matches, double *queryTime) {
+    if (!keys && numKeys == 0) numKeys = -1;                             /* (a key list, though an empty one: refused) */
+    return order_ids_run(engine, whereClause, &(struct order_request){ keys, numKeys, NULL, false }, limit, ids, matches, queryTime);
+}
+
+long long executeQueryOrderIdsHIP(struct engineS *engine, struct whereClauseS *whereClause, const char *orderColumn,
+                                  bool descending, long long limit, unsigned int **ids, long long *matches, double *queryTime) {
+    return order_ids_run(engine, whereClause, &(struct order_request){ NULL, 0, orderColumn, descending }, limit, ids, matches, queryTime);
 }
 
 /* rows[0 .. n) (table-wide, in the result's order) projected into res (caller holds the table shared and the query's lane):
@@ -2447,14 +2556,13 @@ static int project_listed_rows(struct query *q, const uint32_t *rows, uint64_t n
     return rc;
 }
 
-struct hipColumnarResult *executeQuerySelectOrderedHIP(struct engineS *engine, const char **selectItems, int numSelectItems,
-                                                       struct whereClauseS *whereClause, const char *orderColumn,
-                                                       bool descending, long long limit, long long *matches) {
+static struct hipColumnarResult *order_select_run(struct engineS *engine, const char **selectItems, int numSelectItems,
+                                                  struct whereClauseS *whereClause, const struct order_request *r, long long limit,
+                                                  long long *matches) {
     if (matches) *matches = 0;
     struct hipColumnarResult *res = calloc(1, sizeof *res);
     if (!res) { perror("Failed to allocate memory for result set"); exit(EXIT_FAILURE); }
     if (!engine || !engine->record_block) return res;
-    struct hipTable *t = engine->record_block;
     if (selectItems == NULL || numSelectItems == 0) { selectItems = (const char **)k_all_columns; numSelectItems = 12; }
     res->numColumns = numSelectItems;
     res->columnNames = calloc((size_t)numSelectItems, sizeof(char *));
@@ -2464,13 +2572,13 @@ struct hipColumnarResult *executeQuerySelectOrderedHIP(struct engineS *engine, c
     res->dictionarySizes = calloc((size_t)numSelectItems, sizeof(int));
     if (!res->columnNames || !res->columnKinds || !res->values || !res->dictionaries || !res->dictionarySizes) { perror("Failed to allocate memory for result set"); exit(EXIT_FAILURE); }
     const double t0 = now_seconds();
-    struct order_plan op;
-    if (order_plan_init(t, orderColumn, descending, &op) != 0) return res;
     struct query q;
     if (!query_open(engine, &q)) return res;                             /* reason on stderr */
+    struct order_plan op;
     uint32_t *rows = NULL;
     uint64_t n = 0, m = 0;
-    int rc = order_rows(engine, whereClause, &q, &op, limit, &rows, &n, &m);
+    int rc = order_request_plan(&q, r, &op);
+    if (rc == 0) rc = order_rows(engine, whereClause, &q, &op, limit, &rows, &n, &m);
     if (rc == 0) rc = project_listed_rows(&q, rows, n, selectItems, numSelectItems, res);
     free(rows);
     query_close(&q);
@@ -2479,6 +2587,21 @@ struct hipColumnarResult *executeQuerySelectOrderedHIP(struct engineS *engine, c
     res->success = rc == 0;
     if (rc == 0 && matches) *matches = (long long)m;
     return res;
+}
+
+struct hipColumnarResult *executeQuerySelectOrderedHIP(struct engineS *engine, const char **selectItems, int numSelectItems,
+                                                       struct whereClauseS *whereClause, const char *orderColumn,
+                                                       bool descending, long long limit, long long *matches) {
+    return order_select_run(engine, selectItems, numSelectItems, whereClause, &(struct order_request){ NULL, 0, orderColumn, descending },
+                            limit, matches);
+}
+
+struct hipColumnarResult *executeQuerySelectOrderedByHIP(struct engineS *engine, const char **selectItems, int numSelectItems,
+                                                         struct whereClauseS *whereClause, const struct hipOrderKey *keys, int numKeys,
+                                                         long long limit, long long *matches) {
+    if (!keys && numKeys == 0) numKeys = -1;                             /* (a key list, though an empty one: refused) */
+    return order_select_run(engine, selectItems, numSelectItems, whereClause, &(struct order_request){ keys, numKeys, NULL, false },
+                            limit, matches);
 }
 
 /* ---- the first row of every group (include/executeEngine-hip.h) ---------------------------------------------------- */

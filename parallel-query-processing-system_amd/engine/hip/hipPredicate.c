@@ -1108,3 +1108,56 @@ int hipFirstKeyDecode(int kind, int descending, unsigned long long word, long lo
     if (row) *row = (unsigned int)(word & 0xFFFFFFFFull);
     return 1;
 }
+
+/* ---- the packed key of ORDER BY several columns ---------------------------------------------------------------------- */
+
+/* ceil(log2 d): the bits that hold 0 .. d - 1 */
+static uint32_t domain_bits(uint64_t d) {
+    uint32_t b = 0;
+    while (b < 64 && (1ull << b) < d) b++;
+    return b;
+}
+
+int hipOrderKeyPlan(const char *const *columns, const int *descending, int n_keys, const int *dict_counts,
+                    const int *lo, const int *hi, struct hipOrderKeyPlan *plan) {
+    if (!columns || !descending || !dict_counts || !lo || !hi || !plan) { fprintf(stderr, "HIP engine: ORDER BY: NULL argument\n"); return -1; }
+    if (n_keys < 1 || n_keys > HIP_ORDER_MAX_KEYS) {
+        fprintf(stderr, "HIP engine: ORDER BY: %d keys, not 1 .. %d\n", n_keys, HIP_ORDER_MAX_KEYS);
+        return -1;
+    }
+    struct hipOrderKeyPlan p;
+    memset(&p, 0, sizeof p);
+    int seen[PQPS_MAX_COLUMNS] = { 0 };
+    int has_u64 = 0;
+    for (int i = 0; i < n_keys; i++) {
+        if (!columns[i]) { fprintf(stderr, "HIP engine: ORDER BY: key %d without a column\n", i); return -1; }
+        const int c = hipColumnId(columns[i]);
+        if (c < 0) { fprintf(stderr, "HIP engine: ORDER BY: unknown column '%s'\n", columns[i]); return -1; }
+        if (seen[c]) continue;                                           /* named before: no information */
+        seen[c] = 1;
+        const int kind = k_bucket_kind[c];
+        if (kind == HIPKIND_DICT && dict_counts[c] <= 1) continue;       /* single-valued: no information */
+        struct hipOrderField *f = &p.field[p.n_fields++];
+        f->column = c;
+        f->kind = kind;
+        f->descending = descending[i] != 0;
+        if (kind == HIPKIND_U64) { f->bits = 64; has_u64 = 1; }
+        else if (kind == HIPKIND_DICT) f->bits = domain_bits((uint64_t)dict_counts[c]);
+        else if (kind == HIPKIND_BOOL) f->bits = 1;
+        else {
+            f->base = (uint32_t)lo[c];
+            f->bits = lo[c] > hi[c] ? 0 : domain_bits((uint64_t)((long long)hi[c] - (long long)lo[c]) + 1u);
+        }
+        p.total_bits += f->bits;
+    }
+    if (p.n_fields == 0) p.form = HIPORDER_ROWS;
+    else if (p.n_fields == 1) p.form = HIPORDER_ONE;
+    else if (has_u64 || p.total_bits > 64) p.form = HIPORDER_CHAIN;
+    else p.form = p.total_bits <= 32 ? HIPORDER_PACK32 : HIPORDER_PACK64;
+    if (p.form == HIPORDER_PACK32 || p.form == HIPORDER_PACK64) {
+        uint32_t shift = 0;
+        for (int j = p.n_fields - 1; j >= 0; j--) { p.field[j].shift = shift; shift += p.field[j].bits; }
+    }
+    *plan = p;
+    return 0;
+}
