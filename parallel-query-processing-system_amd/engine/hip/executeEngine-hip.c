@@ -44,6 +44,11 @@ static int engine_error(const char *what) {
     return -1;
 }
 
+static int oom(void) {
+    fprintf(stderr, "HIP engine: out of memory\n");
+    return -1;
+}
+
 #define TRY(call, what) do { if ((call) != PQPS_OK) return engine_error(what); } while (0)
 
 /* ---- predicate binding --------------------------------------------------------- */
@@ -139,8 +144,7 @@ static int head_passes(const struct hipPlan *plan, struct hipTable *sh, struct s
     if (!sp->flags || !sp->member || !sp->plane) {
         free(sp->flags); free(sp->member); free(sp->plane);
         sp->flags = NULL; sp->member = NULL; sp->plane = NULL;
-        fprintf(stderr, "HIP engine: out of memory\n");
-        return -1;
+        return oom();
     }
     sp->n_flags = (int)n;
     for (int k = 0; k < sp->n_flags; k++) {
@@ -572,7 +576,7 @@ static struct hipQueryTicket *ticket_begin(struct engineS *engine, struct whereC
     if (!engine || !engine->record_block) return NULL;
     struct hipTable *t = engine->record_block;
     struct hipQueryTicket *tk = calloc(1, sizeof *tk);
-    if (!tk) { fprintf(stderr, "HIP engine: out of memory\n"); return NULL; }
+    if (!tk) { oom(); return NULL; }
     tk->t0 = now_seconds();
     hipTableLockShared(t);                                            /* until releaseQueryHIP: no writer meanwhile */
     const int lane = hipTableAcquireLane(t);
@@ -824,6 +828,51 @@ static int fused_issue(struct query *q, fused_call call, void *arg) {
     return rc;
 }
 
+/* The query on every shard, reduced on the host: what the dense bins of grouped COUNT, the aggregates, the buckets, the
+ * pairs and the first rows do.  Every shard with rows gets one device buffer of the query's own, [head][out]: `head_bytes`
+ * uploaded from `head` before anything is issued (the out part starts on the next 16 bytes), `bytes` of output.  Then
+ * either `fused` makes the one launch per shard (fused_issue), or the selection is left per shard (query_lists) and `list`
+ * runs over every shard's list that has rows, on the lane's copy context, writes `out` and returns the shim's status.
+ * After the waits a shard's out part is downloaded and handed to `combine`.  No callback sees a shard without rows. */
+struct shard_reduce {
+    const char *what;                    /* the query's word in the messages of a failed device call */
+    const void *head;
+    size_t head_bytes, bytes;
+    fused_call fused;
+    int (*list)(struct query *q, int s, pqps_ctx *cs, const struct hipLane *L, void *out, void *arg);
+    void (*combine)(void *arg, const void *host);
+};
+
+static size_t pad16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+
+/* buf[0 .. n_shards): filled with the shards' buffers for the callbacks (which find it through `arg`), freed on return. */
+static int shard_reduce(struct query *q, bool fused, const struct shard_reduce *r, void **buf, void *arg) {
+    const size_t head = pad16(r->head_bytes);
+    void *host = malloc(r->bytes);
+    int rc = host ? 0 : oom();
+    for (int s = 0; s < q->n_shards; s++) buf[s] = NULL;
+    for (int s = 0; s < q->n_shards && rc == 0; s++) {
+        struct hipTable *sh = hipTableShard(q->t, s);
+        if (sh->n_rows == 0) continue;
+        if (pqps_malloc(sh->ctx, head + r->bytes, &buf[s]) != PQPS_OK ||
+            (r->head_bytes && pqps_upload(lane_copy_ctx(q, s), buf[s], r->head, r->head_bytes, NULL) != PQPS_OK))
+            rc = engine_error(r->what);
+    }
+    if (rc == 0) rc = fused ? fused_issue(q, r->fused, arg) : query_lists(q);
+    for (int s = 0; s < q->n_shards && rc == 0; s++) {
+        if (!buf[s] || (!fused && q->count[s] == 0)) continue;
+        pqps_ctx *cs = lane_copy_ctx(q, s);
+        void *out = (char *)buf[s] + head;
+        if ((!fused && r->list(q, s, cs, query_lane(q, s), out, arg) != PQPS_OK) ||
+            pqps_download(cs, host, out, r->bytes, NULL) != PQPS_OK)
+            rc = engine_error(r->what);
+        else r->combine(arg, host);
+    }
+    for (int s = 0; s < q->n_shards; s++) if (buf[s]) pqps_free(hipTableShard(q->t, s)->ctx, buf[s]);
+    free(host);
+    return rc;
+}
+
 /* ---- grouped COUNT(*) (include/executeEngine-hip.h) --------------------------------------------------------------- */
 
 static const int k_group_kind[HIPCOL_COUNT] = {
@@ -880,6 +929,17 @@ static int group_column_id(const char *what, const char *column) {
     if (c < 0) { fprintf(stderr, "HIP engine: %s: unknown column '%s'\n", what, column); return -1; }
     if (c == HIPCOL_COMMAND_ID) { fprintf(stderr, "HIP engine: %s: command_id is unique -- grouping on it is the SELECT\n", what); return -1; }
     return c;
+}
+
+/* The HIPCOL_* of a value column (a number: i32 or command_id), or -1 with the reason on stderr. */
+static int value_column_id(const char *what, const char *column) {
+    const int v = hipColumnId(column);
+    if (v < 0) { fprintf(stderr, "HIP engine: %s: unknown value column '%s'\n", what, column); return -1; }
+    if (k_group_kind[v] != HIPKIND_I32 && k_group_kind[v] != HIPKIND_U64) {
+        fprintf(stderr, "HIP engine: %s: %s is a %s column, not a number\n", what, column, k_group_kind[v] == HIPKIND_BOOL ? "boolean" : "dictionary");
+        return -1;
+    }
+    return v;
 }
 
 /* Binds the WHERE into q: the plan and the index probes. */
@@ -945,10 +1005,28 @@ static int group_plan_init(struct engineS *engine, struct whereClauseS *whereCla
     return group_plan_column(q, query_bind(engine, whereClause, q), c, column, what, gp);
 }
 
-/* One shard's result added into the host accumulators: COUNT (vc < 0) u32 bins into acc[0 .. n_bins); an aggregate the
- * [4][n_bins] u64 fields of pqps_filter_aggregate into acc[4 * n_bins] (counts and sums added, min / max images taken). */
-static void group_combine(uint64_t *acc, const void *host, uint32_t n_bins, int vc) {
-    if (vc < 0) {
+/* The host accumulator of n > 0 dense bins: n counts (COUNT(DISTINCT)'s per-group answers too), or with a value column the
+ * [4][n] u64 fields of pqps_filter_aggregate (count, sum, min image, max image) with the min images all ones.  NULL, said
+ * on stderr: out of memory. */
+static uint64_t *bins_alloc(uint64_t n, bool valued) {
+    uint64_t *acc = calloc((size_t)(valued ? 4 : 1) * n, sizeof *acc);
+    if (!acc) oom();
+    for (uint64_t k = 0; acc && valued && k < n; k++) acc[2 * n + k] = UINT64_MAX;
+    return acc;
+}
+
+static size_t bins_bytes(uint32_t n, int vc) { return vc < 0 ? (size_t)n * sizeof(uint32_t) : (size_t)n * 4 * sizeof(uint64_t); }
+
+/* What the dense bins are added into: first in the arg of every shard_reduce whose combine is group_combine. */
+struct bins_acc { uint64_t *acc; uint32_t n_bins; int vc; };
+
+/* One shard's result added into the host accumulator: COUNT (vc < 0) u32 bins into acc[0 .. n_bins); an aggregate the
+ * [4][n_bins] u64 fields into acc[4 * n_bins] (counts and sums added, min / max images taken). */
+static void group_combine(void *arg, const void *host) {
+    const struct bins_acc *b = arg;
+    const uint32_t n_bins = b->n_bins;
+    uint64_t *acc = b->acc;
+    if (b->vc < 0) {
         for (uint32_t k = 0; k < n_bins; k++) acc[k] += ((const uint32_t *)host)[k];
         return;
     }
@@ -958,11 +1036,10 @@ static void group_combine(uint64_t *acc, const void *host, uint32_t n_bins, int 
     for (uint32_t k = 3 * n_bins; k < 4 * n_bins; k++) if (h[k] > acc[k]) acc[k] = h[k];
 }
 
-/* The bins of the query on every shard, combined on the host (group_combine).  vc < 0: grouped COUNT (pqps_filter_group /
- * pqps_group_list); otherwise the aggregates of value column vc (pqps_filter_aggregate / pqps_aggregate_list; no group
- * column without GROUP BY or for a single-valued one).  gp->fused: one launch per shard on the query's lane; otherwise the
- * selection (query_issue_all + query_await, each shard's list left on its own device) and the list kernel over every list. */
-struct group_call { const struct group_plan *gp; int vc; void **bins_dev; };
+/* The bins of the query on every shard, combined on the host (shard_reduce, group_combine).  vc < 0: grouped COUNT
+ * (pqps_filter_group / pqps_group_list); otherwise the aggregates of value column vc (pqps_filter_aggregate /
+ * pqps_aggregate_list; no group column without GROUP BY or for a single-valued one). */
+struct group_call { struct bins_acc into; const struct group_plan *gp; void **bins_dev; };
 
 static int group_fused_call(struct query *q, int s, pqps_ctx *ctx, void *stream, void *arg) {
     const struct group_call *a = arg;
@@ -970,46 +1047,29 @@ static int group_fused_call(struct query *q, int s, pqps_ctx *ctx, void *stream,
     const struct hipTable *sh = hipTableShard(q->t, s);
     const struct shard_pred *sp = &q->sp[s];
     const bool grouped = gp->c >= 0 && !gp->single;
-    const int rc = a->vc < 0 ? pqps_filter_group(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, &gp->gcol[s], gp->bin_base, gp->n_bins, a->bins_dev[s], stream)
-                             : pqps_filter_aggregate(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, &sh->col[a->vc], grouped ? &gp->gcol[s] : NULL,
-                                                     gp->bin_base, gp->n_bins, a->bins_dev[s], stream);
+    const int vc = a->into.vc;
+    const int rc = vc < 0 ? pqps_filter_group(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, &gp->gcol[s], gp->bin_base, gp->n_bins, a->bins_dev[s], stream)
+                          : pqps_filter_aggregate(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, &sh->col[vc], grouped ? &gp->gcol[s] : NULL,
+                                                  gp->bin_base, gp->n_bins, a->bins_dev[s], stream);
     return rc == PQPS_OK ? 0 : engine_error("group filter");
 }
 
-static int group_bins(struct query *q, const struct group_plan *gp, int vc, uint64_t *acc) {
-    const uint32_t n_bins = gp->n_bins, bin_base = gp->bin_base;
-    const size_t bytes = vc < 0 ? (size_t)n_bins * sizeof(uint32_t) : (size_t)n_bins * 4 * sizeof(uint64_t);
+static int group_list_call(struct query *q, int s, pqps_ctx *cs, const struct hipLane *L, void *out, void *arg) {
+    const struct group_call *a = arg;
+    const struct group_plan *gp = a->gp;
+    const struct hipTable *sh = hipTableShard(q->t, s);
     const bool grouped = gp->c >= 0 && !gp->single;
-    void *bins_dev[HIP_MAX_SHARDS] = { NULL };
-    void *host = malloc(bytes);
-    int rc = host ? 0 : -1;
-    if (!host) fprintf(stderr, "HIP engine: out of memory\n");
-    for (int s = 0; s < q->n_shards && rc == 0; s++)
-        if (pqps_malloc(hipTableShard(q->t, s)->ctx, bytes, &bins_dev[s]) != PQPS_OK) rc = engine_error("bins allocation");
-    if (rc == 0 && gp->fused) {
-        rc = fused_issue(q, group_fused_call, &(struct group_call){ gp, vc, bins_dev });
-        for (int s = 0; s < q->n_shards && rc == 0; s++)
-            if (hipTableShard(q->t, s)->n_rows == 0) continue;
-            else if (pqps_download(lane_copy_ctx(q, s), host, bins_dev[s], bytes, NULL) != PQPS_OK) rc = engine_error("bins download");
-            else group_combine(acc, host, n_bins, vc);
-    } else if (rc == 0) {
-        rc = query_lists(q);
-        for (int s = 0; s < q->n_shards && rc == 0; s++) {
-            struct hipTable *sh = hipTableShard(q->t, s);
-            struct hipLane *L = query_lane(q, s);
-            pqps_ctx *cs = lane_copy_ctx(q, s);
-            if (q->count[s] == 0) continue;
-            if ((vc < 0 ? pqps_group_list(cs, &gp->gcol[s], sh->n_rows, L->ids_dev, L->count_dev, q->count[s], (uint32_t)sh->row0, bin_base, n_bins, bins_dev[s], NULL)
-                        : pqps_aggregate_list(cs, &sh->col[vc], grouped ? &gp->gcol[s] : NULL, sh->n_rows, L->ids_dev, L->count_dev, q->count[s],
-                                              (uint32_t)sh->row0, bin_base, n_bins, bins_dev[s], NULL)) != PQPS_OK ||
-                pqps_download(cs, host, bins_dev[s], bytes, NULL) != PQPS_OK)
-                rc = engine_error("group list");
-            else group_combine(acc, host, n_bins, vc);
-        }
-    }
-    for (int s = 0; s < q->n_shards; s++) if (bins_dev[s]) pqps_free(hipTableShard(q->t, s)->ctx, bins_dev[s]);
-    free(host);
-    return rc;
+    const int vc = a->into.vc;
+    return vc < 0 ? pqps_group_list(cs, &gp->gcol[s], sh->n_rows, L->ids_dev, L->count_dev, q->count[s], (uint32_t)sh->row0, gp->bin_base, gp->n_bins, out, NULL)
+                  : pqps_aggregate_list(cs, &sh->col[vc], grouped ? &gp->gcol[s] : NULL, sh->n_rows, L->ids_dev, L->count_dev, q->count[s],
+                                        (uint32_t)sh->row0, gp->bin_base, gp->n_bins, out, NULL);
+}
+
+static int group_bins(struct query *q, const struct group_plan *gp, int vc, uint64_t *acc) {
+    void *bins_dev[HIP_MAX_SHARDS];
+    const struct shard_reduce r = { .what = "group bins", .bytes = bins_bytes(gp->n_bins, vc), .fused = group_fused_call,
+                                    .list = group_list_call, .combine = group_combine };
+    return shard_reduce(q, gp->fused, &r, bins_dev, &(struct group_call){ { acc, gp->n_bins, vc }, gp, bins_dev });
 }
 
 /* The rows of every group (counts[0 .. n_bins)), as grouped COUNT finds them (COUNT(DISTINCT) of a single-valued column too). */
@@ -1049,8 +1109,7 @@ static int group_keys_fill(const struct hipTable *t, int column, int kind, int32
         ++*numGroups;
     }
     if (*keys && *keyText && *numGroups == n) return 0;
-    fprintf(stderr, "HIP engine: out of memory\n");
-    return -1;
+    return oom();
 }
 
 static void free_group_keys(long long *keys, char **keyText, int numGroups) {
@@ -1059,10 +1118,40 @@ static void free_group_keys(long long *keys, char **keyText, int numGroups) {
     free(keys);
 }
 
+/* The per-group arrays of a result with n groups: counts and, with a value column, sums / mins / maxs; n + 1 entries each. */
+static int group_arrays_alloc(size_t n, bool valued, unsigned long long **counts, long long **sums, long long **mins, long long **maxs) {
+    *counts = calloc(n + 1, sizeof **counts);
+    if (valued) {
+        *sums = calloc(n + 1, sizeof **sums);
+        *mins = calloc(n + 1, sizeof **mins);
+        *maxs = calloc(n + 1, sizeof **maxs);
+    }
+    return *counts && (!valued || (*sums && *mins && *maxs)) ? 0 : oom();
+}
+
+/* Group g of those arrays (sums == NULL: its count alone) from the accumulated fields.  The image of an i32 value is
+ * (u64)(i64)v ^ 2^63, of a u64 value the value itself. */
+static void group_arrays_set(unsigned long long *counts, long long *sums, long long *mins, long long *maxs, size_t g,
+                             uint64_t count, uint64_t sum, uint64_t min_image, uint64_t max_image, int valueKind) {
+    const uint64_t flip = valueKind == HIPKIND_I32 ? 0x8000000000000000ull : 0;
+    counts[g] = count;
+    if (!sums) return;
+    sums[g] = (long long)sum;
+    mins[g] = (long long)(min_image ^ flip);
+    maxs[g] = (long long)(max_image ^ flip);
+}
+
+static void group_arrays_free(unsigned long long *counts, long long *sums, long long *mins, long long *maxs) {
+    free(counts);
+    free(sums);
+    free(mins);
+    free(maxs);
+}
+
 static int group_result_fill(struct hipGroupResult *res, const struct hipTable *t, const uint64_t *counts, uint32_t n_bins, int32_t lo) {
     if (group_keys_fill(t, res->column, res->kind, lo, counts, n_bins, &res->keys, &res->keyText, &res->numGroups) != 0) return -1;
     res->counts = calloc((size_t)res->numGroups + 1, sizeof *res->counts);
-    if (!res->counts) { fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
+    if (!res->counts) return oom();
     int g = 0;
     for (uint32_t k = 0; k < n_bins; k++) {
         if (!counts[k]) continue;
@@ -1075,7 +1164,7 @@ static int group_result_fill(struct hipGroupResult *res, const struct hipTable *
 struct hipGroupResult *executeQueryGroupCountHIP(struct engineS *engine, const char *groupColumn, struct whereClauseS *whereClause) {
     const double t0 = now_seconds();
     struct hipGroupResult *res = calloc(1, sizeof *res);
-    if (!res) { fprintf(stderr, "HIP engine: out of memory\n"); return NULL; }
+    if (!res) { oom(); return NULL; }
     res->column = -1;
     res->kind = -1;
     if (!engine || !engine->record_block || !groupColumn) { fprintf(stderr, "HIP engine: grouped COUNT without an engine or a column\n"); return res; }
@@ -1090,10 +1179,7 @@ struct hipGroupResult *executeQueryGroupCountHIP(struct engineS *engine, const c
     uint64_t *counts = NULL;
     struct group_plan gp;
     int rc = group_plan_init(engine, whereClause, &q, c, groupColumn, "grouped COUNT", &gp);
-    if (rc == 0 && !gp.empty) {
-        counts = calloc(gp.n_bins, sizeof *counts);
-        if (!counts) { fprintf(stderr, "HIP engine: out of memory\n"); rc = -1; }
-    }
+    if (rc == 0 && !gp.empty && !(counts = bins_alloc(gp.n_bins, false))) rc = -1;
     if (rc == 0 && !gp.empty) rc = group_counts(&q, &gp, counts);
     if (rc == 0 && group_result_fill(res, t, counts ? counts : (uint64_t[1]){ 0 }, gp.empty ? 0u : gp.n_bins, gp.lo) == 0) res->success = true;
     free(counts);
@@ -1114,23 +1200,12 @@ void freeGroupResultHIP(struct hipGroupResult *res) {
 /* acc[4][n_bins] (count, sum, min image, max image: pqps_filter_aggregate's layout) into the result, groups with rows only */
 static int aggregate_result_fill(struct hipAggregateResult *res, const struct hipTable *t, const uint64_t *acc, uint32_t n_bins, int32_t lo) {
     if (group_keys_fill(t, res->groupColumn, res->groupKind, lo, acc, n_bins, &res->keys, &res->keyText, &res->numGroups) != 0) return -1;
-    const size_t n = (size_t)res->numGroups;
-    res->counts = calloc(n + 1, sizeof *res->counts);
-    res->sums = calloc(n + 1, sizeof *res->sums);
-    res->mins = calloc(n + 1, sizeof *res->mins);
-    res->maxs = calloc(n + 1, sizeof *res->maxs);
-    if (!res->counts || !res->sums || !res->mins || !res->maxs) { fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
-    /* the image of an i32 value is (u64)(i64)v ^ 2^63, of a u64 value the value itself */
-    const uint64_t flip = res->valueKind == HIPKIND_I32 ? 0x8000000000000000ull : 0;
-    int g = 0;
+    if (group_arrays_alloc((size_t)res->numGroups, true, &res->counts, &res->sums, &res->mins, &res->maxs) != 0) return -1;
+    size_t g = 0;
     for (uint32_t k = 0; k < n_bins; k++) {
         if (!acc[k]) continue;
-        res->counts[g] = acc[k];
-        res->sums[g] = (long long)acc[n_bins + k];
-        res->mins[g] = (long long)(acc[2 * n_bins + k] ^ flip);
-        res->maxs[g] = (long long)(acc[3 * n_bins + k] ^ flip);
+        group_arrays_set(res->counts, res->sums, res->mins, res->maxs, g++, acc[k], acc[n_bins + k], acc[2 * n_bins + k], acc[3 * n_bins + k], res->valueKind);
         res->total += (long long)acc[k];
-        g++;
     }
     return 0;
 }
@@ -1139,15 +1214,11 @@ struct hipAggregateResult *executeQueryAggregateHIP(struct engineS *engine, cons
                                                     struct whereClauseS *whereClause) {
     const double t0 = now_seconds();
     struct hipAggregateResult *res = calloc(1, sizeof *res);
-    if (!res) { fprintf(stderr, "HIP engine: out of memory\n"); return NULL; }
+    if (!res) { oom(); return NULL; }
     res->valueColumn = res->valueKind = res->groupColumn = res->groupKind = -1;
     if (!engine || !engine->record_block || !valueColumn) { fprintf(stderr, "HIP engine: aggregate without an engine or a value column\n"); return res; }
-    const int v = hipColumnId(valueColumn);
-    if (v < 0) { fprintf(stderr, "HIP engine: aggregate: unknown value column '%s'\n", valueColumn); return res; }
-    if (k_group_kind[v] != HIPKIND_I32 && k_group_kind[v] != HIPKIND_U64) {
-        fprintf(stderr, "HIP engine: aggregate: %s is a %s column, not a number\n", valueColumn, k_group_kind[v] == HIPKIND_BOOL ? "boolean" : "dictionary");
-        return res;
-    }
+    const int v = value_column_id("aggregate", valueColumn);
+    if (v < 0) return res;
     const int c = groupColumn ? group_column_id("aggregate", groupColumn) : -1;
     if (groupColumn && c < 0) return res;
     struct hipTable *t = engine->record_block;
@@ -1161,11 +1232,7 @@ struct hipAggregateResult *executeQueryAggregateHIP(struct engineS *engine, cons
     uint64_t *acc = NULL;
     struct group_plan gp;
     int rc = group_plan_init(engine, whereClause, &q, c, groupColumn, "aggregate", &gp);
-    if (rc == 0 && !gp.empty) {
-        acc = calloc((size_t)4 * gp.n_bins, sizeof *acc);
-        if (!acc) { fprintf(stderr, "HIP engine: out of memory\n"); rc = -1; }
-        else for (uint32_t k = 0; k < gp.n_bins; k++) acc[2 * gp.n_bins + k] = UINT64_MAX;
-    }
+    if (rc == 0 && !gp.empty && !(acc = bins_alloc(gp.n_bins, true))) rc = -1;
     if (rc == 0 && !gp.empty) rc = group_bins(&q, &gp, v, acc);
     if (rc == 0 && aggregate_result_fill(res, t, acc ? acc : (uint64_t[4]){ 0 }, gp.empty ? 0u : gp.n_bins, gp.lo) == 0) res->success = true;
     free(acc);
@@ -1177,10 +1244,7 @@ struct hipAggregateResult *executeQueryAggregateHIP(struct engineS *engine, cons
 void freeAggregateResultHIP(struct hipAggregateResult *res) {
     if (!res) return;
     free_group_keys(res->keys, res->keyText, res->numGroups);
-    free(res->counts);
-    free(res->sums);
-    free(res->mins);
-    free(res->maxs);
+    group_arrays_free(res->counts, res->sums, res->mins, res->maxs);
     free(res);
 }
 
@@ -1228,7 +1292,7 @@ static void bucket_plan_free(struct bucket_plan *bp) {
     free(bp->keys);
 }
 
-struct bucket_call { const struct bucket_plan *bp; int vc; void **buf; size_t head; };
+struct bucket_call { struct bins_acc into; const struct bucket_plan *bp; void **buf; size_t head; };
 
 static int bucket_fused_call(struct query *q, int s, pqps_ctx *ctx, void *stream, void *arg) {
     const struct bucket_call *a = arg;
@@ -1238,58 +1302,35 @@ static int bucket_fused_call(struct query *q, int s, pqps_ctx *ctx, void *stream
     const uint32_t *bounds_dev = a->buf[s];
     void *out = (char *)a->buf[s] + a->head;
     const uint32_t domain = a->bp->bounds[gp->n_bins];
-    const int rc = a->vc < 0 ? pqps_filter_group_buckets(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, &gp->gcol[s], gp->bin_base, bounds_dev,
-                                                         gp->n_bins, domain, out, stream)
-                             : pqps_filter_aggregate_buckets(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, &sh->col[a->vc], &gp->gcol[s],
-                                                             gp->bin_base, bounds_dev, gp->n_bins, domain, out, stream);
+    const int vc = a->into.vc;
+    const int rc = vc < 0 ? pqps_filter_group_buckets(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, &gp->gcol[s], gp->bin_base, bounds_dev,
+                                                      gp->n_bins, domain, out, stream)
+                          : pqps_filter_aggregate_buckets(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, &sh->col[vc], &gp->gcol[s],
+                                                          gp->bin_base, bounds_dev, gp->n_bins, domain, out, stream);
     return rc == PQPS_OK ? 0 : engine_error("bucket filter");
 }
 
-/* The buckets of the query on every shard, combined on the host (group_combine): vc < 0 the counts, otherwise the aggregates
- * of value column vc.  Per shard one buffer of the query's own, [bounds][bins], the bounds uploaded once before anything is
- * issued.  gp.fused: one launch per shard on the query's lane; otherwise the selection and the list call over every list. */
+static int bucket_list_call(struct query *q, int s, pqps_ctx *cs, const struct hipLane *L, void *out, void *arg) {
+    const struct bucket_call *a = arg;
+    const struct group_plan *gp = &a->bp->gp;
+    const struct hipTable *sh = hipTableShard(q->t, s);
+    const uint32_t *bounds_dev = a->buf[s];
+    const uint32_t domain = a->bp->bounds[gp->n_bins];
+    const int vc = a->into.vc;
+    return vc < 0 ? pqps_group_buckets_list(cs, &gp->gcol[s], sh->n_rows, L->ids_dev, L->count_dev, q->count[s], (uint32_t)sh->row0, gp->bin_base,
+                                            bounds_dev, gp->n_bins, domain, out, NULL)
+                  : pqps_aggregate_buckets_list(cs, &sh->col[vc], &gp->gcol[s], sh->n_rows, L->ids_dev, L->count_dev, q->count[s],
+                                                (uint32_t)sh->row0, gp->bin_base, bounds_dev, gp->n_bins, domain, out, NULL);
+}
+
+/* The buckets of the query on every shard, combined on the host (shard_reduce, group_combine): vc < 0 the counts, otherwise
+ * the aggregates of value column vc.  A shard's buffer is [bounds][bins], the bounds the head that is uploaded once. */
 static int bucket_bins(struct query *q, const struct bucket_plan *bp, int vc, uint64_t *acc) {
-    const struct group_plan *gp = &bp->gp;
-    const uint32_t n_bins = gp->n_bins, domain = bp->bounds[n_bins];
-    const size_t head = (((size_t)n_bins + 1) * sizeof(uint32_t) + 15) & ~(size_t)15;
-    const size_t bytes = vc < 0 ? (size_t)n_bins * sizeof(uint32_t) : (size_t)n_bins * 4 * sizeof(uint64_t);
-    void *buf[HIP_MAX_SHARDS] = { NULL };
-    void *host = malloc(bytes);
-    int rc = host ? 0 : -1;
-    if (!host) fprintf(stderr, "HIP engine: out of memory\n");
-    for (int s = 0; s < q->n_shards && rc == 0; s++) {
-        struct hipTable *sh = hipTableShard(q->t, s);
-        if (sh->n_rows == 0) continue;
-        if (pqps_malloc(sh->ctx, head + bytes, &buf[s]) != PQPS_OK) rc = engine_error("bucket scratch");
-        else if (pqps_upload(lane_copy_ctx(q, s), buf[s], bp->bounds, ((size_t)n_bins + 1) * sizeof(uint32_t), NULL) != PQPS_OK)
-            rc = engine_error("bucket bounds upload");
-    }
-    if (rc == 0 && gp->fused) {
-        rc = fused_issue(q, bucket_fused_call, &(struct bucket_call){ bp, vc, buf, head });
-        for (int s = 0; s < q->n_shards && rc == 0; s++)
-            if (!buf[s]) continue;
-            else if (pqps_download(lane_copy_ctx(q, s), host, (char *)buf[s] + head, bytes, NULL) != PQPS_OK) rc = engine_error("buckets download");
-            else group_combine(acc, host, n_bins, vc);
-    } else if (rc == 0) {
-        rc = query_lists(q);
-        for (int s = 0; s < q->n_shards && rc == 0; s++) {
-            struct hipTable *sh = hipTableShard(q->t, s);
-            struct hipLane *L = query_lane(q, s);
-            pqps_ctx *cs = lane_copy_ctx(q, s);
-            void *out = buf[s] ? (char *)buf[s] + head : NULL;
-            if (q->count[s] == 0 || !buf[s]) continue;
-            if ((vc < 0 ? pqps_group_buckets_list(cs, &gp->gcol[s], sh->n_rows, L->ids_dev, L->count_dev, q->count[s], (uint32_t)sh->row0, gp->bin_base,
-                                                  buf[s], n_bins, domain, out, NULL)
-                        : pqps_aggregate_buckets_list(cs, &sh->col[vc], &gp->gcol[s], sh->n_rows, L->ids_dev, L->count_dev, q->count[s],
-                                                      (uint32_t)sh->row0, gp->bin_base, buf[s], n_bins, domain, out, NULL)) != PQPS_OK ||
-                pqps_download(cs, host, out, bytes, NULL) != PQPS_OK)
-                rc = engine_error("bucket list");
-            else group_combine(acc, host, n_bins, vc);
-        }
-    }
-    for (int s = 0; s < q->n_shards; s++) if (buf[s]) pqps_free(hipTableShard(q->t, s)->ctx, buf[s]);
-    free(host);
-    return rc;
+    const uint32_t n_bins = bp->gp.n_bins;
+    void *buf[HIP_MAX_SHARDS];
+    const struct shard_reduce r = { .what = "buckets", .head = bp->bounds, .head_bytes = ((size_t)n_bins + 1) * sizeof(uint32_t),
+                                    .bytes = bins_bytes(n_bins, vc), .fused = bucket_fused_call, .list = bucket_list_call, .combine = group_combine };
+    return shard_reduce(q, bp->gp.fused, &r, buf, &(struct bucket_call){ { acc, n_bins, vc }, bp, buf, pad16(r.head_bytes) });
 }
 
 /* acc (counts, or the [4][n_bins] fields) into the result: buckets with rows only, with their keys and key texts */
@@ -1299,18 +1340,8 @@ static int bucket_result_fill(struct hipBucketResult *res, const struct hipTable
     for (uint32_t k = 0; k < n_bins; k++) n += acc[k] != 0;
     res->keys = calloc(n + 1, sizeof *res->keys);
     res->keyText = calloc(n + 1, sizeof *res->keyText);
-    res->counts = calloc(n + 1, sizeof *res->counts);
-    if (valued) {
-        res->sums = calloc(n + 1, sizeof *res->sums);
-        res->mins = calloc(n + 1, sizeof *res->mins);
-        res->maxs = calloc(n + 1, sizeof *res->maxs);
-    }
-    if (!res->keys || !res->keyText || !res->counts || (valued && (!res->sums || !res->mins || !res->maxs))) {
-        fprintf(stderr, "HIP engine: out of memory\n");
-        return -1;
-    }
-    /* the image of an i32 value is (u64)(i64)v ^ 2^63, of a u64 value the value itself */
-    const uint64_t flip = res->valueKind == HIPKIND_I32 ? 0x8000000000000000ull : 0;
+    if (!res->keys || !res->keyText) return oom();
+    if (group_arrays_alloc(n, valued, &res->counts, &res->sums, &res->mins, &res->maxs) != 0) return -1;
     for (uint32_t k = 0; k < n_bins; k++) {
         if (!acc[k]) continue;
         const int g = res->numGroups;
@@ -1324,13 +1355,9 @@ static int bucket_result_fill(struct hipBucketResult *res, const struct hipTable
             const size_t len = strlen(text);
             res->keyText[g] = strndup(text, (unsigned long long)bp->arg < len ? (size_t)bp->arg : len);
         }
-        if (!res->keyText[g]) { fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
-        res->counts[g] = acc[k];
-        if (valued) {
-            res->sums[g] = (long long)acc[n_bins + k];
-            res->mins[g] = (long long)(acc[2 * n_bins + k] ^ flip);
-            res->maxs[g] = (long long)(acc[3 * n_bins + k] ^ flip);
-        }
+        if (!res->keyText[g]) return oom();
+        group_arrays_set(res->counts, res->sums, res->mins, res->maxs, (size_t)g, acc[k], valued ? acc[n_bins + k] : 0,
+                         valued ? acc[2 * n_bins + k] : 0, valued ? acc[3 * n_bins + k] : 0, res->valueKind);
         res->total += (long long)acc[k];
         res->numGroups++;
     }
@@ -1341,7 +1368,7 @@ struct hipBucketResult *executeQueryGroupBucketsHIP(struct engineS *engine, cons
                                                     const char *valueColumn, struct whereClauseS *whereClause) {
     const double t0 = now_seconds();
     struct hipBucketResult *res = calloc(1, sizeof *res);
-    if (!res) { fprintf(stderr, "HIP engine: out of memory\n"); return NULL; }
+    if (!res) { oom(); return NULL; }
     res->groupColumn = res->groupKind = res->valueColumn = res->valueKind = -1;
     res->bucketMode = bucketMode;
     res->bucketArg = bucketArg;
@@ -1356,12 +1383,8 @@ struct hipBucketResult *executeQueryGroupBucketsHIP(struct engineS *engine, cons
         free(k);
     }
     const int c = hipColumnId(groupColumn);
-    const int v = valueColumn ? hipColumnId(valueColumn) : -1;
-    if (valueColumn && v < 0) { fprintf(stderr, "HIP engine: GROUP BY buckets: unknown value column '%s'\n", valueColumn); return res; }
-    if (v >= 0 && k_group_kind[v] != HIPKIND_I32 && k_group_kind[v] != HIPKIND_U64) {
-        fprintf(stderr, "HIP engine: GROUP BY buckets: %s is a %s column, not a number\n", valueColumn, k_group_kind[v] == HIPKIND_BOOL ? "boolean" : "dictionary");
-        return res;
-    }
+    const int v = valueColumn ? value_column_id("GROUP BY buckets", valueColumn) : -1;
+    if (valueColumn && v < 0) return res;
     struct hipTable *t = engine->record_block;
     if (t->xch) { fprintf(stderr, "HIP engine: GROUP BY buckets is not exchanged across ranks\n"); return res; }
     res->groupColumn = c;
@@ -1374,11 +1397,7 @@ struct hipBucketResult *executeQueryGroupBucketsHIP(struct engineS *engine, cons
     struct bucket_plan bp;
     int rc = bucket_plan_init(engine, whereClause, &q, c, groupColumn, bucketMode, bucketArg, &bp);
     const uint32_t n_bins = rc == 0 && !bp.gp.empty ? bp.gp.n_bins : 0u;
-    if (n_bins) {
-        acc = calloc((size_t)(v >= 0 ? 4 : 1) * n_bins, sizeof *acc);
-        if (!acc) { fprintf(stderr, "HIP engine: out of memory\n"); rc = -1; }
-        else if (v >= 0) for (uint32_t k = 0; k < n_bins; k++) acc[2 * n_bins + k] = UINT64_MAX;
-    }
+    if (n_bins && !(acc = bins_alloc(n_bins, v >= 0))) rc = -1;
     /* a single-valued column has no device buffer: one bucket from the selection (group_counts), or the ungrouped aggregate */
     if (rc == 0 && n_bins) rc = !bp.gp.single ? bucket_bins(&q, &bp, v, acc) : v < 0 ? group_counts(&q, &bp.gp, acc) : group_bins(&q, &bp.gp, v, acc);
     if (rc == 0 && bucket_result_fill(res, t, &bp, acc ? acc : (uint64_t[4]){ 0 }, n_bins) == 0) res->success = true;
@@ -1392,10 +1411,7 @@ struct hipBucketResult *executeQueryGroupBucketsHIP(struct engineS *engine, cons
 void freeBucketResultHIP(struct hipBucketResult *res) {
     if (!res) return;
     free_group_keys(res->keys, res->keyText, res->numGroups);
-    free(res->counts);
-    free(res->sums);
-    free(res->mins);
-    free(res->maxs);
+    group_arrays_free(res->counts, res->sums, res->mins, res->maxs);
     free(res);
 }
 
@@ -1468,7 +1484,7 @@ static int distinct_fused_call(struct query *q, int s, pqps_ctx *ctx, void *stre
 static int distinct_bitmap(struct query *q, const struct group_plan *gp, const struct distinct_plan *dp, uint64_t *distinct, uint64_t *total) {
     const uint32_t G = gp->n_bins, D = dp->n_values;
     const uint64_t words = pqps_distinct_bitmap_words(D, G);
-    const size_t head = 16 + (((size_t)G * 8 + 15) & ~(size_t)15);   /* [total][distinct][bitmap] */
+    const size_t head = 16 + pad16((size_t)G * 8);   /* [total][distinct][bitmap] */
     const size_t bytes = head + words * 4;
     const bool grouped = gp->c >= 0 && !gp->single;
     const bool multi = q->n_shards > 1;
@@ -1503,7 +1519,7 @@ static int distinct_bitmap(struct query *q, const struct group_plan *gp, const s
         if (filled[0] && pqps_download(lane_copy_ctx(q, 0), distinct, DBUF_DISTINCT(0), (size_t)G * 8, NULL) != PQPS_OK) rc = engine_error("COUNT(DISTINCT) download");
     } else if (rc == 0) {
         uint32_t *merged = calloc(words, sizeof *merged), *part = malloc(words * sizeof *part);
-        if (!merged || !part) { fprintf(stderr, "HIP engine: out of memory\n"); rc = -1; }
+        if (!merged || !part) rc = oom();
         bool any = false;
         for (int s = 0; s < q->n_shards && rc == 0; s++) {
             if (!filled[s]) continue;
@@ -1559,7 +1575,7 @@ static int distinct_sort(struct query *q, const struct group_plan *gp, const str
         if (pqps_distinct_sort(cs, &sh->col[dp->v], dp->v_base, grouped ? &sh->col[gp->c] : NULL, gp->bin_base, G, query_lane(q, s)->ids_dev, n,
                                (uint32_t)sh->row0, dev, keys_dev, NULL) != PQPS_OK) rc = engine_error("COUNT(DISTINCT) sort");
         else if (!multi) { if (pqps_download(cs, distinct, dev, (size_t)G * 8, NULL) != PQPS_OK) rc = engine_error("COUNT(DISTINCT) download"); }
-        else if (!(host[s] = malloc(key_bytes))) { fprintf(stderr, "HIP engine: out of memory\n"); rc = -1; }
+        else if (!(host[s] = malloc(key_bytes))) rc = oom();
         else if (pqps_download(cs, host[s], keys_dev, key_bytes, NULL) != PQPS_OK) rc = engine_error("COUNT(DISTINCT) download");
         else keys[s] = (struct distinct_keys){ host[s], wide ? (const uint32_t *)((uint64_t *)host[s] + n) : NULL, n, 0, wide };
         pqps_free(sh->ctx, dev);
@@ -1593,7 +1609,7 @@ static int distinct_sort(struct query *q, const struct group_plan *gp, const str
 static int distinct_result_fill(struct hipDistinctResult *res, const struct hipTable *t, const uint64_t *distinct, uint32_t n_bins, int32_t lo) {
     if (group_keys_fill(t, res->groupColumn, res->groupKind, lo, distinct, n_bins, &res->keys, &res->keyText, &res->numGroups) != 0) return -1;
     res->distinct = calloc((size_t)res->numGroups + 1, sizeof *res->distinct);
-    if (!res->distinct) { fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
+    if (!res->distinct) return oom();
     int g = 0;
     for (uint32_t k = 0; k < n_bins; k++) if (distinct[k]) res->distinct[g++] = distinct[k];
     return 0;
@@ -1603,7 +1619,7 @@ struct hipDistinctResult *executeQueryCountDistinctHIP(struct engineS *engine, c
                                                        struct whereClauseS *whereClause) {
     const double t0 = now_seconds();
     struct hipDistinctResult *res = calloc(1, sizeof *res);
-    if (!res) { fprintf(stderr, "HIP engine: out of memory\n"); return NULL; }
+    if (!res) { oom(); return NULL; }
     res->valueColumn = res->valueKind = res->groupColumn = res->groupKind = -1;
     if (!engine || !engine->record_block || !valueColumn) { fprintf(stderr, "HIP engine: COUNT(DISTINCT) without an engine or a value column\n"); return res; }
     const int v = hipColumnId(valueColumn);
@@ -1622,10 +1638,7 @@ struct hipDistinctResult *executeQueryCountDistinctHIP(struct engineS *engine, c
     struct group_plan gp;
     struct distinct_plan dp;
     int rc = group_plan_init(engine, whereClause, &q, c, groupColumn, "COUNT(DISTINCT)", &gp);
-    if (rc == 0 && !gp.empty) {
-        distinct = calloc(gp.n_bins, sizeof *distinct);
-        if (!distinct) { fprintf(stderr, "HIP engine: out of memory\n"); rc = -1; }
-    }
+    if (rc == 0 && !gp.empty && !(distinct = bins_alloc(gp.n_bins, false))) rc = -1;
     if (rc == 0 && !gp.empty) rc = distinct_plan_init(&q, &gp, v, &dp);
     if (rc == 0 && !gp.empty) {
         if (dp.single) {                                                 /* one value: 1 for every group with rows */
@@ -1673,9 +1686,8 @@ static int pair_rows_alloc(struct pair_rows *pr, uint64_t n, bool valued) {
         pr->mx = calloc((size_t)n + 1, sizeof *pr->mx);
     }
     if (pr->key && pr->cnt && (!valued || (pr->sum && pr->mn && pr->mx))) return 0;
-    fprintf(stderr, "HIP engine: out of memory\n");
     pair_rows_free(pr);
-    return -1;
+    return oom();
 }
 
 /* Dense bins (acc: D counts, or the [4][D] fields of group_combine) into pairs: bin k is the pair (k / n_b, k % n_b). */
@@ -1693,52 +1705,35 @@ static int pair_rows_from_bins(const uint64_t *acc, uint32_t D, uint32_t n_b, bo
     return 0;
 }
 
-struct pair_call { const struct group_plan *a, *b; int vc; void **out_dev; };
+struct pair_call { struct bins_acc into; const struct group_plan *a, *b; void **out_dev; };
 
 static int pair_fused_call(struct query *q, int s, pqps_ctx *ctx, void *stream, void *arg) {
     const struct pair_call *p = arg;
     const struct hipTable *sh = hipTableShard(q->t, s);
     const struct shard_pred *sp = &q->sp[s];
+    const int vc = p->into.vc;
     const int rc = pqps_filter_group_pair(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, &p->a->gcol[s], p->a->bin_base, p->a->n_bins,
-                                          &p->b->gcol[s], p->b->bin_base, p->b->n_bins, p->vc >= 0 ? &sh->col[p->vc] : NULL, p->out_dev[s], stream);
+                                          &p->b->gcol[s], p->b->bin_base, p->b->n_bins, vc >= 0 ? &sh->col[vc] : NULL, p->out_dev[s], stream);
     return rc == PQPS_OK ? 0 : engine_error("group pair filter");
 }
 
-/* The dense bins (D = n_a x n_b <= 65 536) of the query on every shard, combined on the host as group_bins does: one fused
- * launch per shard (pqps_filter_group_pair), or the selection and pqps_group_pair_list over every shard's list. */
+/* (off the fused path gcol[s] is the shard's own column) */
+static int pair_list_call(struct query *q, int s, pqps_ctx *cs, const struct hipLane *L, void *out, void *arg) {
+    const struct pair_call *p = arg;
+    const struct hipTable *sh = hipTableShard(q->t, s);
+    const int vc = p->into.vc;
+    return pqps_group_pair_list(cs, &p->a->gcol[s], p->a->bin_base, p->a->n_bins, &p->b->gcol[s], p->b->bin_base, p->b->n_bins,
+                                vc >= 0 ? &sh->col[vc] : NULL, sh->n_rows, L->ids_dev, L->count_dev, q->count[s], (uint32_t)sh->row0, out, NULL);
+}
+
+/* The dense bins (D = n_a x n_b <= 65 536) of the query on every shard, combined on the host (shard_reduce, group_combine):
+ * pqps_filter_group_pair, or pqps_group_pair_list over every shard's list. */
 static int pair_dense(struct query *q, const struct group_plan *a, const struct group_plan *b, int vc, uint64_t *acc) {
     const uint32_t D = a->n_bins * b->n_bins;
-    const size_t bytes = vc < 0 ? (size_t)D * sizeof(uint32_t) : (size_t)D * 4 * sizeof(uint64_t);
-    void *out_dev[HIP_MAX_SHARDS] = { NULL };
-    void *host = malloc(bytes);
-    int rc = host ? 0 : -1;
-    if (!host) fprintf(stderr, "HIP engine: out of memory\n");
-    for (int s = 0; s < q->n_shards && rc == 0; s++)
-        if (pqps_malloc(hipTableShard(q->t, s)->ctx, bytes, &out_dev[s]) != PQPS_OK) rc = engine_error("bins allocation");
-    if (rc == 0 && a->fused) {
-        rc = fused_issue(q, pair_fused_call, &(struct pair_call){ a, b, vc, out_dev });
-        for (int s = 0; s < q->n_shards && rc == 0; s++)
-            if (hipTableShard(q->t, s)->n_rows == 0) continue;
-            else if (pqps_download(lane_copy_ctx(q, s), host, out_dev[s], bytes, NULL) != PQPS_OK) rc = engine_error("bins download");
-            else group_combine(acc, host, D, vc);
-    } else if (rc == 0) {
-        rc = query_lists(q);
-        for (int s = 0; s < q->n_shards && rc == 0; s++) {
-            struct hipTable *sh = hipTableShard(q->t, s);
-            struct hipLane *L = query_lane(q, s);
-            pqps_ctx *cs = lane_copy_ctx(q, s);
-            if (q->count[s] == 0) continue;
-            if (pqps_group_pair_list(cs, &sh->col[a->c], a->bin_base, a->n_bins, &sh->col[b->c], b->bin_base, b->n_bins,
-                                     vc >= 0 ? &sh->col[vc] : NULL, sh->n_rows, L->ids_dev, L->count_dev, q->count[s], (uint32_t)sh->row0,
-                                     out_dev[s], NULL) != PQPS_OK ||
-                pqps_download(cs, host, out_dev[s], bytes, NULL) != PQPS_OK)
-                rc = engine_error("group pair list");
-            else group_combine(acc, host, D, vc);
-        }
-    }
-    for (int s = 0; s < q->n_shards; s++) if (out_dev[s]) pqps_free(hipTableShard(q->t, s)->ctx, out_dev[s]);
-    free(host);
-    return rc;
+    void *out_dev[HIP_MAX_SHARDS];
+    const struct shard_reduce r = { .what = "group pair bins", .bytes = bins_bytes(D, vc), .fused = pair_fused_call,
+                                    .list = pair_list_call, .combine = group_combine };
+    return shard_reduce(q, a->fused, &r, out_dev, &(struct pair_call){ { acc, D, vc }, a, b, out_dev });
 }
 
 /* The sparse form: the selection, every shard's list sorted and reduced to its runs on its device (pqps_group_pair_sort),
@@ -1758,7 +1753,7 @@ static int pair_sparse(struct query *q, const struct group_plan *a, const struct
         if (pqps_group_pair_sort(cs, &sh->col[a->c], a->bin_base, a->n_bins, &sh->col[b->c], b->bin_base, b->n_bins, valued ? &sh->col[vc] : NULL,
                                  sh->n_rows, query_lane(q, s)->ids_dev, q->count[s], (uint32_t)sh->row0, &runs_dev, &runs[s], NULL) != PQPS_OK)
             rc = engine_error("group pair sort");
-        else if (runs[s] && !(host[s] = malloc(fields * (size_t)runs[s] * 8))) { fprintf(stderr, "HIP engine: out of memory\n"); rc = -1; }
+        else if (runs[s] && !(host[s] = malloc(fields * (size_t)runs[s] * 8))) rc = oom();
         else if (runs[s] && pqps_download(cs, host[s], runs_dev, fields * (size_t)runs[s] * 8, NULL) != PQPS_OK) rc = engine_error("group pair download");
         if (runs_dev) pqps_free(sh->ctx, runs_dev);
         all += runs[s];
@@ -1791,30 +1786,19 @@ static int pair_result_fill(struct hipGroupPairResult *res, const struct hipTabl
         res->keys[j] = calloc(n + 1, sizeof **res->keys);
         res->keyText[j] = calloc(n + 1, sizeof **res->keyText);
     }
-    res->counts = calloc(n + 1, sizeof *res->counts);
-    if (valued) {
-        res->sums = calloc(n + 1, sizeof *res->sums);
-        res->mins = calloc(n + 1, sizeof *res->mins);
-        res->maxs = calloc(n + 1, sizeof *res->maxs);
-    }
-    if (!res->keys[0] || !res->keys[1] || !res->keyText[0] || !res->keyText[1] || !res->counts ||
-        (valued && (!res->sums || !res->mins || !res->maxs))) { fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
-    const uint64_t flip = res->valueKind == HIPKIND_I32 ? 0x8000000000000000ull : 0;
+    if (!res->keys[0] || !res->keys[1] || !res->keyText[0] || !res->keyText[1]) return oom();
+    if (group_arrays_alloc(n, valued, &res->counts, &res->sums, &res->mins, &res->maxs) != 0) return -1;
     for (size_t g = 0; g < n; g++) {
         const uint32_t bin[2] = { (uint32_t)(pr->key[g] >> 32), (uint32_t)pr->key[g] };
         res->numGroups = (int)g + 1;                                     /* (what freeGroupPairResultHIP frees) */
         for (int j = 0; j < 2; j++) {
             char buf[32];
             res->keyText[j][g] = strdup(group_key(t, gp[j]->c, gp[j]->kind, bin[j], gp[j]->lo, &res->keys[j][g], buf, sizeof buf));
-            if (!res->keyText[j][g]) { fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
+            if (!res->keyText[j][g]) return oom();
         }
-        res->counts[g] = pr->cnt[g];
+        group_arrays_set(res->counts, res->sums, res->mins, res->maxs, g, pr->cnt[g], valued ? pr->sum[g] : 0, valued ? pr->mn[g] : 0,
+                         valued ? pr->mx[g] : 0, res->valueKind);
         res->total += (long long)pr->cnt[g];
-        if (valued) {
-            res->sums[g] = (long long)pr->sum[g];
-            res->mins[g] = (long long)(pr->mn[g] ^ flip);
-            res->maxs[g] = (long long)(pr->mx[g] ^ flip);
-        }
     }
     return 0;
 }
@@ -1823,20 +1807,13 @@ struct hipGroupPairResult *executeQueryGroupPairHIP(struct engineS *engine, cons
                                                     const char *valueColumn, struct whereClauseS *whereClause) {
     const double t0 = now_seconds();
     struct hipGroupPairResult *res = calloc(1, sizeof *res);
-    if (!res) { fprintf(stderr, "HIP engine: out of memory\n"); return NULL; }
+    if (!res) { oom(); return NULL; }
     res->groupColumn[0] = res->groupColumn[1] = res->groupKind[0] = res->groupKind[1] = res->valueColumn = res->valueKind = -1;
     if (!engine || !engine->record_block || !groupColumnA || !groupColumnB) { fprintf(stderr, "HIP engine: GROUP BY pair without an engine or two columns\n"); return res; }
     const char *names[2] = { groupColumnA, groupColumnB };
     int c[2], v = -1;
     for (int j = 0; j < 2; j++) if ((c[j] = group_column_id("GROUP BY pair", names[j])) < 0) return res;
-    if (valueColumn) {
-        v = hipColumnId(valueColumn);
-        if (v < 0) { fprintf(stderr, "HIP engine: GROUP BY pair: unknown value column '%s'\n", valueColumn); return res; }
-        if (k_group_kind[v] != HIPKIND_I32 && k_group_kind[v] != HIPKIND_U64) {
-            fprintf(stderr, "HIP engine: GROUP BY pair: %s is a %s column, not a number\n", valueColumn, k_group_kind[v] == HIPKIND_BOOL ? "boolean" : "dictionary");
-            return res;
-        }
-    }
+    if (valueColumn && (v = value_column_id("GROUP BY pair", valueColumn)) < 0) return res;
     struct hipTable *t = engine->record_block;
     if (t->xch) { fprintf(stderr, "HIP engine: GROUP BY pair is not exchanged across ranks\n"); return res; }
     for (int j = 0; j < 2; j++) { res->groupColumn[j] = c[j]; res->groupKind[j] = k_group_kind[c[j]]; }
@@ -1860,9 +1837,8 @@ struct hipGroupPairResult *executeQueryGroupPairHIP(struct engineS *engine, cons
         const uint64_t D = reduced ? (one ? one->n_bins : 1u) : (uint64_t)gp[0].n_bins * gp[1].n_bins;   /* 64 bits: 65 536 x 65 536 = 2^32 */
         if (!reduced && D > HIP_GROUP_MAX_BINS) rc = pair_sparse(&q, &gp[0], &gp[1], v, &pr);
         else {
-            uint64_t *acc = calloc((size_t)(v < 0 ? 1 : 4) * D, sizeof *acc);
-            if (!acc) { fprintf(stderr, "HIP engine: out of memory\n"); rc = -1; }
-            else if (v >= 0) for (uint64_t k = 0; k < D; k++) acc[2 * D + k] = UINT64_MAX;
+            uint64_t *acc = bins_alloc(D, v >= 0);
+            if (!acc) rc = -1;
             if (rc == 0 && !reduced) rc = pair_dense(&q, &gp[0], &gp[1], v, acc);
             else if (rc == 0) {
                 if (!one) { (void)group_plan_column(&q, 0, -1, NULL, "GROUP BY pair", &none); one = &none; }
@@ -1883,10 +1859,7 @@ struct hipGroupPairResult *executeQueryGroupPairHIP(struct engineS *engine, cons
 void freeGroupPairResultHIP(struct hipGroupPairResult *res) {
     if (!res) return;
     for (int j = 0; j < 2; j++) free_group_keys(res->keys[j], res->keyText[j], res->numGroups);
-    free(res->counts);
-    free(res->sums);
-    free(res->mins);
-    free(res->maxs);
+    group_arrays_free(res->counts, res->sums, res->mins, res->maxs);
     free(res);
 }
 
@@ -2213,7 +2186,7 @@ static bool order_is_packed(const struct order_plan *op) { return op->multi && o
 static int order_collect(pqps_ctx *cs, const uint64_t *out_dev, uint64_t n, bool wide, struct order_key *keys, uint64_t *n_keys) {
     if (n == 0) return 0;
     uint64_t *h = malloc((size_t)n * (wide ? 16 : 8));
-    if (!h) { fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
+    if (!h) return oom();
     if (pqps_download(cs, h, out_dev, (size_t)n * (wide ? 16 : 8), NULL) != PQPS_OK) { free(h); return engine_error("ORDER BY download"); }
     for (uint64_t i = 0; i < n; i++) keys[*n_keys + i] = wide ? (struct order_key){ h[2 * i], h[2 * i + 1] } : (struct order_key){ h[i], 0 };
     *n_keys += n;
@@ -2320,7 +2293,7 @@ static int order_sort(struct query *q, const struct order_plan *op, uint64_t wan
         uint64_t *keys_dev = NULL;
         ids[s] = malloc((size_t)take[s] * sizeof **ids);
         if (merge) keys[s] = malloc((size_t)take[s] * (size_t)nk * sizeof **keys);
-        if (!ids[s] || (merge && !keys[s])) { fprintf(stderr, "HIP engine: out of memory\n"); rc = -1; break; }
+        if (!ids[s] || (merge && !keys[s])) { rc = oom(); break; }
         if (pqps_malloc(sh->ctx, n * sizeof(uint32_t), (void **)&ids_dev) != PQPS_OK ||
             (merge && pqps_malloc(sh->ctx, n * (size_t)nk * sizeof(uint64_t), (void **)&keys_dev) != PQPS_OK)) rc = engine_error("ORDER BY buffers");
         else if ((chain ? pqps_sort_list_chain(cs, op->ccol[s], op->csigned, op->cdesc, (uint32_t)nk, query_lane(q, s)->ids_dev, n, (uint32_t)sh->row0,
@@ -2342,7 +2315,7 @@ static int order_sort(struct query *q, const struct order_plan *op, uint64_t wan
     if (rc == 0 && !merge) { out = ids[0]; ids[0] = NULL; }
     else if (rc == 0) {
         out = malloc((size_t)(total ? total : 1) * sizeof *out);
-        if (!out) { fprintf(stderr, "HIP engine: out of memory\n"); rc = -1; }
+        if (!out) rc = oom();
         uint64_t at[HIP_MAX_SHARDS] = { 0 };
         for (uint64_t i = 0; i < total && rc == 0; i++) {              /* (a later shard holds later rows: the keys decide) */
             int best = -1;
@@ -2400,13 +2373,13 @@ static int order_rows(struct engineS *engine, struct whereClauseS *whereClause, 
     if (op->k == 0) return order_sort(q, op, limit > 0 ? (uint64_t)limit : UINT64_MAX, rows, n_rows, matches);
     struct order_key *keys = malloc((size_t)q->n_shards * op->k * sizeof *keys);
     uint64_t n_keys = 0;
-    if (!keys) { fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
+    if (!keys) return oom();
     rc = order_topk(q, op, keys, &n_keys, matches);
     if (rc == 0) {
         qsort(keys, (size_t)n_keys, sizeof *keys, order_key_cmp);
         const uint64_t n = n_keys < op->k ? n_keys : op->k;
         *rows = malloc((size_t)(n ? n : 1) * sizeof **rows);
-        if (!*rows) { fprintf(stderr, "HIP engine: out of memory\n"); rc = -1; }
+        if (!*rows) rc = oom();
         else {
             for (uint64_t i = 0; i < n; i++) (*rows)[i] = order_key_row(&keys[i], op->wide);
             *n_rows = n;
@@ -2530,7 +2503,7 @@ static int project_listed_rows(struct query *q, const uint32_t *rows, uint64_t n
     for (int s = 0; s < n_shards && rc == 0; s++) {
         sub_ids[s] = malloc((size_t)(n ? n : 1) * sizeof **sub_ids);
         sub_pos[s] = malloc((size_t)(n ? n : 1) * sizeof **sub_pos);
-        if (!sub_ids[s] || !sub_pos[s]) { fprintf(stderr, "HIP engine: out of memory\n"); rc = -1; }
+        if (!sub_ids[s] || !sub_pos[s]) rc = oom();
         q->count[s] = 0;
     }
     for (uint64_t i = 0; i < n && rc == 0; i++) {
@@ -2607,7 +2580,7 @@ struct hipColumnarResult *executeQuerySelectOrderedByHIP(struct engineS *engine,
 /* ---- the first row of every group (include/executeEngine-hip.h) ---------------------------------------------------- */
 
 /* One shard's device buffer: [16 B: the matching rows][out: n_bins words][best: n_bins words, command_id only]. */
-struct first_call { const struct group_plan *gp; const struct order_plan *op; uint64_t **buf; };
+struct first_call { const struct group_plan *gp; const struct order_plan *op; void **buf; uint64_t *out, *best, *matches; bool fused; };
 
 static int first_fused_call(struct query *q, int s, pqps_ctx *ctx, void *stream, void *arg) {
     const struct first_call *a = arg;
@@ -2624,58 +2597,47 @@ static int first_fused_call(struct query *q, int s, pqps_ctx *ctx, void *stream,
     return 0;
 }
 
-/* One shard's words h (out[n_bins], then best[n_bins] for command_id) merged into the host's: rows are table-wide, so the
- * minimum word per bin is the answer; command_id compares (best, row). */
-static void first_combine(uint64_t *out, uint64_t *best, const uint64_t *h, uint32_t n_bins, bool wide) {
+static int first_list_call(struct query *q, int s, pqps_ctx *cs, const struct hipLane *L, void *out, void *arg) {
+    const struct first_call *a = arg;
+    const struct group_plan *gp = a->gp;
+    const struct order_plan *op = a->op;
+    const struct hipTable *sh = hipTableShard(q->t, s);
+    const bool grouped = gp->c >= 0 && !gp->single;
+    uint64_t *b = out;
+    return pqps_group_first_list(cs, op->no_key ? NULL : &op->kcol[s], op->key_signed, op->desc, grouped ? &gp->gcol[s] : NULL, gp->bin_base,
+                                 gp->n_bins, sh->n_rows, L->ids_dev, L->count_dev, q->count[s], (uint32_t)sh->row0, b + 2,
+                                 op->wide ? b + 2 + gp->n_bins : NULL, NULL);
+}
+
+/* One shard's buffer merged into the host's words: rows are table-wide, so the minimum word per bin is the answer;
+ * command_id compares (best, row).  The match count in front of the words is added up on the fused path only (a->fused:
+ * the path first_bins gave shard_reduce): the list call does not write it, and first_bins takes the selection's total. */
+static void first_combine(void *arg, const void *host) {
+    const struct first_call *a = arg;
+    const uint32_t n_bins = a->gp->n_bins;
+    const uint64_t *h = (const uint64_t *)host + 2;
+    uint64_t *out = a->out, *best = a->best;
+    if (a->fused) *a->matches += *(const uint64_t *)host;
     for (uint32_t k = 0; k < n_bins; k++) {
         if (h[k] == UINT64_MAX) continue;
-        if (!wide) { if (h[k] < out[k]) out[k] = h[k]; continue; }
+        if (!a->op->wide) { if (h[k] < out[k]) out[k] = h[k]; continue; }
         const uint64_t hb = h[n_bins + k];
         if (out[k] == UINT64_MAX || hb < best[k] || (hb == best[k] && h[k] < out[k])) { out[k] = h[k]; best[k] = hb; }
     }
 }
 
-/* The words of the query on every shard, merged on the host (first_combine) into out[n_bins] (and best[n_bins] for
- * command_id), all ones on entry; *matches = the selection's rows.  gp->fused: pqps_filter_group_first on the query's lane;
- * otherwise the selection, each shard's list left on its own device, and pqps_group_first_list over every list. */
+/* The words of the query on every shard, merged on the host (shard_reduce, first_combine) into out[n_bins] (and best[n_bins]
+ * for command_id), all ones on entry; *matches = the selection's rows: the shards' counts added up by first_combine on the
+ * fused path (pqps_filter_group_first), the selection's total on the list path (pqps_group_first_list). */
 static int first_bins(struct query *q, const struct group_plan *gp, const struct order_plan *op, uint64_t *out, uint64_t *best,
                       uint64_t *matches) {
-    const uint32_t n_bins = gp->n_bins;
-    const size_t bytes = 16 + (size_t)n_bins * (op->wide ? 2 : 1) * sizeof(uint64_t);
-    const bool grouped = gp->c >= 0 && !gp->single;
-    uint64_t *buf[HIP_MAX_SHARDS] = { NULL };
-    uint64_t *host = malloc(bytes);
-    int rc = host ? 0 : -1;
+    void *buf[HIP_MAX_SHARDS];
+    const struct shard_reduce r = { .what = "first-row words", .bytes = 16 + (size_t)gp->n_bins * (op->wide ? 2 : 1) * sizeof(uint64_t),
+                                    .fused = first_fused_call, .list = first_list_call, .combine = first_combine };
+    const bool fused = gp->fused;                                        /* one source for the driver, the combine and the total */
     *matches = 0;
-    if (!host) fprintf(stderr, "HIP engine: out of memory\n");
-    for (int s = 0; s < q->n_shards && rc == 0; s++)
-        if (pqps_malloc(hipTableShard(q->t, s)->ctx, bytes, (void **)&buf[s]) != PQPS_OK) rc = engine_error("first-row buffers");
-    if (rc == 0 && gp->fused) {
-        rc = fused_issue(q, first_fused_call, &(struct first_call){ gp, op, buf });
-        for (int s = 0; s < q->n_shards && rc == 0; s++) {
-            if (hipTableShard(q->t, s)->n_rows == 0) continue;
-            if (pqps_download(lane_copy_ctx(q, s), host, buf[s], bytes, NULL) != PQPS_OK) { rc = engine_error("first-row download"); break; }
-            *matches += host[0];
-            first_combine(out, best, host + 2, n_bins, op->wide);
-        }
-    } else if (rc == 0) {
-        rc = query_lists(q);
-        if (rc == 0) *matches = q->total;
-        for (int s = 0; s < q->n_shards && rc == 0; s++) {
-            struct hipTable *sh = hipTableShard(q->t, s);
-            struct hipLane *L = query_lane(q, s);
-            pqps_ctx *cs = lane_copy_ctx(q, s);
-            if (q->count[s] == 0) continue;
-            if (pqps_group_first_list(cs, op->no_key ? NULL : &op->kcol[s], op->key_signed, op->desc, grouped ? &gp->gcol[s] : NULL,
-                                      gp->bin_base, n_bins, sh->n_rows, L->ids_dev, L->count_dev, q->count[s], (uint32_t)sh->row0,
-                                      buf[s] + 2, op->wide ? buf[s] + 2 + n_bins : NULL, NULL) != PQPS_OK ||
-                pqps_download(cs, host, buf[s], bytes, NULL) != PQPS_OK)
-                rc = engine_error("first-row list");
-            else first_combine(out, best, host + 2, n_bins, op->wide);
-        }
-    }
-    for (int s = 0; s < q->n_shards; s++) if (buf[s]) pqps_free(hipTableShard(q->t, s)->ctx, buf[s]);
-    free(host);
+    const int rc = shard_reduce(q, fused, &r, buf, &(struct first_call){ gp, op, buf, out, best, matches, fused });
+    if (rc == 0 && !fused) *matches = q->total;
     return rc;
 }
 
@@ -2705,7 +2667,7 @@ static int group_first_begin(struct engineS *engine, const char *groupColumn, co
 static int group_first_fill(struct hipGroupFirstResult *res, const struct hipTable *t, const uint64_t *out, const uint64_t *best,
                             uint32_t n_bins, int32_t lo) {
     uint64_t *present = calloc((size_t)n_bins + 1, sizeof *present);
-    if (!present) { fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
+    if (!present) return oom();
     for (uint32_t k = 0; k < n_bins; k++) present[k] = out[k] != UINT64_MAX;
     const int rc = group_keys_fill(t, res->groupColumn, res->groupKind, lo, present, n_bins, &res->keys, &res->keyText, &res->numGroups);
     free(present);
@@ -2714,7 +2676,7 @@ static int group_first_fill(struct hipGroupFirstResult *res, const struct hipTab
     res->rows = calloc(n + 1, sizeof *res->rows);
     res->orderKeys = calloc(n + 1, sizeof *res->orderKeys);
     res->orderText = calloc(n + 1, sizeof *res->orderText);
-    if (!res->rows || !res->orderKeys || !res->orderText) { fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
+    if (!res->rows || !res->orderKeys || !res->orderText) return oom();
     const int oc = res->orderColumn, kind = res->orderKind;
     size_t g = 0;
     for (uint32_t k = 0; k < n_bins; k++) {
@@ -2732,7 +2694,7 @@ static int group_first_fill(struct hipGroupFirstResult *res, const struct hipTab
             else if (res->orderKeys[g] < (long long)t->dict[oc].count) text = t->dict[oc].values[res->orderKeys[g]];
             else { fprintf(stderr, "HIP engine: first row per group: code %lld outside the dictionary\n", res->orderKeys[g]); return -1; }
         }
-        if (!(res->orderText[g] = strdup(text))) { fprintf(stderr, "HIP engine: out of memory\n"); return -1; }
+        if (!(res->orderText[g] = strdup(text))) return oom();
         g++;
     }
     return 0;
@@ -2748,7 +2710,7 @@ static int group_first_run(struct engineS *engine, struct query *q, const char *
     if (rc == 0 && !gp.empty) {
         out = malloc((size_t)gp.n_bins * sizeof *out);
         best = op->wide ? malloc((size_t)gp.n_bins * sizeof *best) : NULL;
-        if (!out || (op->wide && !best)) { fprintf(stderr, "HIP engine: out of memory\n"); rc = -1; }
+        if (!out || (op->wide && !best)) rc = oom();
         else {
             memset(out, 0xFF, (size_t)gp.n_bins * sizeof *out);
             if (best) memset(best, 0xFF, (size_t)gp.n_bins * sizeof *best);
@@ -2780,7 +2742,7 @@ struct hipGroupFirstResult *executeQueryGroupFirstHIP(struct engineS *engine, co
                                                       bool descending, struct whereClauseS *whereClause) {
     const double t0 = now_seconds();
     struct hipGroupFirstResult *res = calloc(1, sizeof *res);
-    if (!res) { fprintf(stderr, "HIP engine: out of memory\n"); return NULL; }
+    if (!res) { oom(); return NULL; }
     struct order_plan op;
     if (group_first_begin(engine, groupColumn, orderColumn, descending, res, &op) != 0) return res;
     struct query q;

@@ -99,9 +99,9 @@ def synth_aggregate(host, ids, value_column, groups):
 SYNTH_GROUPS = (None, "user_name", "risk_level", "sudo_used", "host_name", "base_command", "user_id", "raw_command")
 
 
-def check_synthetic(n, chains=grp.SYNTH_CHAINS, groups=SYNTH_GROUPS, values=VALUES):
+def check_synthetic(n, chains=grp.SYNTH_CHAINS, groups=SYNTH_GROUPS, values=VALUES, indexes=()):
     host = q.HostSynth(n, full=True)
-    eng = pq.HipEngine.synthetic(n)
+    eng = pq.HipEngine.synthetic(n, indexes=indexes)
     try:
         for cname, chain in chains.items():
             ids = host.oracle_scan(chain or [], nthreads=min(16, os.cpu_count() or 1))
@@ -111,8 +111,10 @@ def check_synthetic(n, chains=grp.SYNTH_CHAINS, groups=SYNTH_GROUPS, values=VALU
                 for value in values:
                     got = eng.aggregate(value, column, chain)
                     assert got == synth_aggregate(host, ids, value, g), (n, cname, value, column)
-                    if cname == "nothing":
+                    if cname.endswith("nothing"):
                         assert got == []
+            if cname == "probe_ge1":
+                assert len(ids) == n
     finally:
         eng.close()
 
@@ -121,6 +123,14 @@ def check_synthetic(n, chains=grp.SYNTH_CHAINS, groups=SYNTH_GROUPS, values=VALU
 @pytest.mark.parametrize("n", [1, 1023, 1024, 1025, 65537, (1 << 20) + 3])
 def test_synthetic_small(n):
     check_synthetic(n)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [1, 1025])
+def test_synthetic_index_probes(n):
+    """WHEREs the risk_level index probes are not fused: the selection's per-shard lists and the list kernels.  Over two
+    shards (test_over_shards) the one-row table leaves the second shard without rows."""
+    check_synthetic(n, chains=grp.PROBED_CHAINS, indexes=grp.PROBE_INDEXES)
 
 
 @pytest.mark.gpu
@@ -241,7 +251,7 @@ def test_over_shards():
     devices = "0,1" if pq.lib().pqps_device_count() >= 2 else "0,0"
     env = dict(os.environ, PQPS_DEVICES=devices)
     p = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", "-p", "no:cacheprovider", __file__,
-                        "-k", "golden_csv or synthetic_small or insert_and_delete or int32_max or command_id_unsigned"],
+                        "-k", "golden_csv or synthetic_small or synthetic_index_probes or insert_and_delete or int32_max or command_id_unsigned"],
                        capture_output=True, text=True, timeout=1500, env=env, cwd=str(q.ROOT))
     assert p.returncode == 0, (devices, p.stdout[-3000:], p.stderr[-2000:])
     assert " passed" in p.stdout and "skipped" not in p.stdout

@@ -204,13 +204,11 @@ def test_more_than_65536_timestamps():
 SYNTH_CHAINS = {k: grp.SYNTH_CHAINS[k] for k in ("s1", "risk_gt2", "nothing", "or_tree")}
 
 
-@pytest.mark.gpu
-def test_synthetic_engine():
-    n = (1 << 20) + 3
+def check_synthetic_engine(n, chains=SYNTH_CHAINS, indexes=()):
     host = q.HostSynth(n, full=True)
-    eng = pq.HipEngine.synthetic(n)
+    eng = pq.HipEngine.synthetic(n, indexes=indexes)
     try:
-        for cname, chain in SYNTH_CHAINS.items():
+        for cname, chain in chains.items():
             rows = host.oracle_scan(chain or [], nthreads=min(16, os.cpu_count() or 1))
             mask = np.zeros(n, bool)
             mask[rows] = True
@@ -230,16 +228,38 @@ def test_synthetic_engine():
             risk = host.arr["risk_level"][rows].astype(np.int64)
             want = [(raw, len(rows), int(risk.sum()), int(risk.min()), int(risk.max()))] if len(rows) else []
             assert eng.group_buckets("raw_command", prefix=3, value_column="risk_level", chain=chain) == want, cname
-            if cname == "nothing":
+            if cname.endswith("nothing"):
                 assert len(rows) == 0
+            if cname == "probe_ge1":
+                assert len(rows) == n
     finally:
         eng.close()
 
 
 @pytest.mark.gpu
+def test_synthetic_engine():
+    check_synthetic_engine((1 << 20) + 3)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [1, 1025])
+def test_synthetic_engine_small(n):
+    """One row: over two shards one of them has no rows at all.  These WHEREs are fused."""
+    check_synthetic_engine(n)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [1, 1025])
+def test_synthetic_engine_index_probes(n):
+    """WHEREs the risk_level index probes are not fused: the selection's per-shard lists and the list kernels.  Over two
+    shards (test_over_shards) the one-row table leaves the second shard without rows."""
+    check_synthetic_engine(n, chains=grp.PROBED_CHAINS, indexes=grp.PROBE_INDEXES)
+
+
+@pytest.mark.gpu
 def test_over_shards():
     """The CSV, wide-dictionary, synthetic and writer cases again with the rows split over two shards of one card (a child
-    process: the engine reads PQPS_DEVICES when it is created)."""
+    process: the engine reads PQPS_DEVICES when it is created).  The one-row table leaves the second shard empty."""
     env = dict(os.environ, PQPS_DEVICES="0,0")
     p = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", "-p", "no:cacheprovider", __file__,
                         "-k", "golden_csv or more_than_65536 or synthetic_engine or writers"],

@@ -31,6 +31,13 @@ SYNTH_CHAINS = {
     "nothing": [("risk_level", ">", "9")],
     "or_tree": [("sudo_used", "=", "TRUE"), "OR", [("risk_level", "=", "5"), "AND", ("shell_type", "=", "bash")]],
 }
+# with PROBE_INDEXES each is one probe of the risk_level index (every row, some rows, none): the list path, never fused
+PROBE_INDEXES = [("risk_level", 1)]
+PROBED_CHAINS = {
+    "probe_ge1": [("risk_level", ">=", "1")],
+    "probe_gt2": [("risk_level", ">", "2")],
+    "probe_nothing": [("risk_level", ">", "9")],
+}
 
 
 def key_order(column, text):
@@ -128,9 +135,9 @@ def synth_expected(host, chain, column):
     return out, len(ids)
 
 
-def check_synthetic(n, chains=SYNTH_CHAINS, columns=SYNTH_GROUPS):
+def check_synthetic(n, chains=SYNTH_CHAINS, columns=SYNTH_GROUPS, indexes=()):
     host = q.HostSynth(n, full=True)
-    eng = pq.HipEngine.synthetic(n)
+    eng = pq.HipEngine.synthetic(n, indexes=indexes)
     try:
         for cname, chain in chains.items():
             for column in columns:
@@ -138,8 +145,10 @@ def check_synthetic(n, chains=SYNTH_CHAINS, columns=SYNTH_GROUPS):
                 got = eng.group_count(column, chain)
                 assert got == want, (n, cname, column)
                 assert sum(c for _, c in got) == k == eng.count(chain or [])
-                if cname == "nothing":
+                if cname.endswith("nothing"):
                     assert got == []
+                if cname == "probe_ge1":
+                    assert k == n
     finally:
         eng.close()
 
@@ -148,6 +157,14 @@ def check_synthetic(n, chains=SYNTH_CHAINS, columns=SYNTH_GROUPS):
 @pytest.mark.parametrize("n", [1, 1023, 1024, 1025, 65537, (1 << 20) + 3])
 def test_synthetic_small(n):
     check_synthetic(n)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [1, 1025])
+def test_synthetic_index_probes(n):
+    """WHEREs the risk_level index probes are not fused: the selection's per-shard lists and the list kernels.  Over two
+    shards (test_over_shards) the one-row table leaves the second shard without rows."""
+    check_synthetic(n, chains=PROBED_CHAINS, indexes=PROBE_INDEXES)
 
 
 @pytest.mark.gpu
@@ -184,7 +201,7 @@ def test_over_shards():
     devices = "0,1" if pq.lib().pqps_device_count() >= 2 else "0,0"
     env = dict(os.environ, PQPS_DEVICES=devices)
     p = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", "-p", "no:cacheprovider", __file__,
-                        "-k", "golden_csv or synthetic_small or insert_and_delete or wide_dictionary"],
+                        "-k", "golden_csv or synthetic_small or synthetic_index_probes or insert_and_delete or wide_dictionary"],
                        capture_output=True, text=True, timeout=1500, env=env, cwd=str(q.ROOT))
     assert p.returncode == 0, (devices, p.stdout[-3000:], p.stderr[-2000:])
     assert " passed" in p.stdout and "skipped" not in p.stdout

@@ -54,6 +54,28 @@ def where_value(column, text):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("n", [1, 1025])
+def test_synthetic_index_probes(n):
+    """WHEREs the risk_level index probes are not fused: the selection's per-shard lists and the list kernels.  Over two
+    shards (test_over_shards) the one-row table leaves the second shard without rows: the total is the
+    selection's there, never the unwritten count in front of a shard's words."""
+    host = q.HostSynth(n, full=True)
+    eng = pq.HipEngine.synthetic(n, indexes=grp.PROBE_INDEXES)
+    try:
+        for cname, chain in grp.PROBED_CHAINS.items():
+            rows = np.asarray(host.oracle_scan(chain, nthreads=min(16, os.cpu_count() or 1)), dtype=np.int64)
+            assert len(rows) == {"probe_ge1": n, "probe_nothing": 0}.get(cname, len(rows))
+            for group in ("user_name", "risk_level", "sudo_used", None):
+                for column in ("timestamp", "command_id", "exit_code", "user_name"):
+                    for desc in (False, True):
+                        got, total = eng.group_first(group, column, chain, desc)
+                        assert total == len(rows), (n, cname, group, column, desc)
+                        assert got == m.synth_expected(host, rows, group, column, desc), (n, cname, group, column, desc)
+    finally:
+        eng.close()
+
+
+@pytest.mark.gpu
 def test_equals_order_ids_limit_1_of_the_group():
     """The consequence the header states: rows[g] is the first row of order_ids(WHERE AND group = key, limit 1)."""
     eng = pq.HipEngine(CSV2K, [])
@@ -227,11 +249,12 @@ def test_extreme_on_the_last_rows():
 @pytest.mark.gpu
 def test_over_shards():
     """Two shards on one card (a child process: the engine reads PQPS_DEVICES when it is created): the extreme of every group
-    on the second shard, a synthetic table, the bins at the LDS switch, the writers and the projection again."""
+    on the second shard, synthetic tables (the one-row table leaves the second shard empty), the bins at the LDS switch, the
+    writers and the projection again."""
     devices = "0,1" if pq.lib().pqps_device_count() >= 2 else "0,0"
     env = dict(os.environ, PQPS_DEVICES=devices)
     p = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", "-p", "no:cacheprovider", __file__,
-                        "-k", "extreme_on_the_last_rows or 65537 or lds_switch or after_writers or select_group_first"],
+                        "-k", "extreme_on_the_last_rows or test_synthetic[1] or test_synthetic[1025] or synthetic_index_probes or 65537 or lds_switch or after_writers or select_group_first"],
                        capture_output=True, text=True, timeout=1500, env=env, cwd=str(q.ROOT))
     assert p.returncode == 0, (devices, p.stdout[-3000:], p.stderr[-2000:])
     assert " passed" in p.stdout and "skipped" not in p.stdout

@@ -82,6 +82,9 @@ def test_golden_csv_every_chain(indexes):
         eng.close()
 
 
+SYNTH_CHAINS = {**grp.SYNTH_CHAINS, **grp.PROBED_CHAINS}
+
+
 @functools.lru_cache(maxsize=2)
 def synth_host(n):
     return q.HostSynth(n, full=True)
@@ -89,7 +92,7 @@ def synth_host(n):
 
 @functools.lru_cache(maxsize=8)
 def synth_ids(n, cname):
-    return synth_host(n).oracle_scan(grp.SYNTH_CHAINS[cname] or [], nthreads=min(16, os.cpu_count() or 1))
+    return synth_host(n).oracle_scan(SYNTH_CHAINS[cname] or [], nthreads=min(16, os.cpu_count() or 1))
 
 
 def synth_expected(host, ids, pair, value):
@@ -98,18 +101,20 @@ def synth_expected(host, ids, pair, value):
                                 host.arr[value][ids] if value else None, value == "command_id")
 
 
-def check_synthetic(n, pair, chains=tuple(grp.SYNTH_CHAINS), values=SYNTH_VALUES):
+def check_synthetic(n, pair, chains=tuple(grp.SYNTH_CHAINS), values=SYNTH_VALUES, indexes=()):
     host = synth_host(n)
-    eng = pq.HipEngine.synthetic(n)
+    eng = pq.HipEngine.synthetic(n, indexes=indexes)
     try:
         for cname in chains:
             ids = synth_ids(n, cname)
             for value in values:
-                got, total, _ = eng.group_pair_total(pair, value, grp.SYNTH_CHAINS[cname])
+                got, total, _ = eng.group_pair_total(pair, value, SYNTH_CHAINS[cname])
                 assert got == synth_expected(host, ids, pair, value), (n, cname, pair, value)
                 assert total == len(ids)
-                if cname == "nothing":
+                if cname.endswith("nothing"):
                     assert got == []
+                if cname == "probe_ge1":
+                    assert total == n
     finally:
         eng.close()
 
@@ -119,6 +124,16 @@ def check_synthetic(n, pair, chains=tuple(grp.SYNTH_CHAINS), values=SYNTH_VALUES
 @pytest.mark.parametrize("n", [1, 1023, 1024, 1025, 65537, (1 << 20) + 3])
 def test_synthetic_small(n, pair):
     check_synthetic(n, pair)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("pair", SYNTH_PAIRS[:4] + SYNTH_PAIRS[5:6], ids=["x".join(p) for p in SYNTH_PAIRS[:4] + SYNTH_PAIRS[5:6]])
+@pytest.mark.parametrize("n", [1, 1025])
+def test_synthetic_index_probes(n, pair):
+    """WHEREs the risk_level index probes are not fused: the selection's per-shard lists and the list kernels.  Over two
+    shards (test_over_shards) the one-row table leaves the second shard without rows.  The pairs: the dense forms,
+    one sort and the one-column form of a single-valued column."""
+    check_synthetic(n, pair, chains=tuple(grp.PROBED_CHAINS), indexes=grp.PROBE_INDEXES)
 
 
 LARGE_PAIRS = (("host_name", "shell_type"), ("user_name", "sudo_used"), ("user_name", "host_name"), ("user_name", "base_command"))
@@ -351,11 +366,12 @@ def test_insert_and_delete(tmp_path):
 def test_over_shards():
     """The CSV (dense fused, dense list through the index probes), small synthetic tables (every path, the sort included) and
     INSERT / DELETE again with the rows split over two shards of one card, so that most pairs have rows in both shards: their
-    counts and sums must be added, their min / max merged (a child process: the engine reads PQPS_DEVICES when it is created)."""
+    counts and sums must be added, their min / max merged (a child process: the engine reads PQPS_DEVICES when it is created).
+    The one-row tables leave the second shard empty."""
     devices = "0,1" if pq.lib().pqps_device_count() >= 2 else "0,0"
     env = dict(os.environ, PQPS_DEVICES=devices)
     p = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", "-p", "no:cacheprovider", __file__,
-                        "-k", "golden_csv or (synthetic_small and 65537) or insert_and_delete or product_of_two or few_hundred"],
+                        "-k", "golden_csv or (synthetic_small and (65537 or [1- or [1025-)) or synthetic_index_probes or insert_and_delete or product_of_two or few_hundred"],
                        capture_output=True, text=True, timeout=1500, env=env, cwd=str(q.ROOT))
     assert p.returncode == 0, (devices, p.stdout[-3000:], p.stderr[-2000:])
     assert " passed" in p.stdout and "skipped" not in p.stdout
