@@ -14,12 +14,14 @@ Readers, each computed without the engine.  The rows of a chain in scan mode com
 chain_true of tests/test_gpu_set_predicates.py.  select_ids with indexes is the oracle's own walk (orc_select_ids_v) over a
 `record` array filled from the model (RecordTable: an OracleTable over records instead of a CSV, its perms from
 orc_index_build): rows in probe order, once per probe.  Every other form is folded from the model's cells over those rows by
-the reference folds the suite already has.  tests/test_column_model.py checks all of it on the CPU against the golden ID lists
+the reference folds the suite already has; group_first is group_first_model.first_rows and order_ids_by Python's stable
+`sorted` once per key, both over the order-preserving codes (tests/test_gpu_many_shards.py checks the two row by row).  tests/test_column_model.py checks all of it on the CPU against the golden ID lists
 and the folds taken over OracleTable(csv)."""
 import ctypes as C
 
 import numpy as np
 
+import group_first_model as gfm
 import qpelib as q
 import test_gpu_count_distinct as cd
 import test_gpu_group_buckets as gb
@@ -419,13 +421,14 @@ class ColumnModel:
         k = q.load_oracle().orc_scan_columns(C.byref(self.orc_columns()), wl.ptr, 0, out.ctypes.data_as(C.POINTER(C.c_uint32)), self.n, 1)
         return out[:k].astype(np.int64)
 
-    def select_ids(self, chain, indexes=()):
-        """executeQuerySelectIdsHIP: scan mode without a probe, otherwise the probes' rows in probe order, re-filtered."""
+    def select_ids(self, chain, indexes=(), probe_bool=False):
+        """executeQuerySelectIdsHIP: scan mode without a probe, otherwise the probes' rows in probe order, re-filtered
+        (probe_bool: the walk of an engine under PQPS_PROBE_BOOL=1, BOOL indexes probed too)."""
         if not indexes or not chain:
             return self.scan_rows(chain).tolist()
         if not has_set_leaf(chain):
-            return self.table(indexes).select_ids(chain)[0]
-        ids = self.table(indexes).select_ids(without_set_leaves(chain))[0]
+            return self.table(indexes).select_ids(chain, probe_bool=probe_bool)[0]
+        ids = self.table(indexes).select_ids(without_set_leaves(chain), probe_bool=probe_bool)[0]
         mask = self.python_mask(chain)
         return [r for r in ids if mask[r]]
 
@@ -466,6 +469,26 @@ class ColumnModel:
         cells = self.cells(column)
         values = self.numbers(value_column) if value_column else None
         return gb.fold([cells[r] for r in ids], [values[r] for r in ids] if value_column else None, prefix, width, value_column)
+
+    def group_first(self, group_column, order_column, ids, descending=False):
+        """executeQueryGroupFirstHIP: ([(key_text or None, row, order_text), ...] in key order, len(ids)) -- per group the
+        candidate that comes first by (order key, row): group_first_model.first_rows over the order-preserving codes."""
+        rows = np.asarray(ids, dtype=np.int64)
+        groups = self.codes(group_column)[rows] if group_column else None
+        _, first, _ = gfm.first_rows(rows, self.codes(order_column)[rows], groups, descending)
+        gcells, ocells = self.cells(group_column) if group_column else None, self.cells(order_column)
+        return [(gcells[r] if group_column else None, r, ocells[r]) for r in first.tolist()], len(ids)
+
+    def order_ids_by(self, keys, ids, limit=None):
+        """executeQueryOrderIdsByHIP: (rows, len(ids)) -- `keys` column names or (column, descending) pairs, the first the
+        most significant; rows equal in all keys in ascending row number.  Python's stable `sorted`, once per key from the
+        last to the first, over each key's order-preserving integers (no key is packed)."""
+        pairs = [(k, False) if isinstance(k, (str, bytes)) else (k[0], bool(k[1])) for k in keys]
+        rows = sorted(ids)
+        for column, descending in reversed(pairs):
+            image = self.codes(column).tolist()
+            rows = sorted(rows, key=image.__getitem__, reverse=descending)
+        return ob.cut(rows, limit), len(ids)
 
     def project(self, ids, columns=None):
         cells = [self.cells(c) for c in (columns or pq.COLUMNS)]

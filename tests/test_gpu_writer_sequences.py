@@ -10,8 +10,9 @@ cached before the writers that leave them.
 
 After every step check() asks select_ids and count over the 26 chains of test_gpu_insert_batch.py, group_count, aggregate,
 count_distinct (a bitmap shape and command_id: the sort form), order_ids, group_pair (dense, and the sort form once the product
-of user_name x host_name exceeds 65 536), group_buckets, select_ordered, the cells of select_columnar and three tickets in
-flight at once -- and compares each answer exactly.  A refusal the model predicts (a writer the engine cannot make in place; a
+of user_name x host_name exceeds 65 536), group_buckets, select_ordered, group_first (a narrow key and command_id), order_ids_by
+(two keys), select_group_first, the cells of select_columnar and three tickets in flight at once -- and compares each answer
+exactly.  A refusal the model predicts (a writer the engine cannot make in place; a
 group column of more than 65 536 values) must be a refusal."""
 import ctypes as C
 import os
@@ -34,6 +35,7 @@ INDEXES = ib.HOST_INDEX
 REFUSED = "refused"
 SEVEN = [b"student%d" % i for i in (1000, 1004, 1008, 1012, 1016, 1020, 1024)]
 STAMP3, DIR2 = b"2024-12-31T23:59:59.000Z", b"/tmp"
+ORDER_KEYS = [("user_name", True), ("exit_code", False)]
 
 
 def ask(call):
@@ -101,6 +103,16 @@ def queries(model, eng=None):
         return model.project(order), matches
 
     out.append((("ordered",), lambda: columnar_rows(lambda: eng.select_ordered(None, CHAINS[1], "user_name", True, 25), eng), ordered_model))
+    for group, column, k, desc in (("user_name", "exit_code", 0, False), ("shell_type", "command_id", 2, True)):
+        out.append((("first", group, column, k, desc), lambda group=group, column=column, k=k, desc=desc: eng.group_first(group, column, CHAINS[k], desc),
+                    grouped([group], lambda group=group, column=column, k=k, desc=desc: model.group_first(group, column, rows(k), desc))))
+    out.append((("order by", 5), lambda: eng.order_ids_by(ORDER_KEYS, CHAINS[5], 60), lambda: model.order_ids_by(ORDER_KEYS, rows(5), 60)))
+
+    def first_model():
+        groups, total = model.group_first("risk_level", "host_name", rows(6), True)
+        return model.project([r for _, r, _ in groups]), total
+
+    out.append((("first rows",), lambda: columnar_rows(lambda: eng.select_group_first(None, CHAINS[6], "risk_level", "host_name", True), eng), first_model))
     for k in (4, ib.CELLS):
         out.append((("cells", k), lambda k=k: columnar_rows(lambda: eng.select_columnar(None, CHAINS[k]), eng)[0], lambda k=k: model.project(rows(k))))
     return out
