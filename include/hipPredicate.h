@@ -195,6 +195,10 @@ struct hipOrderKeyPlan {
 int hipOrderKeyPlan(const char *const *columns, const int *descending, int n_keys, const int *dict_counts,
                     const int *lo, const int *hi, struct hipOrderKeyPlan *plan);
 
+/* The number of values[0 .. count) (ascending in strcmp order) below `text`: its code when it is in the dictionary
+ * (*present = 1), the rank it is inserted at otherwise (*present = 0). */
+int hipDictionaryRank(const char *const *values, int count, const char *text, int *present);
+
 /* Column name -> HIPCOL_* id, -1 if unknown. */
 int hipColumnId(const char *name);
 

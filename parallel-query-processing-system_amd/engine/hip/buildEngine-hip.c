@@ -894,6 +894,45 @@ static void rebuild_indexes(struct engineS *engine, struct hipTable *t) {
     for (int i = 0; i < engine->num_indexes; i++) rebuild_index(engine, t, i);
 }
 
+/* ... and those on the columns of `mask` (bit c: column c) that have a buffer on this shard. */
+static void rebuild_indexes_of(struct engineS *engine, struct hipTable *sh, uint32_t mask) {
+    for (int i = 0; i < engine->num_indexes; i++) {
+        const int c = sh->index[i].column >= 0 ? sh->index[i].column : hipColumnId(engine->indexed_attributes[i]);
+        if (c >= 0 && sh->col[c].data && (mask & (1u << c))) rebuild_index(engine, sh, i);
+    }
+}
+
+/* What the writers share.  The codes a column of `width` bytes per row can number: */
+static uint64_t code_limit(uint32_t width) { return width == 0 ? 1 : width == 1 ? 256 : width == 2 ? 65536 : 0xFFFFFFFFull; }
+
+/* a known cached range of column c widened to cover [lo, hi] (an unknown one is computed from the rows when it is asked for): */
+static void bounds_cover(struct hipTable *t, int c, int32_t lo, int32_t hi) {
+    if (!t->bounds_known[c]) return;
+    if (lo < t->bounds_lo[c]) t->bounds_lo[c] = lo;
+    if (hi > t->bounds_hi[c]) t->bounds_hi[c] = hi;
+}
+
+/* a string that is new to a dictionary, at its rank `pos`, as a copy of the dictionary's own; */
+static void dictionary_insert(struct hipDictionary *d, size_t pos, const char *text) {
+    const char **grown = realloc(d->values, ((size_t)d->count + 1) * sizeof *grown);
+    char *copy = strdup(text);
+    if (!grown || !copy) { perror("Failed to grow dictionary"); exit(EXIT_FAILURE); }
+    d->values = grown;
+    memmove(&d->values[pos + 1], &d->values[pos], ((size_t)d->count - pos) * sizeof *grown);
+    d->values[pos] = copy;
+    d->count++;
+}
+
+/* and the same for column c of a table: the codes at or above the rank make room on every shard, so they stay ranks. */
+static void table_insert_string(struct hipTable *t, int c, size_t pos, const char *text) {
+    dictionary_insert(&t->dict[c], pos, text);
+    for (int s = 0; s < hipTableShards(t); s++) {
+        struct hipTable *sh = hipTableShard(t, s);
+        if (pqps_bump_codes(sh->ctx, (void *)sh->col[c].data, sh->col[c].width, sh->n_rows, (uint32_t)pos, NULL) != PQPS_OK)
+            hip_die("dictionary code shift");
+    }
+}
+
 /* INSERT: appends the last host row (engine->all_records[n-1]) to the device columns of the last shard
  * in place.  A string value that is new to its dictionary is inserted at its rank and the codes at or
  * above that rank are bumped on every shard (order-preserving codes stay order-preserving).
@@ -911,14 +950,8 @@ bool appendRowDeviceTableHIP(struct engineS *engine, const record *r) {
     int pos[HIPCOL_COUNT], present[HIPCOL_COUNT];
     for (int c = 0; c < HIPCOL_COUNT; c++) {
         if (k_kind[c] != HIPKIND_DICT) continue;
-        struct hipDictionary *d = &t->dict[c];
-        const char *s = (const char *)r + k_offset[c];
-        int l = 0, h = d->count;
-        while (l < h) { const int m = l + (h - l) / 2; if (strcmp(d->values[m], s) < 0) l = m + 1; else h = m; }
-        pos[c] = l;
-        present[c] = l < d->count && strcmp(d->values[l], s) == 0;
-        const uint64_t limit = t->col[c].width == 0 ? 1 : t->col[c].width == 1 ? 256 : t->col[c].width == 2 ? 65536 : 0xFFFFFFFFull;
-        if (!present[c] && (uint64_t)d->count + 1 > limit) REBUILD_OR_FAIL();
+        pos[c] = hipDictionaryRank(t->dict[c].values, t->dict[c].count, (const char *)r + k_offset[c], &present[c]);
+        if (!present[c] && (uint64_t)t->dict[c].count + 1 > code_limit(t->col[c].width)) REBUILD_OR_FAIL();
     }
 #undef REBUILD_OR_FAIL
     bool bumped = false;
@@ -930,32 +963,13 @@ bool appendRowDeviceTableHIP(struct engineS *engine, const record *r) {
         case HIPKIND_U64: value = *(const uint64_t *)p; break;
         case HIPKIND_I32:
             value = (uint32_t)*(const int *)p;
-            if (t->bounds_known[c]) {                           /* a cached group range covers the new row */
-                if (*(const int *)p < t->bounds_lo[c]) t->bounds_lo[c] = *(const int *)p;
-                if (*(const int *)p > t->bounds_hi[c]) t->bounds_hi[c] = *(const int *)p;
-            }
+            bounds_cover(t, c, *(const int *)p, *(const int *)p);       /* a cached group range covers the new row */
             break;
         case HIPKIND_BOOL: value = *(const bool *)p ? 1 : 0; break;
-        default: {
-            struct hipDictionary *d = &t->dict[c];
-            if (!present[c]) {
-                const char **grown = realloc(d->values, ((size_t)d->count + 1) * sizeof *grown);
-                char *copy = strdup(p);
-                if (!grown || !copy) { perror("Failed to grow dictionary"); exit(EXIT_FAILURE); }
-                d->values = grown;
-                memmove(&d->values[pos[c] + 1], &d->values[pos[c]], ((size_t)d->count - (size_t)pos[c]) * sizeof *grown);
-                d->values[pos[c]] = copy;
-                d->count++;
-                for (int s = 0; s < n_shards; s++) {
-                    struct hipTable *sh = hipTableShard(t, s);
-                    if (pqps_bump_codes(sh->ctx, (void *)sh->col[c].data, w, sh->n_rows, (uint32_t)pos[c], NULL) != PQPS_OK)
-                        hip_die("dictionary code shift");
-                }
-                bumped = true;
-            }
+        default:
+            if (!present[c]) { table_insert_string(t, c, (size_t)pos[c], p); bumped = true; }
             value = (uint64_t)pos[c];
             break;
-        }
         }
         if (w && pqps_upload(last->ctx, (char *)last->col[c].data + last->n_rows * w, &value, w, NULL) != PQPS_OK) hip_die("row upload");
     }
@@ -967,8 +981,6 @@ bool appendRowDeviceTableHIP(struct engineS *engine, const record *r) {
 }
 
 /* UPDATE: see include/buildEngine-hip.h. */
-static uint64_t code_limit(uint32_t width) { return width == 0 ? 1 : width == 1 ? 256 : width == 2 ? 65536 : 0xFFFFFFFFull; }
-
 bool updateNeedsRebuildHIP(struct engineS *engine, const struct hipAssignment *a, int n) {
     const struct hipTable *t = engine->record_block;
     for (int i = 0; i < n; i++) {
@@ -983,22 +995,8 @@ uint32_t updateInsertStringsHIP(struct engineS *engine, const struct hipAssignme
     uint32_t bumped = 0;
     for (int i = 0; i < n; i++) {
         if (a[i].kind != HIPKIND_DICT || a[i].present) continue;
-        const int c = a[i].column;
-        struct hipDictionary *d = &t->dict[c];
-        const size_t pos = a[i].rank;
-        const char **grown = realloc(d->values, ((size_t)d->count + 1) * sizeof *grown);
-        char *copy = strdup(a[i].text);
-        if (!grown || !copy) { perror("Failed to grow dictionary"); exit(EXIT_FAILURE); }
-        d->values = grown;
-        memmove(&d->values[pos + 1], &d->values[pos], ((size_t)d->count - pos) * sizeof *grown);
-        d->values[pos] = copy;
-        d->count++;
-        for (int s = 0; s < hipTableShards(t); s++) {
-            struct hipTable *sh = hipTableShard(t, s);
-            if (pqps_bump_codes(sh->ctx, (void *)sh->col[c].data, sh->col[c].width, sh->n_rows, (uint32_t)pos, NULL) != PQPS_OK)
-                hip_die("dictionary code shift");
-        }
-        bumped |= 1u << c;
+        table_insert_string(t, a[i].column, a[i].rank, a[i].text);
+        bumped |= 1u << a[i].column;
     }
     return bumped;
 }
@@ -1019,22 +1017,14 @@ void finishUpdateDeviceTableHIP(struct engineS *engine, const struct hipAssignme
     uint64_t total = 0;
     for (int s = 0; s < hipTableShards(t); s++) total += matched[s];
     for (int i = 0; i < n; i++) {
-        const int c = a[i].column;
-        assigned |= 1u << c;
-        if (a[i].kind == HIPKIND_I32 && total && t->bounds_known[c]) {     /* a cached group range covers the new value */
-            const int32_t v = (int32_t)(uint32_t)a[i].value;
-            if (v < t->bounds_lo[c]) t->bounds_lo[c] = v;
-            if (v > t->bounds_hi[c]) t->bounds_hi[c] = v;
-        }
+        const int32_t v = (int32_t)(uint32_t)a[i].value;
+        assigned |= 1u << a[i].column;
+        if (a[i].kind == HIPKIND_I32 && total) bounds_cover(t, a[i].column, v, v);     /* a cached group range covers the new value */
     }
     for (int s = 0; s < hipTableShards(t); s++) {
         struct hipTable *sh = hipTableShard(t, s);
         if (matched[s] && (assigned & (1u << HIPCOL_SUDO_USED))) shard_pack_all_bits(sh);
-        for (int i = 0; i < engine->num_indexes; i++) {
-            const int c = sh->index[i].column >= 0 ? sh->index[i].column : hipColumnId(engine->indexed_attributes[i]);
-            if (c < 0 || !sh->col[c].data) continue;
-            if ((bumped & (1u << c)) || (matched[s] && (assigned & (1u << c)))) rebuild_index(engine, sh, i);
-        }
+        rebuild_indexes_of(engine, sh, bumped | (matched[s] ? assigned : 0));
     }
 }
 
@@ -1598,10 +1588,7 @@ void commitAppendHIP(struct engineS *engine, struct hipAppend *b) {
         const uint32_t w = last->col[c].width;
         if (!w) continue;
         if (pqps_copy_peer(last->ctx, (char *)last->col[c].data + first_new * w, last->ctx, b->stage[c], B * w, NULL) != PQPS_OK) hip_die("row copy");
-        if (b->have_bounds[c] && t->bounds_known[c]) {             /* a cached group range covers the new rows */
-            if (b->lo[c] < t->bounds_lo[c]) t->bounds_lo[c] = b->lo[c];
-            if (b->hi[c] > t->bounds_hi[c]) t->bounds_hi[c] = b->hi[c];
-        }
+        if (b->have_bounds[c]) bounds_cover(t, c, b->lo[c], b->hi[c]);     /* a cached group range covers the new rows */
     }
     if (pqps_ctx_sync(last->ctx, NULL) != PQPS_OK) hip_die("row copy");
     last->n_rows += B;
@@ -1617,14 +1604,7 @@ void commitAppendHIP(struct engineS *engine, struct hipAppend *b) {
         t->dict[c] = d;
     }
     /* 5. the indexes, once: all of the last shard's, elsewhere those whose keys changed */
-    for (int s = 0; s < n_shards; s++) {
-        struct hipTable *sh = hipTableShard(t, s);
-        for (int i = 0; i < engine->num_indexes; i++) {
-            const int c = sh->index[i].column >= 0 ? sh->index[i].column : hipColumnId(engine->indexed_attributes[i]);
-            if (c < 0 || !sh->col[c].data) continue;
-            if (sh == last || (changed & (1u << c))) rebuild_index(engine, sh, i);
-        }
-    }
+    for (int s = 0; s < n_shards; s++) rebuild_indexes_of(engine, hipTableShard(t, s), s == n_shards - 1 ? ~0u : changed);
     engine->num_records += (int)B;
     discardAppendHIP(engine, b);
 }

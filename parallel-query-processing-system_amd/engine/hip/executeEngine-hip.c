@@ -3196,6 +3196,50 @@ static void write_csv_table(FILE *f, const record *rows, size_t n) {
     }
 }
 
+/* n rows into the engine's CSV, opened in `mode`: "a" behind the rows it holds, "w" in their place (S:683-701: no header
+ * written).  false: the file cannot be opened. */
+static bool csv_write_rows(const struct engineS *engine, const char *mode, const record *rows, size_t n) {
+    FILE *f = fopen(engine->datafile, mode);
+    if (!f) return false;
+    write_csv_table(f, rows, n);
+    fclose(f);
+    return true;
+}
+
+/* Room for `total` host rows in row_block and all_records[], all_records[i] == &row_block[i] for the rows there are.  The
+ * store grows geometrically; all_records[] is re-pointed only when the block moved, and at once: the table is whole even
+ * when the second allocation fails (-1, as when the first does). */
+static int host_rows_reserve(struct engineS *engine, struct hipTable *t, size_t total) {
+    if (total <= t->row_capacity) return 0;
+    const size_t n = (size_t)engine->num_records, cap = total + total / 8 + 64;
+    record *block = realloc(t->row_block, cap * sizeof *block);
+    if (!block) return -1;
+    if (block != t->row_block) for (size_t i = 0; i < n; i++) engine->all_records[i] = &block[i];
+    t->row_block = block;
+    record **rows = realloc(engine->all_records, cap * sizeof *rows);
+    if (!rows) return -1;
+    engine->all_records = rows;
+    t->row_capacity = cap;
+    return 0;
+}
+
+/* A writer's flags (DELETE: the rows that go, UPDATE: the rows that change): per shard on the device, where row_flags()
+ * allocates them, and for the whole table on the host -- on an engine with host rows. */
+struct writer_flags { uint8_t *dev[HIP_MAX_SHARDS], *host; };
+
+static int writer_flags_host(struct writer_flags *wf, const struct hipTable *t, size_t n, const char *writer) {
+    if (t->device_only) return 0;
+    wf->host = malloc(n ? n : 1);
+    if (!wf->host) { fprintf(stderr, "HIP engine: out of memory for %zu %s flags\n", n, writer); return -1; }
+    return 0;
+}
+
+static void writer_flags_free(struct writer_flags *wf, struct hipTable *t) {
+    for (int s = 0; s < hipTableShards(t); s++) if (wf->dev[s]) pqps_free(hipTableShard(t, s)->ctx, wf->dev[s]);
+    free(wf->host);
+    memset(wf, 0, sizeof *wf);
+}
+
 bool executeQueryInsertHIP(struct engineS *engine, const char *tableName, const record *r) {
     (void)tableName;
     if (r->command_id == 0 || !r->raw_command[0] || !r->base_command[0] || !r->shell_type[0] ||
@@ -3218,25 +3262,8 @@ bool executeQueryInsertHIP(struct engineS *engine, const char *tableName, const 
         hipTableUnlockExclusive(t);
         return ok;
     }
-    /* room for the row first: a failed allocation must not leave the CSV one row ahead of the engine.
-     * The host row store grows geometrically; all_records[] is re-pointed only when the block moved */
-    if (n + 1 > t->row_capacity) {
-        const size_t cap = n + n / 8 + 64;
-        record *block = realloc(t->row_block, cap * sizeof *block);
-        if (block) {
-            if (block != t->row_block) for (size_t i = 0; i < n; i++) engine->all_records[i] = &block[i];
-            t->row_block = block;
-        }
-        record **rows = block ? realloc(engine->all_records, cap * sizeof *rows) : NULL;
-        if (rows) engine->all_records = rows;
-        if (!block || !rows) { hipTableUnlockExclusive(t); return false; }
-        t->row_capacity = cap;
-    }
-    FILE *f = fopen(engine->datafile, "a");
-    if (!f) { hipTableUnlockExclusive(t); return false; }
-    write_csv_row(f, r);
-    fclose(f);
-
+    /* room for the row first: a failed allocation must not leave the CSV one row ahead of the engine */
+    if (host_rows_reserve(engine, t, n + 1) != 0 || !csv_write_rows(engine, "a", r, 1)) { hipTableUnlockExclusive(t); return false; }
     t->row_block[n] = *r;
     engine->all_records[n] = &t->row_block[n];
     engine->num_records = (int)(n + 1);
@@ -3285,18 +3312,6 @@ static int row_flags(struct query *q, size_t n, uint8_t **flags_dev, uint8_t *fl
     return rc;
 }
 
-static int delete_flags(struct engineS *engine, struct hipTable *t, struct whereClauseS *whereClause, size_t n, uint8_t **flags_dev, uint8_t *flags,
-                        uint64_t *deleted) {
-    struct query q;
-    query_init(&q, engine, t, -1, true);                            /* the writer is alone: the table's own context and buffers */
-    *deleted = 0;
-    if (bind_where(t, whereClause, &q.plan) != 0) return -1;
-    q.have_plan = true;
-    const int rc = row_flags(&q, n, flags_dev, flags, deleted, NULL);
-    query_free(&q);
-    return rc;
-}
-
 struct resultSetS *executeQueryDeleteHIP(struct engineS *engine, const char *tableName,
                                          struct whereClauseS *whereClause) {
     (void)tableName;
@@ -3306,15 +3321,19 @@ struct resultSetS *executeQueryDeleteHIP(struct engineS *engine, const char *tab
     struct hipTable *t = engine->record_block;
     if (hipTableLockExclusive(t) != 0) { memset(rs, 0, sizeof *rs); rs->success = false; return rs; }
     const size_t n = (size_t)engine->num_records;
-    const int n_shards = hipTableShards(t);
-    uint8_t *flags_dev[HIP_MAX_SHARDS];
-    memset(flags_dev, 0, sizeof flags_dev);
-    uint8_t *flags = t->device_only ? NULL : malloc(n ? n : 1);
+    struct writer_flags wf;
+    memset(&wf, 0, sizeof wf);
     uint64_t flagged = 0;
-    if ((!flags && !t->device_only) || delete_flags(engine, t, whereClause, n, flags_dev, flags, &flagged) != 0) {
-        if (!flags && !t->device_only) fprintf(stderr, "HIP engine: out of memory for %zu delete flags\n", n);
-        for (int s = 0; s < n_shards; s++) if (flags_dev[s]) pqps_free(hipTableShard(t, s)->ctx, flags_dev[s]);
-        free(flags);
+    int rc = writer_flags_host(&wf, t, n, "delete");
+    if (rc == 0) {
+        struct query q;
+        query_init(&q, engine, t, -1, true);                        /* the writer is alone: the table's own context and buffers */
+        rc = bind_where(t, whereClause, &q.plan);
+        if (rc == 0) { q.have_plan = true; rc = row_flags(&q, n, wf.dev, wf.host, &flagged, NULL); }
+        query_free(&q);
+    }
+    if (rc != 0) {
+        writer_flags_free(&wf, t);
         hipTableUnlockExclusive(t);
         rs->success = false;                                       /* nothing was deleted */
         return rs;
@@ -3329,28 +3348,21 @@ struct resultSetS *executeQueryDeleteHIP(struct engineS *engine, const char *tab
     } else {
         record *block = t->row_block;
         for (size_t i = 0; i < n; i++) {
-            if (flags[i]) { deleted++; continue; }
+            if (wf.host[i]) { deleted++; continue; }
             if (keep != i) block[keep] = block[i];
             keep++;
         }
-        free(flags);
         for (size_t i = 0; i < keep; i++) engine->all_records[i] = &block[i];
         engine->num_records = (int)keep;
     }
     const double t2 = now_seconds();
 
-    if (!t->device_only) {
-        FILE *f = fopen(engine->datafile, "w");                   /* S:683-701: no header written */
-        if (f) {
-            write_csv_table(f, t->row_block, keep);
-            fclose(f);
-        }
-    }
+    if (!t->device_only) (void)csv_write_rows(engine, "w", t->row_block, keep);     /* a file that cannot be opened is left */
     const double t3 = now_seconds();
     /* device side: the same flags compact the 12 columns of every shard in place (order kept); dictionaries
      * stay as they are (a code without rows is harmless), indexes are re-sorted */
-    if (deleted) compactDeviceTableHIP(engine, flags_dev, keep);
-    for (int s = 0; s < n_shards; s++) pqps_free(hipTableShard(t, s)->ctx, flags_dev[s]);
+    if (deleted) compactDeviceTableHIP(engine, wf.dev, keep);
+    writer_flags_free(&wf, t);
     TRACE("DELETE: %zu of %zu rows, flags %.3f ms, host rows %.3f ms, CSV rewrite %.3f ms, device compaction + indexes %.3f ms\n",
           deleted, n, (t1 - t0) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3, (now_seconds() - t3) * 1e3);
     hipTableUnlockExclusive(t);
@@ -3449,11 +3461,10 @@ static long long update_locked(struct engineS *engine, struct hipTable *t, const
 
     /* 3. the rows */
     uint64_t matched[HIP_MAX_SHARDS];
-    uint8_t *flags_dev[HIP_MAX_SHARDS];
+    struct writer_flags wf;
     memset(matched, 0, sizeof matched);
-    memset(flags_dev, 0, sizeof flags_dev);
+    memset(&wf, 0, sizeof wf);
     uint64_t total = 0;
-    uint8_t *flags = NULL;
     bool fused = false;
     struct query q;
     query_init(&q, engine, t, -1, true);                            /* the writer is alone: the table's own context and buffers */
@@ -3465,11 +3476,8 @@ static long long update_locked(struct engineS *engine, struct hipTable *t, const
             rc = update_fused(&q, a, numSet, matched);
             for (int s = 0; s < n_shards; s++) total += matched[s];
         } else {
-            if (!t->device_only) {
-                flags = malloc(n ? n : 1);
-                if (!flags) { fprintf(stderr, "HIP engine: out of memory for %zu update flags\n", n); rc = -1; }
-            }
-            if (rc == 0) rc = row_flags(&q, n, flags_dev, flags, &total, matched);
+            rc = writer_flags_host(&wf, t, n, "update");
+            if (rc == 0) rc = row_flags(&q, n, wf.dev, wf.host, &total, matched);
         }
         TRACE("UPDATE: %s route, %llu of %zu rows\n", fused ? "fused" : "flags", (unsigned long long)total, n);
     }
@@ -3481,23 +3489,18 @@ static long long update_locked(struct engineS *engine, struct hipTable *t, const
     double t3 = t2;
     if (rc == 0 && !t->device_only && total) {
         for (size_t i = 0; i < n; i++)
-            if (flags[i]) assign_host_row(&t->row_block[i], a, numSet);
-        FILE *f = fopen(engine->datafile, "w");                    /* no header written, S:683-701 */
-        if (f) {
-            write_csv_table(f, t->row_block, n);
-            fclose(f);
-        }
+            if (wf.host[i]) assign_host_row(&t->row_block[i], a, numSet);
+        (void)csv_write_rows(engine, "w", t->row_block, n);        /* a file that cannot be opened is left */
         t3 = now_seconds();
     }
-    free(flags);
 
     /* the stores of the flags route, or the rebuild from the updated host rows.  A device step that fails after the host rows
      * and the CSV have changed is fatal, as in INSERT / DELETE. */
-    if (rc == 0 && !fused && total && !rebuild && update_by_flags(t, a, numSet, flags_dev, matched) != 0) {
+    if (rc == 0 && !fused && total && !rebuild && update_by_flags(t, a, numSet, wf.dev, matched) != 0) {
         if (!t->device_only) exit(EXIT_FAILURE);
         rc = -1;
     }
-    for (int s = 0; s < n_shards; s++) if (flags_dev[s]) pqps_free(hipTableShard(t, s)->ctx, flags_dev[s]);
+    writer_flags_free(&wf, t);
     /* 4. plane, bounds, indexes (bumped codes are keys of indexes whatever became of the WHERE) */
     if (rebuild) { if (rc == 0 && total) rebuildDeviceTableHIP(engine); }
     else finishUpdateDeviceTableHIP(engine, a, numSet, matched, bumped);
@@ -3575,27 +3578,11 @@ long long executeQueryInsertRowsHIP(struct engineS *engine, const char *tableNam
     if (b && !t->device_only) {
         /* the host rows and the CSV, as B single INSERTs leave them: room first, then the file, then the rows */
         const size_t n = (size_t)engine->num_records, total = n + (size_t)num_rows;
-        bool ok = true;
-        if (total > t->row_capacity) {
-            const size_t cap = total + total / 8 + 64;
-            record *block = realloc(t->row_block, cap * sizeof *block);
-            if (block) {
-                if (block != t->row_block) for (size_t i = 0; i < n; i++) engine->all_records[i] = &block[i];
-                t->row_block = block;
-            }
-            record **ptrs = block ? realloc(engine->all_records, cap * sizeof *ptrs) : NULL;
-            if (ptrs) engine->all_records = ptrs;
-            ok = block && ptrs;
-            if (ok) t->row_capacity = cap;
-        }
-        FILE *f = ok ? fopen(engine->datafile, "a") : NULL;
-        if (!f) {
+        if (host_rows_reserve(engine, t, total) != 0 || !csv_write_rows(engine, "a", rows, (size_t)num_rows)) {
             fprintf(stderr, "HIP engine: batch INSERT: no room for the host rows, or the CSV cannot be appended to\n");
             discardAppendHIP(engine, b);
             b = NULL;
         } else {
-            write_csv_table(f, rows, (size_t)num_rows);
-            fclose(f);
             memcpy(&t->row_block[n], rows, (size_t)num_rows * sizeof *rows);
             for (size_t i = n; i < total; i++) engine->all_records[i] = &t->row_block[i];
         }

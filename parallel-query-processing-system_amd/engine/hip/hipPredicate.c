@@ -85,14 +85,18 @@ static void window_i32(struct step *s, int op, int v) {
     s->span &= 0xFFFFFFFFull;
 }
 
+int hipDictionaryRank(const char *const *values, int count, const char *text, int *present) {
+    int l = 0, r = count;
+    while (l < r) { const int m = l + (r - l) / 2; if (strcmp(values[m], text) < 0) l = m + 1; else r = m; }
+    *present = l < count && strcmp(values[l], text) == 0;
+    return l;
+}
+
 /* String column as order-preserving codes: strcmp(field, lit) OP 0 (S:23-26)
  * rewritten on ranks.  lb = #values < lit, ub = #values <= lit. */
 static void window_dict(struct step *s, int op, const char *lit, const struct hipColumnInfo *ci) {
-    int l = 0, r = ci->dict_count;
-    while (l < r) { int m = l + (r - l) / 2; if (strcmp(ci->dict[m], lit) < 0) l = m + 1; else r = m; }
-    const int lb = l;
-    const int present = (lb < ci->dict_count && strcmp(ci->dict[lb], lit) == 0);
-    const int ub = lb + present;
+    int present;
+    const int lb = hipDictionaryRank(ci->dict, ci->dict_count, lit, &present), ub = lb + present;
     const uint64_t top = 0xFFFFFFFFull;
     s->kind = ST_LEAF;
     s->neg = 0;
@@ -409,10 +413,9 @@ static int resolve_one(const struct hipSchema *schema, const struct whereClauseS
             uint8_t *mark = calloc((size_t)ci->dict_count + 1, 1);
             if (!mark) rc = -1;
             else if (is_like) rc = like_marks(ci, c->value, mark);
-            else for (int i = 0; i < n_items; i++) {
-                int l = 0, r = ci->dict_count;
-                while (l < r) { const int m = l + (r - l) / 2; if (strcmp(ci->dict[m], items[i]) < 0) l = m + 1; else r = m; }
-                if (l < ci->dict_count && strcmp(ci->dict[l], items[i]) == 0) mark[l] = 1;
+            else for (int i = 0, present; i < n_items; i++) {
+                const int l = hipDictionaryRank(ci->dict, ci->dict_count, items[i], &present);
+                if (present) mark[l] = 1;
             }
             for (int k = 0; rc == 0 && k < ci->dict_count; k++) if (mark[k]) rc = runs_add(&S, (uint64_t)k);
             free(mark);
@@ -958,11 +961,8 @@ int hipCompileAssignments(const struct hipSchema *schema, const char *const *col
         default: {
             if (!values[i][0]) return assign_fail(columns[i], "an empty string");
             if (strlen(values[i]) + 1 > field_bytes(col)) return assign_fail(columns[i], "the string does not fit the record's field");
-            int l = 0, r = ci->dict_count;
-            while (l < r) { const int m = l + (r - l) / 2; if (strcmp(ci->dict[m], values[i]) < 0) l = m + 1; else r = m; }
-            a[i].rank = (uint32_t)l;
-            a[i].value = (uint64_t)l;
-            a[i].present = l < ci->dict_count && strcmp(ci->dict[l], values[i]) == 0;
+            a[i].rank = (uint32_t)hipDictionaryRank(ci->dict, ci->dict_count, values[i], &a[i].present);
+            a[i].value = a[i].rank;
             a[i].text = values[i];
             break;
         }
