@@ -15,7 +15,7 @@
 //                           reads its word and ORs only if its bit is clear, so once the bitmap has warmed up a row costs
 //                           one LDS read and no atomic.  The workgroup stores its whole bitmap into a partial row.
 //   GLOBAL G x W x 32 <= cap  test before set on the HBM word, then a global atomic OR (a correctness path for high
-//                           cardinality, like GROUP_GLOBAL)
+//                           cardinality, like BINS_GLOBAL)
 // REG and LDS flush by store-and-OR (dist_or_kernel: 64 partial rows per workgroup, one atomic OR per non-zero word), the
 // form agg_sum_kernel uses: a dense bitmap costs every workgroup the same plain stores, where one atomic per non-zero word
 // and workgroup would queue thousands of same-address ORs at the memory side.  The matching-row count comes from the same

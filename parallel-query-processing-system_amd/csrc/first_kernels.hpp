@@ -19,10 +19,10 @@
 //   LDS    D <= 8192     a table of 8 B per bin in dynamic LDS, 64 KiB at most (two workgroups per CU); ONE ds_min_u64 per
 //                        matching row
 //   GLOBAL D <= 65536    one global 64-bit atomic min per matching row straight into the output (a correctness path, like
-//                        GROUP_GLOBAL / AGG_GLOBAL: one lane per scattered address)
+//                        BINS_GLOBAL: one lane per scattered address)
 // ONE and LDS end the workgroup's loop with plain stores of a partial row (store-and-combine);
 // first_min_kernel takes the minimum of 64 rows per workgroup with one atomic per bin that has a row.  No same-address global
-// atomic per row or per wave.  There is no register path for tiny D (per-lane minima of D bins, as GROUP_SMALL counts): D
+// atomic per row or per wave.  There is no register path for tiny D (per-lane minima of D bins, as BINS_REGS counts): D
 // words of 64 bits per lane and a D-fold wave reduction buy nothing the LDS table's one ds_min_u64 does not already give.
 //
 // List form (pqps_group_first_list): the same words over an ID list, gathering the key column (and the group column) per

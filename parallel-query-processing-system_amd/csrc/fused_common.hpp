@@ -1,5 +1,5 @@
-// fused_common.hpp -- device scaffolding shared by the fused filter-and-aggregate families: group_, agg_, topk_, first_ and
-// dist_kernels.hpp (included once by pqps_hip.hip, after filter_kernels.hpp and before them).
+// fused_common.hpp -- device scaffolding shared by the fused filter-and-aggregate families: bins_, topk_, order_multi_,
+// first_, distinct_, group_pair_ and assign_kernels.hpp (included once by pqps_hip.hip, after filter_kernels.hpp and before them).
 //
 // A fused scan is the grid-stride form of the COUNT kernels (fused_scan_steps): a wave takes the 1024-row steps wave,
 // wave + n_waves, ... of a persistent grid, evaluates the WHERE of each (eval_step_full; match bit p of lane l <-> row

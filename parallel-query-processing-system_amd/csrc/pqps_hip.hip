@@ -23,10 +23,8 @@
 #include "pqps_hip.h"
 #include "filter_kernels.hpp"
 #include "fused_common.hpp"
-#include "bucket_kernels.hpp"
+#include "bins_kernels.hpp"
 #include "member_kernels.hpp"
-#include "group_kernels.hpp"
-#include "aggregate_kernels.hpp"
 #include "topk_kernels.hpp"
 #include "order_multi_kernels.hpp"
 #include "first_kernels.hpp"
@@ -940,6 +938,28 @@ void fused_close(pqps_ctx *ctx, hipEvent_t stop, bool stop_is_eval) {
     ctx->stop_is_eval[ctx->timed] = stop_is_eval;
     ctx->timed++;
 }
+
+// The dense-bins kernels (bins_kernels.hpp).  One row per (bin source, bins path, bin value) that a request can reach:
+// its two scan instances (NT = false, true) and its list instance (the list form has no register counters).
+typedef void (*bins_scan_fn)(const BinsArgs);
+typedef void (*bins_list_fn)(const BinsListArgs);
+template <int S, int P, int V> constexpr bins_list_fn bins_list_instance() {
+    if constexpr (P == BINS_REGS && V == BINS_COUNT) return nullptr;
+    else return bins_list_kernel<S, P, V>;
+}
+const struct BinsInstance { int src, path, val; bins_scan_fn scan[2]; bins_list_fn list; } kBinsInstances[] = {
+#define PQPS_BINS(S, P, V) {S, P, V, {bins_scan_kernel<S, P, V, false>, bins_scan_kernel<S, P, V, true>}, bins_list_instance<S, P, V>()}
+#define PQPS_BINS_VALUED(S, P) PQPS_BINS(S, P, BINS_I32), PQPS_BINS(S, P, BINS_U64)
+    PQPS_BINS(BIN_COLUMN, BINS_REGS, BINS_COUNT), PQPS_BINS(BIN_COLUMN, BINS_LDS, BINS_COUNT), PQPS_BINS(BIN_COLUMN, BINS_GLOBAL, BINS_COUNT),
+    PQPS_BINS_VALUED(BIN_NONE, BINS_REGS), PQPS_BINS_VALUED(BIN_COLUMN, BINS_LDS), PQPS_BINS_VALUED(BIN_COLUMN, BINS_GLOBAL),
+    PQPS_BINS(BIN_BUCKET_LDS, BINS_REGS, BINS_COUNT), PQPS_BINS(BIN_BUCKET_LDS, BINS_LDS, BINS_COUNT),
+    PQPS_BINS(BIN_BUCKET_LDS, BINS_GLOBAL, BINS_COUNT), PQPS_BINS(BIN_BUCKET_GLOBAL, BINS_GLOBAL, BINS_COUNT),
+    PQPS_BINS_VALUED(BIN_BUCKET_LDS, BINS_LDS), PQPS_BINS_VALUED(BIN_BUCKET_LDS, BINS_GLOBAL), PQPS_BINS_VALUED(BIN_BUCKET_GLOBAL, BINS_GLOBAL),
+    PQPS_BINS(BIN_PAIR, BINS_LDS, BINS_COUNT), PQPS_BINS(BIN_PAIR, BINS_GLOBAL, BINS_COUNT),
+    PQPS_BINS_VALUED(BIN_PAIR, BINS_LDS), PQPS_BINS_VALUED(BIN_PAIR, BINS_GLOBAL),
+#undef PQPS_BINS_VALUED
+#undef PQPS_BINS
+};
 
 // Placement in the grid.  The chip has ~8 workgroups per CU in flight, i.e. `base` groups, and a round of loads
 // takes about as long as `base` groups take to pass.  A group (and, from the same count words, a supergroup) is
@@ -2932,7 +2952,7 @@ int pqps_ids_checksum(pqps_ctx *ctx, const uint32_t *ids, uint64_t count, uint64
     return PQPS_OK;
 }
 
-// ---- grouped COUNT(*) (group_kernels.hpp) --------------------------------------------------------------------------
+// ---- dense bins: grouped COUNT(*), COUNT / SUM / MIN / MAX, GROUP BY buckets, GROUP BY two columns (bins_kernels.hpp) --
 // ctx->group_parts holds at least `words` u32 words.  The name is grouped COUNT's; all four fused scans keep what their
 // workgroups hand to the follow-up kernel here (partial histograms, aggregate tables, bitmaps and totals), one query at a
 // time per context.
@@ -2944,73 +2964,294 @@ static int grow_group_parts(pqps_ctx *ctx, hipStream_t s, size_t words) {
     return PQPS_OK;
 }
 
+// What a dense-bins call asks for.  src.gcol == NULL: no GROUP BY (one bin); src.bounds != NULL: buckets; src.gcol2 != NULL:
+// a pair of columns.  value_col == NULL: COUNT(*), out = n_bins u32 bins; else out = [4][n_bins] u64 fields.
+struct BinsRequest {
+    BinSourceArgs src;
+    const pqps_column *value_col;
+    void *out;
+};
+
+// Which instance a request takes (the limits: bins_kernels.hpp), and the dynamic LDS of a workgroup.  `scan`: the fused
+// form, which has the per-lane counters for up to 16 count bins of one column or of buckets.
+struct BinsPlan { const BinsInstance *inst; uint32_t lds; bool valued, buckets, pair; };
+static BinsPlan bins_plan(const BinsRequest &r, bool scan) {
+    BinsPlan p;
+    const uint32_t nb = r.src.n_bins;
+    p.valued = r.value_col != nullptr;
+    p.buckets = r.src.bounds != nullptr;
+    p.pair = r.src.gcol2 != nullptr;
+    const bool bounds_lds = p.buckets && nb <= kBucketBoundsLds;
+    const uint32_t lds_max = p.buckets ? (p.valued ? kBucketAggLds : kBucketCountLds) : (p.valued ? kAggLdsBins : kCountLdsBins);
+    const bool regs = p.valued ? !r.src.gcol : scan && !p.pair && nb <= kBinsSmall;
+    const int path = regs ? BINS_REGS : nb <= lds_max ? BINS_LDS : BINS_GLOBAL;
+    const int src = !r.src.gcol ? BIN_NONE : p.pair ? BIN_PAIR : !p.buckets ? BIN_COLUMN : bounds_lds ? BIN_BUCKET_LDS : BIN_BUCKET_GLOBAL;
+    const int val = !p.valued ? BINS_COUNT : r.value_col->width == 8 ? BINS_U64 : BINS_I32;
+    p.lds = (bounds_lds ? (nb + 1u) * (uint32_t)sizeof(uint32_t) : 0u) + (path == BINS_LDS ? nb * (p.valued ? kAggBinBytes : kCountBinBytes) : 0u);
+    p.inst = nullptr;
+    for (const BinsInstance &i : kBinsInstances)
+        if (i.src == src && i.path == path && i.val == val) p.inst = &i;
+    return p;
+}
+
+static const char *const kPairValueName[3] = {"PAIR_COUNT", "PAIR_I32", "PAIR_U64"};
+
+// What pqps_last_kernel() reports after a fused call: the family's name with the path that was taken, e.g.
+// "agg_scan_kernel<AGG_LDS, u64, NT=true>", "bucket_scan_kernel<BUCKET_GLOBAL, BLDS=false, NT=false>"
+static void bins_scan_name(const BinsPlan &p, bool nt) {
+    const char *family = p.pair ? "pair" : p.buckets ? (p.valued ? "bucket_agg" : "bucket") : p.valued ? "agg" : "group";
+    const char *prefix = p.pair ? "PAIR" : p.buckets ? "BUCKET" : p.valued ? "AGG" : "GROUP";
+    const char *path = p.inst->path == BINS_LDS ? "LDS" : p.inst->path == BINS_GLOBAL ? "GLOBAL" : p.valued ? "ONE" : "SMALL";
+    const char *bounds = !p.buckets ? "" : p.inst->src == BIN_BUCKET_LDS ? ", BLDS=true" : ", BLDS=false";
+    const char *sep = p.pair || p.valued ? ", " : "";
+    const char *val = p.pair ? kPairValueName[p.inst->val] : !p.valued ? "" : p.inst->val == BINS_U64 ? "u64" : "i32";
+    snprintf(g_kernel, sizeof g_kernel, "%s_scan_kernel<%s_%s%s%s%s, NT=%s>", family, prefix, path, bounds, sep, val, nt ? "true" : "false");
+}
+
+// n_bins u32 bins zeroed, or out[4][n_bins]: counts and sums 0, min images ~0, max images 0
+static int init_bins_out(void *out, uint32_t n_bins, bool valued, hipStream_t s) {
+    if (!valued) {
+        HIP_TRY(hipMemsetAsync(out, 0, (size_t)n_bins * sizeof(uint32_t), s));
+        return PQPS_OK;
+    }
+    HIP_TRY(hipMemsetAsync(out, 0, (size_t)kAggFields * n_bins * sizeof(uint64_t), s));
+    HIP_TRY(hipMemsetAsync((uint64_t *)out + 2 * (size_t)n_bins, 0xFF, (size_t)n_bins * sizeof(uint64_t), s));
+    return PQPS_OK;
+}
+
+// The fused form of a (checked) request: the scan, and on the REGS and LDS paths the kernel that adds the workgroups'
+// partial rows up.
+static int bins_scan(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                     const BinsRequest &r, void *stream) {
+    BinsArgs g;
+    memset(&g, 0, sizeof g);
+    int rc = fused_args(g.e, cols, n_cols, n_rows, pred);
+    if (rc) return rc;
+    const BinsPlan p = bins_plan(r, true);
+    if (!p.inst) return fail(PQPS_EINVAL, "no kernel for this grouped query");
+    const uint32_t nb = r.src.n_bins;
+    hipStream_t s = pick_stream(ctx, stream);
+    rc = init_bins_out(r.out, nb, p.valued, s);
+    if (rc || n_rows == 0) return rc;
+    const bool summed = p.inst->path != BINS_GLOBAL;
+    const uint32_t grid = fused_grid(ctx, n_rows, p.lds);
+    const uint32_t stride = (nb + 63u) & ~63u;
+    if (summed) {                                               // partial rows: [grid][stride] u32 or [grid][4][nb] u64
+        rc = grow_group_parts(ctx, s, p.valued ? (size_t)grid * kAggFields * nb * 2 : (size_t)grid * stride);
+        if (rc) return rc;
+    }
+    g.src = r.src;
+    g.vcol = p.valued ? r.value_col->data : nullptr;
+    g.out = r.out;
+    g.parts = ctx->group_parts;
+    g.stride = stride;
+    bins_scan_name(p, g.e.streaming != 0);
+    hipEvent_t stop;
+    rc = fused_launch(ctx, p.inst->scan[g.e.streaming ? 1 : 0], grid, p.lds, s, g, &stop);
+    if (rc) return rc;
+    if (summed && p.valued) {
+        const dim3 sg((nb + 63u) / 64u, (grid + kAggSumParts - 1) / kAggSumParts);
+        rc = launch_stop(agg_sum_kernel, sg, 0, s, stop, (const uint64_t *)ctx->group_parts, grid, nb, (uint64_t *)r.out);
+    } else if (summed) {
+        const dim3 sg(stride / 64u, (grid + kGroupSumParts - 1) / kGroupSumParts);
+        rc = launch_stop(group_sum_kernel, sg, 0, s, stop, (const uint32_t *)ctx->group_parts, grid, stride, nb, (uint32_t *)r.out);
+    }
+    fused_close(ctx, stop, !summed);
+    return rc;
+}
+
+// The list form of a (checked) request: the bins of ids[0 .. min(*count_dev, capacity)).
+static int bins_list(pqps_ctx *ctx, const BinsRequest &r, uint64_t n_rows, const uint32_t *ids, const uint64_t *count_dev, uint64_t capacity,
+                     uint32_t id_base, void *stream) {
+    const BinsPlan p = bins_plan(r, false);
+    if (!p.inst || !p.inst->list) return fail(PQPS_EINVAL, "no kernel for this grouped query");
+    hipStream_t s = pick_stream(ctx, stream);
+    const int rc = init_bins_out(r.out, r.src.n_bins, p.valued, s);
+    if (rc || capacity == 0 || n_rows == 0) return rc;
+    BinsListArgs g;
+    memset(&g, 0, sizeof g);
+    g.src = r.src;
+    g.vcol = p.valued ? r.value_col->data : nullptr;
+    g.ids = ids;
+    g.count = count_dev;
+    g.out = r.out;
+    g.n_rows = n_rows;
+    g.capacity = capacity;
+    g.id_base = id_base;
+    if (p.pair) snprintf(g_kernel, sizeof g_kernel, "pair_list_kernel<LDS=%s, %s>", p.inst->path == BINS_LDS ? "true" : "false", kPairValueName[p.inst->val]);
+    hipLaunchKernelGGL(p.inst->list, dim3(list_grid(ctx, capacity, 4)), dim3(kBlock), p.lds, s, g);
+    HIP_TRY(hipGetLastError());
+    return PQPS_OK;
+}
+
+static int check_bin_count(uint32_t n_bins) {
+    return n_bins == 0 || n_bins > kBinsMax ? fail(PQPS_EINVAL, "%u bins: 1 .. %u", n_bins, kBinsMax) : PQPS_OK;
+}
+
+static int check_value_col(const pqps_column *value_col) {
+    if (!value_col) return fail(PQPS_EINVAL, "value column is NULL");
+    if (value_col->width != 4 && value_col->width != 8) return fail(PQPS_EINVAL, "value column: width %u not in {4,8}", value_col->width);
+    if (!value_col->data || ((uintptr_t)value_col->data & 15u) != 0) return fail(PQPS_EINVAL, "value column: NULL or not 16-byte aligned");
+    return PQPS_OK;
+}
+
+// The request for the bins of one column (group_col == NULL: no GROUP BY), checked.  value_col == NULL: COUNT(*).  `aligned`
+// is asked of the group column of a COUNT(*) only: the valued forms always ask for it.
+static int column_request(BinsRequest &r, const pqps_column *value_col, const pqps_column *group_col, uint32_t bin_base, uint32_t n_bins,
+                          bool plane_ok, bool aligned, void *out) {
+    memset(&r, 0, sizeof r);
+    int rc = value_col ? check_value_col(value_col) : PQPS_OK;
+    if (rc) return rc;
+    if (!group_col) {
+        if (n_bins != 1) return fail(PQPS_EINVAL, "no group column: 1 bin, not %u", n_bins);
+    } else {
+        rc = check_bin_count(n_bins);
+        if (rc == PQPS_OK) rc = column_width_code("group", group_col, plane_ok, false, aligned || value_col, &r.src.gwidth_log2);
+        if (rc) return rc;
+        r.src.gcol = group_col->data;
+    }
+    r.src.bin_base = bin_base;
+    r.src.n_bins = n_bins;
+    r.value_col = value_col;
+    r.out = out;
+    return PQPS_OK;
+}
+
 int pqps_filter_group(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
                       const pqps_column *group_col, uint32_t bin_base, uint32_t n_bins, uint32_t *bins, void *stream) {
     if (!ctx || !group_col || !bins) return fail(PQPS_EINVAL, "ctx/group_col/bins is NULL");
-    if (n_bins == 0 || n_bins > kGroupMaxBins) return fail(PQPS_EINVAL, "%u bins: 1 .. %u", n_bins, kGroupMaxBins);
-    GroupArgs g;
-    memset(&g, 0, sizeof g);
-    int rc = column_width_code("group", group_col, true, false, true, &g.gwidth_log2);
-    if (rc == PQPS_OK) rc = fused_args(g.e, cols, n_cols, n_rows, pred);
-    if (rc) return rc;
-    hipStream_t s = pick_stream(ctx, stream);
-    HIP_TRY(hipMemsetAsync(bins, 0, (size_t)n_bins * sizeof(uint32_t), s));
-    if (n_rows == 0) return PQPS_OK;
-    const int path = n_bins <= kGroupSmallBins ? GROUP_SMALL : n_bins <= kGroupLdsBins ? GROUP_LDS : GROUP_GLOBAL;
-    const uint32_t hist_bytes = path == GROUP_LDS ? n_bins * (uint32_t)sizeof(uint32_t) : 0u;
-    const uint32_t grid = fused_grid(ctx, n_rows, hist_bytes);
-    const uint32_t stride = (n_bins + 63u) & ~63u;
-    if (path != GROUP_GLOBAL) {
-        rc = grow_group_parts(ctx, s, (size_t)grid * stride);
-        if (rc) return rc;
-    }
-    g.gcol = group_col->data;
-    g.bins = bins;
-    g.parts = ctx->group_parts;
-    g.stride = stride;
-    g.bin_base = bin_base;
-    g.n_bins = n_bins;
-    // the instance and its name side by side: pqps_last_kernel() reports the entry that is launched
-    static const struct { void (*fn)(const GroupArgs); const char *name; } fns[3][2] = {
-#define PQPS_GROUP_SCAN(P, NT) {group_scan_kernel<P, NT>, "group_scan_kernel<" #P ", NT=" #NT ">"}
-        {PQPS_GROUP_SCAN(GROUP_SMALL, false), PQPS_GROUP_SCAN(GROUP_SMALL, true)},
-        {PQPS_GROUP_SCAN(GROUP_LDS, false), PQPS_GROUP_SCAN(GROUP_LDS, true)},
-        {PQPS_GROUP_SCAN(GROUP_GLOBAL, false), PQPS_GROUP_SCAN(GROUP_GLOBAL, true)},
-#undef PQPS_GROUP_SCAN
-    };
-    const auto &scan = fns[path][g.e.streaming ? 1 : 0];
-    snprintf(g_kernel, sizeof g_kernel, "%s", scan.name);
-    hipEvent_t stop;
-    rc = fused_launch(ctx, scan.fn, grid, hist_bytes, s, g, &stop);
-    if (rc) return rc;
-    if (path != GROUP_GLOBAL) {
-        const dim3 sg(stride / 64u, (grid + kGroupSumParts - 1) / kGroupSumParts);
-        rc = launch_stop(group_sum_kernel, sg, 0, s, stop, (const uint32_t *)ctx->group_parts, grid, stride, n_bins, bins);
-        if (rc) return rc;
-    }
-    fused_close(ctx, stop, path == GROUP_GLOBAL);
-    return PQPS_OK;
+    BinsRequest r;
+    const int rc = column_request(r, nullptr, group_col, bin_base, n_bins, true, true, bins);
+    return rc ? rc : bins_scan(ctx, cols, n_cols, n_rows, pred, r, stream);
 }
 
 int pqps_group_list(pqps_ctx *ctx, const pqps_column *group_col, uint64_t n_rows, const uint32_t *ids, const uint64_t *count_dev,
                     uint64_t capacity, uint32_t id_base, uint32_t bin_base, uint32_t n_bins, uint32_t *bins, void *stream) {
     if (!ctx || !group_col || !bins || !count_dev || (capacity && !ids)) return fail(PQPS_EINVAL, "NULL argument");
-    if (n_bins == 0 || n_bins > kGroupMaxBins) return fail(PQPS_EINVAL, "%u bins: 1 .. %u", n_bins, kGroupMaxBins);
-    uint32_t wl;
-    const int rc = column_width_code("group", group_col, false, false, false, &wl);   // gathered by row: any alignment
+    BinsRequest r;
+    const int rc = column_request(r, nullptr, group_col, bin_base, n_bins, false, false, bins);   // gathered by row: any alignment
+    return rc ? rc : bins_list(ctx, r, n_rows, ids, count_dev, capacity, id_base, stream);
+}
+
+int pqps_filter_aggregate(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                          const pqps_column *value_col, const pqps_column *group_col, uint32_t bin_base, uint32_t n_bins,
+                          uint64_t *out, void *stream) {
+    if (!ctx || !out) return fail(PQPS_EINVAL, "ctx/out is NULL");
+    if (!value_col) return fail(PQPS_EINVAL, "value column is NULL");
+    BinsRequest r;
+    const int rc = column_request(r, value_col, group_col, bin_base, n_bins, true, true, out);
+    return rc ? rc : bins_scan(ctx, cols, n_cols, n_rows, pred, r, stream);
+}
+
+int pqps_aggregate_list(pqps_ctx *ctx, const pqps_column *value_col, const pqps_column *group_col, uint64_t n_rows,
+                        const uint32_t *ids, const uint64_t *count_dev, uint64_t capacity, uint32_t id_base, uint32_t bin_base,
+                        uint32_t n_bins, uint64_t *out, void *stream) {
+    if (!ctx || !out || !count_dev || (capacity && !ids)) return fail(PQPS_EINVAL, "NULL argument");
+    if (!value_col) return fail(PQPS_EINVAL, "value column is NULL");
+    BinsRequest r;
+    const int rc = column_request(r, value_col, group_col, bin_base, n_bins, false, true, out);
+    return rc ? rc : bins_list(ctx, r, n_rows, ids, count_dev, capacity, id_base, stream);
+}
+
+// The request for the buckets of one column, checked; value_col == NULL: COUNT(*) per bucket.
+static int bucket_request(BinsRequest &r, const pqps_column *value_col, const pqps_column *group_col, uint32_t bin_base,
+                          const uint32_t *bounds_dev, uint32_t n_buckets, uint32_t domain, bool aligned, void *out) {
+    if (n_buckets == 0 || n_buckets > kBinsMax) return fail(PQPS_EINVAL, "%u buckets: 1 .. %u", n_buckets, kBinsMax);
+    if (!bounds_dev) return fail(PQPS_EINVAL, "bounds is NULL");
+    if (domain == 0 || domain < n_buckets) return fail(PQPS_EINVAL, "domain %u: at least one bin per bucket (%u)", domain, n_buckets);
+    const int rc = column_request(r, value_col, group_col, bin_base, n_buckets, false, aligned, out);
     if (rc) return rc;
-    hipStream_t s = pick_stream(ctx, stream);
-    HIP_TRY(hipMemsetAsync(bins, 0, (size_t)n_bins * sizeof(uint32_t), s));
-    if (capacity == 0 || n_rows == 0) return PQPS_OK;
-    const dim3 grid(list_grid(ctx, capacity, 4));
-    if (n_bins <= kGroupLdsBins)
-        hipLaunchKernelGGL(group_list_kernel<true>, grid, dim3(kBlock), n_bins * (uint32_t)sizeof(uint32_t), s,
-                           group_col->data, wl, n_rows, ids, count_dev, capacity, id_base, bin_base, n_bins, bins);
-    else
-        hipLaunchKernelGGL(group_list_kernel<false>, grid, dim3(kBlock), 0, s,
-                           group_col->data, wl, n_rows, ids, count_dev, capacity, id_base, bin_base, n_bins, bins);
-    HIP_TRY(hipGetLastError());
+    r.src.bounds = bounds_dev;
+    r.src.top = 1;
+    while (r.src.top * 2u <= n_buckets + 1u) r.src.top *= 2u;
     return PQPS_OK;
+}
+
+int pqps_filter_group_buckets(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                              const pqps_column *group_col, uint32_t bin_base, const uint32_t *bounds_dev, uint32_t n_buckets,
+                              uint32_t domain, uint32_t *bins, void *stream) {
+    if (!ctx || !group_col || !bins) return fail(PQPS_EINVAL, "ctx/group_col/out is NULL");
+    BinsRequest r;
+    const int rc = bucket_request(r, nullptr, group_col, bin_base, bounds_dev, n_buckets, domain, true, bins);
+    return rc ? rc : bins_scan(ctx, cols, n_cols, n_rows, pred, r, stream);
+}
+
+int pqps_group_buckets_list(pqps_ctx *ctx, const pqps_column *group_col, uint64_t n_rows, const uint32_t *ids, const uint64_t *count_dev,
+                            uint64_t capacity, uint32_t id_base, uint32_t bin_base, const uint32_t *bounds_dev, uint32_t n_buckets,
+                            uint32_t domain, uint32_t *bins, void *stream) {
+    if (!ctx || !group_col || !bins || !count_dev || (capacity && !ids)) return fail(PQPS_EINVAL, "NULL argument");
+    BinsRequest r;
+    const int rc = bucket_request(r, nullptr, group_col, bin_base, bounds_dev, n_buckets, domain, false, bins);   // gathered by row
+    return rc ? rc : bins_list(ctx, r, n_rows, ids, count_dev, capacity, id_base, stream);
+}
+
+int pqps_filter_aggregate_buckets(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                                  const pqps_column *value_col, const pqps_column *group_col, uint32_t bin_base,
+                                  const uint32_t *bounds_dev, uint32_t n_buckets, uint32_t domain, uint64_t *out, void *stream) {
+    if (!value_col) return fail(PQPS_EINVAL, "value column is NULL");
+    if (!ctx || !group_col || !out) return fail(PQPS_EINVAL, "ctx/group_col/out is NULL");
+    BinsRequest r;
+    const int rc = bucket_request(r, value_col, group_col, bin_base, bounds_dev, n_buckets, domain, true, out);
+    return rc ? rc : bins_scan(ctx, cols, n_cols, n_rows, pred, r, stream);
+}
+
+int pqps_aggregate_buckets_list(pqps_ctx *ctx, const pqps_column *value_col, const pqps_column *group_col, uint64_t n_rows,
+                                const uint32_t *ids, const uint64_t *count_dev, uint64_t capacity, uint32_t id_base, uint32_t bin_base,
+                                const uint32_t *bounds_dev, uint32_t n_buckets, uint32_t domain, uint64_t *out, void *stream) {
+    if (!value_col) return fail(PQPS_EINVAL, "value column is NULL");
+    if (!ctx || !group_col || !out || !count_dev || (capacity && !ids)) return fail(PQPS_EINVAL, "NULL argument");
+    BinsRequest r;
+    const int rc = bucket_request(r, value_col, group_col, bin_base, bounds_dev, n_buckets, domain, true, out);
+    return rc ? rc : bins_list(ctx, r, n_rows, ids, count_dev, capacity, id_base, stream);
+}
+
+// D = n_a x n_b in 64 bits; the dense calls take 1 .. 65 536.  *awl / *bwl: the width codes.
+static int check_pair_cols(const pqps_column *a_col, uint32_t n_a, const pqps_column *b_col, uint32_t n_b, const pqps_column *value_col,
+                           bool dense, bool plane_ok, bool aligned, uint32_t *awl, uint32_t *bwl) {
+    if (!a_col || !b_col) return fail(PQPS_EINVAL, "a group column is NULL");
+    const uint64_t D = (uint64_t)n_a * n_b;
+    if (D == 0 || n_a > kBinsMax || n_b > kBinsMax || (dense && D > kBinsMax))
+        return fail(PQPS_EINVAL, "%u x %u bins: 1 .. %u each%s", n_a, n_b, kBinsMax, dense ? " and in all" : "");
+    int rc = column_width_code("group", a_col, plane_ok, false, aligned, awl);
+    if (rc == PQPS_OK) rc = column_width_code("group", b_col, plane_ok, false, aligned, bwl);
+    if (rc == PQPS_OK && value_col) rc = check_value_col(value_col);
+    return rc;
+}
+
+// The request for the dense bins of two columns, checked.
+static int pair_request(BinsRequest &r, const pqps_column *a_col, uint32_t a_base, uint32_t n_a, const pqps_column *b_col, uint32_t b_base,
+                        uint32_t n_b, const pqps_column *value_col, bool plane_ok, bool aligned, void *out) {
+    memset(&r, 0, sizeof r);
+    const int rc = check_pair_cols(a_col, n_a, b_col, n_b, value_col, true, plane_ok, aligned, &r.src.gwidth_log2, &r.src.gwidth2_log2);
+    if (rc) return rc;
+    r.src.gcol = a_col->data;
+    r.src.gcol2 = b_col->data;
+    r.src.bin_base = a_base;
+    r.src.bin_base2 = b_base;
+    r.src.n_a = n_a;
+    r.src.n_b = n_b;
+    r.src.n_bins = n_a * n_b;
+    r.value_col = value_col;
+    r.out = out;
+    return PQPS_OK;
+}
+
+int pqps_filter_group_pair(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                           const pqps_column *a_col, uint32_t a_base, uint32_t n_a, const pqps_column *b_col, uint32_t b_base,
+                           uint32_t n_b, const pqps_column *value_col, void *out, void *stream) {
+    if (!ctx || !out) return fail(PQPS_EINVAL, "ctx/out is NULL");
+    BinsRequest r;
+    const int rc = pair_request(r, a_col, a_base, n_a, b_col, b_base, n_b, value_col, true, true, out);
+    return rc ? rc : bins_scan(ctx, cols, n_cols, n_rows, pred, r, stream);
+}
+
+int pqps_group_pair_list(pqps_ctx *ctx, const pqps_column *a_col, uint32_t a_base, uint32_t n_a, const pqps_column *b_col, uint32_t b_base,
+                         uint32_t n_b, const pqps_column *value_col, uint64_t n_rows, const uint32_t *ids, const uint64_t *count_dev,
+                         uint64_t capacity, uint32_t id_base, void *out, void *stream) {
+    if (!ctx || !out || !count_dev || (capacity && !ids)) return fail(PQPS_EINVAL, "NULL argument");
+    BinsRequest r;
+    const int rc = pair_request(r, a_col, a_base, n_a, b_col, b_base, n_b, value_col, false, false, out);   // gathered by row: any alignment
+    return rc ? rc : bins_list(ctx, r, n_rows, ids, count_dev, capacity, id_base, stream);
 }
 
 int pqps_column_bounds(pqps_ctx *ctx, const pqps_column *col, uint64_t n_rows, int32_t *out_dev, void *stream) {
@@ -3025,282 +3266,6 @@ int pqps_column_bounds(pqps_ctx *ctx, const pqps_column *col, uint64_t n_rows, i
     hipLaunchKernelGGL(group_bounds_finish_kernel, dim3(1), dim3(1), 0, s, (uint32_t *)out_dev);
     HIP_TRY(hipGetLastError());
     return PQPS_OK;
-}
-
-// ---- COUNT / SUM / MIN / MAX of a value column (aggregate_kernels.hpp) -----------------------------------------------
-// *gwl = the group column's width code (0 without one)
-static int check_aggregate_cols(const pqps_column *value_col, const pqps_column *group_col, uint32_t n_bins, bool plane_ok, uint32_t *gwl) {
-    *gwl = 0;
-    if (!value_col) return fail(PQPS_EINVAL, "value column is NULL");
-    if (value_col->width != 4 && value_col->width != 8) return fail(PQPS_EINVAL, "value column: width %u not in {4,8}", value_col->width);
-    if (!value_col->data || ((uintptr_t)value_col->data & 15u) != 0) return fail(PQPS_EINVAL, "value column: NULL or not 16-byte aligned");
-    if (!group_col) return n_bins == 1 ? PQPS_OK : fail(PQPS_EINVAL, "no group column: 1 bin, not %u", n_bins);
-    if (n_bins == 0 || n_bins > kGroupMaxBins) return fail(PQPS_EINVAL, "%u bins: 1 .. %u", n_bins, kGroupMaxBins);
-    return column_width_code("group", group_col, plane_ok, false, true, gwl);
-}
-
-// out[4][n_bins]: counts and sums 0, min images ~0, max images 0
-static int init_aggregate_out(uint64_t *out, uint32_t n_bins, hipStream_t s) {
-    HIP_TRY(hipMemsetAsync(out, 0, (size_t)kAggFields * n_bins * sizeof(uint64_t), s));
-    HIP_TRY(hipMemsetAsync(out + 2 * (size_t)n_bins, 0xFF, (size_t)n_bins * sizeof(uint64_t), s));
-    return PQPS_OK;
-}
-
-int pqps_filter_aggregate(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
-                          const pqps_column *value_col, const pqps_column *group_col, uint32_t bin_base, uint32_t n_bins,
-                          uint64_t *out, void *stream) {
-    if (!ctx || !out) return fail(PQPS_EINVAL, "ctx/out is NULL");
-    AggArgs g;
-    memset(&g, 0, sizeof g);
-    int rc = check_aggregate_cols(value_col, group_col, n_bins, true, &g.gwidth_log2);
-    if (rc == PQPS_OK) rc = fused_args(g.e, cols, n_cols, n_rows, pred);
-    if (rc) return rc;
-    hipStream_t s = pick_stream(ctx, stream);
-    rc = init_aggregate_out(out, n_bins, s);
-    if (rc || n_rows == 0) return rc;
-    const int path = !group_col ? AGG_ONE : n_bins <= kAggLdsBins ? AGG_LDS : AGG_GLOBAL;
-    const uint32_t table_bytes = path == AGG_LDS ? n_bins * (uint32_t)(3 * sizeof(uint64_t) + sizeof(uint32_t)) : 0u;
-    const uint32_t grid = fused_grid(ctx, n_rows, table_bytes);
-    if (path != AGG_GLOBAL) {
-        rc = grow_group_parts(ctx, s, (size_t)grid * kAggFields * n_bins * 2);
-        if (rc) return rc;
-    }
-    g.vcol = value_col->data;
-    g.gcol = group_col ? group_col->data : nullptr;
-    g.out = out;
-    g.parts = (uint64_t *)ctx->group_parts;
-    g.bin_base = bin_base;
-    g.n_bins = n_bins;
-    const bool u64 = value_col->width == 8;
-    // the instance and its name side by side: pqps_last_kernel() reports the entry that is launched
-    static const struct { void (*fn)(const AggArgs); const char *name; } fns[3][2][2] = {
-#define PQPS_AGG_SCAN(P, U64, V, NT) {agg_scan_kernel<P, U64, NT>, "agg_scan_kernel<" #P ", " V ", NT=" #NT ">"}
-        {{PQPS_AGG_SCAN(AGG_ONE, false, "i32", false), PQPS_AGG_SCAN(AGG_ONE, false, "i32", true)},
-         {PQPS_AGG_SCAN(AGG_ONE, true, "u64", false), PQPS_AGG_SCAN(AGG_ONE, true, "u64", true)}},
-        {{PQPS_AGG_SCAN(AGG_LDS, false, "i32", false), PQPS_AGG_SCAN(AGG_LDS, false, "i32", true)},
-         {PQPS_AGG_SCAN(AGG_LDS, true, "u64", false), PQPS_AGG_SCAN(AGG_LDS, true, "u64", true)}},
-        {{PQPS_AGG_SCAN(AGG_GLOBAL, false, "i32", false), PQPS_AGG_SCAN(AGG_GLOBAL, false, "i32", true)},
-         {PQPS_AGG_SCAN(AGG_GLOBAL, true, "u64", false), PQPS_AGG_SCAN(AGG_GLOBAL, true, "u64", true)}},
-#undef PQPS_AGG_SCAN
-    };
-    const auto &scan = fns[path][u64 ? 1 : 0][g.e.streaming ? 1 : 0];
-    snprintf(g_kernel, sizeof g_kernel, "%s", scan.name);
-    hipEvent_t stop;
-    rc = fused_launch(ctx, scan.fn, grid, table_bytes, s, g, &stop);
-    if (rc) return rc;
-    if (path != AGG_GLOBAL) {
-        const dim3 sg((n_bins + 63u) / 64u, (grid + kAggSumParts - 1) / kAggSumParts);
-        rc = launch_stop(agg_sum_kernel, sg, 0, s, stop, (const uint64_t *)ctx->group_parts, grid, n_bins, out);
-        if (rc) return rc;
-    }
-    fused_close(ctx, stop, path == AGG_GLOBAL);
-    return PQPS_OK;
-}
-
-int pqps_aggregate_list(pqps_ctx *ctx, const pqps_column *value_col, const pqps_column *group_col, uint64_t n_rows,
-                        const uint32_t *ids, const uint64_t *count_dev, uint64_t capacity, uint32_t id_base, uint32_t bin_base,
-                        uint32_t n_bins, uint64_t *out, void *stream) {
-    if (!ctx || !out || !count_dev || (capacity && !ids)) return fail(PQPS_EINVAL, "NULL argument");
-    uint32_t wl;
-    int rc = check_aggregate_cols(value_col, group_col, n_bins, false, &wl);
-    if (rc) return rc;
-    hipStream_t s = pick_stream(ctx, stream);
-    rc = init_aggregate_out(out, n_bins, s);
-    if (rc || capacity == 0 || n_rows == 0) return rc;
-    const void *gdata = group_col ? group_col->data : nullptr;
-    const int path = !group_col ? AGG_ONE : n_bins <= kAggLdsBins ? AGG_LDS : AGG_GLOBAL;
-    const uint32_t lds = path == AGG_LDS ? n_bins * (uint32_t)(3 * sizeof(uint64_t) + sizeof(uint32_t)) : 0u;
-    typedef void (*list_fn)(const void *, const void *, uint32_t, uint64_t, const uint32_t *, const uint64_t *, uint64_t, uint32_t,
-                            uint32_t, uint32_t, uint64_t *);
-    static const list_fn fns[3][2] = {
-        {agg_list_kernel<AGG_ONE, false>, agg_list_kernel<AGG_ONE, true>},
-        {agg_list_kernel<AGG_LDS, false>, agg_list_kernel<AGG_LDS, true>},
-        {agg_list_kernel<AGG_GLOBAL, false>, agg_list_kernel<AGG_GLOBAL, true>},
-    };
-    hipLaunchKernelGGL(fns[path][value_col->width == 8 ? 1 : 0], dim3(list_grid(ctx, capacity, 4)), dim3(kBlock), lds, s,
-                       value_col->data, gdata, wl, n_rows, ids, count_dev, capacity, id_base, bin_base, n_bins, out);
-    HIP_TRY(hipGetLastError());
-    return PQPS_OK;
-}
-
-// ---- GROUP BY buckets (bucket_kernels.hpp) ---------------------------------------------------------------------------
-// The bins path and where the bounds live, by the number of buckets (the limits: bucket_kernels.hpp).  `small_ok`: the
-// per-lane counters of the COUNT scan.  *lds = the dynamic LDS of a workgroup.
-static int bucket_path(uint32_t nb, bool valued, bool small_ok, bool *blds, uint32_t *lds) {
-    const uint32_t bounds_bytes = (nb + 1u) * (uint32_t)sizeof(uint32_t);
-    const uint32_t lds_max = valued ? kBucketAggLds : kBucketCountLds;
-    const int path = !valued && small_ok && nb <= kBucketSmall ? BUCKET_SMALL : nb <= lds_max ? BUCKET_LDS : BUCKET_GLOBAL;
-    *blds = nb <= kBucketBoundsLds;
-    *lds = (*blds ? bounds_bytes : 0u) + (path == BUCKET_LDS ? nb * (valued ? kBucketAggBinBytes : (uint32_t)sizeof(uint32_t)) : 0u);
-    return path;
-}
-
-static int check_buckets(const uint32_t *bounds_dev, uint32_t n_buckets, uint32_t domain) {
-    if (n_buckets == 0 || n_buckets > kBucketMax) return fail(PQPS_EINVAL, "%u buckets: 1 .. %u", n_buckets, kBucketMax);
-    if (!bounds_dev) return fail(PQPS_EINVAL, "bounds is NULL");
-    if (domain == 0 || domain < n_buckets) return fail(PQPS_EINVAL, "domain %u: at least one bin per bucket (%u)", domain, n_buckets);
-    return PQPS_OK;
-}
-
-static uint32_t bucket_top(uint32_t n_buckets) {
-    uint32_t top = 1;
-    while (top * 2u <= n_buckets + 1u) top *= 2u;
-    return top;
-}
-
-// the output of the four calls: n_buckets u32 bins, or the [4][n_buckets] u64 fields of pqps_filter_aggregate
-static int init_bucket_out(void *out, uint32_t n_buckets, bool valued, hipStream_t s) {
-    if (valued) return init_aggregate_out((uint64_t *)out, n_buckets, s);
-    HIP_TRY(hipMemsetAsync(out, 0, (size_t)n_buckets * sizeof(uint32_t), s));
-    return PQPS_OK;
-}
-
-// value_col == NULL: COUNT(*) per bucket
-static int filter_buckets(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
-                          const pqps_column *value_col, const pqps_column *group_col, uint32_t bin_base, const uint32_t *bounds_dev,
-                          uint32_t n_buckets, uint32_t domain, void *out, void *stream) {
-    if (!ctx || !group_col || !out) return fail(PQPS_EINVAL, "ctx/group_col/out is NULL");
-    const bool valued = value_col != nullptr;
-    BucketArgs g;
-    memset(&g, 0, sizeof g);
-    int rc = check_buckets(bounds_dev, n_buckets, domain);
-    if (rc == PQPS_OK) rc = valued ? check_aggregate_cols(value_col, group_col, n_buckets, false, &g.gwidth_log2)
-                                   : column_width_code("group", group_col, false, false, true, &g.gwidth_log2);
-    if (rc == PQPS_OK) rc = fused_args(g.e, cols, n_cols, n_rows, pred);
-    if (rc) return rc;
-    hipStream_t s = pick_stream(ctx, stream);
-    rc = init_bucket_out(out, n_buckets, valued, s);
-    if (rc || n_rows == 0) return rc;
-    bool blds;
-    uint32_t lds;
-    const int path = bucket_path(n_buckets, valued, true, &blds, &lds);
-    const uint32_t grid = fused_grid(ctx, n_rows, lds);
-    const uint32_t stride = (n_buckets + 63u) & ~63u;
-    if (path != BUCKET_GLOBAL) {
-        rc = grow_group_parts(ctx, s, valued ? (size_t)grid * kAggFields * n_buckets * 2 : (size_t)grid * stride);
-        if (rc) return rc;
-    }
-    g.gcol = group_col->data;
-    g.vcol = valued ? value_col->data : nullptr;
-    g.bounds = bounds_dev;
-    g.out = out;
-    g.parts = ctx->group_parts;
-    g.stride = stride;
-    g.bin_base = bin_base;
-    g.n_buckets = n_buckets;
-    g.top = bucket_top(n_buckets);
-    const int nt = g.e.streaming ? 1 : 0;
-    // the instances and their names side by side: pqps_last_kernel() reports the entry that is launched.  Index: SMALL, LDS,
-    // GLOBAL with the bounds in LDS, GLOBAL with the bounds in global memory (the aggregates have no SMALL).
-    typedef struct { void (*fn)(const BucketArgs); const char *name; } entry;
-    static const entry count_fns[4][2] = {
-#define PQPS_BUCKET_SCAN(P, B, NT) {bucket_scan_kernel<P, B, NT>, "bucket_scan_kernel<" #P ", BLDS=" #B ", NT=" #NT ">"}
-        {PQPS_BUCKET_SCAN(BUCKET_SMALL, true, false), PQPS_BUCKET_SCAN(BUCKET_SMALL, true, true)},
-        {PQPS_BUCKET_SCAN(BUCKET_LDS, true, false), PQPS_BUCKET_SCAN(BUCKET_LDS, true, true)},
-        {PQPS_BUCKET_SCAN(BUCKET_GLOBAL, true, false), PQPS_BUCKET_SCAN(BUCKET_GLOBAL, true, true)},
-        {PQPS_BUCKET_SCAN(BUCKET_GLOBAL, false, false), PQPS_BUCKET_SCAN(BUCKET_GLOBAL, false, true)},
-#undef PQPS_BUCKET_SCAN
-    };
-    static const entry agg_fns[4][2][2] = {
-#define PQPS_BUCKET_AGG(P, B, U64, V, NT) {bucket_agg_scan_kernel<P, B, U64, NT>, "bucket_agg_scan_kernel<" #P ", BLDS=" #B ", " V ", NT=" #NT ">"}
-#define PQPS_BUCKET_AGG4(P, B) {{PQPS_BUCKET_AGG(P, B, false, "i32", false), PQPS_BUCKET_AGG(P, B, false, "i32", true)}, \
-                                {PQPS_BUCKET_AGG(P, B, true, "u64", false), PQPS_BUCKET_AGG(P, B, true, "u64", true)}}
-        {{{nullptr, ""}, {nullptr, ""}}, {{nullptr, ""}, {nullptr, ""}}},
-        PQPS_BUCKET_AGG4(BUCKET_LDS, true),
-        PQPS_BUCKET_AGG4(BUCKET_GLOBAL, true),
-        PQPS_BUCKET_AGG4(BUCKET_GLOBAL, false),
-#undef PQPS_BUCKET_AGG4
-#undef PQPS_BUCKET_AGG
-    };
-    const int row = path == BUCKET_GLOBAL && !blds ? 3 : path;
-    const entry &scan = valued ? agg_fns[row][value_col->width == 8 ? 1 : 0][nt] : count_fns[row][nt];
-    snprintf(g_kernel, sizeof g_kernel, "%s", scan.name);
-    hipEvent_t stop;
-    rc = fused_launch(ctx, scan.fn, grid, lds, s, g, &stop);
-    if (rc) return rc;
-    if (path != BUCKET_GLOBAL) {
-        if (valued) {
-            const dim3 sg((n_buckets + 63u) / 64u, (grid + kAggSumParts - 1) / kAggSumParts);
-            rc = launch_stop(agg_sum_kernel, sg, 0, s, stop, (const uint64_t *)ctx->group_parts, grid, n_buckets, (uint64_t *)out);
-        } else {
-            const dim3 sg(stride / 64u, (grid + kGroupSumParts - 1) / kGroupSumParts);
-            rc = launch_stop(group_sum_kernel, sg, 0, s, stop, (const uint32_t *)ctx->group_parts, grid, stride, n_buckets, (uint32_t *)out);
-        }
-        if (rc) return rc;
-    }
-    fused_close(ctx, stop, path == BUCKET_GLOBAL);
-    return PQPS_OK;
-}
-
-static int list_buckets(pqps_ctx *ctx, const pqps_column *value_col, const pqps_column *group_col, uint64_t n_rows, const uint32_t *ids,
-                        const uint64_t *count_dev, uint64_t capacity, uint32_t id_base, uint32_t bin_base, const uint32_t *bounds_dev,
-                        uint32_t n_buckets, uint32_t domain, void *out, void *stream) {
-    if (!ctx || !group_col || !out || !count_dev || (capacity && !ids)) return fail(PQPS_EINVAL, "NULL argument");
-    const bool valued = value_col != nullptr;
-    BucketListArgs g;
-    memset(&g, 0, sizeof g);
-    int rc = check_buckets(bounds_dev, n_buckets, domain);
-    if (rc == PQPS_OK) rc = valued ? check_aggregate_cols(value_col, group_col, n_buckets, false, &g.gwidth_log2)
-                                   : column_width_code("group", group_col, false, false, false, &g.gwidth_log2);   // gathered by row
-    if (rc) return rc;
-    hipStream_t s = pick_stream(ctx, stream);
-    rc = init_bucket_out(out, n_buckets, valued, s);
-    if (rc || capacity == 0 || n_rows == 0) return rc;
-    bool blds;
-    uint32_t lds;
-    const int path = bucket_path(n_buckets, valued, false, &blds, &lds);
-    g.gcol = group_col->data;
-    g.vcol = valued ? value_col->data : nullptr;
-    g.bounds = bounds_dev;
-    g.ids = ids;
-    g.count = count_dev;
-    g.out = out;
-    g.n_rows = n_rows;
-    g.capacity = capacity;
-    g.id_base = id_base;
-    g.bin_base = bin_base;
-    g.n_buckets = n_buckets;
-    g.top = bucket_top(n_buckets);
-    typedef void (*list_fn)(const BucketListArgs);
-    // LDS, GLOBAL with the bounds in LDS, GLOBAL with the bounds in global memory
-    static const list_fn count_fns[3] = {bucket_list_kernel<BUCKET_LDS, true>, bucket_list_kernel<BUCKET_GLOBAL, true>,
-                                         bucket_list_kernel<BUCKET_GLOBAL, false>};
-    static const list_fn agg_fns[3][2] = {
-        {bucket_agg_list_kernel<BUCKET_LDS, true, false>, bucket_agg_list_kernel<BUCKET_LDS, true, true>},
-        {bucket_agg_list_kernel<BUCKET_GLOBAL, true, false>, bucket_agg_list_kernel<BUCKET_GLOBAL, true, true>},
-        {bucket_agg_list_kernel<BUCKET_GLOBAL, false, false>, bucket_agg_list_kernel<BUCKET_GLOBAL, false, true>},
-    };
-    const int row = path == BUCKET_LDS ? 0 : blds ? 1 : 2;
-    hipLaunchKernelGGL(valued ? agg_fns[row][value_col->width == 8 ? 1 : 0] : count_fns[row], dim3(list_grid(ctx, capacity, 4)), dim3(kBlock),
-                       lds, s, g);
-    HIP_TRY(hipGetLastError());
-    return PQPS_OK;
-}
-
-int pqps_filter_group_buckets(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
-                              const pqps_column *group_col, uint32_t bin_base, const uint32_t *bounds_dev, uint32_t n_buckets,
-                              uint32_t domain, uint32_t *bins, void *stream) {
-    return filter_buckets(ctx, cols, n_cols, n_rows, pred, nullptr, group_col, bin_base, bounds_dev, n_buckets, domain, bins, stream);
-}
-
-int pqps_group_buckets_list(pqps_ctx *ctx, const pqps_column *group_col, uint64_t n_rows, const uint32_t *ids, const uint64_t *count_dev,
-                            uint64_t capacity, uint32_t id_base, uint32_t bin_base, const uint32_t *bounds_dev, uint32_t n_buckets,
-                            uint32_t domain, uint32_t *bins, void *stream) {
-    return list_buckets(ctx, nullptr, group_col, n_rows, ids, count_dev, capacity, id_base, bin_base, bounds_dev, n_buckets, domain, bins, stream);
-}
-
-int pqps_filter_aggregate_buckets(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
-                                  const pqps_column *value_col, const pqps_column *group_col, uint32_t bin_base,
-                                  const uint32_t *bounds_dev, uint32_t n_buckets, uint32_t domain, uint64_t *out, void *stream) {
-    if (!value_col) return fail(PQPS_EINVAL, "value column is NULL");
-    return filter_buckets(ctx, cols, n_cols, n_rows, pred, value_col, group_col, bin_base, bounds_dev, n_buckets, domain, out, stream);
-}
-
-int pqps_aggregate_buckets_list(pqps_ctx *ctx, const pqps_column *value_col, const pqps_column *group_col, uint64_t n_rows,
-                                const uint32_t *ids, const uint64_t *count_dev, uint64_t capacity, uint32_t id_base, uint32_t bin_base,
-                                const uint32_t *bounds_dev, uint32_t n_buckets, uint32_t domain, uint64_t *out, void *stream) {
-    if (!value_col) return fail(PQPS_EINVAL, "value column is NULL");
-    return list_buckets(ctx, value_col, group_col, n_rows, ids, count_dev, capacity, id_base, bin_base, bounds_dev, n_buckets, domain, out, stream);
 }
 
 // ---- ORDER BY column [DESC] LIMIT K (topk_kernels.hpp) --------------------------------------------------------------
@@ -3720,7 +3685,7 @@ static int check_first_cols(const pqps_column *key_col, const pqps_column *group
     if (rc) return rc;
     if (*wide && !best) return fail(PQPS_EINVAL, "an 8-byte key column needs `best`");
     if (!group_col) return n_bins == 1 ? PQPS_OK : fail(PQPS_EINVAL, "no group column: 1 bin, not %u", n_bins);
-    if (n_bins == 0 || n_bins > kGroupMaxBins) return fail(PQPS_EINVAL, "%u bins: 1 .. %u", n_bins, kGroupMaxBins);
+    if (n_bins == 0 || n_bins > kBinsMax) return fail(PQPS_EINVAL, "%u bins: 1 .. %u", n_bins, kBinsMax);
     return column_width_code("group", group_col, plane_ok, false, plane_ok, gwl);
 }
 
@@ -3840,7 +3805,7 @@ static int check_distinct_bins(const pqps_column *value_col, const pqps_column *
     *gwl = 0;
     if (!group_col && n_groups != 1) return fail(PQPS_EINVAL, "no group column: 1 group, not %u", n_groups);
     if (group_col && (rc = column_width_code("group", group_col, plane_ok, false, true, gwl)) != 0) return rc;
-    if (n_values == 0 || n_groups == 0 || n_groups > kGroupMaxBins) return fail(PQPS_EINVAL, "%u values x %u groups", n_values, n_groups);
+    if (n_values == 0 || n_groups == 0 || n_groups > kBinsMax) return fail(PQPS_EINVAL, "%u values x %u groups", n_values, n_groups);
     if (pqps_distinct_bitmap_words(n_values, n_groups) * 32 > kDistMaxBits)
         return fail(PQPS_EINVAL, "%u values x %u groups: over the bitmap cap of 2^30 bits", n_values, n_groups);
     return PQPS_OK;
@@ -3963,7 +3928,7 @@ int pqps_distinct_sort(pqps_ctx *ctx, const pqps_column *value_col, uint32_t v_b
                        uint32_t n_groups, const uint32_t *ids, uint64_t n, uint32_t id_base, uint64_t *distinct, uint64_t *out_keys,
                        void *stream) {
     if (!ctx || !value_col || !distinct || (n && !ids)) return fail(PQPS_EINVAL, "NULL argument");
-    if (n_groups == 0 || n_groups > kGroupMaxBins || (!group_col && n_groups != 1)) return fail(PQPS_EINVAL, "%u groups", n_groups);
+    if (n_groups == 0 || n_groups > kBinsMax || (!group_col && n_groups != 1)) return fail(PQPS_EINVAL, "%u groups", n_groups);
     const bool wide = value_col->width == 8;
     uint32_t vwl, gwl = 0;
     int rc = column_width_code("value", value_col, false, true, true, &vwl);
@@ -4040,126 +4005,7 @@ int pqps_distinct_sort(pqps_ctx *ctx, const pqps_column *value_col, uint32_t v_b
     return PQPS_OK;
 }
 
-// ---- GROUP BY two columns (group_pair_kernels.hpp) -------------------------------------------------------------------
-// D = n_a x n_b in 64 bits; the dense calls take 1 .. 65 536.  *awl / *bwl / *val: the width codes and the PairValue.
-static int check_pair_cols(const pqps_column *a_col, uint32_t n_a, const pqps_column *b_col, uint32_t n_b, const pqps_column *value_col,
-                           bool dense, bool plane_ok, bool aligned, uint32_t *awl, uint32_t *bwl, int *val) {
-    if (!a_col || !b_col) return fail(PQPS_EINVAL, "a group column is NULL");
-    const uint64_t D = (uint64_t)n_a * n_b;
-    if (D == 0 || n_a > kGroupMaxBins || n_b > kGroupMaxBins || (dense && D > kGroupMaxBins))
-        return fail(PQPS_EINVAL, "%u x %u bins: 1 .. %u each%s", n_a, n_b, kGroupMaxBins, dense ? " and in all" : "");
-    int rc = column_width_code("group", a_col, plane_ok, false, aligned, awl);
-    if (rc == PQPS_OK) rc = column_width_code("group", b_col, plane_ok, false, aligned, bwl);
-    if (rc) return rc;
-    *val = PAIR_COUNT;
-    if (value_col) {
-        if (value_col->width != 4 && value_col->width != 8) return fail(PQPS_EINVAL, "value column: width %u not in {4,8}", value_col->width);
-        if (!value_col->data || ((uintptr_t)value_col->data & 15u) != 0) return fail(PQPS_EINVAL, "value column: NULL or not 16-byte aligned");
-        *val = value_col->width == 8 ? PAIR_U64 : PAIR_I32;
-    }
-    return PQPS_OK;
-}
-
-// the dense calls' output: D u32 bins, or the [4][D] u64 fields of pqps_filter_aggregate
-static int init_pair_out(void *out, uint32_t D, int val, hipStream_t s) {
-    if (val != PAIR_COUNT) return init_aggregate_out((uint64_t *)out, D, s);
-    HIP_TRY(hipMemsetAsync(out, 0, (size_t)D * sizeof(uint32_t), s));
-    return PQPS_OK;
-}
-
-static uint32_t pair_lds_bytes(uint32_t D, int val, bool *lds) {
-    *lds = val == PAIR_COUNT ? D <= kGroupLdsBins : D <= kAggLdsBins;
-    if (!*lds) return 0u;
-    return val == PAIR_COUNT ? D * (uint32_t)sizeof(uint32_t) : D * (uint32_t)(3 * sizeof(uint64_t) + sizeof(uint32_t));
-}
-
-int pqps_filter_group_pair(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
-                           const pqps_column *a_col, uint32_t a_base, uint32_t n_a, const pqps_column *b_col, uint32_t b_base,
-                           uint32_t n_b, const pqps_column *value_col, void *out, void *stream) {
-    if (!ctx || !out) return fail(PQPS_EINVAL, "ctx/out is NULL");
-    PairArgs g;
-    memset(&g, 0, sizeof g);
-    int val;
-    int rc = check_pair_cols(a_col, n_a, b_col, n_b, value_col, true, true, true, &g.awidth_log2, &g.bwidth_log2, &val);
-    if (rc == PQPS_OK) rc = fused_args(g.e, cols, n_cols, n_rows, pred);
-    if (rc) return rc;
-    const uint32_t D = n_a * n_b;
-    hipStream_t s = pick_stream(ctx, stream);
-    rc = init_pair_out(out, D, val, s);
-    if (rc || n_rows == 0) return rc;
-    bool lds;
-    const uint32_t lds_bytes = pair_lds_bytes(D, val, &lds);
-    const uint32_t grid = fused_grid(ctx, n_rows, lds_bytes);
-    const uint32_t stride = (D + 63u) & ~63u;
-    if (lds) {
-        rc = grow_group_parts(ctx, s, val == PAIR_COUNT ? (size_t)grid * stride : (size_t)grid * kAggFields * D * 2);
-        if (rc) return rc;
-    }
-    g.acol = a_col->data;
-    g.bcol = b_col->data;
-    g.vcol = value_col ? value_col->data : nullptr;
-    g.bins = (uint32_t *)out;
-    g.out = (uint64_t *)out;
-    g.parts = ctx->group_parts;
-    g.stride = stride;
-    g.a_base = a_base;
-    g.b_base = b_base;
-    g.n_a = n_a;
-    g.n_b = n_b;
-    // the instance and its name side by side: pqps_last_kernel() reports the entry that is launched
-    static const struct { void (*fn)(const PairArgs); const char *name; } fns[2][3][2] = {
-#define PQPS_PAIR_SCAN(P, V, NT) {pair_scan_kernel<P, V, NT>, "pair_scan_kernel<" #P ", " #V ", NT=" #NT ">"}
-        {{PQPS_PAIR_SCAN(PAIR_LDS, PAIR_COUNT, false), PQPS_PAIR_SCAN(PAIR_LDS, PAIR_COUNT, true)},
-         {PQPS_PAIR_SCAN(PAIR_LDS, PAIR_I32, false), PQPS_PAIR_SCAN(PAIR_LDS, PAIR_I32, true)},
-         {PQPS_PAIR_SCAN(PAIR_LDS, PAIR_U64, false), PQPS_PAIR_SCAN(PAIR_LDS, PAIR_U64, true)}},
-        {{PQPS_PAIR_SCAN(PAIR_GLOBAL, PAIR_COUNT, false), PQPS_PAIR_SCAN(PAIR_GLOBAL, PAIR_COUNT, true)},
-         {PQPS_PAIR_SCAN(PAIR_GLOBAL, PAIR_I32, false), PQPS_PAIR_SCAN(PAIR_GLOBAL, PAIR_I32, true)},
-         {PQPS_PAIR_SCAN(PAIR_GLOBAL, PAIR_U64, false), PQPS_PAIR_SCAN(PAIR_GLOBAL, PAIR_U64, true)}},
-#undef PQPS_PAIR_SCAN
-    };
-    const auto &scan = fns[lds ? PAIR_LDS : PAIR_GLOBAL][val][g.e.streaming ? 1 : 0];
-    snprintf(g_kernel, sizeof g_kernel, "%s", scan.name);
-    hipEvent_t stop;
-    rc = fused_launch(ctx, scan.fn, grid, lds_bytes, s, g, &stop);
-    if (rc) return rc;
-    if (lds && val == PAIR_COUNT) {
-        const dim3 sg(stride / 64u, (grid + kGroupSumParts - 1) / kGroupSumParts);
-        rc = launch_stop(group_sum_kernel, sg, 0, s, stop, (const uint32_t *)ctx->group_parts, grid, stride, D, (uint32_t *)out);
-    } else if (lds) {
-        const dim3 sg((D + 63u) / 64u, (grid + kAggSumParts - 1) / kAggSumParts);
-        rc = launch_stop(agg_sum_kernel, sg, 0, s, stop, (const uint64_t *)ctx->group_parts, grid, D, (uint64_t *)out);
-    }
-    fused_close(ctx, stop, !lds);
-    return rc;
-}
-
-int pqps_group_pair_list(pqps_ctx *ctx, const pqps_column *a_col, uint32_t a_base, uint32_t n_a, const pqps_column *b_col, uint32_t b_base,
-                         uint32_t n_b, const pqps_column *value_col, uint64_t n_rows, const uint32_t *ids, const uint64_t *count_dev,
-                         uint64_t capacity, uint32_t id_base, void *out, void *stream) {
-    if (!ctx || !out || !count_dev || (capacity && !ids)) return fail(PQPS_EINVAL, "NULL argument");
-    uint32_t awl, bwl;
-    int val;
-    int rc = check_pair_cols(a_col, n_a, b_col, n_b, value_col, true, false, false, &awl, &bwl, &val);   // gathered by row: any alignment
-    if (rc) return rc;
-    const uint32_t D = n_a * n_b;
-    hipStream_t s = pick_stream(ctx, stream);
-    rc = init_pair_out(out, D, val, s);
-    if (rc || capacity == 0 || n_rows == 0) return rc;
-    bool lds;
-    const uint32_t lds_bytes = pair_lds_bytes(D, val, &lds);
-    typedef void (*list_fn)(const void *, uint32_t, const void *, uint32_t, const void *, uint64_t, const uint32_t *, const uint64_t *, uint64_t,
-                            uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, void *);
-    static const list_fn fns[2][3] = {
-        {pair_list_kernel<false, PAIR_COUNT>, pair_list_kernel<false, PAIR_I32>, pair_list_kernel<false, PAIR_U64>},
-        {pair_list_kernel<true, PAIR_COUNT>, pair_list_kernel<true, PAIR_I32>, pair_list_kernel<true, PAIR_U64>},
-    };
-    snprintf(g_kernel, sizeof g_kernel, "pair_list_kernel<LDS=%s, %s>", lds ? "true" : "false", val == PAIR_COUNT ? "PAIR_COUNT" : val == PAIR_I32 ? "PAIR_I32" : "PAIR_U64");
-    hipLaunchKernelGGL(fns[lds ? 1 : 0][val], dim3(list_grid(ctx, capacity, 4)), dim3(kBlock), lds_bytes, s, a_col->data, awl, b_col->data, bwl,
-                       value_col ? value_col->data : nullptr, n_rows, ids, count_dev, capacity, id_base, a_base, b_base, n_a, n_b, out);
-    HIP_TRY(hipGetLastError());
-    return PQPS_OK;
-}
-
+// ---- GROUP BY two columns, sparse: sort and reduce runs (group_pair_kernels.hpp) ------------------------------------
 int pqps_group_pair_sort(pqps_ctx *ctx, const pqps_column *a_col, uint32_t a_base, uint32_t n_a, const pqps_column *b_col, uint32_t b_base,
                          uint32_t n_b, const pqps_column *value_col, uint64_t n_rows, const uint32_t *ids, uint64_t n, uint32_t id_base,
                          uint64_t **runs_dev, uint64_t *n_runs, void *stream) {
@@ -4167,16 +4013,16 @@ int pqps_group_pair_sort(pqps_ctx *ctx, const pqps_column *a_col, uint32_t a_bas
     *runs_dev = nullptr;
     *n_runs = 0;
     uint32_t awl, bwl;
-    int val;
-    int rc = check_pair_cols(a_col, n_a, b_col, n_b, value_col, false, false, false, &awl, &bwl, &val);
+    const int rc = check_pair_cols(a_col, n_a, b_col, n_b, value_col, false, false, false, &awl, &bwl);
     if (rc) return rc;
+    const int val = !value_col ? BINS_COUNT : value_col->width == 8 ? BINS_U64 : BINS_I32;
     if (n >= 0xFFFFFFFFull) return fail(PQPS_EINVAL, "a list of %llu rows", (unsigned long long)n);
     hipStream_t s = pick_stream(ctx, stream);
-    snprintf(g_kernel, sizeof g_kernel, "pair_runs_kernel<%s> (sort)", val == PAIR_COUNT ? "PAIR_COUNT" : val == PAIR_I32 ? "PAIR_I32" : "PAIR_U64");
+    snprintf(g_kernel, sizeof g_kernel, "pair_runs_kernel<%s> (sort)", kPairValueName[val]);
     if (n == 0 || n_rows == 0) { HIP_TRY(hipStreamSynchronize(s)); return PQPS_OK; }
     const uint64_t tiles = (n + 63) / 64, m = tiles + 1;        // heads[tiles] receives the number of runs
     const uint32_t scan_blocks = (uint32_t)((m + pqps_sort::kScanBlock - 1) / pqps_sort::kScanBlock);
-    const uint32_t fields = val == PAIR_COUNT ? 2u : 5u;        // keys, counts [, sums, min images, max images]
+    const uint32_t fields = val == BINS_COUNT ? 2u : 5u;        // keys, counts [, sums, min images, max images]
     pqps_sort::Workspace w;
     uint64_t *ka = nullptr, *kb = nullptr, *out = nullptr;
     uint32_t *ra = nullptr, *rb = nullptr, *heads = nullptr, *sums = nullptr;
@@ -4214,10 +4060,10 @@ int pqps_group_pair_sort(pqps_ctx *ctx, const pqps_column *a_col, uint32_t a_bas
     if (e == hipSuccess && runs) {
         e = hipMalloc((void **)&out, (size_t)fields * runs * 8);
         if (e == hipSuccess) e = hipMemsetAsync(out, 0, (size_t)fields * runs * 8, s);
-        if (e == hipSuccess && val != PAIR_COUNT) e = hipMemsetAsync(out + 3 * (size_t)runs, 0xFF, (size_t)runs * 8, s);
+        if (e == hipSuccess && val != BINS_COUNT) e = hipMemsetAsync(out + 3 * (size_t)runs, 0xFF, (size_t)runs * 8, s);
         if (e == hipSuccess) {
             typedef void (*runs_fn)(const uint64_t *, const uint32_t *, uint64_t, uint64_t, const uint32_t *, const void *, uint64_t, uint64_t *);
-            static const runs_fn fns[3] = {pair_runs_kernel<PAIR_COUNT>, pair_runs_kernel<PAIR_I32>, pair_runs_kernel<PAIR_U64>};
+            static const runs_fn fns[3] = {pair_runs_kernel<BINS_COUNT>, pair_runs_kernel<BINS_I32>, pair_runs_kernel<BINS_U64>};
             hipLaunchKernelGGL(fns[val], dim3(list_grid(ctx, n, 4)), dim3(kBlock), 0, s, keys, rows, n, tiles, (const uint32_t *)heads,
                                value_col ? value_col->data : nullptr, (uint64_t)runs, out);
             e = hipGetLastError();

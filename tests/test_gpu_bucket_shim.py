@@ -34,7 +34,7 @@ SIZES = (1, 1023, 1024, 1025, 4097, 300_001)
 VALS = (None, "val_i32", "val_u64")
 VAL_NAME = {"val_i32": "i32", "val_u64": "u64"}
 PREDS = fd.PRED_NAMES + ("last",)
-SMALL, COUNT_LDS, AGG_LDS, BOUNDS_LDS, MAX = 16, 8191, 2047, 16383, 65536     # the limits of csrc/bucket_kernels.hpp
+SMALL, COUNT_LDS, AGG_LDS, BOUNDS_LDS, MAX = 16, 8191, 2047, 16383, 65536     # the limits of csrc/bins_kernels.hpp
 # (group column width, buckets, kind, domain): "unit" one code per bucket, "whole" one bucket over the domain, "runs" random runs
 SHAPES = (
     (1, 1, "whole", 200), (2, 1, "whole", 65536), (4, 1, "whole", 1 << 31),
