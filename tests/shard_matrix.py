@@ -14,7 +14,10 @@ with the CPU model.  No expected answer comes from an engine.
 
 <devices> is the PQPS_DEVICES value the engines are created under ("0,0,0": three shards on one card).  Both print the number
 of cases and OK, or exit non-zero with the first case that differs.  PQPS_PROBE_BOOL=1 in the environment is followed by the
-model (BOOL indexes probed too)."""
+model (BOOL indexes probed too).
+
+Both ask from one thread.  tests/concurrent_matrix.py asks the same cases of the same table from several threads at once, and
+replays the history's writers (model_step / engine_step, recorded through History's `recorder`) under readers that never stop."""
 import ctypes as C
 import os
 import sys
@@ -320,13 +323,18 @@ def cases(model, indexes, probe_bool=False, routes=None, families=FAMILIES, full
     return out
 
 
-def tickets_in_flight(eng):
-    """Three tickets issued before the first is awaited; -> their answers (the IDs read from the device)."""
+def tickets_in_flight(eng, while_held=None):
+    """Three tickets issued before the first is awaited; -> their answers (the IDs read from the device).  `while_held` is
+    called with the three tickets held and none awaited."""
+    if not isinstance(eng, pq.HipEngine):
+        return eng.tickets_in_flight(while_held)                    # a stand-in without a device (tests/concurrent_matrix.py)
     tickets = [eng.select_async(ROUTES[r][0], count_only) for r, count_only in TICKETS]
     out = []
     ctx = pq.Context(0)
     try:
         assert all(tickets)
+        if while_held:
+            while_held()
         for tk, (_, count_only) in reversed(list(zip(tickets, TICKETS))):
             n, res = eng.await_ticket(tk)
             assert n >= 0
@@ -380,15 +388,57 @@ def run(devices, families=FAMILIES):
     print("CASES", count, "OK", flush=True)
 
 
-class History:
-    """An engine over table() with INDEXES, the model beside it; every writer is the model's prediction, refusals included."""
+# ---- a writer step: the model's prediction, the engine's call ------------------------------------------------------------------
+WRITERS = ("UPDATE", "batch INSERT", "INSERT", "DELETE")
 
-    def __init__(self, n_shards, dry=False):
+
+def model_step(model, kind, args):
+    """The step applied to the model; -> what the engine must return (rows matched / appended / deleted, True), None for a
+    step it must refuse (the model is unchanged then)."""
+    if kind == "UPDATE":
+        return model.update(*args)
+    if kind == "batch INSERT":
+        return model.insert_batch(*args)
+    if kind == "INSERT":
+        return model.insert_one(*args)
+    assert kind == "DELETE", kind
+    return model.delete(*args)
+
+
+def engine_step(eng, kind, args):
+    """The step asked of the engine; -> what it returned, "refused" for a refusal."""
+    if not isinstance(eng, pq.HipEngine):
+        return eng.writer(kind, args)                                # a stand-in without a device (tests/concurrent_matrix.py)
+    if kind == "UPDATE":
+        return ask(lambda: eng.update(*args))
+    if kind == "batch INSERT":
+        return ask(lambda: eng.insert_columns(cm.rows_of(args[0]), args[0]))
+    if kind == "INSERT":
+        r = pq.Record()
+        for column, value in args[0].items():
+            setattr(r, column, value)
+        return True if pq.lib().executeQueryInsertHIP(eng.e, b"commands", C.byref(r)) else "refused"
+    assert kind == "DELETE", kind
+    rs = pq.lib().executeQueryDeleteHIP(eng.e, b"commands", pq.WhereList(args[0]).ptr)
+    ok, k = bool(rs.contents.success), rs.contents.numRecords
+    pq.lib().freeResultSet(rs)
+    return k if ok else "refused"
+
+
+class History:
+    """An engine over table() with INDEXES, the model beside it; every writer is the model's prediction, refusals included.
+    `recorder(model, step)` is called with step None for the untouched table and with (kind, args, prediction) after every
+    writer has been applied to the model."""
+
+    def __init__(self, n_shards, dry=False, recorder=None):
         columns = table()
         self.model = cm.ColumnModel(columns, n_shards)
         self.eng = None if dry else pq.HipEngine.from_columns(N, columns, INDEXES)      # dry: the model's side alone, on the CPU
         self.probe_bool = os.environ.get("PQPS_PROBE_BOOL") == "1"
         self.log, self.count = [], 0
+        self.recorder = recorder
+        if recorder:
+            recorder(self.model, None)
 
     def check(self):
         eng, model = self.eng, self.model
@@ -400,41 +450,28 @@ class History:
         assert eng.n == model.n and eng.shards() == model.shard_rows, (eng.n, eng.shards(), model.shard_rows, self.log)
         self.count += compare(eng, todo, self.log)
 
-    def update(self, assignments, chain):
-        want = self.model.update(assignments, chain)
-        self.log.append(("UPDATE", assignments, want))
-        if self.eng is None:
-            return want
-        got = ask(lambda: self.eng.update(assignments, chain))
-        assert got == ("refused" if want is None else want), (got, self.log)
+    def step(self, kind, args, entry):
+        """One writer: the model first, then the engine, whose return must be the model's prediction."""
+        want = model_step(self.model, kind, args)
+        self.log.append(entry(want))
+        if self.recorder:
+            self.recorder(self.model, (kind, args, want))
+        if self.eng is not None:
+            got = engine_step(self.eng, kind, args)
+            assert got == ("refused" if want is None else want), (got, self.log)
         return want
+
+    def update(self, assignments, chain):
+        return self.step("UPDATE", (assignments, chain), lambda want: ("UPDATE", assignments, want))
 
     def batch(self, b):
-        want = self.model.insert_batch(b)
-        self.log.append(("batch INSERT", want, self.model.route))
-        assert self.eng is None or self.eng.insert_columns(cm.rows_of(b), b) == want, self.log
+        return self.step("batch INSERT", (b,), lambda want: ("batch INSERT", want, self.model.route))
 
     def insert(self, row):
-        want = self.model.insert_one(row)
-        self.log.append(("INSERT", want))
-        if self.eng is None:
-            return want
-        r = pq.Record()
-        for column, value in row.items():
-            setattr(r, column, value)
-        assert bool(pq.lib().executeQueryInsertHIP(self.eng.e, b"commands", C.byref(r))) == (want is True), self.log
-        return want
+        return self.step("INSERT", (row,), lambda want: ("INSERT", want))
 
     def delete(self, chain):
-        want = self.model.delete(chain)
-        self.log.append(("DELETE", want, list(self.model.shard_rows)))
-        if self.eng is None:
-            return want
-        rs = pq.lib().executeQueryDeleteHIP(self.eng.e, b"commands", pq.WhereList(chain).ptr)
-        ok, k = bool(rs.contents.success), rs.contents.numRecords
-        pq.lib().freeResultSet(rs)
-        assert ok and k == want, (ok, k, self.log)
-        return want
+        return self.step("DELETE", (chain,), lambda want: ("DELETE", want, list(self.model.shard_rows)))
 
 
 def one_row(command_id, **over):
@@ -444,10 +481,13 @@ def one_row(command_id, **over):
     return row
 
 
-def history(devices, dry=False):
+def history(devices, dry=False, recorder=None):
+    """The scripted writers; `recorder`: see History.  On a single shard (tests/concurrent_matrix.py) the same steps take their
+    row ranges from the three-shard layout, and what they say about shards 1 and -1 has nothing to hold for."""
     n_shards = len(devices.split(","))
-    first = starts(N, n_shards)
-    h = History(n_shards, dry)
+    sharded = n_shards > 1
+    first = starts(N, n_shards if sharded else LAYOUTS[0])
+    h = History(n_shards, dry, recorder)
     model = h.model
     try:
         for column in ("user_id", "risk_level"):                      # the i32 ranges cached before any writer
@@ -455,14 +495,14 @@ def history(devices, dry=False):
         h.check()
         # 1. exactly the rows of shard 1: an empty shard in the middle
         assert h.delete(rows_between(first[1], first[2] - 1)) == first[2] - first[1]
-        assert model.shard_rows[1] == 0 and all(model.shard_rows[:1] + model.shard_rows[2:])
+        assert not sharded or (model.shard_rows[1] == 0 and all(model.shard_rows[:1] + model.shard_rows[2:]))
         h.check()
         # 2. a WHERE that matches in the first and the last shard only: a string new to user_name (the codes are bumped on every
         #    shard, the empty one included) and an i32 past the cached range; then an UPDATE the engine must refuse
         chain = ROUTES["band_ends"][0]
         held = shard_counts(np.flatnonzero(model.mask(chain)), model.shard_rows)
         assert held[0] and held[-1] and not any(held[1:-1])
-        assert h.update({"user_name": "mmm-middle", "risk_level": 12}, chain) == held[0] + held[-1]
+        assert h.update({"user_name": "mmm-middle", "risk_level": 12}, chain) == sum(held)
         assert model.route == dict(bumped=["user_name"])
         h.check()
         assert h.update({"raw_command": "a second raw command"}, chain) is None
@@ -474,10 +514,10 @@ def history(devices, dry=False):
         # 4. the rows of the last shard: an empty shard at the end, after growth; then a single INSERT, and one refused
         last = rows_between(first[-2], N - 1)[0]
         assert h.delete([last, "OR", ("timestamp", ">=", "2026")]) == (N - first[-2]) + B
-        assert model.shard_rows[-1] == 0 and model.shard_rows[1] == 0
+        assert not sharded or (model.shard_rows[-1] == 0 and model.shard_rows[1] == 0)
         h.check()
         assert h.insert(one_row(7_000_001, user_name=b"aaa-first", timestamp=b"2027-01-01T00:00:00.000Z")) is True
-        assert model.shard_rows[-1] == 1
+        assert model.shard_rows[-1] == (1 if sharded else first[1] + 1)
         h.check()
         assert h.insert(one_row(7_000_002, raw_command=b"a second raw command")) is None
         # 5. everything deleted, then a batch into the empty table
@@ -490,7 +530,6 @@ def history(devices, dry=False):
     finally:
         if h.eng:
             h.eng.close()
-    print("CASES", h.count, "OK", flush=True)
     return h
 
 
@@ -500,7 +539,7 @@ def main(argv):
     if what == "run":
         run(devices, tuple(argv[3:]) or FAMILIES)
     elif what == "history":
-        history(devices)
+        print("CASES", history(devices).count, "OK", flush=True)
     else:
         raise SystemExit(f"shard_matrix: unknown command {what!r}")
 
