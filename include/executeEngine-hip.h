@@ -587,6 +587,59 @@ struct hipColumnarResult *executeQuerySelectGroupFirstHIP(struct engineS *engine
                                                           struct whereClauseS *whereClause, const char *groupColumn /* may be NULL */,
                                                           const char *orderColumn, bool descending, long long *matches);
 
+/* THE TOP N GROUPS: GROUP BY one column of ANY size, ORDER BY an aggregate [DESC], LIMIT n -- "the 20 most frequent commands",
+ * "the 10 users with the highest summed risk" (no aggregates in the reference; reached through the C API and the Python
+ * package only, like the grouped COUNT above).
+ * ROWS: exactly the rows executeQuerySelectIdsHIP(engine, whereClause) returns -- in index mode a row several probed conditions
+ * return counts that many times, as in executeQueryGroupCountHIP.
+ * GROUPS: the keys, key text and key order of executeQueryGroupCountHIP, but NOTHING is refused for the size of the column's
+ * domain: any dictionary (raw_command, timestamp of a large CSV) and any i32 span, INT_MIN .. INT_MAX (2^32 bins) included.
+ * VALUES (valueColumn, may be NULL: COUNT(*) only): as executeQueryAggregateHIP -- i32 sums exact in int64, command_id sums
+ * modulo 2^64 and its min / max unsigned, returned as the u64 bits.
+ * ORDER: by the aggregate `orderBy` names -- COUNT compares unsigned; SUM / MIN / MAX signed for an i32 value column and
+ * unsigned on the u64 bits for command_id -- ascending, or reversed when `descending`.  Groups whose aggregate is equal come
+ * in ascending key order in BOTH directions: the order is total, and the same for every shard layout and every path.
+ * HIPTOP_BY_KEY is the key order, or its reverse.  (hipGroupTopOrder of hipPredicate.h is the rule, as host code.)
+ * LIMIT: limit > 0 lists the first min(limit, groupsTotal) groups of that order, limit <= 0 all of them; `total` and
+ * `groupsTotal` describe the whole answer either way.
+ * A NULL WHERE groups the whole table; an empty table, or a WHERE that matches nothing, gives 0 groups with success = true; a
+ * single-valued string column gives one group from the selection, with no kernel.
+ * REFUSED (success = false, the reason on stderr): an unknown group or value column, command_id as the group column, a
+ * dictionary or boolean value column, orderBy outside the enum, HIPTOP_BY_SUM / _MIN / _MAX without a value column, an engine
+ * joined across ranks, a listing of more than INT_MAX groups (numGroups is an int: such an answer needs a LIMIT).  A reader
+ * like COUNT: shared lock and one query lane, the lane rules above apply; device buffers are
+ * allocated for the query and freed with it.
+ * Execution, per shard.  Up to 65 536 bins: the dense bins of executeQueryGroupCountHIP / executeQueryAggregateHIP.  Above,
+ * while the shard's bins (4 B each, 32 B with a value column) fit HIP_TOP_BINS_BUDGET: the wide bins in device memory behind
+ * an LDS front -- ONE fused launch for a single-pass scan-mode WHERE (pqps_filter_group_wide), otherwise the selection and
+ * pqps_group_wide_list over the shard's list -- compacted on the device to one entry per group that occurs
+ * (pqps_bins_compact), which is all that is downloaded.  Above the budget: the selection's list sorted by bin and reduced run
+ * by run (pqps_group_sort), the same compact format.  The shards' runs are merged
+ * by key on the host (counts and sums added, min and max taken), ordered by hipGroupTopOrder, and only the listed groups get
+ * their key text. */
+enum { HIPTOP_BY_KEY = 0, HIPTOP_BY_COUNT = 1, HIPTOP_BY_SUM = 2, HIPTOP_BY_MIN = 3, HIPTOP_BY_MAX = 4 };
+#define HIP_TOP_BINS_BUDGET (256ull << 20)   /* bytes of bins per shard: the part's 256 MiB of Infinity Cache */
+struct hipGroupTopResult {
+    int groupColumn, groupKind;        /* HIPCOL_*, HIPKIND_I32 / _BOOL / _DICT                            */
+    int valueColumn, valueKind;        /* HIPCOL_*, HIPKIND_I32 / HIPKIND_U64; -1 / -1: COUNT(*) only      */
+    int orderBy;                       /* HIPTOP_BY_*                                                      */
+    bool descending;
+    long long limit;
+    int numGroups;                     /* groups listed: min(limit, groupsTotal), all when limit <= 0      */
+    long long groupsTotal;             /* groups with at least one matching row                            */
+    long long total;                   /* executeQuerySelectIdsHIP's count, over ALL groups                */
+    long long *keys;                   /* as hipGroupResult, in the order asked for                        */
+    char **keyText;                    /* as hipGroupResult                                                */
+    unsigned long long *counts;
+    long long *sums, *mins, *maxs;     /* NULL without a value column; u64 bits for command_id             */
+    double queryTime;
+    bool success;
+};
+struct hipGroupTopResult *executeQueryGroupTopHIP(struct engineS *engine, const char *groupColumn,
+                                                  const char *valueColumn /* may be NULL */, int orderBy, bool descending,
+                                                  long long limit, struct whereClauseS *whereClause);
+void freeGroupTopResultHIP(struct hipGroupTopResult *result);
+
 /* COUNT(*) through the backend API (the reference parser cannot express it,
  * SURVEY.md fact 10): scan-mode count of matching rows, no ID list. */
 long long executeQueryCountHIP(struct engineS *engine, struct whereClauseS *whereClause);

@@ -195,6 +195,24 @@ struct hipOrderKeyPlan {
 int hipOrderKeyPlan(const char *const *columns, const int *descending, int n_keys, const int *dict_counts,
                     const int *lo, const int *hi, struct hipOrderKeyPlan *plan);
 
+/* THE ORDER OF "THE TOP N GROUPS" (executeQueryGroupTopHIP).  Orders the merged groups of a grouped answer by one of their
+ * aggregates and lists the first `limit` of them; pure host code.
+ *   INPUT   bins[0 .. n_groups): the groups' keys in bin space, all different (any order); counts; and, where order_by is
+ *           HIPTOP_BY_SUM / _MIN / _MAX, sums (the i32 sums as two's-complement int64 bits, command_id's mod 2^64), min_images,
+ *           max_images -- the u64 IMAGES of pqps_filter_aggregate, (u64)(i64)v ^ 2^63 for an i32 value and v itself for
+ *           command_id -- with value_kind = HIPKIND_I32 or HIPKIND_U64.  Arrays the order does not read may be NULL.
+ *   ORDER   HIPTOP_BY_KEY: the bin.  _COUNT: unsigned.  _SUM: signed for HIPKIND_I32, unsigned for HIPKIND_U64.  _MIN / _MAX:
+ *           the images, unsigned (that IS the signed order of i32 values).  Ascending, or reversed when `descending`; groups
+ *           that compare equal come in ascending bin order in BOTH directions, so the order is total.
+ *   OUTPUT  order[0 .. return value): indices into the input arrays, the listed groups in order; the return value is
+ *           min(limit, n_groups) for limit > 0 and n_groups for limit <= 0, and `order` has room for that many.
+ * A partial selection: a heap of `limit` entries over one pass when limit < n_groups, a sort otherwise.  Returns -1 with the
+ * reason on stderr and `order` untouched for: order_by outside the enum, a NULL array the order reads, a value_kind that is
+ * no number where sums are compared, out of memory.  (HIPTOP_BY_*: executeEngine-hip.h.) */
+long long hipGroupTopOrder(const uint64_t *bins, const uint64_t *counts, const uint64_t *sums, const uint64_t *min_images,
+                           const uint64_t *max_images, uint64_t n_groups, int value_kind, int order_by, int descending,
+                           long long limit, uint64_t *order);
+
 /* The number of values[0 .. count) (ascending in strcmp order) below `text`: its code when it is in the dictionary
  * (*present = 1), the rank it is inserted at otherwise (*present = 0). */
 int hipDictionaryRank(const char *const *values, int count, const char *text, int *present);

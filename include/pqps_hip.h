@@ -725,6 +725,46 @@ int pqps_group_pair_sort(pqps_ctx *ctx, const pqps_column *a_col, uint32_t a_bas
                          uint32_t n_b, const pqps_column *value_col, uint64_t n_rows, const uint32_t *ids, uint64_t n, uint32_t id_base,
                          uint64_t **runs_dev, uint64_t *n_runs, void *stream);
 
+/* ---- GROUP BY one column of any size: the wide bins, their compaction, and the sort form ------------------------------------
+ * No counterpart in the reference.  What the top-N groups query runs above the 65 536 bins of pqps_filter_group and
+ * pqps_filter_aggregate; those calls keep their limit.  BINS as theirs: (value - bin_base) in 32-bit arithmetic, a row whose
+ * bin is not below n_bins is left out, and whatever the column holds nothing is indexed out of range.  `group_col` 1, 2 or 4
+ * bytes wide (no bit plane); `value_col` NULL: COUNT(*) only, else 4 bytes (signed i32) or 8 bytes (u64).
+ * DENSE OUTPUT (`out`, device, the caller's): without a value column n_bins u32 counts, with one the [4][n_bins] u64 fields of
+ * pqps_filter_aggregate (counts, sums, min images, max images; a bin without rows reads 0, 0, UINT64_MAX, 0).
+ * RUN FORMAT (pqps_bins_compact, pqps_group_sort): that of pqps_group_pair_sort with key = the bin -- *n_runs (host) = the bins
+ *   that have rows, *runs_dev = device memory the call allocates (NULL for no runs; the caller frees it with pqps_free),
+ *   field-major, *n_runs u64 entries per field, ascending by key: keys, counts, and with a value sums, min images, max images.
+ *
+ * pqps_filter_group_wide: ONE scan of `pred` over rows [0, n_rows) of `cols` into `out`, any n_bins >= 1; the group and the
+ *   value column are read only in steps of 1024 rows that hold a match, the readable-padding rule of pqps_filter_scan applies
+ *   to them (16-byte aligned).  Every workgroup keeps a write-combining FRONT in LDS before the global atomics: a direct-mapped
+ *   table of PQPS_WIDE_COUNT_SLOTS (COUNT(*)) or PQPS_WIDE_VALUE_SLOTS slots, slot = bin mod slots, each a tag and an
+ *   accumulator.  A row whose slot is free or holds its bin is added in LDS; any other row goes to `out` with one global
+ *   atomic per field.  The first bin to arrive keeps its slot (no eviction); the workgroup ends by adding every claimed slot
+ *   to `out`.  pqps_ctx_set_option(ctx, "wide_front", 0) runs without the front (global atomics alone; < 0: the default, on).
+ *   The call initialises `out` and is asynchronous on `stream`; the timing recorder records the launch like a COUNT's.
+ * pqps_group_wide_list: the same over an ID list -- ids[0 .. min(*count_dev, capacity)), row = id - id_base; a row >= n_rows
+ *   is skipped -- gathering the columns per listed row (any alignment of `group_col`).
+ * pqps_bins_compact: dense bins (`valued` != 0: the [4][n_bins] fields) into the run format, in two launches of waves that
+ *   each take tiles of PQPS_COMPACT_TILE bins -- the bins with rows per tile, an exclusive scan, the writes; no workgroup
+ *   waits for another.  Synchronous.
+ * pqps_group_sort: the one-column form of pqps_group_pair_sort over ids[0 .. n) (n below 2^32 - 1), n_bins = 1 .. 2^32 as a
+ *   64-bit count: one key per listed row (its bin; rows outside the bins or the table are left out), the same sort and the
+ *   same run reduction.  Its runs equal pqps_bins_compact's of the same rows.  Synchronous. */
+#define PQPS_COMPACT_TILE      1024u
+#define PQPS_WIDE_COUNT_SLOTS  8192u
+#define PQPS_WIDE_VALUE_SLOTS  2048u
+int pqps_filter_group_wide(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                           const pqps_column *value_col, const pqps_column *group_col, uint32_t bin_base, uint32_t n_bins,
+                           void *out, void *stream);
+int pqps_group_wide_list(pqps_ctx *ctx, const pqps_column *value_col, const pqps_column *group_col, uint64_t n_rows,
+                         const uint32_t *ids, const uint64_t *count_dev, uint64_t capacity, uint32_t id_base, uint32_t bin_base,
+                         uint32_t n_bins, void *out, void *stream);
+int pqps_bins_compact(pqps_ctx *ctx, const void *bins, uint32_t n_bins, int valued, uint64_t **runs_dev, uint64_t *n_runs, void *stream);
+int pqps_group_sort(pqps_ctx *ctx, const pqps_column *group_col, uint32_t bin_base, uint64_t n_bins, const pqps_column *value_col,
+                    uint64_t n_rows, const uint32_t *ids, uint64_t n, uint32_t id_base, uint64_t **runs_dev, uint64_t *n_runs, void *stream);
+
 /* ---- UPDATE SET ... WHERE: constants assigned in place to the rows a WHERE selects -----------------------------------------
  * No counterpart in the reference (its parser knows no UPDATE).  A TARGET is a column and the value every selected row of it
  * receives: `data` 16-byte aligned and WRITABLE up to n_rows rounded up to PQPS_STEP_ROWS rows, `width` 1, 2, 4 or 8 bytes

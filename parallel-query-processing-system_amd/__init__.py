@@ -40,6 +40,11 @@ REMAP_LDS_CODES = 4096             # a table of up to this many codes is staged 
 MEMBER_LDS_BITS = 1 << 18          # a bitmap of up to this many bits is staged into LDS
 MEMBER_MAX_RUNS, MEMBER_MAX_ITEMS = 4, 65536
 SYNTH_USERS = 2000
+COMPACT_TILE = 1024                # PQPS_COMPACT_TILE: bins one wave of pqps_bins_compact takes
+WIDE_COUNT_SLOTS = 8192            # PQPS_WIDE_COUNT_SLOTS / PQPS_WIDE_VALUE_SLOTS: the LDS front of the wide bins
+WIDE_VALUE_SLOTS = 2048
+TOP_BY = {"key": 0, "count": 1, "sum": 2, "min": 3, "max": 4}           # HIPTOP_BY_*
+TOP_BINS_BUDGET = 256 << 20        # HIP_TOP_BINS_BUDGET
 
 COLUMNS = ["command_id", "raw_command", "base_command", "shell_type", "exit_code", "timestamp",
            "sudo_used", "working_directory", "user_id", "user_name", "host_name", "risk_level"]
@@ -134,6 +139,16 @@ class GroupPairResult(C.Structure):
     _fields_ = [("groupColumn", C.c_int * 2), ("groupKind", C.c_int * 2), ("valueColumn", C.c_int), ("valueKind", C.c_int),
                 ("numGroups", C.c_int), ("total", C.c_longlong),
                 ("keys", C.POINTER(C.c_longlong) * 2), ("keyText", C.POINTER(C.c_char_p) * 2), ("counts", C.POINTER(C.c_ulonglong)),
+                ("sums", C.POINTER(C.c_longlong)), ("mins", C.POINTER(C.c_longlong)), ("maxs", C.POINTER(C.c_longlong)),
+                ("queryTime", C.c_double), ("success", C.c_bool)]
+
+
+class GroupTopResult(C.Structure):
+    """struct hipGroupTopResult (include/executeEngine-hip.h)."""
+    _fields_ = [("groupColumn", C.c_int), ("groupKind", C.c_int), ("valueColumn", C.c_int), ("valueKind", C.c_int),
+                ("orderBy", C.c_int), ("descending", C.c_bool), ("limit", C.c_longlong), ("numGroups", C.c_int),
+                ("groupsTotal", C.c_longlong), ("total", C.c_longlong),
+                ("keys", C.POINTER(C.c_longlong)), ("keyText", C.POINTER(C.c_char_p)), ("counts", C.POINTER(C.c_ulonglong)),
                 ("sums", C.POINTER(C.c_longlong)), ("mins", C.POINTER(C.c_longlong)), ("maxs", C.POINTER(C.c_longlong)),
                 ("queryTime", C.c_double), ("success", C.c_bool)]
 
@@ -547,6 +562,17 @@ def lib():
                                        u64, u32, vp, vp]
     L.pqps_group_pair_sort.argtypes = [vp, C.POINTER(Column), u32, u32, C.POINTER(Column), u32, u32, C.POINTER(Column), u64, vp, u64,
                                        u32, C.POINTER(vp), C.POINTER(u64), vp]
+    L.executeQueryGroupTopHIP.restype = C.POINTER(GroupTopResult)
+    L.executeQueryGroupTopHIP.argtypes = [E, C.c_char_p, C.c_char_p, C.c_int, C.c_bool, C.c_longlong, W]
+    L.freeGroupTopResultHIP.argtypes = [C.POINTER(GroupTopResult)]
+    L.freeGroupTopResultHIP.restype = None
+    L.pqps_filter_group_wide.argtypes = [vp, C.POINTER(Column), u32, u64, C.POINTER(Predicate), C.POINTER(Column), C.POINTER(Column),
+                                         u32, u32, vp, vp]
+    L.pqps_group_wide_list.argtypes = [vp, C.POINTER(Column), C.POINTER(Column), u64, vp, vp, u64, u32, u32, u32, vp, vp]
+    L.pqps_bins_compact.argtypes = [vp, vp, u32, C.c_int, C.POINTER(vp), C.POINTER(u64), vp]
+    L.pqps_group_sort.argtypes = [vp, C.POINTER(Column), u32, u64, C.POINTER(Column), u64, vp, u64, u32, C.POINTER(vp), C.POINTER(u64), vp]
+    L.hipGroupTopOrder.restype = C.c_longlong
+    L.hipGroupTopOrder.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, C.c_int, C.c_int, C.c_longlong, vp]
     L.executeQueryCountDistinctHIP.restype = C.POINTER(DistinctResult)
     L.executeQueryCountDistinctHIP.argtypes = [E, C.c_char_p, C.c_char_p, W]
     L.freeDistinctResultHIP.argtypes = [C.POINTER(DistinctResult)]
@@ -878,6 +904,20 @@ def sort_list_chain(ctx, keys, ids_dev, n, id_base, out_ids_dev, out_keys_dev=No
 
 
 BUCKET_PREFIX, BUCKET_WIDTH = 1, 2                          # HIPBUCKET_* (include/executeEngine-hip.h)
+
+
+def group_top_order(bins, counts, sums=None, min_images=None, max_images=None, value_kind=-1, by="count", descending=True, limit=10):
+    """hipGroupTopOrder: the indices of the listed groups, in order (arrays of u64, any sequence; `by` a TOP_BY name or a
+    number).  Raises PqpsError where the function refuses."""
+    import numpy as np
+    arrays = [None if a is None else np.ascontiguousarray(a, dtype=np.uint64) for a in (bins, counts, sums, min_images, max_images)]
+    n = len(arrays[0])
+    order = np.zeros(max(n, 1), dtype=np.uint64)
+    ptrs = [None if a is None else a.ctypes.data for a in arrays]
+    k = lib().hipGroupTopOrder(*ptrs, n, value_kind, TOP_BY.get(by, by), int(bool(descending)), int(limit), order.ctypes.data)
+    if k < 0:
+        raise PqpsError("hipGroupTopOrder refused (reason on stderr)")
+    return [int(i) for i in order[:k]]
 
 
 def bucket_bounds(column, mode, arg, dictionary=None, lo=0, hi=0):
@@ -1251,6 +1291,36 @@ class HipEngine:
                      fix(r.sums[g]), fix(r.mins[g]), fix(r.maxs[g])) for g in range(r.numGroups)]
         finally:
             lib().freeAggregateResultHIP(res)
+
+    def group_top_result(self, column, value_column=None, by="count", descending=True, limit=10, chain=None):
+        """executeQueryGroupTopHIP: {"rows": [(key_text, count[, sum, min, max]), ...], "total", "groups_total"} -- the groups
+        of `column` (of any size) over the rows select_ids(chain) returns, ordered by `by` ("key", "count", "sum", "min",
+        "max"; ties in ascending key order), the first `limit` of them (limit <= 0 or None: all).  Python ints; command_id's
+        sum (mod 2^64), min and max are unsigned.  Raises PqpsError when the engine refuses (reason on stderr)."""
+        wl = WhereList(chain)
+        what = f"group_top({column!r}, {value_column!r}, by={by!r})"
+        res = lib().executeQueryGroupTopHIP(self.e, column.encode(), value_column.encode() if value_column else None,
+                                            TOP_BY.get(by, by), bool(descending), int(limit or 0), wl.ptr)
+        if not res:
+            raise PqpsError(f"{what}: no result")
+        try:
+            r = res.contents
+            if not r.success:
+                raise PqpsError(f"{what} refused or failed (reason on stderr)")
+            n = r.numGroups
+            fields = [[t.decode("latin-1") for t in r.keyText[:n]], r.counts[:n]]
+            if r.valueColumn >= 0:
+                fields += [r.sums[:n], r.mins[:n], r.maxs[:n]]
+                if r.valueKind == HIPKIND_U64:
+                    fields[2:] = [[x & 0xFFFFFFFFFFFFFFFF for x in f] for f in fields[2:]]
+            rows = list(zip(*fields))
+            return {"rows": rows, "total": int(r.total), "groups_total": int(r.groupsTotal), "seconds": float(r.queryTime)}
+        finally:
+            lib().freeGroupTopResultHIP(res)
+
+    def group_top(self, column, value_column=None, by="count", descending=True, limit=10, chain=None):
+        """The rows of group_top_result: [(key_text, count[, sum, min, max]), ...]."""
+        return self.group_top_result(column, value_column, by, descending, limit, chain)["rows"]
 
     def group_buckets(self, column, prefix=None, width=None, value_column=None, chain=None):
         """executeQueryGroupBucketsHIP: the rows select_ids(chain) returns, grouped by the first `prefix` bytes of a string

@@ -43,6 +43,14 @@
 //                beside it, so that two workgroups fit in a CU's 160 KiB
 //   BINS_GLOBAL  global atomics per matching row straight into the output (one lane per scattered address: an order of
 //                magnitude below the shaped-atomic rate -- this path is for correctness at high cardinality, not for speed)
+//   BINS_WIDE    any number of bins (BIN_COLUMN only; the top-N groups' route above kBinsMax): the bins in global memory as
+//                BINS_GLOBAL's, behind a write-combining FRONT in LDS (BinsFront): a direct-mapped table of `front` slots
+//                (a power of two; 8 B per count slot, 32 B per value slot, kBinsLdsBytes at most), slot = bin & (front - 1),
+//                each a tag (the bin, all ones = free) and an accumulator.  A lane claims the slot with ONE compare-and-swap
+//                on the tag; where the slot was free or already held its bin the row is added in LDS, otherwise it goes
+//                to the global bins with the atomics of BINS_GLOBAL.  Nothing is evicted -- the first bin to arrive keeps
+//                its slot, and a bin that owns a third of the rows arrives early -- and the workgroup ends by flushing
+//                every claimed slot with one global atomic per field.  front == 0: no table, BINS_GLOBAL's atomics alone.
 // REGS and LDS end the workgroup's loop with plain coalesced stores of its bins into a partial row of its own
 // (store-and-sum rather than atomics: thousands of workgroups adding to the same few bin words would queue at the memory
 // side): [gridDim.x][stride] u32 counts or [gridDim.x][4][n_bins] u64 fields; group_sum_kernel / agg_sum_kernel add the rows
@@ -59,7 +67,7 @@
 namespace {
 
 enum BinSource { BIN_NONE = 0, BIN_COLUMN = 1, BIN_BUCKET_LDS = 2, BIN_BUCKET_GLOBAL = 3, BIN_PAIR = 4 };
-enum BinPath { BINS_REGS = 0, BINS_LDS = 1, BINS_GLOBAL = 2 };
+enum BinPath { BINS_REGS = 0, BINS_LDS = 1, BINS_GLOBAL = 2, BINS_WIDE = 3 };
 enum BinValue { BINS_COUNT = 0, BINS_I32 = 1, BINS_U64 = 2 };
 
 constexpr uint32_t kBinsMax = 65536;
@@ -72,6 +80,10 @@ constexpr uint32_t kAggLdsBins = 2304;                                  // 64 51
 constexpr uint32_t kBucketCountLds = (kBinsLdsBytes - 4) / (kCountBinBytes + 4);   // 8191: bins + bounds + the sentinel
 constexpr uint32_t kBucketAggLds = (kBinsLdsBytes - 4) / (kAggBinBytes + 4);       // 2047: table + bounds + the sentinel
 constexpr uint32_t kBucketBoundsLds = kBinsLdsBytes / 4 - 1;            // 16383: the bounds alone (GLOBAL bins)
+constexpr uint32_t kWideCountSlots = kBinsLdsBytes / (kCountBinBytes + 4);    // 8192: u32 tag + u32 count
+constexpr uint32_t kWideAggSlots = kBinsLdsBytes / (kAggBinBytes + 4);        // 2048: u32 tag + the 28-byte accumulator
+constexpr uint32_t kWideFree = 0xFFFFFFFFu;                              // tag of a free slot (a bin is below n_bins <= 2^32 - 1)
+constexpr uint32_t kCompactTile = 1024;                                 // bins one wave of the compaction kernels takes
 constexpr uint32_t kAggFields = 4;                                      // count, sum, min image, max image
 constexpr uint32_t kGroupSumParts = 64;            // partial rows one workgroup of group_sum_kernel adds up
 constexpr uint32_t kAggSumParts = 64;              // partial rows one workgroup of agg_sum_kernel combines
@@ -95,6 +107,7 @@ struct BinsArgs {
     void *out;                       // GLOBAL: n_bins u32 bins (zeroed) / [4][n_bins] u64 fields (initialised before the launch)
     void *parts;                     // REGS / LDS: [gridDim.x][stride] u32 / [gridDim.x][4][n_bins] u64 partial rows
     uint32_t stride;                 // BINS_COUNT: words per partial row (n_bins rounded up to 64)
+    uint32_t front;                  // WIDE: slots of the LDS front (a power of two), 0 = none
 };
 
 struct BinsListArgs {
@@ -105,6 +118,7 @@ struct BinsListArgs {
     void *out;                       // n_bins u32 bins (zeroed) / [4][n_bins] u64 fields (initialised before the launch)
     uint64_t n_rows, capacity;
     uint32_t id_base;
+    uint32_t front;                  // WIDE: slots of the LDS front (a power of two), 0 = none
 };
 
 // pos[p] = number of entries of bounds[0 .. n) that are <= b[p]; N independent searches advanced together.
@@ -233,12 +247,12 @@ __device__ __forceinline__ void block_reduce_acc(uint64_t &cnt, uint64_t &sum, u
 }
 
 // the four fields of bin b of out[4][n_bins]: the GLOBAL path, the list flushes, agg_sum_kernel
-__device__ __forceinline__ void agg_global_add(void *out, uint32_t nb, uint32_t b, uint64_t cnt, uint64_t sum, uint64_t mn, uint64_t mx) {
+__device__ __forceinline__ void agg_global_add(void *out, uint64_t nb, uint32_t b, uint64_t cnt, uint64_t sum, uint64_t mn, uint64_t mx) {
     unsigned long long *o = (unsigned long long *)out;
     atomicAdd(&o[b], (unsigned long long)cnt);
     atomicAdd(&o[nb + b], (unsigned long long)sum);
-    atomicMin(&o[2 * (uint64_t)nb + b], (unsigned long long)mn);
-    atomicMax(&o[3 * (uint64_t)nb + b], (unsigned long long)mx);
+    atomicMin(&o[2 * nb + b], (unsigned long long)mn);
+    atomicMax(&o[3 * nb + b], (unsigned long long)mx);
 }
 
 // The bins of a workgroup in LDS, nb of them: with a value u64 sum / min / max arrays, then (always) the u32 counts.  What
@@ -290,6 +304,39 @@ struct BinsLds {
     }
 };
 
+// The write-combining front of BINS_WIDE: `slots` accumulators (a BinsLds table) and, behind them, their u32 tags.
+template <int VAL>
+struct BinsFront {
+    static constexpr bool VALUED = VAL != BINS_COUNT, U64 = VAL == BINS_U64;
+    BinsLds<VAL> t;
+    uint32_t *tag;
+    uint32_t slots;
+    __device__ __forceinline__ BinsFront(void *base, uint32_t n) : t(base, n), tag(t.end), slots(n) {}
+    __device__ __forceinline__ void clear() const {
+        t.clear(slots);
+        for (uint32_t i = threadIdx.x; i < slots; i += kBlock) tag[i] = kWideFree;
+    }
+    // one row with the value `wide` into bin b < nb: its slot where the lane owns or shares it, else the global bins
+    __device__ __forceinline__ void add(void *out, uint32_t nb, uint32_t b, uint64_t wide) const {
+        if (slots) {
+            const uint32_t s = b & (slots - 1u);
+            const uint32_t was = atomicCAS(&tag[s], kWideFree, b);
+            if (was == kWideFree || was == b) { t.add(s, wide); return; }
+        }
+        if constexpr (VALUED) agg_global_add(out, nb, b, 1, wide, agg_image<U64>(wide), agg_image<U64>(wide));
+        else atomicAdd(&((uint32_t *)out)[b], 1u);
+    }
+    // every claimed slot into the output (after a sync): one atomic per field
+    __device__ __forceinline__ void flush(void *out, uint32_t nb) const {
+        for (uint32_t i = threadIdx.x; i < slots; i += kBlock) {
+            const uint32_t b = tag[i];
+            if (b == kWideFree) continue;
+            if constexpr (VALUED) agg_global_add(out, nb, b, t.cnt[i], t.sum[i], t.mn[i], t.mx[i]);
+            else atomicAdd(&((uint32_t *)out)[b], t.cnt[i]);
+        }
+    }
+};
+
 // one row with the value `wide` into bin b < nb: the LDS table, or the output in global memory
 template <int PATH, int VAL>
 __device__ __forceinline__ void bins_add(const BinsLds<VAL> &t, void *out, uint32_t nb, uint32_t b, uint64_t wide) {
@@ -304,6 +351,7 @@ __global__ __launch_bounds__(kBlock, 1) void bins_scan_kernel(const BinsArgs) {
     constexpr bool VALUED = VAL != BINS_COUNT, U64 = VAL == BINS_U64;
     static_assert(PATH != BINS_REGS || (VALUED ? SRC == BIN_NONE : SRC == BIN_COLUMN || SRC == BIN_BUCKET_LDS), "no such register path");
     static_assert(SRC != BIN_NONE || (VALUED && PATH == BINS_REGS), "no GROUP BY: one accumulator in registers");
+    static_assert(PATH != BINS_WIDE || SRC == BIN_COLUMN, "the wide bins are those of one column");
     const auto &g = kernarg<BinsArgs>();
     CArgs &a = g.e;
     extern __shared__ uint64_t bins_lds[];
@@ -330,6 +378,22 @@ __global__ __launch_bounds__(kBlock, 1) void bins_scan_kernel(const BinsArgs) {
             uint64_t *row = (uint64_t *)g.parts + (uint64_t)blockIdx.x * kAggFields;
             row[0] = cnt; row[1] = sum; row[2] = mn; row[3] = mx;
         }
+    } else if constexpr (PATH == BINS_WIDE) {
+        const BinsFront<VAL> f(bins_lds, g.front);
+        const Binner<SRC> binner(g.src, nullptr);
+        f.clear();
+        __syncthreads();
+        fused_scan_steps<NT>(a, lane, wv, [&](uint64_t step_row0, uint32_t mbits) {
+            uint64_t v[16] = {};
+            uint32_t bin[16];
+            if constexpr (VALUED) load_step_u64<U64, NT>(vbase, step_row0, lane, v);
+            binner.template step<NT>(step_row0, lane, bin);
+#pragma unroll
+            for (int p = 0; p < 16; p++)
+                if (((mbits >> p) & 1u) && bin[p] < nb) f.add(g.out, nb, bin[p], v[p]);
+        });
+        __syncthreads();
+        f.flush(g.out, nb);
     } else {
         const BinsLds<VAL> t(bins_lds, PATH == BINS_LDS ? nb : 0u);
         const Binner<SRC> binner(g.src, t.end);
@@ -439,7 +503,7 @@ __global__ __launch_bounds__(kBlock) void agg_sum_kernel(const uint64_t *__restr
 
 // The bins over an ID list: ids[0 .. min(*count, capacity)), row = id - id_base.  REGS (no GROUP BY): per-lane registers
 // reduced per workgroup, one atomic per field and workgroup; LDS: a workgroup table flushed at the end; GLOBAL: atomics per
-// row.  Dynamic LDS as the scan's.
+// row; WIDE: the front, flushed at the end.  Dynamic LDS as the scan's.
 template <int SRC, int PATH, int VAL>
 __global__ __launch_bounds__(kBlock) void bins_list_kernel(const BinsListArgs g) {
     constexpr bool VALUED = VAL != BINS_COUNT, U64 = VAL == BINS_U64;
@@ -456,6 +520,20 @@ __global__ __launch_bounds__(kBlock) void bins_list_kernel(const BinsListArgs g)
         });
         block_reduce_acc(cnt, sum, mn, mx);
         if (threadIdx.x == 0 && cnt) agg_global_add(g.out, 1, 0, cnt, sum, mn, mx);
+    } else if constexpr (PATH == BINS_WIDE) {
+        const BinsFront<VAL> f(bins_lds, g.front);
+        const Binner<SRC> binner(g.src, nullptr);
+        f.clear();
+        __syncthreads();
+        for_each_listed_row(g.ids, g.count, g.capacity, g.id_base, g.n_rows, [&](uint64_t row) {
+            const uint32_t b = binner.row(row);
+            if (b >= nb) return;
+            uint64_t v = 0;
+            if constexpr (VALUED) v = gather_value<U64>(g.vcol, row);
+            f.add(g.out, nb, b, v);
+        });
+        __syncthreads();
+        f.flush(g.out, nb);
     } else {
         const BinsLds<VAL> t(bins_lds, PATH == BINS_LDS ? nb : 0u);
         const Binner<SRC> binner(g.src, t.end);
@@ -471,6 +549,61 @@ __global__ __launch_bounds__(kBlock) void bins_list_kernel(const BinsListArgs g)
         if constexpr (PATH == BINS_LDS) {
             __syncthreads();
             t.flush(g.out, nb);
+        }
+    }
+}
+
+// The bins of a wide answer into compact runs (pqps_bins_compact): two launches with an exclusive scan of tile_runs[0 ..
+// tiles] between them -- no workgroup waits for another.  A wave takes the tiles wave, wave + n_waves, ... of kCompactTile
+// bins, 64 bins a round; a bin has rows when its count (u32 counts, or the first of the [4][n_bins] u64 fields) is not 0.
+template <bool VALUED>
+__device__ __forceinline__ uint64_t compact_count_of(const void *bins, uint64_t b) {
+    return VALUED ? ((const uint64_t *)bins)[b] : (uint64_t)((const uint32_t *)bins)[b];
+}
+
+// tile_runs[t] = the bins with rows among [t * kCompactTile, (t + 1) * kCompactTile); tile_runs[tiles] = 0 (the scan leaves
+// the number of runs there)
+template <bool VALUED>
+__global__ __launch_bounds__(kBlock) void bins_compact_count_kernel(const void *__restrict__ bins, uint64_t n_bins, uint64_t tiles,
+                                                                    uint32_t *tile_runs) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t n_waves = (uint64_t)gridDim.x * kWaves;
+    for (uint64_t t = (uint64_t)blockIdx.x * kWaves + (threadIdx.x >> 6); t <= tiles; t += n_waves) {
+        uint32_t c = 0;
+        for (uint32_t r = 0; r < kCompactTile / 64 && t < tiles; r++) {
+            const uint64_t b = t * kCompactTile + r * 64u + lane;
+            c += (uint32_t)__popcll(__ballot(b < n_bins && compact_count_of<VALUED>(bins, b) != 0));
+        }
+        if (lane == 0) tile_runs[t] = c;
+    }
+}
+
+// out: keys[n_runs], counts[n_runs], and VALUED sums / min images / max images [n_runs] each, all u64, ascending by bin:
+// the run format of pqps_group_pair_sort.  first[t] = the runs in front of tile t.
+template <bool VALUED>
+__global__ __launch_bounds__(kBlock) void bins_compact_write_kernel(const void *__restrict__ bins, uint64_t n_bins, uint64_t tiles,
+                                                                    const uint32_t *__restrict__ first, uint64_t n_runs, uint64_t *out) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t lt_mask = (1ull << lane) - 1ull;
+    const uint64_t n_waves = (uint64_t)gridDim.x * kWaves;
+    for (uint64_t t = (uint64_t)blockIdx.x * kWaves + (threadIdx.x >> 6); t < tiles; t += n_waves) {
+        uint64_t at = first[t];
+        for (uint32_t r = 0; r < kCompactTile / 64; r++) {
+            const uint64_t b = t * kCompactTile + r * 64u + lane;
+            const uint64_t c = b < n_bins ? compact_count_of<VALUED>(bins, b) : 0ull;
+            const uint64_t has = __ballot(c != 0);
+            const uint64_t g = at + (uint64_t)__popcll(has & lt_mask);
+            if (c != 0 && g < n_runs) {                         // (g < n_runs always: first[] counted the same bins)
+                out[g] = b;
+                out[n_runs + g] = c;
+                if constexpr (VALUED) {
+                    const uint64_t *f = (const uint64_t *)bins;
+                    out[2 * n_runs + g] = f[n_bins + b];
+                    out[3 * n_runs + g] = f[2 * n_bins + b];
+                    out[4 * n_runs + g] = f[3 * n_bins + b];
+                }
+            }
+            at += (uint64_t)__popcll(has);
         }
     }
 }

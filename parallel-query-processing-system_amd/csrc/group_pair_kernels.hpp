@@ -34,6 +34,23 @@ __global__ __launch_bounds__(kBlock) void pair_keys_kernel(const void *acol, uin
     }
 }
 
+// The one-column form (pqps_group_sort): key[i] = the bin of listed row i, (value - base) in 32-bit arithmetic, where it is
+// below n_bins (up to 2^32), kPairNoKey otherwise or outside the table; row[i] = id - id_base
+__global__ __launch_bounds__(kBlock) void group_keys_kernel(const void *gcol, uint32_t gwl, const uint32_t *__restrict__ ids, uint64_t n,
+                                                            uint32_t id_base, uint64_t n_rows, uint32_t base, uint64_t n_bins,
+                                                            uint64_t *key, uint32_t *rows) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t r = ids[i] - id_base;
+        uint64_t k = kPairNoKey;
+        if (r < n_rows) {
+            const uint32_t b = gather_narrow(gcol, gwl, r) - base;
+            if (b < n_bins) k = b;
+        }
+        key[i] = k;
+        rows[i] = r;
+    }
+}
+
 // element i of the sorted keys starts a run
 __device__ __forceinline__ bool pair_is_head(const uint64_t *__restrict__ key, uint64_t i, uint64_t k) {
     return k != kPairNoKey && (i == 0 || key[i - 1] != k);

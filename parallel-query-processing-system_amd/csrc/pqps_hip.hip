@@ -515,7 +515,7 @@ struct pqps_ctx {
     uint64_t *check_dev;        // [2] pqps_ids_checksum
     // per-context overrides of the launch parameters (pqps_ctx_set_option: A/B runs inside ONE process, where the physical
     // placement of the table is the same for every variant); -1 = the default
-    long opt_list16, opt_list16_min, opt_list16_min_u8, opt_list_max, opt_list_max_u8, opt_tiny_max, opt_expand_lag, opt_sum_lag, opt_tune;
+    long opt_list16, opt_list16_min, opt_list16_min_u8, opt_list_max, opt_list_max_u8, opt_tiny_max, opt_expand_lag, opt_sum_lag, opt_tune, opt_wide_front;
     void *sort_tmp;
     size_t sort_tmp_bytes;
     uint32_t *group_parts;      // every fused scan (group / aggregate / distinct): its workgroups' partial results (grow_group_parts)
@@ -957,6 +957,7 @@ const struct BinsInstance { int src, path, val; bins_scan_fn scan[2]; bins_list_
     PQPS_BINS_VALUED(BIN_BUCKET_LDS, BINS_LDS), PQPS_BINS_VALUED(BIN_BUCKET_LDS, BINS_GLOBAL), PQPS_BINS_VALUED(BIN_BUCKET_GLOBAL, BINS_GLOBAL),
     PQPS_BINS(BIN_PAIR, BINS_LDS, BINS_COUNT), PQPS_BINS(BIN_PAIR, BINS_GLOBAL, BINS_COUNT),
     PQPS_BINS_VALUED(BIN_PAIR, BINS_LDS), PQPS_BINS_VALUED(BIN_PAIR, BINS_GLOBAL),
+    PQPS_BINS(BIN_COLUMN, BINS_WIDE, BINS_COUNT), PQPS_BINS_VALUED(BIN_COLUMN, BINS_WIDE),
 #undef PQPS_BINS_VALUED
 #undef PQPS_BINS
 };
@@ -1241,7 +1242,7 @@ int create_ctx(int device, bool lane, pqps_ctx **out) {
     ctx->status_host = nullptr; ctx->status_dev = nullptr;
     ctx->parity = 0; ctx->epoch = 0; ctx->hand_groups = 0; ctx->needs_reset.store(false);
     ctx->check_dev = nullptr;
-    ctx->opt_list16 = ctx->opt_list16_min = ctx->opt_list16_min_u8 = ctx->opt_list_max = ctx->opt_list_max_u8 = ctx->opt_tiny_max = ctx->opt_expand_lag = ctx->opt_sum_lag = ctx->opt_tune = -1;
+    ctx->opt_list16 = ctx->opt_list16_min = ctx->opt_list16_min_u8 = ctx->opt_list_max = ctx->opt_list_max_u8 = ctx->opt_tiny_max = ctx->opt_expand_lag = ctx->opt_sum_lag = ctx->opt_tune = ctx->opt_wide_front = -1;
     ctx->sort_tmp = nullptr;
     ctx->sort_tmp_bytes = 0;
     ctx->group_parts = nullptr;
@@ -1367,6 +1368,7 @@ int pqps_ctx_set_option(pqps_ctx *ctx, const char *name, long value) {
         {"list16", &ctx->opt_list16}, {"list16_min", &ctx->opt_list16_min}, {"list16_min_u8", &ctx->opt_list16_min_u8},
         {"list_max", &ctx->opt_list_max}, {"tiny_max", &ctx->opt_tiny_max},
         {"expand_lag", &ctx->opt_expand_lag}, {"sum_lag", &ctx->opt_sum_lag}, {"tune", &ctx->opt_tune},
+        {"wide_front", &ctx->opt_wide_front},                   // 0: the wide bins take their global atomics without the LDS front
     };
     for (auto &o : opts)
         if (strcmp(o.name, name) == 0) { *o.slot = value < 0 ? -1 : value; return PQPS_OK; }
@@ -2965,16 +2967,18 @@ static int grow_group_parts(pqps_ctx *ctx, hipStream_t s, size_t words) {
 }
 
 // What a dense-bins call asks for.  src.gcol == NULL: no GROUP BY (one bin); src.bounds != NULL: buckets; src.gcol2 != NULL:
-// a pair of columns.  value_col == NULL: COUNT(*), out = n_bins u32 bins; else out = [4][n_bins] u64 fields.
+// a pair of columns.  value_col == NULL: COUNT(*), out = n_bins u32 bins; else out = [4][n_bins] u64 fields.  `wide`: the
+// bins of one column behind the LDS front (BINS_WIDE), any n_bins; front_off: without the front.
 struct BinsRequest {
     BinSourceArgs src;
     const pqps_column *value_col;
     void *out;
+    bool wide, front_off;
 };
 
 // Which instance a request takes (the limits: bins_kernels.hpp), and the dynamic LDS of a workgroup.  `scan`: the fused
 // form, which has the per-lane counters for up to 16 count bins of one column or of buckets.
-struct BinsPlan { const BinsInstance *inst; uint32_t lds; bool valued, buckets, pair; };
+struct BinsPlan { const BinsInstance *inst; uint32_t lds, front; bool valued, buckets, pair; };
 static BinsPlan bins_plan(const BinsRequest &r, bool scan) {
     BinsPlan p;
     const uint32_t nb = r.src.n_bins;
@@ -2984,10 +2988,12 @@ static BinsPlan bins_plan(const BinsRequest &r, bool scan) {
     const bool bounds_lds = p.buckets && nb <= kBucketBoundsLds;
     const uint32_t lds_max = p.buckets ? (p.valued ? kBucketAggLds : kBucketCountLds) : (p.valued ? kAggLdsBins : kCountLdsBins);
     const bool regs = p.valued ? !r.src.gcol : scan && !p.pair && nb <= kBinsSmall;
-    const int path = regs ? BINS_REGS : nb <= lds_max ? BINS_LDS : BINS_GLOBAL;
+    const int path = r.wide ? BINS_WIDE : regs ? BINS_REGS : nb <= lds_max ? BINS_LDS : BINS_GLOBAL;
     const int src = !r.src.gcol ? BIN_NONE : p.pair ? BIN_PAIR : !p.buckets ? BIN_COLUMN : bounds_lds ? BIN_BUCKET_LDS : BIN_BUCKET_GLOBAL;
     const int val = !p.valued ? BINS_COUNT : r.value_col->width == 8 ? BINS_U64 : BINS_I32;
     p.lds = (bounds_lds ? (nb + 1u) * (uint32_t)sizeof(uint32_t) : 0u) + (path == BINS_LDS ? nb * (p.valued ? kAggBinBytes : kCountBinBytes) : 0u);
+    p.front = path != BINS_WIDE || r.front_off ? 0u : p.valued ? kWideAggSlots : kWideCountSlots;
+    if (path == BINS_WIDE) p.lds = p.front * ((p.valued ? kAggBinBytes : kCountBinBytes) + 4u);
     p.inst = nullptr;
     for (const BinsInstance &i : kBinsInstances)
         if (i.src == src && i.path == path && i.val == val) p.inst = &i;
@@ -3001,7 +3007,7 @@ static const char *const kPairValueName[3] = {"PAIR_COUNT", "PAIR_I32", "PAIR_U6
 static void bins_scan_name(const BinsPlan &p, bool nt) {
     const char *family = p.pair ? "pair" : p.buckets ? (p.valued ? "bucket_agg" : "bucket") : p.valued ? "agg" : "group";
     const char *prefix = p.pair ? "PAIR" : p.buckets ? "BUCKET" : p.valued ? "AGG" : "GROUP";
-    const char *path = p.inst->path == BINS_LDS ? "LDS" : p.inst->path == BINS_GLOBAL ? "GLOBAL" : p.valued ? "ONE" : "SMALL";
+    const char *path = p.inst->path == BINS_LDS ? "LDS" : p.inst->path == BINS_GLOBAL ? "GLOBAL" : p.inst->path == BINS_WIDE ? "WIDE" : p.valued ? "ONE" : "SMALL";
     const char *bounds = !p.buckets ? "" : p.inst->src == BIN_BUCKET_LDS ? ", BLDS=true" : ", BLDS=false";
     const char *sep = p.pair || p.valued ? ", " : "";
     const char *val = p.pair ? kPairValueName[p.inst->val] : !p.valued ? "" : p.inst->val == BINS_U64 ? "u64" : "i32";
@@ -3033,7 +3039,7 @@ static int bins_scan(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, ui
     hipStream_t s = pick_stream(ctx, stream);
     rc = init_bins_out(r.out, nb, p.valued, s);
     if (rc || n_rows == 0) return rc;
-    const bool summed = p.inst->path != BINS_GLOBAL;
+    const bool summed = p.inst->path != BINS_GLOBAL && p.inst->path != BINS_WIDE;
     const uint32_t grid = fused_grid(ctx, n_rows, p.lds);
     const uint32_t stride = (nb + 63u) & ~63u;
     if (summed) {                                               // partial rows: [grid][stride] u32 or [grid][4][nb] u64
@@ -3045,6 +3051,7 @@ static int bins_scan(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, ui
     g.out = r.out;
     g.parts = ctx->group_parts;
     g.stride = stride;
+    g.front = p.front;
     bins_scan_name(p, g.e.streaming != 0);
     hipEvent_t stop;
     rc = fused_launch(ctx, p.inst->scan[g.e.streaming ? 1 : 0], grid, p.lds, s, g, &stop);
@@ -3078,6 +3085,7 @@ static int bins_list(pqps_ctx *ctx, const BinsRequest &r, uint64_t n_rows, const
     g.n_rows = n_rows;
     g.capacity = capacity;
     g.id_base = id_base;
+    g.front = p.front;
     if (p.pair) snprintf(g_kernel, sizeof g_kernel, "pair_list_kernel<LDS=%s, %s>", p.inst->path == BINS_LDS ? "true" : "false", kPairValueName[p.inst->val]);
     hipLaunchKernelGGL(p.inst->list, dim3(list_grid(ctx, capacity, 4)), dim3(kBlock), p.lds, s, g);
     HIP_TRY(hipGetLastError());
@@ -3151,6 +3159,93 @@ int pqps_aggregate_list(pqps_ctx *ctx, const pqps_column *value_col, const pqps_
     BinsRequest r;
     const int rc = column_request(r, value_col, group_col, bin_base, n_bins, false, true, out);
     return rc ? rc : bins_list(ctx, r, n_rows, ids, count_dev, capacity, id_base, stream);
+}
+
+// ---- the wide bins of one column: any n_bins, behind the LDS front (BINS_WIDE of bins_kernels.hpp) ------------------------
+// The request, checked.  value_col == NULL: COUNT(*).  `aligned`: the fused form's vector loads of the group column.
+static int wide_request(pqps_ctx *ctx, BinsRequest &r, const pqps_column *value_col, const pqps_column *group_col, uint32_t bin_base,
+                        uint32_t n_bins, bool aligned, void *out) {
+    memset(&r, 0, sizeof r);
+    int rc = value_col ? check_value_col(value_col) : PQPS_OK;
+    if (rc) return rc;
+    if (n_bins == 0) return fail(PQPS_EINVAL, "0 bins");
+    rc = column_width_code("group", group_col, false, false, aligned, &r.src.gwidth_log2);
+    if (rc) return rc;
+    r.src.gcol = group_col->data;
+    r.src.bin_base = bin_base;
+    r.src.n_bins = n_bins;
+    r.value_col = value_col;
+    r.out = out;
+    r.wide = true;
+    r.front_off = ctx->opt_wide_front == 0;
+    return PQPS_OK;
+}
+
+int pqps_filter_group_wide(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                           const pqps_column *value_col, const pqps_column *group_col, uint32_t bin_base, uint32_t n_bins,
+                           void *out, void *stream) {
+    if (!ctx || !group_col || !out) return fail(PQPS_EINVAL, "ctx/group_col/out is NULL");
+    BinsRequest r;
+    const int rc = wide_request(ctx, r, value_col, group_col, bin_base, n_bins, true, out);
+    return rc ? rc : bins_scan(ctx, cols, n_cols, n_rows, pred, r, stream);
+}
+
+int pqps_group_wide_list(pqps_ctx *ctx, const pqps_column *value_col, const pqps_column *group_col, uint64_t n_rows,
+                         const uint32_t *ids, const uint64_t *count_dev, uint64_t capacity, uint32_t id_base, uint32_t bin_base,
+                         uint32_t n_bins, void *out, void *stream) {
+    if (!ctx || !group_col || !out || !count_dev || (capacity && !ids)) return fail(PQPS_EINVAL, "NULL argument");
+    BinsRequest r;
+    const int rc = wide_request(ctx, r, value_col, group_col, bin_base, n_bins, false, out);
+    return rc ? rc : bins_list(ctx, r, n_rows, ids, count_dev, capacity, id_base, stream);
+}
+
+static_assert(PQPS_COMPACT_TILE == kCompactTile && PQPS_WIDE_COUNT_SLOTS == kWideCountSlots && PQPS_WIDE_VALUE_SLOTS == kWideAggSlots,
+              "pqps_hip.h states the kernels' constants");
+
+int pqps_bins_compact(pqps_ctx *ctx, const void *bins, uint32_t n_bins, int valued, uint64_t **runs_dev, uint64_t *n_runs, void *stream) {
+    if (!ctx || !bins || !runs_dev || !n_runs) return fail(PQPS_EINVAL, "NULL argument");
+    *runs_dev = nullptr;
+    *n_runs = 0;
+    if (n_bins == 0) return fail(PQPS_EINVAL, "0 bins");
+    hipStream_t s = pick_stream(ctx, stream);
+    const uint64_t tiles = ((uint64_t)n_bins + kCompactTile - 1) / kCompactTile, m = tiles + 1;   // tile_runs[tiles] receives the number of runs
+    const uint32_t scan_blocks = (uint32_t)((m + pqps_sort::kScanBlock - 1) / pqps_sort::kScanBlock);
+    const uint32_t fields = valued ? 5u : 2u;
+    const dim3 grid(list_grid(ctx, m * 64, 8));
+    uint32_t *tile_runs = nullptr, *sums = nullptr, runs = 0;
+    uint64_t *out = nullptr;
+    snprintf(g_kernel, sizeof g_kernel, "bins_compact_write_kernel<%s>", valued ? "valued" : "count");
+    hipError_t e = hipMalloc((void **)&tile_runs, m * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&sums, (size_t)scan_blocks * 4);
+    if (e == hipSuccess) {
+        if (valued) hipLaunchKernelGGL(bins_compact_count_kernel<true>, grid, dim3(kBlock), 0, s, bins, (uint64_t)n_bins, tiles, tile_runs);
+        else hipLaunchKernelGGL(bins_compact_count_kernel<false>, grid, dim3(kBlock), 0, s, bins, (uint64_t)n_bins, tiles, tile_runs);
+        hipLaunchKernelGGL(pqps_sort::scan_sums_kernel, dim3(scan_blocks), dim3(pqps_sort::kThreads), 0, s, (const uint32_t *)tile_runs, m, sums);
+        hipLaunchKernelGGL(pqps_sort::scan_top_kernel, dim3(1), dim3(pqps_sort::kThreads), 0, s, sums, scan_blocks);
+        hipLaunchKernelGGL(pqps_sort::scan_apply_kernel, dim3(scan_blocks), dim3(pqps_sort::kThreads), 0, s, tile_runs, m, (const uint32_t *)sums);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(&runs, tile_runs + tiles, sizeof runs, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+    }
+    if (e == hipSuccess && runs) {
+        e = hipMalloc((void **)&out, (size_t)fields * runs * 8);
+        if (e == hipSuccess) {
+            if (valued) hipLaunchKernelGGL(bins_compact_write_kernel<true>, grid, dim3(kBlock), 0, s, bins, (uint64_t)n_bins, tiles,
+                                           (const uint32_t *)tile_runs, (uint64_t)runs, out);
+            else hipLaunchKernelGGL(bins_compact_write_kernel<false>, grid, dim3(kBlock), 0, s, bins, (uint64_t)n_bins, tiles,
+                                    (const uint32_t *)tile_runs, (uint64_t)runs, out);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+    }
+    (void)hipFree(tile_runs); (void)hipFree(sums);
+    if (e != hipSuccess) {
+        if (out) (void)hipFree(out);
+        return fail(PQPS_EHIP, "bins compaction: %s", hipGetErrorString(e));
+    }
+    *runs_dev = out;
+    *n_runs = runs;
+    return PQPS_OK;
 }
 
 // The request for the buckets of one column, checked; value_col == NULL: COUNT(*) per bucket.
@@ -4005,21 +4100,15 @@ int pqps_distinct_sort(pqps_ctx *ctx, const pqps_column *value_col, uint32_t v_b
     return PQPS_OK;
 }
 
-// ---- GROUP BY two columns, sparse: sort and reduce runs (group_pair_kernels.hpp) ------------------------------------
-int pqps_group_pair_sort(pqps_ctx *ctx, const pqps_column *a_col, uint32_t a_base, uint32_t n_a, const pqps_column *b_col, uint32_t b_base,
-                         uint32_t n_b, const pqps_column *value_col, uint64_t n_rows, const uint32_t *ids, uint64_t n, uint32_t id_base,
-                         uint64_t **runs_dev, uint64_t *n_runs, void *stream) {
-    if (!ctx || !runs_dev || !n_runs || (n && !ids)) return fail(PQPS_EINVAL, "NULL argument");
-    *runs_dev = nullptr;
-    *n_runs = 0;
-    uint32_t awl, bwl;
-    const int rc = check_pair_cols(a_col, n_a, b_col, n_b, value_col, false, false, false, &awl, &bwl);
-    if (rc) return rc;
+// ---- GROUP BY two columns, sparse, and its one-column form: sort and reduce runs (group_pair_kernels.hpp) ------------
+// What pqps_group_pair_sort and pqps_group_sort share: `make_keys(grid, keys, rows)` launches the kernel that writes one key (and
+// the row number) per listed row, the keys are sorted over their low `bits` bits and reduced run by run.
+extern "C++" {
+template <class MakeKeys>
+static int runs_sort(pqps_ctx *ctx, hipStream_t s, const pqps_column *value_col, uint64_t n, uint32_t bits, const char *what,
+                     const MakeKeys &make_keys, uint64_t **runs_dev, uint64_t *n_runs) {
     const int val = !value_col ? BINS_COUNT : value_col->width == 8 ? BINS_U64 : BINS_I32;
-    if (n >= 0xFFFFFFFFull) return fail(PQPS_EINVAL, "a list of %llu rows", (unsigned long long)n);
-    hipStream_t s = pick_stream(ctx, stream);
     snprintf(g_kernel, sizeof g_kernel, "pair_runs_kernel<%s> (sort)", kPairValueName[val]);
-    if (n == 0 || n_rows == 0) { HIP_TRY(hipStreamSynchronize(s)); return PQPS_OK; }
     const uint64_t tiles = (n + 63) / 64, m = tiles + 1;        // heads[tiles] receives the number of runs
     const uint32_t scan_blocks = (uint32_t)((m + pqps_sort::kScanBlock - 1) / pqps_sort::kScanBlock);
     const uint32_t fields = val == BINS_COUNT ? 2u : 5u;        // keys, counts [, sums, min images, max images]
@@ -4038,13 +4127,12 @@ int pqps_group_pair_sort(pqps_ctx *ctx, const pqps_column *a_col, uint32_t a_bas
     const uint32_t *rows = nullptr;
     uint32_t runs = 0;
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(pair_keys_kernel, grid, dim3(kBlock), 0, s, a_col->data, awl, b_col->data, bwl, ids, n, id_base, n_rows, a_base, b_base,
-                           n_a, n_b, ka, ra);
+        make_keys(grid, ka, ra);
         e = hipGetLastError();
     }
     if (e == hipSuccess) {
         bool in_a = true;
-        e = pqps_sort::sort_pairs<uint64_t, false>(w, ka, ra, kb, rb, n, 64, ctx->compute_units, s, &in_a);
+        e = pqps_sort::sort_pairs<uint64_t, false>(w, ka, ra, kb, rb, n, bits, ctx->compute_units, s, &in_a);
         keys = in_a ? ka : kb;
         rows = in_a ? ra : rb;
     }
@@ -4074,11 +4162,53 @@ int pqps_group_pair_sort(pqps_ctx *ctx, const pqps_column *a_col, uint32_t a_bas
     pqps_sort::workspace_free(w);
     if (e != hipSuccess) {
         if (out) (void)hipFree(out);
-        return fail(PQPS_EHIP, "GROUP BY pair sort: %s", hipGetErrorString(e));
+        return fail(PQPS_EHIP, "%s: %s", what, hipGetErrorString(e));
     }
     *runs_dev = out;
     *n_runs = runs;
     return PQPS_OK;
+}
+}  // extern "C++"
+
+int pqps_group_pair_sort(pqps_ctx *ctx, const pqps_column *a_col, uint32_t a_base, uint32_t n_a, const pqps_column *b_col, uint32_t b_base,
+                         uint32_t n_b, const pqps_column *value_col, uint64_t n_rows, const uint32_t *ids, uint64_t n, uint32_t id_base,
+                         uint64_t **runs_dev, uint64_t *n_runs, void *stream) {
+    if (!ctx || !runs_dev || !n_runs || (n && !ids)) return fail(PQPS_EINVAL, "NULL argument");
+    *runs_dev = nullptr;
+    *n_runs = 0;
+    uint32_t awl, bwl;
+    const int rc = check_pair_cols(a_col, n_a, b_col, n_b, value_col, false, false, false, &awl, &bwl);
+    if (rc) return rc;
+    if (n >= 0xFFFFFFFFull) return fail(PQPS_EINVAL, "a list of %llu rows", (unsigned long long)n);
+    hipStream_t s = pick_stream(ctx, stream);
+    if (n == 0 || n_rows == 0) {
+        snprintf(g_kernel, sizeof g_kernel, "pair_runs_kernel<%s> (sort)", kPairValueName[!value_col ? BINS_COUNT : value_col->width == 8 ? BINS_U64 : BINS_I32]);
+        HIP_TRY(hipStreamSynchronize(s));
+        return PQPS_OK;
+    }
+    return runs_sort(ctx, s, value_col, n, 64, "GROUP BY pair sort", [&](dim3 grid, uint64_t *keys, uint32_t *rows) {
+        hipLaunchKernelGGL(pair_keys_kernel, grid, dim3(kBlock), 0, s, a_col->data, awl, b_col->data, bwl, ids, n, id_base, n_rows, a_base, b_base,
+                           n_a, n_b, keys, rows);
+    }, runs_dev, n_runs);
+}
+
+int pqps_group_sort(pqps_ctx *ctx, const pqps_column *group_col, uint32_t bin_base, uint64_t n_bins, const pqps_column *value_col,
+                    uint64_t n_rows, const uint32_t *ids, uint64_t n, uint32_t id_base, uint64_t **runs_dev, uint64_t *n_runs, void *stream) {
+    if (!ctx || !group_col || !runs_dev || !n_runs || (n && !ids)) return fail(PQPS_EINVAL, "NULL argument");
+    *runs_dev = nullptr;
+    *n_runs = 0;
+    if (n_bins == 0 || n_bins > (1ull << 32)) return fail(PQPS_EINVAL, "%llu bins: 1 .. 2^32", (unsigned long long)n_bins);
+    uint32_t gwl;
+    int rc = column_width_code("group", group_col, false, false, false, &gwl);
+    if (rc == PQPS_OK && value_col) rc = check_value_col(value_col);
+    if (rc) return rc;
+    if (n >= 0xFFFFFFFFull) return fail(PQPS_EINVAL, "a list of %llu rows", (unsigned long long)n);
+    hipStream_t s = pick_stream(ctx, stream);
+    if (n == 0 || n_rows == 0) { HIP_TRY(hipStreamSynchronize(s)); return PQPS_OK; }
+    // a bin is below 2^32 and kPairNoKey has bits 32 .. 39 set: 40 key bits order the bins and keep the rows left out behind them
+    return runs_sort(ctx, s, value_col, n, 40, "GROUP BY sort", [&](dim3 grid, uint64_t *keys, uint32_t *rows) {
+        hipLaunchKernelGGL(group_keys_kernel, grid, dim3(kBlock), 0, s, group_col->data, gwl, ids, n, id_base, n_rows, bin_base, n_bins, keys, rows);
+    }, runs_dev, n_runs);
 }
 
 // ---- UPDATE SET ... WHERE (assign_kernels.hpp) -----------------------------------------------------------------------

@@ -833,7 +833,10 @@ static int fused_issue(struct query *q, fused_call call, void *arg) {
  * uploaded from `head` before anything is issued (the out part starts on the next 16 bytes), `bytes` of output.  Then
  * either `fused` makes the one launch per shard (fused_issue), or the selection is left per shard (query_lists) and `list`
  * runs over every shard's list that has rows, on the lane's copy context, writes `out` and returns the shim's status.
- * After the waits a shard's out part is downloaded and handed to `combine`.  No callback sees a shard without rows. */
+ * After the waits a shard's out part is downloaded and handed to `combine`; or, where the answer is no buffer of a fixed
+ * size, `post` takes the out part on its device instead (on the lane's copy context; it returns 0 or its engine_error), and
+ * `bytes` may be 0: no buffer, out is NULL.  `list` may be NULL when `post` does the list's work.  No callback sees a shard
+ * without rows. */
 struct shard_reduce {
     const char *what;                    /* the query's word in the messages of a failed device call */
     const void *head;
@@ -841,6 +844,7 @@ struct shard_reduce {
     fused_call fused;
     int (*list)(struct query *q, int s, pqps_ctx *cs, const struct hipLane *L, void *out, void *arg);
     void (*combine)(void *arg, const void *host);
+    int (*post)(struct query *q, int s, pqps_ctx *cs, void *out, void *arg);
 };
 
 static size_t pad16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
@@ -848,24 +852,24 @@ static size_t pad16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
 /* buf[0 .. n_shards): filled with the shards' buffers for the callbacks (which find it through `arg`), freed on return. */
 static int shard_reduce(struct query *q, bool fused, const struct shard_reduce *r, void **buf, void *arg) {
     const size_t head = pad16(r->head_bytes);
-    void *host = malloc(r->bytes);
-    int rc = host ? 0 : oom();
+    void *host = r->post ? NULL : malloc(r->bytes);
+    int rc = host || r->post ? 0 : oom();
     for (int s = 0; s < q->n_shards; s++) buf[s] = NULL;
     for (int s = 0; s < q->n_shards && rc == 0; s++) {
         struct hipTable *sh = hipTableShard(q->t, s);
-        if (sh->n_rows == 0) continue;
+        if (sh->n_rows == 0 || head + r->bytes == 0) continue;
         if (pqps_malloc(sh->ctx, head + r->bytes, &buf[s]) != PQPS_OK ||
             (r->head_bytes && pqps_upload(lane_copy_ctx(q, s), buf[s], r->head, r->head_bytes, NULL) != PQPS_OK))
             rc = engine_error(r->what);
     }
     if (rc == 0) rc = fused ? fused_issue(q, r->fused, arg) : query_lists(q);
     for (int s = 0; s < q->n_shards && rc == 0; s++) {
-        if (!buf[s] || (!fused && q->count[s] == 0)) continue;
+        if (hipTableShard(q->t, s)->n_rows == 0 || (!fused && q->count[s] == 0)) continue;
         pqps_ctx *cs = lane_copy_ctx(q, s);
-        void *out = (char *)buf[s] + head;
-        if ((!fused && r->list(q, s, cs, query_lane(q, s), out, arg) != PQPS_OK) ||
-            pqps_download(cs, host, out, r->bytes, NULL) != PQPS_OK)
-            rc = engine_error(r->what);
+        void *out = buf[s] ? (char *)buf[s] + head : NULL;
+        if (!fused && r->list && r->list(q, s, cs, query_lane(q, s), out, arg) != PQPS_OK) rc = engine_error(r->what);
+        else if (r->post) rc = r->post(q, s, cs, out, arg);
+        else if (pqps_download(cs, host, out, r->bytes, NULL) != PQPS_OK) rc = engine_error(r->what);
         else r->combine(arg, host);
     }
     for (int s = 0; s < q->n_shards; s++) if (buf[s]) pqps_free(hipTableShard(q->t, s)->ctx, buf[s]);
@@ -916,6 +920,8 @@ struct group_plan {
     int c;                               /* HIPCOL_* of the group column, -1 without GROUP BY                        */
     int kind;                            /* k_group_kind[c], -1 without GROUP BY                                     */
     uint32_t n_bins, bin_base;           /* 1 / 0 without GROUP BY                                                   */
+    uint64_t span;                       /* the bins as a 64-bit count: n_bins, but 2^32 for an i32 column that holds
+                                            INT_MIN and INT_MAX (n_bins is then 2^32 - 1; only the top groups ask)   */
     int32_t lo;                          /* i32 group column: the key of bin 0                                       */
     bool single;                         /* a single-valued dictionary column (no buffer): every row is bin 0        */
     bool empty;                          /* no rows in the table: no groups, nothing to launch                      */
@@ -954,8 +960,9 @@ static int query_bind(struct engineS *engine, struct whereClauseS *whereClause, 
 }
 
 /* The bins of group column c (-1: none) of a bound query: codes of a dictionary (none for a single-valued column: every row
- * is bin 0), 0 / 1, or the i32 range.  `column`: its name, `what`: the query's, for the messages. */
-static int group_plan_bins(struct query *q, int c, const char *column, const char *what, struct group_plan *gp) {
+ * is bin 0), 0 / 1, or the i32 range.  `column`: its name, `what`: the query's, for the messages.  `any_span`: the caller
+ * takes an i32 range of any size (the top groups); every other caller refuses one above HIP_GROUP_MAX_BINS here. */
+static int group_plan_bins(struct query *q, int c, const char *column, const char *what, bool any_span, struct group_plan *gp) {
     struct hipTable *t = q->t;
     int rc = 0;
     int32_t hi = -1;
@@ -970,33 +977,40 @@ static int group_plan_bins(struct query *q, int c, const char *column, const cha
             gp->n_bins = 2;
         } else if ((rc = column_bounds(q, c, &gp->lo, &hi)) == 0) {
             if (gp->lo > hi) gp->empty = true;                           /* no rows at all */
-            else if ((uint64_t)((int64_t)hi - (int64_t)gp->lo) + 1u > HIP_GROUP_MAX_BINS) {
+            else if (!any_span && (uint64_t)((int64_t)hi - (int64_t)gp->lo) + 1u > HIP_GROUP_MAX_BINS) {
                 fprintf(stderr, "HIP engine: %s: %s spans %lld values, more than %llu groups\n", what, column,
                         (long long)hi - (long long)gp->lo + 1, HIP_GROUP_MAX_BINS);
                 rc = -1;
             } else {
-                gp->n_bins = (uint32_t)((int64_t)hi - (int64_t)gp->lo + 1);
+                gp->span = (uint64_t)((int64_t)hi - (int64_t)gp->lo) + 1u;
+                gp->n_bins = gp->span > UINT32_MAX ? UINT32_MAX : (uint32_t)gp->span;
                 gp->bin_base = (uint32_t)gp->lo;
             }
         }
     }
+    if (gp->kind != HIPKIND_I32) gp->span = gp->n_bins;
     return rc;
 }
 
 /* The plan of group column c (-1: none) of a query whose WHERE is bound (`bound` == 0; otherwise only the fields that need
  * no table are set, and `bound` is returned): its bins, whether the query is fused, and every shard's group column. */
-static int group_plan_column(struct query *q, int bound, int c, const char *column, const char *what, struct group_plan *gp) {
+static int group_plan_column_span(struct query *q, int bound, int c, const char *column, const char *what, bool any_span, struct group_plan *gp) {
     memset(gp, 0, sizeof *gp);
     gp->c = c;
     gp->kind = c >= 0 ? k_group_kind[c] : -1;
     gp->n_bins = 1;
-    const int rc = bound == 0 ? group_plan_bins(q, c, column, what, gp) : bound;
+    gp->span = 1;
+    const int rc = bound == 0 ? group_plan_bins(q, c, column, what, any_span, gp) : bound;
     gp->fused = q->plan.n_passes == 1 && q->n_probes == 0;
     for (int s = 0; s < q->n_shards && c >= 0; s++) {
         const struct hipTable *sh = hipTableShard(q->t, s);
         gp->gcol[s] = gp->fused && c == HIPCOL_SUDO_USED && sh->sudo_bits.data ? sh->sudo_bits : sh->col[c];
     }
     return rc;
+}
+
+static int group_plan_column(struct query *q, int bound, int c, const char *column, const char *what, struct group_plan *gp) {
+    return group_plan_column_span(q, bound, c, column, what, false, gp);
 }
 
 /* Binds the WHERE into q (query_bind) and decides the bins of group column c (group_plan_column). */
@@ -1736,13 +1750,47 @@ static int pair_dense(struct query *q, const struct group_plan *a, const struct 
     return shard_reduce(q, a->fused, &r, out_dev, &(struct pair_call){ { acc, D, vc }, a, b, out_dev });
 }
 
+/* The shards' compact runs (the run format of pqps_group_pair_sort: host[s] holds runs[s] entries per field, ascending by
+ * key) merged by key into pr: counts and sums added, min / max images taken. */
+static int runs_merge(int n_shards, uint64_t *const *host, const uint64_t *runs, bool valued, struct pair_rows *pr) {
+    uint64_t at[HIP_MAX_SHARDS] = { 0 }, all = 0;
+    for (int s = 0; s < n_shards; s++) all += runs[s];
+    int rc = pair_rows_alloc(pr, all, valued);
+    while (rc == 0) {                                                    /* k-way merge by key */
+        int best = -1;
+        for (int s = 0; s < n_shards; s++)
+            if (at[s] < runs[s] && (best < 0 || host[s][at[s]] < host[best][at[best]])) best = s;
+        if (best < 0) break;
+        const uint64_t *h = host[best], r = runs[best], i = at[best]++;
+        uint64_t g = pr->n;
+        if (g && pr->key[g - 1] == h[i]) g--;                            /* the key of another shard's run */
+        else { pr->n++; pr->key[g] = h[i]; if (valued) pr->mn[g] = UINT64_MAX; }
+        pr->cnt[g] += h[r + i];
+        if (valued) {
+            pr->sum[g] += h[2 * r + i];
+            if (h[3 * r + i] < pr->mn[g]) pr->mn[g] = h[3 * r + i];
+            if (h[4 * r + i] > pr->mx[g]) pr->mx[g] = h[4 * r + i];
+        }
+    }
+    return rc;
+}
+
+/* One shard's runs from its device to the host: *host = malloc'd, `fields` x n_runs u64 (NULL for no runs); runs_dev is freed. */
+static int runs_fetch(pqps_ctx *cs, pqps_ctx *owner, uint64_t *runs_dev, uint64_t n_runs, bool valued, const char *what, uint64_t **host) {
+    const size_t bytes = (valued ? 5 : 2) * (size_t)n_runs * 8;
+    int rc = 0;
+    if (n_runs && !(*host = malloc(bytes))) rc = oom();
+    else if (n_runs && pqps_download(cs, *host, runs_dev, bytes, NULL) != PQPS_OK) rc = engine_error(what);
+    if (runs_dev) pqps_free(owner, runs_dev);
+    return rc;
+}
+
 /* The sparse form: the selection, every shard's list sorted and reduced to its runs on its device (pqps_group_pair_sort),
- * the compact runs downloaded and merged by key on the host: counts and sums added, min / max images taken. */
+ * the compact runs downloaded and merged by key on the host (runs_merge). */
 static int pair_sparse(struct query *q, const struct group_plan *a, const struct group_plan *b, int vc, struct pair_rows *pr) {
     const bool valued = vc >= 0;
-    const size_t fields = valued ? 5 : 2;
     uint64_t *host[HIP_MAX_SHARDS] = { NULL };
-    uint64_t runs[HIP_MAX_SHARDS] = { 0 }, at[HIP_MAX_SHARDS] = { 0 }, all = 0;
+    uint64_t runs[HIP_MAX_SHARDS] = { 0 };
     memset(pr, 0, sizeof *pr);
     int rc = query_lists(q);
     for (int s = 0; s < q->n_shards && rc == 0; s++) {
@@ -1753,28 +1801,10 @@ static int pair_sparse(struct query *q, const struct group_plan *a, const struct
         if (pqps_group_pair_sort(cs, &sh->col[a->c], a->bin_base, a->n_bins, &sh->col[b->c], b->bin_base, b->n_bins, valued ? &sh->col[vc] : NULL,
                                  sh->n_rows, query_lane(q, s)->ids_dev, q->count[s], (uint32_t)sh->row0, &runs_dev, &runs[s], NULL) != PQPS_OK)
             rc = engine_error("group pair sort");
-        else if (runs[s] && !(host[s] = malloc(fields * (size_t)runs[s] * 8))) rc = oom();
-        else if (runs[s] && pqps_download(cs, host[s], runs_dev, fields * (size_t)runs[s] * 8, NULL) != PQPS_OK) rc = engine_error("group pair download");
-        if (runs_dev) pqps_free(sh->ctx, runs_dev);
-        all += runs[s];
+        if (rc == 0) rc = runs_fetch(cs, sh->ctx, runs_dev, runs[s], valued, "group pair download", &host[s]);
+        else if (runs_dev) pqps_free(sh->ctx, runs_dev);
     }
-    if (rc == 0) rc = pair_rows_alloc(pr, all, valued);
-    while (rc == 0) {                                                    /* k-way merge by key */
-        int best = -1;
-        for (int s = 0; s < q->n_shards; s++)
-            if (at[s] < runs[s] && (best < 0 || host[s][at[s]] < host[best][at[best]])) best = s;
-        if (best < 0) break;
-        const uint64_t *h = host[best], r = runs[best], i = at[best]++;
-        uint64_t g = pr->n;
-        if (g && pr->key[g - 1] == h[i]) g--;                            /* the pair of another shard's run */
-        else { pr->n++; pr->key[g] = h[i]; if (valued) pr->mn[g] = UINT64_MAX; }
-        pr->cnt[g] += h[r + i];
-        if (valued) {
-            pr->sum[g] += h[2 * r + i];
-            if (h[3 * r + i] < pr->mn[g]) pr->mn[g] = h[3 * r + i];
-            if (h[4 * r + i] > pr->mx[g]) pr->mx[g] = h[4 * r + i];
-        }
-    }
+    if (rc == 0) rc = runs_merge(q->n_shards, host, runs, valued, pr);
     for (int s = 0; s < q->n_shards; s++) free(host[s]);
     return rc;
 }
@@ -1859,6 +1889,151 @@ struct hipGroupPairResult *executeQueryGroupPairHIP(struct engineS *engine, cons
 void freeGroupPairResultHIP(struct hipGroupPairResult *res) {
     if (!res) return;
     for (int j = 0; j < 2; j++) free_group_keys(res->keys[j], res->keyText[j], res->numGroups);
+    group_arrays_free(res->counts, res->sums, res->mins, res->maxs);
+    free(res);
+}
+
+/* ---- the top N groups (include/executeEngine-hip.h) ------------------------------------------------------------------ */
+
+/* Whether a shard's `span` wide bins fit the budget: 4 B a bin, 32 B with a value column; n_bins must fit a u32 count too. */
+static bool top_bins_fit(uint64_t span, bool valued) {
+    return span <= UINT32_MAX && span * (valued ? 4 * sizeof(uint64_t) : sizeof(uint32_t)) <= HIP_TOP_BINS_BUDGET;
+}
+
+struct top_call { const struct group_plan *gp; int vc; bool fit; void **bins_dev; uint64_t **host; uint64_t *runs; };
+
+static int top_fused_call(struct query *q, int s, pqps_ctx *ctx, void *stream, void *arg) {
+    const struct top_call *a = arg;
+    const struct hipTable *sh = hipTableShard(q->t, s);
+    const struct shard_pred *sp = &q->sp[s];
+    const int rc = pqps_filter_group_wide(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, a->vc >= 0 ? &sh->col[a->vc] : NULL, &sh->col[a->gp->c],
+                                          a->gp->bin_base, a->gp->n_bins, a->bins_dev[s], stream);
+    return rc == PQPS_OK ? 0 : engine_error("wide group filter");
+}
+
+/* A shard's bins (filled by the fused launch, or here from its list) compacted on its device; or, without bins (past the
+ * budget), its list sorted and reduced.  Either way the shard hands over its runs only. */
+static int top_post(struct query *q, int s, pqps_ctx *cs, void *out, void *arg) {
+    const struct top_call *a = arg;
+    const struct group_plan *gp = a->gp;
+    const struct hipTable *sh = hipTableShard(q->t, s);
+    const struct hipLane *L = query_lane(q, s);
+    const bool valued = a->vc >= 0;
+    const pqps_column *vcol = valued ? &sh->col[a->vc] : NULL;
+    uint64_t *runs_dev = NULL;
+    int rc = 0;
+    if (!a->fit) {
+        if (pqps_group_sort(cs, &sh->col[gp->c], gp->bin_base, gp->span, vcol, sh->n_rows, L->ids_dev, q->count[s], (uint32_t)sh->row0,
+                            &runs_dev, &a->runs[s], NULL) != PQPS_OK)
+            rc = engine_error("group sort");
+    } else {
+        if (!gp->fused && pqps_group_wide_list(cs, vcol, &sh->col[gp->c], sh->n_rows, L->ids_dev, L->count_dev, q->count[s], (uint32_t)sh->row0,
+                                               gp->bin_base, gp->n_bins, out, NULL) != PQPS_OK)
+            rc = engine_error("wide group list");
+        if (rc == 0 && pqps_bins_compact(cs, out, gp->n_bins, valued, &runs_dev, &a->runs[s], NULL) != PQPS_OK) rc = engine_error("bins compaction");
+    }
+    if (rc == 0) return runs_fetch(cs, sh->ctx, runs_dev, a->runs[s], valued, "group runs download", &a->host[s]);
+    if (runs_dev) pqps_free(sh->ctx, runs_dev);
+    return rc;
+}
+
+/* The groups of a column of more than HIP_GROUP_MAX_BINS bins, merged over the shards into pr (key = the bin), through
+ * shard_reduce with top_post as its post step.  Fused (a single-pass scan-mode WHERE whose bins fit the budget): one
+ * pqps_filter_group_wide launch per shard.  Otherwise the selection, and per shard the wide bins over its list where they
+ * fit the budget, the sort form where they do not (measured, DESIGN.md 7l: inside the budget the wide bins win down to a
+ * list of 5 000 rows against 10^7 bins). */
+static int top_wide(struct query *q, const struct group_plan *gp, int vc, struct pair_rows *pr) {
+    const bool valued = vc >= 0, fit = top_bins_fit(gp->span, valued);
+    void *bins_dev[HIP_MAX_SHARDS];
+    uint64_t *host[HIP_MAX_SHARDS] = { NULL };
+    uint64_t runs[HIP_MAX_SHARDS] = { 0 };
+    const struct shard_reduce r = { .what = "wide group bins", .bytes = fit ? bins_bytes(gp->n_bins, vc) : 0, .fused = top_fused_call, .post = top_post };
+    memset(pr, 0, sizeof *pr);
+    int rc = shard_reduce(q, gp->fused && fit, &r, bins_dev, &(struct top_call){ gp, vc, fit, bins_dev, host, runs });
+    if (rc == 0) rc = runs_merge(q->n_shards, host, runs, valued, pr);
+    for (int s = 0; s < q->n_shards; s++) free(host[s]);
+    return rc;
+}
+
+/* The listed groups into the result: pr holds every group (ascending by bin), order[0 .. n) the indices of the listed ones. */
+static int top_result_fill(struct hipGroupTopResult *res, const struct hipTable *t, const struct group_plan *gp, const struct pair_rows *pr,
+                           const uint64_t *order, size_t n) {
+    const bool valued = res->valueColumn >= 0;
+    res->keys = calloc(n + 1, sizeof *res->keys);
+    res->keyText = calloc(n + 1, sizeof *res->keyText);
+    if (!res->keys || !res->keyText) return oom();
+    if (group_arrays_alloc(n, valued, &res->counts, &res->sums, &res->mins, &res->maxs) != 0) return -1;
+    for (size_t g = 0; g < n; g++) {
+        const uint64_t i = order[g];
+        char buf[32];
+        if (!(res->keyText[g] = strdup(group_key(t, gp->c, gp->kind, (uint32_t)pr->key[i], gp->lo, &res->keys[g], buf, sizeof buf)))) return oom();
+        res->numGroups = (int)g + 1;                                     /* (what freeGroupTopResultHIP frees) */
+        group_arrays_set(res->counts, res->sums, res->mins, res->maxs, g, pr->cnt[i], valued ? pr->sum[i] : 0, valued ? pr->mn[i] : 0,
+                         valued ? pr->mx[i] : 0, res->valueKind);
+    }
+    return 0;
+}
+
+struct hipGroupTopResult *executeQueryGroupTopHIP(struct engineS *engine, const char *groupColumn, const char *valueColumn, int orderBy,
+                                                  bool descending, long long limit, struct whereClauseS *whereClause) {
+    const double t0 = now_seconds();
+    struct hipGroupTopResult *res = calloc(1, sizeof *res);
+    if (!res) { oom(); return NULL; }
+    res->groupColumn = res->groupKind = res->valueColumn = res->valueKind = -1;
+    res->orderBy = orderBy;
+    res->descending = descending;
+    res->limit = limit;
+    if (!engine || !engine->record_block || !groupColumn) { fprintf(stderr, "HIP engine: top groups without an engine or a column\n"); return res; }
+    const int c = group_column_id("top groups", groupColumn);
+    if (c < 0) return res;
+    int v = -1;
+    if (valueColumn && (v = value_column_id("top groups", valueColumn)) < 0) return res;
+    if (orderBy < HIPTOP_BY_KEY || orderBy > HIPTOP_BY_MAX) { fprintf(stderr, "HIP engine: top groups: order %d is none of HIPTOP_BY_*\n", orderBy); return res; }
+    if (orderBy >= HIPTOP_BY_SUM && v < 0) { fprintf(stderr, "HIP engine: top groups: ordering by SUM / MIN / MAX needs a value column\n"); return res; }
+    struct hipTable *t = engine->record_block;
+    if (t->xch) { fprintf(stderr, "HIP engine: top groups are not exchanged across ranks\n"); return res; }
+    res->groupColumn = c;
+    res->groupKind = k_group_kind[c];
+    res->valueColumn = v;
+    res->valueKind = v >= 0 ? k_group_kind[v] : -1;
+    struct query q;
+    if (!query_open(engine, &q)) return res;                             /* reason on stderr */
+    struct group_plan gp;
+    struct pair_rows pr;
+    uint64_t *order = NULL;
+    long long listed = 0;
+    memset(&pr, 0, sizeof pr);
+    int rc = group_plan_column_span(&q, query_bind(engine, whereClause, &q), c, groupColumn, "top groups", true, &gp);
+    if (rc == 0 && !gp.empty) {
+        if (gp.span > HIP_GROUP_MAX_BINS && !gp.single) rc = top_wide(&q, &gp, v, &pr);
+        else {                                                           /* the dense bins of the other grouped queries */
+            uint64_t *acc = bins_alloc(gp.n_bins, v >= 0);
+            if (!acc) rc = -1;
+            if (rc == 0) rc = v < 0 ? group_counts(&q, &gp, acc) : group_bins(&q, &gp, v, acc);
+            if (rc == 0) rc = pair_rows_from_bins(acc, gp.n_bins, UINT32_MAX, v >= 0, &pr);   /* n_b past every bin: key = bin */
+            free(acc);
+        }
+    }
+    for (uint64_t g = 0; g < pr.n; g++) res->total += (long long)pr.cnt[g];
+    res->groupsTotal = (long long)pr.n;
+    const uint64_t listing = limit > 0 && (uint64_t)limit < pr.n ? (uint64_t)limit : pr.n;
+    if (rc == 0 && listing > INT_MAX) {                                  /* numGroups is an int */
+        fprintf(stderr, "HIP engine: top groups: %llu groups to list, more than %d: give a LIMIT\n", (unsigned long long)listing, INT_MAX);
+        rc = -1;
+    }
+    if (rc == 0 && pr.n && !(order = malloc((size_t)pr.n * sizeof *order))) rc = oom();
+    if (rc == 0 && (listed = hipGroupTopOrder(pr.key, pr.cnt, pr.sum, pr.mn, pr.mx, pr.n, res->valueKind, orderBy, descending, limit, order)) < 0) rc = -1;
+    if (rc == 0 && top_result_fill(res, t, &gp, &pr, order, (size_t)listed) == 0) res->success = true;
+    free(order);
+    pair_rows_free(&pr);
+    query_close(&q);
+    res->queryTime = now_seconds() - t0;
+    return res;
+}
+
+void freeGroupTopResultHIP(struct hipGroupTopResult *res) {
+    if (!res) return;
+    free_group_keys(res->keys, res->keyText, res->numGroups);
     group_arrays_free(res->counts, res->sums, res->mins, res->maxs);
     free(res);
 }

@@ -1109,6 +1109,65 @@ int hipFirstKeyDecode(int kind, int descending, unsigned long long word, long lo
     return 1;
 }
 
+/* ---- the order of the top N groups ------------------------------------------------------------------------------------- */
+
+/* One group as the order sees it: `rank` ascends in the wanted order (complemented for a descending one), ties by bin. */
+struct top_item { uint64_t rank, bin, index; };
+
+static int top_before(const struct top_item *x, const struct top_item *y) {
+    return x->rank != y->rank ? x->rank < y->rank : x->bin < y->bin;
+}
+
+static int top_item_cmp(const void *x, const void *y) {
+    return top_before(x, y) ? -1 : top_before(y, x) ? 1 : 0;
+}
+
+/* h[0 .. n) is a heap whose root is the LAST of its entries in the order; the entry at i sinks to its place */
+static void top_sift_down(struct top_item *h, uint64_t n, uint64_t i) {
+    for (;;) {
+        uint64_t last = i;
+        const uint64_t l = 2 * i + 1, r = l + 1;
+        if (l < n && top_before(&h[last], &h[l])) last = l;
+        if (r < n && top_before(&h[last], &h[r])) last = r;
+        if (last == i) return;
+        const struct top_item t = h[i]; h[i] = h[last]; h[last] = t;
+        i = last;
+    }
+}
+
+long long hipGroupTopOrder(const uint64_t *bins, const uint64_t *counts, const uint64_t *sums, const uint64_t *min_images,
+                           const uint64_t *max_images, uint64_t n_groups, int value_kind, int order_by, int descending,
+                           long long limit, uint64_t *order) {
+    const uint64_t *by = order_by == HIPTOP_BY_KEY ? bins : order_by == HIPTOP_BY_COUNT ? counts : order_by == HIPTOP_BY_SUM ? sums :
+                         order_by == HIPTOP_BY_MIN ? min_images : max_images;
+    uint64_t flip = 0;
+    if (order_by < HIPTOP_BY_KEY || order_by > HIPTOP_BY_MAX) { fprintf(stderr, "HIP engine: top groups: order %d is none of HIPTOP_BY_*\n", order_by); return -1; }
+    if (order_by == HIPTOP_BY_SUM) {
+        if (value_kind != HIPKIND_I32 && value_kind != HIPKIND_U64) { fprintf(stderr, "HIP engine: top groups: sums of a column that is no number\n"); return -1; }
+        if (value_kind == HIPKIND_I32) flip = 0x8000000000000000ull;     /* signed order as unsigned */
+    }
+    if (n_groups && (!bins || !by || !order)) { fprintf(stderr, "HIP engine: top groups: an array the order reads is NULL\n"); return -1; }
+    const uint64_t k = limit > 0 && (uint64_t)limit < n_groups ? (uint64_t)limit : n_groups;
+    if (k == 0) return 0;
+    if (descending) flip = ~flip;
+    struct top_item *h = malloc((size_t)k * sizeof *h);
+    if (!h) { fprintf(stderr, "HIP engine: top groups: out of memory\n"); return -1; }
+    for (uint64_t i = 0; i < n_groups; i++) {
+        const struct top_item it = { by[i] ^ flip, bins[i], i };
+        if (i < k) {
+            h[i] = it;
+            if (i + 1 == k && k < n_groups) for (uint64_t j = k / 2; j-- > 0;) top_sift_down(h, k, j);   /* the heap is made */
+        } else if (top_before(&it, &h[0])) {                             /* replaces the last of the k kept */
+            h[0] = it;
+            top_sift_down(h, k, 0);
+        }
+    }
+    qsort(h, (size_t)k, sizeof *h, top_item_cmp);
+    for (uint64_t i = 0; i < k; i++) order[i] = h[i].index;
+    free(h);
+    return (long long)k;
+}
+
 /* ---- the packed key of ORDER BY several columns ---------------------------------------------------------------------- */
 
 /* ceil(log2 d): the bits that hold 0 .. d - 1 */
