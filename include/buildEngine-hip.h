@@ -105,6 +105,9 @@ struct hipTable {
      * shard 0 only, computed on first use.  INSERT widens a known range; DELETE leaves it (then possibly wider than the data). */
     int bounds_known[HIPCOL_COUNT];
     int32_t bounds_lo[HIPCOL_COUNT], bounds_hi[HIPCOL_COUNT];
+    /* The value sets of the engine (hipEngineCreateSetHIP; engine/hip/executeEngine-hip.c owns the type): shard 0 only, made
+     * with the first set, kept across a rebuild like the locks, freed by destroyEngineHIP. */
+    struct hipValueSets *sets;
 };
 
 #define HIP_MAX_SHARDS 16

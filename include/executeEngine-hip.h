@@ -640,6 +640,79 @@ struct hipGroupTopResult *executeQueryGroupTopHIP(struct engineS *engine, const 
                                                   long long limit, struct whereClauseS *whereClause);
 void freeGroupTopResultHIP(struct hipGroupTopResult *result);
 
+/* VALUE SETS: column IN (SELECT column FROM table WHERE ... [GROUP BY column HAVING agg op n]) -- a self semi-join whose set
+ * stays on the device (no counterpart in the reference; reached through the C API and the Python package only).
+ * A VALUE SET S belongs to one engine and one column B (`column`).  It is made from an inner WHERE chain (NULL: every row) and
+ * an optional HAVING `aggregate op constant`.
+ * INNER ROWS: the rows for which the inner WHERE is true, each row ONCE -- scan semantics also on an engine with indexes, as
+ *   UPDATE and DELETE have them.  The chain may hold LIKE / IN and the IN SET nodes of sets made earlier.
+ * WITHOUT HAVING S is the set of values of B that at least one inner row carries.  WITH HAVING S is the set of values v of B
+ *   that at least one inner row carries AND whose aggregate over the inner rows carrying v satisfies `op constant`.  A value
+ *   without inner rows is never in S: COUNT(*) < 5 and SUM(x) = 0 do not select it.
+ *   aggregate: HIPTOP_BY_COUNT (COUNT(*); valueColumn is not read), HIPTOP_BY_SUM / _MIN / _MAX of valueColumn, a numeric
+ *   column, with the arithmetic of executeQueryAggregateHIP: an i32 sum is an int64 compared signed, a command_id sum is taken
+ *   mod 2^64 and compared unsigned, MIN and MAX are compared in value order.  op: "=", "!=", "<", ">", "<=", ">=".  constant:
+ *   decimal text -- strtoll for the aggregates of an i32 column, strtoull for those of command_id and for COUNT; a negative
+ *   constant where the number is unsigned, trailing garbage, an empty text or a value out of range is refused
+ *   (hipCompileHaving of hipPredicate.h is that rule, as host code).  AVG is a follow-up.
+ * OUTER USE: the whereClauseS node {attribute = A, operator = "IN SET" | "NOT IN SET", value = "<id>"} (the id in decimal) is
+ *   true for a row iff its value of A is (is not) in S.  Like the other set operators it is reached through this API only, is
+ *   never an index probe (in index mode it is part of the re-filter), and works in every call that takes a WHERE -- every
+ *   reader form, DELETE and UPDATE -- as a member pass (pqps_member_flags) that reads the set's bitmap where the build left it.
+ *   A string column A only with B = A; any i32 column A with any i32 column B (values of A outside B's range are no members);
+ *   command_id and sudo_used neither as A nor as B.
+ * LIFETIME: every successful writer (single and batch INSERT, DELETE, UPDATE -- and an UPDATE that put a new string into a
+ *   dictionary, whatever became of its rows) makes every set of the engine STALE, because the codes may have moved, and gives
+ *   their device memory back; a WHERE that names a stale set, a freed set or an unknown id is refused at compile, saying which.
+ *   At most HIP_MAX_VALUE_SETS sets per engine that are not freed.  Creating a set is a READER: shared lock and one lane,
+ *   legal from a thread that holds tickets, under the lane rules above.  hipEngineFreeSetHIP waits like a WRITER and is refused
+ *   (-1, nothing freed) from a thread that holds a ticket.  destroyEngineHIP frees what is left.
+ * REFUSED (success = false, the reason on stderr, nothing changed): an unknown column; command_id or sudo_used as B; a
+ *   dictionary or boolean value column; SUM / MIN / MAX without a value column; an aggregate outside COUNT .. MAX; a bad op or
+ *   constant; a domain that fits no route; an engine joined across ranks; one set too many; a WHERE that does not compile.
+ * ROUTES, by the domain D of B (dictionary codes, or value - lo over the column's range), per shard:
+ *   no HAVING, D <= PQPS_MEMBER_MAX_BITS: the presence bitmap of pqps_filter_distinct (a single-pass WHERE: ONE fused scan) or
+ *     of pqps_distinct_list over the selection; the popcount is pqps_distinct_count's.
+ *   HAVING, D <= 65 536: the dense bins of pqps_filter_group / pqps_filter_aggregate (or their list forms), then
+ *     pqps_bins_having.  HAVING, D above, the bins (4 B for COUNT, 32 B with a value) within HIP_TOP_BINS_BUDGET: the wide bins
+ *     of pqps_filter_group_wide / pqps_group_wide_list, then pqps_bins_having.  Anything larger is refused (follow-up: the runs
+ *     of the sort form into a list set).
+ *   ONE SHARD: neither bins nor bitmap leave the device; only `rows` and `members` come to the host, and the member pass of
+ *   every later query reads the buffer the build wrote.  SEVERAL SHARDS: the shards' bitmaps are ORed, or their bins combined
+ *   as the grouped queries combine them, on the host; the combined bins go to shard 0 for the same pqps_bins_having (the
+ *   comparison exists once, in the kernel), and the resulting bitmap is placed on every shard.
+ * hipEngineSetKeysHIP downloads the bitmap and decodes it as the grouped queries decode bins: the members' keys and key text
+ * in key order (refused for a stale or freed set). */
+#define HIP_MAX_VALUE_SETS 64
+struct hipSetHaving {
+    int aggregate;                     /* HIPTOP_BY_COUNT .. HIPTOP_BY_MAX                                  */
+    const char *valueColumn;           /* SUM / MIN / MAX: a numeric column; COUNT: not read, may be NULL   */
+    const char *op;
+    const char *constant;
+};
+struct hipValueSet {
+    bool success;
+    unsigned int id;                   /* what an IN SET node names, in decimal; never 0 for a set that was made */
+    int column, kind;                  /* B: HIPCOL_*, HIPKIND_DICT / HIPKIND_I32                           */
+    unsigned long long members;        /* values in S                                                      */
+    unsigned long long rows;           /* the inner rows                                                   */
+    double queryTime;
+};
+struct hipSetKeys {
+    bool success;
+    int column, kind;
+    int numKeys;
+    long long *keys;                   /* as hipGroupResult: dictionary codes, or the i32 values            */
+    char **keyText;                    /* as hipGroupResult                                                */
+};
+struct hipValueSet *hipEngineCreateSetHIP(struct engineS *engine, const char *column, struct whereClauseS *whereClause,
+                                          const struct hipSetHaving *having /* may be NULL */);
+struct hipSetKeys *hipEngineSetKeysHIP(struct engineS *engine, const struct hipValueSet *set);
+void freeSetKeysHIP(struct hipSetKeys *keys);
+/* Frees the set on the device and `set` itself: 0, or -1 (nothing freed) from a thread that holds a ticket.  A `set` that was
+ * refused (success = false) is just freed. */
+int hipEngineFreeSetHIP(struct engineS *engine, struct hipValueSet *set);
+
 /* COUNT(*) through the backend API (the reference parser cannot express it,
  * SURVEY.md fact 10): scan-mode count of matching rows, no ID list. */
 long long executeQueryCountHIP(struct engineS *engine, struct whereClauseS *whereClause);

@@ -68,6 +68,8 @@ struct hipPass {
     uint32_t *member_bitmap;     /* (member_bits + 31) / 32 words, LSB first; malloc'd          */
     uint64_t *member_list;       /* list: ascending, duplicate-free values; malloc'd            */
     uint32_t member_count;       /* list: number of values                                      */
+    uint32_t member_set;         /* a value set (IN SET, below): its id, and member_bitmap is NULL -- the bitmap is the
+                                    set's own, on the device; 0: none                            */
 };
 struct hipPlan {
     int n_passes;
@@ -95,7 +97,57 @@ int hipCompileWherePlan(const struct hipSchema *schema, const struct whereClause
                         struct hipPlan *plan, char *err, size_t errlen);
 void hipPlanFree(struct hipPlan *plan);
 
-/* 1 for "LIKE", "NOT LIKE", "IN", "NOT IN" (exactly so written), else 0. */
+/* VALUE SETS.  Two more set operators, "IN SET" and "NOT IN SET": the node {attribute = A, value = "<id>"} is true for a row
+ * iff its value of A is (is not) in the value set whose id the value text is, in decimal (hipEngineCreateSetHIP of
+ * executeEngine-hip.h makes such sets and keeps their bitmaps on the device).  The compiler sees a set as a hipSetInfo:
+ *   id       never 0
+ *   column   HIPCOL_* id of the column B the set was made over
+ *   kind     HIPKIND_DICT or HIPKIND_I32 (nothing else has sets)
+ *   base, n_bits   bit i of the set's bitmap stands for the code i (base 0) or the i32 value base + i (mod 2^32)
+ *   members  the number of set bits
+ *   stale    the table was written after the set was made: its codes may have moved
+ * Which A for which B: a string column only with itself (the codes of two dictionaries do not compare); any i32 column with
+ * any i32 column (a value of A outside [base, base + n_bits) is no member); command_id and sudo_used never.
+ * The node compiles to a MEMBER PASS with member_form = PQPS_MEMBER_BITMAP, member_base = base, member_bits = n_bits,
+ * member_bitmap = NULL and member_set = id, read as the leaf `flags = 1` (negated for NOT IN SET) like every other member pass.
+ * FOLDED TO A CONSTANT, no pass: a set without members (IN SET false, NOT IN SET true), and a string column's set that holds
+ * the whole dictionary (IN SET true, NOT IN SET false) -- which is also how a single-valued column without a device buffer
+ * is decided.  The compile FAILS, saying so in err, for: a value that is no decimal id, an id the table does not hold (never
+ * made, or freed), a stale set, a pair of columns outside the rule above.
+ * hipCompileWherePlanSets is hipCompileWherePlan given the table sets[0 .. n_sets) (NULL with 0); hipCompileWherePlan is that
+ * call with no sets.  It and hipCompileWhere therefore refuse every chain that names a set. */
+struct hipSetInfo {
+    uint32_t id;
+    int column;
+    int kind;
+    uint32_t base;
+    uint64_t n_bits;
+    uint64_t members;
+    int stale;
+};
+int hipCompileWherePlanSets(const struct hipSchema *schema, const struct whereClauseS *where, const struct hipSetInfo *sets,
+                            int n_sets, struct hipPlan *plan, char *err, size_t errlen);
+
+/* THE HAVING OF A VALUE SET, `aggregate op constant`, as pqps_bins_having takes it; pure host code.
+ *   aggregate   HIPTOP_BY_COUNT / _SUM / _MIN / _MAX (executeEngine-hip.h) -> field PQPS_HAVING_COUNT / _SUM / _MIN / _MAX
+ *   value_kind  HIPKIND_I32 or HIPKIND_U64 for SUM / MIN / MAX (the value column's kind); not read for COUNT
+ *   op          "=", "!=", "<", ">", "<=", ">=" (exactly so written) -> PQPS_HAVING_EQ .. _GE
+ *   constant    decimal text, optional white space and sign in front, nothing behind the digits: strtoll for the aggregates of
+ *               an i32 column, strtoull (no '-') for those of command_id and for COUNT.  SUM and COUNT keep the number's bits;
+ *               MIN and MAX get its IMAGE: (u64)c ^ 2^63 for an i32 column (any int64 c: one outside the i32 range compares as
+ *               it should), c itself for command_id.
+ *   value_signed  1 for the SUM of an i32 column (compared as int64), else 0
+ * Returns 0, or -1 with the reason on stderr and *out untouched for: a NULL argument, an aggregate outside COUNT .. MAX, a
+ * value_kind that is no number where one is read, an unknown op, an empty constant, one without digits, trailing garbage, a
+ * negative number where it is unsigned, a value out of the range of int64 / uint64. */
+struct hipHaving {
+    int field, op;
+    uint64_t constant;
+    int value_signed;
+};
+int hipCompileHaving(int aggregate, int value_kind, const char *op, const char *constant, struct hipHaving *out);
+
+/* 1 for "LIKE", "NOT LIKE", "IN", "NOT IN", "IN SET", "NOT IN SET" (exactly so written), else 0. */
 int hipIsSetOperator(const char *op);
 
 /* THE SET LIST OF AN UPDATE.  One assignment `column = value`, its value text typed by the column exactly as the literal of

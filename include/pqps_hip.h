@@ -765,6 +765,29 @@ int pqps_bins_compact(pqps_ctx *ctx, const void *bins, uint32_t n_bins, int valu
 int pqps_group_sort(pqps_ctx *ctx, const pqps_column *group_col, uint32_t bin_base, uint64_t n_bins, const pqps_column *value_col,
                     uint64_t n_rows, const uint32_t *ids, uint64_t n, uint32_t id_base, uint64_t **runs_dev, uint64_t *n_runs, void *stream);
 
+/* ---- HAVING: dense bins into the presence bitmap of a value set -------------------------------------------------------------
+ * No counterpart in the reference.  pqps_bins_having turns the dense bins of a grouped scan into the bitmap pqps_member_flags
+ * reads (PQPS_MEMBER_BITMAP with n_bits = n_bins), all on the device.
+ * INPUT   `bins` (device): `valued` 0 -- the n_bins u32 counts of pqps_filter_group / pqps_filter_group_wide (`field` must be
+ *         PQPS_HAVING_COUNT); otherwise the field-major [4][n_bins] u64 of pqps_filter_aggregate (counts, sums, min images,
+ *         max images).  `field` PQPS_HAVING_COUNT / _SUM / _MIN / _MAX picks the compared row, `op` PQPS_HAVING_EQ .. _GE the
+ *         comparison with `constant`: counts unsigned; sums as int64 when `value_signed`, else unsigned; MIN and MAX unsigned on
+ *         IMAGES (the caller passes the constant as an image: (u64)(i64)v ^ 2^63 for an i32 value, v itself for command_id).
+ * OUTPUT  bit b of `bitmap` (device, 8-byte aligned, u32 words, LSB first) = count[b] != 0 && field[b] OP constant: a bin
+ *         without rows is never set.  All (n_bins + 31) / 32 words are written in full, the tail bits of the last word 0,
+ *         nothing past them.  *members (device, may be NULL; the call zeroes it first) = the popcount.
+ * Wave64, one bin per lane per round: streaming loads of the count and of the compared field alone, one ballot and one 8-byte
+ * store per wave and round, a persistent grid, one atomic add per workgroup for `members`; no workgroup waits for another.
+ * Asynchronous on `stream`.  PQPS_EINVAL before any launch: a NULL ctx / bins / bitmap, a bitmap that is not 8-byte aligned,
+ * n_bins 0, a field or op outside the enums, `valued` 0 with a field other than PQPS_HAVING_COUNT.
+ * pqps_bins_rows: *rows (device; zeroed by the call) = the sum of the counts of the same bins -- the rows a fused grouped scan
+ * matched, which that scan does not report.  Asynchronous; PQPS_EINVAL for a NULL argument or n_bins 0. */
+enum { PQPS_HAVING_COUNT = 0, PQPS_HAVING_SUM = 1, PQPS_HAVING_MIN = 2, PQPS_HAVING_MAX = 3 };
+enum { PQPS_HAVING_EQ = 0, PQPS_HAVING_NE = 1, PQPS_HAVING_LT = 2, PQPS_HAVING_GT = 3, PQPS_HAVING_LE = 4, PQPS_HAVING_GE = 5 };
+int pqps_bins_having(pqps_ctx *ctx, const void *bins, uint32_t n_bins, int valued, int field, int op, uint64_t constant,
+                     int value_signed, uint32_t *bitmap, uint64_t *members, void *stream);
+int pqps_bins_rows(pqps_ctx *ctx, const void *bins, uint32_t n_bins, int valued, uint64_t *rows, void *stream);
+
 /* ---- UPDATE SET ... WHERE: constants assigned in place to the rows a WHERE selects -----------------------------------------
  * No counterpart in the reference (its parser knows no UPDATE).  A TARGET is a column and the value every selected row of it
  * receives: `data` 16-byte aligned and WRITABLE up to n_rows rounded up to PQPS_STEP_ROWS rows, `width` 1, 2, 4 or 8 bytes

@@ -153,6 +153,34 @@ class GroupTopResult(C.Structure):
                 ("queryTime", C.c_double), ("success", C.c_bool)]
 
 
+class SetHaving(C.Structure):
+    """struct hipSetHaving (include/executeEngine-hip.h)."""
+    _fields_ = [("aggregate", C.c_int), ("valueColumn", C.c_char_p), ("op", C.c_char_p), ("constant", C.c_char_p)]
+
+
+class ValueSetResult(C.Structure):
+    """struct hipValueSet (include/executeEngine-hip.h)."""
+    _fields_ = [("success", C.c_bool), ("id", C.c_uint), ("column", C.c_int), ("kind", C.c_int),
+                ("members", C.c_ulonglong), ("rows", C.c_ulonglong), ("queryTime", C.c_double)]
+
+
+class SetKeysResult(C.Structure):
+    """struct hipSetKeys (include/executeEngine-hip.h)."""
+    _fields_ = [("success", C.c_bool), ("column", C.c_int), ("kind", C.c_int), ("numKeys", C.c_int),
+                ("keys", C.POINTER(C.c_longlong)), ("keyText", C.POINTER(C.c_char_p))]
+
+
+class SetInfo(C.Structure):
+    """struct hipSetInfo (include/hipPredicate.h)."""
+    _fields_ = [("id", C.c_uint32), ("column", C.c_int), ("kind", C.c_int), ("base", C.c_uint32), ("n_bits", C.c_uint64),
+                ("members", C.c_uint64), ("stale", C.c_int)]
+
+
+class Having(C.Structure):
+    """struct hipHaving (include/hipPredicate.h)."""
+    _fields_ = [("field", C.c_int), ("op", C.c_int), ("constant", C.c_uint64), ("value_signed", C.c_int)]
+
+
 class DistinctResult(C.Structure):
     """struct hipDistinctResult (include/executeEngine-hip.h)."""
     _fields_ = [("valueColumn", C.c_int), ("valueKind", C.c_int), ("groupColumn", C.c_int), ("groupKind", C.c_int),
@@ -230,7 +258,7 @@ class Pass(C.Structure):
     _fields_ = [("pred", Predicate), ("column_ids", C.c_int * MAX_COLUMNS),
                 ("member", C.c_int), ("member_column", C.c_int), ("member_form", C.c_int), ("member_base", C.c_uint32),
                 ("member_bits", C.c_uint64), ("member_bitmap", C.POINTER(C.c_uint32)), ("member_list", C.POINTER(C.c_uint64)),
-                ("member_count", C.c_uint32)]
+                ("member_count", C.c_uint32), ("member_set", C.c_uint32)]
 
 
 class Plan(C.Structure):
@@ -473,6 +501,10 @@ def lib():
     L.pqps_exchange_destroy.argtypes = [vp]
     L.hipCompileWhere.argtypes = [C.POINTER(Schema), W, C.POINTER(Predicate), C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
     L.hipCompileWherePlan.argtypes = [C.POINTER(Schema), W, C.POINTER(Plan), C.c_char_p, C.c_size_t]
+    L.hipCompileWherePlanSets.argtypes = [C.POINTER(Schema), W, C.POINTER(SetInfo), C.c_int, C.POINTER(Plan), C.c_char_p, C.c_size_t]
+    L.hipCompileHaving.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.POINTER(Having)]
+    L.pqps_bins_having.argtypes = [vp, vp, u32, C.c_int, C.c_int, C.c_int, u64, C.c_int, vp, vp, vp]
+    L.pqps_bins_rows.argtypes = [vp, vp, u32, C.c_int, vp, vp]
     L.hipPlanFree.argtypes = [C.POINTER(Plan)]
     L.hipPlanFree.restype = None
     L.hipColumnId.argtypes = [C.c_char_p]
@@ -573,6 +605,13 @@ def lib():
     L.pqps_group_sort.argtypes = [vp, C.POINTER(Column), u32, u64, C.POINTER(Column), u64, vp, u64, u32, C.POINTER(vp), C.POINTER(u64), vp]
     L.hipGroupTopOrder.restype = C.c_longlong
     L.hipGroupTopOrder.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, C.c_int, C.c_int, C.c_longlong, vp]
+    L.hipEngineCreateSetHIP.restype = C.POINTER(ValueSetResult)
+    L.hipEngineCreateSetHIP.argtypes = [E, C.c_char_p, W, C.POINTER(SetHaving)]
+    L.hipEngineSetKeysHIP.restype = C.POINTER(SetKeysResult)
+    L.hipEngineSetKeysHIP.argtypes = [E, C.POINTER(ValueSetResult)]
+    L.freeSetKeysHIP.argtypes = [C.POINTER(SetKeysResult)]
+    L.freeSetKeysHIP.restype = None
+    L.hipEngineFreeSetHIP.argtypes = [E, C.POINTER(ValueSetResult)]
     L.executeQueryCountDistinctHIP.restype = C.POINTER(DistinctResult)
     L.executeQueryCountDistinctHIP.argtypes = [E, C.c_char_p, C.c_char_p, W]
     L.freeDistinctResultHIP.argtypes = [C.POINTER(DistinctResult)]
@@ -694,15 +733,26 @@ class SchemaSpec:
         return self
 
 
-def compile_plan_sets(spec: SchemaSpec, chain):
+def compile_plan_sets(spec: SchemaSpec, chain, sets=None):
     """-> [(Predicate, [column id per slot], member), ...]: the passes of hipCompileWherePlan.  A column id >= MAX_COLUMNS
     names the flags of pass (id - MAX_COLUMNS); the last pass is the query's result.  `member` is None for a filter pass;
     for a member pass (a LIKE / IN set, include/hipPredicate.h; its Predicate is empty) it is a dict: "column" (id), "form"
-    (MEMBER_BITMAP / MEMBER_LIST), "base", "n_bits", "words" (the bitmap's u32 words) and "values" (the sorted list)."""
+    (MEMBER_BITMAP / MEMBER_LIST), "base", "n_bits", "words" (the bitmap's u32 words), "values" (the sorted list) and "set"
+    (the id of the value set an IN SET node names, 0 otherwise: such a pass has no words of its own).
+    `sets`: the table of value sets the chain may name (hipCompileWherePlanSets) -- dicts with "id", "column" (name or id),
+    "kind", "base", "n_bits", "members", "stale"; None compiles through hipCompileWherePlan itself."""
     wl = WhereList(chain)
     plan = Plan()
     err = C.create_string_buffer(200)
-    rc = lib().hipCompileWherePlan(C.byref(spec.schema), wl.ptr, C.byref(plan), err, 200)
+    if sets is None:
+        rc = lib().hipCompileWherePlan(C.byref(spec.schema), wl.ptr, C.byref(plan), err, 200)
+    else:
+        infos = (SetInfo * max(1, len(sets)))()
+        for i, d in enumerate(sets):
+            col = d["column"]
+            infos[i] = SetInfo(d["id"], COL[col] if isinstance(col, str) else col, d["kind"], d.get("base", 0) & 0xFFFFFFFF,
+                               d["n_bits"], d["members"], int(d.get("stale", 0)))
+        rc = lib().hipCompileWherePlanSets(C.byref(spec.schema), wl.ptr, infos, len(sets), C.byref(plan), err, 200)
     if rc != 0:
         raise PqpsError("hipCompileWherePlan: " + err.value.decode())
     out = []
@@ -713,8 +763,8 @@ def compile_plan_sets(spec: SchemaSpec, chain):
         member = None
         if p.member:
             bitmap = p.member_form == MEMBER_BITMAP
-            member = dict(column=p.member_column, form=p.member_form, base=p.member_base, n_bits=p.member_bits,
-                          words=list(p.member_bitmap[:(p.member_bits + 31) // 32]) if bitmap else [],
+            member = dict(column=p.member_column, form=p.member_form, base=p.member_base, n_bits=p.member_bits, set=p.member_set,
+                          words=list(p.member_bitmap[:(p.member_bits + 31) // 32]) if bitmap and not p.member_set else [],
                           values=[] if bitmap else list(p.member_list[:p.member_count]))
         out.append((pred, list(p.column_ids[:pred.n_columns]), member))
     lib().hipPlanFree(C.byref(plan))
@@ -1082,6 +1132,42 @@ class SyntheticTable:
         self.ptr = {}
 
 
+class ValueSet:
+    """A value set of an engine (hipEngineCreateSetHIP): the values of `column` that the rows of an inner WHERE carry,
+    optionally filtered by a HAVING, kept on the device.  `item()` is the chain item that tests a column against it."""
+
+    def __init__(self, engine, handle, column):
+        self.engine, self._h, self.column = engine, handle, column
+        r = handle.contents
+        self.id, self.members, self.rows, self.seconds = int(r.id), int(r.members), int(r.rows), float(r.queryTime)
+
+    def item(self, attribute=None, negate=False):
+        """(attribute or the set's own column, "IN SET" | "NOT IN SET", str(id))."""
+        return (attribute or self.column, "NOT IN SET" if negate else "IN SET", str(self.id))
+
+    def keys(self):
+        """hipEngineSetKeysHIP: the members' key texts in key order.  Raises PqpsError for a stale or freed set."""
+        if not self._h or not self.engine.e:
+            raise PqpsError(f"value set {self.id}: freed")
+        res = lib().hipEngineSetKeysHIP(self.engine.e, self._h)
+        if not res:
+            raise PqpsError(f"value set {self.id}: no keys")
+        try:
+            r = res.contents
+            if not r.success:
+                raise PqpsError(f"value set {self.id}: keys refused (reason on stderr)")
+            return [r.keyText[g].decode("latin-1") for g in range(r.numKeys)]
+        finally:
+            lib().freeSetKeysHIP(res)
+
+    def free(self):
+        """hipEngineFreeSetHIP; raises PqpsError when refused (the calling thread holds a ticket).  After the engine is
+        closed there is nothing left to free."""
+        if self._h and lib().hipEngineFreeSetHIP(self.engine.e or None, self._h) != 0:
+            raise PqpsError(f"value set {self.id}: free refused (reason on stderr)")
+        self._h = None
+
+
 class HipEngine:
     """initializeEngineHIP / executeQuerySelectHIP / destroyEngineHIP from Python."""
 
@@ -1256,6 +1342,33 @@ class HipEngine:
     def count(self, chain):
         wl = WhereList(chain)
         return lib().executeQueryCountHIP(self.e, wl.ptr)
+
+    def value_set(self, column, chain=None, having=None):
+        """hipEngineCreateSetHIP: the ValueSet of the values of `column` over the rows for which `chain` is true (None: every
+        row; scan semantics, each row once).  having = ("count" | "sum" | "min" | "max", value_column | None, op, constant)
+        keeps the values whose aggregate over those rows satisfies `op constant`.  Raises PqpsError when the engine refuses
+        (reason on stderr)."""
+        wl = WhereList(chain)
+        hv = None
+        if having is not None:
+            agg, vcol, op, const = having
+            hv = SetHaving(TOP_BY.get(agg, agg), vcol.encode() if vcol else None, str(op).encode(), str(const).encode())
+        res = lib().hipEngineCreateSetHIP(self.e, column.encode(), wl.ptr, C.byref(hv) if hv is not None else None)
+        if not res:
+            raise PqpsError(f"value_set({column!r}): no result")
+        if not res.contents.success:
+            lib().hipEngineFreeSetHIP(self.e, res)
+            raise PqpsError(f"value_set({column!r}, having={having!r}) refused or failed (reason on stderr)")
+        return ValueSet(self, res, column)
+
+    def in_select(self, attribute, column, chain=None, having=None, negate=False):
+        """The chain item `attribute [NOT] IN (SELECT column FROM commands WHERE chain [GROUP BY column HAVING having])`: makes
+        the value set and keeps it alive with the engine (close() frees it)."""
+        vs = self.value_set(column, chain, having)
+        if not hasattr(self, "_kept_sets"):
+            self._kept_sets = []
+        self._kept_sets.append(vs)
+        return vs.item(attribute, negate)
 
     def group_count(self, column, chain=None):
         """executeQueryGroupCountHIP: [(key_text, count), ...] in key order for the rows select_ids(chain) returns,
@@ -1593,5 +1706,5 @@ class HipEngine:
 
     def close(self):
         if self.e:
-            lib().destroyEngineHIP(self.e)
+            lib().destroyEngineHIP(self.e)                     # frees the value sets that are left, too
             self.e = None

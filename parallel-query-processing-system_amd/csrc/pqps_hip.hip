@@ -25,6 +25,7 @@
 #include "fused_common.hpp"
 #include "bins_kernels.hpp"
 #include "member_kernels.hpp"
+#include "set_kernels.hpp"
 #include "topk_kernels.hpp"
 #include "order_multi_kernels.hpp"
 #include "first_kernels.hpp"
@@ -3245,6 +3246,42 @@ int pqps_bins_compact(pqps_ctx *ctx, const void *bins, uint32_t n_bins, int valu
     }
     *runs_dev = out;
     *n_runs = runs;
+    return PQPS_OK;
+}
+
+int pqps_bins_having(pqps_ctx *ctx, const void *bins, uint32_t n_bins, int valued, int field, int op, uint64_t constant,
+                     int value_signed, uint32_t *bitmap, uint64_t *members, void *stream) {
+    if (!ctx || !bins || !bitmap) return fail(PQPS_EINVAL, "NULL argument");
+    if (((uintptr_t)bitmap & 7u) != 0) return fail(PQPS_EINVAL, "bitmap not 8-byte aligned");
+    if (n_bins == 0) return fail(PQPS_EINVAL, "0 bins");
+    if (field < PQPS_HAVING_COUNT || field > PQPS_HAVING_MAX) return fail(PQPS_EINVAL, "HAVING field %d", field);
+    if (op < PQPS_HAVING_EQ || op > PQPS_HAVING_GE) return fail(PQPS_EINVAL, "HAVING op %d", op);
+    if (!valued && field != PQPS_HAVING_COUNT) return fail(PQPS_EINVAL, "counts alone have no field %d", field);
+    hipStream_t s = pick_stream(ctx, stream);
+    if (members) HIP_TRY(hipMemsetAsync(members, 0, sizeof(uint64_t), s));
+    using having_fn = void (*)(const void *, uint64_t, int, int, uint64_t, uint32_t *, unsigned long long *);
+    static const having_fn fns[5] = {
+        bins_having_kernel<false, PQPS_HAVING_COUNT>, bins_having_kernel<true, PQPS_HAVING_COUNT>, bins_having_kernel<true, PQPS_HAVING_SUM>,
+        bins_having_kernel<true, PQPS_HAVING_MIN>, bins_having_kernel<true, PQPS_HAVING_MAX>,
+    };
+    const uint64_t rounds = ((uint64_t)n_bins + 63) / 64;
+    snprintf(g_kernel, sizeof g_kernel, "bins_having_kernel<%s, %d>", valued ? "valued" : "count", field);
+    hipLaunchKernelGGL(fns[valued ? 1 + field : 0], dim3(list_grid(ctx, rounds * 64, 8)), dim3(kHavingBlock), 0, s, bins, (uint64_t)n_bins, op,
+                       value_signed ? 1 : 0, constant, bitmap, (unsigned long long *)members);
+    HIP_TRY(hipGetLastError());
+    return PQPS_OK;
+}
+
+int pqps_bins_rows(pqps_ctx *ctx, const void *bins, uint32_t n_bins, int valued, uint64_t *rows, void *stream) {
+    if (!ctx || !bins || !rows) return fail(PQPS_EINVAL, "NULL argument");
+    if (n_bins == 0) return fail(PQPS_EINVAL, "0 bins");
+    hipStream_t s = pick_stream(ctx, stream);
+    HIP_TRY(hipMemsetAsync(rows, 0, sizeof(uint64_t), s));
+    snprintf(g_kernel, sizeof g_kernel, "bins_rows_kernel<%s>", valued ? "valued" : "count");
+    const dim3 grid(list_grid(ctx, n_bins, 8));
+    if (valued) hipLaunchKernelGGL(bins_rows_kernel<true>, grid, dim3(kHavingBlock), 0, s, bins, (uint64_t)n_bins, (unsigned long long *)rows);
+    else hipLaunchKernelGGL(bins_rows_kernel<false>, grid, dim3(kHavingBlock), 0, s, bins, (uint64_t)n_bins, (unsigned long long *)rows);
+    HIP_TRY(hipGetLastError());
     return PQPS_OK;
 }
 

@@ -865,12 +865,14 @@ void rebuildDeviceTableHIP(struct engineS *engine) {
     record *block = t->row_block;
     const size_t row_capacity = t->row_capacity;
     struct hipLocks *locks = t->locks;
+    struct hipValueSets *sets = t->sets;
     table_release(t, engine->num_indexes);
     memset(t, 0, sizeof *t);
     table_fill(t, ctxs, n_shards, NULL, engine->all_records, (size_t)engine->num_records);
     t->row_block = block;
     t->row_capacity = row_capacity;
     t->locks = locks;
+    t->sets = sets;
     table_make_engine(t);
     for (int s = 0; s < n_shards && engine->num_indexes > 0; s++) {
         struct hipTable *sh = hipTableShard(t, s);

@@ -53,12 +53,95 @@ static int oom(void) {
 
 /* ---- predicate binding --------------------------------------------------------- */
 
-/* The compiled WHERE of one query: usually one pass; see hipCompileWherePlan. */
+/* The value sets of one engine (include/executeEngine-hip.h): what an IN SET node of a WHERE names.  The registry hangs off
+ * the engine's table; `set[i].id` 0 is a free entry.  Sets are made by readers (several at once) and freed or made stale by
+ * writers (alone): g_sets_lock guards the entries themselves, the table's locks keep a bitmap where a query in flight reads it. */
+struct value_set {
+    uint32_t id;
+    int column, kind;                    /* B: HIPCOL_*, HIPKIND_DICT / HIPKIND_I32                                   */
+    uint64_t version;                    /* the registry's when the set was made                                     */
+    bool stale;                          /* a writer came after it: no device memory any more                        */
+    uint32_t base;                       /* bit i of the bitmap: the code i, or the i32 value base + i               */
+    int32_t lo;
+    uint64_t n_bits, members, rows;
+    uint32_t *bitmap[HIP_MAX_SHARDS];    /* one copy per shard, on its device                                        */
+};
+struct hipValueSets {
+    uint64_t version;                    /* bumped by every successful writer                                        */
+    uint32_t next_id;
+    struct value_set set[HIP_MAX_VALUE_SETS];
+};
+static pthread_mutex_t g_sets_lock = PTHREAD_MUTEX_INITIALIZER;
+
+/* (g_sets_lock held) the entry of set `id`, NULL if there is none */
+static struct value_set *value_set_find(const struct hipTable *t, uint32_t id) {
+    for (int i = 0; t->sets && id && i < HIP_MAX_VALUE_SETS; i++)
+        if (t->sets->set[i].id == id) return &t->sets->set[i];
+    return NULL;
+}
+
+/* What the WHERE compiler may know of the table's sets: infos[HIP_MAX_VALUE_SETS], the number filled in returned. */
+static int value_set_infos(const struct hipTable *t, struct hipSetInfo *infos) {
+    int n = 0;
+    pthread_mutex_lock(&g_sets_lock);
+    for (int i = 0; t->sets && i < HIP_MAX_VALUE_SETS; i++) {
+        const struct value_set *vs = &t->sets->set[i];
+        if (!vs->id) continue;
+        infos[n++] = (struct hipSetInfo){ .id = vs->id, .column = vs->column, .kind = vs->kind, .base = vs->base, .n_bits = vs->n_bits,
+                                          .members = vs->members, .stale = vs->stale };
+    }
+    pthread_mutex_unlock(&g_sets_lock);
+    return n;
+}
+
+/* The bitmap of set `id` on shard s: the set's own buffer, which the caller does not own (NULL: no such set). */
+static const uint32_t *value_set_bitmap(const struct hipTable *t, uint32_t id, int s) {
+    pthread_mutex_lock(&g_sets_lock);
+    const struct value_set *vs = value_set_find(t, id);
+    const uint32_t *bitmap = vs && !vs->stale ? vs->bitmap[s] : NULL;
+    pthread_mutex_unlock(&g_sets_lock);
+    return bitmap;
+}
+
+/* (g_sets_lock held, no query in flight) gives back the device memory of a set */
+static void value_set_release(struct hipTable *t, struct value_set *vs) {
+    for (int s = 0; s < hipTableShards(t) && s < HIP_MAX_SHARDS; s++) {
+        if (vs->bitmap[s]) pqps_free(hipTableShard(t, s)->ctx, vs->bitmap[s]);
+        vs->bitmap[s] = NULL;
+    }
+}
+
+/* A writer succeeded (the caller holds the table exclusively): the codes may have moved, every set is stale from now on. */
+static void value_sets_invalidate(struct hipTable *t) {
+    if (!t || !t->sets) return;
+    pthread_mutex_lock(&g_sets_lock);
+    t->sets->version++;
+    for (int i = 0; i < HIP_MAX_VALUE_SETS; i++) {
+        struct value_set *vs = &t->sets->set[i];
+        if (!vs->id || vs->stale) continue;
+        vs->stale = true;
+        value_set_release(t, vs);
+    }
+    pthread_mutex_unlock(&g_sets_lock);
+}
+
+/* destroyEngineHIP: whatever is left, before the contexts go */
+static void value_sets_destroy(struct hipTable *t) {
+    if (!t || !t->sets) return;
+    pthread_mutex_lock(&g_sets_lock);
+    for (int i = 0; i < HIP_MAX_VALUE_SETS; i++) if (t->sets->set[i].id) value_set_release(t, &t->sets->set[i]);
+    free(t->sets);
+    t->sets = NULL;
+    pthread_mutex_unlock(&g_sets_lock);
+}
+
+/* The compiled WHERE of one query: usually one pass; see hipCompileWherePlan.  An IN SET node names a set of the table. */
 static int bind_where(const struct hipTable *t, const struct whereClauseS *where, struct hipPlan *plan) {
     struct hipSchema schema;
+    struct hipSetInfo infos[HIP_MAX_VALUE_SETS];
     char err[160];
     hipSchemaOfTable(t, &schema);
-    if (hipCompileWherePlan(&schema, where, plan, err, sizeof err) != 0) {
+    if (hipCompileWherePlanSets(&schema, where, infos, value_set_infos(t, infos), plan, err, sizeof err) != 0) {
         fprintf(stderr, "HIP engine: cannot compile WHERE clause: %s\n", err);
         return -1;
     }
@@ -132,10 +215,11 @@ static bool member_writes_plane(const struct hipPlan *plan, int k, bool scan_las
 }
 
 /* The passes in front of the last on one shard, on (ctx, stream): each leaves one flag per row -- a filter pass through
- * pqps_filter_flags, a member pass (a LIKE / IN set as a bitmap or list, uploaded here, owned by `sp`) through
- * pqps_member_flags.  `count_dev`: a device word for the counts nobody reads. */
-static int head_passes(const struct hipPlan *plan, struct hipTable *sh, struct shard_pred *sp, pqps_ctx *ctx, void *stream,
+ * pqps_filter_flags, a member pass (a LIKE / IN set as a bitmap or list, uploaded here, owned by `sp`; or the bitmap of a
+ * value set of table `t`, which stays the set's) through pqps_member_flags on shard s.  `count_dev`: a device word for the counts nobody reads. */
+static int head_passes(const struct hipPlan *plan, const struct hipTable *t, int s, struct shard_pred *sp, pqps_ctx *ctx, void *stream,
                        uint64_t *count_dev, bool scan_last) {
+    struct hipTable *sh = hipTableShard((struct hipTable *)t, s);
     if (plan->n_passes < 2) return 0;
     const size_t n = (size_t)plan->n_passes - 1;
     sp->flags = calloc(n, sizeof *sp->flags);
@@ -159,13 +243,19 @@ static int head_passes(const struct hipPlan *plan, struct hipTable *sh, struct s
         const bool bitmap = pass->member_form == PQPS_MEMBER_BITMAP;
         const void *host = bitmap ? (const void *)pass->member_bitmap : (const void *)pass->member_list;
         const size_t bytes = bitmap ? (size_t)((pass->member_bits + 31) / 32) * sizeof(uint32_t) : (size_t)pass->member_count * sizeof(uint64_t);
-        if (bytes) {
+        const void *set = NULL;
+        if (pass->member_set) {
+            /* a value set: its bitmap is on this device already, where the build left it, and stays the set's */
+            set = value_set_bitmap(t, pass->member_set, s);
+            if (!set) { fprintf(stderr, "HIP engine: value set %u has no bitmap on shard %d\n", pass->member_set, s); return -1; }
+        } else if (bytes) {
             TRY(pqps_malloc(sh->ctx, bytes, &sp->member[k]), "member set allocation");
             TRY(pqps_upload(ctx, sp->member[k], host, bytes, stream), "member set upload");
+            set = sp->member[k];
         }
         sp->plane[k] = member_writes_plane(plan, k, scan_last);
         TRY(pqps_member_flags(ctx, &sh->col[pass->member_column], sh->n_rows, pass->member_form, pass->member_base, pass->member_bits,
-                              bitmap ? sp->member[k] : NULL, bitmap ? NULL : sp->member[k], pass->member_count,
+                              bitmap ? set : NULL, bitmap ? NULL : set, pass->member_count,
                               sp->plane[k] ? PQPS_MEMBER_PLANE : PQPS_MEMBER_BYTES, sp->flags[k], count_dev, stream), "member flags");
     }
     return 0;
@@ -320,7 +410,7 @@ static int issue_calls(struct query *q, int s, pqps_ctx *ctx, void *stream) {
     const struct hipPass *last = &plan->pass[plan->n_passes - 1];
     /* the passes before the last: one flag per row each */
     const bool scan_last = q->count_only || q->n_probes == 0;
-    if (head_passes(plan, sh, sp, ctx, stream, L->count_dev + 4, scan_last) != 0) return -1;
+    if (head_passes(plan, q->t, s, sp, ctx, stream, L->count_dev + 4, scan_last) != 0) return -1;
     sp->pred = &last->pred;
     sp->n_cols = last->pred.n_columns;
     pass_columns(sh, last, sp, scan_last, sp->cols);
@@ -2038,6 +2128,343 @@ void freeGroupTopResultHIP(struct hipGroupTopResult *res) {
     free(res);
 }
 
+/* ---- value sets: IN (SELECT column ... [GROUP BY column HAVING agg op n]) (include/executeEngine-hip.h) ----------------- */
+
+/* How one set is built on every shard: the bins of B (gp) and what is made of them. */
+struct set_plan {
+    const struct group_plan *gp;
+    bool having;                         /* bins, then pqps_bins_having; otherwise the presence bitmap of the distinct calls */
+    bool wide;                           /* more than HIP_GROUP_MAX_BINS bins: the wide bins                                 */
+    int vc;                              /* the value column of the bins, -1: u32 counts                                     */
+    struct hipHaving hv;
+    size_t words;                        /* u32 words of the bitmap                                                          */
+    void **work;                         /* shard s: its bins (having), or the words [total][distinct]                       */
+    uint32_t **bitmap;                   /* shard s: the set's bitmap                                                        */
+    bool *filled;                        /* shard s: a launch wrote work[s] / bitmap[s]                                      */
+};
+
+static int set_fused_call(struct query *q, int s, pqps_ctx *ctx, void *stream, void *arg) {
+    const struct set_plan *p = arg;
+    const struct group_plan *gp = p->gp;
+    const struct hipTable *sh = hipTableShard(q->t, s);
+    const struct shard_pred *sp = &q->sp[s];
+    const pqps_column *vcol = p->vc >= 0 ? &sh->col[p->vc] : NULL;
+    int rc;
+    if (!p->having)
+        rc = pqps_filter_distinct(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, &gp->gcol[s], gp->bin_base, gp->n_bins, NULL, 0, 1,
+                                  p->bitmap[s], (uint64_t *)p->work[s], q->n_shards > 1 ? NULL : (uint64_t *)p->work[s] + 1, stream);
+    else if (p->wide)
+        rc = pqps_filter_group_wide(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, vcol, &gp->gcol[s], gp->bin_base, gp->n_bins, p->work[s], stream);
+    else if (vcol)
+        rc = pqps_filter_aggregate(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, vcol, gp->single ? NULL : &gp->gcol[s], gp->bin_base,
+                                   gp->n_bins, p->work[s], stream);
+    else
+        rc = pqps_filter_group(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, &gp->gcol[s], gp->bin_base, gp->n_bins, p->work[s], stream);
+    if (rc != PQPS_OK) return engine_error("value set scan");
+    p->filled[s] = true;
+    return 0;
+}
+
+/* the same over shard s's list (query_lists), on the lane's copy context */
+static int set_list_call(struct query *q, int s, const struct set_plan *p) {
+    const struct group_plan *gp = p->gp;
+    const struct hipTable *sh = hipTableShard(q->t, s);
+    const struct hipLane *L = query_lane(q, s);
+    pqps_ctx *cs = lane_copy_ctx(q, s);
+    const pqps_column *vcol = p->vc >= 0 ? &sh->col[p->vc] : NULL;
+    const uint32_t row0 = (uint32_t)sh->row0;
+    int rc;
+    if (!p->having)
+        rc = pqps_distinct_list(cs, &gp->gcol[s], gp->bin_base, gp->n_bins, NULL, 0, 1, sh->n_rows, L->ids_dev, L->count_dev, q->count[s], row0,
+                                p->bitmap[s], q->n_shards > 1 ? NULL : (uint64_t *)p->work[s] + 1, NULL);
+    else if (p->wide)
+        rc = pqps_group_wide_list(cs, vcol, &gp->gcol[s], sh->n_rows, L->ids_dev, L->count_dev, q->count[s], row0, gp->bin_base, gp->n_bins, p->work[s], NULL);
+    else if (vcol)
+        rc = pqps_aggregate_list(cs, vcol, gp->single ? NULL : &gp->gcol[s], sh->n_rows, L->ids_dev, L->count_dev, q->count[s], row0, gp->bin_base,
+                                 gp->n_bins, p->work[s], NULL);
+    else
+        rc = pqps_group_list(cs, &gp->gcol[s], sh->n_rows, L->ids_dev, L->count_dev, q->count[s], row0, gp->bin_base, gp->n_bins, p->work[s], NULL);
+    if (rc != PQPS_OK) return engine_error("value set list");
+    p->filled[s] = true;
+    return 0;
+}
+
+/* The HAVING of bins on shard 0's device into the set's bitmap there: out[0] = the rows the bins hold, out[1] = the members.
+ * This is the only place the comparison is made. */
+static int set_having(pqps_ctx *c0, const struct set_plan *p, const void *bins, uint32_t *bitmap, uint64_t *cnt_dev, uint64_t out[2]) {
+    const int valued = p->vc >= 0;
+    if (pqps_bins_rows(c0, bins, p->gp->n_bins, valued, cnt_dev, NULL) != PQPS_OK ||
+        pqps_bins_having(c0, bins, p->gp->n_bins, valued, p->hv.field, p->hv.op, p->hv.constant, p->hv.value_signed, bitmap, cnt_dev + 1, NULL) != PQPS_OK ||
+        pqps_download(c0, out, cnt_dev, 2 * sizeof *out, NULL) != PQPS_OK)
+        return engine_error("HAVING");
+    return 0;
+}
+
+/* Builds the bitmap of vs on every shard (vs->bitmap[s]; on failure none is left) and fills vs->rows / vs->members. */
+static int set_build(struct query *q, struct set_plan *p, struct value_set *vs) {
+    const struct group_plan *gp = p->gp;
+    const bool valued = p->vc >= 0, multi = q->n_shards > 1;
+    const uint32_t n_bins = gp->n_bins;
+    const size_t bm_bytes = (p->words + (p->words & 1u)) * sizeof(uint32_t);       /* whole 8-byte stores of pqps_bins_having */
+    const size_t work_bytes = p->having ? bins_bytes(n_bins, p->vc) : 2 * sizeof(uint64_t);
+    void *work[HIP_MAX_SHARDS] = { NULL };
+    bool filled[HIP_MAX_SHARDS] = { false };
+    uint64_t *cnt_dev = NULL, out[2] = { 0, 0 };
+    void *host = NULL;
+    int rc = 0;
+    p->work = work; p->bitmap = vs->bitmap; p->filled = filled;
+    for (int s = 0; s < q->n_shards && rc == 0; s++) {
+        struct hipTable *sh = hipTableShard(q->t, s);
+        if (pqps_malloc(sh->ctx, bm_bytes, (void **)&vs->bitmap[s]) != PQPS_OK || pqps_malloc(sh->ctx, work_bytes, &work[s]) != PQPS_OK)
+            rc = engine_error("value set buffers");
+    }
+    if (rc == 0 && pqps_malloc(hipTableShard(q->t, 0)->ctx, 2 * sizeof(uint64_t), (void **)&cnt_dev) != PQPS_OK) rc = engine_error("value set buffers");
+    if (rc == 0 && gp->fused) rc = fused_issue(q, set_fused_call, p);
+    else if (rc == 0) {
+        rc = query_lists(q);
+        for (int s = 0; s < q->n_shards && rc == 0; s++) if (q->count[s]) rc = set_list_call(q, s, p);
+    }
+    pqps_ctx *c0 = lane_copy_ctx(q, 0);
+    if (rc == 0 && !multi) {
+        /* one shard: neither bins nor bitmap leave the device, the two counts do */
+        if (!filled[0]) {
+            if (pqps_memset(c0, vs->bitmap[0], 0, bm_bytes, NULL) != PQPS_OK || pqps_ctx_sync(c0, NULL) != PQPS_OK) rc = engine_error("value set bitmap");
+        } else if (p->having) rc = set_having(c0, p, work[0], vs->bitmap[0], cnt_dev, out);
+        else {
+            if (pqps_download(c0, out, work[0], sizeof out, NULL) != PQPS_OK) rc = engine_error("value set counts");
+            if (!gp->fused) out[0] = q->total;                              /* (the list form leaves no total) */
+        }
+    } else if (rc == 0 && !p->having) {
+        /* several shards: the OR of their bitmaps, placed on every shard; the popcount on shard 0 */
+        uint32_t *merged = calloc(p->words, sizeof *merged);
+        host = malloc(p->words * sizeof(uint32_t));
+        if (!merged || !host) rc = oom();
+        for (int s = 0; s < q->n_shards && rc == 0; s++) {
+            uint64_t n = 0;
+            if (!filled[s]) continue;
+            pqps_ctx *cs = lane_copy_ctx(q, s);
+            if (pqps_download(cs, host, vs->bitmap[s], p->words * sizeof(uint32_t), NULL) != PQPS_OK ||
+                (gp->fused && pqps_download(cs, &n, work[s], sizeof n, NULL) != PQPS_OK)) { rc = engine_error("value set download"); break; }
+            for (size_t i = 0; i < p->words; i++) merged[i] |= ((const uint32_t *)host)[i];
+            out[0] += n;
+        }
+        if (rc == 0 && !gp->fused) out[0] = q->total;
+        for (int s = 0; s < q->n_shards && rc == 0; s++)
+            if (pqps_upload(lane_copy_ctx(q, s), vs->bitmap[s], merged, p->words * sizeof(uint32_t), NULL) != PQPS_OK) rc = engine_error("value set upload");
+        if (rc == 0 && (pqps_distinct_count(c0, vs->bitmap[0], n_bins, 1, cnt_dev + 1, NULL) != PQPS_OK ||
+                        pqps_download(c0, &out[1], cnt_dev + 1, sizeof out[1], NULL) != PQPS_OK))
+            rc = engine_error("value set popcount");
+        free(merged);
+    } else if (rc == 0) {
+        /* several shards: their bins combined as the grouped queries combine them, HAVING on shard 0, the bitmap to the others */
+        uint64_t *acc = bins_alloc(n_bins, valued);
+        host = malloc(work_bytes > p->words * sizeof(uint32_t) ? work_bytes : p->words * sizeof(uint32_t));
+        if (!acc) rc = -1;
+        else if (!host) rc = oom();
+        for (int s = 0; s < q->n_shards && rc == 0; s++) {
+            if (!filled[s]) continue;
+            if (pqps_download(lane_copy_ctx(q, s), host, work[s], work_bytes, NULL) != PQPS_OK) rc = engine_error("value set download");
+            else group_combine(&(struct bins_acc){ acc, n_bins, p->vc }, host);
+        }
+        if (rc == 0 && !valued) for (uint32_t k = 0; k < n_bins; k++) ((uint32_t *)host)[k] = (uint32_t)acc[k];   /* (a table has fewer than 2^31 rows) */
+        if (rc == 0 && pqps_upload(c0, work[0], valued ? (const void *)acc : host, work_bytes, NULL) != PQPS_OK) rc = engine_error("value set upload");
+        if (rc == 0) rc = set_having(c0, p, work[0], vs->bitmap[0], cnt_dev, out);
+        if (rc == 0 && pqps_download(c0, host, vs->bitmap[0], p->words * sizeof(uint32_t), NULL) != PQPS_OK) rc = engine_error("value set download");
+        for (int s = 1; s < q->n_shards && rc == 0; s++)
+            if (pqps_upload(lane_copy_ctx(q, s), vs->bitmap[s], host, p->words * sizeof(uint32_t), NULL) != PQPS_OK) rc = engine_error("value set upload");
+        free(acc);
+    }
+    free(host);
+    for (int s = 0; s < q->n_shards; s++) {
+        struct hipTable *sh = hipTableShard(q->t, s);
+        if (work[s]) pqps_free(sh->ctx, work[s]);
+        if (rc != 0 && vs->bitmap[s]) { pqps_free(sh->ctx, vs->bitmap[s]); vs->bitmap[s] = NULL; }
+    }
+    if (cnt_dev) pqps_free(hipTableShard(q->t, 0)->ctx, cnt_dev);
+    vs->rows = out[0];
+    vs->members = out[1];
+    return rc;
+}
+
+/* Enters vs into the table's registry under a new id; -1 (reason on stderr) when HIP_MAX_VALUE_SETS sets are there already. */
+static int value_set_register(struct hipTable *t, struct value_set *vs) {
+    int rc = -1;
+    pthread_mutex_lock(&g_sets_lock);
+    if (!t->sets && (t->sets = calloc(1, sizeof *t->sets))) t->sets->next_id = 1;
+    for (int i = 0; t->sets && i < HIP_MAX_VALUE_SETS && rc != 0; i++) {
+        if (t->sets->set[i].id) continue;
+        vs->id = t->sets->next_id++;
+        if (t->sets->next_id == 0) t->sets->next_id = 1;
+        vs->version = t->sets->version;
+        t->sets->set[i] = *vs;
+        rc = 0;
+    }
+    pthread_mutex_unlock(&g_sets_lock);
+    if (rc != 0) fprintf(stderr, "HIP engine: value set: %d sets are alive already (free one first)\n", HIP_MAX_VALUE_SETS);
+    return rc;
+}
+
+static bool value_sets_full(const struct hipTable *t) {
+    int n = 0;
+    pthread_mutex_lock(&g_sets_lock);
+    for (int i = 0; t->sets && i < HIP_MAX_VALUE_SETS; i++) n += t->sets->set[i].id != 0;
+    pthread_mutex_unlock(&g_sets_lock);
+    return n >= HIP_MAX_VALUE_SETS;
+}
+
+struct hipValueSet *hipEngineCreateSetHIP(struct engineS *engine, const char *column, struct whereClauseS *whereClause,
+                                          const struct hipSetHaving *having) {
+    const double t0 = now_seconds();
+    struct hipValueSet *res = calloc(1, sizeof *res);
+    if (!res) { oom(); return NULL; }
+    res->column = res->kind = -1;
+    if (!engine || !engine->record_block || !column) { fprintf(stderr, "HIP engine: value set without an engine or a column\n"); return res; }
+    const int c = hipColumnId(column);
+    if (c < 0) { fprintf(stderr, "HIP engine: value set: unknown column '%s'\n", column); return res; }
+    if (c == HIPCOL_COMMAND_ID || c == HIPCOL_SUDO_USED) {
+        fprintf(stderr, "HIP engine: value set: %s takes no value set (sudo_used never needs one, command_id is a follow-up: the list form)\n", column);
+        return res;
+    }
+    struct set_plan p;
+    memset(&p, 0, sizeof p);
+    p.vc = -1;
+    if (having) {
+        int v = -1;
+        if (having->aggregate < HIPTOP_BY_COUNT || having->aggregate > HIPTOP_BY_MAX) {
+            fprintf(stderr, "HIP engine: value set: HAVING aggregate %d is none of HIPTOP_BY_COUNT .. HIPTOP_BY_MAX\n", having->aggregate);
+            return res;
+        }
+        if (having->aggregate != HIPTOP_BY_COUNT) {
+            if (!having->valueColumn) { fprintf(stderr, "HIP engine: value set: HAVING SUM / MIN / MAX needs a value column\n"); return res; }
+            if ((v = value_column_id("value set", having->valueColumn)) < 0) return res;
+        }
+        if (hipCompileHaving(having->aggregate, v >= 0 ? k_group_kind[v] : -1, having->op, having->constant, &p.hv) != 0) return res;
+        p.having = true;
+        p.vc = v;
+    }
+    struct hipTable *t = engine->record_block;
+    if (t->xch) { fprintf(stderr, "HIP engine: value sets are not made on an engine joined across ranks\n"); return res; }
+    if (value_sets_full(t)) { fprintf(stderr, "HIP engine: value set: %d sets are alive already (free one first)\n", HIP_MAX_VALUE_SETS); return res; }
+    struct query q;
+    if (!query_open(engine, &q)) return res;                             /* reason on stderr */
+    struct group_plan gp;
+    struct value_set vs;
+    memset(&vs, 0, sizeof vs);
+    /* scan semantics: the WHERE is bound without index probes, every inner row counts once */
+    int rc = bind_where(t, whereClause, &q.plan);
+    q.have_plan = rc == 0;
+    rc = group_plan_column_span(&q, rc, c, column, "value set", true, &gp);
+    if (rc == 0 && !gp.empty) {
+        if (gp.single) {
+            /* a single-valued string column has no buffer to group by: one bin over every inner row, `COUNT(*) != 0` without a HAVING */
+            if (!p.having) p.hv = (struct hipHaving){ PQPS_HAVING_COUNT, PQPS_HAVING_NE, 0, 0 };
+            p.having = true;
+            if (p.vc < 0) p.vc = HIPCOL_COMMAND_ID;
+        }
+        p.wide = gp.span > HIP_GROUP_MAX_BINS;
+        if (!p.having && gp.span > PQPS_MEMBER_MAX_BITS) {
+            fprintf(stderr, "HIP engine: value set: %s spans %llu values, more than the %llu a set's bitmap takes\n", column,
+                    (unsigned long long)gp.span, (unsigned long long)PQPS_MEMBER_MAX_BITS);
+            rc = -1;
+        } else if (p.having && p.wide && !top_bins_fit(gp.span, p.vc >= 0)) {
+            fprintf(stderr, "HIP engine: value set: the %llu bins of %s (%d bytes each) do not fit the budget of %llu bytes\n",
+                    (unsigned long long)gp.span, column, p.vc >= 0 ? 32 : 4, (unsigned long long)HIP_TOP_BINS_BUDGET);
+            rc = -1;
+        }
+    }
+    vs.column = c;
+    vs.kind = k_group_kind[c];
+    if (rc == 0 && !gp.empty) {
+        p.gp = &gp;
+        p.words = ((size_t)gp.n_bins + 31) / 32;
+        vs.base = gp.bin_base;
+        vs.lo = gp.lo;
+        vs.n_bits = gp.n_bins;
+        rc = set_build(&q, &p, &vs);
+    }
+    if (rc == 0 && value_set_register(t, &vs) != 0) {
+        pthread_mutex_lock(&g_sets_lock);
+        value_set_release(t, &vs);
+        pthread_mutex_unlock(&g_sets_lock);
+        rc = -1;
+    }
+    query_close(&q);
+    if (rc == 0) {
+        res->success = true;
+        res->id = vs.id;
+        res->column = c;
+        res->kind = vs.kind;
+        res->members = vs.members;
+        res->rows = vs.rows;
+    }
+    res->queryTime = now_seconds() - t0;
+    return res;
+}
+
+struct hipSetKeys *hipEngineSetKeysHIP(struct engineS *engine, const struct hipValueSet *set) {
+    struct hipSetKeys *res = calloc(1, sizeof *res);
+    if (!res) { oom(); return NULL; }
+    res->column = res->kind = -1;
+    if (!engine || !engine->record_block || !set || !set->success) { fprintf(stderr, "HIP engine: set keys without an engine or a set\n"); return res; }
+    struct hipTable *t = engine->record_block;
+    struct query q;
+    if (!query_open(engine, &q)) return res;                             /* reason on stderr */
+    struct value_set vs;
+    pthread_mutex_lock(&g_sets_lock);
+    const struct value_set *found = value_set_find(t, set->id);
+    if (found) vs = *found;
+    pthread_mutex_unlock(&g_sets_lock);
+    int rc = 0;
+    if (!found || vs.stale) {
+        fprintf(stderr, "HIP engine: set keys: value set %u %s\n", set->id, found ? "is stale: the table was written after it was made" : "does not exist (freed)");
+        rc = -1;
+    }
+    const size_t words = rc == 0 && vs.members ? (size_t)((vs.n_bits + 31) / 32) : 0;
+    uint32_t *bits = NULL;
+    if (rc == 0 && vs.members > INT_MAX) { fprintf(stderr, "HIP engine: set keys: more than %d keys\n", INT_MAX); rc = -1; }
+    if (rc == 0 && words && !(bits = malloc(words * sizeof *bits))) rc = oom();
+    if (rc == 0 && words && pqps_download(lane_copy_ctx(&q, 0), bits, vs.bitmap[0], words * sizeof *bits, NULL) != PQPS_OK) rc = engine_error("set keys download");
+    if (rc == 0) {
+        res->column = vs.column;
+        res->kind = vs.kind;
+        res->keys = calloc((size_t)vs.members + 1, sizeof *res->keys);
+        res->keyText = calloc((size_t)vs.members + 1, sizeof *res->keyText);
+        if (!res->keys || !res->keyText) rc = oom();
+    }
+    for (uint64_t k = 0; rc == 0 && words && k < vs.n_bits; k++) {
+        if (!((bits[k >> 5] >> (k & 31)) & 1u)) continue;
+        char buf[32];
+        if ((uint64_t)res->numKeys >= vs.members) { fprintf(stderr, "HIP engine: set keys: the bitmap holds more than its %llu members\n", (unsigned long long)vs.members); rc = -1; break; }
+        if (!(res->keyText[res->numKeys] = strdup(group_key(t, vs.column, vs.kind, (uint32_t)k, vs.lo, &res->keys[res->numKeys], buf, sizeof buf)))) rc = oom();
+        else res->numKeys++;
+    }
+    free(bits);
+    query_close(&q);
+    res->success = rc == 0;
+    return res;
+}
+
+void freeSetKeysHIP(struct hipSetKeys *keys) {
+    if (!keys) return;
+    free_group_keys(keys->keys, keys->keyText, keys->numKeys);
+    free(keys);
+}
+
+int hipEngineFreeSetHIP(struct engineS *engine, struct hipValueSet *set) {
+    if (!set) return 0;
+    if (set->success && set->id && engine && engine->record_block) {
+        struct hipTable *t = engine->record_block;
+        if (hipTableLockExclusive(t) != 0) return -1;                    /* a thread that holds a ticket: refused, nothing freed */
+        pthread_mutex_lock(&g_sets_lock);
+        struct value_set *vs = value_set_find(t, set->id);
+        if (vs) { value_set_release(t, vs); memset(vs, 0, sizeof *vs); }
+        pthread_mutex_unlock(&g_sets_lock);
+        hipTableUnlockExclusive(t);
+    }
+    free(set);
+    return 0;
+}
+
 /* ---- projection ------------------------------------------------------------------ */
 
 /* get_attribute_string_value, S:216-248, with the column resolved once per query
@@ -3211,6 +3638,7 @@ struct engineS *initializeEngineSyntheticHIP(unsigned long long num_rows, unsign
 void destroyEngineHIP(struct engineS *engine) {
     if (!engine) { fprintf(stderr, "Attempted to destroy a NULL engine pointer\n"); return; }
     const double t_destroy = now_seconds();
+    value_sets_destroy(engine->record_block);                      /* the sets nobody freed, while their contexts live */
     destroyDeviceTableHIP(engine);                                 /* frees the row block too */
     TRACE("destroy: device table + context %.3f ms\n", (now_seconds() - t_destroy) * 1e3);
     free(engine->bplus_tree_roots);
@@ -3434,6 +3862,7 @@ bool executeQueryInsertHIP(struct engineS *engine, const char *tableName, const 
             fprintf(stderr, "HIP engine: INSERT needs a table rebuild (head-room used up or a dictionary outgrowing its code width), which an engine without host rows cannot do\n");
         }
         TRACE("INSERT (device only): %.3f ms\n", (now_seconds() - t0) * 1e3);
+        if (ok) value_sets_invalidate(t);
         hipTableUnlockExclusive(t);
         return ok;
     }
@@ -3445,6 +3874,7 @@ bool executeQueryInsertHIP(struct engineS *engine, const char *tableName, const 
     const double t1 = now_seconds();
     appendRowDeviceTableHIP(engine, engine->all_records[n]);
     TRACE("INSERT: CSV append + host row %.3f ms, device append + indexes %.3f ms\n", (t1 - t0) * 1e3, (now_seconds() - t1) * 1e3);
+    value_sets_invalidate(t);
     hipTableUnlockExclusive(t);
     return true;
 }
@@ -3465,7 +3895,7 @@ static int row_flags(struct query *q, size_t n, uint8_t **flags_dev, uint8_t *fl
         struct shard_pred *sp = &q->sp[s];
         memset(sp, 0, sizeof *sp);
         const struct hipPass *last = &head.pass[head.n_passes - 1];
-        rc = head_passes(&head, sh, sp, sh->ctx, NULL, sh->own.count_dev + 4, true);
+        rc = head_passes(&head, t, s, sp, sh->ctx, NULL, sh->own.count_dev + 4, true);
         if (rc != 0) break;
         sp->pred = &last->pred;
         sp->n_cols = last->pred.n_columns;
@@ -3540,6 +3970,7 @@ struct resultSetS *executeQueryDeleteHIP(struct engineS *engine, const char *tab
     writer_flags_free(&wf, t);
     TRACE("DELETE: %zu of %zu rows, flags %.3f ms, host rows %.3f ms, CSV rewrite %.3f ms, device compaction + indexes %.3f ms\n",
           deleted, n, (t1 - t0) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3, (now_seconds() - t3) * 1e3);
+    value_sets_invalidate(t);
     hipTableUnlockExclusive(t);
     rs->numRecords = (int)deleted;
     rs->queryTime = now_seconds() - t0;
@@ -3632,6 +4063,7 @@ static long long update_locked(struct engineS *engine, struct hipTable *t, const
     const int n_shards = hipTableShards(t);
     /* 2. new strings into their dictionaries, before the WHERE is bound: its constants are codes */
     const uint32_t bumped = rebuild ? 0u : updateInsertStringsHIP(engine, a, numSet);
+    if (bumped) value_sets_invalidate(t);                            /* codes moved: the sets are stale whatever becomes of the rows */
     const double t1 = now_seconds();
 
     /* 3. the rows */
@@ -3692,6 +4124,7 @@ long long executeQueryUpdateHIP(struct engineS *engine, const char *tableName, c
     struct hipTable *t = engine->record_block;
     if (hipTableLockExclusive(t) != 0) return -1;
     const long long k = update_locked(engine, t, setColumns, setValues, numSet, whereClause);
+    if (k >= 0) value_sets_invalidate(t);
     hipTableUnlockExclusive(t);
     if (queryTime) *queryTime = now_seconds() - t0;
     return k;
@@ -3734,6 +4167,7 @@ long long executeQueryInsertColumnsHIP(struct engineS *engine, const char *table
             TRACE("INSERT of %llu rows: merge + staging %.3f ms, remap + append + indexes %.3f ms\n", num_rows, (t1 - t0) * 1e3, (now_seconds() - t1) * 1e3);
         }
     }
+    if (k >= 0) value_sets_invalidate(t);
     hipTableUnlockExclusive(t);
     if (queryTime) *queryTime = now_seconds() - t0;
     return k;
@@ -3766,6 +4200,7 @@ long long executeQueryInsertRowsHIP(struct engineS *engine, const char *tableNam
         commitAppendHIP(engine, b);
         k = (long long)num_rows;
     }
+    if (k >= 0) value_sets_invalidate(t);
     hipTableUnlockExclusive(t);
     if (queryTime) *queryTime = now_seconds() - t0;
     return k;

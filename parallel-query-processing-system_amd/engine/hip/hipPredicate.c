@@ -9,6 +9,7 @@
 #include "hipPredicate.h"
 #include "logType.h"
 
+#include <errno.h>
 #include <limits.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -156,13 +157,15 @@ static int node_leaves(const struct whereClauseS *c) {
  * planned: resolve_sets leaves one entry per node in a side table, the sorted runs of codes / values the node selects.
  * A set of few runs becomes that many ordinary window leaves, anything more fragmented a member pass of the plan whose
  * flags the node reads as the leaf `flags = 1` (include/hipPredicate.h). */
-enum { SET_LIKE = 0, SET_NOT_LIKE = 1, SET_IN = 2, SET_NOT_IN = 3 };
+enum { SET_LIKE = 0, SET_NOT_LIKE = 1, SET_IN = 2, SET_NOT_IN = 3, SET_IN_SET = 4, SET_NOT_IN_SET = 5 };
 static int set_op_code(const char *op) {
     if (!op) return -1;
     if (strcmp(op, "LIKE") == 0) return SET_LIKE;
     if (strcmp(op, "NOT LIKE") == 0) return SET_NOT_LIKE;
     if (strcmp(op, "IN") == 0) return SET_IN;
     if (strcmp(op, "NOT IN") == 0) return SET_NOT_IN;
+    if (strcmp(op, "IN SET") == 0) return SET_IN_SET;
+    if (strcmp(op, "NOT IN SET") == 0) return SET_NOT_IN_SET;
     return -1;
 }
 
@@ -182,9 +185,13 @@ struct set_node {
     uint32_t *bitmap;
     uint64_t *list;
     uint32_t n_list;
+    uint32_t set_id;                             /* a value set (IN SET): its id; the bitmap is the set's own, on the device */
 };
 struct set_table { struct set_node *node; int n, cap; };
 static _Thread_local const struct set_table *sets;   /* the table of the compile running on this thread */
+/* ... and the value sets it may name (hipCompileWherePlanSets) */
+static _Thread_local const struct hipSetInfo *value_sets;
+static _Thread_local int n_value_sets;
 
 static const struct set_node *find_set(const struct whereClauseS *c) {
     if (!sets || c->sub) return NULL;
@@ -392,9 +399,38 @@ static int set_from_runs(struct set_node *sn, const struct runs *S, uint64_t dma
     return 0;
 }
 
+/* IN SET / NOT IN SET: the node's value names a value set of the table (include/hipPredicate.h). */
+static int resolve_value_set(const struct whereClauseS *c, int not_form, int col, int kind, struct set_node *sn, char *err, size_t errlen) {
+    char *end = NULL;
+    const unsigned long long id = c->value[0] >= '0' && c->value[0] <= '9' ? strtoull(c->value, &end, 10) : 0;
+    if (!end || *end || id == 0 || id > 0xFFFFFFFFull) return set_fail(err, errlen, c->attribute, "IN SET needs the decimal id of a value set");
+    const struct hipSetInfo *si = NULL;
+    for (int i = 0; i < n_value_sets && !si; i++) if (value_sets[i].id == (uint32_t)id) si = &value_sets[i];
+    if (!si) return set_fail(err, errlen, c->attribute, "IN SET names a value set that does not exist (never made, or freed)");
+    if (si->stale) return set_fail(err, errlen, c->attribute, "IN SET names a stale value set: the table was written after the set was made");
+    if (kind == HIPKIND_U64 || kind == HIPKIND_BOOL) return set_fail(err, errlen, c->attribute, "command_id and sudo_used take no value set");
+    if (kind != si->kind || (kind == HIPKIND_DICT && col != si->column))
+        return set_fail(err, errlen, c->attribute, "the value set is over another column: a string column takes only its own sets, an i32 column those of i32 columns");
+    if (si->members == 0) { sn->mode = not_form ? SM_TRUE : SM_FALSE; return 0; }
+    if (kind == HIPKIND_DICT && si->members == si->n_bits) { sn->mode = not_form ? SM_FALSE : SM_TRUE; return 0; }
+    sn->mode = SM_MEMBER;
+    sn->negate = not_form;
+    sn->form = PQPS_MEMBER_BITMAP;
+    sn->base = si->base;
+    sn->n_bits = si->n_bits;
+    sn->set_id = si->id;
+    return 0;
+}
+
 static int resolve_one(const struct hipSchema *schema, const struct whereClauseS *c, int op, int col, struct set_node *sn,
                        char *err, size_t errlen) {
     const struct hipColumnInfo *ci = &schema->col[col];
+    if (op == SET_IN_SET || op == SET_NOT_IN_SET) {
+        const int k = col == 0 ? HIPKIND_U64 : (col == 4 || col == 8 || col == 11) ? HIPKIND_I32 : col == 6 ? HIPKIND_BOOL : HIPKIND_DICT;
+        if (resolve_value_set(c, op == SET_NOT_IN_SET, col, k, sn, err, errlen) != 0) return -1;
+        if (sn->mode == SM_MEMBER && !ci->present) sn->mode = SM_ABSENT;         /* no column for a pass to read */
+        return 0;
+    }
     const int not_form = op == SET_NOT_LIKE || op == SET_NOT_IN;
     const int is_like = op == SET_LIKE || op == SET_NOT_LIKE;
     /* typed by the column, as the literal of `=` is (make_leaf) */
@@ -808,6 +844,7 @@ static int emit_member(struct planner *P, struct set_node *sn) {
     pass->member_bitmap = sn->bitmap; sn->bitmap = NULL;
     pass->member_list = sn->list; sn->list = NULL;
     pass->member_count = sn->n_list;
+    pass->member_set = sn->set_id;
     sn->pass = P->plan->n_passes;
     return P->plan->n_passes++;
 }
@@ -876,6 +913,11 @@ static struct whereClauseS *fit_chain(struct planner *P, const struct whereClaus
 
 int hipCompileWherePlan(const struct hipSchema *schema, const struct whereClauseS *where,
                         struct hipPlan *plan, char *err, size_t errlen) {
+    return hipCompileWherePlanSets(schema, where, NULL, 0, plan, err, errlen);
+}
+
+int hipCompileWherePlanSets(const struct hipSchema *schema, const struct whereClauseS *where, const struct hipSetInfo *value_set_table,
+                            int n_sets, struct hipPlan *plan, char *err, size_t errlen) {
     memset(plan, 0, sizeof *plan);
     struct planner P;
     memset(&P, 0, sizeof P);
@@ -884,7 +926,11 @@ int hipCompileWherePlan(const struct hipSchema *schema, const struct whereClause
     /* set nodes first: what each selects, and a member pass for every set too fragmented for window leaves */
     struct set_table T;
     memset(&T, 0, sizeof T);
+    value_sets = value_set_table;
+    n_value_sets = value_set_table && n_sets > 0 ? n_sets : 0;
     int last = resolve_sets(schema, where, &T, err, errlen);
+    value_sets = NULL;
+    n_value_sets = 0;
     sets = &T;
     flag_passes = 0;
     for (int i = 0; last == 0 && i < T.n; i++)
@@ -914,6 +960,43 @@ void hipPlanFree(struct hipPlan *plan) {
     free(plan->pass);
     plan->pass = NULL;
     plan->n_passes = 0;
+}
+
+/* ---- the HAVING of a value set ------------------------------------------------------------------------------------- */
+
+static int having_fail(const char *what, const char *text) {
+    fprintf(stderr, "HIP engine: HAVING: %s%s%s%s\n", what, text ? " '" : "", text ? text : "", text ? "'" : "");
+    return -1;
+}
+
+int hipCompileHaving(int aggregate, int value_kind, const char *op, const char *constant, struct hipHaving *out) {
+    static const char *const k_ops[6] = { "=", "!=", "<", ">", "<=", ">=" };    /* PQPS_HAVING_EQ .. _GE */
+    if (!op || !constant || !out) return having_fail("NULL argument", NULL);
+    if (aggregate < HIPTOP_BY_COUNT || aggregate > HIPTOP_BY_MAX) return having_fail("the aggregate is none of COUNT, SUM, MIN, MAX", NULL);
+    const int counted = aggregate == HIPTOP_BY_COUNT;
+    if (!counted && value_kind != HIPKIND_I32 && value_kind != HIPKIND_U64) return having_fail("SUM / MIN / MAX need a numeric value column", NULL);
+    struct hipHaving h;
+    memset(&h, 0, sizeof h);
+    h.field = aggregate - HIPTOP_BY_COUNT;
+    h.op = -1;
+    for (int i = 0; i < 6; i++) if (strcmp(op, k_ops[i]) == 0) h.op = i;
+    if (h.op < 0) return having_fail("unknown operator", op);
+    const char *p = constant;
+    while (is_blank(*p)) p++;
+    const int is_signed = !counted && value_kind == HIPKIND_I32;
+    const char *digits = p + (*p == '+' || *p == '-');
+    if (*digits < '0' || *digits > '9') return having_fail("the constant is no decimal number", constant);
+    if (*p == '-' && !is_signed) return having_fail("a negative constant for an unsigned aggregate", constant);
+    char *end = NULL;
+    errno = 0;
+    if (is_signed) h.constant = (uint64_t)strtoll(p, &end, 10);
+    else h.constant = strtoull(p, &end, 10);
+    if (errno == ERANGE) return having_fail("the constant is out of range", constant);
+    if (!end || *end) return having_fail("trailing garbage behind the constant", constant);
+    if (is_signed && aggregate >= HIPTOP_BY_MIN) h.constant ^= 0x8000000000000000ull;      /* the image of pqps_filter_aggregate */
+    h.value_signed = is_signed && aggregate == HIPTOP_BY_SUM;
+    *out = h;
+    return 0;
 }
 
 /* ---- the SET list of an UPDATE ------------------------------------------------------------------------------------ */
