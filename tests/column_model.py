@@ -16,12 +16,18 @@ chain_true of tests/test_gpu_set_predicates.py.  select_ids with indexes is the 
 orc_index_build): rows in probe order, once per probe.  Every other form is folded from the model's cells over those rows by
 the reference folds the suite already has; group_first is group_first_model.first_rows and order_ids_by Python's stable
 `sorted` once per key, both over the order-preserving codes (tests/test_gpu_many_shards.py checks the two row by row).  tests/test_column_model.py checks all of it on the CPU against the golden ID lists
-and the folds taken over OracleTable(csv)."""
+and the folds taken over OracleTable(csv).
+
+The two newest forms, for tests/concurrent_sets.py: group_top is group_top_model's fold and order, value_set the same fold with
+the HAVING compared in Python ints; a chain that names value sets becomes the IN-list chain over the model's members
+(resolve_sets) and is evaluated leaf by leaf with numpy (member_mask).  tests/test_gpu_concurrent_sets.py holds them against the
+plain-dict members_of, group_top_matrix's expectation and chain_true."""
 import ctypes as C
 
 import numpy as np
 
 import group_first_model as gfm
+import group_top_model as gtm
 import qpelib as q
 import test_gpu_count_distinct as cd
 import test_gpu_group_buckets as gb
@@ -36,6 +42,9 @@ NUMERIC = [c for c in pq.COLUMNS if pq.COLUMN_KIND[pq.COL[c]] != pq.KIND_DICT]
 M64 = (1 << 64) - 1
 GROUP_MAX_BINS = 65536                                           # HIP_GROUP_MAX_BINS: a group column of more values is refused
 SET_OPERATORS = ("LIKE", "NOT LIKE", "IN", "NOT IN")
+VALUE_SET_OPERATORS = ("IN SET", "NOT IN SET")
+HAVING_OPS = {"=": lambda a, b: a == b, "!=": lambda a, b: a != b, "<": lambda a, b: a < b, ">": lambda a, b: a > b,
+              "<=": lambda a, b: a <= b, ">=": lambda a, b: a >= b}
 
 
 # ---- the model operations of the writers ------------------------------------------------------------------------------------
@@ -170,6 +179,34 @@ def register_in_lists(chain):
     for leaf in leaves_of(chain):
         if leaf[1] in ("IN", "NOT IN") and leaf[2] not in sp._ITEMS:
             sp._ITEMS[leaf[2]] = parse_in_list(leaf[2])
+
+
+class MemberLeaf(tuple):
+    """The IN / NOT IN leaf a value-set leaf stands for (resolve_sets): an ordinary leaf for chain_true, with the members
+    kept beside the text so that ColumnModel.member_mask need not parse them back."""
+    members = ()
+
+
+def resolve_sets(chain, sets):
+    """The chain with every IN SET / NOT IN SET leaf replaced by the IN / NOT IN leaf over the MODEL's members of the set the
+    leaf names (sets: the leaf's value text -> key texts, ColumnModel.value_set's)."""
+    if chain is None:
+        return None
+    out = []
+    for k, item in enumerate(chain):
+        if k % 2 == 1 or (not isinstance(item, list) and item[1] not in VALUE_SET_OPERATORS):
+            out.append(item)
+        elif isinstance(item, list):
+            out.append(resolve_sets(item, sets))
+        else:
+            leaf = MemberLeaf(sp.IN(item[0], list(sets[item[2]]), item[1].startswith("NOT")))
+            leaf.members = tuple(sets[item[2]])
+            out.append(leaf)
+    return out
+
+
+def has_member_leaf(chain):
+    return any(isinstance(leaf, MemberLeaf) for leaf in leaves_of(chain))
 
 
 def without_set_leaves(chain):
@@ -400,10 +437,34 @@ class ColumnModel:
         truth = np.array([bool(sp.chain_true(recs[int(r)], chain)) for r in first])
         return truth[np.asarray(inverse).reshape(-1)]
 
+    def member_mask(self, chain):
+        """A chain that resolve_sets made: evaluateWhereClause's right-recursive fold, no precedence, over one mask per leaf
+        -- a MemberLeaf by numpy.isin over the column (a set of 60 000 members is no matter for it), any other leaf by mask()
+        of the leaf alone.  tests/test_gpu_concurrent_sets.py holds it against python_mask row by row."""
+        acc = None
+        items, ops = chain[0::2], chain[1::2]
+        for k in range(len(items) - 1, -1, -1):
+            it = items[k]
+            if isinstance(it, list):
+                m = self.member_mask(it)
+            elif isinstance(it, MemberLeaf):
+                if it[0] in STRINGS:
+                    words = {t.encode("latin-1") for t in it.members}
+                    m = np.array([w in words for w in self.m[it[0]][1]], dtype=bool)[self.codes(it[0])]
+                else:
+                    m = np.isin(self.m[it[0]].astype(np.int64), np.array([int(t) for t in it.members], dtype=np.int64))
+                m = m != (it[1] == "NOT IN")
+            else:
+                m = self.mask([it])
+            acc = m if acc is None else (m | acc) if ops[k] == "OR" else (m & acc)
+        return acc
+
     def mask(self, chain):
         """The rows for which the WHERE is true (scan semantics)."""
         if not chain:
             return np.ones(self.n, dtype=bool)
+        if has_member_leaf(chain):
+            return self.member_mask(chain) if self.n else np.zeros(0, dtype=bool)
         if has_set_leaf(chain):
             return self.python_mask(chain)
         out = np.zeros(self.n, dtype=bool)
@@ -415,7 +476,7 @@ class ColumnModel:
         if not chain:
             return np.arange(self.n, dtype=np.int64)
         if has_set_leaf(chain):
-            return np.flatnonzero(self.python_mask(chain))
+            return np.flatnonzero(self.mask(chain))
         wl = q.WhereList(chain)
         out = np.zeros(max(self.n, 1), dtype=np.uint32)
         k = q.load_oracle().orc_scan_columns(C.byref(self.orc_columns()), wl.ptr, 0, out.ctypes.data_as(C.POINTER(C.c_uint32)), self.n, 1)
@@ -429,7 +490,7 @@ class ColumnModel:
         if not has_set_leaf(chain):
             return self.table(indexes).select_ids(chain, probe_bool=probe_bool)[0]
         ids = self.table(indexes).select_ids(without_set_leaves(chain), probe_bool=probe_bool)[0]
-        mask = self.python_mask(chain)
+        mask = self.mask(chain)
         return [r for r in ids if mask[r]]
 
     # ---- the other forms, folded over the rows of select_ids ----
@@ -457,6 +518,24 @@ class ColumnModel:
         cells = self.cells(column)
         keys = [ob.cell_key(column, cells[r]) for r in ids]
         return ob.cut(ob.sort_rows(ids, keys, descending), limit), len(ids)
+
+    def group_top(self, column, value_column, rows, by="count", descending=True, limit=10):
+        """HipEngine.group_top_result without `seconds`: the groups of group_top_model.fold over the listed rows (duplicates
+        counted), the first `limit` (None or <= 0: all) in group_top_model.order's order."""
+        return gtm.top(self, column, value_column, np.asarray(rows, dtype=np.int64), by, descending, limit)
+
+    def value_set(self, column, rows, having=None):
+        """hipEngineCreateSetHIP over the inner rows `rows` (scan semantics: scan_rows(chain), each row once): -> (the members'
+        key texts in key order, len(rows)).  having = (aggregate, value column | None, op, constant) with the header's
+        arithmetic: an i32 sum in int64 compared signed, a command_id sum mod 2^64 compared unsigned, MIN and MAX in value
+        order (group_top_model.fold's dtypes; compared as Python ints).  Only values that some inner row carries are folded,
+        so a value without inner rows is never a member."""
+        f = gtm.fold(self.codes(column), self.m[having[1]] if having and having[1] else None, rows, bool(having) and having[1] == "command_id")
+        keys = f["key"].tolist()
+        if having is not None:
+            agg, _, op, constant = having
+            keys = [k for k, x in zip(keys, f[agg].tolist()) if HAVING_OPS[op](int(x), int(constant))]
+        return [gtm.key_text(self, column, k) for k in keys], len(rows)
 
     def group_pair(self, columns, value_column, ids):
         rows = np.asarray(ids, dtype=np.int64)
