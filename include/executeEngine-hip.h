@@ -587,6 +587,61 @@ struct hipColumnarResult *executeQuerySelectGroupFirstHIP(struct engineS *engine
                                                           struct whereClauseS *whereClause, const char *groupColumn /* may be NULL */,
                                                           const char *orderColumn, bool descending, long long *matches);
 
+/* THE FIRST N ROWS OF EVERY GROUP: per value of `groupColumn`, the n matching rows that come first in the order of
+ * `orderColumn` -- "the n latest commands of every user", "the three riskiest commands per host" (SQL: ROW_NUMBER() OVER
+ * (PARTITION BY g ORDER BY k [DESC]) <= n; no counterpart in the reference, reached through the C API and the Python package
+ * only, as every grouped form is).
+ * ROWS: exactly the rows executeQuerySelectIdsHIP returns, each row at most once.  An index-mode duplicate changes nothing
+ * but `total`.
+ * GROUPS: the groups, keys, key text and key order of executeQueryGroupFirstHIP.  groupColumn == NULL means one group.
+ * ORDER: exactly executeQueryOrderIdsHIP's.  Ties go to the lowest row number in both directions.  Every one of the 12
+ * columns is a legal order column, command_id included.  Single-valued columns are legal.  The order column may equal the
+ * group column.
+ * ANSWER: for each group that has a matching row, its first min(n, rows of the group) rows in that order.  Groups come in
+ * key order, and rows in order inside each group: group g's rows are entries offsets[g] .. offsets[g + 1] of rows /
+ * orderKeys / orderText.
+ * CONSEQUENCE: the rows of group g are executeQueryOrderIdsHIP(orderColumn, whereClause AND groupColumn = keyText[g],
+ * descending, limit n) with repeated ids removed.  With n = 1 the answer is executeQueryGroupFirstHIP's.
+ * N: any n >= 1 is legal.  Nothing is refused for the size of n or of the order column's domain.
+ * REFUSED (success = false, the reason on stderr): n < 1, unknown columns, and every group-column refusal of
+ * executeQueryGroupFirstHIP: command_id as the group column, more than 65 536 bins, an engine joined across ranks.
+ * CONCURRENCY: a reader like COUNT: shared lock, one lane, and its device buffers live and die with the query.
+ * An empty table, or a WHERE that matches nothing, gives numGroups = 0 with success = true.
+ * Execution: routed as executeQueryGroupFirstHIP.  n up to the round cap (PQPS_HEAD_ROUNDS_MAX of pqps_hip.h; the
+ * environment variable PQPS_HEAD_ROUNDS, read per query, lowers it -- 0: never -- for the bench): the ROUNDS form, a
+ * single-pass scan-mode WHERE by pqps_filter_group_head (n scans issued back to back, no host wait between them), everything
+ * else by the selection and pqps_group_head_list.  Above the cap both routes take the selection and the SORT form
+ * (pqps_group_head_sort: one sort by (group, key, row), repeated ids out, the first n of every run kept by one flag pass
+ * and a compaction).  Either way a shard hands at most n entries per bin, and hipHeadMerge (hipPredicate.h) keeps the n
+ * smallest per bin of the shards' union. */
+struct hipGroupHeadResult {
+    int groupColumn, groupKind;        /* as hipGroupFirstResult                                            */
+    int orderColumn, orderKind;
+    bool descending;
+    int limit;                         /* n                                                                 */
+    int numGroups;
+    long long total;                   /* executeQuerySelectIdsHIP's count                                  */
+    long long *keys;                   /* as hipGroupFirstResult; NULL without GROUP BY                     */
+    char **keyText;
+    long long *offsets;                /* numGroups + 1 entries: group g's rows are offsets[g] .. offsets[g + 1] */
+    unsigned int *rows;                /* offsets[numGroups] entries each, group by group, in order:         */
+    long long *orderKeys;              /*   as hipGroupFirstResult's                                         */
+    char **orderText;
+    double queryTime;
+    bool success;
+};
+struct hipGroupHeadResult *executeQueryGroupHeadHIP(struct engineS *engine, const char *groupColumn /* may be NULL */,
+                                                    const char *orderColumn, bool descending, long long n,
+                                                    struct whereClauseS *whereClause);
+void freeGroupHeadResultHIP(struct hipGroupHeadResult *result);
+/* The same rows, projected in answer order (cells exactly as executeQuerySelectColumnarHIP makes them).  *matches (may be
+ * NULL) = executeQuerySelectIdsHIP's count; *offsets (may be NULL) = a malloc'd array of numGroups + 1 entries, as above
+ * (the caller frees it; NULL after a refusal). */
+struct hipColumnarResult *executeQuerySelectGroupHeadHIP(struct engineS *engine, const char **selectItems, int numSelectItems,
+                                                         struct whereClauseS *whereClause, const char *groupColumn /* may be NULL */,
+                                                         const char *orderColumn, bool descending, long long n, long long *matches,
+                                                         long long **offsets);
+
 /* THE TOP N GROUPS: GROUP BY one column of ANY size, ORDER BY an aggregate [DESC], LIMIT n -- "the 20 most frequent commands",
  * "the 10 users with the highest summed risk" (no aggregates in the reference; reached through the C API and the Python
  * package only, like the grouped COUNT above).

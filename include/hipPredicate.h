@@ -212,6 +212,21 @@ int hipBucketBounds(const char *column, const char *const *dict, int dict_count,
  * *key = the i32 value, 0 / 1, or the dictionary code, and *row = the table-wide row number (either may be NULL). */
 int hipFirstKeyDecode(int kind, int descending, unsigned long long word, long long *key, unsigned int *row);
 
+/* THE SHARD MERGE OF "THE FIRST N ROWS OF EVERY GROUP" (executeQueryGroupHeadHIP).  Every shard hands its candidates -- at
+ * most `limit` per bin -- as ONE list of n entries in ascending (bin, word) order: words[i] is the word of
+ * pqps_filter_group_head for a narrow order column, (img ^ x) << 32 | row; for command_id best[i] = v ^ x and words[i] = the
+ * row, in ascending (bin, best, word) order, and `best` is NULL otherwise.  Both forms of the query (the rounds and the sort)
+ * hand this shape.  Rows are table-wide, so the words of different shards compare directly: per bin the merge keeps the
+ * `limit` smallest entries of the union, command_id comparing (best, row); an entry equal in everything (the same row) on
+ * two shards cannot happen and would be kept twice.  Pure host code, one pass over the lists.
+ *   OUTPUT  out_bins / out_words / out_best (NULL unless the lists carry best) [0 .. return value): the kept entries in
+ *           ascending (bin, [best,] word) order; each has room for the sum of the lists' n.
+ * Returns -1 with the reason on stderr for limit < 1, a NULL list or output that is needed, lists with and without best
+ * mixed, out of memory. */
+struct hipHeadList { uint64_t n; const uint32_t *bins; const uint64_t *words; const uint64_t *best; };
+long long hipHeadMerge(const struct hipHeadList *shards, int n_shards, long long limit, uint32_t *out_bins, uint64_t *out_words,
+                       uint64_t *out_best);
+
 /* THE PACKED KEY OF ORDER BY k1 [DESC], ... , kN [DESC].  Turns a key list into the fields of one unsigned number whose
  * ascending order is the lexicographic order of the keys, each in its own direction; pure host code.
  *   INPUT   columns[0 .. n_keys) / descending[0 .. n_keys): the key list, 1 <= n_keys <= HIP_ORDER_MAX_KEYS;

@@ -654,6 +654,51 @@ int pqps_group_first_list(pqps_ctx *ctx, const pqps_column *key_col, int key_sig
                           uint32_t bin_base, uint32_t n_bins, uint64_t n_rows, const uint32_t *ids, const uint64_t *count_dev,
                           uint64_t capacity, uint32_t id_base, uint64_t *out, uint64_t *best, void *stream);
 
+/* ---- the first N rows of every group: per bin, the N matching rows that come first in the order of a key column --------
+ * No counterpart in the reference (SQL: ROW_NUMBER() OVER (PARTITION BY g ORDER BY k [DESC]) <= n).  BINS, ORDER and WORDS
+ * are those of the first-row calls above.  A row's word is unique, so the r-th row of a bin is the minimum word strictly
+ * above the bin's (r-1)-th word: the calls run `n_rounds` ROUNDS, round 0 the first-row call itself, round r >= 1 the same
+ * scan with one more test per matching row (word > the bin's word of round r-1).
+ * WORDS: out[n_rounds][n_bins] u64 device words, row r being round r: out[r][b] = the word of the bin's (r+1)-th row; all
+ *   ones = the bin has fewer than r + 1 rows (and then every later round reads all ones too).  `best` has the same shape
+ *   for an 8-byte key (command_id), else it is not used and may be NULL: each round of an 8-byte key is the two passes of
+ *   the first-row call, with the floor the pair (best[r-1][b], out[r-1][b]).
+ * n_rounds 1 .. PQPS_HEAD_ROUNDS_MAX.  The calls initialise `out`, `best` and `*count` and are asynchronous on `stream`:
+ * ALL rounds are issued without a host wait, each round reading the previous one's words from device memory.
+ *
+ * pqps_filter_group_head: n_rounds scans of `pred` (twice that for an 8-byte key), columns, padding rule and scratch as
+ *   pqps_filter_group_first.  The floor is one register without GROUP BY; for D <= 4096 bins of a narrow key it lies in
+ *   LDS beside the min table (16 B per bin); otherwise it is read from device memory per matching row (D <= 8192: the min
+ *   table alone in LDS; above: atomics straight into `out`).  *count (device) is written by round 0 only.  Every round is
+ *   recorded by the context's timing recorder like a COUNT (an 8-byte key: two records per round).
+ * pqps_group_head_list: the same words over an ID list, arguments as pqps_group_first_list; an id listed twice is ONE
+ *   candidate in every round (the test is a strict >).
+ *
+ * The SORT form, for an N above the round cap, over a selection sorted by (group, key, row):
+ * pqps_runs_head_flags: keep[i] = (i < limit) || (sorted_keys[i - limit] != sorted_keys[i]) for i < n: in a sorted array an
+ *   entry has rank >= limit inside its run of equal keys exactly when the entry `limit` places before it is in the same
+ *   run.  limit >= 1; n = 0 launches nothing.  Asynchronous.
+ * pqps_group_head_sort: the whole sort form over ids[0 .. n) (table-wide rows, local row = id - id_base): the list sorted
+ *   by (group image, key image [descending], row) (pqps_sort_list_chain; pqps_sort_list where a column is NULL = every
+ *   value 0), ids listed twice removed where `repeats` says the list may hold some (adjacent after the sort), the first
+ *   `limit` entries of every run of equal group images flagged (pqps_runs_head_flags), and the kept entries compacted in
+ *   order by the scan's compaction, as pqps_compact_rows builds DELETE's keep list.  out_ids[0 .. *kept_out) = the rows,
+ *   out_keys[0 .. *kept_out) = their group images and out_keys[n .. n + *kept_out) their key images (pqps_sort_list's
+ *   u64 images; `group_signed` / `key_signed`: i32 columns).  out_ids holds n entries, out_keys 2 n.  Columns 1, 2, 4 bytes
+ *   wide, the key column also 8.  Synchronous. */
+#define PQPS_HEAD_ROUNDS_MAX 16u
+int pqps_filter_group_head(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                           const pqps_column *key_col, int key_signed, int descending, uint32_t row_base,
+                           const pqps_column *group_col, uint32_t bin_base, uint32_t n_bins, uint32_t n_rounds, uint64_t *out,
+                           uint64_t *best, uint64_t *count, void *stream);
+int pqps_group_head_list(pqps_ctx *ctx, const pqps_column *key_col, int key_signed, int descending, const pqps_column *group_col,
+                         uint32_t bin_base, uint32_t n_bins, uint64_t n_rows, const uint32_t *ids, const uint64_t *count_dev,
+                         uint64_t capacity, uint32_t id_base, uint32_t n_rounds, uint64_t *out, uint64_t *best, void *stream);
+int pqps_runs_head_flags(pqps_ctx *ctx, const uint64_t *sorted_keys, uint64_t n, uint64_t limit, uint8_t *keep, void *stream);
+int pqps_group_head_sort(pqps_ctx *ctx, const pqps_column *key_col, int key_signed, int descending, const pqps_column *group_col,
+                         int group_signed, const uint32_t *ids, uint64_t n, uint32_t id_base, uint64_t limit, int repeats,
+                         uint32_t *out_ids, uint64_t *out_keys, uint64_t *kept_out, void *stream);
+
 /* ---- COUNT(DISTINCT value column), overall or per group ---------------------------------------------------------------
  * No counterpart in the reference.  BINS: a value bin is (value - v_base) in 32-bit arithmetic (dictionary codes with
  * v_base 0, an i32 value minus the column's minimum, the bool byte or bit), a group bin (value - g_base) likewise;

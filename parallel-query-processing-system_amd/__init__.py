@@ -198,6 +198,23 @@ class GroupFirstResult(C.Structure):
                 ("queryTime", C.c_double), ("success", C.c_bool)]
 
 
+class GroupHeadResult(C.Structure):
+    """struct hipGroupHeadResult (include/executeEngine-hip.h)."""
+    _fields_ = [("groupColumn", C.c_int), ("groupKind", C.c_int), ("orderColumn", C.c_int), ("orderKind", C.c_int),
+                ("descending", C.c_bool), ("limit", C.c_int), ("numGroups", C.c_int), ("total", C.c_longlong),
+                ("keys", C.POINTER(C.c_longlong)), ("keyText", C.POINTER(C.c_char_p)), ("offsets", C.POINTER(C.c_longlong)),
+                ("rows", C.POINTER(C.c_uint)), ("orderKeys", C.POINTER(C.c_longlong)), ("orderText", C.POINTER(C.c_char_p)),
+                ("queryTime", C.c_double), ("success", C.c_bool)]
+
+
+class HeadList(C.Structure):
+    """struct hipHeadList (include/hipPredicate.h)."""
+    _fields_ = [("n", C.c_uint64), ("bins", C.POINTER(C.c_uint32)), ("words", C.POINTER(C.c_uint64)), ("best", C.POINTER(C.c_uint64))]
+
+
+HEAD_ROUNDS_MAX = 16        # PQPS_HEAD_ROUNDS_MAX (include/pqps_hip.h)
+
+
 class ColumnData(C.Structure):
     """struct hipColumnData (include/executeEngine-hip.h)."""
     _fields_ = [("values", C.c_void_p), ("width", C.c_uint), ("on_device", C.c_int),
@@ -651,7 +668,24 @@ def lib():
     L.executeQueryGroupFirstHIP.argtypes = [E, C.c_char_p, C.c_char_p, C.c_bool, W]
     L.freeGroupFirstResultHIP.argtypes = [C.POINTER(GroupFirstResult)]
     L.freeGroupFirstResultHIP.restype = None
+    L.pqps_filter_group_head.argtypes = [vp, C.POINTER(Column), u32, u64, C.POINTER(Predicate), C.POINTER(Column), C.c_int, C.c_int, u32,
+                                         C.POINTER(Column), u32, u32, u32, vp, vp, vp, vp]
+    L.pqps_group_head_list.argtypes = [vp, C.POINTER(Column), C.c_int, C.c_int, C.POINTER(Column), u32, u32, u64, vp, vp, u64, u32,
+                                       u32, vp, vp, vp]
+    L.pqps_runs_head_flags.argtypes = [vp, vp, u64, u64, vp, vp]
+    L.pqps_group_head_sort.argtypes = [vp, C.POINTER(Column), C.c_int, C.c_int, C.POINTER(Column), C.c_int, vp, u64, u32, u64, C.c_int,
+                                       vp, vp, C.POINTER(u64), vp]
+    L.hipHeadMerge.restype = C.c_longlong
+    L.hipHeadMerge.argtypes = [C.POINTER(HeadList), C.c_int, C.c_longlong, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                               C.POINTER(C.c_uint64)]
+    L.executeQueryGroupHeadHIP.restype = C.POINTER(GroupHeadResult)
+    L.executeQueryGroupHeadHIP.argtypes = [E, C.c_char_p, C.c_char_p, C.c_bool, C.c_longlong, W]
+    L.freeGroupHeadResultHIP.argtypes = [C.POINTER(GroupHeadResult)]
+    L.freeGroupHeadResultHIP.restype = None
     CR = C.POINTER(ColumnarResult)
+    L.executeQuerySelectGroupHeadHIP.restype = CR
+    L.executeQuerySelectGroupHeadHIP.argtypes = [E, C.POINTER(C.c_char_p), C.c_int, W, C.c_char_p, C.c_char_p, C.c_bool, C.c_longlong,
+                                                 C.POINTER(C.c_longlong), C.POINTER(C.POINTER(C.c_longlong))]
     L.executeQuerySelectColumnarHIP.restype = CR
     L.executeQuerySelectColumnarHIP.argtypes = [E, C.POINTER(C.c_char_p), C.c_int, W]
     L.executeQuerySelectOrderedHIP.restype = CR
@@ -855,6 +889,57 @@ def group_first_list(ctx, key_col, key_signed, descending, group_col, bin_base, 
     ref = lambda c: C.byref(c) if c is not None else None
     check(lib().pqps_group_first_list(ctx.h, ref(key_col), int(key_signed), int(descending), ref(group_col), bin_base, n_bins, n_rows,
                                       ids_dev, count_dev, capacity, id_base, out_dev, best_dev, stream), "pqps_group_first_list")
+
+
+def filter_group_head(ctx, cols, n_cols, n_rows, pred, key_col, key_signed, descending, row_base, group_col, bin_base, n_bins,
+                      n_rounds, out_dev, best_dev, count_dev, stream=None):
+    """pqps_filter_group_head: the rounds of the fused filter-and-first-row launch; out_dev holds [n_rounds][n_bins] words."""
+    ref = lambda c: C.byref(c) if c is not None else None
+    check(lib().pqps_filter_group_head(ctx.h, cols, n_cols, n_rows, C.byref(pred) if isinstance(pred, Predicate) else pred,
+                                       ref(key_col), int(key_signed), int(descending), row_base, ref(group_col), bin_base, n_bins,
+                                       n_rounds, out_dev, best_dev, count_dev, stream), "pqps_filter_group_head")
+
+
+def group_head_list(ctx, key_col, key_signed, descending, group_col, bin_base, n_bins, n_rows, ids_dev, count_dev, capacity, id_base,
+                    n_rounds, out_dev, best_dev, stream=None):
+    """pqps_group_head_list: the same words over an ID list."""
+    ref = lambda c: C.byref(c) if c is not None else None
+    check(lib().pqps_group_head_list(ctx.h, ref(key_col), int(key_signed), int(descending), ref(group_col), bin_base, n_bins, n_rows,
+                                     ids_dev, count_dev, capacity, id_base, n_rounds, out_dev, best_dev, stream), "pqps_group_head_list")
+
+
+def runs_head_flags(ctx, sorted_keys_dev, n, limit, keep_dev, stream=None):
+    """pqps_runs_head_flags: keep[i] = i < limit or sorted_keys[i - limit] != sorted_keys[i]."""
+    check(lib().pqps_runs_head_flags(ctx.h, sorted_keys_dev, n, limit, keep_dev, stream), "pqps_runs_head_flags")
+
+
+def group_head_sort(ctx, key_col, key_signed, descending, group_col, group_signed, ids_dev, n, id_base, limit, repeats, out_ids_dev,
+                    out_keys_dev, stream=None):
+    """pqps_group_head_sort: the sort form over an ID list; returns the kept entries' count."""
+    ref = lambda c: C.byref(c) if c is not None else None
+    kept = C.c_uint64()
+    check(lib().pqps_group_head_sort(ctx.h, ref(key_col), int(key_signed), int(descending), ref(group_col), int(group_signed), ids_dev, n,
+                                     id_base, limit, int(repeats), out_ids_dev, out_keys_dev, C.byref(kept), stream), "pqps_group_head_sort")
+    return int(kept.value)
+
+
+def head_merge(shards, limit):
+    """hipHeadMerge: shards = [(bins, words, best_or_None), ...] (sequences in ascending (bin, [best,] word) order); returns
+    (bins, words, best_or_None) of the kept entries, or raises ValueError where the C function refuses."""
+    keep, arr, total, wide = [], (HeadList * max(1, len(shards)))(), 0, False
+    for i, (bins, words, best) in enumerate(shards):
+        n = len(bins)
+        b, w = (C.c_uint32 * max(1, n))(*bins), (C.c_uint64 * max(1, n))(*words)
+        e = (C.c_uint64 * max(1, n))(*best) if best is not None else None
+        keep.append((b, w, e))
+        arr[i] = HeadList(n, b, w, e)
+        total += n
+        wide = wide or (best is not None and n > 0)
+    ob, ow, oe = (C.c_uint32 * max(1, total))(), (C.c_uint64 * max(1, total))(), (C.c_uint64 * max(1, total))()
+    n = lib().hipHeadMerge(arr, len(shards), limit, ob, ow, oe)
+    if n < 0:
+        raise ValueError("hipHeadMerge refused (reason on stderr)")
+    return list(ob[:n]), list(ow[:n]), list(oe[:n]) if wide else None
 
 
 def first_key_decode(kind, descending, word):
@@ -1696,6 +1781,68 @@ class HipEngine:
             raise PqpsError(f"select_group_first({group_column!r}, {order_column!r}) refused or failed (reason on stderr)")
         out = self._columnar_dict(res, text)
         out["matches"] = int(matches.value)
+        return out
+
+    def group_head(self, group_column, order_column, n, chain=None, descending=False):
+        """executeQueryGroupHeadHIP: (groups, total) -- per group of `group_column` (None: one group) among the rows
+        select_ids(chain) returns, (key_text_or_None, [(row, order_text), ...]) of its first min(n, rows) rows in order_ids'
+        order of `order_column` (ties to the lowest row number in both directions), groups in group_count's key order; total =
+        len(select_ids(chain)).  Raises PqpsError when the engine refuses (reason on stderr)."""
+        return self.group_head_result(group_column, order_column, n, chain, descending)[:2]
+
+    def group_head_result(self, group_column, order_column, n, chain=None, descending=False):
+        """group_head plus the raw arrays: (groups, total, dict(keys, offsets, rows, order_keys, seconds, ...))."""
+        wl = WhereList(chain)
+        res = lib().executeQueryGroupHeadHIP(self.e, group_column.encode() if group_column else None,
+                                             order_column.encode() if order_column else None, bool(descending), int(n), wl.ptr)
+        what = f"group_head({group_column!r}, {order_column!r}, {n})"
+        if not res:
+            raise PqpsError(f"{what}: no result")
+        try:
+            r = res.contents
+            if not r.success:
+                raise PqpsError(f"{what} refused or failed (reason on stderr)")
+            ng = r.numGroups
+            grouped = r.groupColumn >= 0
+            offsets = [int(r.offsets[g]) for g in range(ng + 1)]
+            rows = [int(r.rows[i]) for i in range(offsets[ng])]
+            text = [r.orderText[i].decode("latin-1") for i in range(offsets[ng])]
+            groups = [(r.keyText[g].decode("latin-1") if grouped else None,
+                       list(zip(rows[offsets[g]:offsets[g + 1]], text[offsets[g]:offsets[g + 1]]))) for g in range(ng)]
+            fix = (lambda x: x & 0xFFFFFFFFFFFFFFFF) if r.orderKind == HIPKIND_U64 else int
+            raw = dict(keys=[int(r.keys[g]) for g in range(ng)] if grouped else None, offsets=offsets, rows=rows,
+                       order_keys=[fix(r.orderKeys[i]) for i in range(offsets[ng])], limit=int(r.limit),
+                       group_column=r.groupColumn, group_kind=r.groupKind, order_column=r.orderColumn, order_kind=r.orderKind,
+                       descending=bool(r.descending), seconds=float(r.queryTime))
+            return groups, int(r.total), raw
+        finally:
+            lib().freeGroupHeadResultHIP(res)
+
+    def select_group_head(self, columns, chain, group_column, order_column, n, descending=False, text=True):
+        """executeQuerySelectGroupHeadHIP: the dict select_columnar returns, its rows those of group_head(group_column,
+        order_column, n, chain, descending) in answer order, plus `matches` and `offsets` (numGroups + 1 entries).  Raises
+        PqpsError when the engine refuses."""
+        wl = WhereList(chain)
+        items = (C.c_char_p * max(1, len(columns or [])))(*[c.encode() for c in (columns or [])])
+        matches = C.c_longlong()
+        offsets = C.POINTER(C.c_longlong)()
+        res = lib().executeQuerySelectGroupHeadHIP(self.e, items if columns else None, len(columns or []), wl.ptr,
+                                                   group_column.encode() if group_column else None,
+                                                   order_column.encode() if order_column else None, bool(descending), int(n),
+                                                   C.byref(matches), C.byref(offsets))
+        if not res or not res.contents.success:
+            if res:
+                lib().freeColumnarResultHIP(res)
+            if offsets:
+                lib().free(C.cast(offsets, C.c_void_p))
+            raise PqpsError(f"select_group_head({group_column!r}, {order_column!r}, {n}) refused or failed (reason on stderr)")
+        rows, off = int(res.contents.numRecords), [0]
+        while off[-1] < rows:                                  # every group has a row: the offsets ascend strictly to numRecords
+            off.append(int(offsets[len(off)]))
+        lib().free(C.cast(offsets, C.c_void_p))
+        out = self._columnar_dict(res, text)
+        out["matches"] = int(matches.value)
+        out["offsets"] = off
         return out
 
     def free_columnar(self, out):

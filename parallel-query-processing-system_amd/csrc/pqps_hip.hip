@@ -29,6 +29,7 @@
 #include "topk_kernels.hpp"
 #include "order_multi_kernels.hpp"
 #include "first_kernels.hpp"
+#include "head_kernels.hpp"
 #include "distinct_kernels.hpp"
 #include "group_pair_kernels.hpp"
 #include "assign_kernels.hpp"
@@ -3926,6 +3927,225 @@ int pqps_group_first_list(pqps_ctx *ctx, const pqps_column *key_col, int key_sig
         HIP_TRY(hipGetLastError());
     }
     return PQPS_OK;
+}
+
+// ---- the first N rows of every group (head_kernels.hpp) --------------------------------------------------------------
+static int check_head_rounds(uint32_t n_rounds) {
+    return n_rounds >= 1 && n_rounds <= PQPS_HEAD_ROUNDS_MAX ? PQPS_OK : fail(PQPS_EINVAL, "%u rounds: 1 .. %u", n_rounds, PQPS_HEAD_ROUNDS_MAX);
+}
+
+int pqps_filter_group_head(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                           const pqps_column *key_col, int key_signed, int descending, uint32_t row_base,
+                           const pqps_column *group_col, uint32_t bin_base, uint32_t n_bins, uint32_t n_rounds, uint64_t *out,
+                           uint64_t *best, uint64_t *count, void *stream) {
+    int rc = check_head_rounds(n_rounds);
+    if (rc) return rc;
+    // round 0: the first-row launch, unchanged (it checks every argument, zeroes *count and fills row 0)
+    rc = pqps_filter_group_first(ctx, cols, n_cols, n_rows, pred, key_col, key_signed, descending, row_base, group_col, bin_base, n_bins,
+                                 out, best, count, stream);
+    if (rc || n_rounds == 1) return rc;
+    HeadArgs h;
+    memset(&h, 0, sizeof h);
+    FirstArgs &g = h.f;
+    bool wide;
+    rc = check_first_cols(key_col, group_col, n_bins, best, true, &wide, &g.kwidth_log2, &g.gwidth_log2);
+    if (!rc) rc = fused_args(g.e, cols, n_cols, n_rows, pred);
+    if (rc) return rc;
+    hipStream_t s = pick_stream(ctx, stream);
+    const size_t later = (size_t)(n_rounds - 1) * n_bins;
+    HIP_TRY(hipMemsetAsync(out + n_bins, 0xFF, later * sizeof(uint64_t), s));
+    if (wide) HIP_TRY(hipMemsetAsync(best + n_bins, 0xFF, later * sizeof(uint64_t), s));
+    if (n_rows == 0) return PQPS_OK;
+    const int path = !group_col ? HEAD_ONE : n_bins <= kHeadLds2Bins && !wide ? HEAD_LDS2 : n_bins <= kFirstLdsBins ? HEAD_LDS : HEAD_GLOBAL;
+    const uint32_t table_bytes = path == HEAD_LDS2 ? n_bins * 2u * (uint32_t)sizeof(uint64_t) : path == HEAD_LDS ? n_bins * (uint32_t)sizeof(uint64_t) : 0u;
+    const uint32_t grid = fused_grid(ctx, n_rows, table_bytes);
+    if (path != HEAD_GLOBAL) {
+        rc = grow_group_parts(ctx, s, (size_t)grid * n_bins * 2);
+        if (rc) return rc;
+    }
+    g.kcol = key_col ? key_col->data : nullptr;
+    g.gcol = group_col ? group_col->data : nullptr;
+    g.parts = (uint64_t *)ctx->group_parts;
+    g.kxor = topk_xor(wide, key_signed, descending);
+    g.bin_base = bin_base;
+    g.n_bins = n_bins;
+    g.row_base = row_base;
+    typedef void (*head_fn)(const HeadArgs);
+    struct Inst { head_fn fn; const char *name; };
+#define PQPS_HEAD_SCAN(P, M, NT) {head_scan_kernel<P, M, NT>, "head_scan_kernel<" #P ", " #M ", NT=" #NT ">"}
+#define PQPS_HEAD_SCANS(P) {{PQPS_HEAD_SCAN(P, FIRST_NARROW, false), PQPS_HEAD_SCAN(P, FIRST_NARROW, true)},   \
+                            {PQPS_HEAD_SCAN(P, FIRST_WIDE_A, false), PQPS_HEAD_SCAN(P, FIRST_WIDE_A, true)},   \
+                            {PQPS_HEAD_SCAN(P, FIRST_WIDE_B, false), PQPS_HEAD_SCAN(P, FIRST_WIDE_B, true)}}
+    static const Inst fns[4][3][2] = {
+        PQPS_HEAD_SCANS(HEAD_ONE),
+        {{PQPS_HEAD_SCAN(HEAD_LDS2, FIRST_NARROW, false), PQPS_HEAD_SCAN(HEAD_LDS2, FIRST_NARROW, true)}, {{nullptr, ""}, {nullptr, ""}}, {{nullptr, ""}, {nullptr, ""}}},
+        PQPS_HEAD_SCANS(HEAD_LDS), PQPS_HEAD_SCANS(HEAD_GLOBAL),
+#undef PQPS_HEAD_SCANS
+#undef PQPS_HEAD_SCAN
+    };
+    // every round is issued here, back to back on `s`: round r reads round r-1's words from device memory
+    for (uint32_t r = 1; r < n_rounds; r++) {
+        h.floor = out + (size_t)(r - 1) * n_bins;
+        h.floor_best = wide ? best + (size_t)(r - 1) * n_bins : nullptr;
+        for (int mode = wide ? FIRST_WIDE_A : FIRST_NARROW; mode <= (wide ? FIRST_WIDE_B : FIRST_NARROW); mode++) {
+            uint64_t *target = (mode == FIRST_WIDE_A ? best : out) + (size_t)r * n_bins;
+            g.out = target;
+            g.best = mode == FIRST_WIDE_B ? best + (size_t)r * n_bins : nullptr;
+            const Inst &scan = fns[path][mode][g.e.streaming ? 1 : 0];
+            snprintf(g_kernel, sizeof g_kernel, "%s", scan.name);
+            hipEvent_t stop;
+            rc = fused_launch(ctx, scan.fn, grid, table_bytes, s, h, &stop);
+            if (rc) return rc;
+            if (path != HEAD_GLOBAL) {
+                const dim3 sg((n_bins + 63u) / 64u, (grid + kFirstMinParts - 1) / kFirstMinParts);
+                rc = launch_stop(first_min_kernel, sg, 0, s, stop, (const uint64_t *)ctx->group_parts, grid, n_bins, target);
+            }
+            fused_close(ctx, stop, path == HEAD_GLOBAL);
+            if (rc) return rc;
+        }
+    }
+    return PQPS_OK;
+}
+
+int pqps_group_head_list(pqps_ctx *ctx, const pqps_column *key_col, int key_signed, int descending, const pqps_column *group_col,
+                         uint32_t bin_base, uint32_t n_bins, uint64_t n_rows, const uint32_t *ids, const uint64_t *count_dev,
+                         uint64_t capacity, uint32_t id_base, uint32_t n_rounds, uint64_t *out, uint64_t *best, void *stream) {
+    int rc = check_head_rounds(n_rounds);
+    if (rc) return rc;
+    rc = pqps_group_first_list(ctx, key_col, key_signed, descending, group_col, bin_base, n_bins, n_rows, ids, count_dev, capacity, id_base,
+                               out, best, stream);
+    if (rc || n_rounds == 1) return rc;
+    bool wide;
+    uint32_t kwl, gwl;
+    rc = check_first_cols(key_col, group_col, n_bins, best, false, &wide, &kwl, &gwl);
+    if (rc) return rc;
+    hipStream_t s = pick_stream(ctx, stream);
+    const size_t later = (size_t)(n_rounds - 1) * n_bins;
+    HIP_TRY(hipMemsetAsync(out + n_bins, 0xFF, later * sizeof(uint64_t), s));
+    if (wide) HIP_TRY(hipMemsetAsync(best + n_bins, 0xFF, later * sizeof(uint64_t), s));
+    if (capacity == 0 || n_rows == 0) return PQPS_OK;
+    const void *kdata = key_col ? key_col->data : nullptr;
+    const void *gdata = group_col ? group_col->data : nullptr;
+    const uint64_t kxor = topk_xor(wide, key_signed, descending);
+    const int path = first_path(group_col, n_bins);
+    const uint32_t lds = path == FIRST_LDS ? n_bins * (uint32_t)sizeof(uint64_t) : 0u;
+    typedef void (*list_fn)(const void *, uint32_t, uint64_t, const void *, uint32_t, uint64_t, const uint32_t *, const uint64_t *,
+                            uint64_t, uint32_t, uint32_t, uint32_t, const uint64_t *, const uint64_t *, const uint64_t *, uint64_t *);
+    static const list_fn fns[3][3] = {
+        {head_list_kernel<FIRST_ONE, FIRST_NARROW>, head_list_kernel<FIRST_ONE, FIRST_WIDE_A>, head_list_kernel<FIRST_ONE, FIRST_WIDE_B>},
+        {head_list_kernel<FIRST_LDS, FIRST_NARROW>, head_list_kernel<FIRST_LDS, FIRST_WIDE_A>, head_list_kernel<FIRST_LDS, FIRST_WIDE_B>},
+        {head_list_kernel<FIRST_GLOBAL, FIRST_NARROW>, head_list_kernel<FIRST_GLOBAL, FIRST_WIDE_A>, head_list_kernel<FIRST_GLOBAL, FIRST_WIDE_B>},
+    };
+    const dim3 grid(list_grid(ctx, capacity, path == FIRST_LDS ? 2 : 4));
+    for (uint32_t r = 1; r < n_rounds; r++) {
+        const uint64_t *floor = out + (size_t)(r - 1) * n_bins;
+        const uint64_t *floor_best = wide ? best + (size_t)(r - 1) * n_bins : nullptr;
+        uint64_t *rout = out + (size_t)r * n_bins, *rbest = wide ? best + (size_t)r * n_bins : nullptr;
+        for (int mode = wide ? FIRST_WIDE_A : FIRST_NARROW; mode <= (wide ? FIRST_WIDE_B : FIRST_NARROW); mode++) {
+            hipLaunchKernelGGL(fns[path][mode], grid, dim3(kBlock), lds, s, kdata, kwl, kxor, gdata, gwl, n_rows, ids, count_dev, capacity,
+                               id_base, bin_base, n_bins, (const uint64_t *)(mode == FIRST_WIDE_B ? rbest : nullptr), floor, floor_best,
+                               mode == FIRST_WIDE_A ? rbest : rout);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    return PQPS_OK;
+}
+
+int pqps_runs_head_flags(pqps_ctx *ctx, const uint64_t *sorted_keys, uint64_t n, uint64_t limit, uint8_t *keep, void *stream) {
+    if (!ctx || (n && (!sorted_keys || !keep))) return fail(PQPS_EINVAL, "NULL argument");
+    if (limit < 1) return fail(PQPS_EINVAL, "limit 0");
+    if (n == 0) return PQPS_OK;
+    hipLaunchKernelGGL(runs_head_flags, dim3(list_grid(ctx, n, 8)), dim3(kBlock), 0, pick_stream(ctx, stream), sorted_keys, n, limit, keep);
+    HIP_TRY(hipGetLastError());
+    return PQPS_OK;
+}
+
+// The i < n with flags[i] == want compacted into the ascending list keep[0 .. *kept): the ordinary scan over a one-column
+// table, as pqps_compact_rows builds DELETE's keep list.  `flags` is readable up to the next multiple of PQPS_TILE_ROWS.  Waits.
+static int head_keep_list(pqps_ctx *ctx, const uint8_t *flags, uint64_t n, uint32_t want, uint32_t *keep, uint64_t *count_dev, uint64_t *kept,
+                          hipStream_t s) {
+    pqps_column fcol = {flags, 1, 0};
+    pqps_predicate p;
+    memset(&p, 0, sizeof p);
+    p.n_leaves = 1; p.n_columns = 1; p.truth = 0x2;
+    p.leaf[0].column = 0; p.leaf[0].lo = want; p.leaf[0].span = 0;
+    p.on_true[0] = PQPS_ACCEPT; p.on_false[0] = PQPS_REJECT; p.order[0] = 0;
+    int rc = pqps_filter_scan(ctx, &fcol, 1, n, 0, &p, keep, n, count_dev, (void *)s);
+    if (rc) return rc;
+    hipError_t e = hipMemcpyAsync(kept, count_dev, sizeof *kept, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    return e == hipSuccess ? PQPS_OK : fail(PQPS_EHIP, "keep count: %s", hipGetErrorString(e));
+}
+
+// a[0 .. kept) = a[keep[i]] through tmp; entries of 4 or 8 bytes
+static hipError_t head_gather(void *a, uint32_t width, const uint32_t *keep, uint64_t kept, void *tmp, uint32_t grid, hipStream_t s) {
+    if (width == 4) hipLaunchKernelGGL(gather_rows_kernel<uint32_t>, dim3(grid), dim3(256), 0, s, (const uint32_t *)a, keep, kept, (uint32_t *)tmp);
+    else hipLaunchKernelGGL(gather_rows_kernel<uint64_t>, dim3(grid), dim3(256), 0, s, (const uint64_t *)a, keep, kept, (uint64_t *)tmp);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? hipMemcpyAsync(a, tmp, kept * width, hipMemcpyDeviceToDevice, s) : e;
+}
+
+int pqps_group_head_sort(pqps_ctx *ctx, const pqps_column *key_col, int key_signed, int descending, const pqps_column *group_col,
+                         int group_signed, const uint32_t *ids, uint64_t n, uint32_t id_base, uint64_t limit, int repeats,
+                         uint32_t *out_ids, uint64_t *out_keys, uint64_t *kept_out, void *stream) {
+    if (!ctx || !out_ids || !out_keys || !kept_out || (n && !ids)) return fail(PQPS_EINVAL, "NULL argument");
+    if (limit < 1) return fail(PQPS_EINVAL, "limit 0");
+    if (n > 0xFFFFFFFFull) return fail(PQPS_EINVAL, "row IDs are u32");
+    *kept_out = 0;
+    if (n == 0) return PQPS_OK;
+    hipStream_t s = pick_stream(ctx, stream);
+    // 1. the selection in (group, key, row) order; out_keys = [group images][key images], zeros for a column that is not there
+    pqps_column kc[2];
+    int sg[2], ds[2];
+    uint32_t nk = 0;
+    if (group_col) { kc[nk] = *group_col; sg[nk] = group_signed; ds[nk] = 0; nk++; }
+    if (key_col) { kc[nk] = *key_col; sg[nk] = key_signed; ds[nk] = descending; nk++; }
+    int rc;
+    if (nk == 2) rc = pqps_sort_list_chain(ctx, kc, sg, ds, 2, ids, n, id_base, out_ids, out_keys, (void *)s);
+    else {
+        rc = pqps_sort_list(ctx, nk ? &kc[0] : nullptr, nk ? sg[0] : 0, nk ? ds[0] : 0, ids, n, id_base, out_ids,
+                            out_keys + (group_col || !nk ? 0 : n), (void *)s);
+        if (!rc) HIP_TRY(hipMemsetAsync(out_keys + (group_col ? n : 0), 0, (nk ? 1 : 2) * n * sizeof(uint64_t), s));
+    }
+    if (rc) return rc;
+    uint64_t padded = (n + PQPS_TILE_ROWS - 1) / PQPS_TILE_ROWS * PQPS_TILE_ROWS;
+    uint8_t *flags = nullptr;
+    uint32_t *keep = nullptr;
+    uint64_t *count_dev = nullptr;
+    void *tmp = nullptr;
+    hipError_t e = hipMalloc((void **)&flags, padded);
+    if (e == hipSuccess) e = hipMalloc((void **)&keep, n * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&count_dev, 64);
+    if (e == hipSuccess) e = hipMalloc(&tmp, n * 8);
+    if (e != hipSuccess) rc = fail(PQPS_EHIP, "head sort scratch: %s", hipGetErrorString(e));
+    uint64_t m = n;
+    const dim3 fg(list_grid(ctx, n, 8));
+    // 2. repeated ids out (adjacent after the sort), 3. the first `limit` of every run of equal group images, each time
+    // 4. compacted in order and the ids and both image arrays gathered
+    for (int step = repeats ? 0 : 1; step < 2 && !rc && m > 0; step++) {
+        e = hipMemsetAsync(flags, 0, padded, s);
+        if (e == hipSuccess) {
+            if (step == 0) hipLaunchKernelGGL(list_repeat_flags, fg, dim3(kBlock), 0, s, (const uint32_t *)out_ids, m, flags);
+            else hipLaunchKernelGGL(runs_head_flags, fg, dim3(kBlock), 0, s, (const uint64_t *)out_keys, m, limit, flags);
+            e = hipGetLastError();
+        }
+        if (e != hipSuccess) { rc = fail(PQPS_EHIP, "head flags: %s", hipGetErrorString(e)); break; }
+        uint64_t kept = 0;
+        rc = head_keep_list(ctx, flags, m, step == 0 ? 0u : 1u, keep, count_dev, &kept, s);   // step 0 flags what GOES
+        if (rc || kept == m) continue;
+        const uint32_t grid = (uint32_t)((kept + 255) / 256 < (uint64_t)ctx->compute_units * 16 ? (kept + 255) / 256 : (uint64_t)ctx->compute_units * 16);
+        if (kept) {
+            e = head_gather(out_ids, 4, keep, kept, tmp, grid, s);
+            if (e == hipSuccess) e = head_gather(out_keys, 8, keep, kept, tmp, grid, s);
+            if (e == hipSuccess) e = head_gather(out_keys + n, 8, keep, kept, tmp, grid, s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            if (e != hipSuccess) rc = fail(PQPS_EHIP, "head compaction: %s", hipGetErrorString(e));
+        }
+        m = kept;
+    }
+    (void)hipFree(flags); (void)hipFree(keep); (void)hipFree(count_dev); (void)hipFree(tmp);
+    if (!rc) *kept_out = m;
+    return rc;
 }
 
 // ---- COUNT(DISTINCT value column) (distinct_kernels.hpp) -------------------------------------------------------------

@@ -3395,6 +3395,313 @@ struct hipColumnarResult *executeQuerySelectGroupFirstHIP(struct engineS *engine
     return res;
 }
 
+/* ---- the first N rows of every group (include/executeEngine-hip.h) ------------------------------------------------- */
+
+/* One shard's candidates on the host, in the shape hipHeadMerge takes: at most `limit` entries per bin, ascending. */
+struct head_list { uint64_t n; uint32_t *bins; uint64_t *words, *best; };
+
+static int head_list_alloc(struct head_list *l, uint64_t cap, bool wide) {
+    l->n = 0;
+    l->bins = malloc((size_t)(cap ? cap : 1) * sizeof *l->bins);
+    l->words = malloc((size_t)(cap ? cap : 1) * sizeof *l->words);
+    l->best = wide ? malloc((size_t)(cap ? cap : 1) * sizeof *l->best) : NULL;
+    return l->bins && l->words && (!wide || l->best) ? 0 : oom();
+}
+
+static void head_list_free(struct head_list *l) { free(l->bins); free(l->words); free(l->best); }
+
+/* The round cap of this query: PQPS_HEAD_ROUNDS_MAX, or what PQPS_HEAD_ROUNDS says below it (0: the sort form always). */
+static uint32_t head_round_cap(void) {
+    const char *e = getenv("PQPS_HEAD_ROUNDS");
+    if (!e || !*e) return PQPS_HEAD_ROUNDS_MAX;
+    const long v = strtol(e, NULL, 0);
+    return v < 0 ? 0u : v > (long)PQPS_HEAD_ROUNDS_MAX ? PQPS_HEAD_ROUNDS_MAX : (uint32_t)v;
+}
+
+/* The rounds form: one shard's device buffer is [16 B: the matching rows][out: rounds x n_bins words][best: the same,
+ * command_id only].  The sort form has no buffer (shard_reduce's post).  lists[0 .. *n_lists): what the shards handed. */
+struct head_call {
+    const struct group_plan *gp; const struct order_plan *op; void **buf;
+    uint32_t rounds; uint64_t limit;
+    struct head_list *lists; int *n_lists;
+    uint64_t *matches; bool fused; int rc;
+};
+
+static int head_fused_call(struct query *q, int s, pqps_ctx *ctx, void *stream, void *arg) {
+    const struct head_call *a = arg;
+    const struct group_plan *gp = a->gp;
+    const struct order_plan *op = a->op;
+    const struct hipTable *sh = hipTableShard(q->t, s);
+    const struct shard_pred *sp = &q->sp[s];
+    const bool grouped = gp->c >= 0 && !gp->single;
+    uint64_t *b = a->buf[s];
+    const size_t words = (size_t)a->rounds * gp->n_bins;
+    if (pqps_filter_group_head(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, op->no_key ? NULL : &op->kcol[s], op->key_signed, op->desc,
+                               (uint32_t)sh->row0, grouped ? &gp->gcol[s] : NULL, gp->bin_base, gp->n_bins, a->rounds, b + 2,
+                               op->wide ? b + 2 + words : NULL, b, stream) != PQPS_OK)
+        return engine_error("first-rows filter");
+    return 0;
+}
+
+static int head_list_call(struct query *q, int s, pqps_ctx *cs, const struct hipLane *L, void *out, void *arg) {
+    const struct head_call *a = arg;
+    const struct group_plan *gp = a->gp;
+    const struct order_plan *op = a->op;
+    const struct hipTable *sh = hipTableShard(q->t, s);
+    const bool grouped = gp->c >= 0 && !gp->single;
+    uint64_t *b = out;
+    const size_t words = (size_t)a->rounds * gp->n_bins;
+    return pqps_group_head_list(cs, op->no_key ? NULL : &op->kcol[s], op->key_signed, op->desc, grouped ? &gp->gcol[s] : NULL, gp->bin_base,
+                                gp->n_bins, sh->n_rows, L->ids_dev, L->count_dev, q->count[s], (uint32_t)sh->row0, a->rounds, b + 2,
+                                op->wide ? b + 2 + words : NULL, NULL);
+}
+
+/* One shard's [round][bin] words into a list: bin by bin, the rounds until the first all-ones word. */
+static void head_combine(void *arg, const void *host) {
+    struct head_call *a = arg;
+    const uint32_t n_bins = a->gp->n_bins, rounds = a->rounds;
+    const bool wide = a->op->wide;
+    const uint64_t *h = (const uint64_t *)host + 2, *hb = h + (size_t)rounds * n_bins;
+    if (a->fused) *a->matches += *(const uint64_t *)host;
+    if (a->rc != 0) return;
+    uint64_t cap = 0;
+    for (size_t i = 0; i < (size_t)rounds * n_bins; i++) cap += h[i] != UINT64_MAX;
+    struct head_list *l = &a->lists[(*a->n_lists)++];
+    if ((a->rc = head_list_alloc(l, cap, wide)) != 0) return;
+    for (uint32_t k = 0; k < n_bins; k++)
+        for (uint32_t r = 0; r < rounds && h[(size_t)r * n_bins + k] != UINT64_MAX; r++) {
+            l->bins[l->n] = k;
+            l->words[l->n] = h[(size_t)r * n_bins + k];
+            if (wide) l->best[l->n] = hb[(size_t)r * n_bins + k];
+            l->n++;
+        }
+}
+
+/* The sort form on one shard's list: pqps_group_head_sort, then the kept entries downloaded into a list. */
+static int head_sort_post(struct query *q, int s, pqps_ctx *cs, void *out, void *arg) {
+    (void)out;
+    struct head_call *a = arg;
+    const struct group_plan *gp = a->gp;
+    const struct order_plan *op = a->op;
+    struct hipTable *sh = hipTableShard(q->t, s);
+    const bool grouped = gp->c >= 0 && !gp->single;
+    const uint64_t n = q->count[s];
+    uint32_t *ids_dev = NULL, *ids = NULL;
+    uint64_t *keys_dev = NULL, *keys = NULL, kept = 0;
+    int rc = 0;
+    if (pqps_malloc(sh->ctx, n * sizeof(uint32_t), (void **)&ids_dev) != PQPS_OK ||
+        pqps_malloc(sh->ctx, 2 * n * sizeof(uint64_t), (void **)&keys_dev) != PQPS_OK) rc = engine_error("first-rows sort buffers");
+    else if (pqps_group_head_sort(cs, op->no_key ? NULL : &op->kcol[s], op->key_signed, op->desc, grouped ? &gp->gcol[s] : NULL,
+                                  gp->kind == HIPKIND_I32, query_lane(q, s)->ids_dev, n, (uint32_t)sh->row0, a->limit, q->n_probes > 0,
+                                  ids_dev, keys_dev, &kept, NULL) != PQPS_OK) rc = engine_error("first-rows sort");
+    struct head_list *l = &a->lists[*a->n_lists];
+    if (rc == 0) {
+        ++*a->n_lists;
+        rc = head_list_alloc(l, kept, op->wide);
+        ids = malloc((size_t)(kept ? kept : 1) * sizeof *ids);
+        keys = malloc((size_t)(kept ? kept : 1) * 2 * sizeof *keys);
+        if (rc == 0 && (!ids || !keys)) rc = oom();
+    }
+    if (rc == 0 && kept > 0 &&
+        (pqps_download(cs, ids, ids_dev, (size_t)kept * sizeof *ids, NULL) != PQPS_OK ||
+         pqps_download(cs, keys, keys_dev, (size_t)kept * sizeof *keys, NULL) != PQPS_OK ||
+         pqps_download(cs, keys + kept, keys_dev + n, (size_t)kept * sizeof *keys, NULL) != PQPS_OK)) rc = engine_error("first-rows download");
+    for (uint64_t i = 0; i < kept && rc == 0; i++) {
+        /* the images of pqps_sort_list: an i32 group's is v ^ 2^31; a key that is not read is 0 in every row */
+        const uint32_t bin = (grouped ? (uint32_t)keys[i] ^ (gp->kind == HIPKIND_I32 ? 0x80000000u : 0u) : gp->bin_base) - gp->bin_base;
+        const uint64_t img = op->no_key ? (op->desc ? 0xFFFFFFFFull : 0ull) : keys[kept + i];
+        if (bin >= gp->n_bins) continue;
+        l->bins[l->n] = bin;
+        l->words[l->n] = op->wide ? (uint64_t)ids[i] : img << 32 | ids[i];
+        if (op->wide) l->best[l->n] = img;
+        l->n++;
+    }
+    free(ids);
+    free(keys);
+    if (ids_dev) pqps_free(sh->ctx, ids_dev);
+    if (keys_dev) pqps_free(sh->ctx, keys_dev);
+    return rc;
+}
+
+/* Checks n, the two columns and the engine (group_first_begin); fills the result's column fields and the order plan. */
+static int group_head_begin(struct engineS *engine, const char *groupColumn, const char *orderColumn, bool descending, long long n,
+                            struct hipGroupHeadResult *res, struct order_plan *op) {
+    struct hipGroupFirstResult gf;
+    memset(&gf, 0, sizeof gf);
+    res->groupColumn = res->groupKind = res->orderColumn = res->orderKind = -1;
+    res->descending = descending;
+    if (n < 1) { fprintf(stderr, "HIP engine: first rows per group: n = %lld, not >= 1\n", n); return -1; }
+    res->limit = n > INT_MAX ? INT_MAX : (int)n;
+    const int rc = group_first_begin(engine, groupColumn, orderColumn, descending, &gf, op);
+    res->groupColumn = gf.groupColumn; res->groupKind = gf.groupKind;
+    res->orderColumn = gf.orderColumn; res->orderKind = gf.orderKind;
+    return rc;
+}
+
+/* The merged entries (ascending bin, then order) into the result: groups with a row only, in bin order. */
+static int group_head_fill(struct hipGroupHeadResult *res, const struct hipTable *t, const uint32_t *bins, const uint64_t *words,
+                           const uint64_t *best, uint64_t n, uint32_t n_bins, int32_t lo) {
+    uint64_t *present = calloc((size_t)n_bins + 1, sizeof *present);
+    if (!present) return oom();
+    for (uint64_t i = 0; i < n; i++) present[bins[i]]++;
+    int rc = group_keys_fill(t, res->groupColumn, res->groupKind, lo, present, n_bins, &res->keys, &res->keyText, &res->numGroups);
+    res->offsets = calloc((size_t)res->numGroups + 1, sizeof *res->offsets);
+    res->rows = calloc((size_t)n + 1, sizeof *res->rows);
+    res->orderKeys = calloc((size_t)n + 1, sizeof *res->orderKeys);
+    res->orderText = calloc((size_t)n + 1, sizeof *res->orderText);
+    if (rc == 0 && (!res->offsets || !res->rows || !res->orderKeys || !res->orderText)) rc = oom();
+    int g = 0;
+    for (uint32_t k = 0; k < n_bins && rc == 0; k++)
+        if (present[k]) { res->offsets[g + 1] = res->offsets[g] + (long long)present[k]; g++; }
+    free(present);
+    const int oc = res->orderColumn, kind = res->orderKind;
+    for (uint64_t i = 0; i < n && rc == 0; i++) {
+        char buf[32];
+        const char *text = buf;
+        if (kind == HIPKIND_U64) {
+            res->rows[i] = (unsigned int)words[i];
+            res->orderKeys[i] = (long long)(best[i] ^ (res->descending ? UINT64_MAX : 0));
+            snprintf(buf, sizeof buf, "%llu", (unsigned long long)res->orderKeys[i]);
+        } else {
+            hipFirstKeyDecode(kind, res->descending, words[i], &res->orderKeys[i], &res->rows[i]);
+            if (kind == HIPKIND_I32) snprintf(buf, sizeof buf, "%d", (int)res->orderKeys[i]);
+            else if (kind == HIPKIND_BOOL) text = res->orderKeys[i] ? "true" : "false";
+            else if (res->orderKeys[i] < (long long)t->dict[oc].count) text = t->dict[oc].values[res->orderKeys[i]];
+            else { fprintf(stderr, "HIP engine: first rows per group: code %lld outside the dictionary\n", res->orderKeys[i]); rc = -1; break; }
+        }
+        if (!(res->orderText[i] = strdup(text))) rc = oom();
+    }
+    return rc;
+}
+
+/* The query itself (caller holds the table shared and the query's lane, group_head_begin has passed). */
+static int group_head_run(struct engineS *engine, struct query *q, const char *groupColumn, struct order_plan *op, long long n,
+                          struct whereClauseS *whereClause, struct hipGroupHeadResult *res) {
+    struct hipTable *t = q->t;
+    struct group_plan gp;
+    struct head_list lists[HIP_MAX_SHARDS];
+    struct hipHeadList in[HIP_MAX_SHARDS];
+    int n_lists = 0;
+    uint64_t matches = 0, total = 0;
+    uint32_t *bins = NULL;
+    uint64_t *words = NULL, *best = NULL;
+    long long kept = 0;
+    int rc = group_plan_init(engine, whereClause, q, res->groupColumn, groupColumn, "first rows per group", &gp);
+    if (rc == 0 && !gp.empty) {
+        const bool rounds = (unsigned long long)n <= head_round_cap();
+        if (!rounds) {                                                   /* the sort form works on the selection's lists */
+            gp.fused = false;
+            for (int s = 0; s < q->n_shards && gp.c >= 0; s++) gp.gcol[s] = hipTableShard(t, s)->col[gp.c];
+        }
+        op->fused = gp.fused;
+        op->no_key = t->col[op->c].width == 0;
+        for (int s = 0; s < q->n_shards; s++) {
+            const struct hipTable *sh = hipTableShard(t, s);
+            op->kcol[s] = gp.fused && op->c == HIPCOL_SUDO_USED && sh->sudo_bits.data ? sh->sudo_bits : sh->col[op->c];
+        }
+        void *buf[HIP_MAX_SHARDS];
+        struct head_call a = { .gp = &gp, .op = op, .buf = buf, .rounds = rounds ? (uint32_t)n : 0, .limit = (uint64_t)n, .lists = lists,
+                               .n_lists = &n_lists, .matches = &matches, .fused = gp.fused, .rc = 0 };
+        const struct shard_reduce r = rounds
+            ? (struct shard_reduce){ .what = "first-rows words", .bytes = 16 + (size_t)a.rounds * gp.n_bins * (op->wide ? 2 : 1) * sizeof(uint64_t),
+                                     .fused = head_fused_call, .list = head_list_call, .combine = head_combine }
+            : (struct shard_reduce){ .what = "first-rows sort", .post = head_sort_post };
+        rc = shard_reduce(q, gp.fused, &r, buf, &a);
+        if (rc == 0) rc = a.rc;
+        if (rc == 0 && !gp.fused) matches = q->total;
+        for (int s = 0; s < n_lists; s++) {
+            in[s] = (struct hipHeadList){ lists[s].n, lists[s].bins, lists[s].words, lists[s].best };
+            total += lists[s].n;
+        }
+        if (rc == 0 && total > 0) {
+            bins = malloc((size_t)total * sizeof *bins);
+            words = malloc((size_t)total * sizeof *words);
+            best = op->wide ? malloc((size_t)total * sizeof *best) : NULL;
+            if (!bins || !words || (op->wide && !best)) rc = oom();
+            else if ((kept = hipHeadMerge(in, n_lists, n, bins, words, best)) < 0) rc = -1;
+        }
+    }
+    if (rc == 0) rc = group_head_fill(res, t, bins, words, best, (uint64_t)kept, gp.empty ? 0u : gp.n_bins, gp.lo);
+    if (rc == 0) res->total = (long long)matches;
+    for (int s = 0; s < n_lists; s++) head_list_free(&lists[s]);
+    free(bins);
+    free(words);
+    free(best);
+    return rc;
+}
+
+static void group_head_clear(struct hipGroupHeadResult *res) {
+    const long long n = res->offsets ? res->offsets[res->numGroups] : 0;
+    free_group_keys(res->keys, res->keyText, res->numGroups);
+    for (long long i = 0; i < n && res->orderText; i++) free(res->orderText[i]);
+    free(res->orderText);
+    free(res->orderKeys);
+    free(res->rows);
+    free(res->offsets);
+}
+
+struct hipGroupHeadResult *executeQueryGroupHeadHIP(struct engineS *engine, const char *groupColumn, const char *orderColumn,
+                                                    bool descending, long long n, struct whereClauseS *whereClause) {
+    const double t0 = now_seconds();
+    struct hipGroupHeadResult *res = calloc(1, sizeof *res);
+    if (!res) { oom(); return NULL; }
+    struct order_plan op;
+    if (group_head_begin(engine, groupColumn, orderColumn, descending, n, res, &op) != 0) return res;
+    struct query q;
+    if (!query_open(engine, &q)) return res;                             /* reason on stderr */
+    if (group_head_run(engine, &q, groupColumn, &op, n, whereClause, res) == 0) res->success = true;
+    query_close(&q);
+    res->queryTime = now_seconds() - t0;
+    return res;
+}
+
+void freeGroupHeadResultHIP(struct hipGroupHeadResult *res) {
+    if (!res) return;
+    group_head_clear(res);
+    free(res);
+}
+
+struct hipColumnarResult *executeQuerySelectGroupHeadHIP(struct engineS *engine, const char **selectItems, int numSelectItems,
+                                                         struct whereClauseS *whereClause, const char *groupColumn,
+                                                         const char *orderColumn, bool descending, long long n, long long *matches,
+                                                         long long **offsets) {
+    if (matches) *matches = 0;
+    if (offsets) *offsets = NULL;
+    struct hipColumnarResult *res = calloc(1, sizeof *res);
+    if (!res) { perror("Failed to allocate memory for result set"); exit(EXIT_FAILURE); }
+    if (!engine || !engine->record_block) return res;
+    if (selectItems == NULL || numSelectItems == 0) { selectItems = (const char **)k_all_columns; numSelectItems = 12; }
+    res->numColumns = numSelectItems;
+    res->columnNames = calloc((size_t)numSelectItems, sizeof(char *));
+    res->columnKinds = calloc((size_t)numSelectItems, sizeof(int));
+    res->values = calloc((size_t)numSelectItems, sizeof(void *));
+    res->dictionaries = calloc((size_t)numSelectItems, sizeof(*res->dictionaries));
+    res->dictionarySizes = calloc((size_t)numSelectItems, sizeof(int));
+    if (!res->columnNames || !res->columnKinds || !res->values || !res->dictionaries || !res->dictionarySizes) { perror("Failed to allocate memory for result set"); exit(EXIT_FAILURE); }
+    const double t0 = now_seconds();
+    struct hipGroupHeadResult gh;
+    struct order_plan op;
+    memset(&gh, 0, sizeof gh);
+    if (group_head_begin(engine, groupColumn, orderColumn, descending, n, &gh, &op) != 0) return res;
+    struct query q;
+    if (!query_open(engine, &q)) return res;                             /* reason on stderr */
+    int rc = group_head_run(engine, &q, groupColumn, &op, n, whereClause, &gh);
+    const uint64_t rows = rc == 0 ? (uint64_t)gh.offsets[gh.numGroups] : 0;
+    if (rc == 0) rc = project_listed_rows(&q, gh.rows, rows, selectItems, numSelectItems, res);
+    query_close(&q);
+    res->numRecords = rc == 0 ? (int)rows : 0;
+    res->queryTime = now_seconds() - t0;
+    res->success = rc == 0;
+    if (rc == 0 && matches) *matches = gh.total;
+    if (rc == 0 && offsets) {
+        *offsets = malloc(((size_t)gh.numGroups + 1) * sizeof **offsets);
+        if (*offsets) memcpy(*offsets, gh.offsets, ((size_t)gh.numGroups + 1) * sizeof **offsets);
+        else { oom(); res->success = false; }
+    }
+    group_head_clear(&gh);
+    return res;
+}
+
 void freeColumnarResultHIP(struct hipColumnarResult *res) {
     if (!res) return;
     for (int j = 0; j < res->numColumns; j++) {

@@ -1192,6 +1192,49 @@ int hipFirstKeyDecode(int kind, int descending, unsigned long long word, long lo
     return 1;
 }
 
+/* ---- the shard merge of the first N rows of every group ----------------------------------------------------------------- */
+
+/* Shard x's entry i against shard y's entry j: (bin, [best,] word). */
+static int head_entry_cmp(const struct hipHeadList *x, uint64_t i, const struct hipHeadList *y, uint64_t j, bool wide) {
+    if (x->bins[i] != y->bins[j]) return x->bins[i] < y->bins[j] ? -1 : 1;
+    if (wide && x->best[i] != y->best[j]) return x->best[i] < y->best[j] ? -1 : 1;
+    return x->words[i] < y->words[j] ? -1 : x->words[i] > y->words[j];
+}
+
+long long hipHeadMerge(const struct hipHeadList *shards, int n_shards, long long limit, uint32_t *out_bins, uint64_t *out_words,
+                       uint64_t *out_best) {
+    if (n_shards < 0 || (n_shards && !shards) || limit < 1) { fprintf(stderr, "hipHeadMerge: no shards, or limit %lld < 1\n", limit); return -1; }
+    bool wide = false;
+    uint64_t total = 0;
+    for (int s = 0; s < n_shards; s++) {
+        if (shards[s].n == 0) continue;
+        if (!shards[s].bins || !shards[s].words) { fprintf(stderr, "hipHeadMerge: shard %d: a NULL list\n", s); return -1; }
+        if (total && wide != (shards[s].best != NULL)) { fprintf(stderr, "hipHeadMerge: shard %d: narrow and wide lists mixed\n", s); return -1; }
+        wide = shards[s].best != NULL;
+        total += shards[s].n;
+    }
+    if (total && (!out_bins || !out_words || (wide && !out_best))) { fprintf(stderr, "hipHeadMerge: a NULL output\n"); return -1; }
+    uint64_t *at = calloc((size_t)(n_shards ? n_shards : 1), sizeof *at);
+    if (!at) { fprintf(stderr, "hipHeadMerge: out of memory\n"); return -1; }
+    uint64_t n = 0, in_bin = 0;
+    for (uint64_t step = 0; step < total; step++) {
+        int b = -1;
+        for (int s = 0; s < n_shards; s++)
+            if (at[s] < shards[s].n && (b < 0 || head_entry_cmp(&shards[s], at[s], &shards[b], at[b], wide) < 0)) b = s;
+        const uint64_t i = at[b]++;
+        const uint32_t bin = shards[b].bins[i];
+        if (n == 0 || out_bins[n - 1] != bin) in_bin = 0;
+        if (in_bin >= (uint64_t)limit) continue;                        /* the bin has its rows: a later shard's surplus */
+        out_bins[n] = bin;
+        out_words[n] = shards[b].words[i];
+        if (wide) out_best[n] = shards[b].best[i];
+        n++;
+        in_bin++;
+    }
+    free(at);
+    return (long long)n;
+}
+
 /* ---- the order of the top N groups ------------------------------------------------------------------------------------- */
 
 /* One group as the order sees it: `rank` ascends in the wanted order (complemented for a descending one), ties by bin. */
