@@ -101,6 +101,12 @@ struct hipTable {
      * the scans read in place of the byte column.  Packed from the byte column wherever that is written (load, INSERT,
      * DELETE) by the writer that wrote it; index builds, gathers, projection and compaction keep using the byte column. */
     pqps_column sudo_bits;
+    /* 12-bit packed copies (width PQPS_WIDTH_P12, capacity_rows * 3 / 2 bytes; data NULL: none) of the dictionary columns
+     * stored as u16 whose dictionary has at most 4096 entries: what a scan of that column alone, or of it and the plane of
+     * sudo_used, reads in place of the u16 column (1.5 bytes per row).  Every writer that changes a row or the codes of
+     * such a column repacks its copy WHOLE before it returns; a dictionary that outgrows 4096 entries, or a column whose
+     * width changes, drops the copy for good.  Everything but those scans keeps using the u16 column. */
+    pqps_column packed12[HIPCOL_COUNT];
     /* Value range of the i32 columns a grouped COUNT has grouped on (executeQueryGroupCountHIP), over every shard's rows;
      * shard 0 only, computed on first use.  INSERT widens a known range; DELETE leaves it (then possibly wider than the data). */
     int bounds_known[HIPCOL_COUNT];

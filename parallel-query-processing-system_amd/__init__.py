@@ -32,6 +32,7 @@ TILE_ROWS = 4096
 SLOT_HEADER_WORDS = 4
 ACCEPT, REJECT = 0xFE, 0xFF
 WIDTH_BITS = 0x81                  # pqps_column.width of a bit plane (PQPS_WIDTH_BITS)
+WIDTH_P12 = 0x8C                   # ... of a 12-bit packed copy of a u16 column (PQPS_WIDTH_P12)
 HIPKIND_U64, HIPKIND_I32, HIPKIND_BOOL, HIPKIND_DICT = 0, 1, 2, 3     # include/hipPredicate.h
 MEMBER_BITMAP, MEMBER_LIST = 0, 1  # pqps_member_flags: lookup form ...
 MEMBER_BYTES, MEMBER_PLANE = 0, 1  # ... and output form
@@ -470,6 +471,7 @@ def lib():
     L.pqps_synth_generate_host.restype = None
     L.pqps_bump_codes.argtypes = [vp, vp, u32, u64, u32, vp]
     L.pqps_pack_bits.argtypes = [vp, vp, u64, vp, u64, u64, vp]
+    L.pqps_pack12.argtypes = [vp, vp, u64, vp, u64, u64, vp]
     L.pqps_member_flags.argtypes = [vp, C.POINTER(Column), u64, C.c_int, u32, u64, vp, vp, u32, C.c_int, vp, vp, vp]
     L.hipIsSetOperator.argtypes = [C.c_char_p]
     L.pqps_filter_assign.argtypes = [vp, C.POINTER(Column), u32, u64, C.POINTER(Predicate), C.POINTER(AssignTarget), u32, vp, vp]
@@ -1104,6 +1106,10 @@ class Context:
 
     def sync(self, stream=None):
         check(lib().pqps_ctx_sync(self.h, stream), "pqps_ctx_sync")
+
+    def pack12(self, codes_dev, n_rows, packed_dev, first_row, padded_rows, stream=None):
+        """The 12-bit packed copy (WIDTH_P12) of a u16 device column: rows [first_row rounded down to 8, padded_rows)."""
+        check(lib().pqps_pack12(self.h, codes_dev, int(n_rows), packed_dev, int(first_row), int(padded_rows), stream), "pqps_pack12")
 
     def set_timing(self, on=True):
         check(lib().pqps_ctx_set_timing(self.h, 1 if on else 0))

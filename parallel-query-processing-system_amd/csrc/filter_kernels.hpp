@@ -55,7 +55,15 @@ constexpr int kSlotWords = 64;              // 16-bit entries of a step's slot i
 // in for -- a shape with a plane keeps the register budget and steps per iteration of the byte shape it replaces.
 constexpr uint8_t kWidthLog2Bits = 7;
 constexpr int kBitPlane = -1;
-constexpr int wcost(int w) { return w == kBitPlane ? 1 : w; }
+// 12-bit packed columns (PQPS_WIDTH_P12: row r = the 12 bits at bit offset 12 r, a copy of a u16 column of codes below 4096):
+// the FIRST column of the shapes (P,0,0) and (P,B,0) only.  Behind the column load it is the u16 column it stands in for:
+// same rows per lane, same register budget, same steps per iteration.
+constexpr uint8_t kWidthLog2P12 = 6;
+constexpr int kPacked12 = -2;
+constexpr int wcost(int w) { return w == kBitPlane ? 1 : (w == kPacked12 ? 2 : w); }
+// consecutive rows per lane per chunk: the widest column is one dwordx4 per chunk (an 8-byte column: two, so that RPL
+// stays in {4, 8, 16}; a packed 12-bit column: 8 rows = three dwords)
+constexpr int rows_per_lane(int w0) { return w0 == 8 ? 4 : 16 / wcost(w0); }
 
 enum Mode { MODE_IDS = 0, MODE_COUNT = 1, MODE_FLAGS = 2 };
 
@@ -2046,6 +2054,26 @@ struct RawChunk<kBitPlane, RPL> {
     __device__ __forceinline__ uint32_t get32() const { return (d[0] >> R) & 1u; }
 };
 
+// 8 rows of a packed 12-bit column: 96 bits at byte 12 * (row0 / 8) -- 4-byte aligned only, so three dword loads that the
+// compiler may merge into one dwordx3 (never a 16-byte access: the column ends with its last row's field).  The 64 lanes
+// of a chunk read 768 contiguous bytes.
+template <>
+struct RawChunk<kPacked12, 8> {
+    uint32_t d[3];
+    template <bool NT>
+    __device__ __forceinline__ void load(const char *p) {
+        const uint32_t *q = (const uint32_t *)p;
+        d[0] = ld_x1<NT>(q); d[1] = ld_x1<NT>(q + 1); d[2] = ld_x1<NT>(q + 2);
+    }
+    template <int R>
+    __device__ __forceinline__ uint32_t get32() const {          // row R: bits [12 R, 12 R + 12)
+        constexpr int bit = 12 * R, w = bit / 32, sh = bit % 32;
+        if constexpr (sh + 12 == 32) return d[w] >> sh;
+        else if constexpr (sh + 12 < 32) return (d[w] >> sh) & 0xFFFu;
+        else return __builtin_amdgcn_alignbit(d[w + 1], d[w], sh) & 0xFFFu;     // R = 2, 5: the field straddles two dwords
+    }
+};
+
 template <int W, int RPL, int U>
 struct RawCol {
     RawChunk<W, RPL> c[U];
@@ -2054,6 +2082,7 @@ struct RawCol {
 #pragma unroll
         for (int u = 0; u < U; u++) {
             if constexpr (W == kBitPlane) c[u].template load_bits<NT>((const char *)base, lane_row0 + (uint64_t)u * 64 * RPL);
+            else if constexpr (W == kPacked12) c[u].template load<NT>((const char *)base + (lane_row0 + (uint64_t)u * 64 * RPL) / 8 * 12);
             else c[u].template load<NT>((const char *)base + (lane_row0 + (uint64_t)u * 64 * RPL) * W);
         }
     }
@@ -2184,6 +2213,20 @@ __device__ __forceinline__ uint32_t chain_bits(CArgs &a, int slot, const RawCol<
     return keep;
 }
 
+// ... and of a 12-bit packed column (the first column of its two shapes): the same, from the extracted values
+template <int RPL, int U>
+__device__ __forceinline__ uint32_t chain_rows(CArgs &a, int slot, const RawCol<kPacked12, RPL, U> &raw) {
+    const uint32_t kb = a.leaf_begin[slot], ke = a.leaf_begin[slot + 1];
+    uint32_t v[16];
+    unpack32(raw, v, std::make_integer_sequence<int, 16>{});
+    uint32_t keep = 0xFFFFu;
+    for (uint32_t k = kb; k < ke; k++) {                            // uniform
+        const uint32_t h = leaf_mask<uint32_t, 16>(v, (uint32_t)a.lo[k], (uint32_t)a.span[k]);
+        keep &= ((a.chain_want >> k) & 1u) ? h : ~h;
+    }
+    return keep;
+}
+
 constexpr int log2i(int x) { return x <= 1 ? 0 : 1 + log2i(x / 2); }
 
 // All raw registers of one step for the (W0, W1, W2) shape.
@@ -2265,15 +2308,22 @@ struct RawStep {
             }
         } else if constexpr (EV == 2) {
             static_assert(W0 <= 4, "narrow columns");
-            uint32_t t[16];
-#pragma unroll
-            for (int r = 0; r < 16; r++) t[r] = 1u << r;
-            eval_col_valu<W0, RPL, U>(a, 0, r0, t);
-            if constexpr (W1 != 0 && W1 != kBitPlane) eval_col_valu<W1, RPL, U>(a, 1, r1, t);
-            if constexpr (W2 != 0 && W2 != kBitPlane) eval_col_valu<W2, RPL, U>(a, 2, r2, t);
             uint32_t m = 0;
+            if constexpr (W0 == kPacked12) {
+                // A packed column's 16 values are extracted, not picked out of the raw dwords by the compare itself: with
+                // valu_leaf's 16 row registers on top of them the kernel spills more than its u16 twin.  So a leaf's hits go
+                // straight into one 16-bit mask (compare + add-with-carry per row, as many VALU as compare + select).
+                m = chain_rows(a, 0, r0);
+            } else {
+                uint32_t t[16];
 #pragma unroll
-            for (int r = 0; r < 16; r++) m |= t[r];
+                for (int r = 0; r < 16; r++) t[r] = 1u << r;
+                eval_col_valu<W0, RPL, U>(a, 0, r0, t);
+                if constexpr (W1 != 0 && W1 != kBitPlane) eval_col_valu<W1, RPL, U>(a, 1, r1, t);
+                if constexpr (W2 != 0 && W2 != kBitPlane) eval_col_valu<W2, RPL, U>(a, 2, r2, t);
+#pragma unroll
+                for (int r = 0; r < 16; r++) m |= t[r];
+            }
             if constexpr (W1 == kBitPlane) m &= chain_bits<RPL, U>(a, 1, r1);     // (a plane is the last column)
             if constexpr (W2 == kBitPlane) m &= chain_bits<RPL, U>(a, 2, r2);
             if (a.chain == 2) m ^= 0xFFFFu;                         // OR form: NOT of the AND
@@ -2314,9 +2364,7 @@ struct RawStep {
 template <int MODE, int W0, int W1, int W2, bool NT>
 __global__ __launch_bounds__(kBlock, MODE == MODE_IDS ? (wcost(W0) + wcost(W1) + wcost(W2) >= 12 ? 7 : 8) : 1) void eval_spec_kernel(const EvalArgs) {
     CArgs &a = kernel_args();
-    // consecutive rows per lane per chunk: the widest column is one dwordx4 per chunk
-    // (an 8-byte column: two, so that RPL stays in {4, 8, 16})
-    constexpr int RPL = W0 == 8 ? 4 : 16 / W0;
+    constexpr int RPL = rows_per_lane(W0);
     constexpr int U = 16 / RPL;                                 // chunks per step
     PQPS_HOIST_KERNARGS(a);
     const uint64_t n_rows = a.n_rows;
@@ -2384,7 +2432,7 @@ constexpr int chain_steps(int w0, int w1, int w2) { return wcost(w0) + wcost(w1)
 template <int MODE, int W0, int W1, int W2, int S, bool NT, int EV>
 __global__ __launch_bounds__(kBlock, MODE == MODE_IDS ? PQPS_CHAIN_WGS : 1) void eval_chain_kernel(const EvalArgs) {
     CArgs &a = kernel_args();
-    constexpr int RPL = W0 == 8 ? 4 : 16 / W0;
+    constexpr int RPL = rows_per_lane(W0);
     constexpr int U = 16 / RPL;
     PQPS_HOIST_KERNARGS(a);
     const uint64_t n_rows = a.n_rows;

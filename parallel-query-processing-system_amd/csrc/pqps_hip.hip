@@ -433,6 +433,27 @@ __global__ void pack_bits_kernel(const uint8_t *bytes, uint64_t n_rows, uint8_t 
     }
 }
 
+// ---- 12-bit packed copies of u16 code columns (PQPS_WIDTH_P12) --------------------------------
+// One thread per 8 rows = 3 dwords of the copy: the 8 codes in one 16-byte load where all of them exist.
+__global__ void pack12_kernel(const uint16_t *codes, uint64_t n_rows, uint32_t *packed, uint64_t first_oct, uint64_t octs) {
+    for (uint64_t o = first_oct + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; o < octs; o += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t r0 = o * 8;
+        uint32_t v[8];
+        if (r0 + 8 <= n_rows) {
+            const uint4 x = *(const uint4 *)(codes + r0);                // (16-byte aligned column, r0 a multiple of 8)
+            v[0] = x.x & 0xFFFu; v[1] = (x.x >> 16) & 0xFFFu; v[2] = x.y & 0xFFFu; v[3] = (x.y >> 16) & 0xFFFu;
+            v[4] = x.z & 0xFFFu; v[5] = (x.z >> 16) & 0xFFFu; v[6] = x.w & 0xFFFu; v[7] = (x.w >> 16) & 0xFFFu;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 8; i++) v[i] = r0 + i < n_rows ? (codes[r0 + i] & 0xFFFu) : 0u;
+        }
+        uint32_t *out = packed + o * 3;
+        out[0] = v[0] | (v[1] << 12) | (v[2] << 24);
+        out[1] = (v[2] >> 8) | (v[3] << 4) | (v[4] << 16) | (v[5] << 28);
+        out[2] = (v[5] >> 4) | (v[6] << 8) | (v[7] << 20);
+    }
+}
+
 // Loads this library's code object (several MB, ~8 ms) when a context is created -- an engine does
 // that on a background thread beside its CSV parse -- instead of inside the first query.
 __global__ void warm_kernel() {}
@@ -654,7 +675,10 @@ int take_status_of(pqps_ctx *ctx, uint32_t lo, uint32_t hi, const char *who) {
 }
 
 // `bits_ok`: the call scans (bit-plane columns are read by the scan kernels); gathers take byte columns only
-int check_pred(const pqps_column *cols, uint32_t n_cols, const pqps_predicate *pred, bool bits_ok = true) {
+// `p12_ok`: the call is a plain ID / COUNT / flag scan, whose specialised kernels read a 12-bit packed first column in the
+// shapes (P) and (P,B) with at most PQPS_TT_LEAVES leaves; everything else (gathers, the fused and grouped scans, the
+// generic kernel) refuses one
+int check_pred(const pqps_column *cols, uint32_t n_cols, const pqps_predicate *pred, bool bits_ok = true, bool p12_ok = false) {
     if (!pred) return fail(PQPS_EINVAL, "predicate is NULL");
     if (n_cols > PQPS_MAX_COLUMNS) return fail(PQPS_EINVAL, "too many columns: %u", n_cols);
     if (n_cols && !cols) return fail(PQPS_EINVAL, "column array is NULL");
@@ -663,6 +687,14 @@ int check_pred(const pqps_column *cols, uint32_t n_cols, const pqps_predicate *p
     for (uint32_t c = 0; c < n_cols; c++) {
         const uint32_t w = cols[c].width;
         if (w == PQPS_WIDTH_BITS && !bits_ok) return fail(PQPS_EINVAL, "column %u: a bit plane is read by scans only", c);
+        if (w == PQPS_WIDTH_P12) {
+            if (!p12_ok) return fail(PQPS_EINVAL, "column %u: a 12-bit packed column is read by plain scans only", c);
+            if (c != 0) return fail(PQPS_EINVAL, "column %u: a 12-bit packed column must be the first column", c);
+            if (n_cols > 2 || (n_cols == 2 && cols[1].width != PQPS_WIDTH_BITS))
+                return fail(PQPS_EINVAL, "a 12-bit packed column scans alone or with one bit plane behind it");
+            if (pred->n_leaves < 1 || pred->n_leaves > PQPS_TT_LEAVES)
+                return fail(PQPS_EINVAL, "a 12-bit packed column takes 1 .. %d leaves, not %u", PQPS_TT_LEAVES, pred->n_leaves);
+        } else
         if (w != 1 && w != 2 && w != 4 && w != 8 && w != PQPS_WIDTH_BITS) return fail(PQPS_EINVAL, "column %u: width %u not in {1,2,4,8,bits}", c, w);
         if (!cols[c].data) return fail(PQPS_EINVAL, "column %u: NULL data", c);
         if (((uintptr_t)cols[c].data & 15u) != 0) return fail(PQPS_EINVAL, "column %u: data not 16-byte aligned", c);
@@ -693,7 +725,7 @@ void fill_args(EvalArgs &a, const pqps_column *cols, uint32_t n_cols, const pqps
     for (uint32_t c = 0; c < n_cols; c++) {
         a.col[c] = cols[c].data;
         const uint32_t w = cols[c].width;
-        a.width_log2[c] = w == PQPS_WIDTH_BITS ? kWidthLog2Bits : w == 1 ? 0 : w == 2 ? 1 : w == 4 ? 2 : 3;
+        a.width_log2[c] = w == PQPS_WIDTH_BITS ? kWidthLog2Bits : w == PQPS_WIDTH_P12 ? kWidthLog2P12 : w == 1 ? 0 : w == 2 ? 1 : w == 4 ? 2 : 3;
     }
     uint32_t k = 0;
     for (uint32_t c = 0; c <= n_cols; c++) {
@@ -732,8 +764,9 @@ typedef void (*eval_fn)(const EvalArgs);
 // every non-increasing (W0, W1, W2) from {8,4,2,1}, W = 0 marks an unused slot -- at most one 8-byte column (the schema has one,
 // command_id) -- and the same shapes with a bit plane (B) as their last column (the schema has one boolean, sudo_used).
 // A shape not listed (several planes, a plane before a byte column, a lone plane) takes the generic kernel.
+// P = a 12-bit packed copy of a u16 column: alone or with the plane behind it, nowhere else (check_pred refuses the rest).
 #ifdef PQPS_DEV_SHAPES   /* development builds: the bench shapes only (compiles in a fraction of the time) */
-#define PQPS_FOR_EACH_SHAPE(X) X(4,0,0) X(2,0,0) X(1,0,0) X(4,1,0) X(2,1,0) X(4,4,4) X(4,B,0) X(2,B,0)
+#define PQPS_FOR_EACH_SHAPE(X) X(4,0,0) X(2,0,0) X(1,0,0) X(4,1,0) X(2,1,0) X(4,4,4) X(4,B,0) X(2,B,0) X(P,0,0) X(P,B,0)
 #else
 #define PQPS_FOR_EACH_SHAPE(X) \
     X(8,0,0) X(4,0,0) X(2,0,0) X(1,0,0) \
@@ -741,7 +774,8 @@ typedef void (*eval_fn)(const EvalArgs);
     X(8,4,4) X(8,4,2) X(8,4,1) X(8,2,2) X(8,2,1) X(8,1,1) \
     X(4,4,4) X(4,4,2) X(4,4,1) X(4,2,2) X(4,2,1) X(4,1,1) X(2,2,2) X(2,2,1) X(2,1,1) X(1,1,1) \
     X(8,B,0) X(4,B,0) X(2,B,0) X(1,B,0) \
-    X(8,4,B) X(8,2,B) X(8,1,B) X(4,4,B) X(4,2,B) X(4,1,B) X(2,2,B) X(2,1,B) X(1,1,B)
+    X(8,4,B) X(8,2,B) X(8,1,B) X(4,4,B) X(4,2,B) X(4,1,B) X(2,2,B) X(2,1,B) X(1,1,B) \
+    X(P,0,0) X(P,B,0)
 #endif
 
 // chain kernels exist with 1 step per iteration and (narrow shapes) with several, and in three evaluator variants:
@@ -755,7 +789,7 @@ constexpr bool valu_chain_shape(int a, int b, int c) { return a <= 4 && wcost(a)
 // tile path spills at 64 VGPRs), at 1 G rows 901 / 959.  So: the u16 + u8 shape, ID output, below the size from which the
 // expanders run among the tiles.
 inline bool valu_chain_default(int w0, int w1, int w2, int mode, uint64_t n_rows) {
-    return mode == MODE_IDS && w0 == 2 && (w1 == 1 || w1 == kBitPlane) && w2 == 0 && n_rows < kListAreaBelowGroups * (uint64_t)kGroupSteps * kStepRows;
+    return mode == MODE_IDS && ((w0 == 2 && (w1 == 1 || w1 == kBitPlane)) || (w0 == kPacked12 && w1 == kBitPlane)) && w2 == 0 && n_rows < kListAreaBelowGroups * (uint64_t)kGroupSteps * kStepRows;
 }
 
 template <int MODE, int A, int B, int C, int S, bool NT>
@@ -770,6 +804,7 @@ eval_fn chain_variant(int ev) {
 }
 
 #define B kBitPlane
+#define P kPacked12
 template <int MODE, bool NT>
 eval_fn find_spec_nt(int w0, int w1, int w2, bool chain, bool multi_step, int vc) {
 #define X(A, B, C) if (w0 == A && w1 == B && w2 == C) return !chain ? eval_spec_kernel<MODE, A, B, C, NT> \
@@ -778,6 +813,7 @@ eval_fn find_spec_nt(int w0, int w1, int w2, bool chain, bool multi_step, int vc
 #undef X
     return nullptr;
 }
+#undef P
 #undef B
 
 // A scan is "streaming" once the columns it reads outgrow the Infinity Cache (256 MB on MI355X) by
@@ -790,18 +826,19 @@ bool is_streaming(uint64_t footprint) {
     return force ? atoi(force) != 0 : footprint > kStreamingFootprint;
 }
 
-// (the bytes the scan reads: a bit plane is an eighth of a byte per row)
+// (the bytes the scan reads: a bit plane is an eighth of a byte per row, a 12-bit packed column twelve eighths)
 void set_streaming(EvalArgs &a, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows) {
     uint64_t row_eighths = 0;
-    for (uint32_t c = 0; c < n_cols; c++) row_eighths += cols[c].width == PQPS_WIDTH_BITS ? 1u : 8u * cols[c].width;
+    for (uint32_t c = 0; c < n_cols; c++)
+        row_eighths += cols[c].width == PQPS_WIDTH_BITS ? 1u : cols[c].width == PQPS_WIDTH_P12 ? 12u : 8u * cols[c].width;
     a.streaming = is_streaming(n_rows * row_eighths / 8) ? 1u : 0u;
 }
 
 // width of a column as the specialised kernels' template parameter
-int spec_width(uint32_t w) { return w == PQPS_WIDTH_BITS ? kBitPlane : (int)w; }
+int spec_width(uint32_t w) { return w == PQPS_WIDTH_BITS ? kBitPlane : w == PQPS_WIDTH_P12 ? kPacked12 : (int)w; }
 const char *width_name(int w) {
     static const char *const names[] = { "0", "1", "2", "?", "4", "?", "?", "?", "8" };
-    return w == kBitPlane ? "B" : (w >= 0 && w <= 8 ? names[w] : "?");
+    return w == kBitPlane ? "B" : w == kPacked12 ? "P12" : (w >= 0 && w <= 8 ? names[w] : "?");
 }
 
 template <int MODE>
@@ -836,6 +873,7 @@ eval_fn pick_eval(const pqps_column *cols, uint32_t n_cols, const pqps_predicate
             return f;
         }
     }
+    if (n_cols && cols[0].width == PQPS_WIDTH_P12) return nullptr;     // (check_pred lets only the two listed shapes through: the generic kernel never reads one)
     snprintf(g_kernel, sizeof g_kernel, "eval_generic_kernel<%s, GATHER=false, NT=%s>", MODE == MODE_IDS ? "MODE_IDS" : MODE == MODE_COUNT ? "MODE_COUNT" : "MODE_FLAGS",
              a.streaming ? "true" : "false");
     return a.streaming ? eval_generic_kernel<MODE, false, true> : eval_generic_kernel<MODE, false, false>;
@@ -1182,11 +1220,12 @@ int scan_request(ScanRequest &r, int mode, const pqps_column *cols, uint32_t n_c
     if (!out_ids && out_capacity) return fail(PQPS_EINVAL, "out_ids is NULL");
     if (mode == MODE_IDS && (n_rows > 0xFFFFFFFFull || (uint64_t)id_base + n_rows > 0x100000000ull))
         return fail(PQPS_EINVAL, "row IDs are u32: id_base + n_rows must be <= 2^32");
-    const int rc = check_pred(cols, n_cols, pred);
+    const int rc = check_pred(cols, n_cols, pred, true, true);
     if (rc) return rc;
     fill_args(r.a, cols, n_cols, pred);
     r.a.n_rows = n_rows;
     r.k1 = mode == MODE_IDS ? pick_eval<MODE_IDS>(cols, n_cols, pred, r.a, n_rows) : pick_eval<MODE_COUNT>(cols, n_cols, pred, r.a, n_rows);
+    if (!r.k1) return fail(PQPS_EINVAL, "no specialised kernel reads this shape with a 12-bit packed column");
     r.mode = mode; r.n_rows = n_rows; r.id_base = id_base; r.out_ids = out_ids; r.out_cap = out_capacity;
     return PQPS_OK;
 }
@@ -1470,7 +1509,7 @@ int pqps_filter_flags(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols,
                       uint64_t n_rows, const pqps_predicate *pred,
                       uint8_t *out_flags, uint64_t *out_count, void *stream) {
     if (!ctx || !out_count || !out_flags) return fail(PQPS_EINVAL, "ctx/out_flags/out_count is NULL");
-    int rc = check_pred(cols, n_cols, pred);
+    int rc = check_pred(cols, n_cols, pred, true, true);
     if (rc) return rc;
     hipStream_t s = pick_stream(ctx, stream);
     EvalArgs a;
@@ -1478,6 +1517,13 @@ int pqps_filter_flags(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols,
     a.n_rows = n_rows;
     a.out_flags = out_flags;
     set_streaming(a, cols, n_cols, n_rows);                      // load policy + grid of a scan that outgrows the Infinity Cache
+    if (n_cols && cols[0].width == PQPS_WIDTH_P12) {             // (no WHERE: no column, `cols` may be NULL)  (P) / (P,B): the row-mask kernels of the two shapes, the generic kernel reads no packed column
+        const bool nt = a.streaming != 0;
+        const eval_fn k = n_cols == 1 ? (nt ? eval_spec_kernel<MODE_FLAGS, kPacked12, 0, 0, true> : eval_spec_kernel<MODE_FLAGS, kPacked12, 0, 0, false>)
+                                      : (nt ? eval_spec_kernel<MODE_FLAGS, kPacked12, kBitPlane, 0, true> : eval_spec_kernel<MODE_FLAGS, kPacked12, kBitPlane, 0, false>);
+        snprintf(g_kernel, sizeof g_kernel, "eval_spec_kernel<MODE_FLAGS, W0=P12, W1=%s, W2=0, NT=%s>", n_cols == 1 ? "0" : "B", nt ? "true" : "false");
+        return run_filter(ctx, k, a, n_rows, MODE_FLAGS, false, 0, nullptr, 0, out_count, s);
+    }
     return run_filter(ctx, a.streaming ? eval_generic_kernel<MODE_FLAGS, false, true> : eval_generic_kernel<MODE_FLAGS, false, false>, a, n_rows, MODE_FLAGS, false,
                       0, nullptr, 0, out_count, s);
 }
@@ -1744,6 +1790,21 @@ int pqps_pack_bits(pqps_ctx *ctx, const uint8_t *bytes, uint64_t n_rows, uint8_t
     const uint64_t want = (plane_bytes - first_byte + 255) / 256;
     const uint32_t blocks = (uint32_t)(want < 8192 ? want : 8192);
     hipLaunchKernelGGL(pack_bits_kernel, dim3(blocks), dim3(256), 0, s, bytes, n_rows, plane, first_byte, plane_bytes);
+    HIP_TRY(hipGetLastError());
+    return PQPS_OK;
+}
+
+int pqps_pack12(pqps_ctx *ctx, const uint16_t *codes, uint64_t n_rows, void *packed, uint64_t first_row, uint64_t padded_rows,
+                void *stream) {
+    if (!ctx || !packed || (!codes && n_rows)) return fail(PQPS_EINVAL, "NULL argument");
+    if ((((uintptr_t)codes | (uintptr_t)packed) & 15u) != 0) return fail(PQPS_EINVAL, "code column / packed copy not 16-byte aligned");
+    if ((padded_rows & 7u) != 0 || padded_rows < n_rows) return fail(PQPS_EINVAL, "padded_rows must be a multiple of 8 and at least n_rows");
+    const uint64_t first_oct = first_row / 8, octs = padded_rows / 8;
+    if (first_oct >= octs) return PQPS_OK;
+    hipStream_t s = pick_stream(ctx, stream);
+    const uint64_t want = (octs - first_oct + 255) / 256;
+    const uint32_t blocks = (uint32_t)(want < 8192 ? want : 8192);
+    hipLaunchKernelGGL(pack12_kernel, dim3(blocks), dim3(256), 0, s, codes, n_rows, (uint32_t *)packed, first_oct, octs);
     HIP_TRY(hipGetLastError());
     return PQPS_OK;
 }

@@ -468,6 +468,41 @@ static void shard_lanes_create(struct hipTable *sh, int n_lanes) {
     if (pqps_qstream_reserve(sh->qs, sh->capacity_rows) != PQPS_OK) hip_die("query stream scratch");
 }
 
+/* 12-bit packed copies (PQPS_WIDTH_P12, capacity_rows * 3 / 2 bytes) of the dictionary columns stored as u16 whose
+ * dictionary -- shard 0's, the table `t` -- has at most 4096 entries: what one- and two-column scans read in place of the
+ * u16 column (executeEngine-hip.c: pass_columns).  A copy the device cannot spare is simply absent, like the list area. */
+#define HIP_PACKED12_CODES 4096
+static bool packed12_fits(const struct hipTable *t, const struct hipTable *sh, int c) {
+    return k_kind[c] == HIPKIND_DICT && sh->col[c].width == 2 && sh->col[c].data && t->dict[c].count <= HIP_PACKED12_CODES;
+}
+
+static void shard_alloc_packed12(struct hipTable *sh, int c) {
+    void *dev = NULL;
+    sh->packed12[c].data = pqps_malloc(sh->ctx, sh->capacity_rows / 2 * 3, &dev) == PQPS_OK ? dev : NULL;
+}
+
+static void shard_free_packed12(struct hipTable *sh, int c) {
+    if (sh->packed12[c].data) pqps_free(sh->ctx, (void *)sh->packed12[c].data);
+    sh->packed12[c].data = NULL;
+}
+
+/* Every packed copy of the shard from its u16 column, WHOLE (writers never patch a copy), the fields past n_rows zero.
+ * Synchronous, like shard_pack_bits.  A column that no longer fits -- its dictionary has outgrown 4096 entries, or its
+ * width changed -- loses its copy for good.  `mask` (bit c: column c): the columns whose rows or codes the caller changed. */
+static void shard_pack12_of(const struct hipTable *t, struct hipTable *sh, uint32_t mask) {
+    bool packed = false;
+    for (int c = 0; c < HIPCOL_COUNT; c++) {
+        if (!sh->packed12[c].data || !(mask & (1u << c))) continue;
+        if (!packed12_fits(t, sh, c)) { shard_free_packed12(sh, c); continue; }
+        if (pqps_pack12(sh->ctx, (const uint16_t *)sh->col[c].data, sh->n_rows, (void *)sh->packed12[c].data, 0, sh->capacity_rows, NULL) != PQPS_OK)
+            hip_die("12-bit packed copy");
+        packed = true;
+    }
+    if (packed && pqps_ctx_sync(sh->ctx, NULL) != PQPS_OK) hip_die("12-bit packed copy");
+}
+
+static void shard_pack12(const struct hipTable *t, struct hipTable *sh) { shard_pack12_of(t, sh, ~0u); }
+
 /* Buffers of one shard for rows [row0, row0 + count): capacity leaves head-room so that INSERT appends in place; the
  * rows past the last one are zero (the filter reads whole 1024-row steps). */
 static void shard_alloc(struct hipTable *sh, pqps_ctx *ctx, const struct hipTable *widths, size_t row0, size_t count) {
@@ -492,6 +527,11 @@ static void shard_alloc(struct hipTable *sh, pqps_ctx *ctx, const struct hipTabl
         void *dev = NULL;
         if (pqps_malloc(ctx, sh->capacity_rows / 8, &dev) != PQPS_OK) hip_die("bit plane allocation");
         sh->sudo_bits.data = dev;
+    }
+    for (int c = 0; c < HIPCOL_COUNT; c++) {
+        sh->packed12[c].data = NULL;
+        sh->packed12[c].width = PQPS_WIDTH_P12;
+        if (packed12_fits(widths, sh, c)) shard_alloc_packed12(sh, c);
     }
     lane_alloc(sh, &sh->own, false);
     if (pqps_ctx_reserve(ctx, sh->capacity_rows) != PQPS_OK) hip_die("filter scratch allocation");   /* not inside the first query */
@@ -519,6 +559,7 @@ static void shard_upload(struct hipTable *sh, pqps_ctx *ctx, const struct hipTab
             hip_die("column upload");
     }
     shard_pack_all_bits(sh);
+    shard_pack12(widths, sh);
 }
 
 /* The shard structs of a table over `n_shards` contexts (shard 0 = the table itself). */
@@ -741,6 +782,7 @@ static void shard_release(struct hipTable *sh, int n_indexes) {
     }
     if (sh->sudo_bits.data) pqps_free(sh->ctx, (void *)sh->sudo_bits.data);
     sh->sudo_bits.data = NULL;
+    for (int c = 0; c < HIPCOL_COUNT; c++) shard_free_packed12(sh, c);
     if (sh->index) {
         for (int i = 0; i < n_indexes; i++) {
             if (sh->index[i].perm_dev) pqps_free(sh->ctx, sh->index[i].perm_dev);
@@ -977,8 +1019,11 @@ bool appendRowDeviceTableHIP(struct engineS *engine, const record *r) {
     }
     last->n_rows += 1;
     shard_pack_bits(last, last->n_rows - 1, (last->n_rows - 1) / 8 + 1);      /* the plane byte of the new row */
-    for (int s = 0; s < n_shards; s++)                          /* shifted codes are keys of the other shards' indexes too */
-        if (bumped || s == n_shards - 1) rebuild_indexes(engine, hipTableShard(t, s));
+    for (int s = 0; s < n_shards; s++) {                        /* shifted codes are keys of the other shards' indexes too */
+        if (!bumped && s != n_shards - 1) continue;
+        shard_pack12(t, hipTableShard(t, s));
+        rebuild_indexes(engine, hipTableShard(t, s));
+    }
     return true;
 }
 
@@ -1026,6 +1071,7 @@ void finishUpdateDeviceTableHIP(struct engineS *engine, const struct hipAssignme
     for (int s = 0; s < hipTableShards(t); s++) {
         struct hipTable *sh = hipTableShard(t, s);
         if (matched[s] && (assigned & (1u << HIPCOL_SUDO_USED))) shard_pack_all_bits(sh);
+        shard_pack12_of(t, sh, bumped | (matched[s] ? assigned : 0));        /* (an UPDATE of other columns repacks nothing) */
         rebuild_indexes_of(engine, sh, bumped | (matched[s] ? assigned : 0));
     }
 }
@@ -1048,6 +1094,7 @@ void compactDeviceTableHIP(struct engineS *engine, uint8_t *const *delete_flags_
         sh->row0 = total;
         total += kept;
         if (changed) shard_pack_all_bits(sh);
+        if (changed) shard_pack12(t, sh);
         if (changed) rebuild_indexes(engine, sh);
     }
     if (total != (uint64_t)expected_rows) {
@@ -1168,6 +1215,7 @@ bool buildDeviceTableFromColumnsHIP(struct engineS *engine, unsigned long long n
         }
         if (pqps_ctx_sync(sh->ctx, NULL) != PQPS_OK) hip_die("column copy");
         shard_pack_all_bits(sh);
+        shard_pack12(t, sh);
     }
     free(ctxs);
     table_make_engine(t);
@@ -1266,6 +1314,7 @@ static bool synthetic_table(struct engineS *engine, unsigned long long num_rows,
         if (sh->n_rows && pqps_synth_generate(sh->ctx, seed, sh->row0, sh->n_rows, cdf_dev, shell_dev, &out, NULL) != PQPS_OK) hip_die("synthetic table generation");
         if (pqps_ctx_sync(sh->ctx, NULL) != PQPS_OK) hip_die("synthetic table generation");
         shard_pack_all_bits(sh);
+        shard_pack12(t, sh);
         pqps_free(sh->ctx, cdf_dev);
         pqps_free(sh->ctx, shell_dev);
     }
@@ -1532,6 +1581,11 @@ static void shard_grow(struct hipTable *sh, uint64_t count) {
         sh->sudo_bits.data = NULL;
         if (pqps_malloc(sh->ctx, sh->capacity_rows / 8, (void **)&sh->sudo_bits.data) != PQPS_OK) hip_die("bit plane allocation");
     }
+    for (int c = 0; c < HIPCOL_COUNT; c++) {                        /* likewise */
+        if (!sh->packed12[c].data) continue;
+        shard_free_packed12(sh, c);
+        shard_alloc_packed12(sh, c);
+    }
     struct hipLane *lanes[HIP_MAX_LANES + 1];
     int n = 0;
     lanes[n++] = &sh->own;
@@ -1605,6 +1659,8 @@ void commitAppendHIP(struct engineS *engine, struct hipAppend *b) {
         dictionary_free(&t->dict[c]);
         t->dict[c] = d;
     }
+    for (int s = 0; s < n_shards; s++)                             /* (after 4: a copy goes by its column's new dictionary) */
+        if (changed || s == n_shards - 1) shard_pack12(t, hipTableShard(t, s));
     /* 5. the indexes, once: all of the last shard's, elsewhere those whose keys changed */
     for (int s = 0; s < n_shards; s++) rebuild_indexes_of(engine, hipTableShard(t, s), s == n_shards - 1 ? ~0u : changed);
     engine->num_records += (int)B;

@@ -182,10 +182,20 @@ static bool plane_slot(const struct hipPass *pass, uint32_t i) {
     return n > 1 && (i == n - 1 || generic);
 }
 
-/* `scan`: the columns go to a scan (pqps_filter_scan / _count / _flags, query stream, exchange), which reads sudo_used from
- * its bit plane where plane_slot allows.  Index-mode gathers always get the byte column.  `sp`: the shard's flag buffers
- * (NULL for a plan of one pass); the flags of a member pass are a plane where head_pass wrote one. */
-static void pass_columns(const struct hipTable *sh, const struct hipPass *pass, const struct shard_pred *sp, bool scan, pqps_column *cols) {
+/* PQPS_PACK12=0 (read once): no scan reads a 12-bit packed copy (A/B runs, tests). */
+static bool packed12_enabled(void) {
+    static int on = -1;
+    if (on < 0) { const char *e = getenv("PQPS_PACK12"); on = !e || atoi(e) != 0; }
+    return on != 0;
+}
+
+/* `scan`: the columns go to a scan (pqps_filter_scan / _count / _flags, query stream, exchange, the fused scans), which
+ * reads sudo_used from its bit plane where plane_slot allows.  Index-mode gathers always get the byte column.  `plain`:
+ * the scan is an ID, COUNT or flag scan -- those read a u16 dictionary column from its 12-bit packed copy where the pass
+ * is that column alone, or that column and the plane of sudo_used, with at most 6 comparisons: the two shapes the
+ * specialised kernels have for a copy.  `sp`: the shard's flag buffers (NULL for a plan of one pass); the flags of a
+ * member pass are a plane where head_pass wrote one. */
+static void pass_columns(const struct hipTable *sh, const struct hipPass *pass, const struct shard_pred *sp, bool scan, bool plain, pqps_column *cols) {
     const uint32_t n = pass->pred.n_columns;
     for (uint32_t i = 0; i < n; i++) {
         const int id = pass->column_ids[i];
@@ -197,6 +207,12 @@ static void pass_columns(const struct hipTable *sh, const struct hipPass *pass, 
         else if (scan && id == HIPCOL_SUDO_USED && sh->sudo_bits.data && plane_slot(pass, i)) cols[i] = sh->sudo_bits;
         else cols[i] = sh->col[id];
     }
+    /* (n < 1 first: a pass without columns -- no WHERE -- has filled in nothing of `cols`, which may be the caller's bare stack array) */
+    if (!scan || !plain || n < 1 || n > 2 || pass->pred.n_leaves < 1 || pass->pred.n_leaves > PQPS_TT_LEAVES || !packed12_enabled()) return;
+    const int first = pass->column_ids[0];
+    if (first >= PQPS_MAX_COLUMNS || !sh->packed12[first].data || cols[0].width != 2) return;
+    if (n == 2 && !(pass->column_ids[1] == HIPCOL_SUDO_USED && cols[1].width == PQPS_WIDTH_BITS)) return;
+    cols[0] = sh->packed12[first];
 }
 
 /* A member pass writes a plane when every reader of its flag column is a scan that takes a plane in that slot
@@ -236,7 +252,7 @@ static int head_passes(const struct hipPlan *plan, const struct hipTable *t, int
         TRY(pqps_malloc(sh->ctx, sh->capacity_rows, (void **)&sp->flags[k]), "flag allocation");
         if (!pass->member) {
             pqps_column cols[PQPS_MAX_COLUMNS];
-            pass_columns(sh, pass, sp, true, cols);
+            pass_columns(sh, pass, sp, true, true, cols);
             TRY(pqps_filter_flags(ctx, cols, pass->pred.n_columns, sh->n_rows, &pass->pred, sp->flags[k], count_dev, stream), "flag filter");
             continue;
         }
@@ -413,7 +429,7 @@ static int issue_calls(struct query *q, int s, pqps_ctx *ctx, void *stream) {
     if (head_passes(plan, q->t, s, sp, ctx, stream, L->count_dev + 4, scan_last) != 0) return -1;
     sp->pred = &last->pred;
     sp->n_cols = last->pred.n_columns;
-    pass_columns(sh, last, sp, scan_last, sp->cols);
+    pass_columns(sh, last, sp, scan_last, true, sp->cols);
     if (q->count_only) {
         TRY(pqps_filter_count(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, L->count_dev, stream), "count filter");
     } else if (q->n_probes > 0) {
@@ -456,7 +472,7 @@ static int issue_on_shard(struct query *q, int s) {
         }
         sp->pred = &last->pred;
         sp->n_cols = last->pred.n_columns;
-        pass_columns(sh, last, NULL, true, sp->cols);
+        pass_columns(sh, last, NULL, true, true, sp->cols);
         if (q->count_only)
             TRY(pqps_exchange_count(q->t->xch, sp->cols, sp->n_cols, sh->n_rows, sp->pred, (uint32_t)q->lane, NULL), "count exchange");
         else
@@ -467,7 +483,7 @@ static int issue_on_shard(struct query *q, int s) {
     if (q->lane >= 0 && single) {
         sp->pred = &last->pred;
         sp->n_cols = last->pred.n_columns;
-        pass_columns(sh, last, NULL, true, sp->cols);
+        pass_columns(sh, last, NULL, true, true, sp->cols);
         if (q->count_only)
             TRY(pqps_qstream_count_slot(sh->qs, (uint32_t)q->lane, sp->cols, sp->n_cols, sh->n_rows, sp->pred, L->count_dev, NULL), "count filter");
         else
@@ -908,7 +924,7 @@ static int fused_issue(struct query *q, fused_call call, void *arg) {
         if (q->lane >= 0 && pqps_qstream_lane(sh->qs, (uint32_t)q->lane, sh->n_rows, NULL, &ctx, &stream) != PQPS_OK) { rc = engine_error("query lane"); break; }
         sp->pred = &last->pred;
         sp->n_cols = last->pred.n_columns;
-        pass_columns(sh, last, NULL, true, sp->cols);
+        pass_columns(sh, last, NULL, true, false, sp->cols);
         rc = call(q, s, ctx, stream, arg);
         /* marked even after a failed call: the lane must not be handed on while a launch of this query runs */
         if (q->lane >= 0 && pqps_qstream_mark(sh->qs, (uint32_t)q->lane) != PQPS_OK && rc == 0) rc = engine_error("query lane");
@@ -4206,7 +4222,7 @@ static int row_flags(struct query *q, size_t n, uint8_t **flags_dev, uint8_t *fl
         if (rc != 0) break;
         sp->pred = &last->pred;
         sp->n_cols = last->pred.n_columns;
-        pass_columns(sh, last, sp, true, sp->cols);
+        pass_columns(sh, last, sp, true, true, sp->cols);
         if (rc == 0 && pqps_malloc(sh->ctx, sh->capacity_rows, (void **)&flags_dev[s]) != PQPS_OK) rc = engine_error("flag allocation");
         if (rc == 0 && pqps_filter_flags(sh->ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, flags_dev[s], sh->own.count_dev, NULL) != PQPS_OK)
             rc = engine_error("flag filter");
@@ -4315,7 +4331,7 @@ static int update_fused(struct query *q, const struct hipAssignment *a, int n, u
         struct hipTable *sh = hipTableShard(q->t, s);
         pqps_column cols[PQPS_MAX_COLUMNS];
         pqps_assign_target targets[PQPS_MAX_COLUMNS];
-        pass_columns(sh, pass, NULL, true, cols);
+        pass_columns(sh, pass, NULL, true, false, cols);
         const int k = updateTargetsHIP(sh, a, n, targets);
         if (k == 0) {                                               /* nothing to store: the rows are counted all the same */
             if (pqps_filter_count(sh->ctx, cols, pass->pred.n_columns, sh->n_rows, &pass->pred, sh->own.count_dev, NULL) != PQPS_OK)

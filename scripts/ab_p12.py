@@ -1,0 +1,118 @@
+#!/usr/bin/env python3
+"""Same-process A/B of the S1 scan over the u16 user_name column against its 12-bit packed copy (PQPS_WIDTH_P12).
+
+    python scripts/ab_p12.py --rows 100000000 --libs head=parallel-query-processing-system_amd/libpqps_hip.so
+
+The same codes go in as a u16 column and as a packed copy; both are scanned with the plane of sudo_used behind them --
+(2,B,0) against (P,B,0) -- as ID list and as COUNT(*), by every build / setting named in --libs, launches interleaved,
+device time from the HIP events on the dispatch.  `--copies 2` (the default) alternates two tables, so nothing a launch
+reads was left in the Infinity Cache by the launch before it.
+
+    --libs name=path[@VAR=value ...],...
+
+A build reads its environment switches once, at its first launch: `@VAR=value` sets them in the process environment for that
+build's warm-up launches, so several settings of ONE switch can be compared in one process on one table -- each from a copy of
+the library file of its own (a path loaded twice is one library).  PQPS_NT_LOADS is read by every build, PQPS_VALU_CHAIN by
+development builds (make libpqps_hip_dev.so); steps per wave are compile time (DEVFLAGS=-DPQPS_MULTI_BYTES=3)."""
+import argparse
+import ctypes as C
+import os
+import pathlib
+import statistics
+import sys
+
+ROOT = pathlib.Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "scripts"))
+import bench  # noqa: E402
+import ab_libs  # noqa: E402
+
+S1 = bench.QUERIES["S1"][0]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=100_000_000)
+    ap.add_argument("--libs", required=True)
+    ap.add_argument("--rounds", type=int, default=6)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--copies", type=int, default=2)
+    args = ap.parse_args()
+    pq, _ = bench.load_pkg()
+    ctx = pq.Context(0)
+    n = args.rows
+    padded = (n + pq.TILE_ROWS - 1) // pq.TILE_ROWS * pq.TILE_ROWS
+    shapes = {"u16": [], "p12": []}
+    pred = None
+    for _ in range(max(1, args.copies)):
+        t = pq.SyntheticTable(ctx, n, seed=0x5EED, columns=["user_name", "sudo_used"])
+        pred, ids = pq.compile_where(t.schema, S1)
+        assert [pq.COLUMNS[i] for i in ids] == ["user_name", "sudo_used"], ids
+        plane, packed = ctx.malloc(padded // 8), ctx.malloc(padded // 2 * 3)
+        pq.check(pq.lib().pqps_pack_bits(ctx.h, t.ptr["sudo_used"], n, plane, 0, padded // 8, None), "pqps_pack_bits")
+        ctx.pack12(t.ptr["user_name"], n, packed, 0, padded)
+        ctx.sync()
+        shapes["u16"].append(pq.column_array([(t.ptr["user_name"], 2), (plane, pq.WIDTH_BITS)]))
+        shapes["p12"].append(pq.column_array([(packed, pq.WIDTH_P12), (plane, pq.WIDTH_BITS)]))
+    bytes_per_row = {"u16": 2.125, "p12": 1.625}
+    ids_dev, cnt = ctx.malloc(4 * max(n // 2, 1024)), ctx.malloc(64)
+    turn = [0]
+
+    def run(L, h, shape, mode):
+        cols = shapes[shape][turn[0] % len(shapes[shape])]
+        turn[0] += 1
+        if mode == "ids":
+            rc = L.pqps_filter_scan(h, cols, 2, n, 0, C.byref(pred), ids_dev, n // 2, cnt, None)
+        else:
+            rc = L.pqps_filter_count(h, cols, 2, n, C.byref(pred), cnt, None)
+        if rc != 0:
+            sys.exit(L.pqps_last_error().decode())
+
+    builds = []
+    for spec in args.libs.split(","):
+        name, rest = spec.split("=", 1)
+        path, *env = rest.split("@")
+        L = ab_libs.bind(ROOT / path, pq)
+        L.pqps_last_kernel.restype = C.c_char_p
+        h = C.c_void_p()
+        if L.pqps_ctx_create(0, C.byref(h)) != 0:
+            sys.exit(f"{name}: {L.pqps_last_error().decode()}")
+        for kv in env:                                               # read once, by this build's first launches below
+            k, v = kv.split("=")
+            os.environ[k] = v
+        kernels = {}
+        for shape in shapes:
+            for mode in ("ids", "count"):
+                for _ in range(2):
+                    run(L, h, shape, mode)
+                kernels[shape, mode] = L.pqps_last_kernel().decode()
+        L.pqps_ctx_sync(h, None)
+        for kv in env:
+            del os.environ[kv.split("=")[0]]
+        builds.append((name, L, h, kernels))
+    print(f"rows={n:,}  copies={args.copies}  rounds={args.rounds} x reps={args.reps}", flush=True)
+    for mode in ("ids", "count"):
+        times = {(b[0], s): [] for b in builds for s in shapes}
+        for _ in range(args.rounds):
+            for name, L, h, _k in builds:
+                for shape in shapes:
+                    L.pqps_ctx_set_timing(h, 1)
+                    for _ in range(args.reps):
+                        run(L, h, shape, mode)
+                    ev, tot, k = C.c_double(), C.c_double(), C.c_int()
+                    L.pqps_ctx_kernel_time(h, C.byref(ev), C.byref(tot), C.byref(k))
+                    L.pqps_ctx_set_timing(h, 0)
+                    times[name, shape].append(tot.value / k.value * 1e3)
+        m = C.c_uint64()
+        ctx.download(C.byref(m), cnt, 8)
+        for name, _L, _h, kernels in builds:
+            for shape in shapes:
+                t = times[name, shape]
+                med = statistics.median(t)
+                byts = n * bytes_per_row[shape] + (4 * m.value if mode == "ids" else 8)
+                print(f"S1/{mode} {name:>10} {shape}: {med:6.1f} us [{min(t):.1f}..{max(t):.1f}]  {byts / (med * 1e-6) / 8e12:.3f} of 8 TB/s"
+                      f"  ({m.value:,} matches)  {kernels[shape, mode]}", flush=True)
+
+
+if __name__ == "__main__":
+    main()
