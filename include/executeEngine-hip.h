@@ -772,6 +772,29 @@ int hipEngineFreeSetHIP(struct engineS *engine, struct hipValueSet *set);
  * SURVEY.md fact 10): scan-mode count of matching rows, no ID list. */
 long long executeQueryCountHIP(struct engineS *engine, struct whereClauseS *whereClause);
 
+/* SEVERAL COUNT(*) OVER ONE TABLE STATE, AS FEW SCANS AS THEY NEED (SQL: SELECT COUNT(*) FILTER (WHERE a), COUNT(*) FILTER
+ * (WHERE b), ...; no counterpart in the reference).  counts[i] is exactly what executeQueryCountHIP(engine, whereClauses[i])
+ * returns on the same table state, for every clause the engine accepts, a NULL clause (every row) included.
+ *   FUSED   a clause that binds to ONE scan pass of at most PQPS_TT_LEAVES comparisons: hipCountManyPack (hipPredicate.h) packs
+ *           these, in the caller's order, into batches of up to HIP_COUNT_MANY_BATCH clauses that share their comparisons and
+ *           columns, and every batch is one pqps_filter_count_many launch per shard -- each column of the batch read once.
+ *   CONSTANT  a clause that folds to true or false (a single-valued column, an empty IN list): answered from the row count,
+ *           no launch.
+ *   ALONE   every other clause -- more passes (over 32 comparisons, a fragmented LIKE / IN, IN SET) or 7 and more
+ *           comparisons -- runs through the COUNT path of executeQueryCountHIP, one after the other on the call's lane.
+ * (COUNT(*) is the scan-mode count whatever indexes the engine has -- executeQueryCountHIP never probes one -- so an indexed
+ * attribute does not keep a clause out of a batch.)  Nothing is refused for its shape.
+ * A reader like COUNT: the table locked shared, ONE lane, one bind per clause; the batches of all shards are issued under the
+ * issue lock before the first wait, the shards' counts summed on the host.  From a thread that holds a ticket it behaves as
+ * the other readers do.
+ * Returns numQueries (0 for an empty list, `counts` not read), or -1 with `counts` untouched and the reason on stderr for: a
+ * NULL engine or `counts`, numQueries < 0, a NULL `whereClauses` with numQueries > 0, a clause that fails to compile (a
+ * malformed IN list, a stale set), an engine joined across ranks (as the grouped calls refuse it), a refused lane, a failed
+ * device call. */
+#define HIP_COUNT_MANY_BATCH 16
+#define HIP_COUNT_MANY_MIN_BATCH 2      /* a batch of fewer clauses runs them ALONE: one clause is faster through COUNT's specialised kernels */
+long long executeQueryCountManyHIP(struct engineS *engine, struct whereClauseS *const *whereClauses, int numQueries, long long *counts);
+
 #ifdef __cplusplus
 }
 #endif

@@ -280,6 +280,36 @@ long long hipGroupTopOrder(const uint64_t *bins, const uint64_t *counts, const u
                            const uint64_t *max_images, uint64_t n_groups, int value_kind, int order_by, int descending,
                            long long limit, uint64_t *order);
 
+/* THE BATCHES OF "SEVERAL COUNTS, ONE SCAN" (executeQueryCountManyHIP).  Packs the one-pass predicates of n queries, in the
+ * caller's order and greedily, into batches that pqps_filter_count_many takes one launch each; pure host code.
+ *   INPUT   queries[i].pred / .column_ids: a filter pass as hipCompileWherePlan leaves it in a one-pass plan (leaves sorted
+ *           by column slot, the jump program in evaluation order, column_ids[slot] = HIPCOL_* id).  max_queries: queries per
+ *           batch, 1 .. PQPS_COUNT_MANY_MAX.
+ *   LEAVES  a batch's leaves are the DISTINCT windows (column, lo, span) of its queries, sorted by (column slot, lo, span).
+ *           Polarity is not part of a leaf's identity: `negate` is 0 in the batch, and a window and its complement -- again
+ *           a window in the kernels' arithmetic, 64 bits for command_id and 32 for every other column -- are ONE leaf, the
+ *           one with the smaller span (`risk_level > 3`, `risk_level <= 3` and a negated `risk_level <= 3` share it).  A
+ *           comparison that is the complement of its leaf becomes a step with on_true and on_false swapped.
+ *   PROGRAM query[p] of the batch: the predicate's steps in evaluation order, step s = (leaf slot of the batch, on_true,
+ *           on_false), targets as in pqps_predicate.
+ *   COLUMNS the union of the queries' columns, ascending HIPCOL_* id: batch.column_ids[slot], -1 behind n_columns.
+ *   CAPS    a query that would take the open batch over max_queries queries, PQPS_MAX_LEAVES distinct leaves or
+ *           PQPS_MAX_COLUMNS columns closes it and opens the next.
+ *   PLACE   place[i].batch >= 0: query i is query[place[i].position] of batches[place[i].batch];
+ *           HIPCOUNT_CONSTANT: n_leaves == 0, the answer is every row (place[i].constant = 1) or none (0), no launch;
+ *           HIPCOUNT_ALONE: more than PQPS_TT_LEAVES leaves, the caller runs it by the one-query COUNT.
+ *   `batches` has room for n entries (at least 1); *n_batches = the batches made.
+ * Returns 0, or -1 with the reason on stderr and every output untouched for: a NULL argument (queries may be NULL when n is
+ * 0), n < 0, max_queries outside 1 .. PQPS_COUNT_MANY_MAX, a query without pred or column_ids, more than PQPS_MAX_LEAVES
+ * leaves or PQPS_MAX_COLUMNS columns, a leaf whose column or a step whose leaf slot is out of range, leaves not sorted by
+ * column, a column slot without an id, a predicate whose jump targets do not go forward. */
+enum { HIPCOUNT_CONSTANT = -1, HIPCOUNT_ALONE = -2 };
+struct hipCountQuery { const pqps_predicate *pred; const int *column_ids; };
+struct hipCountBatch { pqps_count_many prog; int column_ids[PQPS_MAX_COLUMNS]; };
+struct hipCountPlace { int batch, position, constant; };
+int hipCountManyPack(const struct hipCountQuery *queries, int n, int max_queries, struct hipCountBatch *batches, int *n_batches,
+                     struct hipCountPlace *place);
+
 /* The number of values[0 .. count) (ascending in strcmp order) below `text`: its code when it is in the dictionary
  * (*present = 1), the rank it is inserted at otherwise (*present = 0). */
 int hipDictionaryRank(const char *const *values, int count, const char *text, int *present);

@@ -874,6 +874,39 @@ int pqps_filter_assign(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, 
 int pqps_assign_flags(pqps_ctx *ctx, const uint8_t *flags, uint64_t n_rows, const pqps_assign_target *targets, uint32_t n_targets,
                       void *stream);
 
+/* ---- several COUNT(*) WHEREs answered by one scan -------------------------------------------------------------------------
+ * No counterpart in the reference (SQL: SELECT COUNT(*) FILTER (WHERE a), COUNT(*) FILTER (WHERE b), ...).  ONE scan of rows
+ * [0, n_rows) of `cols` -- the union of the queries' columns, each loaded once per 1024-row step -- answers up to
+ * PQPS_COUNT_MANY_MAX queries: counts_dev[i] (device, n_queries u64, written whole by the call: no zeroing by the caller)
+ * = the exact number of rows query i accepts.
+ *   leaf[0 .. n_leaves)    the DISTINCT window tests of all queries, sorted by `column`, `negate` 0 (pqps_leaf arithmetic);
+ *                          each is evaluated once per row whatever the number of queries that use it
+ *   query[i]               a jump program as pqps_predicate carries it, in evaluation order: step s tests leaf slot leaf[s]
+ *                          and goes to on_true[s] / on_false[s] -- a LATER step, PQPS_ACCEPT or PQPS_REJECT.  A negated
+ *                          comparison is a step with the two targets swapped.  n_steps == 0: the constant `constant` (0 / 1).
+ * Columns: 1, 2, 4 or 8 bytes or a bit plane, 16-byte aligned, readable up to n_rows rounded up to PQPS_STEP_ROWS as
+ * pqps_filter_scan reads them; a PQPS_WIDTH_P12 column is PQPS_EINVAL (that form stays the one-query scan's).
+ * PQPS_EINVAL, nothing launched: a NULL argument; n_queries 0 or above PQPS_COUNT_MANY_MAX; n_leaves above PQPS_MAX_LEAVES;
+ * n_columns != n_cols or above PQPS_MAX_COLUMNS; a leaf whose column is out of range, leaves not sorted by column, a leaf
+ * with `negate` set; n_steps above PQPS_TT_LEAVES; a step's leaf slot out of range; a jump target that is neither a later
+ * step of the query nor accept / reject; `constant` above 1.
+ * One scan launch (count_many_scan_kernel, the persistent grid of the fused scans) and, behind it, the one-workgroup
+ * reduction of the workgroups' totals, as a COUNT has; n_rows == 0 launches the reduction only.  Asynchronous on `stream`.
+ * The context's timing recorder records the call like a COUNT's: ONE record per call. */
+#define PQPS_COUNT_MANY_MAX 16u
+typedef struct pqps_count_query {
+    uint32_t n_steps;
+    uint8_t leaf[PQPS_TT_LEAVES], on_true[PQPS_TT_LEAVES], on_false[PQPS_TT_LEAVES];
+    uint8_t constant;
+} pqps_count_query;
+typedef struct pqps_count_many {
+    uint32_t n_queries, n_leaves, n_columns;
+    pqps_leaf leaf[PQPS_MAX_LEAVES];
+    pqps_count_query query[PQPS_COUNT_MANY_MAX];
+} pqps_count_many;
+int pqps_filter_count_many(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows,
+                           const pqps_count_many *prog, uint64_t *counts_dev /* n_queries u64 */, void *stream);
+
 /* ---- batch INSERT: dictionary codes through a lookup table ----------------------------------------------------------------
  * No counterpart in the reference.  dst[i] = lut[src[i]] for i < n: what is left for the device when a batch of rows merges
  * its dictionary into a column's -- ONE pass per column and shard whatever the number of new strings (pqps_bump_codes is one

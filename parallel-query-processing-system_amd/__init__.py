@@ -288,6 +288,37 @@ class AssignTarget(C.Structure):
     _fields_ = [("data", C.c_void_p), ("width", C.c_uint32), ("value", C.c_uint64)]
 
 
+COUNT_MANY_MAX = 16                                          # PQPS_COUNT_MANY_MAX
+COUNT_CONSTANT, COUNT_ALONE = -1, -2                         # HIPCOUNT_* (include/hipPredicate.h)
+
+
+class CountQuery(C.Structure):
+    """pqps_count_query (include/pqps_hip.h)."""
+    _fields_ = [("n_steps", C.c_uint32), ("leaf", C.c_uint8 * TT_LEAVES), ("on_true", C.c_uint8 * TT_LEAVES),
+                ("on_false", C.c_uint8 * TT_LEAVES), ("constant", C.c_uint8)]
+
+
+class CountMany(C.Structure):
+    """pqps_count_many (include/pqps_hip.h)."""
+    _fields_ = [("n_queries", C.c_uint32), ("n_leaves", C.c_uint32), ("n_columns", C.c_uint32),
+                ("leaf", Leaf * MAX_LEAVES), ("query", CountQuery * COUNT_MANY_MAX)]
+
+
+class CountPackQuery(C.Structure):                           # struct hipCountQuery
+    _fields_ = [("pred", C.POINTER(Predicate)), ("column_ids", C.POINTER(C.c_int))]
+
+
+class CountBatch(C.Structure):                               # struct hipCountBatch
+    _fields_ = [("prog", CountMany), ("column_ids", C.c_int * MAX_COLUMNS)]
+
+
+class CountPlace(C.Structure):                               # struct hipCountPlace
+    _fields_ = [("batch", C.c_int), ("position", C.c_int), ("constant", C.c_int)]
+
+
+assert C.sizeof(CountQuery) == 24 and C.sizeof(CountMany) == 16 + 24 * MAX_LEAVES + 24 * COUNT_MANY_MAX
+
+
 class SynthCols(C.Structure):
     _fields_ = [
         ("command_id", C.c_void_p), ("exit_code", C.c_void_p), ("user_id", C.c_void_p),
@@ -457,6 +488,7 @@ def lib():
     L.pqps_download.argtypes = [vp, vp, vp, C.c_size_t, vp]
     L.pqps_filter_scan.argtypes = [vp, C.POINTER(Column), u32, u64, u32, C.POINTER(Predicate), vp, u64, vp, vp]
     L.pqps_filter_count.argtypes = [vp, C.POINTER(Column), u32, u64, C.POINTER(Predicate), vp, vp]
+    L.pqps_filter_count_many.argtypes = [vp, C.POINTER(Column), u32, u64, C.POINTER(CountMany), vp, vp]
     L.pqps_filter_flags.argtypes = [vp, C.POINTER(Column), u32, u64, C.POINTER(Predicate), vp, vp, vp]
     L.pqps_filter_gather.argtypes = [vp, C.POINTER(Column), u32, vp, vp, u64, u32, C.POINTER(Predicate), vp, u64, vp, vp]
     L.pqps_index_build.argtypes = [vp, C.POINTER(Column), u64, C.c_int, vp, vp, vp]
@@ -578,6 +610,10 @@ def lib():
     L.hipEngineShards.argtypes = [E, C.POINTER(C.c_ulonglong), C.c_int]
     L.executeQueryCountHIP.restype = C.c_longlong
     L.executeQueryCountHIP.argtypes = [E, W]
+    L.executeQueryCountManyHIP.restype = C.c_longlong
+    L.executeQueryCountManyHIP.argtypes = [E, C.POINTER(W), C.c_int, C.POINTER(C.c_longlong)]
+    L.hipCountManyPack.argtypes = [C.POINTER(CountPackQuery), C.c_int, C.c_int, C.POINTER(CountBatch), C.POINTER(C.c_int),
+                                   C.POINTER(CountPlace)]
     L.executeQueryGroupCountHIP.restype = C.POINTER(GroupResult)
     L.executeQueryGroupCountHIP.argtypes = [E, C.c_char_p, W]
     L.freeGroupResultHIP.argtypes = [C.POINTER(GroupResult)]
@@ -923,6 +959,38 @@ def group_head_sort(ctx, key_col, key_signed, descending, group_col, group_signe
     check(lib().pqps_group_head_sort(ctx.h, ref(key_col), int(key_signed), int(descending), ref(group_col), int(group_signed), ids_dev, n,
                                      id_base, limit, int(repeats), out_ids_dev, out_keys_dev, C.byref(kept), stream), "pqps_group_head_sort")
     return int(kept.value)
+
+
+def count_many_pack(queries, max_queries=COUNT_MANY_MAX):
+    """hipCountManyPack: queries = [(Predicate, [column id per slot]), ...], one-pass predicates as compile_plan leaves them.
+    -> (batches, places): batches = [(CountMany, [column id per slot of the batch]), ...]; places[i] = (batch, position) of
+    query i, (COUNT_CONSTANT, truth value) or (COUNT_ALONE, 0).  Raises ValueError where the packer refuses (reason on
+    stderr)."""
+    n = len(queries)
+    arr = (CountPackQuery * max(1, n))()
+    keep = []
+    for i, (pred, ids) in enumerate(queries):
+        cid = (C.c_int * MAX_COLUMNS)(*([-1] * MAX_COLUMNS))
+        for k, c in enumerate(ids):
+            cid[k] = c
+        keep.append(cid)
+        arr[i].pred = C.pointer(pred)
+        arr[i].column_ids = C.cast(cid, C.POINTER(C.c_int))
+    batches = (CountBatch * max(1, n))()
+    places = (CountPlace * max(1, n))()
+    nb = C.c_int(0)
+    if lib().hipCountManyPack(arr, n, max_queries, batches, C.byref(nb), places) != 0:
+        raise ValueError("hipCountManyPack refused (reason on stderr)")
+    out = []
+    for b in range(nb.value):
+        prog = CountMany()
+        C.memmove(C.byref(prog), C.byref(batches[b].prog), C.sizeof(CountMany))
+        out.append((prog, list(batches[b].column_ids[:prog.n_columns])))
+    where = []
+    for i in range(n):
+        pl = places[i]
+        where.append((pl.batch, pl.constant if pl.batch == COUNT_CONSTANT else pl.position if pl.batch >= 0 else 0))
+    return out, where
 
 
 def head_merge(shards, limit):
@@ -1433,6 +1501,22 @@ class HipEngine:
     def count(self, chain):
         wl = WhereList(chain)
         return lib().executeQueryCountHIP(self.e, wl.ptr)
+
+    def count_many(self, chains):
+        """executeQueryCountManyHIP: -> [COUNT(*) of every chain (None: every row)], each what count(chain) gives on the same
+        table state; the chains that bind to one scan pass of at most 6 comparisons share their scans, 16 to a launch.
+        Raises PqpsError where the engine refuses the call (reason on stderr)."""
+        lists = [WhereList(chain) for chain in chains]
+        n = len(lists)
+        W = C.POINTER(WhereClause)
+        ptrs = (W * max(1, n))()
+        for i, wl in enumerate(lists):
+            if wl.head is not None:
+                ptrs[i] = C.pointer(wl.head)
+        counts = (C.c_longlong * max(1, n))()
+        if lib().executeQueryCountManyHIP(self.e, ptrs, n, counts) != n:
+            raise PqpsError("executeQueryCountManyHIP failed")
+        return list(counts[:n])
 
     def value_set(self, column, chain=None, having=None):
         """hipEngineCreateSetHIP: the ValueSet of the values of `column` over the rows for which `chain` is true (None: every

@@ -33,6 +33,7 @@
 #include "distinct_kernels.hpp"
 #include "group_pair_kernels.hpp"
 #include "assign_kernels.hpp"
+#include "count_many_kernels.hpp"
 #include "remap_kernels.hpp"
 #include "radix_sort.hpp"
 
@@ -4583,6 +4584,87 @@ int pqps_assign_flags(pqps_ctx *ctx, const uint8_t *flags, uint64_t n_rows, cons
     hipLaunchKernelGGL(assign_flags_kernel, dim3(fused_grid(ctx, n_rows, 0)), dim3(kBlock), 0, pick_stream(ctx, stream), g);
     HIP_TRY(hipGetLastError());
     return PQPS_OK;
+}
+
+// ---- several COUNT(*) WHEREs in one scan (count_many_kernels.hpp) ------------------------------------------------------
+int pqps_filter_count_many(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows,
+                           const pqps_count_many *prog, uint64_t *counts_dev, void *stream) {
+    if (!ctx || !prog || !counts_dev) return fail(PQPS_EINVAL, "ctx/prog/counts is NULL");
+    if (prog->n_queries == 0 || prog->n_queries > PQPS_COUNT_MANY_MAX) return fail(PQPS_EINVAL, "%u queries: 1 .. %u", prog->n_queries, PQPS_COUNT_MANY_MAX);
+    if (prog->n_leaves > PQPS_MAX_LEAVES) return fail(PQPS_EINVAL, "too many leaves: %u", prog->n_leaves);
+    if (n_cols > PQPS_MAX_COLUMNS) return fail(PQPS_EINVAL, "too many columns: %u", n_cols);
+    if (prog->n_columns != n_cols) return fail(PQPS_EINVAL, "the queries use %u columns, call passes %u", prog->n_columns, n_cols);
+    if (n_cols && !cols) return fail(PQPS_EINVAL, "column array is NULL");
+    CountManyArgs g;
+    memset(&g, 0, sizeof g);
+    uint64_t row_eighths = 0;
+    for (uint32_t c = 0; c < n_cols; c++) {
+        if (cols[c].width == PQPS_WIDTH_P12) return fail(PQPS_EINVAL, "column %u: a 12-bit packed column is read by plain scans only", c);
+        char what[24];
+        snprintf(what, sizeof what, "column %u", c);
+        uint32_t wl = 0;
+        const int rc = column_width_code(what, &cols[c], true, true, true, &wl);
+        if (rc) return rc;
+        g.col[c] = cols[c].data;
+        g.width_log2[c] = wl;
+        row_eighths += cols[c].width == PQPS_WIDTH_BITS ? 1u : 8u * cols[c].width;
+    }
+    uint32_t prev = 0;
+    for (uint32_t k = 0; k < prog->n_leaves; k++) {
+        const pqps_leaf &l = prog->leaf[k];
+        if (l.column >= n_cols) return fail(PQPS_EINVAL, "leaf %u: column %u out of range", k, l.column);
+        if (l.column < prev) return fail(PQPS_EINVAL, "leaves must be sorted by column");
+        prev = l.column;
+        if (l.negate) return fail(PQPS_EINVAL, "leaf %u: a shared leaf is never negated (swap the step's targets)", k);
+        g.lo[k] = l.lo;
+        g.span[k] = l.span;
+    }
+    for (uint32_t c = 0, k = 0; c <= n_cols; c++) {
+        while (k < prog->n_leaves && prog->leaf[k].column < c) k++;
+        g.leaf_begin[c] = c == n_cols ? prog->n_leaves : k;
+    }
+    for (uint32_t q = 0; q < prog->n_queries; q++) {
+        const pqps_count_query &p = prog->query[q];
+        if (p.n_steps > PQPS_TT_LEAVES) return fail(PQPS_EINVAL, "query %u: %u steps, at most %d", q, p.n_steps, PQPS_TT_LEAVES);
+        if (p.constant > 1) return fail(PQPS_EINVAL, "query %u: constant must be 0/1", q);
+        uint4 w = make_uint4(p.n_steps | ((uint32_t)p.constant << 8), 0, 0, 0);
+        bool linear = p.n_steps > 0;
+        for (uint32_t s = 0; s < p.n_steps; s++) {
+            if (p.leaf[s] >= prog->n_leaves) return fail(PQPS_EINVAL, "query %u step %u: leaf slot %u out of range", q, s, p.leaf[s]);
+            uint32_t jump[2] = {p.on_true[s], p.on_false[s]};
+            for (uint32_t &t : jump) {
+                if (t == PQPS_ACCEPT) t = kCmAccept;
+                else if (t == PQPS_REJECT) t = kCmReject;
+                else if (t <= s || t >= p.n_steps) return fail(PQPS_EINVAL, "query %u step %u: jump targets must point forward", q, s);
+                else if (t != s + 1) linear = false;
+            }
+            w.y |= (uint32_t)p.leaf[s] << (5 * s);
+            w.z |= jump[0] << (3 * s);
+            w.w |= jump[1] << (3 * s);
+        }
+        if (linear) w.x |= kCmLinear;
+        g.prog[q][0] = w.x; g.prog[q][1] = w.y; g.prog[q][2] = w.z; g.prog[q][3] = w.w;
+    }
+    hipStream_t s = pick_stream(ctx, stream);
+    int rc = ensure_scratch(ctx, (n_rows + kStepRows - 1) / kStepRows);      // the partial slots
+    if (rc) return rc;
+    g.n_cols = n_cols;
+    g.n_leaves = prog->n_leaves;
+    g.n_queries = prog->n_queries;
+    g.n_rows = n_rows;
+    g.partials = ctx->partials;
+    g.streaming = is_streaming(n_rows * row_eighths / 8) ? 1u : 0u;
+    const bool nt = g.streaming != 0;
+    snprintf(g_kernel, sizeof g_kernel, "count_many_scan_kernel<NT=%s>", nt ? "true" : "false");
+    hipEvent_t stop = nullptr;
+    if (n_rows) {
+        rc = fused_launch(ctx, nt ? count_many_scan_kernel<true> : count_many_scan_kernel<false>,
+                          fused_grid(ctx, n_rows, sizeof(uint16_t) * PQPS_MAX_LEAVES * kBlock), 0, s, g, &stop);
+        if (rc) return rc;
+    }
+    rc = launch_stop(count_many_reduce_kernel, dim3(1), 0, s, stop, ctx->partials, counts_dev, g.n_queries);
+    fused_close(ctx, stop, false);
+    return rc;
 }
 
 // ---- batch INSERT: dictionary codes through a lookup table (remap_kernels.hpp) ----------------------------------------

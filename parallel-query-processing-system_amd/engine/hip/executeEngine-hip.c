@@ -983,6 +983,122 @@ static int shard_reduce(struct query *q, bool fused, const struct shard_reduce *
     return rc;
 }
 
+/* ---- several COUNT(*) in as few scans as they need (include/executeEngine-hip.h) ---------------------------------- */
+
+/* The batches of one call: batch b is `pass[b]` to pass_columns (its columns; more comparisons than the specialised shapes
+ * take, so that sudo_used is read from its plane in every slot but a lone one) and one launch into buf[s] + b * 16. */
+struct count_many_call {
+    const struct hipCountBatch *batch;
+    const struct hipPass *pass;
+    int n_batches;
+    uint64_t *buf[HIP_MAX_SHARDS];
+};
+
+static int count_many_fused_call(struct query *q, int s, pqps_ctx *ctx, void *stream, void *arg) {
+    const struct count_many_call *c = arg;
+    const struct hipTable *sh = hipTableShard(q->t, s);
+    for (int b = 0; b < c->n_batches; b++) {
+        pqps_column cols[PQPS_MAX_COLUMNS];
+        if (c->batch[b].prog.n_queries < HIP_COUNT_MANY_MIN_BATCH) continue;       /* (its clauses run alone) */
+        pass_columns(sh, &c->pass[b], NULL, true, false, cols);
+        TRY(pqps_filter_count_many(ctx, cols, c->batch[b].prog.n_columns, sh->n_rows, &c->batch[b].prog,
+                                   c->buf[s] + (size_t)b * PQPS_COUNT_MANY_MAX, stream), "count many");
+    }
+    return 0;
+}
+
+long long executeQueryCountManyHIP(struct engineS *engine, struct whereClauseS *const *whereClauses, int numQueries, long long *counts) {
+    if (!engine || !engine->record_block || !counts || numQueries < 0 || (numQueries && !whereClauses)) {
+        fprintf(stderr, "HIP engine: count many: NULL engine, clauses or counts, or a negative number of clauses\n");
+        return -1;
+    }
+    if (numQueries == 0) return 0;
+    struct hipTable *t = engine->record_block;
+    if (t->xch) { fprintf(stderr, "HIP engine: several counts in one scan are not exchanged across ranks\n"); return -1; }
+    struct query qs, *q = &qs;
+    if (!query_open(engine, q)) return -1;
+    const size_t n = (size_t)numQueries;
+    struct hipPlan *plans = calloc(n, sizeof *plans);
+    bool *bound = calloc(n, sizeof *bound);
+    int *fused_of = malloc(n * sizeof *fused_of);                   /* clause i is queries[fused_of[i]] of the packer, or -1: alone */
+    struct hipCountQuery *queries = malloc(n * sizeof *queries);
+    struct hipCountPlace *place = malloc(n * sizeof *place);
+    struct hipCountBatch *batches = malloc(n * sizeof *batches);
+    long long *answer = malloc(n * sizeof *answer);
+    struct hipPass *passes = NULL;
+    struct count_many_call call;
+    memset(&call, 0, sizeof call);
+    int rc = plans && bound && fused_of && queries && place && batches && answer ? 0 : oom();
+    int n_fused = 0, n_batches = 0;
+    for (size_t i = 0; i < n && rc == 0; i++) {                     /* one bind per clause */
+        if (bind_where(t, whereClauses[i], &plans[i]) != 0) { rc = -1; break; }
+        bound[i] = true;
+        fused_of[i] = -1;
+        if (plans[i].n_passes != 1 || plans[i].pass[0].member) continue;
+        queries[n_fused].pred = &plans[i].pass[0].pred;
+        queries[n_fused].column_ids = plans[i].pass[0].column_ids;
+        fused_of[i] = n_fused++;
+    }
+    if (rc == 0 && hipCountManyPack(queries, n_fused, HIP_COUNT_MANY_BATCH, batches, &n_batches, place) != 0) rc = -1;
+    uint64_t rows = 0;
+    for (int s = 0; s < q->n_shards; s++) rows += hipTableShard(t, s)->n_rows;
+    if (rc == 0 && n_batches) {
+        passes = calloc((size_t)n_batches, sizeof *passes);
+        if (!passes) rc = oom();
+        for (int b = 0; b < n_batches && rc == 0; b++) {
+            passes[b].pred.n_columns = batches[b].prog.n_columns;
+            passes[b].pred.n_leaves = PQPS_MAX_LEAVES;
+            memcpy(passes[b].column_ids, batches[b].column_ids, sizeof passes[b].column_ids);
+        }
+        call.batch = batches;
+        call.pass = passes;
+        call.n_batches = n_batches;
+        const size_t bytes = (size_t)n_batches * PQPS_COUNT_MANY_MAX * sizeof(uint64_t);
+        for (int s = 0; s < q->n_shards && rc == 0; s++)
+            if (hipTableShard(t, s)->n_rows && pqps_malloc(hipTableShard(t, s)->ctx, bytes, (void **)&call.buf[s]) != PQPS_OK) rc = engine_error("count many buffer");
+        if (rc == 0) {
+            q->plan.n_passes = 1;                                   /* (fused_issue: the first batch as the pass; it fills q->sp, the call takes its own columns) */
+            q->plan.pass = passes;
+            rc = fused_issue(q, count_many_fused_call, &call);
+            q->plan.n_passes = 0;
+            q->plan.pass = NULL;
+        }
+    }
+    for (size_t i = 0; i < n && rc == 0; i++) answer[i] = 0;
+    uint64_t *host = rc == 0 && n_batches ? malloc((size_t)n_batches * PQPS_COUNT_MANY_MAX * sizeof *host) : NULL;
+    if (rc == 0 && n_batches && !host) rc = oom();
+    for (int s = 0; s < q->n_shards && rc == 0 && n_batches; s++) {
+        if (!call.buf[s]) continue;
+        if (pqps_download(lane_copy_ctx(q, s), host, call.buf[s], (size_t)n_batches * PQPS_COUNT_MANY_MAX * sizeof *host, NULL) != PQPS_OK) { rc = engine_error("count many download"); break; }
+        for (size_t i = 0; i < n; i++) {
+            if (fused_of[i] < 0 || place[fused_of[i]].batch < 0 || batches[place[fused_of[i]].batch].prog.n_queries < HIP_COUNT_MANY_MIN_BATCH) continue;
+            answer[i] += (long long)host[(size_t)place[fused_of[i]].batch * PQPS_COUNT_MANY_MAX + (size_t)place[fused_of[i]].position];
+        }
+    }
+    free(host);
+    for (size_t i = 0; i < n && rc == 0; i++) {
+        const int f = fused_of[i];
+        if (f >= 0 && place[f].batch >= 0 && batches[place[f].batch].prog.n_queries >= HIP_COUNT_MANY_MIN_BATCH) continue;
+        if (f >= 0 && place[f].batch == HIPCOUNT_CONSTANT) { answer[i] = place[f].constant ? (long long)rows : 0; continue; }
+        /* alone, or in a batch too small to pay: the COUNT of executeQueryCountHIP with the plan bound above, on this call's lane */
+        struct query one;
+        query_init(&one, engine, t, q->lane, true);
+        one.plan = plans[i];
+        one.have_plan = true;
+        bound[i] = false;                                           /* (query_free frees the plan) */
+        if (query_issue_all(&one) != 0) { rc = -1; for (int s = 0; s < one.n_shards; s++) (void)wait_shard(&one, s); }
+        else if (query_await(&one) != 0) rc = -1;
+        answer[i] = (long long)one.total;
+        query_free(&one);
+    }
+    for (int s = 0; s < q->n_shards; s++) if (call.buf[s]) pqps_free(hipTableShard(t, s)->ctx, call.buf[s]);
+    for (size_t i = 0; plans && bound && i < n; i++) if (bound[i]) hipPlanFree(&plans[i]);
+    if (rc == 0) memcpy(counts, answer, n * sizeof *counts);
+    free(plans); free(bound); free(fused_of); free(queries); free(place); free(batches); free(answer); free(passes);
+    query_close(q);
+    return rc == 0 ? (long long)numQueries : -1;
+}
+
 /* ---- grouped COUNT(*) (include/executeEngine-hip.h) --------------------------------------------------------------- */
 
 static const int k_group_kind[HIPCOL_COUNT] = {

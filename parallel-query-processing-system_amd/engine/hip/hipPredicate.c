@@ -1346,3 +1346,154 @@ int hipOrderKeyPlan(const char *const *columns, const int *descending, int n_key
     *plan = p;
     return 0;
 }
+
+/* ---- the batches of several counts in one scan ------------------------------------------------------------------------ */
+
+/* the batch being filled: columns and leaves in order of arrival, the programs' leaf slots index leaf[] */
+struct count_open {
+    int n_queries, n_leaves, n_cols;
+    int col[PQPS_MAX_COLUMNS];                                   /* HIPCOL_* ids */
+    struct count_leaf { int col; uint64_t lo, span; } leaf[PQPS_MAX_LEAVES];
+    pqps_count_query query[PQPS_COUNT_MANY_MAX];
+};
+
+static int count_fail(int query, const char *what) {
+    if (query >= 0) fprintf(stderr, "HIP engine: count many: query %d: %s\n", query, what);
+    else fprintf(stderr, "HIP engine: count many: %s\n", what);
+    return -1;
+}
+
+static int count_leaf_cmp(const struct count_leaf *a, const struct count_leaf *b) {
+    if (a->col != b->col) return a->col < b->col ? -1 : 1;
+    if (a->lo != b->lo) return a->lo < b->lo ? -1 : 1;
+    if (a->span != b->span) return a->span < b->span ? -1 : 1;
+    return 0;
+}
+
+static int count_find_leaf(const struct count_leaf *leaf, int n, const struct count_leaf *key) {
+    for (int i = 0; i < n; i++) if (count_leaf_cmp(&leaf[i], key) == 0) return i;
+    return -1;
+}
+
+/* The leaf a comparison becomes in a batch, and whether the comparison is its complement.  The window test is taken in the
+ * arithmetic the kernels use -- 64 bits for command_id, 32 for every other column (pqps_leaf) -- where the complement of a
+ * window is again a window: of the two, the one with the smaller span (then the smaller lo) names the leaf. */
+static struct count_leaf count_canonical(int col, const pqps_leaf *l, int *negated) {
+    const uint64_t mask = col >= 0 && col < PQPS_MAX_COLUMNS && k_bucket_kind[col] == HIPKIND_U64 ? ~0ull : 0xFFFFFFFFull;
+    struct count_leaf c = { col, l->lo & mask, l->span & mask };
+    *negated = l->negate != 0;
+    if (c.span != mask) {                                        /* (the full window has no complement) */
+        const uint64_t lo = (c.lo + c.span + 1) & mask, span = (mask - c.span - 1) & mask;
+        if (span < c.span || (span == c.span && lo < c.lo)) { c.lo = lo; c.span = span; *negated = !*negated; }
+    }
+    return c;
+}
+
+static int count_find_col(const int *col, int n, int id) {
+    for (int i = 0; i < n; i++) if (col[i] == id) return i;
+    return -1;
+}
+
+/* the open batch, its columns ascending and its leaves sorted by (column slot, lo, span), into *out */
+static void count_close(const struct count_open *o, struct hipCountBatch *out) {
+    memset(out, 0, sizeof *out);
+    int col[PQPS_MAX_COLUMNS];
+    memcpy(col, o->col, sizeof col);
+    qsort(col, (size_t)o->n_cols, sizeof col[0], cmp_int);
+    for (int c = 0; c < PQPS_MAX_COLUMNS; c++) out->column_ids[c] = c < o->n_cols ? col[c] : -1;
+    int by_rank[PQPS_MAX_LEAVES], slot_of[PQPS_MAX_LEAVES];
+    for (int i = 0; i < o->n_leaves; i++) {                       /* insertion sort of the indices */
+        int j = i;
+        while (j > 0 && count_leaf_cmp(&o->leaf[by_rank[j - 1]], &o->leaf[i]) > 0) { by_rank[j] = by_rank[j - 1]; j--; }
+        by_rank[j] = i;
+    }
+    for (int r = 0; r < o->n_leaves; r++) {
+        const struct count_leaf *l = &o->leaf[by_rank[r]];
+        slot_of[by_rank[r]] = r;
+        out->prog.leaf[r].column = (uint32_t)count_find_col(col, o->n_cols, l->col);
+        out->prog.leaf[r].negate = 0;
+        out->prog.leaf[r].lo = l->lo;
+        out->prog.leaf[r].span = l->span;
+    }
+    out->prog.n_queries = (uint32_t)o->n_queries;
+    out->prog.n_leaves = (uint32_t)o->n_leaves;
+    out->prog.n_columns = (uint32_t)o->n_cols;
+    for (int q = 0; q < o->n_queries; q++) {
+        out->prog.query[q] = o->query[q];
+        for (uint32_t s = 0; s < o->query[q].n_steps; s++) out->prog.query[q].leaf[s] = (uint8_t)slot_of[o->query[q].leaf[s]];
+    }
+}
+
+int hipCountManyPack(const struct hipCountQuery *queries, int n, int max_queries, struct hipCountBatch *batches, int *n_batches,
+                     struct hipCountPlace *place) {
+    if (n < 0) return count_fail(-1, "a negative number of queries");
+    if ((n && !queries) || !batches || !n_batches || !place) return count_fail(-1, "NULL argument");
+    if (max_queries < 1 || max_queries > (int)PQPS_COUNT_MANY_MAX) return count_fail(-1, "queries per batch outside 1 .. 16");
+    for (int i = 0; i < n; i++) {
+        const pqps_predicate *p = queries[i].pred;
+        const int *ids = queries[i].column_ids;
+        if (!p || !ids) return count_fail(i, "no predicate or no column ids");
+        if (p->n_leaves > PQPS_MAX_LEAVES || p->n_columns > PQPS_MAX_COLUMNS) return count_fail(i, "too many leaves or columns");
+        uint32_t prev = 0;
+        for (uint32_t k = 0; k < p->n_leaves; k++) {
+            if (p->leaf[k].column >= p->n_columns) return count_fail(i, "a leaf's column is out of range");
+            if (p->leaf[k].column < prev) return count_fail(i, "leaves not sorted by column");
+            prev = p->leaf[k].column;
+            if (ids[p->leaf[k].column] < 0) return count_fail(i, "a column slot without an id");
+        }
+        for (uint32_t s = 0; s < p->n_leaves; s++) {
+            const uint8_t t = p->on_true[s], f = p->on_false[s];
+            if (p->order[s] >= p->n_leaves) return count_fail(i, "a step's leaf slot is out of range");
+            if ((t < PQPS_ACCEPT && (t <= s || t >= p->n_leaves)) || (f < PQPS_ACCEPT && (f <= s || f >= p->n_leaves)))
+                return count_fail(i, "jump targets must point forward");
+        }
+    }
+    struct count_open *o = calloc(1, sizeof *o);
+    if (!o) return count_fail(-1, "out of memory");
+    int nb = 0;
+    for (int i = 0; i < n; i++) {
+        const pqps_predicate *p = queries[i].pred;
+        const int *ids = queries[i].column_ids;
+        place[i].position = 0;
+        place[i].constant = 0;
+        if (p->n_leaves == 0) { place[i].batch = HIPCOUNT_CONSTANT; place[i].constant = (int)(p->truth & 1u); continue; }
+        if (p->n_leaves > PQPS_TT_LEAVES) { place[i].batch = HIPCOUNT_ALONE; continue; }
+        for (;;) {
+            /* what the query adds to the open batch */
+            struct count_leaf add_leaf[PQPS_TT_LEAVES];
+            int add_col[PQPS_TT_LEAVES], n_add_leaf = 0, n_add_col = 0;
+            for (uint32_t k = 0; k < p->n_leaves; k++) {
+                int negated;
+                const struct count_leaf l = count_canonical(ids[p->leaf[k].column], &p->leaf[k], &negated);
+                if (count_find_leaf(o->leaf, o->n_leaves, &l) < 0 && count_find_leaf(add_leaf, n_add_leaf, &l) < 0) add_leaf[n_add_leaf++] = l;
+                if (count_find_col(o->col, o->n_cols, l.col) < 0 && count_find_col(add_col, n_add_col, l.col) < 0) add_col[n_add_col++] = l.col;
+            }
+            const int fits = o->n_queries < max_queries && o->n_leaves + n_add_leaf <= PQPS_MAX_LEAVES && o->n_cols + n_add_col <= PQPS_MAX_COLUMNS;
+            if (!fits) {                                         /* (never an empty batch: six leaves fit every cap) */
+                count_close(o, &batches[nb++]);
+                memset(o, 0, sizeof *o);
+                continue;
+            }
+            for (int k = 0; k < n_add_leaf; k++) o->leaf[o->n_leaves++] = add_leaf[k];
+            for (int k = 0; k < n_add_col; k++) o->col[o->n_cols++] = add_col[k];
+            break;
+        }
+        pqps_count_query *q = &o->query[o->n_queries];
+        memset(q, 0, sizeof *q);
+        q->n_steps = p->n_leaves;
+        for (uint32_t s = 0; s < p->n_leaves; s++) {
+            const pqps_leaf *pl = &p->leaf[p->order[s]];
+            int negated;
+            const struct count_leaf l = count_canonical(ids[pl->column], pl, &negated);
+            q->leaf[s] = (uint8_t)count_find_leaf(o->leaf, o->n_leaves, &l);
+            q->on_true[s] = negated ? p->on_false[s] : p->on_true[s];
+            q->on_false[s] = negated ? p->on_true[s] : p->on_false[s];
+        }
+        place[i].batch = nb;
+        place[i].position = o->n_queries++;
+    }
+    if (o->n_queries) count_close(o, &batches[nb++]);
+    free(o);
+    *n_batches = nb;
+    return 0;
+}
