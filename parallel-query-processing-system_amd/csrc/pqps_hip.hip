@@ -29,7 +29,6 @@
 #include "topk_kernels.hpp"
 #include "order_multi_kernels.hpp"
 #include "first_kernels.hpp"
-#include "head_kernels.hpp"
 #include "distinct_kernels.hpp"
 #include "group_pair_kernels.hpp"
 #include "assign_kernels.hpp"
@@ -3870,7 +3869,7 @@ int pqps_sort_list_chain(pqps_ctx *ctx, const pqps_column *key_cols, const int *
     return list_sort_close(b, e, s, "ORDER BY chain sort");
 }
 
-// ---- the first row of every group (first_kernels.hpp) ----------------------------------------------------------------
+// ---- the first row and the first N rows of every group (first_kernels.hpp) -------------------------------------------
 // The key column as the top-K family checks it, the group column and the bins as the aggregates check theirs; an 8-byte key
 // needs `best`.
 static int check_first_cols(const pqps_column *key_col, const pqps_column *group_col, uint32_t n_bins, const uint64_t *best,
@@ -3884,21 +3883,28 @@ static int check_first_cols(const pqps_column *key_col, const pqps_column *group
     return column_width_code("group", group_col, plane_ok, false, plane_ok, gwl);
 }
 
-// out[n_bins] (and best[n_bins] of an 8-byte key): all ones
-static int init_first_out(uint64_t *out, uint64_t *best, bool wide, uint32_t n_bins, hipStream_t s) {
-    HIP_TRY(hipMemsetAsync(out, 0xFF, (size_t)n_bins * sizeof(uint64_t), s));
-    if (wide) HIP_TRY(hipMemsetAsync(best, 0xFF, (size_t)n_bins * sizeof(uint64_t), s));
-    return PQPS_OK;
-}
-
 static int first_path(const pqps_column *group_col, uint32_t n_bins) {
     return !group_col ? FIRST_ONE : n_bins <= kFirstLdsBins ? FIRST_LDS : FIRST_GLOBAL;
 }
 
-int pqps_filter_group_first(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
-                            const pqps_column *key_col, int key_signed, int descending, uint32_t row_base,
-                            const pqps_column *group_col, uint32_t bin_base, uint32_t n_bins, uint64_t *out, uint64_t *best,
-                            uint64_t *count, void *stream) {
+static int check_head_rounds(uint32_t n_rounds) {
+    return n_rounds >= 1 && n_rounds <= PQPS_HEAD_ROUNDS_MAX ? PQPS_OK : fail(PQPS_EINVAL, "%u rounds: 1 .. %u", n_rounds, PQPS_HEAD_ROUNDS_MAX);
+}
+
+// out[n_rounds][n_bins] (and best, of an 8-byte key): all ones
+static int init_first_out(uint64_t *out, uint64_t *best, bool wide, size_t words, hipStream_t s) {
+    HIP_TRY(hipMemsetAsync(out, 0xFF, words * sizeof(uint64_t), s));
+    if (wide) HIP_TRY(hipMemsetAsync(best, 0xFF, words * sizeof(uint64_t), s));
+    return PQPS_OK;
+}
+
+// Rounds 0 .. n_rounds-1 of the fused scan, issued back to back on the stream: round r reads round r-1's words from device
+// memory.  Round 0 is the first-row query (no floor, the 8 B x D table, the match count); a later round keeps its floor in
+// LDS where D <= kFloorLdsBins and the key is narrow (the 16 B x D table, and the grid that goes with it).
+static int first_scan_rounds(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                             const pqps_column *key_col, int key_signed, int descending, uint32_t row_base,
+                             const pqps_column *group_col, uint32_t bin_base, uint32_t n_bins, uint32_t n_rounds, uint64_t *out,
+                             uint64_t *best, uint64_t *count, void *stream) {
     if (!ctx || !out || !count) return fail(PQPS_EINVAL, "ctx/out/count is NULL");
     FirstArgs g;
     memset(&g, 0, sizeof g);
@@ -3910,13 +3916,18 @@ int pqps_filter_group_first(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_c
     if (rc) return rc;
     hipStream_t s = pick_stream(ctx, stream);
     HIP_TRY(hipMemsetAsync(count, 0, sizeof(uint64_t), s));
-    rc = init_first_out(out, best, wide, n_bins, s);
+    rc = init_first_out(out, best, wide, (size_t)n_rounds * n_bins, s);
     if (rc || n_rows == 0) return rc;
     const int path = first_path(group_col, n_bins);
-    const uint32_t table_bytes = path == FIRST_LDS ? n_bins * (uint32_t)sizeof(uint64_t) : 0u;
-    const uint32_t grid = fused_grid(ctx, n_rows, table_bytes);
-    if (path != FIRST_GLOBAL) {
-        rc = grow_group_parts(ctx, s, (size_t)grid * n_bins * 2);
+    // [0]: round 0, [1]: the later rounds
+    const int floor[2] = {FLOOR_NONE, path == FIRST_LDS && n_bins <= kFloorLdsBins && !wide ? FLOOR_LDS : FLOOR_MEM};
+    uint32_t table_bytes[2], grid[2];
+    for (int i = 0; i < 2; i++) {
+        table_bytes[i] = path == FIRST_LDS ? n_bins * (floor[i] == FLOOR_LDS ? 2u : 1u) * (uint32_t)sizeof(uint64_t) : 0u;
+        grid[i] = fused_grid(ctx, n_rows, table_bytes[i]);
+    }
+    if (path != FIRST_GLOBAL) {                                         // fused_grid falls as the table grows: grid[0] is the larger
+        rc = grow_group_parts(ctx, s, (size_t)grid[0] * n_bins * 2);
         if (rc) return rc;
     }
     g.kcol = key_col ? key_col->data : nullptr;
@@ -3926,40 +3937,70 @@ int pqps_filter_group_first(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_c
     g.bin_base = bin_base;
     g.n_bins = n_bins;
     g.row_base = row_base;
-    // the instance and its name side by side: pqps_last_kernel() reports the entry that is launched
-    static const struct { void (*fn)(const FirstArgs); const char *name; } fns[3][3][2] = {
-#define PQPS_FIRST_SCAN(P, M, NT) {first_scan_kernel<P, M, NT>, "first_scan_kernel<" #P ", " #M ", NT=" #NT ">"}
-#define PQPS_FIRST_SCANS(P) {{PQPS_FIRST_SCAN(P, FIRST_NARROW, false), PQPS_FIRST_SCAN(P, FIRST_NARROW, true)},   \
-                             {PQPS_FIRST_SCAN(P, FIRST_WIDE_A, false), PQPS_FIRST_SCAN(P, FIRST_WIDE_A, true)},   \
-                             {PQPS_FIRST_SCAN(P, FIRST_WIDE_B, false), PQPS_FIRST_SCAN(P, FIRST_WIDE_B, true)}}
-        PQPS_FIRST_SCANS(FIRST_ONE), PQPS_FIRST_SCANS(FIRST_LDS), PQPS_FIRST_SCANS(FIRST_GLOBAL),
+    // the instance and its name side by side: pqps_last_kernel() reports the entry that is launched.  The names are the
+    // labels of the paths: a later round's says where its floor lives (HEAD_LDS2: in LDS; HEAD_ONE / HEAD_LDS / HEAD_GLOBAL:
+    // in device memory).  [FLOOR_LDS] has the LDS path's narrow entries only; nothing else selects it.
+    static const struct { void (*fn)(const FirstArgs); const char *name; } fns[3][3][3][2] = {
+#define PQPS_FIRST_SCAN(K, L, P, M, F, NT) {first_scan_kernel<P, M, F, NT>, #K "_scan_kernel<" #L ", " #M ", NT=" #NT ">"}
+#define PQPS_FIRST_NTS(K, L, P, M, F) {PQPS_FIRST_SCAN(K, L, P, M, F, false), PQPS_FIRST_SCAN(K, L, P, M, F, true)}
+#define PQPS_FIRST_SCANS(K, L, P, F) {PQPS_FIRST_NTS(K, L, P, FIRST_NARROW, F), PQPS_FIRST_NTS(K, L, P, FIRST_WIDE_A, F), PQPS_FIRST_NTS(K, L, P, FIRST_WIDE_B, F)}
+        {PQPS_FIRST_SCANS(first, FIRST_ONE, FIRST_ONE, FLOOR_NONE), PQPS_FIRST_SCANS(first, FIRST_LDS, FIRST_LDS, FLOOR_NONE),
+         PQPS_FIRST_SCANS(first, FIRST_GLOBAL, FIRST_GLOBAL, FLOOR_NONE)},
+        {{}, {PQPS_FIRST_NTS(head, HEAD_LDS2, FIRST_LDS, FIRST_NARROW, FLOOR_LDS)}, {}},
+        {PQPS_FIRST_SCANS(head, HEAD_ONE, FIRST_ONE, FLOOR_MEM), PQPS_FIRST_SCANS(head, HEAD_LDS, FIRST_LDS, FLOOR_MEM),
+         PQPS_FIRST_SCANS(head, HEAD_GLOBAL, FIRST_GLOBAL, FLOOR_MEM)},
 #undef PQPS_FIRST_SCANS
+#undef PQPS_FIRST_NTS
 #undef PQPS_FIRST_SCAN
     };
-    // narrow keys: one pass into `out`; an 8-byte key: pass A into `best`, then pass B into `out`
-    for (int mode = wide ? FIRST_WIDE_A : FIRST_NARROW; mode <= (wide ? FIRST_WIDE_B : FIRST_NARROW); mode++) {
-        uint64_t *target = mode == FIRST_WIDE_A ? best : out;
-        g.out = target;
-        g.best = mode == FIRST_WIDE_B ? best : nullptr;
-        g.count = mode == FIRST_WIDE_B ? nullptr : (unsigned long long *)count;
-        const auto &scan = fns[path][mode][g.e.streaming ? 1 : 0];
-        snprintf(g_kernel, sizeof g_kernel, "%s", scan.name);
-        hipEvent_t stop;
-        rc = fused_launch(ctx, scan.fn, grid, table_bytes, s, g, &stop);
-        if (rc) return rc;
-        if (path != FIRST_GLOBAL) {
-            const dim3 sg((n_bins + 63u) / 64u, (grid + kFirstMinParts - 1) / kFirstMinParts);
-            rc = launch_stop(first_min_kernel, sg, 0, s, stop, (const uint64_t *)ctx->group_parts, grid, n_bins, target);
+    for (uint32_t r = 0; r < n_rounds; r++) {
+        const int i = r ? 1 : 0;
+        uint64_t *rout = out + (size_t)r * n_bins, *rbest = wide ? best + (size_t)r * n_bins : nullptr;
+        g.floor = r ? rout - n_bins : nullptr;
+        g.floor_best = r && wide ? rbest - n_bins : nullptr;
+        // narrow keys: one pass into `out`; an 8-byte key: pass A into `best`, then pass B into `out`
+        for (int mode = wide ? FIRST_WIDE_A : FIRST_NARROW; mode <= (wide ? FIRST_WIDE_B : FIRST_NARROW); mode++) {
+            uint64_t *target = mode == FIRST_WIDE_A ? rbest : rout;
+            g.out = target;
+            g.best = mode == FIRST_WIDE_B ? rbest : nullptr;
+            g.count = r || mode == FIRST_WIDE_B ? nullptr : (unsigned long long *)count;
+            const auto &scan = fns[floor[i]][path][mode][g.e.streaming ? 1 : 0];
+            snprintf(g_kernel, sizeof g_kernel, "%s", scan.name);
+            hipEvent_t stop;
+            rc = fused_launch(ctx, scan.fn, grid[i], table_bytes[i], s, g, &stop);
+            if (rc) return rc;
+            if (path != FIRST_GLOBAL) {
+                const dim3 sg((n_bins + 63u) / 64u, (grid[i] + kFirstMinParts - 1) / kFirstMinParts);
+                rc = launch_stop(first_min_kernel, sg, 0, s, stop, (const uint64_t *)ctx->group_parts, grid[i], n_bins, target);
+            }
+            fused_close(ctx, stop, path == FIRST_GLOBAL);
+            if (rc) return rc;
         }
-        fused_close(ctx, stop, path == FIRST_GLOBAL);
-        if (rc) return rc;
     }
     return PQPS_OK;
 }
 
-int pqps_group_first_list(pqps_ctx *ctx, const pqps_column *key_col, int key_signed, int descending, const pqps_column *group_col,
-                          uint32_t bin_base, uint32_t n_bins, uint64_t n_rows, const uint32_t *ids, const uint64_t *count_dev,
-                          uint64_t capacity, uint32_t id_base, uint64_t *out, uint64_t *best, void *stream) {
+int pqps_filter_group_first(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                            const pqps_column *key_col, int key_signed, int descending, uint32_t row_base,
+                            const pqps_column *group_col, uint32_t bin_base, uint32_t n_bins, uint64_t *out, uint64_t *best,
+                            uint64_t *count, void *stream) {
+    return first_scan_rounds(ctx, cols, n_cols, n_rows, pred, key_col, key_signed, descending, row_base, group_col, bin_base, n_bins, 1,
+                             out, best, count, stream);
+}
+
+int pqps_filter_group_head(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                           const pqps_column *key_col, int key_signed, int descending, uint32_t row_base,
+                           const pqps_column *group_col, uint32_t bin_base, uint32_t n_bins, uint32_t n_rounds, uint64_t *out,
+                           uint64_t *best, uint64_t *count, void *stream) {
+    const int rc = check_head_rounds(n_rounds);
+    return rc ? rc : first_scan_rounds(ctx, cols, n_cols, n_rows, pred, key_col, key_signed, descending, row_base, group_col, bin_base,
+                                       n_bins, n_rounds, out, best, count, stream);
+}
+
+// The same rounds over an ID list.
+static int first_list_rounds(pqps_ctx *ctx, const pqps_column *key_col, int key_signed, int descending, const pqps_column *group_col,
+                             uint32_t bin_base, uint32_t n_bins, uint64_t n_rows, const uint32_t *ids, const uint64_t *count_dev,
+                             uint64_t capacity, uint32_t id_base, uint32_t n_rounds, uint64_t *out, uint64_t *best, void *stream) {
     if (!ctx || !out || !count_dev || (capacity && !ids)) return fail(PQPS_EINVAL, "NULL argument");
     bool wide;
     uint32_t kwl, gwl;
@@ -3967,7 +4008,7 @@ int pqps_group_first_list(pqps_ctx *ctx, const pqps_column *key_col, int key_sig
     if (rc) return rc;
     if ((uint64_t)id_base + n_rows >= 0xFFFFFFFFull) return fail(PQPS_EINVAL, "row numbers must stay below 2^32 - 1");
     hipStream_t s = pick_stream(ctx, stream);
-    rc = init_first_out(out, best, wide, n_bins, s);
+    rc = init_first_out(out, best, wide, (size_t)n_rounds * n_bins, s);
     if (rc || capacity == 0 || n_rows == 0) return rc;
     const void *kdata = key_col ? key_col->data : nullptr;
     const void *gdata = group_col ? group_col->data : nullptr;
@@ -3975,142 +4016,40 @@ int pqps_group_first_list(pqps_ctx *ctx, const pqps_column *key_col, int key_sig
     const int path = first_path(group_col, n_bins);
     const uint32_t lds = path == FIRST_LDS ? n_bins * (uint32_t)sizeof(uint64_t) : 0u;
     typedef void (*list_fn)(const void *, uint32_t, uint64_t, const void *, uint32_t, uint64_t, const uint32_t *, const uint64_t *,
-                            uint64_t, uint32_t, uint32_t, uint32_t, const uint64_t *, uint64_t *);
-    static const list_fn fns[3][3] = {
-        {first_list_kernel<FIRST_ONE, FIRST_NARROW>, first_list_kernel<FIRST_ONE, FIRST_WIDE_A>, first_list_kernel<FIRST_ONE, FIRST_WIDE_B>},
-        {first_list_kernel<FIRST_LDS, FIRST_NARROW>, first_list_kernel<FIRST_LDS, FIRST_WIDE_A>, first_list_kernel<FIRST_LDS, FIRST_WIDE_B>},
-        {first_list_kernel<FIRST_GLOBAL, FIRST_NARROW>, first_list_kernel<FIRST_GLOBAL, FIRST_WIDE_A>, first_list_kernel<FIRST_GLOBAL, FIRST_WIDE_B>},
+                            uint64_t, uint32_t, uint32_t, uint32_t, const uint64_t *, const uint64_t *, const uint64_t *, uint64_t *);
+#define PQPS_FIRST_LISTS(P, F) {first_list_kernel<P, FIRST_NARROW, F>, first_list_kernel<P, FIRST_WIDE_A, F>, first_list_kernel<P, FIRST_WIDE_B, F>}
+    static const list_fn fns[2][3][3] = {
+        {PQPS_FIRST_LISTS(FIRST_ONE, FLOOR_NONE), PQPS_FIRST_LISTS(FIRST_LDS, FLOOR_NONE), PQPS_FIRST_LISTS(FIRST_GLOBAL, FLOOR_NONE)},
+        {PQPS_FIRST_LISTS(FIRST_ONE, FLOOR_MEM), PQPS_FIRST_LISTS(FIRST_LDS, FLOOR_MEM), PQPS_FIRST_LISTS(FIRST_GLOBAL, FLOOR_MEM)},
     };
+#undef PQPS_FIRST_LISTS
     const dim3 grid(list_grid(ctx, capacity, path == FIRST_LDS ? 2 : 4));
-    for (int mode = wide ? FIRST_WIDE_A : FIRST_NARROW; mode <= (wide ? FIRST_WIDE_B : FIRST_NARROW); mode++) {
-        hipLaunchKernelGGL(fns[path][mode], grid, dim3(kBlock), lds, s, kdata, kwl, kxor, gdata, gwl, n_rows, ids, count_dev, capacity,
-                           id_base, bin_base, n_bins, (const uint64_t *)(mode == FIRST_WIDE_B ? best : nullptr),
-                           mode == FIRST_WIDE_A ? best : out);
-        HIP_TRY(hipGetLastError());
-    }
-    return PQPS_OK;
-}
-
-// ---- the first N rows of every group (head_kernels.hpp) --------------------------------------------------------------
-static int check_head_rounds(uint32_t n_rounds) {
-    return n_rounds >= 1 && n_rounds <= PQPS_HEAD_ROUNDS_MAX ? PQPS_OK : fail(PQPS_EINVAL, "%u rounds: 1 .. %u", n_rounds, PQPS_HEAD_ROUNDS_MAX);
-}
-
-int pqps_filter_group_head(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
-                           const pqps_column *key_col, int key_signed, int descending, uint32_t row_base,
-                           const pqps_column *group_col, uint32_t bin_base, uint32_t n_bins, uint32_t n_rounds, uint64_t *out,
-                           uint64_t *best, uint64_t *count, void *stream) {
-    int rc = check_head_rounds(n_rounds);
-    if (rc) return rc;
-    // round 0: the first-row launch, unchanged (it checks every argument, zeroes *count and fills row 0)
-    rc = pqps_filter_group_first(ctx, cols, n_cols, n_rows, pred, key_col, key_signed, descending, row_base, group_col, bin_base, n_bins,
-                                 out, best, count, stream);
-    if (rc || n_rounds == 1) return rc;
-    HeadArgs h;
-    memset(&h, 0, sizeof h);
-    FirstArgs &g = h.f;
-    bool wide;
-    rc = check_first_cols(key_col, group_col, n_bins, best, true, &wide, &g.kwidth_log2, &g.gwidth_log2);
-    if (!rc) rc = fused_args(g.e, cols, n_cols, n_rows, pred);
-    if (rc) return rc;
-    hipStream_t s = pick_stream(ctx, stream);
-    const size_t later = (size_t)(n_rounds - 1) * n_bins;
-    HIP_TRY(hipMemsetAsync(out + n_bins, 0xFF, later * sizeof(uint64_t), s));
-    if (wide) HIP_TRY(hipMemsetAsync(best + n_bins, 0xFF, later * sizeof(uint64_t), s));
-    if (n_rows == 0) return PQPS_OK;
-    const int path = !group_col ? HEAD_ONE : n_bins <= kHeadLds2Bins && !wide ? HEAD_LDS2 : n_bins <= kFirstLdsBins ? HEAD_LDS : HEAD_GLOBAL;
-    const uint32_t table_bytes = path == HEAD_LDS2 ? n_bins * 2u * (uint32_t)sizeof(uint64_t) : path == HEAD_LDS ? n_bins * (uint32_t)sizeof(uint64_t) : 0u;
-    const uint32_t grid = fused_grid(ctx, n_rows, table_bytes);
-    if (path != HEAD_GLOBAL) {
-        rc = grow_group_parts(ctx, s, (size_t)grid * n_bins * 2);
-        if (rc) return rc;
-    }
-    g.kcol = key_col ? key_col->data : nullptr;
-    g.gcol = group_col ? group_col->data : nullptr;
-    g.parts = (uint64_t *)ctx->group_parts;
-    g.kxor = topk_xor(wide, key_signed, descending);
-    g.bin_base = bin_base;
-    g.n_bins = n_bins;
-    g.row_base = row_base;
-    typedef void (*head_fn)(const HeadArgs);
-    struct Inst { head_fn fn; const char *name; };
-#define PQPS_HEAD_SCAN(P, M, NT) {head_scan_kernel<P, M, NT>, "head_scan_kernel<" #P ", " #M ", NT=" #NT ">"}
-#define PQPS_HEAD_SCANS(P) {{PQPS_HEAD_SCAN(P, FIRST_NARROW, false), PQPS_HEAD_SCAN(P, FIRST_NARROW, true)},   \
-                            {PQPS_HEAD_SCAN(P, FIRST_WIDE_A, false), PQPS_HEAD_SCAN(P, FIRST_WIDE_A, true)},   \
-                            {PQPS_HEAD_SCAN(P, FIRST_WIDE_B, false), PQPS_HEAD_SCAN(P, FIRST_WIDE_B, true)}}
-    static const Inst fns[4][3][2] = {
-        PQPS_HEAD_SCANS(HEAD_ONE),
-        {{PQPS_HEAD_SCAN(HEAD_LDS2, FIRST_NARROW, false), PQPS_HEAD_SCAN(HEAD_LDS2, FIRST_NARROW, true)}, {{nullptr, ""}, {nullptr, ""}}, {{nullptr, ""}, {nullptr, ""}}},
-        PQPS_HEAD_SCANS(HEAD_LDS), PQPS_HEAD_SCANS(HEAD_GLOBAL),
-#undef PQPS_HEAD_SCANS
-#undef PQPS_HEAD_SCAN
-    };
-    // every round is issued here, back to back on `s`: round r reads round r-1's words from device memory
-    for (uint32_t r = 1; r < n_rounds; r++) {
-        h.floor = out + (size_t)(r - 1) * n_bins;
-        h.floor_best = wide ? best + (size_t)(r - 1) * n_bins : nullptr;
+    for (uint32_t r = 0; r < n_rounds; r++) {
+        uint64_t *rout = out + (size_t)r * n_bins, *rbest = wide ? best + (size_t)r * n_bins : nullptr;
+        const uint64_t *floor = r ? rout - n_bins : nullptr, *floor_best = r && wide ? rbest - n_bins : nullptr;
         for (int mode = wide ? FIRST_WIDE_A : FIRST_NARROW; mode <= (wide ? FIRST_WIDE_B : FIRST_NARROW); mode++) {
-            uint64_t *target = (mode == FIRST_WIDE_A ? best : out) + (size_t)r * n_bins;
-            g.out = target;
-            g.best = mode == FIRST_WIDE_B ? best + (size_t)r * n_bins : nullptr;
-            const Inst &scan = fns[path][mode][g.e.streaming ? 1 : 0];
-            snprintf(g_kernel, sizeof g_kernel, "%s", scan.name);
-            hipEvent_t stop;
-            rc = fused_launch(ctx, scan.fn, grid, table_bytes, s, h, &stop);
-            if (rc) return rc;
-            if (path != HEAD_GLOBAL) {
-                const dim3 sg((n_bins + 63u) / 64u, (grid + kFirstMinParts - 1) / kFirstMinParts);
-                rc = launch_stop(first_min_kernel, sg, 0, s, stop, (const uint64_t *)ctx->group_parts, grid, n_bins, target);
-            }
-            fused_close(ctx, stop, path == HEAD_GLOBAL);
-            if (rc) return rc;
+            hipLaunchKernelGGL(fns[r ? 1 : 0][path][mode], grid, dim3(kBlock), lds, s, kdata, kwl, kxor, gdata, gwl, n_rows, ids, count_dev,
+                               capacity, id_base, bin_base, n_bins, (const uint64_t *)(mode == FIRST_WIDE_B ? rbest : nullptr), floor,
+                               floor_best, mode == FIRST_WIDE_A ? rbest : rout);
+            HIP_TRY(hipGetLastError());
         }
     }
     return PQPS_OK;
+}
+
+int pqps_group_first_list(pqps_ctx *ctx, const pqps_column *key_col, int key_signed, int descending, const pqps_column *group_col,
+                          uint32_t bin_base, uint32_t n_bins, uint64_t n_rows, const uint32_t *ids, const uint64_t *count_dev,
+                          uint64_t capacity, uint32_t id_base, uint64_t *out, uint64_t *best, void *stream) {
+    return first_list_rounds(ctx, key_col, key_signed, descending, group_col, bin_base, n_bins, n_rows, ids, count_dev, capacity, id_base, 1,
+                             out, best, stream);
 }
 
 int pqps_group_head_list(pqps_ctx *ctx, const pqps_column *key_col, int key_signed, int descending, const pqps_column *group_col,
                          uint32_t bin_base, uint32_t n_bins, uint64_t n_rows, const uint32_t *ids, const uint64_t *count_dev,
                          uint64_t capacity, uint32_t id_base, uint32_t n_rounds, uint64_t *out, uint64_t *best, void *stream) {
-    int rc = check_head_rounds(n_rounds);
-    if (rc) return rc;
-    rc = pqps_group_first_list(ctx, key_col, key_signed, descending, group_col, bin_base, n_bins, n_rows, ids, count_dev, capacity, id_base,
-                               out, best, stream);
-    if (rc || n_rounds == 1) return rc;
-    bool wide;
-    uint32_t kwl, gwl;
-    rc = check_first_cols(key_col, group_col, n_bins, best, false, &wide, &kwl, &gwl);
-    if (rc) return rc;
-    hipStream_t s = pick_stream(ctx, stream);
-    const size_t later = (size_t)(n_rounds - 1) * n_bins;
-    HIP_TRY(hipMemsetAsync(out + n_bins, 0xFF, later * sizeof(uint64_t), s));
-    if (wide) HIP_TRY(hipMemsetAsync(best + n_bins, 0xFF, later * sizeof(uint64_t), s));
-    if (capacity == 0 || n_rows == 0) return PQPS_OK;
-    const void *kdata = key_col ? key_col->data : nullptr;
-    const void *gdata = group_col ? group_col->data : nullptr;
-    const uint64_t kxor = topk_xor(wide, key_signed, descending);
-    const int path = first_path(group_col, n_bins);
-    const uint32_t lds = path == FIRST_LDS ? n_bins * (uint32_t)sizeof(uint64_t) : 0u;
-    typedef void (*list_fn)(const void *, uint32_t, uint64_t, const void *, uint32_t, uint64_t, const uint32_t *, const uint64_t *,
-                            uint64_t, uint32_t, uint32_t, uint32_t, const uint64_t *, const uint64_t *, const uint64_t *, uint64_t *);
-    static const list_fn fns[3][3] = {
-        {head_list_kernel<FIRST_ONE, FIRST_NARROW>, head_list_kernel<FIRST_ONE, FIRST_WIDE_A>, head_list_kernel<FIRST_ONE, FIRST_WIDE_B>},
-        {head_list_kernel<FIRST_LDS, FIRST_NARROW>, head_list_kernel<FIRST_LDS, FIRST_WIDE_A>, head_list_kernel<FIRST_LDS, FIRST_WIDE_B>},
-        {head_list_kernel<FIRST_GLOBAL, FIRST_NARROW>, head_list_kernel<FIRST_GLOBAL, FIRST_WIDE_A>, head_list_kernel<FIRST_GLOBAL, FIRST_WIDE_B>},
-    };
-    const dim3 grid(list_grid(ctx, capacity, path == FIRST_LDS ? 2 : 4));
-    for (uint32_t r = 1; r < n_rounds; r++) {
-        const uint64_t *floor = out + (size_t)(r - 1) * n_bins;
-        const uint64_t *floor_best = wide ? best + (size_t)(r - 1) * n_bins : nullptr;
-        uint64_t *rout = out + (size_t)r * n_bins, *rbest = wide ? best + (size_t)r * n_bins : nullptr;
-        for (int mode = wide ? FIRST_WIDE_A : FIRST_NARROW; mode <= (wide ? FIRST_WIDE_B : FIRST_NARROW); mode++) {
-            hipLaunchKernelGGL(fns[path][mode], grid, dim3(kBlock), lds, s, kdata, kwl, kxor, gdata, gwl, n_rows, ids, count_dev, capacity,
-                               id_base, bin_base, n_bins, (const uint64_t *)(mode == FIRST_WIDE_B ? rbest : nullptr), floor, floor_best,
-                               mode == FIRST_WIDE_A ? rbest : rout);
-            HIP_TRY(hipGetLastError());
-        }
-    }
-    return PQPS_OK;
+    const int rc = check_head_rounds(n_rounds);
+    return rc ? rc : first_list_rounds(ctx, key_col, key_signed, descending, group_col, bin_base, n_bins, n_rows, ids, count_dev, capacity,
+                                       id_base, n_rounds, out, best, stream);
 }
 
 int pqps_runs_head_flags(pqps_ctx *ctx, const uint64_t *sorted_keys, uint64_t n, uint64_t limit, uint8_t *keep, void *stream) {

@@ -2856,20 +2856,30 @@ static int select_columnar(struct engineS *engine, struct hipTable *t, const cha
     return rc;
 }
 
-struct hipColumnarResult *executeQuerySelectColumnarHIP(struct engineS *engine, const char **selectItems, int numSelectItems,
-                                                        struct whereClauseS *whereClause) {
+/* The empty result of a columnar SELECT: the column arrays for *selectItems -- none: all 12 columns, and the two arguments
+ * are set to that list -- or, without an engine, the bare result.  Out of memory ends the process, as the reference's
+ * result sets do. */
+static struct hipColumnarResult *columnar_shell(struct engineS *engine, const char ***selectItems, int *numSelectItems) {
     struct hipColumnarResult *res = calloc(1, sizeof *res);
     if (!res) { perror("Failed to allocate memory for result set"); exit(EXIT_FAILURE); }
     if (!engine || !engine->record_block) return res;
-    struct hipTable *t = engine->record_block;
-    if (selectItems == NULL || numSelectItems == 0) { selectItems = (const char **)k_all_columns; numSelectItems = 12; }
-    res->numColumns = numSelectItems;
-    res->columnNames = calloc((size_t)numSelectItems, sizeof(char *));
-    res->columnKinds = calloc((size_t)numSelectItems, sizeof(int));
-    res->values = calloc((size_t)numSelectItems, sizeof(void *));
-    res->dictionaries = calloc((size_t)numSelectItems, sizeof(*res->dictionaries));
-    res->dictionarySizes = calloc((size_t)numSelectItems, sizeof(int));
+    if (*selectItems == NULL || *numSelectItems == 0) { *selectItems = (const char **)k_all_columns; *numSelectItems = 12; }
+    const size_t n = (size_t)*numSelectItems;
+    res->numColumns = *numSelectItems;
+    res->columnNames = calloc(n, sizeof(char *));
+    res->columnKinds = calloc(n, sizeof(int));
+    res->values = calloc(n, sizeof(void *));
+    res->dictionaries = calloc(n, sizeof(*res->dictionaries));
+    res->dictionarySizes = calloc(n, sizeof(int));
     if (!res->columnNames || !res->columnKinds || !res->values || !res->dictionaries || !res->dictionarySizes) { perror("Failed to allocate memory for result set"); exit(EXIT_FAILURE); }
+    return res;
+}
+
+struct hipColumnarResult *executeQuerySelectColumnarHIP(struct engineS *engine, const char **selectItems, int numSelectItems,
+                                                        struct whereClauseS *whereClause) {
+    struct hipColumnarResult *res = columnar_shell(engine, &selectItems, &numSelectItems);
+    if (!engine || !engine->record_block) return res;
+    struct hipTable *t = engine->record_block;
 
     const double t0 = now_seconds();
     hipTableLockShared(t);
@@ -3267,17 +3277,8 @@ static struct hipColumnarResult *order_select_run(struct engineS *engine, const 
                                                   struct whereClauseS *whereClause, const struct order_request *r, long long limit,
                                                   long long *matches) {
     if (matches) *matches = 0;
-    struct hipColumnarResult *res = calloc(1, sizeof *res);
-    if (!res) { perror("Failed to allocate memory for result set"); exit(EXIT_FAILURE); }
+    struct hipColumnarResult *res = columnar_shell(engine, &selectItems, &numSelectItems);
     if (!engine || !engine->record_block) return res;
-    if (selectItems == NULL || numSelectItems == 0) { selectItems = (const char **)k_all_columns; numSelectItems = 12; }
-    res->numColumns = numSelectItems;
-    res->columnNames = calloc((size_t)numSelectItems, sizeof(char *));
-    res->columnKinds = calloc((size_t)numSelectItems, sizeof(int));
-    res->values = calloc((size_t)numSelectItems, sizeof(void *));
-    res->dictionaries = calloc((size_t)numSelectItems, sizeof(*res->dictionaries));
-    res->dictionarySizes = calloc((size_t)numSelectItems, sizeof(int));
-    if (!res->columnNames || !res->columnKinds || !res->values || !res->dictionaries || !res->dictionarySizes) { perror("Failed to allocate memory for result set"); exit(EXIT_FAILURE); }
     const double t0 = now_seconds();
     struct query q;
     if (!query_open(engine, &q)) return res;                             /* reason on stderr */
@@ -3311,69 +3312,8 @@ struct hipColumnarResult *executeQuerySelectOrderedByHIP(struct engineS *engine,
                             limit, matches);
 }
 
-/* ---- the first row of every group (include/executeEngine-hip.h) ---------------------------------------------------- */
-
-/* One shard's device buffer: [16 B: the matching rows][out: n_bins words][best: n_bins words, command_id only]. */
-struct first_call { const struct group_plan *gp; const struct order_plan *op; void **buf; uint64_t *out, *best, *matches; bool fused; };
-
-static int first_fused_call(struct query *q, int s, pqps_ctx *ctx, void *stream, void *arg) {
-    const struct first_call *a = arg;
-    const struct group_plan *gp = a->gp;
-    const struct order_plan *op = a->op;
-    const struct hipTable *sh = hipTableShard(q->t, s);
-    const struct shard_pred *sp = &q->sp[s];
-    const bool grouped = gp->c >= 0 && !gp->single;
-    uint64_t *b = a->buf[s];
-    if (pqps_filter_group_first(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, op->no_key ? NULL : &op->kcol[s], op->key_signed, op->desc,
-                                (uint32_t)sh->row0, grouped ? &gp->gcol[s] : NULL, gp->bin_base, gp->n_bins, b + 2,
-                                op->wide ? b + 2 + gp->n_bins : NULL, b, stream) != PQPS_OK)
-        return engine_error("first-row filter");
-    return 0;
-}
-
-static int first_list_call(struct query *q, int s, pqps_ctx *cs, const struct hipLane *L, void *out, void *arg) {
-    const struct first_call *a = arg;
-    const struct group_plan *gp = a->gp;
-    const struct order_plan *op = a->op;
-    const struct hipTable *sh = hipTableShard(q->t, s);
-    const bool grouped = gp->c >= 0 && !gp->single;
-    uint64_t *b = out;
-    return pqps_group_first_list(cs, op->no_key ? NULL : &op->kcol[s], op->key_signed, op->desc, grouped ? &gp->gcol[s] : NULL, gp->bin_base,
-                                 gp->n_bins, sh->n_rows, L->ids_dev, L->count_dev, q->count[s], (uint32_t)sh->row0, b + 2,
-                                 op->wide ? b + 2 + gp->n_bins : NULL, NULL);
-}
-
-/* One shard's buffer merged into the host's words: rows are table-wide, so the minimum word per bin is the answer;
- * command_id compares (best, row).  The match count in front of the words is added up on the fused path only (a->fused:
- * the path first_bins gave shard_reduce): the list call does not write it, and first_bins takes the selection's total. */
-static void first_combine(void *arg, const void *host) {
-    const struct first_call *a = arg;
-    const uint32_t n_bins = a->gp->n_bins;
-    const uint64_t *h = (const uint64_t *)host + 2;
-    uint64_t *out = a->out, *best = a->best;
-    if (a->fused) *a->matches += *(const uint64_t *)host;
-    for (uint32_t k = 0; k < n_bins; k++) {
-        if (h[k] == UINT64_MAX) continue;
-        if (!a->op->wide) { if (h[k] < out[k]) out[k] = h[k]; continue; }
-        const uint64_t hb = h[n_bins + k];
-        if (out[k] == UINT64_MAX || hb < best[k] || (hb == best[k] && h[k] < out[k])) { out[k] = h[k]; best[k] = hb; }
-    }
-}
-
-/* The words of the query on every shard, merged on the host (shard_reduce, first_combine) into out[n_bins] (and best[n_bins]
- * for command_id), all ones on entry; *matches = the selection's rows: the shards' counts added up by first_combine on the
- * fused path (pqps_filter_group_first), the selection's total on the list path (pqps_group_first_list). */
-static int first_bins(struct query *q, const struct group_plan *gp, const struct order_plan *op, uint64_t *out, uint64_t *best,
-                      uint64_t *matches) {
-    void *buf[HIP_MAX_SHARDS];
-    const struct shard_reduce r = { .what = "first-row words", .bytes = 16 + (size_t)gp->n_bins * (op->wide ? 2 : 1) * sizeof(uint64_t),
-                                    .fused = first_fused_call, .list = first_list_call, .combine = first_combine };
-    const bool fused = gp->fused;                                        /* one source for the driver, the combine and the total */
-    *matches = 0;
-    const int rc = shard_reduce(q, fused, &r, buf, &(struct first_call){ gp, op, buf, out, best, matches, fused });
-    if (rc == 0 && !fused) *matches = q->total;
-    return rc;
-}
+/* ---- the first row and the first N rows of every group (include/executeEngine-hip.h) ------------------------------- */
+/* One driver (head_reduce): the first row is one round of the first N; only what the host does with the words differs. */
 
 /* Checks the two columns and the engine; fills the result's column fields and the order plan.  -1: refused, reason on stderr. */
 static int group_first_begin(struct engineS *engine, const char *groupColumn, const char *orderColumn, bool descending,
@@ -3397,138 +3337,6 @@ static int group_first_begin(struct engineS *engine, const char *groupColumn, co
     return 0;
 }
 
-/* out[n_bins] (best[n_bins] for command_id) into the result: groups with a row only, in bin order. */
-static int group_first_fill(struct hipGroupFirstResult *res, const struct hipTable *t, const uint64_t *out, const uint64_t *best,
-                            uint32_t n_bins, int32_t lo) {
-    uint64_t *present = calloc((size_t)n_bins + 1, sizeof *present);
-    if (!present) return oom();
-    for (uint32_t k = 0; k < n_bins; k++) present[k] = out[k] != UINT64_MAX;
-    const int rc = group_keys_fill(t, res->groupColumn, res->groupKind, lo, present, n_bins, &res->keys, &res->keyText, &res->numGroups);
-    free(present);
-    if (rc != 0) return -1;
-    const size_t n = (size_t)res->numGroups;
-    res->rows = calloc(n + 1, sizeof *res->rows);
-    res->orderKeys = calloc(n + 1, sizeof *res->orderKeys);
-    res->orderText = calloc(n + 1, sizeof *res->orderText);
-    if (!res->rows || !res->orderKeys || !res->orderText) return oom();
-    const int oc = res->orderColumn, kind = res->orderKind;
-    size_t g = 0;
-    for (uint32_t k = 0; k < n_bins; k++) {
-        if (out[k] == UINT64_MAX) continue;
-        char buf[32];
-        const char *text = buf;
-        if (kind == HIPKIND_U64) {
-            res->rows[g] = (unsigned int)out[k];
-            res->orderKeys[g] = (long long)(best[k] ^ (res->descending ? UINT64_MAX : 0));
-            snprintf(buf, sizeof buf, "%llu", (unsigned long long)res->orderKeys[g]);
-        } else {
-            hipFirstKeyDecode(kind, res->descending, out[k], &res->orderKeys[g], &res->rows[g]);
-            if (kind == HIPKIND_I32) snprintf(buf, sizeof buf, "%d", (int)res->orderKeys[g]);
-            else if (kind == HIPKIND_BOOL) text = res->orderKeys[g] ? "true" : "false";
-            else if (res->orderKeys[g] < (long long)t->dict[oc].count) text = t->dict[oc].values[res->orderKeys[g]];
-            else { fprintf(stderr, "HIP engine: first row per group: code %lld outside the dictionary\n", res->orderKeys[g]); return -1; }
-        }
-        if (!(res->orderText[g] = strdup(text))) return oom();
-        g++;
-    }
-    return 0;
-}
-
-/* The query itself (caller holds the table shared and the query's lane, group_first_begin has passed). */
-static int group_first_run(struct engineS *engine, struct query *q, const char *groupColumn, struct order_plan *op,
-                           struct whereClauseS *whereClause, struct hipGroupFirstResult *res) {
-    struct hipTable *t = q->t;
-    struct group_plan gp;
-    uint64_t *out = NULL, *best = NULL, matches = 0;
-    int rc = group_plan_init(engine, whereClause, q, res->groupColumn, groupColumn, "first row per group", &gp);
-    if (rc == 0 && !gp.empty) {
-        out = malloc((size_t)gp.n_bins * sizeof *out);
-        best = op->wide ? malloc((size_t)gp.n_bins * sizeof *best) : NULL;
-        if (!out || (op->wide && !best)) rc = oom();
-        else {
-            memset(out, 0xFF, (size_t)gp.n_bins * sizeof *out);
-            if (best) memset(best, 0xFF, (size_t)gp.n_bins * sizeof *best);
-        }
-        op->fused = gp.fused;
-        op->no_key = t->col[op->c].width == 0;
-        for (int s = 0; s < q->n_shards; s++) {
-            const struct hipTable *sh = hipTableShard(t, s);
-            op->kcol[s] = gp.fused && op->c == HIPCOL_SUDO_USED && sh->sudo_bits.data ? sh->sudo_bits : sh->col[op->c];
-        }
-    }
-    if (rc == 0 && !gp.empty) rc = first_bins(q, &gp, op, out, best, &matches);
-    if (rc == 0) rc = group_first_fill(res, t, out, best, gp.empty ? 0u : gp.n_bins, gp.lo);
-    if (rc == 0) res->total = (long long)matches;
-    free(out);
-    free(best);
-    return rc;
-}
-
-static void group_first_clear(struct hipGroupFirstResult *res) {
-    free_group_keys(res->keys, res->keyText, res->numGroups);
-    for (int g = 0; g < res->numGroups && res->orderText; g++) free(res->orderText[g]);
-    free(res->orderText);
-    free(res->orderKeys);
-    free(res->rows);
-}
-
-struct hipGroupFirstResult *executeQueryGroupFirstHIP(struct engineS *engine, const char *groupColumn, const char *orderColumn,
-                                                      bool descending, struct whereClauseS *whereClause) {
-    const double t0 = now_seconds();
-    struct hipGroupFirstResult *res = calloc(1, sizeof *res);
-    if (!res) { oom(); return NULL; }
-    struct order_plan op;
-    if (group_first_begin(engine, groupColumn, orderColumn, descending, res, &op) != 0) return res;
-    struct query q;
-    if (!query_open(engine, &q)) return res;                             /* reason on stderr */
-    if (group_first_run(engine, &q, groupColumn, &op, whereClause, res) == 0) res->success = true;
-    query_close(&q);
-    res->queryTime = now_seconds() - t0;
-    return res;
-}
-
-void freeGroupFirstResultHIP(struct hipGroupFirstResult *res) {
-    if (!res) return;
-    group_first_clear(res);
-    free(res);
-}
-
-struct hipColumnarResult *executeQuerySelectGroupFirstHIP(struct engineS *engine, const char **selectItems, int numSelectItems,
-                                                          struct whereClauseS *whereClause, const char *groupColumn,
-                                                          const char *orderColumn, bool descending, long long *matches) {
-    if (matches) *matches = 0;
-    struct hipColumnarResult *res = calloc(1, sizeof *res);
-    if (!res) { perror("Failed to allocate memory for result set"); exit(EXIT_FAILURE); }
-    if (!engine || !engine->record_block) return res;
-    if (selectItems == NULL || numSelectItems == 0) { selectItems = (const char **)k_all_columns; numSelectItems = 12; }
-    res->numColumns = numSelectItems;
-    res->columnNames = calloc((size_t)numSelectItems, sizeof(char *));
-    res->columnKinds = calloc((size_t)numSelectItems, sizeof(int));
-    res->values = calloc((size_t)numSelectItems, sizeof(void *));
-    res->dictionaries = calloc((size_t)numSelectItems, sizeof(*res->dictionaries));
-    res->dictionarySizes = calloc((size_t)numSelectItems, sizeof(int));
-    if (!res->columnNames || !res->columnKinds || !res->values || !res->dictionaries || !res->dictionarySizes) { perror("Failed to allocate memory for result set"); exit(EXIT_FAILURE); }
-    const double t0 = now_seconds();
-    struct hipGroupFirstResult gf;
-    struct order_plan op;
-    memset(&gf, 0, sizeof gf);
-    if (group_first_begin(engine, groupColumn, orderColumn, descending, &gf, &op) != 0) return res;
-    struct query q;
-    if (!query_open(engine, &q)) return res;                             /* reason on stderr */
-    int rc = group_first_run(engine, &q, groupColumn, &op, whereClause, &gf);
-    const uint64_t n = rc == 0 ? (uint64_t)gf.numGroups : 0;
-    if (rc == 0) rc = project_listed_rows(&q, gf.rows, n, selectItems, numSelectItems, res);
-    query_close(&q);
-    res->numRecords = rc == 0 ? (int)n : 0;
-    res->queryTime = now_seconds() - t0;
-    res->success = rc == 0;
-    if (rc == 0 && matches) *matches = gf.total;
-    group_first_clear(&gf);
-    return res;
-}
-
-/* ---- the first N rows of every group (include/executeEngine-hip.h) ------------------------------------------------- */
-
 /* One shard's candidates on the host, in the shape hipHeadMerge takes: at most `limit` entries per bin, ascending. */
 struct head_list { uint64_t n; uint32_t *bins; uint64_t *words, *best; };
 
@@ -3551,11 +3359,14 @@ static uint32_t head_round_cap(void) {
 }
 
 /* The rounds form: one shard's device buffer is [16 B: the matching rows][out: rounds x n_bins words][best: the same,
- * command_id only].  The sort form has no buffer (shard_reduce's post).  lists[0 .. *n_lists): what the shards handed. */
+ * command_id only].  The sort form has no buffer (shard_reduce's post).  lists[0 .. *n_lists): what the shards handed
+ * (the N-rows query); the first-row query hands no lists: its one round's words meet in out[n_bins] (best[n_bins]:
+ * command_id), all ones before the first shard.  head_reduce() says who sets what. */
 struct head_call {
     const struct group_plan *gp; const struct order_plan *op; void **buf;
     uint32_t rounds; uint64_t limit;
     struct head_list *lists; int *n_lists;
+    uint64_t *out, *best;
     uint64_t *matches; bool fused; int rc;
 };
 
@@ -3571,7 +3382,7 @@ static int head_fused_call(struct query *q, int s, pqps_ctx *ctx, void *stream, 
     if (pqps_filter_group_head(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, op->no_key ? NULL : &op->kcol[s], op->key_signed, op->desc,
                                (uint32_t)sh->row0, grouped ? &gp->gcol[s] : NULL, gp->bin_base, gp->n_bins, a->rounds, b + 2,
                                op->wide ? b + 2 + words : NULL, b, stream) != PQPS_OK)
-        return engine_error("first-rows filter");
+        return engine_error(a->out ? "first-row filter" : "first-rows filter");   /* a->out: the first-row query */
     return 0;
 }
 
@@ -3588,7 +3399,25 @@ static int head_list_call(struct query *q, int s, pqps_ctx *cs, const struct hip
                                 op->wide ? b + 2 + words : NULL, NULL);
 }
 
-/* One shard's [round][bin] words into a list: bin by bin, the rounds until the first all-ones word. */
+/* One round: one shard's words merged into the host's.  Rows are table-wide, so the minimum word per bin is the answer;
+ * command_id compares (best, row).  (Lists and hipHeadMerge give the same answer; with 40 000 bins they were measured
+ * 4 % slower per query)  The match count in front of the words is added up on the fused path only: the
+ * list call does not write it, and the total is the selection's there. */
+static void first_combine(void *arg, const void *host) {
+    const struct head_call *a = arg;
+    const uint32_t n_bins = a->gp->n_bins;
+    const uint64_t *h = (const uint64_t *)host + 2;
+    uint64_t *out = a->out, *best = a->best;
+    if (a->fused) *a->matches += *(const uint64_t *)host;
+    for (uint32_t k = 0; k < n_bins; k++) {
+        if (h[k] == UINT64_MAX) continue;
+        if (!a->op->wide) { if (h[k] < out[k]) out[k] = h[k]; continue; }
+        const uint64_t hb = h[n_bins + k];
+        if (out[k] == UINT64_MAX || hb < best[k] || (hb == best[k] && h[k] < out[k])) { out[k] = h[k]; best[k] = hb; }
+    }
+}
+
+/* Several rounds: one shard's [round][bin] words into a list: bin by bin, the rounds until the first all-ones word. */
 static void head_combine(void *arg, const void *host) {
     struct head_call *a = arg;
     const uint32_t n_bins = a->gp->n_bins, rounds = a->rounds;
@@ -3670,6 +3499,26 @@ static int group_head_begin(struct engineS *engine, const char *groupColumn, con
     return rc;
 }
 
+/* One word (and its `best`: command_id) into the row, the order key and the key's text as the order column's cell reads.
+ * Inline: it runs once per answer row, and the fills pass it the same columns and kinds every time. */
+static inline int first_word_decode(const struct hipTable *t, const char *what, int oc, int kind, bool desc, uint64_t word, uint64_t best,
+                             unsigned int *row, long long *key, char **text) {
+    char buf[32];
+    const char *cell = buf;
+    if (kind == HIPKIND_U64) {
+        *row = (unsigned int)word;
+        *key = (long long)(best ^ (desc ? UINT64_MAX : 0));
+        snprintf(buf, sizeof buf, "%llu", (unsigned long long)*key);
+    } else {
+        hipFirstKeyDecode(kind, desc, word, key, row);
+        if (kind == HIPKIND_I32) snprintf(buf, sizeof buf, "%d", (int)*key);
+        else if (kind == HIPKIND_BOOL) cell = *key ? "true" : "false";
+        else if (*key < (long long)t->dict[oc].count) cell = t->dict[oc].values[*key];
+        else { fprintf(stderr, "HIP engine: %s: code %lld outside the dictionary\n", what, *key); return -1; }
+    }
+    return (*text = strdup(cell)) ? 0 : oom();
+}
+
 /* The merged entries (ascending bin, then order) into the result: groups with a row only, in bin order. */
 static int group_head_fill(struct hipGroupHeadResult *res, const struct hipTable *t, const uint32_t *bins, const uint64_t *words,
                            const uint64_t *best, uint64_t n, uint32_t n_bins, int32_t lo) {
@@ -3686,30 +3535,67 @@ static int group_head_fill(struct hipGroupHeadResult *res, const struct hipTable
     for (uint32_t k = 0; k < n_bins && rc == 0; k++)
         if (present[k]) { res->offsets[g + 1] = res->offsets[g] + (long long)present[k]; g++; }
     free(present);
-    const int oc = res->orderColumn, kind = res->orderKind;
-    for (uint64_t i = 0; i < n && rc == 0; i++) {
-        char buf[32];
-        const char *text = buf;
-        if (kind == HIPKIND_U64) {
-            res->rows[i] = (unsigned int)words[i];
-            res->orderKeys[i] = (long long)(best[i] ^ (res->descending ? UINT64_MAX : 0));
-            snprintf(buf, sizeof buf, "%llu", (unsigned long long)res->orderKeys[i]);
-        } else {
-            hipFirstKeyDecode(kind, res->descending, words[i], &res->orderKeys[i], &res->rows[i]);
-            if (kind == HIPKIND_I32) snprintf(buf, sizeof buf, "%d", (int)res->orderKeys[i]);
-            else if (kind == HIPKIND_BOOL) text = res->orderKeys[i] ? "true" : "false";
-            else if (res->orderKeys[i] < (long long)t->dict[oc].count) text = t->dict[oc].values[res->orderKeys[i]];
-            else { fprintf(stderr, "HIP engine: first rows per group: code %lld outside the dictionary\n", res->orderKeys[i]); rc = -1; break; }
-        }
-        if (!(res->orderText[i] = strdup(text))) rc = oom();
+    for (uint64_t i = 0; i < n && rc == 0; i++)
+        rc = first_word_decode(t, "first rows per group", res->orderColumn, res->orderKind, res->descending, words[i], best ? best[i] : 0,
+                               &res->rows[i], &res->orderKeys[i], &res->orderText[i]);
+    return rc;
+}
+
+/* One round's words, out[n_bins] (best[n_bins] for command_id), into the result: the bins with a row only, in bin order. */
+static int group_first_fill(struct hipGroupFirstResult *res, const struct hipTable *t, const uint64_t *out, const uint64_t *best,
+                            uint32_t n_bins, int32_t lo) {
+    uint64_t *present = calloc((size_t)n_bins + 1, sizeof *present);
+    if (!present) return oom();
+    for (uint32_t k = 0; k < n_bins; k++) present[k] = out[k] != UINT64_MAX;
+    int rc = group_keys_fill(t, res->groupColumn, res->groupKind, lo, present, n_bins, &res->keys, &res->keyText, &res->numGroups);
+    free(present);
+    if (rc != 0) return -1;
+    const size_t n = (size_t)res->numGroups;
+    res->rows = calloc(n + 1, sizeof *res->rows);
+    res->orderKeys = calloc(n + 1, sizeof *res->orderKeys);
+    res->orderText = calloc(n + 1, sizeof *res->orderText);
+    if (!res->rows || !res->orderKeys || !res->orderText) return oom();
+    size_t g = 0;
+    for (uint32_t k = 0; k < n_bins && rc == 0; k++) {
+        if (out[k] == UINT64_MAX) continue;
+        rc = first_word_decode(t, "first row per group", res->orderColumn, res->orderKind, res->descending, out[k], best ? best[k] : 0,
+                               &res->rows[g], &res->orderKeys[g], &res->orderText[g]);
+        g++;
     }
     return rc;
 }
 
-/* The query itself (caller holds the table shared and the query's lane, group_head_begin has passed). */
-static int group_head_run(struct engineS *engine, struct query *q, const char *groupColumn, struct order_plan *op, long long n,
-                          struct whereClauseS *whereClause, struct hipGroupHeadResult *res) {
+/* The query on every shard (shard_reduce).  a->rounds: that many rounds of the scan; 0: the sort form.  With a->out the one
+ * round's words meet per bin in a->out (first_combine); without it every shard hands a list into a->lists.  *a->matches =
+ * the selection's rows.  The caller sets rounds, limit, out / best or lists / n_lists, and matches; the rest is set here. */
+static int head_reduce(struct query *q, struct group_plan *gp, struct order_plan *op, struct head_call *a) {
     struct hipTable *t = q->t;
+    void *buf[HIP_MAX_SHARDS];
+    if (!a->rounds) {                                                    /* the sort form works on the selection's lists */
+        gp->fused = false;
+        for (int s = 0; s < q->n_shards && gp->c >= 0; s++) gp->gcol[s] = hipTableShard(t, s)->col[gp->c];
+    }
+    op->fused = gp->fused;
+    op->no_key = t->col[op->c].width == 0;
+    for (int s = 0; s < q->n_shards; s++) {
+        const struct hipTable *sh = hipTableShard(t, s);
+        op->kcol[s] = gp->fused && op->c == HIPCOL_SUDO_USED && sh->sudo_bits.data ? sh->sudo_bits : sh->col[op->c];
+    }
+    a->gp = gp; a->op = op; a->buf = buf; a->fused = gp->fused;
+    const struct shard_reduce r = a->rounds
+        ? (struct shard_reduce){ .what = a->out ? "first-row words" : "first-rows words", .bytes = 16 + (size_t)a->rounds * gp->n_bins * (op->wide ? 2 : 1) * sizeof(uint64_t),
+                                 .fused = head_fused_call, .list = head_list_call, .combine = a->out ? first_combine : head_combine }
+        : (struct shard_reduce){ .what = "first-rows sort", .post = head_sort_post };
+    int rc = shard_reduce(q, gp->fused, &r, buf, a);
+    if (rc == 0) rc = a->rc;
+    if (rc == 0 && !gp->fused) *a->matches = q->total;
+    return rc;
+}
+
+/* The first N rows of every group (caller holds the table shared and the query's lane, group_head_begin has passed).
+ * `rounds`: the caller's choice of the rounds form; else the sort form. */
+static int group_head_run(struct engineS *engine, struct query *q, const char *groupColumn, struct order_plan *op, long long n,
+                          bool rounds, struct whereClauseS *whereClause, struct hipGroupHeadResult *res) {
     struct group_plan gp;
     struct head_list lists[HIP_MAX_SHARDS];
     struct hipHeadList in[HIP_MAX_SHARDS];
@@ -3720,27 +3606,8 @@ static int group_head_run(struct engineS *engine, struct query *q, const char *g
     long long kept = 0;
     int rc = group_plan_init(engine, whereClause, q, res->groupColumn, groupColumn, "first rows per group", &gp);
     if (rc == 0 && !gp.empty) {
-        const bool rounds = (unsigned long long)n <= head_round_cap();
-        if (!rounds) {                                                   /* the sort form works on the selection's lists */
-            gp.fused = false;
-            for (int s = 0; s < q->n_shards && gp.c >= 0; s++) gp.gcol[s] = hipTableShard(t, s)->col[gp.c];
-        }
-        op->fused = gp.fused;
-        op->no_key = t->col[op->c].width == 0;
-        for (int s = 0; s < q->n_shards; s++) {
-            const struct hipTable *sh = hipTableShard(t, s);
-            op->kcol[s] = gp.fused && op->c == HIPCOL_SUDO_USED && sh->sudo_bits.data ? sh->sudo_bits : sh->col[op->c];
-        }
-        void *buf[HIP_MAX_SHARDS];
-        struct head_call a = { .gp = &gp, .op = op, .buf = buf, .rounds = rounds ? (uint32_t)n : 0, .limit = (uint64_t)n, .lists = lists,
-                               .n_lists = &n_lists, .matches = &matches, .fused = gp.fused, .rc = 0 };
-        const struct shard_reduce r = rounds
-            ? (struct shard_reduce){ .what = "first-rows words", .bytes = 16 + (size_t)a.rounds * gp.n_bins * (op->wide ? 2 : 1) * sizeof(uint64_t),
-                                     .fused = head_fused_call, .list = head_list_call, .combine = head_combine }
-            : (struct shard_reduce){ .what = "first-rows sort", .post = head_sort_post };
-        rc = shard_reduce(q, gp.fused, &r, buf, &a);
-        if (rc == 0) rc = a.rc;
-        if (rc == 0 && !gp.fused) matches = q->total;
+        rc = head_reduce(q, &gp, op, &(struct head_call){ .rounds = rounds ? (uint32_t)n : 0, .limit = (uint64_t)n, .lists = lists,
+                                                          .n_lists = &n_lists, .matches = &matches });
         for (int s = 0; s < n_lists; s++) {
             in[s] = (struct hipHeadList){ lists[s].n, lists[s].bins, lists[s].words, lists[s].best };
             total += lists[s].n;
@@ -3753,11 +3620,35 @@ static int group_head_run(struct engineS *engine, struct query *q, const char *g
             else if ((kept = hipHeadMerge(in, n_lists, n, bins, words, best)) < 0) rc = -1;
         }
     }
-    if (rc == 0) rc = group_head_fill(res, t, bins, words, best, (uint64_t)kept, gp.empty ? 0u : gp.n_bins, gp.lo);
+    if (rc == 0) rc = group_head_fill(res, q->t, bins, words, best, (uint64_t)kept, gp.empty ? 0u : gp.n_bins, gp.lo);
     if (rc == 0) res->total = (long long)matches;
     for (int s = 0; s < n_lists; s++) head_list_free(&lists[s]);
     free(bins);
     free(words);
+    free(best);
+    return rc;
+}
+
+/* The first row of every group: one round of the same scan, whatever PQPS_HEAD_ROUNDS says (that variable moves the switch
+ * of the N-rows query only).  One word per bin, so the shards' words meet in a dense array and no list is built. */
+static int group_first_run(struct engineS *engine, struct query *q, const char *groupColumn, struct order_plan *op,
+                           struct whereClauseS *whereClause, struct hipGroupFirstResult *res) {
+    struct group_plan gp;
+    uint64_t *out = NULL, *best = NULL, matches = 0;
+    int rc = group_plan_init(engine, whereClause, q, res->groupColumn, groupColumn, "first row per group", &gp);
+    if (rc == 0 && !gp.empty) {
+        out = malloc((size_t)gp.n_bins * sizeof *out);
+        best = op->wide ? malloc((size_t)gp.n_bins * sizeof *best) : NULL;
+        if (!out || (op->wide && !best)) rc = oom();
+        else {
+            memset(out, 0xFF, (size_t)gp.n_bins * sizeof *out);
+            if (best) memset(best, 0xFF, (size_t)gp.n_bins * sizeof *best);
+            rc = head_reduce(q, &gp, op, &(struct head_call){ .rounds = 1, .limit = 1, .out = out, .best = best, .matches = &matches });
+        }
+    }
+    if (rc == 0) rc = group_first_fill(res, q->t, out, best, gp.empty ? 0u : gp.n_bins, gp.lo);
+    if (rc == 0) res->total = (long long)matches;
+    free(out);
     free(best);
     return rc;
 }
@@ -3772,6 +3663,60 @@ static void group_head_clear(struct hipGroupHeadResult *res) {
     free(res->offsets);
 }
 
+static void group_first_clear(struct hipGroupFirstResult *res) {
+    free_group_keys(res->keys, res->keyText, res->numGroups);
+    for (int g = 0; g < res->numGroups && res->orderText; g++) free(res->orderText[g]);
+    free(res->orderText);
+    free(res->orderKeys);
+    free(res->rows);
+}
+
+struct hipGroupFirstResult *executeQueryGroupFirstHIP(struct engineS *engine, const char *groupColumn, const char *orderColumn,
+                                                      bool descending, struct whereClauseS *whereClause) {
+    const double t0 = now_seconds();
+    struct hipGroupFirstResult *res = calloc(1, sizeof *res);
+    if (!res) { oom(); return NULL; }
+    struct order_plan op;
+    if (group_first_begin(engine, groupColumn, orderColumn, descending, res, &op) != 0) return res;
+    struct query q;
+    if (!query_open(engine, &q)) return res;                             /* reason on stderr */
+    if (group_first_run(engine, &q, groupColumn, &op, whereClause, res) == 0) res->success = true;
+    query_close(&q);
+    res->queryTime = now_seconds() - t0;
+    return res;
+}
+
+void freeGroupFirstResultHIP(struct hipGroupFirstResult *res) {
+    if (!res) return;
+    group_first_clear(res);
+    free(res);
+}
+
+struct hipColumnarResult *executeQuerySelectGroupFirstHIP(struct engineS *engine, const char **selectItems, int numSelectItems,
+                                                          struct whereClauseS *whereClause, const char *groupColumn,
+                                                          const char *orderColumn, bool descending, long long *matches) {
+    if (matches) *matches = 0;
+    struct hipColumnarResult *res = columnar_shell(engine, &selectItems, &numSelectItems);
+    if (!engine || !engine->record_block) return res;
+    const double t0 = now_seconds();
+    struct hipGroupFirstResult gf;
+    struct order_plan op;
+    memset(&gf, 0, sizeof gf);
+    if (group_first_begin(engine, groupColumn, orderColumn, descending, &gf, &op) != 0) return res;
+    struct query q;
+    if (!query_open(engine, &q)) return res;                             /* reason on stderr */
+    int rc = group_first_run(engine, &q, groupColumn, &op, whereClause, &gf);
+    const uint64_t n = rc == 0 ? (uint64_t)gf.numGroups : 0;
+    if (rc == 0) rc = project_listed_rows(&q, gf.rows, n, selectItems, numSelectItems, res);
+    query_close(&q);
+    res->numRecords = rc == 0 ? (int)n : 0;
+    res->queryTime = now_seconds() - t0;
+    res->success = rc == 0;
+    if (rc == 0 && matches) *matches = gf.total;
+    group_first_clear(&gf);
+    return res;
+}
+
 struct hipGroupHeadResult *executeQueryGroupHeadHIP(struct engineS *engine, const char *groupColumn, const char *orderColumn,
                                                     bool descending, long long n, struct whereClauseS *whereClause) {
     const double t0 = now_seconds();
@@ -3781,7 +3726,8 @@ struct hipGroupHeadResult *executeQueryGroupHeadHIP(struct engineS *engine, cons
     if (group_head_begin(engine, groupColumn, orderColumn, descending, n, res, &op) != 0) return res;
     struct query q;
     if (!query_open(engine, &q)) return res;                             /* reason on stderr */
-    if (group_head_run(engine, &q, groupColumn, &op, n, whereClause, res) == 0) res->success = true;
+    if (group_head_run(engine, &q, groupColumn, &op, n, (unsigned long long)n <= head_round_cap(), whereClause, res) == 0)
+        res->success = true;
     query_close(&q);
     res->queryTime = now_seconds() - t0;
     return res;
@@ -3799,17 +3745,8 @@ struct hipColumnarResult *executeQuerySelectGroupHeadHIP(struct engineS *engine,
                                                          long long **offsets) {
     if (matches) *matches = 0;
     if (offsets) *offsets = NULL;
-    struct hipColumnarResult *res = calloc(1, sizeof *res);
-    if (!res) { perror("Failed to allocate memory for result set"); exit(EXIT_FAILURE); }
+    struct hipColumnarResult *res = columnar_shell(engine, &selectItems, &numSelectItems);
     if (!engine || !engine->record_block) return res;
-    if (selectItems == NULL || numSelectItems == 0) { selectItems = (const char **)k_all_columns; numSelectItems = 12; }
-    res->numColumns = numSelectItems;
-    res->columnNames = calloc((size_t)numSelectItems, sizeof(char *));
-    res->columnKinds = calloc((size_t)numSelectItems, sizeof(int));
-    res->values = calloc((size_t)numSelectItems, sizeof(void *));
-    res->dictionaries = calloc((size_t)numSelectItems, sizeof(*res->dictionaries));
-    res->dictionarySizes = calloc((size_t)numSelectItems, sizeof(int));
-    if (!res->columnNames || !res->columnKinds || !res->values || !res->dictionaries || !res->dictionarySizes) { perror("Failed to allocate memory for result set"); exit(EXIT_FAILURE); }
     const double t0 = now_seconds();
     struct hipGroupHeadResult gh;
     struct order_plan op;
@@ -3817,7 +3754,7 @@ struct hipColumnarResult *executeQuerySelectGroupHeadHIP(struct engineS *engine,
     if (group_head_begin(engine, groupColumn, orderColumn, descending, n, &gh, &op) != 0) return res;
     struct query q;
     if (!query_open(engine, &q)) return res;                             /* reason on stderr */
-    int rc = group_head_run(engine, &q, groupColumn, &op, n, whereClause, &gh);
+    int rc = group_head_run(engine, &q, groupColumn, &op, n, (unsigned long long)n <= head_round_cap(), whereClause, &gh);
     const uint64_t rows = rc == 0 ? (uint64_t)gh.offsets[gh.numGroups] : 0;
     if (rc == 0) rc = project_listed_rows(&q, gh.rows, rows, selectItems, numSelectItems, res);
     query_close(&q);

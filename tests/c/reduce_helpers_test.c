@@ -66,7 +66,7 @@ static void first_rows(uint32_t n) {
             memset(best, 0xFF, ((size_t)n + 1) * 8);
             memset(h, 0xFF, (2 + 2 * (size_t)n) * 8);
             matches = 0;
-            struct first_call a = { &gp, &op, NULL, out, best, &matches, fused };
+            struct head_call a = { .gp = &gp, .op = &op, .rounds = 1, .out = out, .best = best, .matches = &matches, .fused = fused };
             h[0] = 0;
             first_combine(&a, h);                                        /* words of all ones in every bin */
             int groups = 0;

@@ -123,6 +123,39 @@ def test_synthetic(n):
         eng.close()
 
 
+@pytest.mark.gpu
+def test_rounds_form_whatever_the_round_cap_says():
+    """group_first is one round of the N-rows driver, always in its rounds form: PQPS_HEAD_ROUNDS moves the switch of
+    group_head only.  With the variable unset and at 0 the answers are the model's and a scan-mode WHERE runs
+    first_scan_kernel, while group_head(.., 1) at 0 still takes the sort form."""
+    n = 4099
+    host = q.HostSynth(n, full=True)
+    eng = pq.HipEngine.synthetic(n)
+    chain = grp.SYNTH_CHAINS["risk_gt2"]
+    rows = np.asarray(host.oracle_scan(chain, nthreads=min(16, os.cpu_count() or 1)), dtype=np.int64)
+    last = lambda: pq.lib().pqps_last_kernel().decode()
+    saved = os.environ.pop("PQPS_HEAD_ROUNDS", None)
+    try:
+        for cap in (None, "0"):
+            if cap is not None:
+                os.environ["PQPS_HEAD_ROUNDS"] = cap
+            for group in ("host_name", "risk_level", "shell_type", "sudo_used", None):
+                for column, desc in (("exit_code", True), ("command_id", False), ("user_name", False)):
+                    got, total = eng.group_first(group, column, chain, desc)
+                    assert "first_scan_kernel" in last(), (cap, group, column, last())
+                    assert total == len(rows), (cap, group, column, desc)
+                    assert got == m.synth_expected(host, rows, group, column, desc), (cap, group, column, desc)
+        first, total = eng.group_first("host_name", "exit_code", chain, True)
+        one, total1 = eng.group_head("host_name", "exit_code", 1, chain, True)
+        assert "first_scan_kernel" not in last() and "head_scan_kernel" not in last(), last()
+        assert total1 == total and one == [(key, [(row, text)]) for key, row, text in first]
+    finally:
+        os.environ.pop("PQPS_HEAD_ROUNDS", None)
+        if saved is not None:
+            os.environ["PQPS_HEAD_ROUNDS"] = saved
+        eng.close()
+
+
 def edge_columns(n, rng, users, **over):
     """from_columns input: user_name a dictionary of `users` words, shell_type of 4, the other strings single-valued."""
     words = [b"w%06d" % i for i in range(users)]
