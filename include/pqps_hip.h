@@ -141,7 +141,9 @@ int  pqps_ctx_sync(pqps_ctx *ctx, void *stream);
  * "list16_min" / "list16_min_u8" (a step with more matches leaves a 16-bit list), "list_max" (a step with at
  * most this many matches leaves 16-bit entries in its slot; 0 .. 128), "tiny_max" (... in its tiny word; 0 .. 3),
  * "expand_lag" / "sum_lag" (groups),
- * "tune" (bits); value < 0 restores the default. */
+ * "tune" (bits), "steps" (chain scans, ID output and COUNT: 0 = one step per wave, 1 = two adjacent steps per wave where
+ * the shape has such a kernel -- a lone byte column, a 12-bit packed column alone or with a plane);
+ * value < 0 restores the default. */
 int  pqps_ctx_set_option(pqps_ctx *ctx, const char *name, long value);
 int  pqps_device_count(void);
 int  pqps_ctx_device(pqps_ctx *ctx);

@@ -2421,10 +2421,18 @@ __global__ __launch_bounds__(kBlock, MODE == MODE_IDS ? (wcost(W0) + wcost(W1) +
 // Measured, fraction of 8 TB/s at 100 M / 1 B rows: a lone 1-byte column wants 2 (COUNT 0.71 / 0.86;
 // 1 step: 0.56 / 0.48; 4: 0.72 / 0.86; 8: worse) -- 1 KB per wave and step is too little in flight; from
 // 2 bytes per row on, 1 is best (u16+u8: 0.83 / 0.82 against 0.80 / 0.82 with 2 and 0.77 / 0.80 with 4).
-#ifndef PQPS_MULTI_BYTES
-#define PQPS_MULTI_BYTES 1
-#endif
-constexpr int chain_steps(int w0, int w1, int w2) { return wcost(w0) + wcost(w1) + wcost(w2) <= PQPS_MULTI_BYTES ? 2 : 1; }
+// The two shapes with a 12-bit packed column read 1.5 / 1.625 bytes per row -- 1.5 - 1.6 KB per wave and step, as little
+// in flight as the lone byte column -- and their two steps are 12 / 14 raw registers, where the u16 shapes' 16 / 18 push
+// the ID kernel over its 64-VGPR cap ((2,B,0) IDs with 2 steps: 103 us against 47).
+// So S is chosen BY SHAPE, not by bytes per row.  Every shape has its S = 1 instance and, where chain_steps() > 1, that
+// one beside it (find_spec_nt); which of the two a launch takes is decided at run time (steps_default, the context
+// option "steps", PQPS_CHAIN_MULTI in development builds).  To try another S for one shape on a development build,
+// return it here for that shape (e.g. `if (w0 == 2 && w1 == kBitPlane && w2 == 0) return 2;`): a tile is 4 S steps, must
+// divide a group and fit FusedShared::tile_cnt / tile_tiny (16 steps), so S is 1, 2 or 4.
+constexpr int chain_steps(int w0, int w1, int w2) {
+    if (w0 == kPacked12 && (w1 == 0 || w1 == kBitPlane) && w2 == 0) return 2;
+    return w0 == 1 && w1 == 0 && w2 == 0 ? 2 : 1;
+}
 
 #ifndef PQPS_CHAIN_WGS
 #define PQPS_CHAIN_WGS 8
@@ -2442,6 +2450,7 @@ __global__ __launch_bounds__(kBlock, MODE == MODE_IDS ? PQPS_CHAIN_WGS : 1) void
     RawStep<W0, W1, W2, RPL, U> A[S];
     if constexpr (MODE == MODE_IDS) {
         constexpr int TS = kWaves * S;                          // a tile = S adjacent steps per wave
+        static_assert(TS <= 16 && kGroupSteps % TS == 0 && kGroupSteps / TS >= 2, "tile_cnt holds 16 steps; a group has a first and a second tile (sum duty)");
         __shared__ FusedShared sh;
         PQPS_STAMP_START(a);
         zero_other_ctl(a);

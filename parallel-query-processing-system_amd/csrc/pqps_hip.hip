@@ -538,7 +538,7 @@ struct pqps_ctx {
     uint64_t *check_dev;        // [2] pqps_ids_checksum
     // per-context overrides of the launch parameters (pqps_ctx_set_option: A/B runs inside ONE process, where the physical
     // placement of the table is the same for every variant); -1 = the default
-    long opt_list16, opt_list16_min, opt_list16_min_u8, opt_list_max, opt_list_max_u8, opt_tiny_max, opt_expand_lag, opt_sum_lag, opt_tune, opt_wide_front;
+    long opt_list16, opt_list16_min, opt_list16_min_u8, opt_list_max, opt_list_max_u8, opt_tiny_max, opt_expand_lag, opt_sum_lag, opt_tune, opt_wide_front, opt_steps;
     void *sort_tmp;
     size_t sort_tmp_bytes;
     uint32_t *group_parts;      // every fused scan (group / aggregate / distinct): its workgroups' partial results (grow_group_parts)
@@ -792,6 +792,14 @@ inline bool valu_chain_default(int w0, int w1, int w2, int mode, uint64_t n_rows
     return mode == MODE_IDS && ((w0 == 2 && (w1 == 1 || w1 == kBitPlane)) || (w0 == kPacked12 && w1 == kBitPlane)) && w2 == 0 && n_rows < kListAreaBelowGroups * (uint64_t)kGroupSteps * kStepRows;
 }
 
+// Steps per wave of a chain launch: true = the shape's chain_steps(), false = 1.  A lone byte column takes its two steps
+// everywhere (comment above chain_steps()).  The packed shapes: see DESIGN section 4, "Round 7", for the measurements
+// behind each answer.
+inline bool steps_default(int w0, int w1, int w2, int mode, uint64_t n_rows) {
+    (void)mode; (void)n_rows;
+    return chain_steps(w0, w1, w2) > 1;
+}
+
 template <int MODE, int A, int B, int C, int S, bool NT>
 eval_fn chain_variant(int ev) {
     if constexpr (B == 0 && C == 0) {
@@ -848,13 +856,14 @@ eval_fn find_spec(int w0, int w1, int w2, bool chain, bool multi_step, bool nt, 
 
 // `a` must already carry the chain classification of fill_args(); sets a.streaming.
 template <int MODE>
-eval_fn pick_eval(const pqps_column *cols, uint32_t n_cols, const pqps_predicate *pred, EvalArgs &a, uint64_t n_rows) {
+eval_fn pick_eval(const pqps_column *cols, uint32_t n_cols, const pqps_predicate *pred, EvalArgs &a, uint64_t n_rows, long opt_steps) {
     set_streaming(a, cols, n_cols, n_rows);
     if (n_cols >= 1 && n_cols <= 3 && pred->n_leaves >= 1 && pred->n_leaves <= PQPS_TT_LEAVES) {
         const int w0 = spec_width(cols[0].width), w1 = n_cols > 1 ? spec_width(cols[1].width) : 0, w2 = n_cols > 2 ? spec_width(cols[2].width) : 0;
-        // several steps per iteration only where chain_steps() says so (a lone 1-byte column)
+        // several steps per iteration only where chain_steps() says so, and there by default where measured faster; the
+        // context option "steps" (0 / 1) and, in development builds, PQPS_CHAIN_MULTI force either side
         static const char *force = tuning_env("PQPS_CHAIN_MULTI");
-        const bool multi = force ? atoi(force) != 0 : true;
+        const bool multi = opt_steps >= 0 ? opt_steps != 0 : (force ? atoi(force) != 0 : steps_default(w0, w1, w2, MODE, n_rows));
         // one comparison on one column (EV 1), or -- where measured faster -- a chain over narrow columns (EV 2), on the
         // vector unit: see RawStep::one_leaf / valu_leaf
         static const char *valu_env = tuning_env("PQPS_VALU_CHAIN");                 // tuning runs: 0 / 1 = ballots / vector unit for every eligible chain
@@ -1214,9 +1223,10 @@ struct ScanRequest {
 };
 
 // Checks in the order every entry point has had them: the ID buffer, the u32 range of the IDs (ID output only), the
-// predicate.  Then the kernel's args and the instantiation that evaluates them (COUNT: out_ids NULL, capacity 0).
+// predicate.  Then the kernel's args and the instantiation that evaluates them (COUNT: out_ids NULL, capacity 0;
+// `opt_steps`: the "steps" option of the caller's context).
 int scan_request(ScanRequest &r, int mode, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, uint32_t id_base,
-                 const pqps_predicate *pred, uint32_t *out_ids, uint64_t out_capacity) {
+                 const pqps_predicate *pred, uint32_t *out_ids, uint64_t out_capacity, long opt_steps) {
     if (!out_ids && out_capacity) return fail(PQPS_EINVAL, "out_ids is NULL");
     if (mode == MODE_IDS && (n_rows > 0xFFFFFFFFull || (uint64_t)id_base + n_rows > 0x100000000ull))
         return fail(PQPS_EINVAL, "row IDs are u32: id_base + n_rows must be <= 2^32");
@@ -1224,7 +1234,7 @@ int scan_request(ScanRequest &r, int mode, const pqps_column *cols, uint32_t n_c
     if (rc) return rc;
     fill_args(r.a, cols, n_cols, pred);
     r.a.n_rows = n_rows;
-    r.k1 = mode == MODE_IDS ? pick_eval<MODE_IDS>(cols, n_cols, pred, r.a, n_rows) : pick_eval<MODE_COUNT>(cols, n_cols, pred, r.a, n_rows);
+    r.k1 = mode == MODE_IDS ? pick_eval<MODE_IDS>(cols, n_cols, pred, r.a, n_rows, opt_steps) : pick_eval<MODE_COUNT>(cols, n_cols, pred, r.a, n_rows, opt_steps);
     if (!r.k1) return fail(PQPS_EINVAL, "no specialised kernel reads this shape with a 12-bit packed column");
     r.mode = mode; r.n_rows = n_rows; r.id_base = id_base; r.out_ids = out_ids; r.out_cap = out_capacity;
     return PQPS_OK;
@@ -1283,7 +1293,7 @@ int create_ctx(int device, bool lane, pqps_ctx **out) {
     ctx->status_host = nullptr; ctx->status_dev = nullptr;
     ctx->parity = 0; ctx->epoch = 0; ctx->hand_groups = 0; ctx->needs_reset.store(false);
     ctx->check_dev = nullptr;
-    ctx->opt_list16 = ctx->opt_list16_min = ctx->opt_list16_min_u8 = ctx->opt_list_max = ctx->opt_list_max_u8 = ctx->opt_tiny_max = ctx->opt_expand_lag = ctx->opt_sum_lag = ctx->opt_tune = ctx->opt_wide_front = -1;
+    ctx->opt_list16 = ctx->opt_list16_min = ctx->opt_list16_min_u8 = ctx->opt_list_max = ctx->opt_list_max_u8 = ctx->opt_tiny_max = ctx->opt_expand_lag = ctx->opt_sum_lag = ctx->opt_tune = ctx->opt_wide_front = ctx->opt_steps = -1;
     ctx->sort_tmp = nullptr;
     ctx->sort_tmp_bytes = 0;
     ctx->group_parts = nullptr;
@@ -1410,6 +1420,7 @@ int pqps_ctx_set_option(pqps_ctx *ctx, const char *name, long value) {
         {"list_max", &ctx->opt_list_max}, {"tiny_max", &ctx->opt_tiny_max},
         {"expand_lag", &ctx->opt_expand_lag}, {"sum_lag", &ctx->opt_sum_lag}, {"tune", &ctx->opt_tune},
         {"wide_front", &ctx->opt_wide_front},                   // 0: the wide bins take their global atomics without the LDS front
+        {"steps", &ctx->opt_steps},                             // chain scans: 0 = one step per wave, 1 = the shape's chain_steps() (ID output and COUNT)
     };
     for (auto &o : opts)
         if (strcmp(o.name, name) == 0) { *o.slot = value < 0 ? -1 : value; return PQPS_OK; }
@@ -1493,7 +1504,7 @@ int pqps_filter_scan(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols,
                      uint32_t *out_ids, uint64_t out_capacity, uint64_t *out_count, void *stream) {
     if (!ctx || !out_count) return fail(PQPS_EINVAL, "ctx/out_count is NULL");
     ScanRequest r;
-    const int rc = scan_request(r, MODE_IDS, cols, n_cols, n_rows, id_base, pred, out_ids, out_capacity);
+    const int rc = scan_request(r, MODE_IDS, cols, n_cols, n_rows, id_base, pred, out_ids, out_capacity, ctx->opt_steps);
     return rc ? rc : r.run(ctx, pick_stream(ctx, stream), out_count);
 }
 
@@ -1501,7 +1512,7 @@ int pqps_filter_count(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols,
                       uint64_t n_rows, const pqps_predicate *pred, uint64_t *out_count, void *stream) {
     if (!ctx || !out_count) return fail(PQPS_EINVAL, "ctx/out_count is NULL");
     ScanRequest r;
-    const int rc = scan_request(r, MODE_COUNT, cols, n_cols, n_rows, 0, pred, nullptr, 0);
+    const int rc = scan_request(r, MODE_COUNT, cols, n_cols, n_rows, 0, pred, nullptr, 0, ctx->opt_steps);
     return rc ? rc : r.run(ctx, pick_stream(ctx, stream), out_count);
 }
 
@@ -2564,7 +2575,7 @@ int pqps_exchange_select(pqps_exchange *x, const pqps_column *cols, uint32_t n_c
     if (slot >= x->ring) return fail(PQPS_EINVAL, "slot %u >= ring %u", slot, x->ring);
     ExchangeSlot &sl = x->slots[slot];
     ScanRequest r;                                               // (the slot's own ID area: this rank's list behind its count)
-    int rc = scan_request(r, MODE_IDS, cols, n_cols, n_rows, id_base, pred, sl.local + kSlotHeaderWords, x->cap);
+    int rc = scan_request(r, MODE_IDS, cols, n_cols, n_rows, id_base, pred, sl.local + kSlotHeaderWords, x->cap, x->ctx->opt_steps);
     if (rc) return rc;
     rc = exchange_claim(x, sl);
     if (rc) return rc;
@@ -2638,7 +2649,7 @@ int pqps_exchange_count(pqps_exchange *x, const pqps_column *cols, uint32_t n_co
     if (slot >= x->ring) return fail(PQPS_EINVAL, "slot %u >= ring %u", slot, x->ring);
     ExchangeSlot &sl = x->slots[slot];
     ScanRequest r;
-    int rc = scan_request(r, MODE_COUNT, cols, n_cols, n_rows, 0, pred, nullptr, 0);
+    int rc = scan_request(r, MODE_COUNT, cols, n_cols, n_rows, 0, pred, nullptr, 0, x->ctx->opt_steps);
     if (rc) return rc;
     rc = exchange_claim(x, sl);
     if (rc) return rc;
@@ -2800,7 +2811,7 @@ int qstream_issue(pqps_qstream *q, uint32_t slot, int mode, const pqps_column *c
                   const pqps_predicate *pred, uint32_t *out_ids, uint64_t out_capacity, uint64_t *out_count, void *scan_stream) {
     if (!q || !out_count) return fail(PQPS_EINVAL, "qstream/out_count is NULL");
     ScanRequest r;
-    int rc = scan_request(r, mode, cols, n_cols, n_rows, id_base, pred, out_ids, out_capacity);
+    int rc = scan_request(r, mode, cols, n_cols, n_rows, id_base, pred, out_ids, out_capacity, q->ctx->opt_steps);
     if (rc) return rc;
     pqps_ctx *c = nullptr; hipStream_t s = nullptr;
     rc = qstream_begin(q, slot, n_rows, pick_stream(q->ctx, scan_stream), q->ctx->timing, &c, &s, mode == MODE_IDS);

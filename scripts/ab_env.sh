@@ -4,7 +4,7 @@
 #   PQPS_NT_LOADS=0|1            plain / streaming loads (default: by scan footprint, 320 MiB)
 #   PQPS_K1_ITERS=<float>        grid of K1 as iterations per wave (default: 1 when streaming, 1.5 otherwise)
 #   PQPS_K1_BLOCKS_PER_CU=<int>  grid cap of K1 per CU
-#   PQPS_CHAIN_MULTI=0|1         several steps per loop iteration for a lone 1-byte column
+#   PQPS_CHAIN_MULTI=0|1         one / two steps per wave: a lone 1-byte column, a 12-bit packed column alone or with a plane
 #   PQPS_SUM_LAG, PQPS_EXPAND_LAG, PQPS_EXPAND_SPIN_LIMIT, PQPS_QSTREAM_LANES: see scripts/README.md
 var=$1; shift
 vals=()
