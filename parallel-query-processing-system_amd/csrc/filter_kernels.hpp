@@ -114,7 +114,8 @@ struct EvalArgs {
     uint32_t negmask;
     uint32_t streaming;              // host side only: the scan outgrows the Infinity Cache (grid + load policy)
     uint32_t steps_per_iter;         // host side only: S of the chosen kernel (grid sizing)
-    uint32_t valu_chain;             // host side only: the one-leaf vector-unit kernel variant was chosen
+    uint32_t eq12;                   // the 12-bit packed column's ONE leaf is a wanted equality on a code <= 0xFFF, in an AND: its steps are
+                                     // tested on the raw dwords first (packed12_eq.hpp).  (In the place of a host-side word nothing read.)
     uint32_t chain;                  // 0: general tree; 1: AND of leaves; 2: NOT(AND) = OR form (spec kernels)
     uint32_t chain_want;             // bit k: raw window hit that leaf slot k must have inside the AND
     uint8_t width_log2[PQPS_MAX_COLUMNS];
@@ -2213,7 +2214,10 @@ __device__ __forceinline__ uint32_t chain_bits(CArgs &a, int slot, const RawCol<
     return keep;
 }
 
-// ... and of a 12-bit packed column (the first column of its two shapes): the same, from the extracted values
+// ... and of a 12-bit packed column (the first column of its two shapes): the same, from the extracted values.  What the
+// compiler makes of a leaf here is a compare, a select and a third of an OR per row, with waits for the VCC hazard in
+// between: ~85 issue slots per step with the extraction -- which is why a step is first tested on its raw dwords where
+// the predicate allows it (Eq12 below), and comes here only with a candidate.
 template <int RPL, int U>
 __device__ __forceinline__ uint32_t chain_rows(CArgs &a, int slot, const RawCol<kPacked12, RPL, U> &raw) {
     const uint32_t kb = a.leaf_begin[slot], ke = a.leaf_begin[slot + 1];
@@ -2225,6 +2229,21 @@ __device__ __forceinline__ uint32_t chain_rows(CArgs &a, int slot, const RawCol<
         keep &= ((a.chain_want >> k) & 1u) ? h : ~h;
     }
     return keep;
+}
+
+// The raw-dword test of a packed column's steps (EvalArgs::eq12): the code in all eight fields of a chunk, built once per
+// wave from a.lo[0] while the column loads are in flight.  93 % of S1's steps hold no row with the wanted code: such a step
+// costs two packed12_any_eq() and a ballot, and neither extraction nor leaf loop nor plane.
+struct Eq12 {
+    uint32_t on;
+    uint32_t pat[3];
+};
+// (kernels that have the test: one comparison on the packed column alone, ID output and COUNT, and the vector-unit chain of
+// packed column + plane as ID output.  A (P,0,0) launch with several leaves takes EV 2 or EV 0 and never meets the condition;
+// COUNT of (P,B,0) takes the ballot kernel (valu_chain_default), so its EV 2 instance -- which only a tuning run of a
+// development build can reach -- stays as it was.)
+constexpr bool eq12_kernel(int mode, int w0, int w1, int w2, int ev) {
+    return w0 == kPacked12 && w2 == 0 && ((ev == 1 && w1 == 0) || (ev == 2 && w1 == kBitPlane && mode == MODE_IDS));
 }
 
 constexpr int log2i(int x) { return x <= 1 ? 0 : 1 + log2i(x / 2); }
@@ -2240,6 +2259,17 @@ struct RawStep {
         r0.template load<NT>(a.col[0], lane_row0);
         if constexpr (W1 != 0) r1.template load<NT>(a.col[1], lane_row0);
         if constexpr (W2 != 0) r2.template load<NT>(a.col[2], lane_row0);
+    }
+    // The S1 shapes -- a 2-byte or 12-bit packed column with the plane behind it: their vector-unit chain kernels load a
+    // step that does not exist (past the table's last) from the last one instead of skipping its loads, see the kernel.
+    static constexpr bool kS1Shape = W1 == kBitPlane && W2 == 0 && wcost(W0) == 2;
+    // eq12: does any row of the step's two chunks carry the code?  (wave-wide)
+    __device__ __forceinline__ bool eq12_candidates(const Eq12 &eq) const {
+        static_assert(W0 == kPacked12 && U == 2, "a packed column's step is two chunks");
+        uint32_t e0[3], e1[3];
+        packed12_eq(r0.c[0].d, eq.pat, e0);
+        packed12_eq(r0.c[1].d, eq.pat, e1);
+        return __ballot((e0[0] | e0[1] | e0[2] | e1[0] | e1[1] | e1[2]) != 0) != 0;
     }
     template <int MODE, int H>
     __device__ __forceinline__ void eval_chain_half(CArgs &a, uint32_t &cnt, uint32_t &mbits) const {
@@ -2289,7 +2319,12 @@ struct RawStep {
     // EV 0: ballots into SGPR planes (any chain); EV 1: ONE comparison on ONE column on the vector unit; EV 2: a chain over
     // narrow columns on the vector unit (valu_leaf).
     template <int MODE, int EV>
-    __device__ __forceinline__ void eval_chain_step(CArgs &a, uint32_t &cnt, uint32_t &mbits, uint32_t &lane_total) const {
+    __device__ __forceinline__ void eval_chain_step(CArgs &a, const Eq12 &eq, uint32_t &cnt, uint32_t &mbits, uint32_t &lane_total) const {
+        if constexpr (eq12_kernel(MODE, W0, W1, W2, EV)) {
+            // no row of the step has the code: no match (cnt and mbits are 0 as the caller passed them, nothing to add to a
+            // COUNT).  With a candidate the step takes the path below, unchanged.
+            if (eq.on && !eq12_candidates(eq)) return;
+        }
         if constexpr (EV == 1) {
             static_assert(W1 == 0 && W2 == 0, "one column");
             uint32_t m = 0;
@@ -2312,7 +2347,7 @@ struct RawStep {
             if constexpr (W0 == kPacked12) {
                 // A packed column's 16 values are extracted, not picked out of the raw dwords by the compare itself: with
                 // valu_leaf's 16 row registers on top of them the kernel spills more than its u16 twin.  So a leaf's hits go
-                // straight into one 16-bit mask (compare + add-with-carry per row, as many VALU as compare + select).
+                // straight into one 16-bit mask (chain_rows: a compare, a select and a third of an OR per row as compiled).
                 m = chain_rows(a, 0, r0);
             } else {
                 uint32_t t[16];
@@ -2354,11 +2389,14 @@ struct RawStep {
 // The kernel arguments the first loads depend on, fetched together at the very top: left to itself the
 // compiler fetches them where first used, three dependent scalar-load round trips (~0.6 us) before a
 // wave has a byte of the table in flight -- which a one-shot workgroup pays on every launch.
-#define PQPS_HOIST_KERNARGS(a)                                                                        \
-    asm volatile("" :: "s"((a).n_rows), "s"((a).col[0]), "s"((a).col[1]), "s"((a).col[2]), "s"(gridDim.x),  \
+#define PQPS_HOIST_OPERANDS(a)                                                                        \
+    "s"((a).n_rows), "s"((a).col[0]), "s"((a).col[1]), "s"((a).col[2]), "s"(gridDim.x),  \
                  "s"((a).masks), "s"((a).chain), "s"((a).chain_want), "s"((a).negmask), "s"((a).lag), "s"((a).sum_lag), "s"((a).counts),     \
                  "s"((uint32_t)(a).leaf_begin[0]), "s"((uint32_t)(a).leaf_begin[1]), "s"((uint32_t)(a).leaf_begin[2]), \
-                 "s"((uint32_t)(a).leaf_begin[3]), "s"((a).lists), "s"((a).list_max), "s"((a).list_max_u8), "s"((a).list16_min), "s"((a).list16_min_u8), "s"((a).tiny_max))
+                 "s"((uint32_t)(a).leaf_begin[3]), "s"((a).lists), "s"((a).list_max), "s"((a).list_max_u8), "s"((a).list16_min), "s"((a).list16_min_u8), "s"((a).tiny_max)
+#define PQPS_HOIST_KERNARGS(a) asm volatile("" :: PQPS_HOIST_OPERANDS(a))
+// ... and with them, in the same round, the two words the raw-dword test of a packed column is set up from (Eq12)
+#define PQPS_HOIST_KERNARGS_EQ12(a) asm volatile("" :: "s"((a).eq12), "s"((uint32_t)(a).lo[0]), PQPS_HOIST_OPERANDS(a))
 
 // General tree of <= 6 leaves (row-mask path).
 template <int MODE, int W0, int W1, int W2, bool NT>
@@ -2442,12 +2480,30 @@ __global__ __launch_bounds__(kBlock, MODE == MODE_IDS ? PQPS_CHAIN_WGS : 1) void
     CArgs &a = kernel_args();
     constexpr int RPL = rows_per_lane(W0);
     constexpr int U = 16 / RPL;
-    PQPS_HOIST_KERNARGS(a);
+    Eq12 eq = { 0u, { 0u, 0u, 0u } };
+    if constexpr (eq12_kernel(MODE, W0, W1, W2, EV)) {
+        PQPS_HOIST_KERNARGS_EQ12(a);
+        // the pattern is scalar work on two kernel arguments: done here, ahead of the first load, not where the first
+        // step's bytes have just arrived
+        eq.on = a.eq12;
+        packed12_pattern((uint32_t)a.lo[0] & 0xFFFu, eq.pat);
+        asm volatile("" : "+s"(eq.on), "+s"(eq.pat[0]), "+s"(eq.pat[1]), "+s"(eq.pat[2]));
+    } else {
+        PQPS_HOIST_KERNARGS(a);
+    }
     const uint64_t n_rows = a.n_rows;
     const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const uint64_t full_steps = n_rows / kStepRows;
     const uint64_t lane_off = lane * RPL;
     RawStep<W0, W1, W2, RPL, U> A[S];
+    // A step past the table's last has no loads -- a uniform guard.  In the kernels named here it is loaded all the same,
+    // from the last step (whose bytes another wave asks for anyway), and not evaluated: with the guard every step's loads
+    // are a basic block of their own, the compiler moves bits16()'s shift of a plane's second chunk up into that block,
+    // behind the load, and with it a wait for the plane bytes -- a full memory latency -- in front of the next step's loads
+    // and the sum-duty load; and where paths with different numbers of loads meet, every later wait is for the shortest
+    // path's count, i.e. for nearly everything.  Without the guard all S x columns loads and the duty load issue back to
+    // back, and the first step is evaluated while the second is still in flight.
+    constexpr bool kAllLoads = eq12_kernel(MODE, W0, W1, W2, EV) || (MODE == MODE_IDS && EV == 2 && RawStep<W0, W1, W2, RPL, U>::kS1Shape);
     if constexpr (MODE == MODE_IDS) {
         constexpr int TS = kWaves * S;                          // a tile = S adjacent steps per wave
         static_assert(TS <= 16 && kGroupSteps % TS == 0 && kGroupSteps / TS >= 2, "tile_cnt holds 16 steps; a group has a first and a second tile (sum duty)");
@@ -2464,8 +2520,11 @@ __global__ __launch_bounds__(kBlock, MODE == MODE_IDS ? PQPS_CHAIN_WGS : 1) void
         if (role.kind != ROLE_SCAN || (uint64_t)role.index * TS >= ex.steps) return;
         const uint64_t step0 = (uint64_t)role.index * TS + (uint64_t)wv * S;
 #pragma unroll
-        for (int i = 0; i < S; i++)
-            if (step0 + i < ex.steps) A[i].template load<NT>(a, (step0 + i) * kStepRows + lane_off);        // uniform guard
+        for (int i = 0; i < S; i++) {
+            // (ex.steps >= 1 here: a tile whose first step is past the end has returned above)
+            if constexpr (kAllLoads) A[i].template load<NT>(a, (step0 + i < ex.steps ? step0 + i : ex.steps - 1) * kStepRows + lane_off);
+            else if (step0 + i < ex.steps) A[i].template load<NT>(a, (step0 + i) * kStepRows + lane_off);   // uniform guard
+        }
         const SumDuty duty = sum_duty_load<kGroupSteps / TS>(a, role.index, wv, lane);   // behind the column loads, consumed after the tile's work
         if constexpr (RPL < 16) zero_tiny_words(sh, wv * S, S);
         uint32_t any = 0;
@@ -2474,7 +2533,7 @@ __global__ __launch_bounds__(kBlock, MODE == MODE_IDS ? PQPS_CHAIN_WGS : 1) void
             const uint64_t step = step0 + (uint64_t)i;
             uint32_t cnt = 0, mbits = 0, lane_total = 0;
             if (step < ex.steps) {
-                A[i].template eval_chain_step<MODE, EV>(a, cnt, mbits, lane_total);
+                A[i].template eval_chain_step<MODE, EV>(a, eq, cnt, mbits, lane_total);
                 if (step >= full_steps) {                       // the partial last step
                     mbits &= rows_below<RPL>(step * kStepRows, n_rows, lane);
                     cnt = wave_sum_u32(__popc(mbits));
@@ -2498,21 +2557,23 @@ __global__ __launch_bounds__(kBlock, MODE == MODE_IDS ? PQPS_CHAIN_WGS : 1) void
 #pragma unroll
             for (int i = 0; i < S; i++) {
                 const uint64_t step = step0 + (uint64_t)i;
-                if (step < full_steps) A[i].template load<NT>(a, step * kStepRows + lane_off);      // uniform guard
+                // (full_steps >= 1 here: the loop runs only while step0 < full_steps)
+                if constexpr (kAllLoads) A[i].template load<NT>(a, (step < full_steps ? step : full_steps - 1) * kStepRows + lane_off);
+                else if (step < full_steps) A[i].template load<NT>(a, step * kStepRows + lane_off); // uniform guard
             }
 #pragma unroll
             for (int i = 0; i < S; i++) {
                 const uint64_t step = step0 + (uint64_t)i;
                 if (step >= full_steps) break;
                 uint32_t cnt = 0, mbits = 0;
-                A[i].template eval_chain_step<MODE, EV>(a, cnt, mbits, lane_total);
+                A[i].template eval_chain_step<MODE, EV>(a, eq, cnt, mbits, lane_total);
                 wave_total += cnt;
             }
         }
         if ((n_rows % kStepRows) != 0 && wave == full_steps % n_waves) {      // the partial last step: match bits, trimmed
             uint32_t cnt = 0, mbits = 0, unused = 0;
             A[0].template load<NT>(a, full_steps * kStepRows + lane_off);
-            A[0].template eval_chain_step<MODE_IDS, EV>(a, cnt, mbits, unused);
+            A[0].template eval_chain_step<MODE_IDS, EV>(a, eq, cnt, mbits, unused);
             wave_total += wave_sum_u32(__popc(mbits & rows_below<RPL>(full_steps * kStepRows, n_rows, lane)));
         }
         wave_total += wave_sum_u32(lane_total);

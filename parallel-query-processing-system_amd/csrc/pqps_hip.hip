@@ -21,6 +21,7 @@
 #include <hip/hip_ext.h>
 
 #include "pqps_hip.h"
+#include "packed12_eq.hpp"
 #include "filter_kernels.hpp"
 #include "fused_common.hpp"
 #include "bins_kernels.hpp"
@@ -538,7 +539,7 @@ struct pqps_ctx {
     uint64_t *check_dev;        // [2] pqps_ids_checksum
     // per-context overrides of the launch parameters (pqps_ctx_set_option: A/B runs inside ONE process, where the physical
     // placement of the table is the same for every variant); -1 = the default
-    long opt_list16, opt_list16_min, opt_list16_min_u8, opt_list_max, opt_list_max_u8, opt_tiny_max, opt_expand_lag, opt_sum_lag, opt_tune, opt_wide_front, opt_steps;
+    long opt_list16, opt_list16_min, opt_list16_min_u8, opt_list_max, opt_list_max_u8, opt_tiny_max, opt_expand_lag, opt_sum_lag, opt_tune, opt_wide_front, opt_steps, opt_eq12;
     void *sort_tmp;
     size_t sort_tmp_bytes;
     uint32_t *group_parts;      // every fused scan (group / aggregate / distinct): its workgroups' partial results (grow_group_parts)
@@ -856,7 +857,7 @@ eval_fn find_spec(int w0, int w1, int w2, bool chain, bool multi_step, bool nt, 
 
 // `a` must already carry the chain classification of fill_args(); sets a.streaming.
 template <int MODE>
-eval_fn pick_eval(const pqps_column *cols, uint32_t n_cols, const pqps_predicate *pred, EvalArgs &a, uint64_t n_rows, long opt_steps) {
+eval_fn pick_eval(const pqps_column *cols, uint32_t n_cols, const pqps_predicate *pred, EvalArgs &a, uint64_t n_rows, long opt_steps, long opt_eq12) {
     set_streaming(a, cols, n_cols, n_rows);
     if (n_cols >= 1 && n_cols <= 3 && pred->n_leaves >= 1 && pred->n_leaves <= PQPS_TT_LEAVES) {
         const int w0 = spec_width(cols[0].width), w1 = n_cols > 1 ? spec_width(cols[1].width) : 0, w2 = n_cols > 2 ? spec_width(cols[2].width) : 0;
@@ -870,13 +871,15 @@ eval_fn pick_eval(const pqps_column *cols, uint32_t n_cols, const pqps_predicate
         const bool one = pred->n_leaves == 1 && n_cols == 1;
         const bool valu = valu_chain_shape(w0, w1, w2) && (valu_env ? atoi(valu_env) != 0 : valu_chain_default(w0, w1, w2, MODE, n_rows));
         const int vc = a.chain == 0 ? 0 : (one ? 1 : (valu ? 2 : 0));
-        a.valu_chain = vc ? 1u : 0u;
+        // the packed column's raw-dword test (Eq12): its one leaf is a wanted equality on a code the column can hold, in an AND --
+        // `!=`, ranges, several leaves on the column, lo > 0xFFF ("no row") and the OR form keep the extracting path alone
+        a.eq12 = opt_eq12 != 0 && eq12_kernel(MODE, w0, w1, w2, vc) && a.chain == 1 && a.leaf_begin[1] == 1 && a.span[0] == 0 && (a.chain_want & 1u) && a.lo[0] <= 0xFFFu ? 1u : 0u;
         if (eval_fn f = find_spec<MODE>(w0, w1, w2, a.chain != 0, multi, a.streaming != 0, vc)) {   // nullptr unless widths are non-increasing
             if (a.chain != 0 && multi) a.steps_per_iter = (uint32_t)chain_steps(w0, w1, w2);
             const char *mode = MODE == MODE_IDS ? "MODE_IDS" : MODE == MODE_COUNT ? "MODE_COUNT" : "MODE_FLAGS";
             if (a.chain != 0)
-                snprintf(g_kernel, sizeof g_kernel, "eval_chain_kernel<%s, W0=%s, W1=%s, W2=%s, S=%u, NT=%s, EV=%d>", mode, width_name(w0), width_name(w1), width_name(w2),
-                         a.steps_per_iter ? a.steps_per_iter : 1u, a.streaming ? "true" : "false", vc);
+                snprintf(g_kernel, sizeof g_kernel, "eval_chain_kernel<%s, W0=%s, W1=%s, W2=%s, S=%u, NT=%s, EV=%d>%s", mode, width_name(w0), width_name(w1), width_name(w2),
+                         a.steps_per_iter ? a.steps_per_iter : 1u, a.streaming ? "true" : "false", vc, a.eq12 ? " eq12" : "");   // (" eq12": the launch tests its steps on the raw dwords first)
             else
                 snprintf(g_kernel, sizeof g_kernel, "eval_spec_kernel<%s, W0=%s, W1=%s, W2=%s, NT=%s>", mode, width_name(w0), width_name(w1), width_name(w2), a.streaming ? "true" : "false");
             return f;
@@ -1226,7 +1229,7 @@ struct ScanRequest {
 // predicate.  Then the kernel's args and the instantiation that evaluates them (COUNT: out_ids NULL, capacity 0;
 // `opt_steps`: the "steps" option of the caller's context).
 int scan_request(ScanRequest &r, int mode, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, uint32_t id_base,
-                 const pqps_predicate *pred, uint32_t *out_ids, uint64_t out_capacity, long opt_steps) {
+                 const pqps_predicate *pred, uint32_t *out_ids, uint64_t out_capacity, long opt_steps, long opt_eq12) {
     if (!out_ids && out_capacity) return fail(PQPS_EINVAL, "out_ids is NULL");
     if (mode == MODE_IDS && (n_rows > 0xFFFFFFFFull || (uint64_t)id_base + n_rows > 0x100000000ull))
         return fail(PQPS_EINVAL, "row IDs are u32: id_base + n_rows must be <= 2^32");
@@ -1234,7 +1237,7 @@ int scan_request(ScanRequest &r, int mode, const pqps_column *cols, uint32_t n_c
     if (rc) return rc;
     fill_args(r.a, cols, n_cols, pred);
     r.a.n_rows = n_rows;
-    r.k1 = mode == MODE_IDS ? pick_eval<MODE_IDS>(cols, n_cols, pred, r.a, n_rows, opt_steps) : pick_eval<MODE_COUNT>(cols, n_cols, pred, r.a, n_rows, opt_steps);
+    r.k1 = mode == MODE_IDS ? pick_eval<MODE_IDS>(cols, n_cols, pred, r.a, n_rows, opt_steps, opt_eq12) : pick_eval<MODE_COUNT>(cols, n_cols, pred, r.a, n_rows, opt_steps, opt_eq12);
     if (!r.k1) return fail(PQPS_EINVAL, "no specialised kernel reads this shape with a 12-bit packed column");
     r.mode = mode; r.n_rows = n_rows; r.id_base = id_base; r.out_ids = out_ids; r.out_cap = out_capacity;
     return PQPS_OK;
@@ -1293,7 +1296,7 @@ int create_ctx(int device, bool lane, pqps_ctx **out) {
     ctx->status_host = nullptr; ctx->status_dev = nullptr;
     ctx->parity = 0; ctx->epoch = 0; ctx->hand_groups = 0; ctx->needs_reset.store(false);
     ctx->check_dev = nullptr;
-    ctx->opt_list16 = ctx->opt_list16_min = ctx->opt_list16_min_u8 = ctx->opt_list_max = ctx->opt_list_max_u8 = ctx->opt_tiny_max = ctx->opt_expand_lag = ctx->opt_sum_lag = ctx->opt_tune = ctx->opt_wide_front = ctx->opt_steps = -1;
+    ctx->opt_list16 = ctx->opt_list16_min = ctx->opt_list16_min_u8 = ctx->opt_list_max = ctx->opt_list_max_u8 = ctx->opt_tiny_max = ctx->opt_expand_lag = ctx->opt_sum_lag = ctx->opt_tune = ctx->opt_wide_front = ctx->opt_steps = ctx->opt_eq12 = -1;
     ctx->sort_tmp = nullptr;
     ctx->sort_tmp_bytes = 0;
     ctx->group_parts = nullptr;
@@ -1420,6 +1423,7 @@ int pqps_ctx_set_option(pqps_ctx *ctx, const char *name, long value) {
         {"list_max", &ctx->opt_list_max}, {"tiny_max", &ctx->opt_tiny_max},
         {"expand_lag", &ctx->opt_expand_lag}, {"sum_lag", &ctx->opt_sum_lag}, {"tune", &ctx->opt_tune},
         {"wide_front", &ctx->opt_wide_front},                   // 0: the wide bins take their global atomics without the LDS front
+        {"eq12", &ctx->opt_eq12},                               // packed 12-bit column, one wanted equality: 0 = every step extracts its values, 1 (default) = raw-dword test first
         {"steps", &ctx->opt_steps},                             // chain scans: 0 = one step per wave, 1 = the shape's chain_steps() (ID output and COUNT)
     };
     for (auto &o : opts)
@@ -1504,7 +1508,7 @@ int pqps_filter_scan(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols,
                      uint32_t *out_ids, uint64_t out_capacity, uint64_t *out_count, void *stream) {
     if (!ctx || !out_count) return fail(PQPS_EINVAL, "ctx/out_count is NULL");
     ScanRequest r;
-    const int rc = scan_request(r, MODE_IDS, cols, n_cols, n_rows, id_base, pred, out_ids, out_capacity, ctx->opt_steps);
+    const int rc = scan_request(r, MODE_IDS, cols, n_cols, n_rows, id_base, pred, out_ids, out_capacity, ctx->opt_steps, ctx->opt_eq12);
     return rc ? rc : r.run(ctx, pick_stream(ctx, stream), out_count);
 }
 
@@ -1512,7 +1516,7 @@ int pqps_filter_count(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols,
                       uint64_t n_rows, const pqps_predicate *pred, uint64_t *out_count, void *stream) {
     if (!ctx || !out_count) return fail(PQPS_EINVAL, "ctx/out_count is NULL");
     ScanRequest r;
-    const int rc = scan_request(r, MODE_COUNT, cols, n_cols, n_rows, 0, pred, nullptr, 0, ctx->opt_steps);
+    const int rc = scan_request(r, MODE_COUNT, cols, n_cols, n_rows, 0, pred, nullptr, 0, ctx->opt_steps, ctx->opt_eq12);
     return rc ? rc : r.run(ctx, pick_stream(ctx, stream), out_count);
 }
 
@@ -2575,7 +2579,7 @@ int pqps_exchange_select(pqps_exchange *x, const pqps_column *cols, uint32_t n_c
     if (slot >= x->ring) return fail(PQPS_EINVAL, "slot %u >= ring %u", slot, x->ring);
     ExchangeSlot &sl = x->slots[slot];
     ScanRequest r;                                               // (the slot's own ID area: this rank's list behind its count)
-    int rc = scan_request(r, MODE_IDS, cols, n_cols, n_rows, id_base, pred, sl.local + kSlotHeaderWords, x->cap, x->ctx->opt_steps);
+    int rc = scan_request(r, MODE_IDS, cols, n_cols, n_rows, id_base, pred, sl.local + kSlotHeaderWords, x->cap, x->ctx->opt_steps, x->ctx->opt_eq12);
     if (rc) return rc;
     rc = exchange_claim(x, sl);
     if (rc) return rc;
@@ -2649,7 +2653,7 @@ int pqps_exchange_count(pqps_exchange *x, const pqps_column *cols, uint32_t n_co
     if (slot >= x->ring) return fail(PQPS_EINVAL, "slot %u >= ring %u", slot, x->ring);
     ExchangeSlot &sl = x->slots[slot];
     ScanRequest r;
-    int rc = scan_request(r, MODE_COUNT, cols, n_cols, n_rows, 0, pred, nullptr, 0, x->ctx->opt_steps);
+    int rc = scan_request(r, MODE_COUNT, cols, n_cols, n_rows, 0, pred, nullptr, 0, x->ctx->opt_steps, x->ctx->opt_eq12);
     if (rc) return rc;
     rc = exchange_claim(x, sl);
     if (rc) return rc;
@@ -2811,7 +2815,7 @@ int qstream_issue(pqps_qstream *q, uint32_t slot, int mode, const pqps_column *c
                   const pqps_predicate *pred, uint32_t *out_ids, uint64_t out_capacity, uint64_t *out_count, void *scan_stream) {
     if (!q || !out_count) return fail(PQPS_EINVAL, "qstream/out_count is NULL");
     ScanRequest r;
-    int rc = scan_request(r, mode, cols, n_cols, n_rows, id_base, pred, out_ids, out_capacity, q->ctx->opt_steps);
+    int rc = scan_request(r, mode, cols, n_cols, n_rows, id_base, pred, out_ids, out_capacity, q->ctx->opt_steps, q->ctx->opt_eq12);
     if (rc) return rc;
     pqps_ctx *c = nullptr; hipStream_t s = nullptr;
     rc = qstream_begin(q, slot, n_rows, pick_stream(q->ctx, scan_stream), q->ctx->timing, &c, &s, mode == MODE_IDS);
