@@ -642,6 +642,56 @@ struct hipColumnarResult *executeQuerySelectGroupHeadHIP(struct engineS *engine,
                                                          const char *orderColumn, bool descending, long long n, long long *matches,
                                                          long long **offsets);
 
+/* EXACT PERCENTILES, overall or per group: "the median and p95 exit_code per host", "the timestamp by which half of each
+ * user's risk-5 commands had happened" (SQL: PERCENTILE_DISC(p) WITHIN GROUP (ORDER BY valueColumn); no counterpart in the
+ * reference, reached through the C API and the Python package only, as every grouped form is).  Exact: no tolerance, no
+ * sketch, and no floating point anywhere in the choice of a row.
+ * ROWS: exactly the rows executeQuerySelectIdsHIP(engine, whereClause) returns; as in executeQueryGroupCountHIP a row that
+ * several probed conditions return more than once counts that many times.  `total` equals that call's count.
+ * GROUPS: the groups, keys, key text and key order of executeQueryGroupCountHIP for the same column and WHERE, only groups
+ * with a row; counts[g] equals its count.  groupColumn == NULL: one group over all those rows -- numGroups is 1 if any row
+ * matches and 0 otherwise, keyText is NULL, groupColumn and groupKind are -1.
+ * VALUE COLUMN: any of the 12 columns, in executeQueryOrderIdsHIP's ascending order: strings in dictionary (strcmp) order,
+ * exit_code / user_id / risk_level signed, command_id unsigned 64-bit, false before true.
+ * FRACTIONS: ppm[0 .. numFractions), 1 .. 16 of them, exact integers in PARTS PER MILLION, 0 .. 1 000 000, in any order,
+ * repeats allowed.  For a group of n rows the answer for p is the element at 0-based rank max(ceil(p n / 10^6) - 1, 0) of the
+ * group's ascending sort (hipQuantileRank, 64-bit integers): p = 0 the minimum, 1 000 000 the maximum, 500 000 the lower
+ * median.  There is no PERCENTILE_CONT: interpolation needs the neighbouring rank too and means nothing for strings.
+ * ANSWER: values[g * numFractions + f] = group g's value for ppm[f]: the i32 value, the u64 bits of command_id, 0 / 1, or the
+ * dictionary code at the time of the query; for a string column valueText[g * numFractions + f] is its (owned) text, for
+ * every other kind valueText is NULL.
+ * REFUSED (success = false, the reason on stderr): an unknown value or group column, numFractions outside 1 .. 16, a ppm
+ * above 1 000 000, and every group-column refusal of executeQueryGroupCountHIP (command_id as the group column, more than
+ * 65 536 groups, an engine joined across ranks -- with or without GROUP BY).  NOTHING is refused for the size of the value
+ * column's domain.  A reader like COUNT: shared lock and one query lane, the lane rules above apply; bounds and dictionaries
+ * are read under the lock; the device buffers of a query are allocated for it and freed with it.
+ * Execution: a radix select over the value column's order-preserving key image (dictionary code, i32 value minus the
+ * table-wide minimum, the bool, command_id minus the selection's minimum -- one MIN / MAX aggregate first), B key bits planned
+ * from the dictionary size or the bounds.  B is split into digits from the top (hipQuantileDigitBits: 11 bits while a launch
+ * counts at most 8 tables, else 8; a domain of at most 2048 values is ONE pass); every pass is one counting scan per shard --
+ * pqps_filter_digit_hist for a single-pass scan-mode WHERE, otherwise the selection ONCE and pqps_digit_hist_list over each
+ * shard's list per pass -- whose tables are downloaded and summed over the shards on the host (a histogram is decomposable
+ * where a quantile is not), and hipQuantilePick narrows every pending fraction by one digit.  Pass 0 also gives every
+ * group's row count.  A launch counts at most 2^22 words (16 MiB per shard and pass): more groups than that run in batches of
+ * consecutive bins (the environment variable PQPS_QUANTILE_WORDS, read per query, lowers the cap -- for the tests).  An
+ * empty table, or a WHERE that matches nothing, gives numGroups = 0 with success = true. */
+struct hipQuantileResult {
+    int valueColumn, valueKind;        /* HIPCOL_*, HIPKIND_*                                               */
+    int groupColumn, groupKind;        /* HIPCOL_*, HIPKIND_*; -1 / -1 without GROUP BY                     */
+    int numGroups, numFractions;
+    int passes;                        /* counting scans per shard the select took (batches counted)         */
+    long long total;                   /* sum of counts = executeQuerySelectIdsHIP's count                   */
+    char **keyText;                    /* as hipGroupResult; NULL without GROUP BY                           */
+    unsigned long long *counts;        /* numGroups: the rows of every group                                 */
+    long long *values;                 /* [numGroups * numFractions]: i32 value, u64 bits, code, or 0 / 1     */
+    char **valueText;                  /* strings only, else NULL: [numGroups * numFractions] owned texts     */
+    double queryTime;
+    bool success;
+};
+struct hipQuantileResult *executeQueryQuantilesHIP(struct engineS *engine, const char *valueColumn, const char *groupColumn /* may be NULL */,
+                                                   const unsigned *ppm, int numFractions, struct whereClauseS *whereClause);
+void freeQuantileResultHIP(struct hipQuantileResult *result);
+
 /* THE TOP N GROUPS: GROUP BY one column of ANY size, ORDER BY an aggregate [DESC], LIMIT n -- "the 20 most frequent commands",
  * "the 10 users with the highest summed risk" (no aggregates in the reference; reached through the C API and the Python
  * package only, like the grouped COUNT above).

@@ -310,6 +310,34 @@ struct hipCountPlace { int batch, position, constant; };
 int hipCountManyPack(const struct hipCountQuery *queries, int n, int max_queries, struct hipCountBatch *batches, int *n_batches,
                      struct hipCountPlace *place);
 
+/* THE HOST HALF OF EXACT PERCENTILES (executeQueryQuantilesHIP): a radix select over the order-preserving key image of the
+ * value column, one digit per counting scan (pqps_filter_digit_hist), most significant digit first.  Pure host code, integer
+ * arithmetic only -- no floating point takes part in choosing a rank.
+ *
+ * hipQuantileRank: the 0-based rank, in the ascending sort of n values, of the fraction `ppm` parts per million (SQL's
+ *   PERCENTILE_DISC): max(ceil(ppm * n / 1 000 000) - 1, 0).  ppm above 1 000 000 counts as 1 000 000; n = 0 gives 0.
+ * hipQuantileDigitBits: the width of the next digit when `bits_left` of the key's `key_bits` are still open and the launch
+ *   counts `tables` tables: a key of at most 11 bits is ONE pass; otherwise 11 bits while tables <= 8 (the tables fit LDS),
+ *   else 8 bits (64 tables fit LDS; more live in global memory), never more than bits_left.  0 when nothing is left.
+ * hipQuantilePick: one group after one pass.  tables[n_slots][2^digit_bits]: the group's counts, summed over the shards;
+ *   prefixes[n_slots]: the prefix every slot stands for (NULL: one slot, prefix 0 -- the first pass); entry i < n_entries is a
+ *   pending fraction: ranks[i] = its rank among the rows of table slots[i].  Per entry: digits[i] = the digit whose bucket
+ *   holds the rank (the first d with ranks[i] < counts[0] + .. + counts[d]), ranks_in[i] = the rank inside that bucket.
+ *   next_prefixes[0 .. *n_next): the distinct values of (prefix << digit_bits | digit) over the entries, ascending -- the
+ *   next pass's slots; next_slots[i]: the one entry i follows.  Every output has room for n_entries.  Returns 0, or -1 with
+ *   the reason on stderr for a NULL argument, digit_bits outside 1 .. 16, n_slots or n_entries above
+ *   HIPQUANTILE_MAX_FRACTIONS, a slot out of range, a rank at or above its table's total. */
+#define HIPQUANTILE_PPM 1000000ull
+#define HIPQUANTILE_MAX_FRACTIONS 16
+#define HIPQUANTILE_DIGIT_LDS 11u        /* = PQPS_DIGIT_BITS_MAX */
+#define HIPQUANTILE_DIGIT_WIDE 8u
+#define HIPQUANTILE_TABLES_LDS 8u
+unsigned long long hipQuantileRank(unsigned long long n, unsigned int ppm);
+unsigned int hipQuantileDigitBits(unsigned int bits_left, unsigned int key_bits, unsigned long long tables);
+int hipQuantilePick(const uint64_t *tables, unsigned int digit_bits, const uint64_t *prefixes, int n_slots, const uint64_t *ranks,
+                    const int *slots, int n_entries, unsigned int *digits, uint64_t *ranks_in, uint64_t *next_prefixes,
+                    int *next_slots, int *n_next);
+
 /* The number of values[0 .. count) (ascending in strcmp order) below `text`: its code when it is in the dictionary
  * (*present = 1), the rank it is inserted at otherwise (*present = 0). */
 int hipDictionaryRank(const char *const *values, int count, const char *text, int *present);

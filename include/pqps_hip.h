@@ -721,6 +721,42 @@ int pqps_group_head_sort(pqps_ctx *ctx, const pqps_column *key_col, int key_sign
                          int group_signed, const uint32_t *ids, uint64_t n, uint32_t id_base, uint64_t limit, int repeats,
                          uint32_t *out_ids, uint64_t *out_keys, uint64_t *kept_out, void *stream);
 
+/* ---- one pass of a radix select: per group, the histogram of one digit of a key under a prefix --------------------------
+ * No counterpart in the reference.  What exact percentiles (SQL: PERCENTILE_DISC) are made of: a few counting scans instead
+ * of a sort.  KEY IMAGE of a row: (uint32_t)(v - key_base) for a key column of 1, 2 or 4 bytes or a bit plane (key_wide 0;
+ * the 32-bit wrap-around makes an i32 value minus the column's minimum monotone), v - key_base in 64 bits for an 8-byte
+ * column (key_wide 1).  The caller promises image < 2^key_bits (key_bits 1 .. 32, or .. 64 when key_wide); a row whose image
+ * has a bit at or above key_bits is left out and never indexes anything.
+ * GROUPS: the bins of pqps_filter_group ((value - bin_base) in 32-bit arithmetic; rows whose bin is >= n_bins are left out, so
+ * bin_base / n_bins is also a window onto a longer run of bins); `group_col` NULL means no GROUP BY: n_bins must be 1.
+ * DIGIT: bits [shift, shift + digit_bits) of the image, digit_bits 1 .. PQPS_DIGIT_BITS_MAX, shift + digit_bits <= key_bits.
+ * PREFIXES: prefix_dev NULL (the first pass): `slots` must be 1 and the table of a row is its group bin.  Otherwise
+ *   prefix_dev[(bin * slots) + j], j < slots (1 .. PQPS_DIGIT_SLOTS_MAX), are u64 device words: the row counts into table
+ *   t = bin * slots + j of the slot whose word equals image >> (shift + digit_bits), and is left out when none does.  All
+ *   ones marks an unused slot; the slots of one group hold distinct words.
+ * OUTPUT: tables_dev[n_bins * slots][2^digit_bits] u32 device counts, at most PQPS_DIGIT_WORDS_MAX words in all, zeroed by the
+ *   call: tables_dev[t * 2^digit_bits + digit] = the matching rows of table t with that digit.  Asynchronous on `stream`.
+ *
+ * pqps_filter_digit_hist: ONE scan of `pred` over rows [0, n_rows) of `cols`; the key column and the group column are read
+ *   only in steps of 1024 rows that hold a match (the readable-padding rule of pqps_filter_scan applies to both; `group_col`
+ *   1, 2 or 4 bytes wide or a bit plane).  Up to 16 384 counts (8 tables of 11 bits, 64 of 8 bits): tables in LDS, a partial
+ *   row per workgroup, summed by a second launch; above: one global atomic per matching row.  Scratch as
+ *   pqps_filter_group_first; the context's timing recorder records the launch like a COUNT's.
+ * pqps_digit_hist_list: the same tables over an ID list -- ids[0 .. min(*count_dev, capacity)), row = id - id_base < n_rows
+ *   -- gathering `key_col` (1, 2, 4 or 8 bytes wide) and `group_col` (1, 2 or 4 bytes wide) per listed row, no bit planes; an
+ *   id listed twice is counted twice.  capacity or n_rows 0: the tables zeroed, nothing launched. */
+#define PQPS_DIGIT_BITS_MAX 11u
+#define PQPS_DIGIT_SLOTS_MAX 16u
+#define PQPS_DIGIT_WORDS_MAX (1u << 22)
+int pqps_filter_digit_hist(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                           const pqps_column *key_col, int key_wide, uint64_t key_base, uint32_t key_bits, const pqps_column *group_col,
+                           uint32_t bin_base, uint32_t n_bins, uint32_t slots, const uint64_t *prefix_dev, uint32_t shift,
+                           uint32_t digit_bits, uint32_t *tables_dev, void *stream);
+int pqps_digit_hist_list(pqps_ctx *ctx, const pqps_column *key_col, int key_wide, uint64_t key_base, uint32_t key_bits,
+                         const pqps_column *group_col, uint32_t bin_base, uint32_t n_bins, uint32_t slots, const uint64_t *prefix_dev,
+                         uint32_t shift, uint32_t digit_bits, uint64_t n_rows, const uint32_t *ids, const uint64_t *count_dev,
+                         uint64_t capacity, uint32_t id_base, uint32_t *tables_dev, void *stream);
+
 /* ---- COUNT(DISTINCT value column), overall or per group ---------------------------------------------------------------
  * No counterpart in the reference.  BINS: a value bin is (value - v_base) in 32-bit arithmetic (dictionary codes with
  * v_base 0, an i32 value minus the column's minimum, the bool byte or bit), a group bin (value - g_base) likewise;

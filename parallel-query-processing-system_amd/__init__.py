@@ -216,6 +216,19 @@ class HeadList(C.Structure):
 HEAD_ROUNDS_MAX = 16        # PQPS_HEAD_ROUNDS_MAX (include/pqps_hip.h)
 
 
+class QuantileResult(C.Structure):
+    """struct hipQuantileResult (include/executeEngine-hip.h)."""
+    _fields_ = [("valueColumn", C.c_int), ("valueKind", C.c_int), ("groupColumn", C.c_int), ("groupKind", C.c_int),
+                ("numGroups", C.c_int), ("numFractions", C.c_int), ("passes", C.c_int), ("total", C.c_longlong),
+                ("keyText", C.POINTER(C.c_char_p)), ("counts", C.POINTER(C.c_ulonglong)), ("values", C.POINTER(C.c_longlong)),
+                ("valueText", C.POINTER(C.c_char_p)), ("queryTime", C.c_double), ("success", C.c_bool)]
+
+
+QUANTILE_PPM = 1_000_000                                     # HIPQUANTILE_PPM (include/hipPredicate.h)
+QUANTILE_MAX_FRACTIONS = 16                                  # HIPQUANTILE_MAX_FRACTIONS
+DIGIT_BITS_MAX, DIGIT_SLOTS_MAX, DIGIT_WORDS_MAX = 11, 16, 1 << 22   # PQPS_DIGIT_* (include/pqps_hip.h)
+
+
 class ColumnData(C.Structure):
     """struct hipColumnData (include/executeEngine-hip.h)."""
     _fields_ = [("values", C.c_void_p), ("width", C.c_uint), ("on_device", C.c_int),
@@ -716,6 +729,21 @@ def lib():
     L.hipHeadMerge.restype = C.c_longlong
     L.hipHeadMerge.argtypes = [C.POINTER(HeadList), C.c_int, C.c_longlong, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
                                C.POINTER(C.c_uint64)]
+    L.pqps_filter_digit_hist.argtypes = [vp, C.POINTER(Column), u32, u64, C.POINTER(Predicate), C.POINTER(Column), C.c_int, u64, u32,
+                                         C.POINTER(Column), u32, u32, u32, vp, u32, u32, vp, vp]
+    L.pqps_digit_hist_list.argtypes = [vp, C.POINTER(Column), C.c_int, u64, u32, C.POINTER(Column), u32, u32, u32, vp, u32, u32, u64,
+                                       vp, vp, u64, u32, vp, vp]
+    L.hipQuantileRank.restype = C.c_ulonglong
+    L.hipQuantileRank.argtypes = [C.c_ulonglong, C.c_uint]
+    L.hipQuantileDigitBits.restype = C.c_uint
+    L.hipQuantileDigitBits.argtypes = [C.c_uint, C.c_uint, C.c_ulonglong]
+    L.hipQuantilePick.argtypes = [C.POINTER(C.c_uint64), C.c_uint, C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_uint64),
+                                  C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_uint), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                  C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.executeQueryQuantilesHIP.restype = C.POINTER(QuantileResult)
+    L.executeQueryQuantilesHIP.argtypes = [E, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint), C.c_int, W]
+    L.freeQuantileResultHIP.argtypes = [C.POINTER(QuantileResult)]
+    L.freeQuantileResultHIP.restype = None
     L.executeQueryGroupHeadHIP.restype = C.POINTER(GroupHeadResult)
     L.executeQueryGroupHeadHIP.argtypes = [E, C.c_char_p, C.c_char_p, C.c_bool, C.c_longlong, W]
     L.freeGroupHeadResultHIP.argtypes = [C.POINTER(GroupHeadResult)]
@@ -1010,6 +1038,68 @@ def head_merge(shards, limit):
     if n < 0:
         raise ValueError("hipHeadMerge refused (reason on stderr)")
     return list(ob[:n]), list(ow[:n]), list(oe[:n]) if wide else None
+
+
+def filter_digit_hist(ctx, cols, n_cols, n_rows, pred, key_col, key_wide, key_base, key_bits, group_col, bin_base, n_bins, slots,
+                      prefix_dev, shift, digit_bits, tables_dev, stream=None):
+    """pqps_filter_digit_hist: one fused pass of a radix select; `pred` a Predicate (or its byref), `key_col` / `group_col`
+    Columns (group_col None: no GROUP BY), prefix_dev None on the first pass."""
+    ref = lambda c: C.byref(c) if c is not None else None
+    check(lib().pqps_filter_digit_hist(ctx.h, cols, n_cols, n_rows, C.byref(pred) if isinstance(pred, Predicate) else pred,
+                                       ref(key_col), int(key_wide), key_base & 0xFFFFFFFFFFFFFFFF, key_bits, ref(group_col), bin_base,
+                                       n_bins, slots, prefix_dev, shift, digit_bits, tables_dev, stream), "pqps_filter_digit_hist")
+
+
+def digit_hist_list(ctx, key_col, key_wide, key_base, key_bits, group_col, bin_base, n_bins, slots, prefix_dev, shift, digit_bits,
+                    n_rows, ids_dev, count_dev, capacity, id_base, tables_dev, stream=None):
+    """pqps_digit_hist_list: the same tables over an ID list."""
+    ref = lambda c: C.byref(c) if c is not None else None
+    check(lib().pqps_digit_hist_list(ctx.h, ref(key_col), int(key_wide), key_base & 0xFFFFFFFFFFFFFFFF, key_bits, ref(group_col),
+                                     bin_base, n_bins, slots, prefix_dev, shift, digit_bits, n_rows, ids_dev, count_dev, capacity,
+                                     id_base, tables_dev, stream), "pqps_digit_hist_list")
+
+
+def quantile_rank(n, ppm):
+    """hipQuantileRank: the 0-based rank of the fraction `ppm` parts per million among n sorted values."""
+    return int(lib().hipQuantileRank(n, ppm))
+
+
+def quantile_digit_bits(bits_left, key_bits, tables):
+    """hipQuantileDigitBits: the width of the next digit of a radix select."""
+    return int(lib().hipQuantileDigitBits(bits_left, key_bits, tables))
+
+
+def quantile_pick(tables, digit_bits, prefixes, entries):
+    """hipQuantilePick: tables = the group's counts, slot by slot ([n_slots][2^digit_bits], flat or nested); prefixes = the
+    slots' prefixes (None: one slot, prefix 0); entries = [(rank, slot), ...].  Returns (digits, ranks_in, next_prefixes,
+    next_slots), or raises ValueError where the C function refuses."""
+    flat = [int(x) for row in tables for x in (row if hasattr(row, "__len__") else [row])]
+    n_slots, n = (len(prefixes) if prefixes is not None else 1), len(entries)
+    t = (C.c_uint64 * max(1, len(flat)))(*flat)
+    p = (C.c_uint64 * n_slots)(*prefixes) if prefixes is not None else None
+    r, s = (C.c_uint64 * max(1, n))(*[e[0] for e in entries]), (C.c_int * max(1, n))(*[e[1] for e in entries])
+    dg, ri, nx, ns = (C.c_uint * max(1, n))(), (C.c_uint64 * max(1, n))(), (C.c_uint64 * max(1, n))(), (C.c_int * max(1, n))()
+    n_next = C.c_int()
+    if len(flat) != n_slots << digit_bits or lib().hipQuantilePick(t, digit_bits, p, n_slots, r, s, n, dg, ri, nx, ns, C.byref(n_next)) != 0:
+        raise ValueError("hipQuantilePick refused (reason on stderr)")
+    return list(dg[:n]), list(ri[:n]), list(nx[:n_next.value]), list(ns[:n])
+
+
+def quantile_ppm(fraction):
+    """A fraction as exact parts per million: an int IS ppm (0 .. 1 000 000); a float or Fraction in [0, 1] is
+    round(x * 1 000 000) and must lie within 1e-9 of that integer.  ValueError otherwise."""
+    if isinstance(fraction, bool):
+        raise ValueError(f"fraction {fraction!r}: not a number")
+    if hasattr(fraction, "__index__"):                       # int, numpy integers
+        ppm = fraction.__index__()
+    else:
+        scaled = fraction * QUANTILE_PPM
+        ppm = round(scaled)
+        if not 0 <= fraction <= 1 or abs(scaled - ppm) > 1e-9:
+            raise ValueError(f"fraction {fraction!r}: not a whole number of parts per million in [0, 1]")
+    if not 0 <= ppm <= QUANTILE_PPM:
+        raise ValueError(f"fraction {fraction!r}: outside 0 .. 1 000 000 parts per million")
+    return int(ppm)
 
 
 def first_key_decode(kind, descending, word):
@@ -1673,6 +1763,51 @@ class HipEngine:
     def average(self, value_column, group_column=None, chain=None):
         """AVG as sum / count of aggregate(): [(key_text, avg), ...] (the device computes no AVG)."""
         return [(k, s / c) for k, c, s, _, _ in self.aggregate(value_column, group_column, chain)]
+
+    def quantiles_result(self, value_column, fractions, group_column=None, chain=None):
+        """quantiles plus the raw fields: (groups, dict(total, passes, seconds))."""
+        ppm = [quantile_ppm(f) for f in fractions]
+        if not 1 <= len(ppm) <= QUANTILE_MAX_FRACTIONS:
+            raise ValueError(f"quantiles: {len(ppm)} fractions, not 1 .. {QUANTILE_MAX_FRACTIONS}")
+        wl = WhereList(chain)
+        res = lib().executeQueryQuantilesHIP(self.e, value_column.encode(), group_column.encode() if group_column else None,
+                                             (C.c_uint * len(ppm))(*ppm), len(ppm), wl.ptr)
+        what = f"quantiles({value_column!r}, {group_column!r})"
+        if not res:
+            raise PqpsError(f"{what}: no result")
+        try:
+            r = res.contents
+            if not r.success:
+                raise PqpsError(f"{what} refused or failed (reason on stderr)")
+            nf = r.numFractions
+            if r.valueKind == HIPKIND_DICT:
+                value = lambda i: r.valueText[i].decode("latin-1")
+            elif r.valueKind == HIPKIND_BOOL:
+                value = lambda i: bool(r.values[i])
+            elif r.valueKind == HIPKIND_U64:
+                value = lambda i: r.values[i] & 0xFFFFFFFFFFFFFFFF
+            else:
+                value = lambda i: int(r.values[i])
+            groups = [(r.keyText[g].decode("latin-1") if r.groupColumn >= 0 else None, int(r.counts[g]),
+                       [value(g * nf + f) for f in range(nf)]) for g in range(r.numGroups)]
+            return groups, {"total": int(r.total), "passes": int(r.passes), "seconds": float(r.queryTime)}
+        finally:
+            lib().freeQuantileResultHIP(res)
+
+    def quantiles(self, value_column, fractions, group_column=None, chain=None):
+        """executeQueryQuantilesHIP: exact percentiles (SQL's PERCENTILE_DISC) of `value_column` -- any of the 12 columns, in
+        order_ids' ascending order -- over the rows select_ids(chain) returns: [(key_text, n, [value, ...]), ...] in the key
+        order of group_count(group_column, chain), or one entry with key_text None without a group column (none when no row
+        matches).  `fractions`: 1 .. 16 of them, ints as parts per million (0 .. 1 000 000) or floats / Fractions in [0, 1]
+        that are whole parts per million (quantile_ppm); for a group of n rows the value for p is the element at 0-based rank
+        max(ceil(p n / 10^6) - 1, 0) of its ascending sort.  Values as aggregate and group_first render them: ints, unsigned
+        ints for command_id, the text of a string, False / True.  Raises ValueError for the fractions, PqpsError when the
+        engine refuses (reason on stderr)."""
+        return self.quantiles_result(value_column, fractions, group_column, chain)[0]
+
+    def median(self, value_column, group_column=None, chain=None):
+        """The lower median as quantiles([500 000]): [(key_text, n, value), ...]."""
+        return [(k, n, v[0]) for k, n, v in self.quantiles(value_column, [500_000], group_column, chain)]
 
     def order_ids(self, order_column, chain=None, descending=False, limit=None):
         """executeQueryOrderIdsHIP: (ids, matches) -- the row numbers of the first `limit` rows (all with limit None or <= 0)

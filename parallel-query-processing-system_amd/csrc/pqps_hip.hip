@@ -25,6 +25,7 @@
 #include "filter_kernels.hpp"
 #include "fused_common.hpp"
 #include "bins_kernels.hpp"
+#include "digit_kernels.hpp"
 #include "member_kernels.hpp"
 #include "set_kernels.hpp"
 #include "topk_kernels.hpp"
@@ -4162,6 +4163,123 @@ int pqps_group_head_sort(pqps_ctx *ctx, const pqps_column *key_col, int key_sign
     (void)hipFree(flags); (void)hipFree(keep); (void)hipFree(count_dev); (void)hipFree(tmp);
     if (!rc) *kept_out = m;
     return rc;
+}
+
+// ---- one pass of a radix select: a digit histogram per group under a prefix (digit_kernels.hpp) -----------------------
+static_assert(PQPS_DIGIT_BITS_MAX == kDigitBitsMax && PQPS_DIGIT_SLOTS_MAX == kDigitSlotsMax && PQPS_DIGIT_WORDS_MAX == kDigitWordsMax,
+              "pqps_hip.h states the kernels' constants");
+
+// The (zeroed) source block of a digit call, checked.  `scan`: the fused form (bit planes allowed, vector loads: aligned).
+static int digit_source(DigitSource &g, const pqps_column *key_col, int key_wide, uint64_t key_base, uint32_t key_bits,
+                        const pqps_column *group_col, uint32_t bin_base, uint32_t n_bins, uint32_t slots, const uint64_t *prefix,
+                        uint32_t shift, uint32_t digit_bits, bool scan) {
+    if (!key_col) return fail(PQPS_EINVAL, "key column is NULL");
+    int rc = column_width_code("key", key_col, scan, true, scan, &g.kwidth_log2);
+    if (rc) return rc;
+    if ((key_col->width == 8) != (key_wide != 0)) return fail(PQPS_EINVAL, "key column: width %u with key_wide %d", key_col->width, key_wide);
+    if (key_bits == 0 || key_bits > (key_wide ? 64u : 32u)) return fail(PQPS_EINVAL, "%u key bits: 1 .. %u", key_bits, key_wide ? 64u : 32u);
+    if (digit_bits == 0 || digit_bits > kDigitBitsMax) return fail(PQPS_EINVAL, "%u digit bits: 1 .. %u", digit_bits, kDigitBitsMax);
+    if ((uint64_t)shift + digit_bits > key_bits) return fail(PQPS_EINVAL, "digit [%u, %u) past %u key bits", shift, shift + digit_bits, key_bits);
+    if (slots == 0 || slots > kDigitSlotsMax) return fail(PQPS_EINVAL, "%u slots: 1 .. %u", slots, kDigitSlotsMax);
+    if (!prefix && slots != 1) return fail(PQPS_EINVAL, "no prefixes: 1 slot, not %u", slots);
+    if (prefix && shift + digit_bits >= 64u) return fail(PQPS_EINVAL, "prefixes above bit 64");
+    if (!group_col) {
+        if (n_bins != 1) return fail(PQPS_EINVAL, "no group column: 1 bin, not %u", n_bins);
+    } else {
+        rc = check_bin_count(n_bins);
+        if (rc == PQPS_OK) rc = column_width_code("group", group_col, scan, false, scan, &g.gwidth_log2);
+        if (rc) return rc;
+    }
+    if (((uint64_t)n_bins * slots) << digit_bits > kDigitWordsMax)
+        return fail(PQPS_EINVAL, "%u x %u tables of %u counts: more than %u words", n_bins, slots, 1u << digit_bits, kDigitWordsMax);
+    g.kcol = key_col->data;
+    g.gcol = group_col ? group_col->data : nullptr;
+    g.prefix = prefix;
+    g.key_base = key_base;
+    g.bin_base = bin_base;
+    g.n_bins = n_bins;
+    g.slots = slots;
+    g.shift = shift;
+    g.digit_bits = digit_bits;
+    g.key_bits = key_bits;
+    return PQPS_OK;
+}
+
+int pqps_filter_digit_hist(pqps_ctx *ctx, const pqps_column *cols, uint32_t n_cols, uint64_t n_rows, const pqps_predicate *pred,
+                           const pqps_column *key_col, int key_wide, uint64_t key_base, uint32_t key_bits, const pqps_column *group_col,
+                           uint32_t bin_base, uint32_t n_bins, uint32_t slots, const uint64_t *prefix_dev, uint32_t shift,
+                           uint32_t digit_bits, uint32_t *tables_dev, void *stream) {
+    if (!ctx || !tables_dev) return fail(PQPS_EINVAL, "ctx/tables is NULL");
+    DigitArgs g;
+    memset(&g, 0, sizeof g);
+    int rc = digit_source(g.src, key_col, key_wide, key_base, key_bits, group_col, bin_base, n_bins, slots, prefix_dev, shift, digit_bits, true);
+    if (rc == PQPS_OK) rc = fused_args(g.e, cols, n_cols, n_rows, pred);
+    if (rc) return rc;
+    const uint32_t nb = (n_bins * slots) << digit_bits;
+    hipStream_t s = pick_stream(ctx, stream);
+    HIP_TRY(hipMemsetAsync(tables_dev, 0, (size_t)nb * sizeof(uint32_t), s));
+    if (n_rows == 0) return PQPS_OK;
+    const bool lds = nb <= kCountLdsBins;
+    const uint32_t lds_bytes = lds ? nb * kCountBinBytes : 0u;
+    const uint32_t grid = fused_grid(ctx, n_rows, lds_bytes);
+    g.stride = (nb + 63u) & ~63u;
+    if (lds) {
+        rc = grow_group_parts(ctx, s, (size_t)grid * g.stride);
+        if (rc) return rc;
+    }
+    g.out = tables_dev;
+    g.parts = ctx->group_parts;
+    // the instance and its name side by side: pqps_last_kernel() reports the entry that is launched
+    static const struct { void (*fn)(const DigitArgs); const char *name; } fns[2][2][2] = {
+#define PQPS_DIGIT_SCAN(W, K, P, NT) {digit_scan_kernel<W, BINS_##P, NT>, "digit_scan_kernel<DIGIT_" #P ", " #K ", NT=" #NT ">"}
+#define PQPS_DIGIT_NTS(W, K, P) {PQPS_DIGIT_SCAN(W, K, P, false), PQPS_DIGIT_SCAN(W, K, P, true)}
+        {PQPS_DIGIT_NTS(false, u32, LDS), PQPS_DIGIT_NTS(false, u32, GLOBAL)},
+        {PQPS_DIGIT_NTS(true, u64, LDS), PQPS_DIGIT_NTS(true, u64, GLOBAL)},
+#undef PQPS_DIGIT_NTS
+#undef PQPS_DIGIT_SCAN
+    };
+    const auto &scan = fns[key_wide ? 1 : 0][lds ? 0 : 1][g.e.streaming ? 1 : 0];
+    snprintf(g_kernel, sizeof g_kernel, "%s", scan.name);
+    hipEvent_t stop;
+    rc = fused_launch(ctx, scan.fn, grid, lds_bytes, s, g, &stop);
+    if (rc) return rc;
+    if (lds) {
+        const dim3 sg(g.stride / 64u, (grid + kGroupSumParts - 1) / kGroupSumParts);
+        rc = launch_stop(group_sum_kernel, sg, 0, s, stop, (const uint32_t *)ctx->group_parts, grid, g.stride, nb, tables_dev);
+    }
+    fused_close(ctx, stop, !lds);
+    return rc;
+}
+
+int pqps_digit_hist_list(pqps_ctx *ctx, const pqps_column *key_col, int key_wide, uint64_t key_base, uint32_t key_bits,
+                         const pqps_column *group_col, uint32_t bin_base, uint32_t n_bins, uint32_t slots, const uint64_t *prefix_dev,
+                         uint32_t shift, uint32_t digit_bits, uint64_t n_rows, const uint32_t *ids, const uint64_t *count_dev,
+                         uint64_t capacity, uint32_t id_base, uint32_t *tables_dev, void *stream) {
+    if (!ctx || !tables_dev || !count_dev || (capacity && !ids)) return fail(PQPS_EINVAL, "NULL argument");
+    DigitListArgs g;
+    memset(&g, 0, sizeof g);
+    const int rc = digit_source(g.src, key_col, key_wide, key_base, key_bits, group_col, bin_base, n_bins, slots, prefix_dev, shift, digit_bits, false);
+    if (rc) return rc;
+    const uint32_t nb = (n_bins * slots) << digit_bits;
+    hipStream_t s = pick_stream(ctx, stream);
+    HIP_TRY(hipMemsetAsync(tables_dev, 0, (size_t)nb * sizeof(uint32_t), s));
+    if (capacity == 0 || n_rows == 0) return PQPS_OK;
+    const bool lds = nb <= kCountLdsBins;
+    g.ids = ids;
+    g.count = count_dev;
+    g.out = tables_dev;
+    g.n_rows = n_rows;
+    g.capacity = capacity;
+    g.id_base = id_base;
+    static const struct { void (*fn)(const DigitListArgs); const char *name; } fns[2][2] = {
+        {{digit_list_kernel<false, BINS_LDS>, "digit_list_kernel<DIGIT_LDS, u32>"}, {digit_list_kernel<false, BINS_GLOBAL>, "digit_list_kernel<DIGIT_GLOBAL, u32>"}},
+        {{digit_list_kernel<true, BINS_LDS>, "digit_list_kernel<DIGIT_LDS, u64>"}, {digit_list_kernel<true, BINS_GLOBAL>, "digit_list_kernel<DIGIT_GLOBAL, u64>"}},
+    };
+    const auto &list = fns[key_wide ? 1 : 0][lds ? 0 : 1];
+    snprintf(g_kernel, sizeof g_kernel, "%s", list.name);
+    hipLaunchKernelGGL(list.fn, dim3(list_grid(ctx, capacity, 4)), dim3(kBlock), lds ? nb * kCountBinBytes : 0u, s, g);
+    HIP_TRY(hipGetLastError());
+    return PQPS_OK;
 }
 
 // ---- COUNT(DISTINCT value column) (distinct_kernels.hpp) -------------------------------------------------------------

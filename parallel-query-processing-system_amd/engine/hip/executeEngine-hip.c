@@ -383,6 +383,8 @@ struct query {
     pqps_ctx *ids_ctx;                   /* a context of the device ids_dev lives on (downloads) */
     bool exchanged;                      /* issued through the ranks' exchange: the answer is the exchange slot's */
     bool per_shard;                      /* several shards: leave each shard's list on its device (grouped COUNT) */
+    bool keep_lists, listed;             /* a query that makes several shard_reduces over ONE selection (the percentiles'
+                                            passes) sets keep_lists; listed: query_lists() has run, the lists stand   */
 };
 
 static struct hipLane *query_lane(const struct query *q, int s) {
@@ -901,10 +903,14 @@ static void query_close(struct query *q) {
 
 /* The selection, every shard's list left on its own device (q->count[s] rows in query_lane(q, s)); q->total of them. */
 static int query_lists(struct query *q) {
+    if (q->listed) return 0;
     q->per_shard = true;
-    const int rc = query_issue_all(q);
-    return rc == 0 ? query_await(q) : rc;
+    int rc = query_issue_all(q);
+    if (rc == 0) rc = query_await(q);
+    if (rc == 0 && q->keep_lists) q->listed = true;
+    return rc;
 }
+
 
 /* A fused query (single-pass scan-mode WHERE): under the issue lock `call` makes the ONE shim call of every non-empty
  * shard s, on (ctx, stream) of the query's lane with q->sp[s] holding the pass's predicate and columns, and returns 0 or
@@ -1481,6 +1487,291 @@ void freeAggregateResultHIP(struct hipAggregateResult *res) {
     if (!res) return;
     free_group_keys(res->keys, res->keyText, res->numGroups);
     group_arrays_free(res->counts, res->sums, res->mins, res->maxs);
+    free(res);
+}
+
+/* ---- exact percentiles, overall or per group (include/executeEngine-hip.h) ------------------------------------------ */
+
+/* The value column as a radix select sees it: an order-preserving key image of key_bits bits (image = value - key_base in
+ * the kernels' arithmetic), and every shard's key column. */
+struct quantile_plan {
+    int v, kind;
+    bool wide;                           /* command_id: 64-bit images                                                */
+    bool no_key;                         /* a single-valued string column (no buffer): every value is code 0         */
+    bool empty;                          /* no row can match (an i32 column without rows, a selection without rows)  */
+    uint64_t key_base;
+    uint32_t key_bits;
+    pqps_column kcol[HIP_MAX_SHARDS];    /* shard s's key column (sudo_used on the fused path: its bit plane)        */
+};
+
+/* the bits an image up to `top` needs, at least 1 */
+static uint32_t quantile_bits(uint64_t top) {
+    uint32_t bits = 1;
+    while (bits < 64 && (top >> bits) != 0) bits++;
+    return bits;
+}
+
+/* The key plan of value column v of a bound query whose group plan is gp: the dictionary size, 0 / 1, the table-wide i32
+ * bounds (column_bounds: cached with the table, kept by the writers), or for command_id the minimum and maximum over the
+ * SELECTION -- one aggregate through the grouped queries' driver, which also leaves the lists of a query that has some. */
+static int quantile_plan_init(struct query *q, const struct group_plan *gp, int v, struct quantile_plan *qp) {
+    struct hipTable *t = q->t;
+    int rc = 0;
+    memset(qp, 0, sizeof *qp);
+    qp->v = v;
+    qp->kind = k_group_kind[v];
+    qp->wide = qp->kind == HIPKIND_U64;
+    qp->key_bits = 1;
+    if (qp->kind == HIPKIND_DICT) {
+        qp->no_key = t->col[v].width == 0;
+        qp->key_bits = quantile_bits(t->dict[v].count > 1 ? (uint64_t)t->dict[v].count - 1 : 0);
+    } else if (qp->kind == HIPKIND_I32) {
+        int32_t lo, hi;
+        if ((rc = column_bounds(q, v, &lo, &hi)) == 0) {
+            if (lo > hi) qp->empty = true;
+            else { qp->key_base = (uint32_t)lo; qp->key_bits = quantile_bits((uint64_t)((int64_t)hi - (int64_t)lo)); }
+        }
+    } else if (qp->kind == HIPKIND_U64) {
+        struct group_plan one;
+        uint64_t acc[4] = { 0, 0, UINT64_MAX, 0 };
+        group_plan_column(q, 0, -1, NULL, "percentiles", &one);
+        if ((rc = group_bins(q, &one, v, acc)) == 0) {
+            if (acc[0] == 0) qp->empty = true;
+            else { qp->key_base = acc[2]; qp->key_bits = quantile_bits(acc[3] - acc[2]); }
+        }
+    }
+    for (int s = 0; s < q->n_shards; s++) {
+        const struct hipTable *sh = hipTableShard(t, s);
+        qp->kcol[s] = gp->fused && v == HIPCOL_SUDO_USED && sh->sudo_bits.data ? sh->sudo_bits : sh->col[v];
+    }
+    return rc;
+}
+
+/* The words one launch may count: PQPS_DIGIT_WORDS_MAX, or what PQPS_QUANTILE_WORDS (read per query; the tests' knob) lowers
+ * it to -- never below one group's 16 slots of 11 bits. */
+static uint32_t quantile_words_cap(void) {
+    const char *env = getenv("PQPS_QUANTILE_WORDS");
+    const long long w = env ? atoll(env) : 0;
+    const long long least = (long long)HIPQUANTILE_MAX_FRACTIONS << HIPQUANTILE_DIGIT_LDS;
+    return w >= least && w < (long long)PQPS_DIGIT_WORDS_MAX ? (uint32_t)w : PQPS_DIGIT_WORDS_MAX;
+}
+
+/* One launch per shard of one pass: the tables of the group bins [bin0, bin0 + n_bins) of gp, `slots` per bin, summed over
+ * the shards into acc[n_bins * slots << d] (shard_reduce).  A shard's buffer is [prefixes: n_bins * slots u64][tables]. */
+struct digit_call {
+    uint64_t *acc; size_t words;         /* first: what digit_combine adds into                                      */
+    const struct group_plan *gp; const struct quantile_plan *qp; void **buf;
+    uint32_t bin0, n_bins, slots, shift, d;
+    bool prefixed; size_t head;
+};
+
+static void digit_combine(void *arg, const void *host) {
+    const struct digit_call *a = arg;
+    const uint32_t *h = host;
+    for (size_t k = 0; k < a->words; k++) a->acc[k] += h[k];
+}
+
+static int digit_fused_call(struct query *q, int s, pqps_ctx *ctx, void *stream, void *arg) {
+    const struct digit_call *a = arg;
+    const struct group_plan *gp = a->gp;
+    const struct quantile_plan *qp = a->qp;
+    const struct hipTable *sh = hipTableShard(q->t, s);
+    const struct shard_pred *sp = &q->sp[s];
+    const bool grouped = gp->c >= 0 && !gp->single;
+    if (pqps_filter_digit_hist(ctx, sp->cols, sp->n_cols, sh->n_rows, sp->pred, &qp->kcol[s], qp->wide, qp->key_base, qp->key_bits,
+                               grouped ? &gp->gcol[s] : NULL, gp->bin_base + a->bin0, a->n_bins, a->slots, a->prefixed ? a->buf[s] : NULL,
+                               a->shift, a->d, (uint32_t *)((char *)a->buf[s] + a->head), stream) != PQPS_OK)
+        return engine_error("percentile filter");
+    return 0;
+}
+
+static int digit_list_call(struct query *q, int s, pqps_ctx *cs, const struct hipLane *L, void *out, void *arg) {
+    const struct digit_call *a = arg;
+    const struct group_plan *gp = a->gp;
+    const struct quantile_plan *qp = a->qp;
+    const struct hipTable *sh = hipTableShard(q->t, s);
+    const bool grouped = gp->c >= 0 && !gp->single;
+    return pqps_digit_hist_list(cs, &qp->kcol[s], qp->wide, qp->key_base, qp->key_bits, grouped ? &gp->gcol[s] : NULL, gp->bin_base + a->bin0,
+                                a->n_bins, a->slots, a->prefixed ? a->buf[s] : NULL, a->shift, a->d, sh->n_rows, L->ids_dev, L->count_dev,
+                                q->count[s], (uint32_t)sh->row0, out, NULL);
+}
+
+/* The select's state: per group bin its rows, its prefix slots (ascending, distinct) and, per fraction, the slot it
+ * follows and its rank among that slot's rows. */
+struct quantile_state {
+    int n_fractions;
+    uint64_t *counts;                    /* [n_bins]                                                                 */
+    uint64_t *prefix;                    /* [n_bins][HIPQUANTILE_MAX_FRACTIONS]                                      */
+    int *n_slots;                        /* [n_bins]; 0: no rows                                                     */
+    int *slot;                           /* [n_bins][n_fractions]                                                    */
+    uint64_t *rank;                      /* [n_bins][n_fractions]                                                    */
+};
+
+static void quantile_state_free(struct quantile_state *st) {
+    free(st->counts); free(st->prefix); free(st->n_slots); free(st->slot); free(st->rank);
+}
+
+static int quantile_state_alloc(struct quantile_state *st, uint32_t n_bins, int n_fractions) {
+    memset(st, 0, sizeof *st);
+    st->n_fractions = n_fractions;
+    st->counts = calloc(n_bins, sizeof *st->counts);
+    st->prefix = calloc((size_t)n_bins * HIPQUANTILE_MAX_FRACTIONS, sizeof *st->prefix);
+    st->n_slots = calloc(n_bins, sizeof *st->n_slots);
+    st->slot = calloc((size_t)n_bins * (size_t)n_fractions, sizeof *st->slot);
+    st->rank = calloc((size_t)n_bins * (size_t)n_fractions, sizeof *st->rank);
+    return st->counts && st->prefix && st->n_slots && st->slot && st->rank ? 0 : oom();
+}
+
+/* The radix select (caller holds the table shared and the query's lane; the WHERE is bound, gp and qp are planned): pass by
+ * pass from the top digit, each pass in batches of consecutive group bins that keep a launch within the words cap.  Pass 0
+ * leaves every group's rows in st->counts; at the end st->prefix[b][st->slot[b][f]] is the image of fraction f of group b. */
+static int quantile_select(struct query *q, const struct group_plan *gp, const struct quantile_plan *qp, const unsigned *ppm,
+                           struct quantile_state *st, int *passes) {
+    const uint32_t G = gp->n_bins, cap = quantile_words_cap();
+    const int F = st->n_fractions;
+    void *buf[HIP_MAX_SHARDS];
+    uint64_t *acc = NULL, *head = NULL;
+    int rc = 0;
+    q->keep_lists = true;
+    for (uint32_t left = qp->key_bits; left > 0 && rc == 0; ) {
+        const bool first = left == qp->key_bits;
+        uint32_t slots = 1;
+        for (uint32_t b = 0; b < G && !first; b++) if ((uint32_t)st->n_slots[b] > slots) slots = (uint32_t)st->n_slots[b];
+        const uint32_t d = hipQuantileDigitBits(left, qp->key_bits, (uint64_t)G * slots), shift = left - d;
+        uint32_t per = (cap >> d) / slots;                               /* group bins per launch */
+        if (per > G) per = G;
+        const size_t words = ((size_t)per * slots) << d, head_words = first ? 0 : (size_t)per * slots;
+        acc = malloc(words * sizeof *acc);
+        head = malloc((head_words + 1) * sizeof *head);
+        if (!acc || !head) rc = oom();
+        for (uint32_t b0 = 0; b0 < G && rc == 0; b0 += per) {
+            const uint32_t nb = G - b0 < per ? G - b0 : per;
+            bool pending = first;
+            for (uint32_t b = b0; b < b0 + nb && !pending; b++) pending = st->n_slots[b] > 0;
+            if (!pending) continue;                                      /* no group of the window has rows */
+            for (size_t k = 0; k < (size_t)nb * slots && !first; k++) {
+                const uint32_t b = b0 + (uint32_t)(k / slots), j = (uint32_t)(k % slots);
+                head[k] = j < (uint32_t)st->n_slots[b] ? st->prefix[(size_t)b * HIPQUANTILE_MAX_FRACTIONS + j] : UINT64_MAX;
+            }
+            struct digit_call a = { .acc = acc, .words = ((size_t)nb * slots) << d, .gp = gp, .qp = qp, .buf = buf, .bin0 = b0, .n_bins = nb,
+                                    .slots = slots, .shift = shift, .d = d, .prefixed = !first, .head = pad16((size_t)nb * slots * (first ? 0 : 8)) };
+            const struct shard_reduce r = { .what = "percentile tables", .head = head, .head_bytes = first ? 0 : (size_t)nb * slots * sizeof *head,
+                                            .bytes = a.words * sizeof(uint32_t), .fused = digit_fused_call, .list = digit_list_call,
+                                            .combine = digit_combine };
+            memset(acc, 0, a.words * sizeof *acc);
+            rc = shard_reduce(q, gp->fused, &r, buf, &a);
+            ++*passes;
+            for (uint32_t b = b0; b < b0 + nb && rc == 0; b++) {
+                const uint64_t *tables = acc + (((size_t)(b - b0) * slots) << d);
+                uint64_t *rank = st->rank + (size_t)b * (size_t)F, *prefix = st->prefix + (size_t)b * HIPQUANTILE_MAX_FRACTIONS;
+                int *slot = st->slot + (size_t)b * (size_t)F;
+                if (first) {
+                    for (uint32_t k = 0; k < 1u << d; k++) st->counts[b] += tables[k];
+                    if (st->counts[b] == 0) continue;
+                    for (int f = 0; f < F; f++) rank[f] = hipQuantileRank(st->counts[b], ppm[f]);
+                } else if (st->n_slots[b] == 0) continue;
+                unsigned int digits[HIPQUANTILE_MAX_FRACTIONS];
+                uint64_t ranks_in[HIPQUANTILE_MAX_FRACTIONS], next[HIPQUANTILE_MAX_FRACTIONS];
+                int next_slot[HIPQUANTILE_MAX_FRACTIONS], n_next = 0;
+                if (hipQuantilePick(tables, d, first ? NULL : prefix, first ? 1 : st->n_slots[b], rank, slot, F, digits, ranks_in, next, next_slot,
+                                    &n_next) != 0) { rc = -1; break; }   /* (never: the ranks come from these very counts) */
+                for (int f = 0; f < F; f++) { rank[f] = ranks_in[f]; slot[f] = next_slot[f]; }
+                for (int j = 0; j < n_next; j++) prefix[j] = next[j];
+                st->n_slots[b] = n_next;
+            }
+        }
+        free(acc);
+        free(head);
+        acc = head = NULL;
+        left = shift;
+    }
+    return rc;
+}
+
+/* The select's answer into the result: the groups with rows in bin order, their counts, and per fraction the value. */
+static int quantile_result_fill(struct hipQuantileResult *res, const struct hipTable *t, const struct group_plan *gp,
+                                const struct quantile_plan *qp, const struct quantile_state *st, uint32_t n_bins) {
+    long long *keys = NULL;
+    const int F = res->numFractions;
+    const int rc = group_keys_fill(t, res->groupColumn, res->groupKind, gp->lo, st->counts, n_bins, &keys, &res->keyText, &res->numGroups);
+    free(keys);
+    if (rc != 0) return -1;
+    const size_t n = (size_t)res->numGroups * (size_t)F;
+    res->counts = calloc((size_t)res->numGroups + 1, sizeof *res->counts);
+    res->values = calloc(n + 1, sizeof *res->values);
+    res->valueText = qp->kind == HIPKIND_DICT ? calloc(n + 1, sizeof *res->valueText) : NULL;
+    if (!res->counts || !res->values || (qp->kind == HIPKIND_DICT && !res->valueText)) return oom();
+    size_t g = 0;
+    for (uint32_t b = 0; b < n_bins; b++) {
+        if (!st->counts[b]) continue;
+        res->counts[g] = st->counts[b];
+        res->total += (long long)st->counts[b];
+        for (int f = 0; f < F; f++) {
+            const uint64_t image = qp->no_key ? 0 : st->prefix[(size_t)b * HIPQUANTILE_MAX_FRACTIONS + (size_t)st->slot[(size_t)b * (size_t)F + (size_t)f]];
+            long long *value = &res->values[g * (size_t)F + (size_t)f];
+            if (qp->kind == HIPKIND_U64) *value = (long long)(image + qp->key_base);
+            else if (qp->kind == HIPKIND_I32) *value = (int32_t)((uint32_t)image + (uint32_t)qp->key_base);
+            else *value = (long long)image;
+            if (qp->kind != HIPKIND_DICT) continue;
+            if (image >= (uint64_t)t->dict[qp->v].count) { fprintf(stderr, "HIP engine: percentiles: code %llu outside the dictionary\n", (unsigned long long)image); return -1; }
+            if (!(res->valueText[g * (size_t)F + (size_t)f] = strdup(t->dict[qp->v].values[image]))) return oom();
+        }
+        g++;
+    }
+    return 0;
+}
+
+struct hipQuantileResult *executeQueryQuantilesHIP(struct engineS *engine, const char *valueColumn, const char *groupColumn,
+                                                   const unsigned *ppm, int numFractions, struct whereClauseS *whereClause) {
+    const double t0 = now_seconds();
+    struct hipQuantileResult *res = calloc(1, sizeof *res);
+    if (!res) { oom(); return NULL; }
+    res->valueColumn = res->valueKind = res->groupColumn = res->groupKind = -1;
+    if (!engine || !engine->record_block || !valueColumn || !ppm) { fprintf(stderr, "HIP engine: percentiles without an engine, a value column or fractions\n"); return res; }
+    if (numFractions < 1 || numFractions > HIPQUANTILE_MAX_FRACTIONS) {
+        fprintf(stderr, "HIP engine: percentiles: %d fractions, not 1 .. %d\n", numFractions, HIPQUANTILE_MAX_FRACTIONS);
+        return res;
+    }
+    for (int f = 0; f < numFractions; f++)
+        if (ppm[f] > HIPQUANTILE_PPM) { fprintf(stderr, "HIP engine: percentiles: %u parts per million is above 1 000 000\n", ppm[f]); return res; }
+    const int v = hipColumnId(valueColumn);
+    if (v < 0) { fprintf(stderr, "HIP engine: percentiles: unknown value column '%s'\n", valueColumn); return res; }
+    const int c = groupColumn ? group_column_id("percentiles", groupColumn) : -1;
+    if (groupColumn && c < 0) return res;
+    struct hipTable *t = engine->record_block;
+    if (t->xch) { fprintf(stderr, "HIP engine: percentiles are not exchanged across ranks\n"); return res; }
+    res->valueColumn = v;
+    res->valueKind = k_group_kind[v];
+    res->groupColumn = c;
+    res->groupKind = c >= 0 ? k_group_kind[c] : -1;
+    res->numFractions = numFractions;
+    struct query q;
+    if (!query_open(engine, &q)) return res;                             /* reason on stderr */
+    struct group_plan gp;
+    struct quantile_plan qp;
+    struct quantile_state st;
+    memset(&st, 0, sizeof st);
+    int rc = group_plan_init(engine, whereClause, &q, c, groupColumn, "percentiles", &gp);
+    if (rc == 0 && !gp.empty) { q.keep_lists = true; rc = quantile_plan_init(&q, &gp, v, &qp); }
+    const bool empty = rc != 0 || gp.empty || qp.empty;
+    if (rc == 0 && !empty) rc = quantile_state_alloc(&st, gp.n_bins, numFractions);
+    if (rc == 0 && !empty) rc = qp.no_key ? group_counts(&q, &gp, st.counts) : quantile_select(&q, &gp, &qp, ppm, &st, &res->passes);
+    if (rc == 0 && !empty) rc = quantile_result_fill(res, t, &gp, &qp, &st, gp.n_bins);
+    if (rc == 0) res->success = true;
+    quantile_state_free(&st);
+    query_close(&q);
+    res->queryTime = now_seconds() - t0;
+    return res;
+}
+
+void freeQuantileResultHIP(struct hipQuantileResult *res) {
+    if (!res) return;
+    const size_t n = (size_t)res->numGroups * (size_t)res->numFractions;
+    for (size_t i = 0; i < n && res->valueText; i++) free(res->valueText[i]);
+    free(res->valueText);
+    free_group_keys(NULL, res->keyText, res->numGroups);
+    free(res->counts);
+    free(res->values);
     free(res);
 }
 

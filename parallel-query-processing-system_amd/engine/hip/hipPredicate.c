@@ -1497,3 +1497,64 @@ int hipCountManyPack(const struct hipCountQuery *queries, int n, int max_queries
     *n_batches = nb;
     return 0;
 }
+
+/* ---- exact percentiles: the host half of the radix select (include/hipPredicate.h) ----------------------------------- */
+
+unsigned long long hipQuantileRank(unsigned long long n, unsigned int ppm) {
+    const unsigned long long p = ppm > HIPQUANTILE_PPM ? HIPQUANTILE_PPM : ppm;
+    const unsigned long long up = (p * n + HIPQUANTILE_PPM - 1) / HIPQUANTILE_PPM;      /* ceil(p n / 10^6): p n < 2^20 n */
+    return up > 0 ? up - 1 : 0;
+}
+
+unsigned int hipQuantileDigitBits(unsigned int bits_left, unsigned int key_bits, unsigned long long tables) {
+    if (bits_left == 0) return 0;
+    if (bits_left == key_bits && key_bits <= HIPQUANTILE_DIGIT_LDS) return key_bits;     /* a small domain: one pass */
+    const unsigned int d = tables <= HIPQUANTILE_TABLES_LDS ? HIPQUANTILE_DIGIT_LDS : HIPQUANTILE_DIGIT_WIDE;
+    return bits_left < d ? bits_left : d;
+}
+
+int hipQuantilePick(const uint64_t *tables, unsigned int digit_bits, const uint64_t *prefixes, int n_slots, const uint64_t *ranks,
+                    const int *slots, int n_entries, unsigned int *digits, uint64_t *ranks_in, uint64_t *next_prefixes,
+                    int *next_slots, int *n_next) {
+    if (!tables || !ranks || !slots || !digits || !ranks_in || !next_prefixes || !next_slots || !n_next) {
+        fprintf(stderr, "HIP engine: quantile pick: NULL argument\n");
+        return -1;
+    }
+    if (digit_bits < 1 || digit_bits > 16 || n_slots < 1 || n_slots > HIPQUANTILE_MAX_FRACTIONS || n_entries < 0 ||
+        n_entries > HIPQUANTILE_MAX_FRACTIONS) {
+        fprintf(stderr, "HIP engine: quantile pick: %u digit bits, %d slots, %d entries\n", digit_bits, n_slots, n_entries);
+        return -1;
+    }
+    const uint64_t width = 1ull << digit_bits;
+    uint64_t next[HIPQUANTILE_MAX_FRACTIONS];
+    for (int i = 0; i < n_entries; i++) {
+        if (slots[i] < 0 || slots[i] >= n_slots) { fprintf(stderr, "HIP engine: quantile pick: slot %d of %d\n", slots[i], n_slots); return -1; }
+        const uint64_t *t = tables + (uint64_t)slots[i] * width;
+        uint64_t below = 0, dg = 0;
+        while (dg < width && ranks[i] >= below + t[dg]) below += t[dg++];
+        if (dg == width) {
+            fprintf(stderr, "HIP engine: quantile pick: rank %llu in a table of %llu rows\n", (unsigned long long)ranks[i], (unsigned long long)below);
+            return -1;
+        }
+        digits[i] = (unsigned int)dg;
+        ranks_in[i] = ranks[i] - below;
+        next[i] = ((prefixes ? prefixes[slots[i]] : 0ull) << digit_bits) | dg;
+    }
+    /* the distinct next prefixes, ascending (at most 16: an insertion sort), and every entry's place among them */
+    int n = 0;
+    for (int i = 0; i < n_entries; i++) {
+        int at = 0;
+        while (at < n && next_prefixes[at] < next[i]) at++;
+        if (at < n && next_prefixes[at] == next[i]) continue;
+        for (int k = n; k > at; k--) next_prefixes[k] = next_prefixes[k - 1];
+        next_prefixes[at] = next[i];
+        n++;
+    }
+    for (int i = 0; i < n_entries; i++) {
+        int at = 0;
+        while (next_prefixes[at] != next[i]) at++;
+        next_slots[i] = at;
+    }
+    *n_next = n;
+    return 0;
+}
